@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s of the MI355X forward-pass backend on BASELINE.json's workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model mistral-7b] [--prompt 512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model mistral-7b] [--prompt 512] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path = ONE greedy decode forward (1 token, KV-cached).  The
 default workload is BASELINE.json configs[2], the configuration the metric is quoted on:
@@ -12,6 +12,16 @@ all-reduce): total work is fixed, so scaling is "strong".
 
 Timed region: inputs resident in HBM (weights, KV cache, prompt already prefilled); barrier +
 device sync on both sides; max over ranks.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, prefill + W warm-up decode steps, a fresh
+prefill, the K timed steps, the result line.  --full adds everything else, as before: the parity
+gate against the oracle (a failed gate nulls `value`), the CPU baseline, prefill timing, per-kernel
+and roofline figures (with rocprofv3 PMC passes), the host loop, the batched-decode legs, the other
+BASELINE configs and the fp32 mode, and on N ranks the all-reduce probes and the group-vs-one-GPU check.
+
+--dump-outputs DIR writes, after the timed steps, what the timed call returned to its caller: the K
+greedy token ids, as DIR/tokens.npy (float64).  Weights and prompt are seeded, so two builds given
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -236,7 +246,8 @@ def traffic_live(model_name, prompt, timeout_s=240):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(out, ctr.lower())
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "16", "--warmup", "4", "--model", model_name, "--prompt", str(prompt), "--no-cpu-baseline", "--no-secondary", "--no-traffic"]
+                   "--steps", "16", "--warmup", "4", "--model", model_name, "--prompt", str(prompt), "--full", "--no-cpu-baseline", "--no-secondary",
+                   "--no-traffic"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout_s)
             if r.returncode != 0:
                 log("traffic pass %s failed (rc %d): %s" % (ctr, r.returncode, r.stderr.decode(errors="replace")[-300:]))
@@ -299,10 +310,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default=os.environ.get("FL_BENCH_MODEL", "mistral-7b"))
     ap.add_argument("--prompt", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other single-GPU configs and the fp32-mode figure")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 PMC passes behind roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity gate, CPU baseline, prefill / per-kernel / roofline figures, host loop, "
+                         "batched decode, the other configs and the fp32 mode, N-rank probes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs (tokens.npy) under DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the other single-GPU configs and the fp32-mode figure")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) skip the in-run rocprofv3 PMC passes behind roofline.traffic")
     args = ap.parse_args()
+    full = args.full
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -438,7 +455,7 @@ def main():
     # the decode step's all-reduce ([h] fp32 after o_proj / down_proj) timed alone on this group's links, one form at a time
     # (fl_comm_probe; max over ranks): what a step's 2 L collectives cost by the form that carries them
     allreduce_us = None
-    if world > 1:
+    if world > 1 and full:
         allreduce_us = {}
         for form, name in ((0, "rccl"), (1, "oneshot_kernel"), (2, "fused_in_gemv_epilogue")):
             try:
@@ -453,14 +470,14 @@ def main():
         allreduce_us["per_step"] = 2 * cfg["num_hidden_layers"]
         log("decode all-reduce, us per call:", allreduce_us)
 
-    # ---- parity gate: no timing counts before the HIP path has matched the oracle on this box ----
-    parity = None
-    if rank == 0:
+    # ---- parity gate (--full): no timing counts before the HIP path has matched the oracle on this box ----
+    parity, parity_ok = None, True
+    if full and rank == 0:
         t0 = time.perf_counter()
         parity = parity_check(torch, fa, binding, cfg, wts, local_rank, T=min(T, 512))      # the workload's own prompt length (oracle: ~1 s)
         log("parity gate: %s (rel_l2 %.2e, max_abs %.3g, argmax_equal %s) in %.1fs"
             % ("ok" if parity["ok"] else "FAILED", parity["rel_l2"], parity["max_abs"], parity["argmax_equal"], time.perf_counter() - t0))
-    if world > 1:
+    if full and world > 1:
         # (rank 0 was busy with the oracle: the others must not already sit in a collective with a bounded wait)
         barrier()
         # the tensor-parallel group against ONE GPU running the whole model: same weights, same prompt, logits of the last position
@@ -484,10 +501,10 @@ def main():
         pk = torch.tensor([1 if (parity is None or parity["ok"]) else 0], dtype=torch.int32)
         dist.all_reduce(pk, op=dist.ReduceOp.MIN)
         parity_ok = int(pk[0]) == 1
-    else:
+    elif full:
         parity_ok = parity["ok"]
 
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    do_cpu = full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu = None
     if do_cpu:
         t0 = time.perf_counter()
@@ -505,23 +522,29 @@ def main():
     first = model.forward_argmax(cache, prompt, 0)
     if W:
         model.decode_greedy(cache, first, T, W)
-    # ---- prefill timing (reported beside the headline): the median of three calls on a reset cache ----
-    samples = []
-    for _ in range(3):
-        cache.reset()
-        barrier(); model.synchronize()
-        t0 = time.perf_counter()
-        first = model.forward_argmax(cache, prompt, 0)
-        model.synchronize(); barrier()
-        samples.append(time.perf_counter() - t0)
-    t_prefill = sorted(samples)[1]
+    t_prefill, pstats = None, None
+    if full:
+        # ---- prefill timing (reported beside the headline): the median of three calls on a reset cache ----
+        samples = []
+        for _ in range(3):
+            cache.reset()
+            barrier(); model.synchronize()
+            t0 = time.perf_counter()
+            first = model.forward_argmax(cache, prompt, 0)
+            model.synchronize(); barrier()
+            samples.append(time.perf_counter() - t0)
+        t_prefill = sorted(samples)[1]
 
-    # ---- per-kernel breakdown of the same prefill (eager, HIP-event pair per launch) ----
-    cache.reset()
-    model.profile_begin()
-    model.forward_argmax(cache, prompt, 0)
-    pstats = model.profile_end()
-    barrier()
+        # ---- per-kernel breakdown of the same prefill (eager, HIP-event pair per launch) ----
+        cache.reset()
+        model.profile_begin()
+        model.forward_argmax(cache, prompt, 0)
+        pstats = model.profile_end()
+        barrier()
+    else:
+        # the warm-up decoded on: back to the prompt, so the timed steps start where they do in a full run
+        cache.reset()
+        first = model.forward_argmax(cache, prompt, 0)
 
     # ---- timed region: exactly K decode steps ----
     barrier(); model.synchronize(); torch.cuda.synchronize()
@@ -530,9 +553,9 @@ def main():
     model.synchronize(); torch.cuda.synchronize(); barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
-        tt = torch.tensor([elapsed, t_prefill], dtype=torch.float64)
+        tt = torch.tensor([elapsed, t_prefill or 0.0], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed, t_prefill = float(tt[0]), float(tt[1])
+        elapsed, t_prefill = float(tt[0]), (float(tt[1]) if full else None)
     assert len(toks) == K
     # every rank of a tensor-parallel group must have produced the same tokens (the sums run in rank order everywhere)
     my_crc = zlib.crc32(np.asarray(toks, dtype=np.uint32).tobytes())
@@ -544,28 +567,35 @@ def main():
         if not ranks_agree:
             log("WARNING: ranks disagree on the generated tokens:", crcs)
 
+    # ---- the timed path's outputs: the K token ids the call returned ----
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), np.asarray(toks, dtype=np.float64))
+        log("outputs written to %s (tokens.npy: %d token ids)" % (args.dump_outputs, K))
+
     # ---- the reference's loop shape for comparison: one fl_forward per token, V fp32 logits copied to the host
     #      and argmax there (mod.rs:421-452): PCIe-inclusive, never the headline value ----
-    n_host = 32
-    tok = int(toks[-1])
-    barrier(); model.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n_host):
-        lg = model.forward(cache, [tok], T + K + i)
-        tok = int(np.flatnonzero(lg == lg.max())[-1])
-    model.synchronize(); barrier()
-    t_host_loop = (time.perf_counter() - t0) / n_host
+    n_host, n_prof = 32, 8
+    t_host_loop, stats = None, None
+    if full:
+        tok = int(toks[-1])
+        barrier(); model.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n_host):
+            lg = model.forward(cache, [tok], T + K + i)
+            tok = int(np.flatnonzero(lg == lg.max())[-1])
+        model.synchronize(); barrier()
+        t_host_loop = (time.perf_counter() - t0) / n_host
 
-    # ---- per-kernel HIP-event timing of the same decode steps (eager, event pair per launch) ----
-    n_prof = 8
-    model.profile_begin()
-    model.decode_greedy(cache, tok, T + K + n_host, n_prof)
-    stats = model.profile_end()
-    barrier()
+        # ---- per-kernel HIP-event timing of the same decode steps (eager, event pair per launch) ----
+        model.profile_begin()
+        model.decode_greedy(cache, tok, T + K + n_host, n_prof)
+        stats = model.profile_end()
+        barrier()
 
     # ---- batched decode (scope row N4: concurrent streams share one weight read); NOT the headline metric ----
     batch8, batch32, stream_batcher = None, None, None
-    if world == 1 and os.environ.get("FL_BENCH_BATCH", "1") == "1":
+    if full and world == 1 and os.environ.get("FL_BENCH_BATCH", "1") == "1":
         try:
             nb, kb = 8, min(K, 64)
             bc, bfirst = [], []
@@ -628,7 +658,7 @@ def main():
 
     # ---- the same 32 streams on the tensor-parallel group (round 5: fl_batch_* on the ranks of a multi-process group).  Every rank builds
     #      the same batch; the headline's numbers are complete at this point and a failure here only drops this entry ----
-    if world > 1 and os.environ.get("FL_BENCH_BATCH", "1") == "1":
+    if full and world > 1 and os.environ.get("FL_BENCH_BATCH", "1") == "1":
         ok_b, bt, bc = 1, None, []
         try:
             nb2, kb = 32, min(K, 32)
@@ -675,7 +705,7 @@ def main():
     #      and the headline workload in fp32 mode, the mode that meets north_star's literal 1e-3 / bit-exact-ids bar.
     #      The headline's numbers are complete at this point: nothing below can take them down. ----
     secondary, fp32_mode = None, None
-    if world == 1 and rank == 0 and args.model == "mistral-7b" and not args.no_secondary and os.environ.get("FL_BENCH_SECONDARY", "1") == "1":
+    if full and world == 1 and rank == 0 and args.model == "mistral-7b" and not args.no_secondary and os.environ.get("FL_BENCH_SECONDARY", "1") == "1":
         secondary = []
         for nm, t_, gen_, steps_ in (("tinyllama-1.1b", 128, 128, 128), ("qwen2-7b", 4096, 64, 64)):
             try:
@@ -701,7 +731,7 @@ def main():
 
     # every rank's own kernel times (a tensor-parallel step is as slow as its slowest rank's launches + collectives)
     per_rank = None
-    if world > 1:
+    if full and world > 1:
         mine = {"rank": rank, "kernel_us_per_step": round(sum(s_["total_ms"] for s_ in stats) * 1e3 / n_prof, 1),
                 "kernels": [{"name": s_["name"], "launches_per_step": s_["launches"] / n_prof,
                              "us_per_launch": round(s_["total_ms"] * 1e3 / s_["launches"], 2)} for s_ in stats]}
@@ -711,80 +741,83 @@ def main():
         tok_s = K / elapsed
         kv_mid = T + K // 2
         b_tok = decode_bytes_per_token(cfg, kv_mid)
-        gv = [s for s in stats if s["name"].startswith("gemv")]
-        gemv = dict(launches=sum(s["launches"] for s in gv), total_ms=sum(s["total_ms"] for s in gv),
-                    bytes=sum(s["bytes"] for s in gv)) if gv else None
-        roof = None
-        if gemv and gemv["launches"]:
-            avg_ms = gemv["total_ms"] / gemv["launches"]
-            ach = gemv["bytes"] / gemv["launches"] / (avg_ms * 1e-3) / 1e9
-            # HBM bytes per launch from the PMC passes committed with the profiles (tools/pmc_traffic.py);
-            # only comparable when the workload is the one they were collected on
-            traffic, tsrc = None, None
-            import glob
-            live = None
-            if world == 1 and not args.no_traffic and os.environ.get("FL_BENCH_TRAFFIC", "1") == "1":
-                t0 = time.perf_counter()
-                live = traffic_live(args.model, T)
-                log("live HBM traffic passes: %s (%.1fs)" % ("%.1f MB per GEMV launch" % (live["hbm_bytes_per_launch"] / 1e6) if live else "not available", time.perf_counter() - t0))
-            tfs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", "traffic_gemv.json")))      # newest round's PMC passes
-            if live:
-                traffic = round(live["hbm_bytes_per_launch"])
-                tsrc = ("measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of this bench as child processes (16 decode steps each, "
-                        "%d launches; separate passes, gfx950 x2 read correction)" % live["launches"])
-            elif tfs and args.model == "mistral-7b" and world == 1:
-                tj = json.load(open(tfs[-1]))
-                traffic = round(tj["hbm_bytes_per_launch"])
-                tsrc = "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, separate runs, gfx950 x2 read correction)" % os.path.relpath(tfs[-1], ROOT)
-            # the same figure as rocprofv3 saw it when the committed profile was collected (tools/rocprof_gemv.py)
-            rocprof = None
-            rfs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", "rocprof_gemv.json")))
-            if rfs and args.model == "mistral-7b" and world == 1:
-                rj = json.load(open(rfs[-1]))
-                rocprof = {"avg_launch_us": rj["avg_launch_us"], "achieved": rj["achieved_GBps"], "frac": rj["frac"],
-                           "source": os.path.relpath(rfs[-1], ROOT) + " (rocprofv3 --kernel-trace --stats of bench.py, collected with the committed profile)"}
-            roof = {"bound": "hbm", "kernel": "gemv_kernel<bf16> (QKV/O/gate-up/down/lm_head weight stream)",
-                    "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4),
-                    "traffic": traffic, "traffic_source": tsrc, "launches_per_step": gemv["launches"] // n_prof,
-                    "bytes_per_launch": round(gemv["bytes"] / gemv["launches"]), "avg_launch_us": round(avg_ms * 1e3, 2),
-                    "rocprof": rocprof}
-        total_prof_ms = sum(s["total_ms"] for s in stats)
         out = {
             "metric": "decode_tokens_per_sec", "value": round(tok_s, 2), "unit": "tokens/s", "n_gpus": world,
             "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "scaling": "strong", "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": full,
             "config": {"workload": "%s bf16 greedy decode, %d-token prompt, %d generated tokens, batch 1, TP=%d"
                                    % (args.model, T, K, world), "kv_len": "%d..%d" % (T, T + K),
                        "parallelism": "tp%d" % world, "collectives": collectives, "tp_fallback_level": fallback_level,
                        "rccl_ranks": int(info.rccl_ranks), "tp_fallback_log": fallback_log},
-            "allreduce_us": allreduce_us,
-            "per_rank": per_rank,
-            "roofline": roof,
-            "cpu_baseline": cpu,
             "e2e_hbm": {"bytes_per_token": b_tok, "achieved_GBps": round(tok_s * b_tok / world / 1e9, 1),
                         "frac_of_8TBps_per_gpu": round(tok_s * b_tok / world / 8e12, 4)},
-            "parity_check": parity,
             "tokens_crc32": my_crc, "ranks_agree": ranks_agree,
-            "batched_decode": batch8,
-            "batched_decode_32": batch32,
-            "stream_batcher": stream_batcher,
-            "secondary": secondary,
-            "fp32_mode_tokens_per_sec": fp32_mode["tokens_per_sec"] if fp32_mode and "tokens_per_sec" in fp32_mode else None,
-            "fp32_mode": fp32_mode,
-            "host_loop": {"tokens_per_sec": round(1.0 / t_host_loop, 2),
-                          "note": "fl_forward per token: logits (V fp32) to the host + host argmax, PCIe-inclusive"},
-            "prefill": {"tokens": T, "tokens_per_sec": round(T / t_prefill, 1), "ms": round(t_prefill * 1e3, 2), "timing": "median of 3 calls",
-                        "mfma_frac_of_2.5PF": round(prefill_flops(cfg, T) / t_prefill / world / 2.5e15, 4),
-                        "kernels": [{"name": s["name"], "launches": s["launches"], "ms": round(s["total_ms"], 3),
-                                     "TFLOPs": round(s["flops"] / s["total_ms"] / 1e9, 1) if s["total_ms"] and s["flops"] else None}
-                                    for s in pstats]},
-            "kernels": [{"name": s["name"], "launches_per_step": s["launches"] / n_prof,
-                         "us_per_step": round(s["total_ms"] * 1e3 / n_prof, 2),
-                         "us_per_launch": round(s["total_ms"] * 1e3 / s["launches"], 2),
-                         "GBps": round(s["bytes"] / s["total_ms"] / 1e6, 1) if s["total_ms"] else None,
-                         "share": round(s["total_ms"] / total_prof_ms, 4) if total_prof_ms else None} for s in stats],
             "hbm_allocated_gb": round(info.hbm_bytes_allocated / 1e9, 2),
         }
+        if full:
+            gv = [s for s in stats if s["name"].startswith("gemv")]
+            gemv = dict(launches=sum(s["launches"] for s in gv), total_ms=sum(s["total_ms"] for s in gv),
+                        bytes=sum(s["bytes"] for s in gv)) if gv else None
+            roof = None
+            if gemv and gemv["launches"]:
+                avg_ms = gemv["total_ms"] / gemv["launches"]
+                ach = gemv["bytes"] / gemv["launches"] / (avg_ms * 1e-3) / 1e9
+                # HBM bytes per launch from the PMC passes committed with the profiles (tools/pmc_traffic.py);
+                # only comparable when the workload is the one they were collected on
+                traffic, tsrc = None, None
+                import glob
+                live = None
+                if world == 1 and not args.no_traffic and os.environ.get("FL_BENCH_TRAFFIC", "1") == "1":
+                    t0 = time.perf_counter()
+                    live = traffic_live(args.model, T)
+                    log("live HBM traffic passes: %s (%.1fs)" % ("%.1f MB per GEMV launch" % (live["hbm_bytes_per_launch"] / 1e6) if live else "not available", time.perf_counter() - t0))
+                tfs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", "traffic_gemv.json")))      # newest round's PMC passes
+                if live:
+                    traffic = round(live["hbm_bytes_per_launch"])
+                    tsrc = ("measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of this bench as child processes (16 decode steps each, "
+                            "%d launches; separate passes, gfx950 x2 read correction)" % live["launches"])
+                elif tfs and args.model == "mistral-7b" and world == 1:
+                    tj = json.load(open(tfs[-1]))
+                    traffic = round(tj["hbm_bytes_per_launch"])
+                    tsrc = "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, separate runs, gfx950 x2 read correction)" % os.path.relpath(tfs[-1], ROOT)
+                # the same figure as rocprofv3 saw it when the committed profile was collected (tools/rocprof_gemv.py)
+                rocprof = None
+                rfs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", "rocprof_gemv.json")))
+                if rfs and args.model == "mistral-7b" and world == 1:
+                    rj = json.load(open(rfs[-1]))
+                    rocprof = {"avg_launch_us": rj["avg_launch_us"], "achieved": rj["achieved_GBps"], "frac": rj["frac"],
+                               "source": os.path.relpath(rfs[-1], ROOT) + " (rocprofv3 --kernel-trace --stats of bench.py, collected with the committed profile)"}
+                roof = {"bound": "hbm", "kernel": "gemv_kernel<bf16> (QKV/O/gate-up/down/lm_head weight stream)",
+                        "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4),
+                        "traffic": traffic, "traffic_source": tsrc, "launches_per_step": gemv["launches"] // n_prof,
+                        "bytes_per_launch": round(gemv["bytes"] / gemv["launches"]), "avg_launch_us": round(avg_ms * 1e3, 2),
+                        "rocprof": rocprof}
+            total_prof_ms = sum(s["total_ms"] for s in stats)
+            out.update({
+                "allreduce_us": allreduce_us,
+                "per_rank": per_rank,
+                "roofline": roof,
+                "cpu_baseline": cpu,
+                "parity_check": parity,
+                "batched_decode": batch8,
+                "batched_decode_32": batch32,
+                "stream_batcher": stream_batcher,
+                "secondary": secondary,
+                "fp32_mode_tokens_per_sec": fp32_mode["tokens_per_sec"] if fp32_mode and "tokens_per_sec" in fp32_mode else None,
+                "fp32_mode": fp32_mode,
+                "host_loop": {"tokens_per_sec": round(1.0 / t_host_loop, 2),
+                              "note": "fl_forward per token: logits (V fp32) to the host + host argmax, PCIe-inclusive"},
+                "prefill": {"tokens": T, "tokens_per_sec": round(T / t_prefill, 1), "ms": round(t_prefill * 1e3, 2), "timing": "median of 3 calls",
+                            "mfma_frac_of_2.5PF": round(prefill_flops(cfg, T) / t_prefill / world / 2.5e15, 4),
+                            "kernels": [{"name": s["name"], "launches": s["launches"], "ms": round(s["total_ms"], 3),
+                                         "TFLOPs": round(s["flops"] / s["total_ms"] / 1e9, 1) if s["total_ms"] and s["flops"] else None}
+                                        for s in pstats]},
+                "kernels": [{"name": s["name"], "launches_per_step": s["launches"] / n_prof,
+                             "us_per_step": round(s["total_ms"] * 1e3 / n_prof, 2),
+                             "us_per_launch": round(s["total_ms"] * 1e3 / s["launches"], 2),
+                             "GBps": round(s["bytes"] / s["total_ms"] / 1e6, 1) if s["total_ms"] else None,
+                             "share": round(s["total_ms"] / total_prof_ms, 4) if total_prof_ms else None} for s in stats],
+            })
         if not (parity_ok and ranks_agree):
             # a fast kernel whose results differ from the reference's is not done: no number is reported
             out["value"] = None

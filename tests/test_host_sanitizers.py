@@ -30,7 +30,8 @@ def driver(tmp_path_factory):
 
 def run(driver, paths):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([driver] + [str(p) for p in paths], capture_output=True, text=True, env=env, timeout=300)
+    # (errors="replace": a rejection message may echo bytes of a mutated header that are not UTF-8)
+    out = subprocess.run([driver] + [str(p) for p in paths], capture_output=True, text=True, errors="replace", env=env, timeout=300)
     assert out.returncode == 0 and "fuzz driver done" in out.stdout, "sanitizer report or crash:\n" + out.stdout[-2000:] + out.stderr[-6000:]
     verdicts = {}
     for ln in out.stdout.splitlines():

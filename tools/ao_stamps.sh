@@ -5,4 +5,4 @@
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$PWD}
 [ -n "$2" ] && export FL_AO_WAVES=$2
-FL_FUSE_OPROJ=1 FL_GRAPH=0 FL_AO_STAMPS=1 FL_BENCH_BATCH=0 timeout -k 10 300 python3 bench.py --steps ${1:-256} --warmup 2 --no-cpu-baseline 2>&1 | grep -a -A9 "^attn_oproj" | tail -10
+FL_FUSE_OPROJ=1 FL_GRAPH=0 FL_AO_STAMPS=1 FL_BENCH_BATCH=0 timeout -k 10 300 python3 bench.py --full --steps ${1:-256} --warmup 2 --no-cpu-baseline 2>&1 | grep -a -A9 "^attn_oproj" | tail -10

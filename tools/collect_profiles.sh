@@ -6,13 +6,13 @@ O=$R/gpurun_out/final
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout -k 10 400 python3 bench.py > $O/bench_mistral7b.json 2> $O/bench_mistral7b.err || exit 1
-timeout -k 10 300 python3 bench.py --model tinyllama-1.1b --prompt 128 --steps 128 > $O/bench_tinyllama.json 2> $O/bench_tinyllama.err || exit 1
-timeout -k 10 400 python3 bench.py --model qwen2-7b --prompt 4096 --steps 64 --no-cpu-baseline > $O/bench_qwen2_7b_4k.json 2> $O/bench_qwen2.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/bench_mistral7b.json 2> $O/bench_mistral7b.err || exit 1
+timeout -k 10 300 python3 bench.py --full --model tinyllama-1.1b --prompt 128 --steps 128 > $O/bench_tinyllama.json 2> $O/bench_tinyllama.err || exit 1
+timeout -k 10 400 python3 bench.py --full --model qwen2-7b --prompt 4096 --steps 64 --no-cpu-baseline > $O/bench_qwen2_7b_4k.json 2> $O/bench_qwen2.err || exit 1
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --steps 64 --no-cpu-baseline > $O/prof_stats_bench.json 2> $O/prof_stats.err || exit 1
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_fetch.err || exit 1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_write.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --full --steps 64 --no-cpu-baseline > $O/prof_stats_bench.json 2> $O/prof_stats.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --full --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_fetch.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --full --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_write.err || exit 1
 cd $R
 # next-row components and the multi-rank rehearsal (all ranks on this one GPU: protocol check, not a scaling figure)
 timeout -k 10 300 python3 tools/batch_bench.py --profile --batches 1,2,3,4,6,8 > $O/batch_decode_mistral7b.txt 2> $O/batch.err || exit 1
@@ -23,7 +23,7 @@ timeout -k 10 200 python3 tools/gemm_probe.py > $O/gemm_probe.txt 2> $O/gemm_pro
 (timeout -k 10 300 python3 tools/prefill_ragged.py mistral-7b; timeout -k 10 300 python3 tools/prefill_ragged.py qwen2-7b; timeout -k 10 200 python3 tools/prefill_ragged.py tinyllama-1.1b 256 384 512 640 768 1024 1100 1536 2048) 2> $O/prefill_ragged.err | grep 'T=' > $O/prefill_ragged.txt || exit 1
 # the way the driver invokes the N-GPU bench: no launcher (bench.py starts its ranks itself)
 for n in 2 4; do
-  FL_BENCH_SAME_DEVICE=1 FL_BENCH_BATCH=0 timeout -k 10 400 python3 bench.py --gpus $n --steps 64 --warmup 8 --no-cpu-baseline > $O/bench_tp${n}_same_device.json 2> $O/bench_tp${n}.err || exit 1
+  FL_BENCH_SAME_DEVICE=1 FL_BENCH_BATCH=0 timeout -k 10 400 python3 bench.py --full --gpus $n --steps 64 --warmup 8 --no-cpu-baseline > $O/bench_tp${n}_same_device.json 2> $O/bench_tp${n}.err || exit 1
 done
 timeout -k 10 300 python3 tools/skinny_probe.py 1,8,128 > $O/projection_probe_cold.txt 2> $O/skinny.err || exit 1
 timeout -k 10 500 python3 tools/cpu_baseline_full.py > $O/cpu_baseline_full_depth.txt 2> $O/cpu_full.err || exit 1

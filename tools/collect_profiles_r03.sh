@@ -8,18 +8,18 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 if [ "$1" != "2" ]; then
-timeout -k 10 400 python3 bench.py > $O/bench_mistral7b_decode.json 2> $O/bench_mistral7b.err || exit 1
-timeout -k 10 300 python3 bench.py --model tinyllama-1.1b --prompt 128 --steps 128 > $O/bench_tinyllama_decode.json 2> $O/bench_tinyllama.err || exit 1
-timeout -k 10 400 python3 bench.py --model qwen2-7b --prompt 4096 --steps 64 --no-cpu-baseline > $O/bench_qwen2_7b_4k.json 2> $O/bench_qwen2.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/bench_mistral7b_decode.json 2> $O/bench_mistral7b.err || exit 1
+timeout -k 10 300 python3 bench.py --full --model tinyllama-1.1b --prompt 128 --steps 128 > $O/bench_tinyllama_decode.json 2> $O/bench_tinyllama.err || exit 1
+timeout -k 10 400 python3 bench.py --full --model qwen2-7b --prompt 4096 --steps 64 --no-cpu-baseline > $O/bench_qwen2_7b_4k.json 2> $O/bench_qwen2.err || exit 1
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --steps 64 --no-cpu-baseline > $O/prof_stats_bench.json 2> $O/prof_stats.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --full --steps 64 --no-cpu-baseline > $O/prof_stats_bench.json 2> $O/prof_stats.err || exit 1
 cd $R
 python3 tools/rocprof_gemv.py $(find $O/prof_stats -name '*kernel_stats.csv' | head -1) $O/rocprof_gemv.json > /dev/null || exit 1
 cp $(find $O/prof_stats -name '*kernel_stats.csv' | head -1) $O/rocprofv3_kernel_stats_mistral7b.csv
 else
 cd /tmp
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_fetch.err || exit 1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_write.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --full --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_fetch.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --full --steps 16 --no-cpu-baseline > /dev/null 2> $O/pmc_write.err || exit 1
 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- python3 $R/tools/prefill_profile.py mistral-7b 512 > /dev/null 2> $O/pmc_mfma.err || exit 1
 cd $R
 python3 tools/pmc_mfma.py $O/pmc_mfma $O/pmc_mfma_mistral_t512.json > /dev/null

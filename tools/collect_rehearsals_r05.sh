@@ -10,8 +10,8 @@ mkdir -p $O
 cd $R
 timeout -k 10 500 python3 tools/tp_rehearsal.py --ranks 8 --procs 4 --model mistral-7b --prompt 512 --steps 64 --out $O/rehearsal_tp8_mistral7b.json > $O/rehearsal_tp8.log 2>&1 || { echo "tp8 rehearsal failed"; tail -5 $O/rehearsal_tp8.log; exit 1; }
 timeout -k 10 500 python3 tools/tp_rehearsal.py --ranks 8 --procs 4 --model mistral-7b --prompt 512 --steps 64 --fused --out $O/rehearsal_tp8_mistral7b_fused.json > $O/rehearsal_tp8_fused.log 2>&1 || { echo "tp8 fused rehearsal failed"; tail -5 $O/rehearsal_tp8_fused.log; exit 1; }
-FL_BENCH_SAME_DEVICE=1 timeout -k 10 500 python3 bench.py --gpus 4 --steps 32 --warmup 4 --no-cpu-baseline > $O/bench_tp4_mistral_same_device.json 2> $O/bench_tp4_mistral.err || { echo "bench tp4 mistral failed"; tail -5 $O/bench_tp4_mistral.err; exit 1; }
-FL_BENCH_SAME_DEVICE=1 timeout -k 10 500 python3 bench.py --gpus 4 --model qwen2-7b --prompt 4096 --steps 32 --warmup 4 --no-cpu-baseline > $O/bench_tp4_qwen2_4k_same_device.json 2> $O/bench_tp4_qwen2.err || { echo "bench tp4 qwen2 failed"; tail -5 $O/bench_tp4_qwen2.err; exit 1; }
+FL_BENCH_SAME_DEVICE=1 timeout -k 10 500 python3 bench.py --full --gpus 4 --steps 32 --warmup 4 --no-cpu-baseline > $O/bench_tp4_mistral_same_device.json 2> $O/bench_tp4_mistral.err || { echo "bench tp4 mistral failed"; tail -5 $O/bench_tp4_mistral.err; exit 1; }
+FL_BENCH_SAME_DEVICE=1 timeout -k 10 500 python3 bench.py --full --gpus 4 --model qwen2-7b --prompt 4096 --steps 32 --warmup 4 --no-cpu-baseline > $O/bench_tp4_qwen2_4k_same_device.json 2> $O/bench_tp4_qwen2.err || { echo "bench tp4 qwen2 failed"; tail -5 $O/bench_tp4_qwen2.err; exit 1; }
 python3 - <<PY
 import json
 for f in ("rehearsal_tp8_mistral7b.json", "rehearsal_tp8_mistral7b_fused.json", "bench_tp4_mistral_same_device.json", "bench_tp4_qwen2_4k_same_device.json"):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MFMA utilisation of the prefill kernels from a rocprofv3 PMC pass.
 
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d DIR -- python3 bench.py ...
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d DIR -- python3 bench.py --full ...
     python tools/pmc_mfma.py DIR out.json
 
 rocprofv3 reports each counter summed over the 8 XCDs.  MfmaUtil (ROCm's derived metric) =

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The roofline figure of the decode weight-streaming kernel as rocprofv3 sees it.
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_stats -- python3 bench.py --steps 64 --no-cpu-baseline
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT/prof_stats -- python3 bench.py --full --steps 64 --no-cpu-baseline
     python tools/rocprof_gemv.py <kernel_stats.csv> profiles/rNN/rocprof_gemv.json [model]
 
 Sums every `fl::gemv_kernel<...>` instantiation of the stats file (calls, total duration), and prices the average launch with
