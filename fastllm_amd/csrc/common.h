@@ -113,7 +113,7 @@ enum TuneKey {
     TK_H4_TAIL,   // a peeled GEMM's tail columns on the 128 x 256 kernel instead of stream-K + fix-up: 0 never, 1 with 2-4 in-launch slices, 2 (default) also unsliced when the tail alone fills the chip
     TK_RS_LAZY,   // 1/rms behind a residual epilogue: taken from the partial sums by the consuming projection (0: rms_finalize launch)
     TK_BATCH_UNFUSED_MIN,   // first batch size on the prefill-shaped step (-1: 3 with the ring kernel, else 7)
-    TK_DEBUG_RS_PARTS,   // tests: gemm_takes_rs_parts() answers yes for every bf16 prompt shape, so that kernels which cannot take partial sums meet them (rs_parts_to_vector)
+    TK_DEBUG_RS_PARTS,   // tests: the planner (plan_linear, plan_qkv_rope) says reads_rs_parts for every bf16 prompt shape, so that kernels which cannot take partial sums meet them (rs_parts_to_vector)
     TK_DEBUG_TP_LOOPBACK,   // tools (EXPERIMENTAL build only): an FL_TP_MULTI_PROCESS model without unique_id connects every inbox entry to ITSELF and plays all ranks' pushes (one rank's step, timed with its exchange in place; results meaningless)
     TK_DEBUG_POISON,   // tests: every device allocation of the model / cache / batch objects is filled with this byte before use (255: bf16 / fp32 NaN patterns; 63: finite 0.75s), so that a read of bytes nobody wrote shows at once instead of depending on what the allocator handed back
     TK_GEMM_SKF,   // short prompts / decode batches (2-128 rows) on the kernel whose K slices meet inside the launch (k_gemm_skf.hip): 0 off; 1 (default) a tensor-parallel rank's complete outputs up to 64 rows; 2 (EXPERIMENTAL build only; the default build treats it as 1) also the five-launch layer (residual + norm and RoPE + KV-append epilogues: measured SLOWER than slabs + rmsnorm_add / rope_kv launches, profiles/r05/README.md); 3 also every plain launch_linear shape (tests)

@@ -538,7 +538,7 @@ bool gemm_h4_supported(int64_t T, int64_t N, int64_t K, int ksplit) {
 // Which shapes run here, and in how many K slices (0: not here).  TK_GEMM_H4 = 2 / TK_H4_SPLIT pin the choice (tests, probes).
 int gemm_h4_plan(int64_t T, int64_t N, int64_t K, int epi) {
     const int mode = tune(TK_GEMM_H4);
-    if (mode <= 0 || T <= 16) return 0;           // (T <= 16: decode batches, whose steps are captured graphs: no host-side launch state)
+    if (mode <= 0 || T <= 16) return 0;           // (T <= 16: decode steps; a decode batch's launches are planned as captured, kernels.h)
     const int forced = tune(TK_H4_SPLIT);
     const int64_t tiles = ((T + H4_BM - 1) / H4_BM) * ((N + H4_BN - 1) / H4_BN), nk = K / P_BK;
     int ks = forced > 0 ? forced : 1;

@@ -265,7 +265,6 @@ bool gemm_mfma_supported(int dtype, int64_t T, int64_t N, int64_t K) {
 // Mistral-7B's gate/up on the 128x128 kernel in two rounds (T = 257: 134 us against 83 at T = 256 and ~106 on the 256x256
 // kernel), Qwen2-7B's at T = 255 likewise (151 us against 89 at 256).  The model reproduces the measured launches within
 // ~10 % (T = 129 gate/up 128x128 86 / 82 measured; T = 256 256x128 82 / 83; Qwen2 T = 255 128x128 151 / 151, 256x256 93 / 89).
-enum { GK_128 = 0, GK_256 = 1, GK_8P = 2 };
 static const double kNoKernel = 1e30;
 // (the write is this launch's ordinary epilogue, spread over ks times the workgroups; what is extra is the summing launch's read:
 // rmsnorm_add with eight 8.4 MB slabs 13.3 us against 5-6 with one)
@@ -298,38 +297,41 @@ static double cost_128(int64_t T, int64_t N, int64_t K, int ks) {
     const double last = (double)(tiles - (rounds - 1) * 512) / 512.0, steps = (double)(K / BK) / ks;
     return (double)(rounds - 1) * (steps * 1.28 + 4.0) + (steps * (0.95 + 0.33 * last) + 4.0) + cost_slabs(T, N, ks);
 }
-static int pick_kernel(int64_t T, int64_t N, int64_t K, int ks, double *cost_out = nullptr) {
+int gemm_pick_kernel(int64_t T, int64_t N, int64_t K, int ks, double *cost_out) {
     const double c8 = cost_8p(T, N, K, ks), c2 = cost_256(T, N, K, ks), c1 = cost_128(T, N, K, ks);
-    int k = GK_128; double c = c1;
-    if (c2 < c) { k = GK_256; c = c2; }
-    if (c8 < c) { k = GK_8P; c = c8; }
+    int k = LK_128; double c = c1;
+    if (c2 < c) { k = LK_256; c = c2; }
+    if (c8 < c) { k = LK_8P; c = c8; }
     if (cost_out) *cost_out = c;
     return k;
 }
+// ... under FL_GEMM_8P (0 off, 1 where the model above prefers it, 2 always); allow8p = false keeps the 256x256 kernel out (the tail of
+// a peeled matrix)
+int gemm_tile_kernel(int64_t T, int64_t N, int64_t K, int epi, bool bias, int ksplit, bool allow8p) {
+    const int use8p = !allow8p ? 0 : tune(TK_GEMM_8P);
+    const bool splittable = ksplit == 1 || (!bias && epi == EPI_F32);
+    int kern = splittable ? gemm_pick_kernel(T, N, K, ksplit) : LK_128;
+    if (!use8p && kern == LK_8P) kern = cost_256(T, N, K, ksplit) < cost_128(T, N, K, ksplit) ? LK_256 : LK_128;
+    if (use8p >= 2 && K % 64 == 0 && (K / 64) / ksplit >= 2 && splittable) kern = LK_8P;
+    return kern;
+}
 
 // how many K splits the launcher will use for this shape when the caller allows up to max_split slabs
-static bool gemm_streamk_whole(int64_t T, int64_t N, int64_t K, int epi);
-static bool peel_plan(int64_t T, int64_t N, int64_t K, int64_t *n_main_out);
 int gemm_mfma_ksplit(int64_t T, int64_t N, int64_t K, int epi, int max_split) {
-    if (gemm_streamk_whole(T, N, K, epi)) return 1;                 // one launch, partials meet inside it
+    if (gemm_streamk_whole(T, N, K)) return 1;                      // one launch, partials meet inside it
     {   // whole rounds + a stream-K tail beat K slices of a grid that large (Mistral-7B o_proj at T = 4100: 272 tiles)
         int64_t n_main = 0;
-        if (peel_plan(T, N, K, &n_main)) return 1;
+        if (gemm_peel_plan(T, N, K, &n_main)) return 1;
     }
     int best = 1;
     double best_us = kNoKernel;
     for (int ks = 1; ks <= (epi == EPI_F32 ? std::max(1, max_split) : 1); ks++) {
         double c;
-        (void)pick_kernel(T, N, K, ks, &c);
+        (void)gemm_pick_kernel(T, N, K, ks, &c);
         if (c < best_us) { best = ks; best_us = c; }               // (ties: fewer slices)
     }
     return best;
 }
-
-// One launch over the column range this call was given (all of N, or a piece of a peeled matrix): ldc = the row stride
-// of the full output; allow8p = false keeps the 256x256 kernel out (the tail of a peeled matrix).
-static int launch_gemm_mfma_impl(Launcher &L, const void *W, const void *x, const float *bias, void *y,
-                                 int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit, int64_t ldc, bool allow8p);
 
 // A long prompt's grid of 256x256 tiles rarely fills whole rounds of the chip: Qwen2-7B at T = 4096 has 288 QKV tiles
 // (1.125 rounds: the kernel was rejected and the projection ran on 128x128 tiles at 0.65 PFLOP/s), 2368 gate/up tiles
@@ -338,16 +340,13 @@ static int launch_gemm_mfma_impl(Launcher &L, const void *W, const void *x, cons
 // that writes its own column range of the same output (ldc) -- in stream-K form (k_gemm_8p.hip: one workgroup per CU,
 // the (tile, K step) line cut into equal pieces), or, with FL_GEMM_STREAMK=0, on the smaller tiles when the remainder
 // is at most a quarter round.  A grid of less than one round runs stream-K whole when that saves more than it costs.
-static int streamk_on() {
-    return tune(TK_GEMM_STREAMK);
-}
+//
 // Whole-matrix stream-K (FL_GEMM_STREAMK=2: grids of 96..255 tiles; =3: every shape the kernel takes -- tests).  Off by
 // default: measured on Qwen2-7B's down_proj at T = 4096 (224 tiles, an eighth of the chip idle) it LOST 440 -> 535 us --
 // pieces that start inside a tile take the workgroups that share a W or X panel out of lock step (their L2 hits become
 // MALL/HBM reads), and every split tile moves its fp32 accumulators through memory twice (profiles/r02/README.md).
-static bool gemm_streamk_whole(int64_t T, int64_t N, int64_t K, int epi) {
-    const int sk = streamk_on();
-    (void)epi;
+bool gemm_streamk_whole(int64_t T, int64_t N, int64_t K) {
+    const int sk = tune(TK_GEMM_STREAMK);
     if (sk < 2 || tune(TK_GEMM_8P) != 1 || T < 256 || K % 64 || K / 64 < 8) return false;
     if (sk >= 3) return true;
     const int64_t t8 = ((T + 255) / 256) * ((N + 255) / 256);
@@ -355,7 +354,7 @@ static bool gemm_streamk_whole(int64_t T, int64_t N, int64_t K, int epi) {
 }
 
 // column peeling of a ragged 256x256 grid: whole rounds first (n_main columns), the rest as a stream-K (or 128x128) tail
-static bool peel_plan(int64_t T, int64_t N, int64_t K, int64_t *n_main_out) {
+bool gemm_peel_plan(int64_t T, int64_t N, int64_t K, int64_t *n_main_out) {
     const int peel = tune(TK_GEMM_PEEL);
     const int use8p = tune(TK_GEMM_8P);
     if (!(peel && use8p == 1 && T >= 256 && K % 64 == 0 && (K / 64) >= 16)) return false;
@@ -363,154 +362,46 @@ static bool peel_plan(int64_t T, int64_t N, int64_t K, int64_t *n_main_out) {
     const int64_t full = t8 / 256;
     const int64_t n_main_tiles = full * 256 / tm;                 // whole column tiles inside the full rounds
     const int64_t tail_tiles = t8 - tm * n_main_tiles;
-    if (!(full >= 1 && tail_tiles > 0 && tail_tiles <= (streamk_on() ? 128 : 64) && n_main_tiles >= 1 && n_main_tiles < tn && tm * n_main_tiles >= 224))
+    if (!(full >= 1 && tail_tiles > 0 && tail_tiles <= (tune(TK_GEMM_STREAMK) ? 128 : 64) && n_main_tiles >= 1 && n_main_tiles < tn && tm * n_main_tiles >= 224))
         return false;
     *n_main_out = n_main_tiles * 256;                              // (256 | 32: gate/up pairs stay whole)
     return true;
 }
 
-int launch_gemm_mfma(Launcher &L, const void *W, const void *x, const float *bias, void *y,
-                     int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit) {
-    const int sk = streamk_on();
-    if (ksplit == 1 && gemm_streamk_whole(T, N, K, epi))
-        return launch_gemm_8p(L, W, x, bias, y, T, N, K, epi, row_scale, 1, N, true);
-    int64_t n_main = 0;
-    if (ksplit == 1 && peel_plan(T, N, K, &n_main)) {
-        const int64_t n_tail = N - n_main;
-        const size_t es_out = epi == EPI_GATEUP ? 2 : 4;
-        const int64_t col_main = epi == EPI_GATEUP ? n_main / 2 : n_main;
-        FL_TRY(launch_gemm_mfma_impl(L, W, x, bias, y, T, n_main, K, epi, row_scale, 1, N, true));
-        const bf16_t *Wt = (const bf16_t *)W + (size_t)n_main * K;
-        const float *bt = bias ? bias + n_main : nullptr;
-        void *yt = (char *)y + (size_t)col_main * es_out;
-        if (const int ks = gemm_h4_tail_slices(T, n_tail, K)) return launch_gemm_h4(L, Wt, x, bt, yt, T, n_tail, K, epi, row_scale, ks, N);
-        if (sk) return launch_gemm_8p(L, Wt, x, bt, yt, T, n_tail, K, epi, row_scale, 1, N, true);
-        return launch_gemm_mfma_impl(L, Wt, x, bt, yt, T, n_tail, K, epi, row_scale, 1, N, false);
-    }
-    return launch_gemm_mfma_impl(L, W, x, bias, y, T, N, K, epi, row_scale, ksplit, N, true);
-}
-
-// ---- a long prompt's QKV projection with the RoPE / bias / KV-append epilogue (EPI_QKV_ROPE) on the four-wave kernel: where launch_linear
-// would run it as ONE plain grid of 256 x 256 tiles, or as whole rounds + tail columns on the 128 x 256 kernel (1, 2 or 4 in-launch
-// slices).  K slabs and stream-K pieces keep the fp32 output and the rope_kv_append launch (which sums the slabs anyway).
-static bool qkv_rope_long_parts(int64_t T, int64_t N, int64_t K, int max_split, int64_t *n_main, int *tail_ks) {
-    *n_main = N; *tail_ks = 0;
-    if (!tune(TK_GEMM_ROPE_4W) || T < 768 || tune(TK_FORCE_GENERIC_GEMM) || tune(TK_GEMM_8P) != 1 || !gemm_mfma_supported(FL_DTYPE_BF16, T, N, K)) return false;
-    if (gemm_streamk_whole(T, N, K, EPI_F32)) return false;
-    int64_t nm = 0;
-    if (peel_plan(T, N, K, &nm)) {
-        const int ks = gemm_h4_tail_slices(T, N - nm, K);
-        if (!ks || ks == 3 || nm % 128 || (N - nm) % 128) return false;
-        *n_main = nm; *tail_ks = ks;
-    } else if (gemm_mfma_ksplit(T, N, K, EPI_F32, max_split) != 1 || pick_kernel(T, N, K, 1) != GK_8P) {
-        return false;
-    }
-    return gemm_4w_rope_supported(T, *n_main, K) && gemm_4w_rule(T, *n_main, K, K / 64, false);
-}
-bool gemm_qkv_rope_long_plan(int64_t T, int64_t N, int64_t K, int max_split) {
-    int64_t nm; int ks;
-    return qkv_rope_long_parts(T, N, K, max_split, &nm, &ks);
-}
-int launch_gemm_qkv_rope_long(Launcher &L, const void *W, const void *x, const float *bias, int64_t T, int64_t N, int64_t K, const float *row_scale,
-                              const RopeEpi &rope, int max_split) {
-    int64_t nm; int ks;
-    if (!qkv_rope_long_parts(T, N, K, max_split, &nm, &ks)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gemm_qkv_rope_long: not planned for this shape");
-    FL_TRY(launch_gemm_4w_rope(L, W, x, bias, T, nm, K, row_scale, rope));
-    if (nm == N) return FL_OK;
-    RopeEpi rt = rope;
-    rt.col_base = (int)nm;
-    return launch_gemm_h4(L, (const bf16_t *)W + (size_t)nm * K, x, bias ? bias + nm : nullptr, nullptr, T, N - nm, K, EPI_QKV_ROPE, row_scale, ks, N - nm, nullptr, &rt);
-}
-
-// Would the kernel launch_linear picks for this projection take its row scales from a residual epilogue's partial sums (Launcher::rsp)?
-// Mirrors launch_linear / launch_gemm_mfma: the 128 x 256 kernel, or a plain (no stream-K, no peeled tail) launch of the 256 x 256 ones.
-bool gemm_takes_rs_parts(int dtype, int64_t T, int64_t N, int64_t K, int epi, int max_split) {
-    if (dtype != FL_DTYPE_BF16 || T <= 1 || tune(TK_FORCE_GENERIC_GEMM)) return false;
-    if (tune(TK_DEBUG_RS_PARTS)) return true;                        // (tests: a plan that is wrong on purpose)
-    if (tune(TK_GEMM_SKF) >= 2 && gemm_skf_plan(T, N, K, epi) > 0 && (epi == EPI_GATEUP || tune(TK_GEMM_SKF) >= 3)) return true;   // short prompts: k_gemm_skf.hip sums the partials itself
-    if (gemm_h4_plan(T, N, K, epi) > 0 || gemm_w14_plan(T, N, K, epi)) return true;
-    if (tune(TK_GEMM_SKINNY) && gemm_skinny_supported(T, N, K)) return false;
-    if (!gemm_mfma_supported(dtype, T, N, K)) return false;
-    const int ks = epi == EPI_F32 ? gemm_mfma_ksplit(T, N, K, epi, max_split) : 1;
-    if (ks == 1 && gemm_streamk_whole(T, N, K, epi)) return false;
-    int64_t n_main = 0;
-    if (ks == 1 && peel_plan(T, N, K, &n_main)) return false;
-    return tune(TK_GEMM_8P) >= 1 && (tune(TK_GEMM_8P) >= 2 ? (K % 64 == 0 && (K / 64) / ks >= 2) : pick_kernel(T, N, K, ks) == GK_8P);
-}
-
-// ---- residual epilogue (EPI_RESID, kernels.h): only where the 256x256 kernel takes the whole K in one launch (or a peeled
-// pair of launches): long prompts.  FL_GEMM_RESID=0 keeps the rmsnorm_add launches.
+// ---- residual epilogue (EPI_RESID, kernels.h) on the 256x256 kernel, whole K: against K slices + the rmsnorm_add launch that sums
+// them (reads ks slabs and h, writes h and xn) the residual epilogue reads h and writes xn itself and leaves a 4 us finalize.  The
+// model is good to ~10 %, the epilogue has won every measured tie (Mistral-7B down_proj at T = 3000: 314 + 4 us against 306 + 47 in
+// four slices): it gets 15 %.
 int gemm_resid_partials(int64_t N) { return (int)((N + 255) / 256) * 4; }
-bool gemm_resid_supported(int dtype, int64_t T, int64_t N, int64_t K, int max_split) {
-    if (tune(TK_GEMM_RESID) == 0) return false;
-    if (dtype == FL_DTYPE_BF16 && tune(TK_GEMM_SKF) >= 2 && gemm_skf_plan(T, N, K, EPI_RESID) > 0) return true;   // short prompts: k_gemm_skf.hip (opt-in)
-    if (dtype == FL_DTYPE_BF16 && N % 16 == 0 && gemm_h4_plan(T, N, K, EPI_RESID) > 0) return true;   // mid-size prompts: k_gemm_h4.hip
-    if (dtype != FL_DTYPE_BF16 || tune(TK_GEMM_8P) != 1 || T < 256 || K % 64 || K / 64 < 2 || N % 16) return false;
-    if (gemm_streamk_whole(T, N, K, EPI_F32)) return false;
-    int64_t n_main = 0;
-    if (peel_plan(T, N, K, &n_main)) return streamk_on() != 0;     // main launch + stream-K tail, both with the residual epilogue
-    if (pick_kernel(T, N, K, 1) != GK_8P) return false;
-    // against K slices + the rmsnorm_add launch that sums them (reads ks slabs and h, writes h and xn): the residual epilogue
-    // reads h and writes xn itself and leaves a 4 us finalize.  The model is good to ~10 %, the epilogue has won every
-    // measured tie (Mistral-7B down_proj at T = 3000: 314 + 4 us against 306 + 47 in four slices): it gets 15 %.
+bool gemm_resid_8p_wins(int64_t T, int64_t N, int64_t K, int max_split) {
     const double tn = (double)T * N;
     double best_split = kNoKernel;
     for (int ks = 1; ks <= std::max(1, max_split); ks++) {
         double c;
-        (void)pick_kernel(T, N, K, ks, &c);
+        (void)gemm_pick_kernel(T, N, K, ks, &c);
         best_split = std::min(best_split, c - cost_slabs(T, N, ks) + tn * (4.0 * (ks + 2) + 2.0) / 6.0e6 + 3.0);
     }
     return cost_8p(T, N, K, 1) + tn * 6.0 / 6.0e6 + 4.3 <= 1.15 * best_split;
 }
-int launch_gemm_resid(Launcher &L, const void *W, const void *x, int64_t T, int64_t N, int64_t K, const ResidEpi &re) {
-    if (re.np != gemm_resid_partials(N)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gemm_resid: partial-sum layout");
-    if (const int ks = tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, N, K, EPI_RESID) : 0) return launch_gemm_skf(L, W, x, nullptr, nullptr, T, N, K, EPI_RESID, nullptr, ks, &re);
-    if (const int ks = gemm_h4_plan(T, N, K, EPI_RESID)) return launch_gemm_h4(L, W, x, nullptr, nullptr, T, N, K, EPI_RESID, nullptr, ks, N, &re);
-    int64_t n_main = 0;
-    if (peel_plan(T, N, K, &n_main)) {
-        FL_TRY(launch_gemm_8p(L, W, x, nullptr, nullptr, T, n_main, K, EPI_RESID, nullptr, 1, N, false, &re));
-        ResidEpi rt = re;                                         // the tail's columns: same rows, later column tiles
-        rt.h += n_main; rt.w += n_main; rt.xn = (bf16_t *)rt.xn + n_main; rt.part += (n_main / 256) * 4;
-        if (const int ks = gemm_h4_tail_slices(T, N - n_main, K))
-            return launch_gemm_h4(L, (const bf16_t *)W + (size_t)n_main * K, x, nullptr, nullptr, T, N - n_main, K, EPI_RESID, nullptr, ks, N, &rt);
-        return launch_gemm_8p(L, (const bf16_t *)W + (size_t)n_main * K, x, nullptr, nullptr, T, N - n_main, K, EPI_RESID, nullptr, 1, N, true, &rt);
-    }
-    return launch_gemm_8p(L, W, x, nullptr, nullptr, T, N, K, EPI_RESID, nullptr, 1, N, false, &re);
-}
 
-static int launch_gemm_mfma_impl(Launcher &L, const void *W, const void *x, const float *bias, void *y,
-                                 int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit, int64_t ldc, bool allow8p) {
-    // 256x256 phase-interleaved kernel (k_gemm_8p.hip).  FL_GEMM_8P: 0 off, 1 where the model above prefers it, 2 always
-    const int use8p = !allow8p ? 0 : tune(TK_GEMM_8P);
-    const bool splittable = ksplit == 1 || (!bias && epi == EPI_F32);
-    int kern = splittable ? pick_kernel(T, N, K, ksplit) : GK_128;
-    if (!use8p && kern == GK_8P) kern = cost_256(T, N, K, ksplit) < cost_128(T, N, K, ksplit) ? GK_256 : GK_128;
-    if (use8p >= 2 && K % 64 == 0 && (K / 64) / ksplit >= 2 && splittable) kern = GK_8P;
-    if (kern == GK_8P) return launch_gemm_8p(L, W, x, bias, y, T, N, K, epi, row_scale, ksplit, ldc);
-    FL_TRY(rs_parts_to_vector(L, row_scale, T));                    // (the 128-column kernels take their row scales as a vector)
-    if (kern == GK_256) {
-        const int tm2 = (int)((T + BM2 - 1) / BM2), tn2 = (int)((N + BN - 1) / BN);
-        const size_t lds2 = 3 * (size_t)STAGE2;                     // 144 KiB
-        FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(gemm_mfma256_kernel), lds2));
-        double bytes2 = ((double)N * K + (double)T * K) * 2.0;
-        char tag2[32];
-        snprintf(tag2, sizeof tag2, "256x128,%lldx%lld%s", (long long)N, (long long)K, ksplit > 1 ? ",splitK" : "");
-        Launcher L2 = L; L2.tag = tag2;
-        return L2.launch(KC_GEMM_MFMA, bytes2, 2.0 * T * N * K, gemm_mfma256_kernel, dim3((unsigned)(tm2 * tn2), (unsigned)ksplit), dim3(512),
-                        lds2, (const bf16_t *)W, (const bf16_t *)x, bias, y, (int)T, (int)N, (int)K, epi, tm2, tn2, row_scale, ksplit, (int)ldc,
-                        (int)(tune(TK_H4_NT) == 1 || (tune(TK_H4_NT) < 0 && tm2 == 1 && T >= 176)));
-    }
-    const int tiles_m = (int)((T + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
+// The 256x128 (wide = true) or 128x128 kernel over the column range this call was given (all of N, or a piece of a peeled
+// matrix): ldc = the row stride of the full output.  Row scales as a vector (launch_plan finishes partial sums first).
+int launch_gemm_mfma(Launcher &L, bool wide, const void *W, const void *x, const float *bias, void *y,
+                     int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit, int64_t ldc) {
     if (ksplit > 1 && bias) FL_FAIL(FL_ERR_BAD_ARGUMENT, "split-K GEMM cannot add a bias");
-    const size_t lds = 4 * TILE_BYTES;     // 64 KiB
-    FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(gemm_mfma_kernel), lds));
-    double bytes = ((double)N * K + (double)T * K) * 2.0;
+    const int tm = (int)((T + (wide ? BM2 : BM) - 1) / (wide ? BM2 : BM)), tn = (int)((N + BN - 1) / BN);
+    const size_t lds = wide ? 3 * (size_t)STAGE2 : 4 * TILE_BYTES;     // 144 / 64 KiB
+    FL_TRY(raise_dynamic_lds(wide ? reinterpret_cast<const void *>(gemm_mfma256_kernel) : reinterpret_cast<const void *>(gemm_mfma_kernel), lds));
+    const double bytes = ((double)N * K + (double)T * K) * 2.0;
     char tag[32];
-    snprintf(tag, sizeof tag, "128x128,%lldx%lld%s", (long long)N, (long long)K, ksplit > 1 ? ",splitK" : "");
+    snprintf(tag, sizeof tag, "%s,%lldx%lld%s", wide ? "256x128" : "128x128", (long long)N, (long long)K, ksplit > 1 ? ",splitK" : "");
     Launcher LL = L; LL.tag = tag;
-    return LL.launch(KC_GEMM_MFMA, bytes, 2.0 * T * N * K, gemm_mfma_kernel, dim3((unsigned)(tiles_m * tiles_n), (unsigned)ksplit),
-                    dim3(256), lds, (const bf16_t *)W, (const bf16_t *)x, bias, y, (int)T, (int)N, (int)K, epi,
-                    tiles_m, tiles_n, row_scale, ksplit, (int)ldc);
+    const dim3 grid((unsigned)(tm * tn), (unsigned)ksplit);
+    if (wide)
+        return LL.launch(KC_GEMM_MFMA, bytes, 2.0 * T * N * K, gemm_mfma256_kernel, grid, dim3(512), lds, (const bf16_t *)W, (const bf16_t *)x, bias, y,
+                         (int)T, (int)N, (int)K, epi, tm, tn, row_scale, ksplit, (int)ldc, (int)(tune(TK_H4_NT) == 1 || (tune(TK_H4_NT) < 0 && tm == 1 && T >= 176)));
+    return LL.launch(KC_GEMM_MFMA, bytes, 2.0 * T * N * K, gemm_mfma_kernel, grid, dim3(256), lds, (const bf16_t *)W, (const bf16_t *)x, bias, y,
+                     (int)T, (int)N, (int)K, epi, tm, tn, row_scale, ksplit, (int)ldc);
 }
 
 }  // namespace fl

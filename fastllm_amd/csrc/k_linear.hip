@@ -89,97 +89,211 @@ static int launch_gemm_generic(Launcher &L, const void *W, const void *x, const 
                     (const WT *)W, (const XT *)x, bias, y, (int)T, (int)N, (int)K, epi, row_scale);
 }
 
-int launch_gemm_mfma(Launcher &L, const void *W, const void *x, const float *bias, void *y,
-                     int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit);   // k_gemm_mfma.hip
-int gemm_mfma_ksplit(int64_t T, int64_t N, int64_t K, int epi, int max_split);
+// ================================================================================ the planner
+static bool kernel_reads_rs_parts(int kernel) {
+    return kernel == LK_H4 || kernel == LK_W14 || kernel == LK_SKF || kernel == LK_8P || kernel == LK_4W_ROPE;
+}
+// a captured launch is never a sliced 128 x 256 one (its host-side word set would be baked into the graph)
+static bool h4_ok(int ks, bool captured) { return ks > 0 && !(captured && ks > 1); }
+static LinearPlan finish(LinearPlan p, int dtype, int64_t T, int64_t N) {
+    // (every launch of the plan must take the sums; a peeled matrix is kept on the vector.  FL_DEBUG_RS_PARTS, tests: every bf16
+    // prompt projection is planned as reading them, so that kernels which take a vector meet them)
+    p.reads_rs_parts = (kernel_reads_rs_parts(p.kernel) && p.n_main == N && (p.rows_main == T || kernel_reads_rs_parts(p.rest))) ||
+                       (dtype == FL_DTYPE_BF16 && T > 1 && !tune(TK_FORCE_GENERIC_GEMM) && tune(TK_DEBUG_RS_PARTS));
+    return p;
+}
 
-static GemvArgs plain_args(const void *W, const void *x, const float *bias, void *y, int64_t N, int64_t K, int epi,
-                           const float *scale) {
-    GemvArgs a; a.W = W; a.x = x; a.bias = bias; a.out = y; a.N = (int)N; a.K = (int)K; a.epi = epi; a.pro = PRO_X;
-    a.x_scale = scale;
-    return a;
+// The tiled kernels (k_gemm_mfma.hip): K slabs, whole-matrix stream-K, a column-peeled matrix (whole rounds of 256 x 256 tiles, the rest
+// on the 128 x 256 kernel, in stream-K form or on the smaller tiles), or one grid of the kernel the cost model picks.
+static void plan_tiles(LinearPlan &p, int64_t T, int64_t N, int64_t K, int epi, bool bias, int max_split, bool takes_slabs, bool captured) {
+    p.ks = p.n_split = (takes_slabs && !bias) ? gemm_mfma_ksplit(T, N, K, epi, max_split) : 1;
+    int64_t n_main = 0;
+    if (p.ks == 1 && gemm_streamk_whole(T, N, K)) {
+        p.kernel = LK_8P_STREAMK;
+    } else if (p.ks == 1 && gemm_peel_plan(T, N, K, &n_main)) {
+        p.kernel = gemm_tile_kernel(T, n_main, K, epi, bias, 1, true);
+        p.n_main = n_main;
+        const int ks = captured ? 0 : gemm_h4_tail_slices(T, N - n_main, K);
+        p.tail = ks ? LK_H4 : tune(TK_GEMM_STREAMK) ? LK_8P_STREAMK : gemm_tile_kernel(T, N - n_main, K, epi, bias, 1, false);
+        p.tail_ks = std::max(ks, 1);
+    } else {
+        p.kernel = gemm_tile_kernel(T, N, K, epi, bias, p.ks, true);
+    }
+}
+
+LinearPlan plan_linear(int dtype, int64_t T, int64_t N, int64_t K, int epi, int tp, int max_split, bool bias, bool takes_slabs, bool captured) {
+    LinearPlan p;
+    p.n_main = N; p.rows_main = T;
+    const bool generic = tune(TK_FORCE_GENERIC_GEMM) != 0;
+    if (dtype == FL_DTYPE_F32) {
+        p.kernel = T == 1 && gemv_supported(dtype, N, K) ? LK_GEMV : !generic && gemv_f32_rows_supported(T, N, K, epi) ? LK_F32_ROWS :
+                   !generic && gemm_f32_mfma_supported(T, N, K) ? LK_F32_MFMA : LK_GENERIC;
+        return p;
+    }
+    if (dtype != FL_DTYPE_BF16) return p;
+    if (T == 1 && gemv_supported(dtype, N, K)) { p.kernel = LK_GEMV; return finish(p, dtype, T, N); }
+    if (!generic && T > 1) {
+        // mid-size prompts: 128 x 256 tiles, K slices summed inside the launch (k_gemm_h4.hip) -- one complete output, no slabs
+        int ks = gemm_h4_plan(T, N, K, epi);
+        // a tensor-parallel rank's projections (no slabs: the all-reduce wants the sum): K slices that meet inside the launch
+        if (!h4_ok(ks, captured) && tp > 1 && max_split <= 1) ks = gemm_h4_plan_whole(T, N, K, epi);
+        if (h4_ok(ks, captured)) { p.kernel = LK_H4; p.ks = ks; return finish(p, dtype, T, N); }
+        // a few tokens past an even number of 256-row tiles: 3 x 128 tiles are a round and a half of the chip and cost two (Mistral-7B gate/up
+        // 512 / 513 tokens: 92.6 / 170.3 us).  The even part keeps its whole rounds and the last rows go as a launch of their own on
+        // whatever serves that many rows (ring kernel 36-46 us up to 32 rows, short-prompt GEMM 47-56 us up to 128).  Whole Mistral-7B
+        // prefills, split / one launch: 513 tokens 10.25 / 10.87 ms, 545 10.76 / 11.01, 600 11.26 / 11.37, 1025 16.49 / 16.83, 1100
+        // 16.91 / 17.08 -- and 700 12.48 / 12.29, 768 12.68 / 12.50, 1280 18.46 / 18.17: the second weight pass stops paying near 100 rows
+        if (epi == EPI_GATEUP && T > 512 && tune(TK_GATEUP_ROWSPLIT) && !bias) {
+            const int64_t tm = (T + 255) / 256, T0 = (tm - 1) * 256;
+            if ((tm & 1) && T - T0 <= 96 && gemm_w14_plan(T0, N, K, epi)) {
+                const LinearPlan r = plan_linear(dtype, T - T0, N, K, epi, tp, max_split, bias, false, captured);
+                p.kernel = LK_W14; p.rows_main = T0; p.rest = r.kernel; p.rest_ks = r.ks;
+                return finish(p, dtype, T, N);
+            }
+        }
+        // 224-column tiles where they fill the chip and 256-column ones do not (k_gemm_w14.hip)
+        if (gemm_w14_plan(T, N, K, epi)) { p.kernel = LK_W14; return finish(p, dtype, T, N); }
+    }
+    // short prompts / decode batches on the kernel whose K slices meet inside the launch (k_gemm_skf.hip): a tensor-parallel rank's
+    // complete outputs (no slabs for its all-reduce) up to 64 rows -- tp = 4, 32 rows: down_proj 22.6 -> 11.6 us, 128 rows: o_proj
+    // 11.1 -> 18.1 (the last arriver's tail grows with the tile) --; gate/up of the opt-in five-launch layer; every shape when forced
+    if (!generic && T > 1 && T <= 128) {
+        const int skf = tune(TK_GEMM_SKF);
+        const bool whole = epi == EPI_F32 && ((skf >= 1 && tp > 1 && max_split <= 1 && T <= 64) || skf >= 3);
+        if ((epi == EPI_GATEUP && skf >= 2) || whole) {
+            const int ks = gemm_skf_plan(T, N, K, epi);
+            if (ks > 0 && (ks > 1 || epi == EPI_GATEUP || skf >= 3)) { p.kernel = LK_SKF; p.ks = ks; return finish(p, dtype, T, N); }
+        }
+    }
+    // prompts of 2-32 tokens: the wide gate/up stream on the LDS-DMA ring kernel of the decode batches (5.8 / 5.3 TB/s at <= 16 / 32 rows against 4.9)
+    if (!generic && T > 1 && T <= 32 && epi == EPI_GATEUP && N >= 8192 && tune(TK_PREFILL_DMA) && gemv_dma_supported((int)T, N, K, epi, 0) &&
+        gemv_dma_ksplit(K, 0, epi) == 1) {
+        p.kernel = LK_DMA;
+    } else if (!generic && tune(TK_GEMM_SKINNY) && gemm_skinny_supported(T, N, K)) {     // short prompts: a weight stream
+        p.kernel = LK_SKINNY;   // (more slabs cost the summing launch more than they save here)
+        p.ks = p.n_split = (takes_slabs && !bias) ? gemm_skinny_ksplit(T, N, K, epi, std::min(max_split, 4)) : 1;
+    } else if (!generic && gemm_mfma_supported(dtype, T, N, K)) {
+        plan_tiles(p, T, N, K, epi, bias, max_split, takes_slabs, captured);
+    } else {
+        p.kernel = LK_GENERIC;
+    }
+    return finish(p, dtype, T, N);
+}
+
+// Long prompts on the 256 x 256 kernel whole (a peeled matrix: + a stream-K tail) or, from 257 tokens of the models' widths, the
+// 128 x 256 kernel in 2-4 in-launch K slices (gemm_h4_plan); short ones on k_gemm_skf.hip when opted in.
+LinearPlan plan_resid(int dtype, int64_t T, int64_t N, int64_t K, int max_split, bool captured) {
+    LinearPlan p;
+    p.n_main = N; p.rows_main = T;
+    if (tune(TK_GEMM_RESID) == 0 || dtype != FL_DTYPE_BF16) return p;
+    int ks = tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, N, K, EPI_RESID) : 0;
+    if (ks > 0) { p.kernel = LK_SKF; p.ks = ks; return p; }
+    ks = N % 16 == 0 ? gemm_h4_plan(T, N, K, EPI_RESID) : 0;
+    if (h4_ok(ks, captured)) { p.kernel = LK_H4; p.ks = ks; return p; }
+    if (tune(TK_GEMM_8P) != 1 || T < 256 || K % 64 || K / 64 < 2 || N % 16 || gemm_streamk_whole(T, N, K)) return p;
+    int64_t n_main = 0;
+    if (gemm_peel_plan(T, N, K, &n_main)) {                           // main launch + a tail, both with the residual epilogue
+        if (!tune(TK_GEMM_STREAMK)) return p;
+        p.kernel = LK_8P; p.n_main = n_main;
+        ks = captured ? 0 : gemm_h4_tail_slices(T, N - n_main, K);
+        p.tail = ks ? LK_H4 : LK_8P_STREAMK; p.tail_ks = std::max(ks, 1);
+    } else if (gemm_pick_kernel(T, N, K, 1) == LK_8P && gemm_resid_8p_wins(T, N, K, max_split)) {
+        p.kernel = LK_8P;
+    }
+    return p;
+}
+
+// The RoPE / bias / KV-append epilogue rides in the QKV projection where a kernel has it -- short prompts on k_gemm_skf.hip (opt-in),
+// mid-size ones (and a tensor-parallel rank's narrower q | k | v) on k_gemm_h4.hip, long ones on the four-wave 256 x 256 kernel where
+// launch_linear would run ONE plain grid of 256 x 256 tiles, or whole rounds + tail columns on the 128 x 256 kernel (1, 2 or 4 in-launch
+// slices) -- so no fp32 QKV matrix exists.  Otherwise the plain projection: K slabs and stream-K pieces keep the fp32 output and the
+// rope_kv launch (which sums the slabs anyway).
+LinearPlan plan_qkv_rope(int dtype, int64_t T, int64_t N, int64_t K, int64_t d, int64_t kv_width, int tp, int max_split) {
+    LinearPlan p;
+    p.n_main = N; p.rows_main = T; p.rope = true;
+    if (dtype == FL_DTYPE_BF16) {
+        int h4 = gemm_h4_plan(T, N, K, EPI_QKV_ROPE);
+        if (!h4 && tp > 1 && kv_width % 128 == 0 && N % 128 == 0) h4 = gemm_h4_plan_whole(T, N, K, EPI_QKV_ROPE);
+        const int skf = !h4 && tp == 1 && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, N, K, EPI_QKV_ROPE, (int)d) : 0;
+        if (skf || h4) { p.kernel = skf ? LK_SKF : LK_H4; p.ks = skf ? skf : h4; return finish(p, dtype, T, N); }
+        if (tune(TK_GEMM_ROPE_4W) && T >= 768 && !tune(TK_FORCE_GENERIC_GEMM) && tune(TK_GEMM_8P) == 1 && gemm_mfma_supported(dtype, T, N, K) &&
+            !gemm_streamk_whole(T, N, K)) {
+            int64_t nm = N;
+            int ks = 0;
+            const bool ok = gemm_peel_plan(T, N, K, &nm) ? (ks = gemm_h4_tail_slices(T, N - nm, K)) && ks != 3 && nm % 128 == 0 && (N - nm) % 128 == 0
+                                                        : gemm_mfma_ksplit(T, N, K, EPI_F32, max_split) == 1 && gemm_pick_kernel(T, N, K, 1) == LK_8P;
+            if (ok && gemm_4w_rope_supported(T, nm, K) && gemm_4w_rule(T, nm, K, K / 64, false)) {
+                p.kernel = LK_4W_ROPE; p.n_main = nm;
+                if (nm < N) { p.tail = LK_H4; p.tail_ks = ks; }
+                return finish(p, dtype, T, N);
+            }
+        }
+    }
+    return plan_linear(dtype, T, N, K, EPI_F32, tp, max_split, false, true, false);
+}
+
+// ================================================================================ carrying a plan out
+// One launch over rows [0, T) and the column range [0, N) of an output whose rows are ldc elements apart.  A kernel that takes its
+// row scales as a vector finishes partial sums the caller left first (rs_parts_to_vector).
+static int launch_one(Launcher &L, int kernel, int ks, int dtype, const void *W, const void *x, const float *bias, void *y, int64_t T, int64_t N,
+                      int64_t K, int epi, const float *row_scale, int64_t ldc, const ResidEpi *re, const RopeEpi *ro) {
+    if (!kernel_reads_rs_parts(kernel)) FL_TRY(rs_parts_to_vector(L, row_scale, T));
+    switch (kernel) {
+    case LK_GEMV: {
+        GemvArgs a; a.W = W; a.x = x; a.bias = bias; a.out = y; a.N = (int)N; a.K = (int)K; a.epi = epi; a.pro = PRO_X; a.x_scale = row_scale;
+        return launch_gemv(L, dtype, a);
+    }
+    case LK_H4: return launch_gemm_h4(L, W, x, bias, y, T, N, K, epi, row_scale, ks, ldc, re, ro);
+    case LK_W14: return launch_gemm_w14(L, W, x, bias, y, T, N, K, epi, row_scale, ldc);
+    case LK_SKF: return launch_gemm_skf(L, W, x, bias, y, T, N, K, epi, row_scale, ks, re, ro);
+    case LK_DMA: {
+        GemvBatchArgs a; a.W = W; a.x = x; a.x_scale = row_scale; a.out = y; a.N = (int)N; a.K = (int)K; a.epi = epi; a.pro = PRO_X; a.B = (int)T; a.nks = 1;
+        return launch_gemv_dma(L, a);
+    }
+    case LK_SKINNY: return launch_gemm_skinny(L, W, x, bias, y, T, N, K, epi, row_scale, ks);
+    case LK_8P: return launch_gemm_8p(L, W, x, bias, y, T, N, K, epi, row_scale, ks, ldc, false, re);
+    case LK_8P_STREAMK: return launch_gemm_8p(L, W, x, bias, y, T, N, K, epi, row_scale, 1, ldc, true, re);
+    case LK_256: case LK_128: return launch_gemm_mfma(L, kernel == LK_256, W, x, bias, y, T, N, K, epi, row_scale, ks, ldc);
+    case LK_4W_ROPE: return launch_gemm_4w_rope(L, W, x, bias, T, N, K, row_scale, *ro);
+    case LK_GENERIC:
+        if (dtype == FL_DTYPE_F32) return launch_gemm_generic<float, float>(L, W, x, bias, y, T, N, K, epi, row_scale);
+        return launch_gemm_generic<bf16_t, bf16_t>(L, W, x, bias, y, T, N, K, epi, row_scale);
+    case LK_F32_ROWS: return launch_gemv_f32_rows(L, W, x, bias, y, T, N, K, epi, row_scale);
+    case LK_F32_MFMA: return launch_gemm_f32_mfma(L, W, x, bias, y, T, N, K, epi, row_scale);
+    }
+    FL_FAIL(FL_ERR_UNSUPPORTED, "no kernel planned for this projection (dtype %d)", dtype);
+}
+
+int launch_plan(Launcher &L, const LinearPlan &p, int dtype, const void *W, const void *x, const float *bias, void *y, int64_t T, int64_t N,
+                int64_t K, int epi, const float *row_scale, const ResidEpi *re, const RopeEpi *ro) {
+    FL_TRY(launch_one(L, p.kernel, p.ks, dtype, W, x, bias, y, p.rows_main, p.n_main, K, epi, row_scale, N, re, ro));
+    if (p.n_main < N) {     // a peeled matrix's tail: the same rows, the output's later columns
+        const int64_t c = p.n_main;
+        ResidEpi rt; RopeEpi ot;
+        if (re) { rt = *re; rt.h += c; rt.w += c; rt.xn = (bf16_t *)rt.xn + c; rt.part += (c / 256) * 4; }
+        if (ro) { ot = *ro; ot.col_base = (int)c; }
+        void *yt = y ? (char *)y + (size_t)(epi == EPI_GATEUP ? c / 2 * 2 : c * 4) : nullptr;
+        FL_TRY(launch_one(L, p.tail, p.tail_ks, dtype, (const bf16_t *)W + (size_t)c * K, x, bias ? bias + c : nullptr, yt, p.rows_main, N - c, K, epi,
+                          row_scale, N, re ? &rt : nullptr, ro ? &ot : nullptr));
+    }
+    if (p.rows_main < T) {  // a gate/up row split: the last rows, all columns
+        const int64_t r = p.rows_main;
+        Launcher L2 = L;
+        if (L2.rsp.part) L2.rsp.part += (size_t)r * L2.rsp.np;
+        FL_TRY(launch_one(L2, p.rest, p.rest_ks, dtype, W, (const char *)x + (size_t)r * K * 2, bias, (char *)y + (size_t)r * (N / 2) * 2, T - r, N, K,
+                          epi, row_scale ? row_scale + r : nullptr, N, re, ro));
+    }
+    return FL_OK;
 }
 
 int launch_linear(Launcher &L, int dtype, const void *W, const void *x, const float *bias, void *y,
-                  int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int max_split, int *n_split_out) {
+                  int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int max_split, int *n_split_out, bool captured) {
     if (n_split_out) *n_split_out = 1;
     if (T <= 0 || N <= 0 || K <= 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_linear: bad shape");
     if (epi == EPI_GATEUP && N % 32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up matrix rows must be a multiple of 32");
-    const int force_generic = tune(TK_FORCE_GENERIC_GEMM);
-    // Launcher::rsp (row scales as partial sums): only the kernels gemm_takes_rs_parts() names read it -- any other path would
-    // silently use a stale vector, so the sums are finished into the vector first (kernels.h, rs_parts_to_vector)
-    auto no_parts = [&]() -> int { return rs_parts_to_vector(L, row_scale, T); };
-    if (dtype == FL_DTYPE_BF16) {
-        if (T == 1 && gemv_supported(dtype, N, K)) { FL_TRY(no_parts()); return launch_gemv(L, dtype, plain_args(W, x, bias, y, N, K, epi, row_scale)); }
-        // mid-size prompts: 128 x 256 tiles, K slices summed inside the launch (k_gemm_h4.hip) -- one complete output, no slabs
-        if (!force_generic && T > 1) {
-            const int ks = gemm_h4_plan(T, N, K, epi);
-            if (ks > 0) return launch_gemm_h4(L, W, x, bias, y, T, N, K, epi, row_scale, ks);
-            // a tensor-parallel rank's projections (no slabs: the all-reduce wants the sum): K slices that meet inside the launch
-            if (L.tp > 1 && max_split <= 1) {
-                const int kw = gemm_h4_plan_whole(T, N, K, epi);
-                if (kw > 0) return launch_gemm_h4(L, W, x, bias, y, T, N, K, epi, row_scale, kw);
-            }
-            // a few tokens past an even number of 256-row tiles: 3 x 128 tiles are a round and a half of the chip and cost two (Mistral-7B gate/up
-            // 512 / 513 tokens: 92.6 / 170.3 us).  The even part keeps its whole rounds and the last rows go as a launch of their own on
-            // whatever serves that many rows (ring kernel 36-46 us up to 32 rows, short-prompt GEMM 47-56 us up to 128).  Whole Mistral-7B
-            // prefills, split / one launch: 513 tokens 10.25 / 10.87 ms, 545 10.76 / 11.01, 600 11.26 / 11.37, 1025 16.49 / 16.83, 1100
-            // 16.91 / 17.08 -- and 700 12.48 / 12.29, 768 12.68 / 12.50, 1280 18.46 / 18.17: the second weight pass stops paying near 100 rows
-            if (epi == EPI_GATEUP && T > 512 && tune(TK_GATEUP_ROWSPLIT) && !bias) {
-                const int64_t tm = (T + 255) / 256, T0 = (tm - 1) * 256;
-                if ((tm & 1) && T - T0 <= 96 && gemm_w14_plan(T0, N, K, epi)) {
-                    FL_TRY(launch_gemm_w14(L, W, x, bias, y, T0, N, K, epi, row_scale));
-                    Launcher L2 = L;
-                    if (L2.rsp.part) L2.rsp.part += (size_t)T0 * L2.rsp.np;
-                    if (T - T0 <= 32) FL_TRY(rs_parts_to_vector(L2, row_scale ? row_scale + T0 : nullptr, T - T0));     // (the ring kernel reads the vector)
-                    return launch_linear(L2, dtype, W, (const char *)x + (size_t)T0 * K * 2, bias, (char *)y + (size_t)T0 * (N / 2) * 2, T - T0, N, K, epi,
-                                         row_scale ? row_scale + T0 : nullptr, max_split, nullptr);
-                }
-            }
-            // 224-column tiles where they fill the chip and 256-column ones do not (k_gemm_w14.hip)
-            if (gemm_w14_plan(T, N, K, epi)) return launch_gemm_w14(L, W, x, bias, y, T, N, K, epi, row_scale);
-        }
-        // short prompts / decode batches on the kernel whose K slices meet inside the launch (k_gemm_skf.hip): a tensor-parallel rank's
-        // complete outputs (no slabs for its all-reduce) up to 64 rows -- tp = 4, 32 rows: down_proj 22.6 -> 11.6 us, 128 rows: o_proj
-        // 11.1 -> 18.1 (the last arriver's tail grows with the tile) --; gate/up of the opt-in five-launch layer; every shape when forced
-        if (!force_generic && T > 1 && T <= 128) {
-            const int skf = tune(TK_GEMM_SKF);
-            const bool whole = epi == EPI_F32 && ((skf >= 1 && L.tp > 1 && max_split <= 1 && T <= 64) || skf >= 3);
-            if ((epi == EPI_GATEUP && skf >= 2) || whole) {
-                const int ks = gemm_skf_plan(T, N, K, epi);
-                if (ks > 0 && (ks > 1 || epi == EPI_GATEUP || skf >= 3)) return launch_gemm_skf(L, W, x, bias, y, T, N, K, epi, row_scale, ks);
-            }
-        }
-        // prompts of 2-32 tokens: the wide gate/up stream on the LDS-DMA ring kernel of the decode batches (5.8 / 5.3 TB/s at <= 16 / 32 rows against 4.9)
-        if (!force_generic && T > 1 && T <= 32 && epi == EPI_GATEUP && N >= 8192 && !L.rsp.part && tune(TK_PREFILL_DMA) &&
-            gemv_dma_supported((int)T, N, K, epi, 0) && gemv_dma_ksplit(K, 0, epi) == 1) {
-            GemvBatchArgs ga;
-            ga.W = W; ga.x = x; ga.x_scale = row_scale; ga.out = y; ga.N = (int)N; ga.K = (int)K; ga.epi = epi; ga.pro = PRO_X; ga.B = (int)T; ga.nks = 1;
-            return launch_gemv_dma(L, ga);
-        }
-        const int use_skinny = tune(TK_GEMM_SKINNY);
-        if (!force_generic && use_skinny && gemm_skinny_supported(T, N, K)) {     // short prompts: a weight stream
-            FL_TRY(no_parts());
-            const int ks = (n_split_out && !bias) ? gemm_skinny_ksplit(T, N, K, epi, std::min(max_split, 4)) : 1;   // (more slabs cost the summing launch more than they save here)
-            if (n_split_out) *n_split_out = ks;
-            return launch_gemm_skinny(L, W, x, bias, y, T, N, K, epi, row_scale, ks);
-        }
-        if (!force_generic && gemm_mfma_supported(dtype, T, N, K)) {
-            const int ks = (n_split_out && !bias) ? gemm_mfma_ksplit(T, N, K, epi, max_split) : 1;
-            if (n_split_out) *n_split_out = ks;
-            return launch_gemm_mfma(L, W, x, bias, y, T, N, K, epi, row_scale, ks);
-        }
-        FL_TRY(no_parts());
-        return launch_gemm_generic<bf16_t, bf16_t>(L, W, x, bias, y, T, N, K, epi, row_scale);
-    }
-    FL_TRY(no_parts());
-    if (dtype == FL_DTYPE_F32) {
-        if (T == 1 && gemv_supported(dtype, N, K)) return launch_gemv(L, dtype, plain_args(W, x, bias, y, N, K, epi, row_scale));
-        if (gemv_f32_rows_supported(T, N, K, epi) && !tune(TK_FORCE_GENERIC_GEMM)) return launch_gemv_f32_rows(L, W, x, bias, y, T, N, K, epi, row_scale);
-        if (gemm_f32_mfma_supported(T, N, K) && !tune(TK_FORCE_GENERIC_GEMM)) return launch_gemm_f32_mfma(L, W, x, bias, y, T, N, K, epi, row_scale);
-        return launch_gemm_generic<float, float>(L, W, x, bias, y, T, N, K, epi, row_scale);
-    }
-    FL_FAIL(FL_ERR_UNSUPPORTED, "launch_linear: unsupported dtype %d", dtype);
+    const LinearPlan p = plan_linear(dtype, T, N, K, epi, L.tp, max_split, bias != nullptr, n_split_out != nullptr, captured);
+    if (n_split_out) *n_split_out = p.n_split;
+    return launch_plan(L, p, dtype, W, x, bias, y, T, N, K, epi, row_scale);
 }
 
 }  // namespace fl

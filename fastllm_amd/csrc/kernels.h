@@ -17,7 +17,7 @@ struct ProfRecord { int kc; double bytes, flops; hipEvent_t e0, e1; char tag[32]
 
 // 1/rms of the rows a residual epilogue (EPI_RESID) left, taken by the CONSUMING projection itself from the partial sums of squares
 // -- row t: 1 / sqrt(sum_i part[t][i] / h + eps), summed left to right -- instead of an rms_finalize launch in between.  Honoured by
-// the 256 x 256 kernels' plain launches and by the 128 x 256 kernel (gemm_takes_rs_parts tells); everything else ignores it.
+// the 256 x 256 kernels' plain launches and by the 128 x 256 kernel (LinearPlan::reads_rs_parts tells); everything else ignores it.
 struct RsParts { const float *part = nullptr; int np = 0; float eps = 0.f, inv_h = 0.f; };
 
 // Launch context: the stream a kernel goes to and, while profiling, where its event pair is kept.
@@ -209,18 +209,48 @@ __host__ __device__ inline int64_t gateup_row(int64_t q, int is_up) { return (q 
 // a preceding RMSNorm, applied after the dot product (see launch_rmsnorm_add).
 // max_split > 1 allows split-K: y then holds *n_split_out fp32 slabs of [T,N] that the consumer sums
 // (launch_rmsnorm_add does); *n_split_out is always written when the pointer is given.
+// captured: the launch may be recorded into a graph (a decode batch's step)
 int launch_linear(Launcher &L, int dtype, const void *W, const void *x, const float *bias, void *y,
                   int64_t T, int64_t N, int64_t K, int epi, const float *row_scale = nullptr,
-                  int max_split = 1, int *n_split_out = nullptr);
-// ldc: row stride of y in elements of the FULL output width (0 = N): a launch may cover a column range of a wider matrix
-bool gemm_takes_rs_parts(int dtype, int64_t T, int64_t N, int64_t K, int epi, int max_split);   // would launch_linear's kernel for this shape honour Launcher::rsp?
-bool gemm_resid_supported(int dtype, int64_t T, int64_t N, int64_t K, int max_split);   // k_gemm_mfma.hip: would launch_gemm_resid take this shape?
+                  int max_split = 1, int *n_split_out = nullptr, bool captured = false);
+
+struct RopeEpi;
+// ---- which kernel runs a projection (k_linear.hip): the one place the selection rules are combined.  The per-kernel rules
+// (gemm_h4_plan, gemm_skf_plan, gemm_pick_kernel, gemm_peel_plan ...) are its inputs; launch_plan carries a plan out.
+enum { LK_NONE, LK_GEMV, LK_H4, LK_W14, LK_SKF, LK_DMA, LK_SKINNY, LK_8P, LK_8P_STREAMK, LK_256, LK_128, LK_4W_ROPE, LK_GENERIC,
+       LK_F32_ROWS, LK_F32_MFMA };
+struct LinearPlan {
+    int kernel = LK_NONE, ks = 1;      // rows [0, rows_main) x columns [0, n_main) in ks K slices (met inside the launch, or slabs)
+    int64_t n_main = 0;                // < N: a peeled matrix -- columns [n_main, N) on `tail`, the same rows
+    int tail = LK_NONE, tail_ks = 1;
+    int64_t rows_main = 0;             // < T: a gate/up row split -- rows [rows_main, T) on `rest`, all columns
+    int rest = LK_NONE, rest_ks = 1;
+    int n_split = 1;                   // fp32 slabs the output is left in (the consumer sums them)
+    bool rope = false;                 // plan_qkv_rope: RoPE / bias / KV append in the epilogue; false: fp32 output for launch_rope_kv
+    bool reads_rs_parts = false;       // every launch takes its row scales from Launcher::rsp (the caller may leave them as partial sums)
+};
+// takes_slabs: the caller sums up to max_split fp32 slabs; tp: the model's tensor-parallel degree (> 1: a rank's shard shapes)
+LinearPlan plan_linear(int dtype, int64_t T, int64_t N, int64_t K, int epi, int tp, int max_split, bool bias, bool takes_slabs, bool captured);
+// o_proj / down_proj with the residual epilogue (EPI_RESID); kernel LK_NONE: keep the rmsnorm_add launches
+LinearPlan plan_resid(int dtype, int64_t T, int64_t N, int64_t K, int max_split, bool captured);
+// the QKV projection of a prompt; kv_width: the k (= v) columns of this shard
+LinearPlan plan_qkv_rope(int dtype, int64_t T, int64_t N, int64_t K, int64_t d, int64_t kv_width, int tp, int max_split);
+int launch_plan(Launcher &L, const LinearPlan &p, int dtype, const void *W, const void *x, const float *bias, void *y, int64_t T, int64_t N,
+                int64_t K, int epi, const float *row_scale, const ResidEpi *re = nullptr, const RopeEpi *ro = nullptr);
+// planner inputs of the tiled kernels (k_gemm_mfma.hip): the cost model's pick (LK_8P / LK_256 / LK_128), the same under FL_GEMM_8P
+int gemm_pick_kernel(int64_t T, int64_t N, int64_t K, int ks, double *cost_out = nullptr);
+int gemm_tile_kernel(int64_t T, int64_t N, int64_t K, int epi, bool bias, int ksplit, bool allow8p);
+int gemm_mfma_ksplit(int64_t T, int64_t N, int64_t K, int epi, int max_split);
+bool gemm_streamk_whole(int64_t T, int64_t N, int64_t K);
+bool gemm_peel_plan(int64_t T, int64_t N, int64_t K, int64_t *n_main_out);
+bool gemm_resid_8p_wins(int64_t T, int64_t N, int64_t K, int max_split);
 int gemm_resid_partials(int64_t N);                                                       // partial sums per row (np)
-int launch_gemm_resid(Launcher &L, const void *W, const void *x, int64_t T, int64_t N, int64_t K, const ResidEpi &re);
+// ldc: row stride of y in elements of the FULL output width (0 = N): a launch may cover a column range of a wider matrix
+int launch_gemm_mfma(Launcher &L, bool wide, const void *W, const void *x, const float *bias, void *y,
+                     int64_t T, int64_t N, int64_t K, int epi, const float *row_scale, int ksplit, int64_t ldc);
 int launch_rms_finalize(Launcher &L, const float *part, int np, float eps, float *inv_rms, int64_t T, int64_t h);
-// A kernel that reads its row scales as a VECTOR was picked although the caller left them as a residual epilogue's partial sums
-// (Launcher::rsp): the plan (gemm_takes_rs_parts) and the launch disagree -- a switch changed in between, or the two rules drifted.
-// Finish the sums into the vector the caller passed as row_scale and go on, instead of failing a forward half way through its layers.
+// Every launch of a kernel that reads its row scales as a VECTOR first finishes Launcher::rsp's partial sums into row_scale: the safety
+// net under a caller that sets rsp where the plan did not say reads_rs_parts (FL_DEBUG_RS_PARTS: on purpose).
 int rs_parts_to_vector(Launcher &L, const float *row_scale, int64_t T);
 int64_t gemm_8p_workspace_bytes(hipStream_t stream);   // stream-K workspace held for a stream on the current device
 void gemm_8p_release_stream(hipStream_t stream);   // frees the stream-K workspace of a stream that is about to be destroyed
@@ -265,14 +295,9 @@ bool gemm_4w_rule(int64_t T, int64_t N, int64_t K, int64_t ksteps, bool streamk)
 bool gemm_4w_rope_supported(int64_t T, int64_t N, int64_t K);
 int launch_gemm_4w_rope(Launcher &L, const void *W, const void *x, const float *bias, int64_t T, int64_t N, int64_t K, const float *row_scale,
                         const RopeEpi &rope);
-// the launches of a long prompt's QKV projection with that epilogue (k_gemm_mfma.hip): one plain grid, or whole rounds + peeled tail columns
-// on the 128 x 256 kernel -- false where launch_linear would cut K into slabs or run stream-K (rope_kv_append then sums / rotates)
-bool gemm_qkv_rope_long_plan(int64_t T, int64_t N, int64_t K, int max_split);
-int launch_gemm_qkv_rope_long(Launcher &L, const void *W, const void *x, const float *bias, int64_t T, int64_t N, int64_t K, const float *row_scale,
-                              const RopeEpi &rope, int max_split);
 int launch_gemm_w14(Launcher &L, const void *W, const void *x, const float *bias, void *y, int64_t T, int64_t N, int64_t K,
                     int epi, const float *row_scale, int64_t ldc = 0);
-int gemm_h4_tail_slices(int64_t T, int64_t N, int64_t K);     // a peeled GEMM's tail columns on this kernel: K slices, or 0 = the stream-K launch + fix-up   // K slices the kernel would run this shape in; 0: another kernel takes it
+int gemm_h4_tail_slices(int64_t T, int64_t N, int64_t K);     // a peeled GEMM's tail columns on this kernel: K slices, or 0 = the stream-K launch + fix-up
 int launch_gemm_h4(Launcher &L, const void *W, const void *x, const float *bias, void *y, int64_t T, int64_t N, int64_t K,
                    int epi, const float *row_scale, int ksplit, int64_t ldc = 0, const ResidEpi *resid = nullptr, const RopeEpi *rope = nullptr);
 int64_t gemm_h4_workspace_bytes(hipStream_t stream);

@@ -529,6 +529,7 @@ static int qkv_split_cap(int64_t T) { return T <= 1 ? 1 : (T <= 128 ? kMaxQkvSpl
 // never write past a buffer that was allocated while it was lowered)
 static int ksplit_cap_max(int64_t T) { return T <= 1 ? 1 : (T > 128 && T <= kMidT ? kMaxKSplitMid : kMaxKSplit); }
 static int qkv_split_cap_max(int64_t T) { return T <= 1 ? 1 : (T <= 128 ? kMaxQkvSplitShort : (T <= kMidT ? kMaxKSplitMid : kMaxQkvSplit)); }
+static int qkv_split(int64_t T) { return std::min(tune(TK_QKV_SPLIT), qkv_split_cap(T)); }   // K slabs a prompt's QKV projection may leave
 // rows of slab storage that serve every prompt of at most T tokens
 static int64_t slab_rows(int64_t T, int (*cap)(int64_t)) {
     return std::max<int64_t>({T * cap(T), std::min<int64_t>(T, kMidT) * cap(std::min<int64_t>(T, kMidT)), std::min<int64_t>(T, 128) * cap(std::min<int64_t>(T, 128))});
@@ -1238,11 +1239,11 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
     // consumer_takes_parts: the projection that follows takes its row scales (1/rms) straight from the partial sums (Launcher::rsp,
     // kernels.h) -- then there is no rms_finalize launch either; rs_lazy says so until that projection is launched
     bool rs_lazy = false;
-    auto linear_resid = [&](Launcher &L, Shard &sh, Scratch &sc, const void *W, const void *x, int64_t K, const float *next_norm_w,
+    auto linear_resid = [&](Launcher &L, Scratch &sc, const LinearPlan &p, const void *W, const void *x, int64_t K, const float *next_norm_w,
                             bool consumer_takes_parts) -> int {
         ResidEpi re;
         re.h = sc.x_res; re.w = next_norm_w; re.xn = sc.xn; re.part = sc.rs_part; re.np = gemm_resid_partials(D.h);
-        FL_TRY(launch_gemm_resid(L, W, x, T, D.h, K, re));
+        FL_TRY(launch_plan(L, p, dt, W, x, nullptr, nullptr, T, D.h, K, EPI_RESID, nullptr, &re));
         // (A/B, whole prefills: Mistral-7B 384 / 512 / 640 tokens 0.987 / 0.997 / 0.999, 4096 tokens 1.011: every workgroup of a long
         // prompt's grid sums 256 rows' partials again, the finalize launch does it once)
         rs_lazy = consumer_takes_parts && tune(TK_RS_LAZY) != 0 && T <= 1024;
@@ -1262,37 +1263,20 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             void *kc = (char *)cs.k + kv_layer, *vc = (char *)cs.v + kv_layer;
             if (!norm_done) FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, l == 0 ? nullptr : sc.delta, ly.ln1, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
             norm_done = false;
-            int qkv_slabs = 1;
-            const int qkv_split = tune(TK_QKV_SPLIT);
             // (Qwen2's q/k/v bias moves into the RoPE launch, which sums the slabs anyway: with the bias in the GEMM epilogue the
             // projection could not run in K slices and a mid-size prompt's QKV sat on 128x128 tiles -- T = 512: 63 us at 0.27 PFLOP/s)
             const int64_t sa = (int64_t)c->seq_alloc;
-            int h4_qkv = dt == FL_DTYPE_BF16 ? gemm_h4_plan(T, nq, D.h, EPI_QKV_ROPE) : 0;
-            if (!h4_qkv && dt == FL_DTYPE_BF16 && m->tp > 1 && D.d * sh.Hkvs % 128 == 0 && nq % 128 == 0) h4_qkv = gemm_h4_plan_whole(T, nq, D.h, EPI_QKV_ROPE);   // (a rank's narrower q | k | v)
             with_parts(L, sc);                                       // (the previous layer's down_proj may have left 1/rms as partial sums)
-            const int skf_qkv = dt == FL_DTYPE_BF16 && !h4_qkv && m->tp == 1 && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
-            if (skf_qkv) {
-                // short prompts: the same epilogue on the weight-streaming kernel (k_gemm_skf.hip), its K slices met inside the launch
+            const LinearPlan qp = plan_qkv_rope(dt, T, nq, D.h, D.d, D.d * sh.Hkvs, m->tp, qkv_split(T));
+            if (qp.rope) {
+                // RoPE, bias and the KV append ride in the projection's epilogue: no fp32 QKV matrix
                 RopeEpi ro;
                 ro.st = cs.st; ro.cos_tab = sh.cos_tab; ro.sin_tab = sh.sin_tab; ro.max_pos = (int)D.max_pos; ro.q_out = sc.q; ro.k_cache = kc; ro.v_cache = vc;
                 ro.H = (int)sh.Hs; ro.Hkv = (int)sh.Hkvs; ro.d = (int)D.d; ro.max_seq = (int)sa; ro.v_transposed = c->v_transposed ? 1 : 0;
-                FL_TRY(launch_gemm_skf(L, ly.wqkv, sc.xn, ly.bqkv, nullptr, T, nq, D.h, EPI_QKV_ROPE, sc.inv_rms, skf_qkv, nullptr, &ro));
-            } else if (h4_qkv) {
-                // mid-size prompts: RoPE, bias and the KV append ride in the projection's epilogue (k_gemm_h4.hip): no fp32 QKV matrix
-                RopeEpi ro;
-                ro.st = cs.st; ro.cos_tab = sh.cos_tab; ro.sin_tab = sh.sin_tab; ro.max_pos = (int)D.max_pos; ro.q_out = sc.q; ro.k_cache = kc; ro.v_cache = vc;
-                ro.H = (int)sh.Hs; ro.Hkv = (int)sh.Hkvs; ro.d = (int)D.d; ro.max_seq = (int)sa; ro.v_transposed = c->v_transposed ? 1 : 0;
-                FL_TRY(launch_gemm_h4(L, ly.wqkv, sc.xn, ly.bqkv, nullptr, T, nq, D.h, EPI_QKV_ROPE, sc.inv_rms, h4_qkv, nq, nullptr, &ro));
-            } else if (dt == FL_DTYPE_BF16 && gemm_qkv_rope_long_plan(T, nq, D.h, std::min(qkv_split, qkv_split_cap(T)))) {
-                // long prompts: the same epilogue on the four-wave 256 x 256 kernel (+ the 128 x 256 kernel for peeled tail columns)
-                RopeEpi ro;
-                ro.st = cs.st; ro.cos_tab = sh.cos_tab; ro.sin_tab = sh.sin_tab; ro.max_pos = (int)D.max_pos; ro.q_out = sc.q; ro.k_cache = kc; ro.v_cache = vc;
-                ro.H = (int)sh.Hs; ro.Hkv = (int)sh.Hkvs; ro.d = (int)D.d; ro.max_seq = (int)sa; ro.v_transposed = c->v_transposed ? 1 : 0;
-                FL_TRY(launch_gemm_qkv_rope_long(L, ly.wqkv, sc.xn, ly.bqkv, T, nq, D.h, sc.inv_rms, ro, std::min(qkv_split, qkv_split_cap(T))));
+                FL_TRY(launch_plan(L, qp, dt, ly.wqkv, sc.xn, ly.bqkv, nullptr, T, nq, D.h, EPI_QKV_ROPE, sc.inv_rms, nullptr, &ro));
             } else {
-                FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms,
-                                     std::min(qkv_split, qkv_split_cap(T)), &qkv_slabs));
-                FL_TRY(launch_rope_kv(L, dt, sc.qkv, cs.st, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kc, vc, T, sh.Hs, sh.Hkvs, D.d, sa, c->v_transposed, qkv_slabs, ly.bqkv));
+                FL_TRY(launch_plan(L, qp, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms));
+                FL_TRY(launch_rope_kv(L, dt, sc.qkv, cs.st, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kc, vc, T, sh.Hs, sh.Hkvs, D.d, sa, c->v_transposed, qp.n_split, ly.bqkv));
             }
             L.rsp = RsParts{};
             if (T == 1) {
@@ -1304,8 +1288,10 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             } else {
                 FL_TRY(launch_attn_prefill(L, dt, sc.q, kc, vc, cs.st, sc.ao, T, sh.Hs, sh.Hkvs, D.d, sa, D.scale, D.window));
             }
-            if (resid_ok && gemm_resid_supported(dt, T, D.h, sh.Hs * D.d, max_split)) {
-                FL_TRY(linear_resid(L, sh, sc, ly.wo, sc.ao, sh.Hs * D.d, ly.ln2, gemm_takes_rs_parts(dt, T, 2 * sh.Ip, D.h, EPI_GATEUP, 1)));
+            const LinearPlan op = resid_ok ? plan_resid(dt, T, D.h, sh.Hs * D.d, max_split, false) : LinearPlan{};
+            if (op.kernel != LK_NONE) {
+                const bool gu_parts = plan_linear(dt, T, 2 * sh.Ip, D.h, EPI_GATEUP, m->tp, 1, false, false, false).reads_rs_parts;
+                FL_TRY(linear_resid(L, sc, op, ly.wo, sc.ao, sh.Hs * D.d, ly.ln2, gu_parts));
                 norm_done = true;
             } else {
                 FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
@@ -1321,12 +1307,12 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             with_parts(L, sc);
             FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
             L.rsp = RsParts{};
-            if (resid_ok && gemm_resid_supported(dt, T, D.h, sh.Ip, max_split)) {
+            const LinearPlan dp = resid_ok ? plan_resid(dt, T, D.h, sh.Ip, max_split, false) : LinearPlan{};
+            if (dp.kernel != LK_NONE) {
                 // (the next layer's QKV projection takes the partial sums if its kernel can; the last layer's final norm wants the vector)
                 const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
-                const bool next_takes = l + 1 < D.L && (gemm_h4_plan(T, nq, D.h, EPI_QKV_ROPE) > 0 || (tune(TK_GEMM_SKF) >= 2 && gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) > 0) ||
-                                                        gemm_takes_rs_parts(dt, T, nq, D.h, EPI_F32, std::min(tune(TK_QKV_SPLIT), qkv_split_cap(T))));
-                FL_TRY(linear_resid(L, sh, sc, ly.wd, sc.act, sh.Ip, l + 1 < D.L ? sh.layers[l + 1].ln1 : sh.norm, next_takes));
+                const bool qkv_parts = l + 1 < D.L && plan_qkv_rope(dt, T, nq, D.h, D.d, D.d * sh.Hkvs, m->tp, qkv_split(T)).reads_rs_parts;
+                FL_TRY(linear_resid(L, sc, dp, ly.wd, sc.act, sh.Ip, l + 1 < D.L ? sh.layers[l + 1].ln1 : sh.norm, qkv_parts));
                 norm_done = true;
             } else {
                 FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
@@ -1723,7 +1709,7 @@ static int enqueue_batch_step_unfused(Batch *b) {
     // the two wide projections (gate/up, lm_head: thousands of 16-row units) stream fastest through the LDS-DMA ring kernel;
     // the narrow ones (QKV, o_proj, down_proj: one or two units per CU) through K slices of the short-prompt GEMM
     auto wide = [&](const void *W, void *out, int64_t N, int epi) -> int {
-        if (!b->dma) return launch_linear(L, dt, W, sc.xn, nullptr, out, T, N, D.h, epi, sc.inv_rms);
+        if (!b->dma) return launch_linear(L, dt, W, sc.xn, nullptr, out, T, N, D.h, epi, sc.inv_rms, 1, nullptr, true);
         GemvBatchArgs ga;
         ga.W = W; ga.x = sc.xn; ga.x_scale = sc.inv_rms; ga.out = out; ga.N = (int)N; ga.K = (int)D.h; ga.epi = epi; ga.pro = PRO_X; ga.B = B; ga.nks = 1;
         return launch_gemv_dma(L, ga);
@@ -1754,13 +1740,13 @@ static int enqueue_batch_step_unfused(Batch *b) {
     // row scales from the partial sums -- where every projection of the model has a plan there; otherwise the eight-launch layer below
     const bool tpr = m->tp > 1;                                        // a rank of a multi-process group: all-reduce behind o_proj / down_proj, gathered logits
     const int ks_q = dt == FL_DTYPE_BF16 && sc.rs_part && !tpr && !ps && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
-    const int ks_o = ks_q ? gemm_skf_plan(T, D.h, sh.Hs * D.d, EPI_RESID) : 0, ks_d = ks_o ? gemm_skf_plan(T, D.h, sh.Ip, EPI_RESID) : 0;
-    if (ks_q && ks_o && ks_d && gemm_skf_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP) > 0 && tune(TK_GEMM_RESID)) {
+    const LinearPlan po = plan_resid(dt, T, D.h, sh.Hs * D.d, 1, true), pd = plan_resid(dt, T, D.h, sh.Ip, 1, true);
+    if (ks_q && po.kernel == LK_SKF && pd.kernel == LK_SKF && gemm_skf_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP) > 0) {
         const int np = gemm_resid_partials(D.h);
-        auto resid = [&](const void *W, const void *x, int64_t K, const float *next_w, int ks) -> int {
+        auto resid = [&](const LinearPlan &p, const void *W, const void *x, int64_t K, const float *next_w) -> int {
             ResidEpi re;
             re.h = sc.x_res; re.w = next_w; re.xn = sc.xn; re.part = sc.rs_part; re.np = np;
-            return launch_gemm_skf(L, W, x, nullptr, nullptr, T, D.h, K, EPI_RESID, nullptr, ks, &re);
+            return launch_plan(L, p, dt, W, x, nullptr, nullptr, T, D.h, K, EPI_RESID, nullptr, &re);
         };
         const RsParts parts{sc.rs_part, np, D.eps, 1.0f / (float)D.h};
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, nullptr, sh.layers[0].ln1, D.eps, sc.xn, sc.inv_rms, T, D.h, 1, slab));
@@ -1775,16 +1761,16 @@ static int enqueue_batch_step_unfused(Batch *b) {
             L.rsp = RsParts{};
             FL_TRY(launch_attn_decode_mfma_batch(L, sc.q, b->seqs_dev, B, b->max_nsplit, (size_t)l * sh.Hkvs * D.d, sc.ao, sh.Hs, sh.Hkvs,
                                                  D.d, D.scale, 0.0));
-            FL_TRY(resid(ly.wo, sc.ao, sh.Hs * D.d, ly.ln2, ks_o));
+            FL_TRY(resid(po, ly.wo, sc.ao, sh.Hs * D.d, ly.ln2));
             if (b->dma) {                                                // (eight rows at most: the LDS-DMA ring kernel streams gate/up fastest, and takes a vector)
                 FL_TRY(launch_rms_finalize(L, sc.rs_part, np, D.eps, sc.inv_rms, T, D.h));
                 FL_TRY(wide(ly.wgu, sc.act, 2 * sh.Ip, EPI_GATEUP));
             } else {
                 L.rsp = parts;
-                FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
+                FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms, 1, nullptr, true));
                 L.rsp = RsParts{};
             }
-            FL_TRY(resid(ly.wd, sc.act, sh.Ip, l + 1 < D.L ? sh.layers[l + 1].ln1 : sh.norm, ks_d));
+            FL_TRY(resid(pd, ly.wd, sc.act, sh.Ip, l + 1 < D.L ? sh.layers[l + 1].ln1 : sh.norm));
         }
         FL_TRY(launch_rms_finalize(L, sc.rs_part, np, D.eps, sc.inv_rms, T, D.h));
         FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
@@ -1798,26 +1784,26 @@ static int enqueue_batch_step_unfused(Batch *b) {
         int qkv_slabs = 1;
         if (b->plain) {
             // plain cache layout (fp32 models; bf16 outside the MFMA attention's head shapes): the batch kernels' plain forms
-            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms));
+            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, 1, nullptr, true));
             FL_TRY(launch_rope_kv_batch(L, sc.qkv, b->seqs_dev, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, (size_t)l * sh.Hkvs * D.d, B, sh.Hs,
                                         sh.Hkvs, D.d, 1, ly.bqkv, dt, false));
             FL_TRY(launch_attn_decode_batch(L, dt, sc.q, b->seqs_dev, B, b->max_nsplit, (size_t)l * sh.Hkvs * D.d, sc.ao, sh.Hs, sh.Hkvs, D.d, D.scale));
         } else if (ps) {
-            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms));
+            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, 1, nullptr, true));
             FL_TRY(rope_attn_per_seq(l, ly.bqkv));
         } else {
-            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs));
+            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, true));
             FL_TRY(launch_rope_kv_batch(L, sc.qkv, b->seqs_dev, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, (size_t)l * sh.Hkvs * D.d, B, sh.Hs,
                                         sh.Hkvs, D.d, qkv_slabs, ly.bqkv));
             FL_TRY(launch_attn_decode_mfma_batch(L, sc.q, b->seqs_dev, B, b->max_nsplit, (size_t)l * sh.Hkvs * D.d, sc.ao, sh.Hs, sh.Hkvs,
                                                  D.d, D.scale, 0.0));
         }
         // (a rank's row-parallel outputs: complete, no slabs -- the all-reduce wants the sum; sums in rank order on every rank)
-        FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab));
+        FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
         FL_TRY(wide(ly.wgu, sc.act, 2 * sh.Ip, EPI_GATEUP));
-        FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab));
+        FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
     }
     FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
