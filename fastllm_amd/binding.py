@@ -15,6 +15,8 @@ F32, BF16, F16 = 0, 1, 2
 TP_NONE, TP_SINGLE_PROCESS, TP_MULTI_PROCESS, TP_EMULATED = 0, 1, 2, 3
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
+WEIGHTS_COMPUTE_DTYPE, WEIGHTS_E4M3_ROW = 0, 1
+DECODE_WEIGHTS = {None: WEIGHTS_COMPUTE_DTYPE, "compute": WEIGHTS_COMPUTE_DTYPE, "e4m3": WEIGHTS_E4M3_ROW}
 
 
 class FastLLMError(RuntimeError):
@@ -45,7 +47,11 @@ class FlModelInfo(C.Structure):
     _fields_ = [("cfg", FlConfig), ("head_dim", C.c_int64), ("compute_dtype", C.c_int32), ("tp_size", C.c_int32),
                 ("weight_bytes_per_token", C.c_int64), ("kv_bytes_per_position", C.c_int64),
                 ("hbm_bytes_allocated", C.c_int64), ("small_collectives", C.c_int32), ("fused_all_reduce", C.c_int32),
-                ("rccl_ranks", C.c_int32), ("_reserved", C.c_int32)]
+                ("rccl_ranks", C.c_int32), ("decode_weights", C.c_int32)]
+
+
+class FlModelOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("decode_weights", C.c_int32), ("_reserved", C.c_int64 * 3)]
 
 
 class FlSampling(C.Structure):
@@ -75,6 +81,8 @@ def lib():
         L.fl_comm_ipc_export.argtypes = [vp, vp]
         L.fl_comm_ipc_connect.argtypes = [vp, vp]
         L.fl_model_create.argtypes = [C.POINTER(FlConfig), C.POINTER(FlTensor), sz, C.c_int32, C.POINTER(FlParallel), C.POINTER(vp)]
+        L.fl_model_create_opts.argtypes = [C.POINTER(FlConfig), C.POINTER(FlTensor), sz, C.c_int32, C.POINTER(FlParallel),
+                                           C.POINTER(FlModelOptions), C.POINTER(vp)]
         L.fl_model_retain.argtypes = [vp]
         L.fl_model_retain.restype = None
         L.fl_model_release.argtypes = [vp]
@@ -112,6 +120,8 @@ def lib():
         L.fl_comm_selftest.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32)]
         L.fl_op_linear.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32,
                                    C.POINTER(C.c_double)]
+        L.fl_op_quantize_rows.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp, vp]
+        L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         _LIB = L
     return _LIB
 
@@ -182,10 +192,12 @@ def _np_dtype_code(a):
 
 class Model:
     """fl_model handle.  tensors: dict name -> numpy array (float32 / float16 / uint16 bf16 bits), or
-    name -> (device_ptr, dtype_code, shape, device_ordinal) for tensors already in HBM."""
+    name -> (device_ptr, dtype_code, shape, device_ordinal) for tensors already in HBM.
+    decode_weights: None / "compute" (fl_model_create) or "e4m3" (FL_WEIGHTS_E4M3_ROW: the decode step streams FP8 weights; an int
+    is passed through as the fl_weight_format value)."""
 
     def __init__(self, cfg, tensors, dtype="bf16", tp_mode=TP_NONE, tp_size=1, tp_rank=0, device_ids=None,
-                 unique_id=None):
+                 unique_id=None, decode_weights=None):
         L = lib()
         self.cfg = dict(cfg)
         self.V = cfg["vocab_size"]
@@ -215,7 +227,14 @@ class Model:
             par.unique_id = C.cast(uid, C.c_void_p)
         c = make_config(cfg)
         h = C.c_void_p()
-        _check(L.fl_model_create(C.byref(c), arr, len(tensors), BF16 if dtype == "bf16" else F32, C.byref(par), C.byref(h)))
+        code = BF16 if dtype == "bf16" else F32
+        if decode_weights is None:
+            _check(L.fl_model_create(C.byref(c), arr, len(tensors), code, C.byref(par), C.byref(h)))
+        else:
+            opts = FlModelOptions()
+            opts.struct_size = C.sizeof(FlModelOptions)
+            opts.decode_weights = decode_weights if isinstance(decode_weights, int) else DECODE_WEIGHTS[decode_weights]
+            _check(L.fl_model_create_opts(C.byref(c), arr, len(tensors), code, C.byref(par), C.byref(opts), C.byref(h)))
         self._h = h
 
     def info(self):
@@ -436,4 +455,32 @@ def op_linear(x, w, bias=None, epilogue=0, iters=0):
     ms = C.c_double(0.0)
     _check(lib().fl_op_linear(x.ctypes.data, w.ctypes.data, b.ctypes.data if b is not None else None, T, N, K,
                               _np_dtype_code(x), epilogue, y.ctypes.data, iters, C.byref(ms)))
+    return (y, ms.value) if iters else y
+
+
+
+def op_quantize_rows(w):
+    """The FP8 row quantiser (device kernel) on a host matrix w [N,K], float32 or uint16 (bf16 bits): returns (q uint8 [N,K] of
+    e4m3fn codes, s float32 [N] power-of-two row scales)."""
+    w = np.ascontiguousarray(w)
+    N, K = w.shape
+    q = np.empty((N, K), dtype=np.uint8)
+    s = np.empty(N, dtype=np.float32)
+    _check(lib().fl_op_quantize_rows(w.ctypes.data, _np_dtype_code(w), N, K, q.ctypes.data, s.ctypes.data))
+    return q, s
+
+
+def op_gemv_w8(x, q, s, bias=None, epilogue=0, iters=0):
+    """y[N] = s * (q . x) (+bias) through the FP8 decode weight stream.  x [K] uint16 (bf16 bits), q [N,K] uint8 (e4m3fn), s [N]
+    float32; epilogue 1: rows are gate | up in HF order, y is [N/2]."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    N, K = q.shape
+    assert x.shape == (K,) and s.shape == (N,)
+    y = np.empty(N // 2 if epilogue == 1 else N, dtype=np.float32)
+    b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_gemv_w8(x.ctypes.data, q.ctypes.data, s.ctypes.data, b.ctypes.data if b is not None else None, N, K,
+                               epilogue, y.ctypes.data, iters, C.byref(ms)))
     return (y, ms.value) if iters else y

@@ -84,7 +84,19 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
         if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_model_create: null out");
         *out = nullptr;
         Model *m = nullptr;
-        int rc = model_create(cfg, tensors, n_tensors, compute_dtype, par, &m);
+        int rc = model_create(cfg, tensors, n_tensors, compute_dtype, par, nullptr, &m);
+        if (rc == FL_OK) *out = reinterpret_cast<fl_model *>(m);
+        return rc;
+    });
+}
+
+int fl_model_create_opts(const fl_config *cfg, const fl_tensor *tensors, size_t n_tensors, int32_t compute_dtype,
+                         const fl_parallel *par, const fl_model_options *opts, fl_model **out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_model_create_opts: null out");
+        *out = nullptr;
+        Model *m = nullptr;
+        int rc = model_create(cfg, tensors, n_tensors, compute_dtype, par, opts, &m);
         if (rc == FL_OK) *out = reinterpret_cast<fl_model *>(m);
         return rc;
     });
@@ -117,6 +129,13 @@ int fl_model_get_info(const fl_model *m, fl_model_info *out) {
         int64_t per_layer = 2 * D.h * D.h + 2 * D.Hkv * D.dm * D.h + 3 * D.h * D.inter;
         int64_t small = 2 * D.h + (D.qkv_bias ? D.h + 2 * D.Hkv * D.dm : 0);
         out->weight_bytes_per_token = es * (D.L * (per_layer + small) + D.h + D.V * D.h);
+        out->decode_weights = mm->decode_weights;
+        if (mm->decode_weights == FL_WEIGHTS_E4M3_ROW) {
+            // what the FP8 step streams: 1 byte per projection weight and one fp32 scale per projection row; the embedding row,
+            // norms and biases as before
+            const int64_t rows = D.h + 2 * D.Hkv * D.dm + D.h + 2 * D.inter + D.h;      // q | k, v | o | gate, up | down
+            out->weight_bytes_per_token = D.L * (per_layer + 4 * rows + es * small) + es * D.h + D.V * D.h + 4 * D.V;
+        }
         out->kv_bytes_per_position = es * D.L * D.Hkv * D.dm * 2;
         out->hbm_bytes_allocated = mm->hbm_bytes;
         // + the GEMM workspaces of each shard's streams (first long prompt).  The workspace tables are keyed by (current device,
@@ -476,6 +495,116 @@ int fl_op_linear(const void *x, const void *w, const float *bias, int64_t T, int
                     for (size_t i = 0; i < (size_t)T * Ny; i++) y[i] += tmp[i];
                 }
             }
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint8_t *q_out, float *s_out) {
+    return guarded([&]() -> int {
+        if (!w || !q_out || !s_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+        if (N <= 0 || K <= 0 || K % 4 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (K must be a multiple of 4)");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        struct Bufs { void *w = 0; uint8_t *q = 0; float *s = 0; hipStream_t st = 0;
+                      ~Bufs() { (void)hipFree(w); (void)hipFree(q); (void)hipFree(s); if (st) (void)hipStreamDestroy(st); } } B;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+        FL_HIP(hipStreamCreate(&B.st));
+        FL_HIP(hipMalloc(&B.w, (size_t)N * K * es));
+        FL_HIP(hipMalloc((void **)&B.q, (size_t)N * K));
+        FL_HIP(hipMalloc((void **)&B.s, (size_t)N * 4));
+        FL_HIP(hipMemcpy(B.w, w, (size_t)N * K * es, hipMemcpyHostToDevice));
+        Launcher L; L.stream = B.st;
+        FL_TRY(launch_quantize_rows(L, dtype, B.w, N, K, B.q, B.s, nullptr));
+        FL_HIP(hipStreamSynchronize(B.st));
+        FL_HIP(hipMemcpy(q_out, B.q, (size_t)N * K, hipMemcpyDeviceToHost));
+        FL_HIP(hipMemcpy(s_out, B.s, (size_t)N * 4, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
+                  float *y, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!x || !q || !s || !y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (N <= 0 || K <= 0 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape");
+        if (epilogue != EPI_F32 && epilogue != EPI_GATEUP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "epilogue must be 0 or 1");
+        if (epilogue == EPI_GATEUP && ((N % 2) || bias)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count and takes no bias");
+        if (!gemv_w8_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "K must be a multiple of 16 (a lane of the FP8 stream loads 16 weights), at most 81792");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        const int64_t I = N / 2, Ip = (I + 15) / 16 * 16;
+        const int64_t Nw = epilogue == EPI_GATEUP ? 2 * Ip : N;          // rows of the device matrix
+        const int64_t Ny = epilogue == EPI_GATEUP ? Ip : N;
+        struct Bufs { void *x = 0, *y = 0; uint8_t *q = 0, *qs = 0; float *s = 0, *ss = 0, *b = 0; hipStream_t st = 0; hipEvent_t e0 = 0, e1 = 0;
+                      std::vector<uint8_t *> copies;
+                      ~Bufs() { (void)hipFree(x); (void)hipFree(y); (void)hipFree(q); (void)hipFree(qs); (void)hipFree(s); (void)hipFree(ss); (void)hipFree(b);
+                                for (size_t i = 1; i < copies.size(); i++) (void)hipFree(copies[i]);
+                                if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+                                if (e0) (void)hipEventDestroy(e0);
+                                if (e1) (void)hipEventDestroy(e1); } } B;
+        FL_HIP(hipStreamCreate(&B.st));
+        FL_HIP(hipMalloc(&B.x, (size_t)K * 2));
+        FL_HIP(hipMalloc((void **)&B.q, (size_t)Nw * K));
+        FL_HIP(hipMalloc((void **)&B.s, (size_t)Nw * 4));
+        const size_t ybytes = (size_t)Ny * (epilogue == EPI_GATEUP ? 2 : 4);
+        FL_HIP(hipMalloc(&B.y, ybytes));
+        FL_HIP(hipMemcpy(B.x, x, (size_t)K * 2, hipMemcpyHostToDevice));
+        Launcher L; L.stream = B.st;
+        if (epilogue == EPI_GATEUP) {
+            FL_HIP(hipMalloc((void **)&B.qs, (size_t)N * K));
+            FL_HIP(hipMalloc((void **)&B.ss, (size_t)N * 4));
+            FL_HIP(hipMemcpy(B.qs, q, (size_t)N * K, hipMemcpyHostToDevice));
+            FL_HIP(hipMemcpy(B.ss, s, (size_t)N * 4, hipMemcpyHostToDevice));
+            FL_HIP(hipMemsetAsync(B.q, 0, (size_t)Nw * K, B.st));
+            FL_HIP(hipMemsetAsync(B.s, 0, (size_t)Nw * 4, B.st));
+            FL_TRY(launch_w8_gateup_layout(L, B.qs, B.ss, I, K, B.q, B.s));
+        } else {
+            FL_HIP(hipMemcpy(B.q, q, (size_t)N * K, hipMemcpyHostToDevice));
+            FL_HIP(hipMemcpy(B.s, s, (size_t)N * 4, hipMemcpyHostToDevice));
+            if (bias) {
+                FL_HIP(hipMalloc((void **)&B.b, (size_t)N * 4));
+                FL_HIP(hipMemcpy(B.b, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+            }
+        }
+        auto run = [&](const uint8_t *qp) -> int {
+            GemvArgs a;
+            a.W = qp; a.x = B.x; a.bias = B.b; a.out = B.y; a.N = (int)Nw; a.K = (int)K; a.epi = epilogue; a.pro = PRO_X;
+            return launch_gemv_w8(L, a, B.s);
+        };
+        FL_TRY(run(B.q));
+        FL_HIP(hipStreamSynchronize(B.st));
+        if (iters > 0 && ms_out) {
+            // rotate over copies of q that together exceed the 256 MiB Infinity Cache (see fl_op_linear)
+            const size_t wbytes = (size_t)Nw * K;
+            const int hot = tune(TK_OP_HOT);
+            const int ncopy = hot > 0 ? hot : (int)std::min<size_t>(24, std::max<size_t>(1, (640u << 20) / wbytes + 1));
+            B.copies.push_back(B.q);
+            for (int c = 1; c < ncopy; c++) {
+                uint8_t *p = nullptr;
+                FL_HIP(hipMalloc((void **)&p, wbytes));
+                B.copies.push_back(p);
+                FL_HIP(hipMemcpyAsync(p, B.q, wbytes, hipMemcpyDeviceToDevice, B.st));
+            }
+            for (int c = 0; c < ncopy; c++) FL_TRY(run(B.copies[c]));   // warm
+            FL_HIP(hipStreamSynchronize(B.st));
+            FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+            FL_HIP(hipEventRecord(B.e0, B.st));
+            for (int i = 0; i < iters; i++) FL_TRY(run(B.copies[i % ncopy]));
+            FL_HIP(hipEventRecord(B.e1, B.st));
+            FL_HIP(hipEventSynchronize(B.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+            *ms_out = ms / iters;
+        }
+        if (epilogue == EPI_GATEUP) {
+            std::unique_ptr<bf16_t[]> tmp(new bf16_t[(size_t)Ny]);
+            FL_HIP(hipMemcpy(tmp.get(), B.y, ybytes, hipMemcpyDeviceToHost));
+            for (int64_t j = 0; j < I; j++) y[j] = bf16_bits_to_float(tmp[(size_t)j]);
+        } else {
+            FL_HIP(hipMemcpy(y, B.y, ybytes, hipMemcpyDeviceToHost));
         }
         return FL_OK;
     });

@@ -101,6 +101,18 @@ bool gemv_leaves_candidates(int dtype, const GemvArgs &a);   // the grid launch_
 bool gemv_norm_supported(int dtype, int64_t N, int64_t K);
 void gemv_set_tuning(int blocks, int waves);   // fl_tune "gemv_blocks" / "gemv_waves": force the grid / waves per workgroup (0 automatic, -1 keep)
 
+// ---- FP8 weights (k_gemv_w8.hip): W' = s[row] * q, q e4m3fn, s a power of two per row (FL_WEIGHTS_E4M3_ROW) ------------
+// the decode stream over them: GemvArgs as for launch_gemv with W = the e4m3 bytes [N,K], x / caches / out bf16 model types;
+// no fused all-reduce (ll) and no sliced delta
+int launch_gemv_w8(Launcher &L, const GemvArgs &a, const float *wscale /* [N] */);
+bool gemv_w8_supported(int64_t N, int64_t K);          // K a multiple of 16 (a lane's 16-byte load)
+bool gemv_w8_norm_supported(int64_t N, int64_t K);
+bool gemv_w8_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgMax candidate buffer
+// src [N,K] bf16 / fp32 -> q [N,K], s [N] and (img non-null; may be src when that is bf16) the bf16 image s * q
+int launch_quantize_rows(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, float *s, void *img_bf16);
+// rows in HF order (gate [0, I) | up [I, 2 I)) -> the 16-interleaved decode layout (test hook)
+int launch_w8_gateup_layout(Launcher &L, const uint8_t *q, const float *s, int64_t I, int64_t K, uint8_t *qo, float *so);
+
 // ---- the persistent decode engine (k_engine.hip): a chain of projections in one launch ---------------------------
 constexpr int ENG_GATHER_WAVES = 4, ENG_STREAM_WAVES = 8, ENG_MAX_OPS = 4;
 enum { ENG_IN_X = 0, ENG_IN_NORM = 1, ENG_IN_ACT = 2 };                 // plain bf16 vector of the previous launch | fp32 delta edge + residual + RMSNorm weight | packed silu(g)*u edge

@@ -31,6 +31,10 @@ struct LayerW {
     void *wgu = nullptr;         // [2*Ip, h] 16-interleaved gate/up rows
     void *wd = nullptr;          // [h, Ip]
     float *ln1 = nullptr, *ln2 = nullptr;
+    // FL_WEIGHTS_E4M3_ROW: the e4m3 bytes (same shape and row layout) and the per-row scales of the four matrices; the pointers
+    // above then hold the bf16 image s * q
+    uint8_t *wqkv8 = nullptr, *wo8 = nullptr, *wgu8 = nullptr, *wd8 = nullptr;
+    float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
 };
 
 struct Scratch {                 // activations of one forward chunk on one shard
@@ -80,6 +84,8 @@ struct Shard {
     std::vector<LayerW> layers;
     float *norm = nullptr;
     void *lm_head = nullptr;     // [Vs,h]
+    uint8_t *lm_head8 = nullptr; // FL_WEIGHTS_E4M3_ROW: its e4m3 bytes and row scales (lm_head is then the bf16 image)
+    float *lm_head_s = nullptr;
     float *cos_tab = nullptr, *sin_tab = nullptr;   // [max_pos][d/2]
     Scratch dec, pre;
     float *logits_local = nullptr;   // [Vs]
@@ -110,6 +116,7 @@ struct Model {
     uint32_t *host_tokens = nullptr;
     bool use_graph = true;
     bool fused_decode = true;    // norm / RoPE / KV-append fused into the GEMV kernels
+    int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;   // FL_WEIGHTS_E4M3_ROW: the decode step streams e4m3 weights (k_gemv_w8.hip)
     int engine = -1;             // persistent decode engine (k_engine.hip): 0 off, 1 on, -1 automatic
     int fuse_oproj = 0;          // decode attention + o_proj in one launch (k_attn_oproj.hip): 0 never (default), 1 wherever it fits, -1 where it pays most
     StepState *host_state = nullptr;   // pinned: device step state read back for the error word
@@ -194,7 +201,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
                       const fl_sampling *sampling_each, uint32_t *tokens_out, size_t *n_out);
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
-                 const fl_parallel *par, Model **out);
+                 const fl_parallel *par, const fl_model_options *opts, Model **out);
 int cache_create(Model *m, size_t max_seq, Cache **out);
 // FL_TP_MULTI_PROCESS: export this rank's inbox / map the peers' (handles: tp x FL_IPC_HANDLE_BYTES in rank order)
 int comm_ipc_export(Model *m, void *handle_out);

@@ -490,6 +490,33 @@ static int build_weights(Builder &B) {
     return FL_OK;
 }
 
+// FL_WEIGHTS_E4M3_ROW: every projection matrix (in its final decode layout: a row scale follows its row through every row
+// permutation) gets its e4m3 bytes and row scales, and the bf16 matrix itself becomes the image s * q -- what prefill, batches
+// and every other bf16 kernel then read.  Both images stay: 1.5x a bf16 model's weight memory.
+static int quantize_weights(Model *m) {
+    const Dims &D = m->D;
+    for (auto &sh : m->shards) {
+        FL_HIP(hipSetDevice(sh.device));
+        Launcher L; L.stream = sh.stream;
+        auto one = [&](void *w, int64_t N, int64_t K, uint8_t **q, float **s) -> int {
+            if (!gemv_w8_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW: a %lld x %lld projection (K must be a multiple of 16)", (long long)N, (long long)K);
+            FL_TRY(dev_alloc(sh.allocs, (void **)q, (size_t)N * K, &m->hbm_bytes));
+            FL_TRY(dev_alloc(sh.allocs, (void **)s, (size_t)N * 4, &m->hbm_bytes));
+            return launch_quantize_rows(L, FL_DTYPE_BF16, w, N, K, *q, *s, w);
+        };
+        const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
+        for (auto &ly : sh.layers) {
+            FL_TRY(one(ly.wqkv, nq, D.h, &ly.wqkv8, &ly.sqkv));
+            FL_TRY(one(ly.wo, D.h, sh.Hs * D.d, &ly.wo8, &ly.so));
+            FL_TRY(one(ly.wgu, 2 * sh.Ip, D.h, &ly.wgu8, &ly.sgu));
+            FL_TRY(one(ly.wd, D.h, sh.Ip, &ly.wd8, &ly.sd));
+        }
+        FL_TRY(one(sh.lm_head, sh.Vs, D.h, &sh.lm_head8, &sh.lm_head_s));
+        FL_HIP(hipStreamSynchronize(sh.stream));
+    }
+    return FL_OK;
+}
+
 // RoPE tables (App. A.4): inv_freq[j] = 1 / theta^(2j/d) in fp32; angle = p * inv_freq[j] (fp32
 // product); cos/sin in fp32.  Built once on the host, one copy per shard.
 static int build_rope(Model *m) {
@@ -583,7 +610,7 @@ static int grow_prefill_scratch(Model *m, Shard &sh, int64_t T) {
 }
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
-                 const fl_parallel *par, Model **out) {
+                 const fl_parallel *par, const fl_model_options *opts, Model **out) {
     if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null out pointer");
     if (!tensors && n) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null tensors");
     if (compute_dtype != FL_DTYPE_BF16 && compute_dtype != FL_DTYPE_F32)
@@ -593,6 +620,22 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
     if (D.h % 8) FL_FAIL(FL_ERR_UNSUPPORTED, "hidden_size must be a multiple of 8 (16-byte rows)");
     if (D.dm > 128) FL_FAIL(FL_ERR_UNSUPPORTED, "head_dim %lld not supported (even values up to 128)", (long long)D.dm);
     if (D.max_pos > (1 << 20)) D.max_pos = 1 << 20;
+    // options (fl_model_create_opts): everything that needs no device is decided here, before the device probe
+    int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;
+    if (opts) {
+        if (opts->struct_size != sizeof(fl_model_options))
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_model_options.struct_size is %u, this library's is %zu", opts->struct_size, sizeof(fl_model_options));
+        decode_weights = opts->decode_weights;
+        if (decode_weights != FL_WEIGHTS_COMPUTE_DTYPE && decode_weights != FL_WEIGHTS_E4M3_ROW)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "unknown decode_weights %d (fl_weight_format)", decode_weights);
+    }
+    if (decode_weights == FL_WEIGHTS_E4M3_ROW) {
+        if (compute_dtype != FL_DTYPE_BF16) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW needs compute dtype BF16 (s * q is exact in bf16, the fp32 mode has no use for it)");
+        if (par && par->mode != FL_TP_NONE && par->tp_size > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW does not support tensor parallelism (tp_size %d)", par->tp_size);
+        // a lane of the FP8 stream loads 16 weights: every projection's K (hidden_size, heads x padded head_dim, intermediate_size
+        // padded to 16) is a multiple of 16 once hidden_size is
+        if (D.h % 16) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW needs hidden_size to be a multiple of 16 (it is %lld)", (long long)D.h);
+    }
     debug_inject("model_create");
 
     int ndev = 0;
@@ -616,6 +659,9 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
     m->cfg_resolved.max_position_embeddings = D.max_pos; m->cfg_resolved.sliding_window = D.window;
     m->use_graph = tune(TK_GRAPH) != 0;                 // (-1 = automatic: on)
     m->fused_decode = tune(TK_FUSED) != 0 && gemv_norm_supported(compute_dtype, 1, D.h);
+    m->decode_weights = decode_weights;
+    if (decode_weights == FL_WEIGHTS_E4M3_ROW && (!m->fused_decode || !gemv_w8_norm_supported(1, D.h)))
+        FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW needs the fused decode step (FL_FUSED=0, or hidden_size %lld above 6144)", (long long)D.h);
 
     auto dev_of = [&](int i) -> int { return (P.device_ids && i < P.n_device_ids) ? P.device_ids[i] : i; };
     int nlocal = 1;
@@ -658,6 +704,7 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
         for (auto &sh : m->shards) { FL_HIP(hipSetDevice(sh.device)); FL_HIP(hipDeviceSynchronize()); }
     }
     FL_TRY(build_weights(B));
+    if (decode_weights == FL_WEIGHTS_E4M3_ROW) FL_TRY(quantize_weights(m.get()));
     FL_TRY(build_rope(m.get()));
     for (auto &sh : m->shards) {
         FL_HIP(hipSetDevice(sh.device));
@@ -808,12 +855,14 @@ int cache_create(Model *m, size_t max_seq, Cache **out) {
             // (4 kv heads: groups of 64 over two XCDs) and long contexts are faster as two launches
             const bool pays = fits && cus / m->shards[0].Hkvs <= 32 && ra <= 16;
             c->fuse_oproj = m->fuse_oproj > 0 ? fits : (m->fuse_oproj < 0 ? pays : false);
+            if (m->decode_weights != FL_WEIGHTS_COMPUTE_DTYPE) c->fuse_oproj = false;     // (that launch streams the bf16 wo itself)
             c->ao_nsplit = ns8; c->ao_waves = aw;
         }
     }
     // short caches: attention replicated in every workgroup of the o_proj launch (k_attn_rep.hip): one launch and one dependent
     // step fewer per layer; FL_ATTN_REP=0 keeps the two launches
     c->rep_attn = tune(TK_ATTN_REP) != 0 && m->fused_decode && c->v_transposed && !c->fuse_oproj && m->dtype == FL_DTYPE_BF16 &&
+                  m->decode_weights == FL_WEIGHTS_COMPUTE_DTYPE &&       // (k_attn_rep.hip streams the bf16 wo itself)
                   attn_oproj_rep_supported(m->shards[0].Hs, m->shards[0].Hkvs, D.d, D.h, (int64_t)c->seq_alloc, tune(TK_ATTN_REP) == 2);
     c->shards.resize(m->shards.size());
     for (size_t i = 0; i < m->shards.size(); i++) {
@@ -960,6 +1009,7 @@ static bool fused_all_reduce(Model *m, Cache *c) { return !c->fuse_oproj && fuse
 static bool engine_usable(Model *m, Cache *c) {
     const int want = m->engine;
     if (want == 0 || m->shards.size() != 1 || m->tp != 1 || m->dtype != FL_DTYPE_BF16 || !m->fused_decode || c->fuse_oproj || !c->v_transposed) return false;
+    if (m->decode_weights != FL_WEIGHTS_COMPUTE_DTYPE) return false;
     Shard &sh = m->shards[0];
     if (!sh.eng_epoch || sh.pc.shares_device || m->D.L < 1) return false;
     if (!gemv_norm_supported(m->dtype, (sh.Hs + 2 * sh.Hkvs) * m->D.d, m->D.h)) return false;
@@ -1031,6 +1081,18 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
     const int dt = m->dtype;
     const size_t ns = m->shards.size();
     const bool far = fused_all_reduce(m, c);
+    // FL_WEIGHTS_E4M3_ROW (one shard, bf16: model_create): all six projections stream the e4m3 bytes (k_gemv_w8.hip)
+    const bool w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW;
+    auto gemv = [&](Launcher &L, GemvArgs &a, const uint8_t *q8, const float *s8) -> int {
+        if (!w8) return launch_gemv(L, dt, a);
+        a.W = q8;
+        return launch_gemv_w8(L, a, s8);
+    };
+    auto plain_w8 = [&](Launcher &L, const uint8_t *q8, const float *s8, const void *x, int64_t K, float *out) -> int {
+        GemvArgs a;
+        a.W = q8; a.x = x; a.out = out; a.N = (int)D.h; a.K = (int)K; a.epi = EPI_F32; a.pro = PRO_X;
+        return launch_gemv_w8(L, a, s8);
+    };
     // out = sum over ranks of W[h, K] . x  -- the row-parallel projection with the exchange in its epilogue
     auto row_parallel = [&](Launcher &L, Shard &sh, const void *W, const void *x, int64_t K, float *out, int slot) -> int {
         GemvArgs a;
@@ -1053,10 +1115,12 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             a.cos_tab = sh.cos_tab; a.sin_tab = sh.sin_tab; a.q_out = sc.q; a.k_cache = kc; a.v_cache = vc;
             a.H = (int)sh.Hs; a.Hkv = (int)sh.Hkvs; a.d = (int)D.d; a.max_seq = (int)c->seq_alloc; a.max_pos = (int)D.max_pos;
             a.v_ld = c->v_transposed ? (int)c->seq_alloc : 0;
-            FL_TRY(launch_gemv(L, dt, a));
+            FL_TRY(gemv(L, a, ly.wqkv8, ly.sqkv));
             AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, len_hint + 1};
-            as.prefetch = ly.wo; as.prefetch_bytes = D.h * sh.Hs * D.d * (int64_t)m->esize();   // o_proj's weights, while HBM idles under the attention
-            as.prefetch_chunk = gemv_owner_chunk(dt, D.h, sh.Hs * D.d); as.prefetch_row = sh.Hs * D.d * (int64_t)m->esize();
+            if (!w8) {
+                as.prefetch = ly.wo; as.prefetch_bytes = D.h * sh.Hs * D.d * (int64_t)m->esize();   // o_proj's weights, while HBM idles under the attention
+                as.prefetch_chunk = gemv_owner_chunk(dt, D.h, sh.Hs * D.d); as.prefetch_row = sh.Hs * D.d * (int64_t)m->esize();
+            }
             if (c->fuse_oproj) {
                 FL_TRY(launch_attn_oproj(L, sc.q, kc, vc, cs.st, cs.st, cs.ao_part, cs.heads_done + l * sh.Hkvs, c->ao_nsplit, c->ao_waves, len_hint + 1, ly.wo,
                                          sc.delta, sh.Hs, sh.Hkvs, D.d, D.h, (int64_t)c->seq_alloc, D.scale));
@@ -1069,7 +1133,8 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             } else {
                 if (c->v_transposed) FL_TRY(launch_attn_decode_mfma(L, sc.q, kc, vc, cs.st, sc.ao, as, sh.Hs, sh.Hkvs, D.d, (int64_t)c->seq_alloc, D.scale));
                 else FL_TRY(launch_attn_decode(L, dt, sc.q, kc, vc, cs.st, sc.ao, as, sh.Hs, sh.Hkvs, D.d, (int64_t)c->seq_alloc, D.scale));
-                if (far) FL_TRY(row_parallel(L, sh, ly.wo, sc.ao, sh.Hs * D.d, sc.delta, (int)(2 * l + 1)));
+                if (w8) FL_TRY(plain_w8(L, ly.wo8, ly.so, sc.ao, sh.Hs * D.d, sc.delta));
+                else if (far) FL_TRY(row_parallel(L, sh, ly.wo, sc.ao, sh.Hs * D.d, sc.delta, (int)(2 * l + 1)));
                 else FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, 1, D.h, sh.Hs * D.d, EPI_F32));
             }
         }
@@ -1082,8 +1147,9 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             a.W = ly.wgu; a.out = sc.act; a.N = (int)(2 * sh.Ip); a.K = (int)D.h; a.epi = EPI_GATEUP; a.pro = PRO_NORM;
             a.x_in = sc.x_res2; a.delta = sc.delta; a.norm_w = ly.ln2; a.eps = D.eps; a.x_out = sc.x_res; a.st = c->shards[i].st;
             if (c->fuse_oproj) a.delta_nslab = (int)sh.Hkvs;           // one partial vector per kv head
-            FL_TRY(launch_gemv(L, dt, a));
-            if (far) FL_TRY(row_parallel(L, sh, ly.wd, sc.act, sh.Ip, sc.delta, (int)(2 * l + 2)));
+            FL_TRY(gemv(L, a, ly.wgu8, ly.sgu));
+            if (w8) FL_TRY(plain_w8(L, ly.wd8, ly.sd, sc.act, sh.Ip, sc.delta));
+            else if (far) FL_TRY(row_parallel(L, sh, ly.wd, sc.act, sh.Ip, sc.delta, (int)(2 * l + 2)));
             else FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, 1, D.h, sh.Ip, EPI_F32));
         }
         if (!far) FL_TRY(all_reduce_delta(m, false, D.h));
@@ -1094,9 +1160,9 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
         Launcher L = make_launcher(m, sh);
         GemvArgs a;
         a.W = sh.lm_head; a.out = lm_head_out(m, sh); a.N = (int)sh.Vs; a.K = (int)D.h; a.epi = EPI_F32; a.pro = PRO_NORM;
-        if (!m->vocab_parallel && tune(TK_ARGMAX_FUSED) && gemv_leaves_candidates(dt, a)) { a.amax = sh.amax; sh.amax_valid = true; }   // token selection reads one candidate per workgroup
+        if (!m->vocab_parallel && tune(TK_ARGMAX_FUSED) && (w8 ? gemv_w8_leaves_candidates(a.N, a.K) : gemv_leaves_candidates(dt, a))) { a.amax = sh.amax; sh.amax_valid = true; }   // token selection reads one candidate per workgroup
         a.x_in = sc.x_res; a.delta = sc.delta; a.norm_w = sh.norm; a.eps = D.eps; a.st = c->shards[i].st;
-        FL_TRY(launch_gemv(L, dt, a));
+        FL_TRY(gemv(L, a, sh.lm_head8, sh.lm_head_s));
     }
     return gather_logits(m);
 }

@@ -60,6 +60,11 @@ enum class DType { F32 = FL_DTYPE_F32, BF16 = FL_DTYPE_BF16, F16 = FL_DTYPE_F16 
 struct Device {                               // candle_core::Device
     enum Kind { Cpu, Mi355x } kind = Cpu;
     std::vector<int32_t> ordinals;            // one GPU, or the TP group driven by this process
+    // load option (no counterpart in the reference): the weight format of the decode step.  FL_WEIGHTS_E4M3_ROW: FP8 weights with one
+    // power-of-two scale per row (bf16 compute, one GPU; 1.5x a bf16 model's weight memory) -- initialize_model then goes through
+    // fl_model_create_opts, and generate_ids / StreamBatcher run on the FP8 model unchanged
+    int32_t decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;
+    Device with_decode_weights(fl_weight_format f) const { Device d = *this; d.decode_weights = (int32_t)f; return d; }
     static Device cpu() { return Device{}; }
     static Device mi355x(int ordinal = 0) { Device d; d.kind = Mi355x; d.ordinals = {ordinal}; return d; }
     static Device mi355x_tp(std::vector<int32_t> ords) { Device d; d.kind = Mi355x; d.ordinals = std::move(ords); return d; }
@@ -264,7 +269,13 @@ inline std::shared_ptr<ModelHandle> create(const fl_config &cfg, const TensorMap
     par.tp_size = (int32_t)std::max<size_t>(1, device.ordinals.size());
     par.device_ids = device.ordinals.data(); par.n_device_ids = (int32_t)device.ordinals.size();
     fl_model *m = nullptr;
-    check(fl_model_create(&cfg, arr.data(), arr.size(), (int32_t)dtype, &par, &m), "Failed to initialize model");
+    if (device.decode_weights == FL_WEIGHTS_COMPUTE_DTYPE) {
+        check(fl_model_create(&cfg, arr.data(), arr.size(), (int32_t)dtype, &par, &m), "Failed to initialize model");
+    } else {
+        fl_model_options opts{};
+        opts.struct_size = (uint32_t)sizeof opts; opts.decode_weights = device.decode_weights;
+        check(fl_model_create_opts(&cfg, arr.data(), arr.size(), (int32_t)dtype, &par, &opts, &m), "Failed to initialize model");
+    }
     return std::make_shared<ModelHandle>(m);
 }
 

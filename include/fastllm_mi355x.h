@@ -141,6 +141,25 @@ int         fl_comm_unique_id(void *out /* FL_UNIQUE_ID_BYTES */);
 int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_tensors,
                     int32_t compute_dtype, const fl_parallel *par, fl_model **out);
 
+/* Weight format of the decode step (fl_model_create_opts).  FL_WEIGHTS_E4M3_ROW: the single-stream decode step (T = 1) reads its
+ * projection weights (q/k/v, o, gate/up, down, lm_head) as FP8: W'[n,k] = s[n] * q[n,k], q OCP e4m3fn, s[n] = 2^e one fp32 scale
+ * per output row, e the smallest integer with absmax(W[n,:]) / 2^e <= 448 (all-zero row: s = 1), q = RNE_e4m3(W / s).  s * q is
+ * exact in bf16, so the model IS the bf16 model whose weights are W': prompts (T > 1) and fl_batch_* steps run the bf16 kernels on
+ * a bf16 image of W', and every path sees the same weights.  Both images are kept: weight memory is 1.5x a bf16 model's -- this
+ * mode buys decode speed (half the bytes of the weight stream), not capacity.  Embedding and norm weights stay as they are.
+ * REFUSED: compute_dtype other than BF16, tp_size > 1 (any mode), a model whose fused decode step is off (FL_FUSED=0, hidden_size
+ * above 6144), hidden_size not a multiple of 16 -> FL_ERR_UNSUPPORTED; an unknown decode_weights or a struct_size that is not
+ * sizeof(fl_model_options) -> FL_ERR_BAD_ARGUMENT.  All but the fused-step one are decided before the device probe. */
+typedef enum fl_weight_format { FL_WEIGHTS_COMPUTE_DTYPE = 0, FL_WEIGHTS_E4M3_ROW = 1 } fl_weight_format;
+typedef struct fl_model_options {
+    uint32_t struct_size;           /* sizeof(fl_model_options) */
+    int32_t  decode_weights;        /* fl_weight_format */
+    int64_t  _reserved[3];          /* 0 */
+} fl_model_options;
+/* fl_model_create with options; opts == NULL is fl_model_create. */
+int fl_model_create_opts(const fl_config *cfg, const fl_tensor *tensors, size_t n_tensors, int32_t compute_dtype,
+                         const fl_parallel *par, const fl_model_options *opts, fl_model **out);
+
 /* FL_TP_MULTI_PROCESS: the decode step's two [h] fp32 all-reduces per layer and the logits all-gather
  * are one-shot pushes into inboxes that every rank maps from every peer's HBM over xGMI (new
  * capability; the reference is single-device, README.md:149).  A model created with a unique_id
@@ -160,13 +179,14 @@ typedef struct fl_model_info {
     int64_t head_dim;
     int32_t compute_dtype;
     int32_t tp_size;
-    int64_t weight_bytes_per_token; /* algorithmic HBM bytes a decode step reads from weights (whole model) */
+    int64_t weight_bytes_per_token; /* algorithmic HBM bytes a decode step reads from weights (whole model); FL_WEIGHTS_E4M3_ROW: what
+                                       that step really streams -- 1 byte per projection weight + 4 per projection row */
     int64_t kv_bytes_per_position;  /* K+V bytes one cached position adds to a decode step */
-    int64_t hbm_bytes_allocated;    /* this process, all shards */
+    int64_t hbm_bytes_allocated;    /* this process, all shards (FL_WEIGHTS_E4M3_ROW: the e4m3 bytes, the scales AND the bf16 image) */
     int32_t small_collectives;      /* decode collectives: 0 none (tp 1), 1 RCCL, 2 one-shot peer inboxes, 3 local (emulated) */
     int32_t fused_all_reduce;       /* 1: decode all-reduces ride in the o_proj / down_proj GEMV epilogues (no kernel of their own) */
     int32_t rccl_ranks;             /* ncclCommCount of this rank's RCCL communicator; 0: no communicator (tp 1, emulated, IPC-only groups) */
-    int32_t _reserved;
+    int32_t decode_weights;         /* fl_weight_format the decode step streams */
 } fl_model_info;
 int fl_model_get_info(const fl_model *m, fl_model_info *out);
 
@@ -308,6 +328,17 @@ int fl_tune(const char *key, int value);
  * up = rows [N/2,N); y is [T, N/2]).  iters > 0 with ms_out != NULL times `iters` launches. */
 int fl_op_linear(const void *x, const void *w, const float *bias, int64_t T, int64_t N, int64_t K,
                  int32_t dtype, int32_t epilogue, float *y, int32_t iters, double *ms_out);
+
+/* The FP8 row quantiser alone (unit tests): w host [N,K] of `dtype` (FL_DTYPE_F32 or FL_DTYPE_BF16), K a multiple of 4, through the
+ * device kernel -> q_out [N,K] e4m3fn bytes and s_out [N] (the format of fl_weight_format above). */
+int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint8_t *q_out, float *s_out);
+
+/* The FP8 decode weight stream alone (unit tests, micro-benchmarks): y[N] = s[n] * (q[n,:] . x) (+bias).  x host bf16 [K], q host
+ * e4m3fn [N,K], s host fp32 [N], K a multiple of 16 (else FL_ERR_UNSUPPORTED); y fp32.  epilogue as fl_op_linear: 0 none, 1
+ * silu-gate (q / s rows are gate/up in HF order, gate = rows [0,N/2); y is [N/2], the kernel's bf16 output widened).
+ * iters > 0 with ms_out != NULL times `iters` launches over rotating copies of q, as fl_op_linear does. */
+int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
+                  float *y, int32_t iters, double *ms_out);
 
 /* The token-selection kernel alone, for unit tests: `n_draws` successive selections from one host logits
  * vector (consuming successive words of the seeded stream; ArgMax when temperature < 1e-7). */

@@ -38,6 +38,10 @@ pub const FL_TP_SINGLE_PROCESS: i32 = 1;
 pub const FL_TP_MULTI_PROCESS: i32 = 2;
 pub const FL_TP_EMULATED: i32 = 3;
 
+// fl_weight_format: what the decode step streams (E4M3_ROW: e4m3fn weights with one power-of-two fp32 scale per output row)
+pub const FL_WEIGHTS_COMPUTE_DTYPE: i32 = 0;
+pub const FL_WEIGHTS_E4M3_ROW: i32 = 1;
+
 /// `fl_config`: the fields of the reference's ConfigFile / BaseModelConfig (config.rs:6-18).  0 in an optional field
 /// = absent from config.json = the reference's default.
 #[repr(C)]
@@ -94,7 +98,16 @@ pub struct fl_model_info {
     pub small_collectives: i32,
     pub fused_all_reduce: i32,
     pub rccl_ranks: i32,
-    pub _reserved: i32,
+    pub decode_weights: i32,
+}
+
+/// `fl_model_options` (fl_model_create_opts): `struct_size` must be `size_of::<fl_model_options>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fl_model_options {
+    pub struct_size: u32,
+    pub decode_weights: i32,
+    pub _reserved: [i64; 3],
 }
 
 /// `fl_sampling`: LogitsProcessor::new(seed, Some(temperature), None) (mod.rs:373-374).
@@ -143,6 +156,15 @@ extern "C" {
         n_tensors: usize,
         compute_dtype: i32,
         par: *const fl_parallel,
+        out: *mut *mut fl_model,
+    ) -> c_int;
+    pub fn fl_model_create_opts(
+        cfg: *const fl_config,
+        tensors: *const fl_tensor,
+        n_tensors: usize,
+        compute_dtype: i32,
+        par: *const fl_parallel,
+        opts: *const fl_model_options,
         out: *mut *mut fl_model,
     ) -> c_int;
     pub fn fl_comm_ipc_export(m: *mut fl_model, handle_out: *mut c_void) -> c_int;
@@ -231,6 +253,19 @@ extern "C" {
         n: i64,
         k: i64,
         dtype: i32,
+        epilogue: i32,
+        y: *mut f32,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
+    pub fn fl_op_quantize_rows(w: *const c_void, dtype: i32, n: i64, k: i64, q_out: *mut u8, s_out: *mut f32) -> c_int;
+    pub fn fl_op_gemv_w8(
+        x: *const c_void,
+        q: *const u8,
+        s: *const f32,
+        bias: *const f32,
+        n: i64,
+        k: i64,
         epilogue: i32,
         y: *mut f32,
         iters: i32,

@@ -15,4 +15,4 @@
 pub mod ffi;
 pub mod safe;
 
-pub use safe::{Batch, Cache, Config, DType, Error, Family, Model, Result, Sampling, TensorView};
+pub use safe::{Batch, Cache, Config, DType, Error, Family, Model, Result, Sampling, TensorView, WeightFormat};

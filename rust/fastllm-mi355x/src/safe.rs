@@ -113,6 +113,14 @@ impl Sampling {
     }
 }
 
+/// `fl_weight_format`: what the single-stream decode step reads its projection weights as.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum WeightFormat {
+    ComputeDtype = ffi::FL_WEIGHTS_COMPUTE_DTYPE,
+    E4m3Row = ffi::FL_WEIGHTS_E4M3_ROW,
+}
+
 /// `fl_model*`.  Immutable after creation; `Clone` is a reference-count bump (the streaming path clones the model per
 /// request, mod.rs:155,181,207).
 pub struct Model {
@@ -139,6 +147,12 @@ impl Drop for Model {
 impl Model {
     /// `ModelInitializer::initialize_model` (model_initializer.rs:10-17): single GPU `device_id`.
     pub fn new(cfg: &Config, tensors: &[TensorView<'_>], compute: DType, device_id: i32) -> Result<Model> {
+        Model::new_with_weights(cfg, tensors, compute, device_id, WeightFormat::ComputeDtype)
+    }
+
+    /// ... with the weight format of the decode step (`fl_model_create_opts`).  `WeightFormat::E4m3Row`: bf16 compute only; weight
+    /// memory is 1.5x a bf16 model's (the e4m3 bytes and their bf16 image are both kept).
+    pub fn new_with_weights(cfg: &Config, tensors: &[TensorView<'_>], compute: DType, device_id: i32, weights: WeightFormat) -> Result<Model> {
         let names: Vec<CString> = tensors
             .iter()
             .map(|t| CString::new(t.name).map_err(|_| Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("tensor name {:?} contains NUL", t.name) }))
@@ -159,7 +173,8 @@ impl Model {
         let par = ffi::fl_parallel { mode: ffi::FL_TP_NONE, tp_size: 1, tp_rank: 0, n_device_ids: 1, device_ids: ids.as_ptr(), unique_id: ptr::null() };
         let mut raw: *mut ffi::fl_model = ptr::null_mut();
         // SAFETY: every pointer is valid for the duration of the call; the library copies what it keeps.
-        check(unsafe { ffi::fl_model_create(&c, descr.as_ptr(), descr.len(), compute as i32, &par, &mut raw) })?;
+        let opts = ffi::fl_model_options { struct_size: std::mem::size_of::<ffi::fl_model_options>() as u32, decode_weights: weights as i32, _reserved: [0; 3] };
+        check(unsafe { ffi::fl_model_create_opts(&c, descr.as_ptr(), descr.len(), compute as i32, &par, &opts, &mut raw) })?;
         Ok(Model { raw, vocab: cfg.vocab_size })
     }
 
