@@ -58,6 +58,17 @@ class FlSampling(C.Structure):
     _fields_ = [("temperature", C.c_double), ("seed", C.c_uint64), ("draws_done", C.c_uint64)]
 
 
+class FlSampler(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("top_k", C.c_int32), ("temperature", C.c_double), ("top_p", C.c_double),
+                ("seed", C.c_uint64), ("draws_done", C.c_uint64), ("_reserved", C.c_int64 * 2)]
+
+
+def make_sampler(temperature, seed=0, draws_done=0, top_p=None, top_k=None):
+    """fl_sampler: top_p None (or outside (0, 1)) and top_k None (or 0) are off."""
+    return FlSampler(C.sizeof(FlSampler), 0 if top_k is None else int(top_k), temperature, 0.0 if top_p is None else top_p,
+                     seed, draws_done)
+
+
 class FlKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_double),
                 ("flops", C.c_double)]
@@ -103,6 +114,10 @@ def lib():
         L.fl_forward_sample.argtypes = [vp, vp, vp, sz, sz, C.POINTER(FlSampling), vp]
         L.fl_decode_sample.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampling), vp, C.POINTER(sz)]
         L.fl_op_sample.argtypes = [vp, C.c_int64, C.POINTER(FlSampling), C.c_int64, vp]
+        L.fl_forward_sample_ex.argtypes = [vp, vp, vp, sz, sz, C.POINTER(FlSampler), vp]
+        L.fl_decode_sample_ex.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampler), vp, C.POINTER(sz)]
+        L.fl_op_sample_ex.argtypes = [vp, C.c_int64, C.POINTER(FlSampler), C.c_int64, vp, vp]
+        L.fl_batch_decode_each_ex.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
         L.fl_batch_create.argtypes = [vp, vp, sz, C.POINTER(vp)]
         L.fl_batch_destroy.argtypes = [vp]
@@ -131,10 +146,16 @@ def _check(rc):
         raise FastLLMError(rc, lib().fl_last_error().decode(errors="replace"))
 
 
-def op_sample(logits, n_draws, temperature, seed=0, draws_done=0):
-    """The token-selection kernel alone on a host logits vector: n_draws successive tokens."""
+def op_sample(logits, n_draws, temperature, seed=0, draws_done=0, top_p=None, top_k=None, return_kept=False):
+    """The token-selection kernel alone on a host logits vector: n_draws successive tokens.  With top_p / top_k (fl_op_sample_ex):
+    nucleus / top-k sampling; return_kept: also how many tokens each draw kept."""
     a = np.ascontiguousarray(logits, dtype=np.float32)
     out = np.zeros(n_draws, dtype=np.uint32)
+    if top_p is not None or top_k is not None or return_kept:
+        sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+        kept = np.zeros(n_draws, dtype=np.int64)
+        _check(lib().fl_op_sample_ex(a.ctypes.data, a.size, C.byref(sp), n_draws, out.ctypes.data, kept.ctypes.data))
+        return (out, kept) if return_kept else out
     sp = FlSampling(temperature, seed, draws_done)
     _check(lib().fl_op_sample(a.ctypes.data, a.size, C.byref(sp), n_draws, out.ctypes.data))
     return out
@@ -263,16 +284,25 @@ class Model:
         _check(lib().fl_decode_greedy(self._h, cache._h, int(first_token), pos, n_steps, eos, toks.ctypes.data, C.byref(n)))
         return toks[: n.value]
 
-    def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0):
+    def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None):
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         tok = C.c_uint32(0)
+        if top_p is not None or top_k is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            _check(lib().fl_forward_sample_ex(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok)))
+            return tok.value
         sp = FlSampling(temperature, seed, draws_done)
         _check(lib().fl_forward_sample(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok)))
         return tok.value
 
-    def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1):
+    def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1, top_p=None, top_k=None):
         toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
         n = C.c_size_t(0)
+        if top_p is not None or top_k is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            _check(lib().fl_decode_sample_ex(self._h, cache._h, int(first_token), pos, n_steps, eos, C.byref(sp), toks.ctypes.data,
+                                             C.byref(n)))
+            return toks[: n.value]
         sp = FlSampling(temperature, seed, draws_done)
         _check(lib().fl_decode_sample(self._h, cache._h, int(first_token), pos, n_steps, eos, C.byref(sp), toks.ctypes.data,
                                       C.byref(n)))
@@ -364,13 +394,23 @@ class Batch:
                                      out.ctypes.data, n_out.ctypes.data))
         return [out[i, : int(n_out[i])] for i in range(self.n)]
 
-    def decode_each(self, first_tokens, pos, n_steps, eos=None, temperatures=None, seeds=None, draws_done=None):
-        """fl_batch_decode_each: per-sequence EOS ids (None / negative: none) and temperatures (None / < 1e-7: ArgMax)."""
+    def decode_each(self, first_tokens, pos, n_steps, eos=None, temperatures=None, seeds=None, draws_done=None, top_p=None, top_k=None):
+        """fl_batch_decode_each: per-sequence EOS ids (None / negative: none) and temperatures (None / < 1e-7: ArgMax).  With top_p /
+        top_k (lists, None entries: off) it is fl_batch_decode_each_ex: one batch mixes ArgMax, Sampling::All and top-p / top-k."""
         first = np.ascontiguousarray(first_tokens, dtype=np.uint32)
         pos = np.ascontiguousarray(pos, dtype=np.uint64)
         out = np.zeros((self.n, max(n_steps, 1)), dtype=np.uint32)
         n_out = np.zeros(self.n, dtype=np.uint64)
         e = np.ascontiguousarray([-1 if x is None else int(x) for x in (eos if eos is not None else [None] * self.n)], dtype=np.int64)
+        if top_p is not None or top_k is not None:
+            spx = (FlSampler * self.n)()
+            for i in range(self.n):
+                t = temperatures[i] if temperatures is not None and temperatures[i] is not None else 0.0
+                spx[i] = make_sampler(t, seeds[i] if seeds is not None else 0, draws_done[i] if draws_done is not None else 1,
+                                      top_p[i] if top_p is not None else None, top_k[i] if top_k is not None else None)
+            _check(lib().fl_batch_decode_each_ex(self._h, first.ctypes.data, pos.ctypes.data, n_steps, e.ctypes.data, C.cast(spx, C.c_void_p),
+                                                 out.ctypes.data, n_out.ctypes.data))
+            return [out[i, : int(n_out[i])] for i in range(self.n)]
         sp = (FlSampling * self.n)()
         for i in range(self.n):
             t = temperatures[i] if temperatures is not None and temperatures[i] is not None else 0.0

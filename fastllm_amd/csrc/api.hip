@@ -206,20 +206,42 @@ int fl_decode_greedy(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos,
     });
 }
 
+// the older sampler struct as the one every path below takes: no top_p, no top_k
+static fl_sampler widen(const fl_sampling &sp) {
+    fl_sampler s{};
+    s.struct_size = sizeof(fl_sampler);
+    s.temperature = sp.temperature; s.seed = sp.seed; s.draws_done = sp.draws_done;
+    return s;
+}
+
+int fl_forward_sample_ex(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_sampler *sampler,
+                         uint32_t *token_out) {
+    return guarded([&]() -> int {
+        if (!token_out || !sampler) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        return forward(M(m), C(c), ids, T, pos, nullptr, token_out, sampler);
+    });
+}
+
 int fl_forward_sample(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_sampling *sampling,
                       uint32_t *token_out) {
+    if (!sampling) return fl_forward_sample_ex(m, c, ids, T, pos, nullptr, token_out);
+    const fl_sampler s = widen(*sampling);
+    return fl_forward_sample_ex(m, c, ids, T, pos, &s, token_out);
+}
+
+int fl_decode_sample_ex(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
+                        const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {
-        if (!token_out || !sampling) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
-        return forward(M(m), C(c), ids, T, pos, nullptr, token_out, sampling);
+        if (!sampler) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null sampling");
+        return decode_greedy(M(m), C(c), first_token, pos, n_steps, eos, tokens_out, n_out, sampler);
     });
 }
 
 int fl_decode_sample(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
                      const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
-    return guarded([&]() -> int {
-        if (!sampling) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null sampling");
-        return decode_greedy(M(m), C(c), first_token, pos, n_steps, eos, tokens_out, n_out, sampling);
-    });
+    if (!sampling) return fl_decode_sample_ex(m, c, first_token, pos, n_steps, eos, nullptr, tokens_out, n_out);
+    const fl_sampler s = widen(*sampling);
+    return fl_decode_sample_ex(m, c, first_token, pos, n_steps, eos, &s, tokens_out, n_out);
 }
 
 int fl_batch_create(fl_model *m, fl_cache *const *caches, size_t n, fl_batch **out) {
@@ -253,13 +275,24 @@ int fl_batch_forward(fl_batch *b, const uint32_t *tokens, const size_t *pos, flo
 int fl_batch_decode(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, int64_t eos,
                     const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {
-        return batch_decode(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, sampling, tokens_out, n_out);
+        fl_sampler s{};
+        if (sampling) s = widen(*sampling);
+        return batch_decode(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, sampling ? &s : nullptr, tokens_out, n_out);
+    });
+}
+int fl_batch_decode_each_ex(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
+                            const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out) {
+    return guarded([&]() -> int {
+        return batch_decode_each(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, samplers, tokens_out, n_out);
     });
 }
 int fl_batch_decode_each(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                          const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {
-        return batch_decode_each(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, sampling, tokens_out, n_out);
+        if (!b) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        std::vector<fl_sampler> sp;
+        if (sampling) for (int i = 0; i < reinterpret_cast<Batch *>(b)->B; i++) sp.push_back(widen(sampling[i]));
+        return batch_decode_each(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, sampling ? sp.data() : nullptr, tokens_out, n_out);
     });
 }
 
@@ -365,32 +398,50 @@ int fl_tune(const char *key, int value) {
     });
 }
 
-int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out) {
+int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, int64_t n_draws, uint32_t *tokens_out, int64_t *kept_out) {
     return guarded([&]() -> int {
-        if (!logits || !sampling || !tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (!logits || !sampler || !tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
         if (V <= 0 || V > (1 << 24) || n_draws <= 0 || n_draws > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size");
+        SampleState ss;
+        FL_TRY(make_sampler(sampler, V, &ss));
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
         FL_HIP(hipSetDevice(0));
-        struct Bufs { float *lg = 0, *sc = 0; StepState *st = 0; SampleState *ss = 0; uint32_t *out = 0; hipStream_t s = 0;
-                      ~Bufs() { (void)hipFree(lg); (void)hipFree(sc); (void)hipFree(st); (void)hipFree(ss); (void)hipFree(out); if (s) (void)hipStreamDestroy(s); } } B;
+        struct Bufs { float *lg = 0, *sc = 0; StepState *st = 0; SampleState *ss = 0; uint32_t *out = 0, *kept = 0; hipStream_t s = 0;
+                      ~Bufs() { (void)hipFree(lg); (void)hipFree(sc); (void)hipFree(st); (void)hipFree(ss); (void)hipFree(out); (void)hipFree(kept);
+                                if (s) (void)hipStreamDestroy(s); } } B;
+        const bool kept_dev = kept_out && ss.filter;       // (no filter: every token is kept)
         FL_HIP(hipStreamCreate(&B.s));
         FL_HIP(hipMalloc((void **)&B.lg, (size_t)V * 4));
         FL_HIP(hipMalloc((void **)&B.sc, (size_t)V * 4));
         FL_HIP(hipMalloc((void **)&B.st, sizeof(StepState)));
         FL_HIP(hipMalloc((void **)&B.ss, sizeof(SampleState)));
         FL_HIP(hipMalloc((void **)&B.out, (size_t)n_draws * 4));
+        if (kept_dev) FL_HIP(hipMalloc((void **)&B.kept, (size_t)n_draws * 4));
         StepState st{}; st.eos = -1;
-        const SampleState ss = make_sampler(sampling);
         FL_HIP(hipMemcpy(B.lg, logits, (size_t)V * 4, hipMemcpyHostToDevice));
         FL_HIP(hipMemcpy(B.st, &st, sizeof st, hipMemcpyHostToDevice));
         FL_HIP(hipMemcpy(B.ss, &ss, sizeof ss, hipMemcpyHostToDevice));
         Launcher L; L.stream = B.s;
-        for (int64_t i = 0; i < n_draws; i++) FL_TRY(launch_select_advance(L, B.lg, V, B.st, B.ss, B.sc, B.out, 1));
+        for (int64_t i = 0; i < n_draws; i++) {
+            FL_TRY(launch_select_advance(L, B.lg, V, B.st, B.ss, B.sc, B.out, 1));
+            if (kept_dev) FL_HIP(hipMemcpyAsync(B.kept + i, &B.ss->kept, 4, hipMemcpyDeviceToDevice, B.s));
+        }
         FL_HIP(hipStreamSynchronize(B.s));
         FL_HIP(hipMemcpy(tokens_out, B.out, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+        if (kept_out) {
+            std::vector<uint32_t> k((size_t)n_draws, (uint32_t)V);
+            if (kept_dev) FL_HIP(hipMemcpy(k.data(), B.kept, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < n_draws; i++) kept_out[i] = (int64_t)k[(size_t)i];
+        }
         return FL_OK;
     });
+}
+
+int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out) {
+    if (!sampling) return fl_op_sample_ex(logits, V, nullptr, n_draws, tokens_out, nullptr);
+    const fl_sampler s = widen(*sampling);
+    return fl_op_sample_ex(logits, V, &s, n_draws, tokens_out, nullptr);
 }
 
 int fl_op_linear(const void *x, const void *w, const float *bias, int64_t T, int64_t N, int64_t K, int32_t dtype,

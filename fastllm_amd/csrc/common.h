@@ -230,13 +230,19 @@ struct StepState {
 };
 
 // Token selection state of a cache, next to StepState: LogitsProcessor (mod.rs:373-374) on the device.
-// on == 0: ArgMax.  Otherwise Sampling::All { temperature }: the u32 words of the seeded ChaCha12 stream
+// on == 0: ArgMax.  Otherwise Sampling::All { temperature } (or, with filter, TopP / TopK / TopKThenTopP): the u32 words of the seeded ChaCha12 stream
 // (rand 0.8 StdRng) consumed so far are counted here, so a captured decode graph draws the next word.
 struct SampleState {
     uint32_t on;
     float inv_temp;          // (f32)(1 / temperature): `logits / temperature` is an affine multiply in candle
     uint32_t draw_lo, draw_hi;
     uint32_t key[8];
+    // Sampling::TopP / TopK / TopKThenTopP (filter != 0, only with on != 0): the kept prefix of the sorted order ends where its
+    // sequential fp32 sum is no longer < top_p (+inf: no top-p) or at rank top_k (0xffffffff: no top-k); kept = its length at the last draw
+    uint32_t filter;
+    float top_p;
+    uint32_t top_k;
+    uint32_t kept;
 };
 
 // acc += a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (gfx950 VOP2; hipcc has no selectable builtin for it)

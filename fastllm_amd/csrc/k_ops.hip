@@ -672,6 +672,155 @@ __device__ inline float ordered_sum(const float *__restrict__ p, int V, OrderedS
     return L.s_in[1024];
 }
 
+// Sampling::TopP / TopK / TopKThenTopP (candle-transformers 0.8 generation::LogitsProcessor) [UPSTREAM-RECALLED]: between
+// the normalisation and the cumulative weights of sample_all, everything outside the kept prefix of the sorted order
+// (prs descending, the lower index first among equals: candle's stable sort) is zeroed.  The prefix ends at the first
+// element whose SEQUENTIAL fp32 running sum (from 0, in sorted order) is not < top_p, or at rank top_k, whichever comes
+// first -- the sum is walked by one lane over exactly sorted keys; the parallel passes only pick what to sort.
+//
+// A key is (bits(prs) << 1) : ~index, a total order over distinct keys whose descending order is the sorted order.
+// The vocabulary is taken in descending BANDS of at most kBandKeys keys: a band is [lo, hi) in key space, hi the lower
+// end of the band before it.  lo comes from a 256-bin histogram of the keys below hi over the top byte (the exponent):
+// as many whole bins from the top as fit.  Only when the top non-empty bin alone is too large (a flat region, ties)
+// is it split by the next byte, and so on down to the index bytes, where a bin holds one key.  The band is gathered
+// into LDS, sorted (bitonic), and walked with the running sum carried in from the band before: no cap on the nucleus.
+// LDS: the block OrderedSumLds occupies, free between the two sums.
+constexpr int kBandKeys = 4096;
+struct TopFilterLds {
+    unsigned long long keys[kBandKeys];
+    unsigned hist[16][256];             // per wave, then [0][] = the workgroup's
+    unsigned long long lo, hi, prefix, cut;
+    unsigned n, walked, found, refine;
+    float acc;
+};
+
+__device__ inline unsigned long long top_key(float v, int i) {
+    return ((unsigned long long)(__float_as_uint(v) << 1) << 32) | (unsigned)~(unsigned)i;
+}
+
+__device__ inline void top_filter(float *__restrict__ p, int V, SampleState *__restrict__ ss, TopFilterLds *__restrict__ F) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float top_p = ss->top_p;                     // +inf: no top-p
+    const unsigned top_k = ss->top_k;                  // >= V: no top-k
+    if (tid == 0) { F->hi = ~0ull; F->walked = 0; F->found = 0; F->acc = 0.f; F->cut = 0; }
+    __syncthreads();
+    for (int band = 0; band < V; band++) {             // (every band holds at least one key)
+        const unsigned long long hi = F->hi;
+        // ---- lo: whole histogram bins from the top while they fit; a level deeper only if the top bin alone does not
+        unsigned long long prefix = 0;
+        bool have = false;
+        for (int level = 0; level < 8 && !have; level++) {
+            const int shift = 56 - 8 * level;
+            for (int j = tid; j < 16 * 256; j += 1024) (&F->hist[0][0])[j] = 0;
+            __syncthreads();
+            for (int i0 = 0; i0 < V; i0 += 1024) {
+                const int i = i0 + tid;
+                unsigned long long key = 0;
+                bool act = false;
+                if (i < V) { key = top_key(p[i], i); act = key < hi && (level == 0 || (key >> (shift + 8)) == prefix); }
+                const int d = (int)((key >> shift) & 255);
+                const unsigned long long am = __ballot(act);
+                if (am) {                              // a wave whose keys share the bin (flat regions) adds once
+                    const int first = __builtin_ctzll(am);
+                    const int d0 = __shfl(d, first, 64);
+                    if (__ballot(act && d != d0) == 0) { if (lane == first) atomicAdd(&F->hist[wave][d0], (unsigned)__builtin_popcountll(am)); }
+                    else if (act) atomicAdd(&F->hist[wave][d], 1u);
+                }
+            }
+            __syncthreads();
+            if (tid < 256) { unsigned s = 0; for (int w = 0; w < 16; w++) s += F->hist[w][tid]; F->hist[0][tid] = s; }
+            __syncthreads();
+            if (tid == 0) {
+                int d = 255;
+                while (d > 0 && F->hist[0][d] == 0) d--;
+                unsigned cum = F->hist[0][d];
+                if (cum > (unsigned)kBandKeys) { F->refine = 1; F->prefix = (prefix << 8) | (unsigned)d; }
+                else {
+                    while (d > 0 && cum + F->hist[0][d - 1] <= (unsigned)kBandKeys) { d--; cum += F->hist[0][d]; }
+                    F->refine = 0; F->lo = ((prefix << 8) | (unsigned)d) << shift; F->n = 0;
+                }
+            }
+            __syncthreads();
+            if (F->refine) prefix = F->prefix; else have = true;
+        }
+        if (!have) break;                              // (cannot happen: at the last level a bin holds one key)
+        const unsigned long long lo = F->lo;
+        // ---- gather [lo, hi) into LDS (any order), pad to a power of two with key 0 (below every real key)
+        for (int i0 = 0; i0 < V; i0 += 1024) {
+            const int i = i0 + tid;
+            unsigned long long key = 0;
+            if (i < V) key = top_key(p[i], i);
+            const bool act = i < V && key >= lo && key < hi;
+            const unsigned long long am = __ballot(act);
+            if (am) {
+                unsigned base = 0;
+                const int first = __builtin_ctzll(am);
+                if (lane == first) base = atomicAdd(&F->n, (unsigned)__builtin_popcountll(am));
+                base = __shfl(base, first, 64);
+                const unsigned at = base + (unsigned)__builtin_popcountll(am & ((1ull << lane) - 1));
+                if (act && at < (unsigned)kBandKeys) F->keys[at] = key;
+            }
+        }
+        __syncthreads();
+        const int n = (int)min(F->n, (unsigned)kBandKeys);
+        if (n == 0) break;                             // (cannot happen while keys remain below hi)
+        int np = 1;
+        while (np < n) np <<= 1;
+        for (int j = n + tid; j < np; j += 1024) F->keys[j] = 0;
+        __syncthreads();
+        // ---- bitonic sort, descending
+        for (int k = 2; k <= np; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int t = tid; t < np / 2; t += 1024) {
+                    const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1)), b = a | j;
+                    const unsigned long long ka = F->keys[a], kb = F->keys[b];
+                    if ((ka < kb) == ((a & k) == 0)) { F->keys[a] = kb; F->keys[b] = ka; }
+                }
+                __syncthreads();
+            }
+        }
+        // ---- one lane walks the band: the sequential fp32 sum of the sorted order, carried from the band before
+        if (tid == 0) {
+            float acc = F->acc;
+            unsigned r = F->walked;
+            const unsigned long long *ks = F->keys;
+            auto val = [](unsigned long long key) { return __uint_as_float((unsigned)(key >> 32) >> 1); };
+            int j = 0, hit = -1;
+            // eight adds per look at the stop conditions (the sums only grow, so the last of the eight decides); the next
+            // eight keys are read before the adds of the current eight
+            unsigned long long cur[8], nxt[8];
+            if (n >= 8) for (int u = 0; u < 8; u++) cur[u] = ks[u];
+            for (; j + 8 <= n; j += 8) {
+                const bool more = j + 16 <= n;
+                if (more) for (int u = 0; u < 8; u++) nxt[u] = ks[j + 8 + u];
+                float c[8];
+                float a = acc;
+#pragma unroll
+                for (int u = 0; u < 8; u++) c[u] = a = __fadd_rn(a, val(cur[u]));
+                if (!(a < top_p) || r + 8 >= top_k) {
+#pragma unroll
+                    for (int u = 0; u < 8; u++) if (hit < 0 && (!(c[u] < top_p) || r + u + 1 >= top_k)) hit = j + u;
+                    break;
+                }
+                acc = a; r += 8;
+                if (more) for (int u = 0; u < 8; u++) cur[u] = nxt[u];
+            }
+            if (hit < 0)
+                for (; j < n; j++) { acc = __fadd_rn(acc, val(ks[j])); r++; if (!(acc < top_p) || r >= top_k) { hit = j; break; } }
+            if (hit >= 0) { F->found = 1; F->cut = ks[hit]; F->walked = F->walked + (unsigned)hit + 1; }
+            else { F->acc = acc; F->walked = r; F->hi = lo; }
+        }
+        __syncthreads();
+        if (F->found || F->walked >= (unsigned)V) break;
+    }
+    // ---- mask: everything after the last kept key of the sorted order is zeroed
+    const bool found = F->found != 0;
+    const unsigned long long cut = F->cut;
+    if (found) for (int i = tid; i < V; i += 1024) { const float v = p[i]; if (top_key(v, i) < cut) p[i] = 0.f; }
+    if (tid == 0) ss->kept = found ? F->walked : (unsigned)V;
+    __syncthreads();
+}
+
 // Sampling::All { temperature } (candle-transformers LogitsProcessor over rand 0.8's WeightedIndex<f32>):
 //   prs = softmax(logits * (f32)(1/temperature));  total = sum(prs);  chosen = uniform[0,1) * total with
 //   uniform = f32::from_bits((next_u32() >> 9) | 0x3f800000) - 1;  token = #{ j < V-1 : prs[0]+..+prs[j] <= chosen }.
@@ -703,6 +852,7 @@ __device__ inline int sample_all(const float *__restrict__ logits, int V, Sample
     for (int i = tid; i < V; i += 1024) p[i] = __fdiv_rn(p[i], S);
     if (tid == 0) *count = 0;
     __syncthreads();
+    if (ss->filter) top_filter(p, V, ss, reinterpret_cast<TopFilterLds *>(lds));       // Sampling::TopP / TopK / TopKThenTopP
     // walk: p[] is replaced by the cumulative weights; ordered: L.s_in[] holds the sum entering every run
     const float total = walk ? sequential_sum(p, V, tiles, bcast, true) : ordered_sum(p, V, L);
     if (tid == 0) {
@@ -758,6 +908,7 @@ __device__ __forceinline__ void select_advance_body(const float *__restrict__ lo
 }
 
 constexpr size_t kSelLds = sizeof(OrderedSumLds) > 2 * kSelTile * 4 ? sizeof(OrderedSumLds) : 2 * kSelTile * 4;
+static_assert(sizeof(TopFilterLds) <= kSelLds, "the top-p / top-k filter lives in the LDS block of the ordered sums");
 
 __global__ __launch_bounds__(1024) void select_advance_kernel(const float *__restrict__ logits, int V,
                                                               StepState *__restrict__ st, SampleState *__restrict__ ss,

@@ -196,9 +196,9 @@ int batch_replace(Batch *b, size_t slot, Cache *c);     // fl_batch_replace: ano
 int batch_forward(Batch *b, const uint32_t *tokens, const size_t *pos, float *logits_out, uint32_t *tokens_out);
 // n_steps greedy / sampled steps; tokens_out [B][n_steps], n_out [B] (stops counting a sequence at its EOS)
 int batch_decode(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, int64_t eos,
-                 const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out);
+                 const fl_sampler *sampling, uint32_t *tokens_out, size_t *n_out);
 int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, const int64_t *eos_each,
-                      const fl_sampling *sampling_each, uint32_t *tokens_out, size_t *n_out);
+                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out);
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
                  const fl_parallel *par, const fl_model_options *opts, Model **out);
@@ -229,13 +229,14 @@ int comm_check(Model *m);                              // a kernel gave up waiti
 // n floats in chunks of at most the inbox size; reduce: out = sum over ranks (in == out allowed); gather: out[r * out_stride + i] = in_r[i]
 int oneshot(Model *m, Shard &sh, bool gather, const float *in, float *out, int64_t n, int64_t out_stride, hipStream_t on = nullptr);
 // mode: 0 = logits to host, 1 = argmax token to host
-// device token-selection state for a LogitsProcessor::new(seed, Some(temperature), None); null: ArgMax
-SampleState make_sampler(const fl_sampling *sampling);
+// device token-selection state for a LogitsProcessor (temperature, top_p, top_k); null: ArgMax.  V: the vocabulary (top_k >= V is
+// off), <= 0: unknown.  FL_ERR_BAD_ARGUMENT: wrong struct_size, NaN top_p, negative top_k.
+int make_sampler(const fl_sampler *sampling, int64_t V, SampleState *out);
 // sampling == null: ArgMax
 int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float *logits_out, uint32_t *token_out,
-            const fl_sampling *sampling = nullptr);
+            const fl_sampler *sampling = nullptr);
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampling *sampling = nullptr);
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr);
 
 // most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (model.hip)
 int ksplit_cap(int64_t T);

@@ -907,12 +907,19 @@ __global__ void set_state_kernel(StepState *st, uint32_t token, uint32_t pos, ui
     for (int l = threadIdx.x; l < n_layers; l += blockDim.x) heads_done[l] = 0;       // targets restart with step
 }
 
-// LogitsProcessor::new(seed, Some(temperature), None) (mod.rs:373-374): ArgMax below 1e-7, else the
+// LogitsProcessor::new(seed, Some(temperature), top_p) / from_sampling (mod.rs:373-374): ArgMax below 1e-7, else the
 // StdRng stream of rand 0.8 -- ChaCha12 keyed by SeedableRng::seed_from_u64 (PCG32 XSH-RR expansion of
-// the u64 into 8 little-endian key words) -- positioned after `draws_done` u32 words.
-SampleState make_sampler(const fl_sampling *sp) {
+// the u64 into 8 little-endian key words) -- positioned after `draws_done` u32 words.  top_p outside (0, 1) and
+// top_k == 0 or >= V are "off" (Sampling::All), as in candle [UPSTREAM-RECALLED]; V <= 0: the vocabulary is not known
+// here, any positive top_k is kept (a top_k >= V keeps everything in the kernel too).
+int make_sampler(const fl_sampler *sp, int64_t V, SampleState *out) {
     SampleState s{};
-    if (!sp || !(sp->temperature >= 1e-7)) return s;
+    *out = s;
+    if (!sp) return FL_OK;
+    if (sp->struct_size != sizeof(fl_sampler)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_sampler.struct_size is %u, expected %zu", sp->struct_size, sizeof(fl_sampler));
+    if (sp->top_p != sp->top_p) FL_FAIL(FL_ERR_BAD_ARGUMENT, "top_p is NaN");
+    if (sp->top_k < 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "negative top_k %d", sp->top_k);
+    if (!(sp->temperature >= 1e-7)) return FL_OK;
     s.on = tune(TK_SAMPLE_WALK) ? 2 : 1;       // 2: plain one-lane walk instead of ordered_sum (cross-check)
     s.inv_temp = (float)(1.0 / sp->temperature);
     uint64_t state = sp->seed;
@@ -922,7 +929,13 @@ SampleState make_sampler(const fl_sampling *sp) {
         s.key[i] = (xs >> rot) | (xs << ((32 - rot) & 31));
     }
     s.draw_lo = (uint32_t)sp->draws_done; s.draw_hi = (uint32_t)(sp->draws_done >> 32);
-    return s;
+    const bool p_on = sp->top_p > 0.0 && sp->top_p < 1.0;
+    const bool k_on = sp->top_k > 0 && (V <= 0 || (int64_t)sp->top_k < V);
+    s.filter = (p_on || k_on) ? 1 : 0;
+    s.top_p = p_on ? (float)sp->top_p : INFINITY;          // compared as (f32)top_p
+    s.top_k = k_on ? (uint32_t)sp->top_k : 0xffffffffu;
+    *out = s;
+    return FL_OK;
 }
 
 Launcher make_launcher(Model *m, Shard &sh) {
@@ -1503,10 +1516,11 @@ static int check_call(Model *m, Cache *c, size_t T, size_t pos) {
 }
 
 int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float *logits_out, uint32_t *token_out,
-            const fl_sampling *sampling) {
+            const fl_sampler *sampling) {
     FL_TRY(check_call(m, c, T, pos));
     debug_inject("forward");
-    const SampleState sampler = make_sampler(sampling);
+    SampleState sampler;
+    FL_TRY(make_sampler(sampling, m->D.V, &sampler));
     if (!ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null ids");
     for (size_t t = 0; t < T; t++)
         if ((int64_t)ids[t] >= m->D.V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "token id %u out of range (vocab %lld)", ids[t], (long long)m->D.V);
@@ -1554,11 +1568,12 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
 }
 
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampling *sampling) {
-    const SampleState sampler = make_sampler(sampling);
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling) {
     if (n_out) *n_out = 0;
     if (n_steps == 0) return FL_OK;
     FL_TRY(check_call(m, c, n_steps, pos));
+    SampleState sampler;
+    FL_TRY(make_sampler(sampling, m->D.V, &sampler));
     if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null tokens_out");
     if ((int64_t)first >= m->D.V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "token id %u out of range", first);
     std::lock_guard<std::mutex> lock(m->mu);
@@ -1915,16 +1930,18 @@ static int batch_check(Batch *b, const size_t *pos, size_t n_steps) {
 }
 
 int batch_decode(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, int64_t eos,
-                 const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
+                 const fl_sampler *sampling, uint32_t *tokens_out, size_t *n_out) {
     if (!b) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
     std::vector<int64_t> e((size_t)b->B, eos);
-    std::vector<fl_sampling> sp((size_t)b->B, sampling ? *sampling : fl_sampling{0.0, 0, 0});
+    fl_sampler greedy{};
+    greedy.struct_size = sizeof(fl_sampler);
+    std::vector<fl_sampler> sp((size_t)b->B, sampling ? *sampling : greedy);
     return batch_decode_each(b, first, pos, n_steps, e.data(), sp.data(), tokens_out, n_out);
 }
 
 // ... with every sequence's own EOS id and sampler (a request's temperature is its own: chat.rs:24-25; temperature < 1e-7 = ArgMax)
 int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, const int64_t *eos_each,
-                      const fl_sampling *sampling_each, uint32_t *tokens_out, size_t *n_out) {
+                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out) {
     if (!b || !first || !tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
     const int B = b->B;
     for (int i = 0; i < B; i++) n_out[i] = 0;
@@ -1935,7 +1952,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
     std::vector<SampleState> samplers((size_t)B);
     std::vector<int64_t> eoss((size_t)B, -1);
     for (int i = 0; i < B; i++) {
-        samplers[(size_t)i] = make_sampler(sampling_each ? sampling_each + i : nullptr);
+        FL_TRY(make_sampler(sampling_each ? sampling_each + i : nullptr, m->D.V, &samplers[(size_t)i]));
         if (eos_each) eoss[(size_t)i] = eos_each[i];
     }
     std::lock_guard<std::mutex> lock(m->mu);

@@ -476,12 +476,29 @@ class StdRng {
 // LogitsProcessor::new(Default::default(), Some(temperature as f64), None) (mod.rs:157-158,373-374).
 // This is the reference's own host-side shape (logits on the host, mod.rs:421-428); the device-side
 // equivalent is fl_forward_sample / fl_decode_sample.
+//
+// With top_p / top_k it is LogitsProcessor::from_sampling(seed, Sampling::TopP / TopK / TopKThenTopP) [UPSTREAM-RECALLED], with the
+// semantics of fl_sampler (include/fastllm_mi355x.h): the kept set is a prefix of the order by prs descending, the LOWER index first
+// among equals; top_p (0 < top_p < 1, compared as f32) ends it where the sequential f32 running sum is no longer < top_p, top_k
+// (0 < top_k < n) at rank top_k; the draw runs over the masked vector in vocabulary order.  top_k = 1 keeps the LOWEST maximal
+// index; ArgMax (temperature < 1e-7, whatever the other two say) keeps the LAST.  The device-side equivalent is fl_*_sample_ex.
 class LogitsProcessor {
    public:
-    LogitsProcessor(uint64_t seed, std::optional<double> temperature) : rng_(seed) {
+    LogitsProcessor(uint64_t seed, std::optional<double> temperature, std::optional<double> top_p = std::nullopt,
+                    std::optional<size_t> top_k = std::nullopt) : rng_(seed) {
         if (temperature && !(*temperature < 1e-7)) { sampling_ = true; temperature_ = *temperature; }
+        if (top_p && *top_p != *top_p) throw Error(FL_ERR_BAD_ARGUMENT, "top_p is NaN");
+        if (top_p && *top_p > 0.0 && *top_p < 1.0) { top_p_on_ = true; top_p_ = (float)*top_p; }
+        if (top_k) top_k_ = *top_k;                                   // 0 or >= n: off
     }
     bool is_argmax() const { return !sampling_; }
+    size_t kept() const { return kept_; }                             // tokens the last sample() kept (n without a filter)
+    // the filter and the draw alone, on probabilities the caller computed (tests)
+    uint32_t sample_prs(const float *prs, size_t n) {
+        if (n == 0) throw Error(FL_ERR_BAD_ARGUMENT, "empty logits");
+        prs_.assign(prs, prs + n);
+        return draw(n);
+    }
     double temperature() const { return temperature_; }
     uint64_t draws() const { return rng_.words_consumed(); }
     uint32_t sample(const float *logits, size_t n) {
@@ -495,6 +512,33 @@ class LogitsProcessor {
         float sum = 0.f;
         for (size_t i = 0; i < n; i++) { prs_[i] = std::exp(prs_[i] - mx); sum += prs_[i]; }
         for (size_t i = 0; i < n; i++) prs_[i] /= sum;
+        return draw(n);
+    }
+
+   private:
+    // Sampling::TopP / TopK / TopKThenTopP: zero everything outside the kept prefix of the sorted order
+    void filter(size_t n) {
+        kept_ = n;
+        const bool k_on = top_k_ > 0 && top_k_ < n;
+        if (!top_p_on_ && !k_on) return;
+        order_.resize(n);
+        for (size_t i = 0; i < n; i++) order_[i] = (uint32_t)i;
+        std::stable_sort(order_.begin(), order_.end(), [&](uint32_t a, uint32_t b) { return prs_[a] > prs_[b]; });
+        size_t m = n;
+        if (top_p_on_) {
+            float cum = 0.f;
+            for (size_t j = 0; j < n; j++) {
+                volatile float c = cum + prs_[order_[j]];              // sequential f32, never widened
+                cum = c;
+                if (!(cum < top_p_)) { m = j + 1; break; }
+            }
+        }
+        if (k_on) m = std::min(m, top_k_);
+        for (size_t j = m; j < n; j++) prs_[order_[j]] = 0.f;
+        kept_ = m;
+    }
+    uint32_t draw(size_t n) {
+        filter(n);
         // WeightedIndex::new: running f32 total, left to right; weights must be >= 0 and not all zero
         float total = 0.f;
         for (size_t i = 0; i < n; i++) {
@@ -515,13 +559,29 @@ class LogitsProcessor {
         while (idx < n - 1 && cum <= chosen) { idx++; cum += prs_[idx]; }
         return (uint32_t)idx;
     }
-
-   private:
     static float mul_rn(float a, float b) { volatile float r = a * b; return r; }     // a product, never fused with an add
     StdRng rng_;
     bool sampling_ = false;
     double temperature_ = 0;
+    bool top_p_on_ = false;
+    float top_p_ = 0.f;
+    size_t top_k_ = 0, kept_ = 0;
     std::vector<float> prs_;
+    std::vector<uint32_t> order_;
+};
+
+// a request's sampling beyond its temperature (chat.rs would carry them as request.top_p / request.top_k); both empty: Sampling::All
+struct SamplingOptions {
+    std::optional<double> top_p;
+    std::optional<size_t> top_k;
+    fl_sampler to_ffi(double temperature, uint64_t draws_done) const {
+        fl_sampler s{};
+        s.struct_size = (uint32_t)sizeof(fl_sampler);
+        s.temperature = temperature; s.seed = 0; s.draws_done = draws_done;
+        s.top_p = top_p ? *top_p : 0.0;
+        s.top_k = top_k ? (int32_t)std::min<size_t>(*top_k, (size_t)INT32_MAX) : 0;
+        return s;
+    }
 };
 
 template <class M>
@@ -537,8 +597,13 @@ struct Model {                                // mod.rs:342-361
     // Model::generate (mod.rs:363-463) on token ids.  eos = tokenizer.token_to_id("</s>") (mod.rs:431).
     std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
                                        std::optional<uint32_t> eos = std::nullopt) {
+        return generate_ids(prompt, max_tokens, temperature, eos, SamplingOptions{});
+    }
+    // ... with top_p / top_k (LogitsProcessor::new(seed, Some(temperature), top_p) / from_sampling)
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt) {
         cache = M::initialize_cache(device, dtype);                       // mod.rs:370
-        LogitsProcessor logits_processor(0, (double)temperature);         // mod.rs:373-374 (Default::default() seed)
+        LogitsProcessor logits_processor(0, (double)temperature, opt.top_p, opt.top_k);   // mod.rs:373-374 (Default::default() seed)
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         Tensor input = Tensor::from_ids(prompt);                           // mod.rs:386-394
         std::vector<uint32_t> output_ids;
@@ -567,9 +632,14 @@ struct Model {                                // mod.rs:342-361
     template <class OnToken>
     size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
                                std::optional<uint32_t> eos, OnToken &&on_token) const {
+        return generate_stream_ids(prompt, max_tokens, temperature, eos, SamplingOptions{}, std::forward<OnToken>(on_token));
+    }
+    template <class OnToken>
+    size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                               std::optional<uint32_t> eos, const SamplingOptions &opt, OnToken &&on_token) const {
         M shared = model;                                                  // Arc::new(RwLock::new(model.model.clone()))
         typename M::Cache own = M::initialize_cache(device, dtype);       // one cache per stream
-        LogitsProcessor logits_processor(0, (double)temperature);
+        LogitsProcessor logits_processor(0, (double)temperature, opt.top_p, opt.top_k);
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         Tensor input = Tensor::from_ids(prompt);                           // mod.rs:283-291
         size_t pos = 0, n_forwards = 0;
@@ -624,11 +694,17 @@ class StreamBatcher {
     // a request as generate_stream sees it (token ids in, one callback per token out); returns its id
     uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, OnToken on_token,
                     OnDone on_done = {}) {
+        return submit(std::move(prompt), max_tokens, temperature, eos, SamplingOptions{}, std::move(on_token), std::move(on_done));
+    }
+    // ... with the request's own top_p / top_k: one batch mixes ArgMax, Sampling::All and top-p / top-k streams
+    uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, const SamplingOptions &opt,
+                    OnToken on_token, OnDone on_done = {}) {
+        if (opt.top_p && *opt.top_p != *opt.top_p) throw Error(FL_ERR_BAD_ARGUMENT, "top_p is NaN");
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         if (prompt.size() + 1 > cap_) throw Error(FL_ERR_BAD_ARGUMENT, "the prompt does not fit a slot's cache");
         if (!on_token) throw Error(FL_ERR_BAD_ARGUMENT, "null token callback");
         Request r;
-        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos;
+        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos; r.opt = opt;
         r.on_token = std::move(on_token); r.on_done = std::move(on_done);
         queue_.push_back(std::move(r));
         return next_id_;
@@ -653,15 +729,15 @@ class StreamBatcher {
         std::vector<uint32_t> first(B, 0), out(B * n, 0);
         std::vector<size_t> pos(B, 0), n_out(B, 0);
         std::vector<int64_t> eos(B, -1);
-        std::vector<fl_sampling> sp(B, fl_sampling{0.0, 0, 0});
+        std::vector<fl_sampler> sp(B, SamplingOptions{}.to_ffi(0.0, 0));
         for (size_t i = 0; i < B; i++) {
             Slot &sl = slots_[i];
             if (!sl.active) { fl_cache_reset(sl.cache); continue; }     // an empty slot computes a throw-away row at position 0
             first[i] = sl.tok; pos[i] = counter_ ? sl.calls : sl.pos;
             if (sl.req.eos) eos[i] = (int64_t)*sl.req.eos;
-            sp[i] = fl_sampling{(double)sl.req.temperature, 0, sl.draws};
+            sp[i] = sl.req.opt.to_ffi((double)sl.req.temperature, sl.draws);
         }
-        check(fl_batch_decode_each(batch_, first.data(), pos.data(), n, eos.data(), sp.data(), out.data(), n_out.data()), "Model forward pass failed");
+        check(fl_batch_decode_each_ex(batch_, first.data(), pos.data(), n, eos.data(), sp.data(), out.data(), n_out.data()), "Model forward pass failed");
         batch_steps += n;
         for (size_t i = 0; i < B; i++) {
             Slot &sl = slots_[i];
@@ -684,6 +760,7 @@ class StreamBatcher {
   private:
     struct Request {
         uint64_t id = 0; std::vector<uint32_t> prompt; size_t max_tokens = 0; float temperature = 0.f; std::optional<uint32_t> eos;
+        SamplingOptions opt;
         OnToken on_token; OnDone on_done;
     };
     struct Slot { fl_cache *cache = nullptr; bool active = false; Request req; size_t pos = 0, calls = 0, emitted = 0; uint32_t tok = 0; uint64_t draws = 0; };
@@ -691,9 +768,9 @@ class StreamBatcher {
     void admit(Slot &sl, Request r) {
         sl.req = std::move(r); sl.emitted = 0; sl.active = true;
         fl_cache_reset(sl.cache);
-        const fl_sampling sp{(double)sl.req.temperature, 0, 0};
+        const fl_sampler sp = sl.req.opt.to_ffi((double)sl.req.temperature, 0);
         uint32_t tok = 0;
-        check(fl_forward_sample(model_->m, sl.cache, sl.req.prompt.data(), sl.req.prompt.size(), 0, &sp, &tok), "Model forward pass failed");
+        check(fl_forward_sample_ex(model_->m, sl.cache, sl.req.prompt.data(), sl.req.prompt.size(), 0, &sp, &tok), "Model forward pass failed");
         prefills++;
         sl.pos = sl.req.prompt.size(); sl.calls = 1; sl.tok = tok; sl.draws = 1;
         if (sl.req.max_tokens == 0 || (sl.req.eos && tok == *sl.req.eos)) { finish(sl); return; }

@@ -240,6 +240,35 @@ int fl_forward_sample(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, s
 int fl_decode_sample(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
                      const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out);
 
+/* The same two calls with candle's other sampling modes (generation::Sampling::TopP / TopK / TopKThenTopP of candle-transformers
+ * 0.8 [UPSTREAM-RECALLED: restated from memory of upstream, not from a copy]), evaluated on the device inside the same decode loop.
+ * prs = softmax(logits / temperature) exactly as above.  The indices are ordered by prs descending, the LOWER index first among
+ * equal values (candle's stable sort_by(total_cmp)); a prefix of that order is kept, the rest get probability 0, and the draw is
+ * the multinomial above over the masked vector in vocabulary order (zeros included in the left-to-right fp32 cumulative weights).
+ *   top_p  0 < top_p < 1, compared as (float)top_p: walk the order with a sequential fp32 running sum from 0; an element is kept
+ *          while the sum BEFORE it is < top_p, so the prefix is the shortest whose sum is >= top_p (all of V if none is).
+ *          top_p <= 0 or >= 1: off (Sampling::All), as in candle.  NaN: FL_ERR_BAD_ARGUMENT.
+ *   top_k  0 < top_k < V: the first top_k of the order.  candle picks its k largest with select_nth_unstable_by and draws over
+ *          them in that unspecified order, so which token a given random word maps to is not defined upstream; HERE it is: the
+ *          masked form above.  The distribution is candle's.  top_k == 0 or >= V: off.  Negative: FL_ERR_BAD_ARGUMENT.
+ *   both   the prefix is min(top_k, what top_p keeps): candle's TopKThenTopP.
+ * Ties: temperature < 1e-7 stays ArgMax whatever top_p / top_k say, and ArgMax keeps the LAST maximal index; top_k = 1 keeps
+ * the LOWEST maximal index (the stable order above).  The two differ on exact ties of the maximum, as they do in candle.
+ * struct_size must be sizeof(fl_sampler) (FL_ERR_BAD_ARGUMENT otherwise); _reserved is 0. */
+typedef struct fl_sampler {
+    uint32_t struct_size;
+    int32_t  top_k;
+    double   temperature;
+    double   top_p;
+    uint64_t seed;
+    uint64_t draws_done;
+    int64_t  _reserved[2];
+} fl_sampler;
+int fl_forward_sample_ex(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos,
+                         const fl_sampler *sampler, uint32_t *token_out);
+int fl_decode_sample_ex(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
+                        const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out);
+
 /* Batched decode: B <= 64 caches of one model advanced together, one read of the weights per step for all
  * of them.  New capability: the reference runs concurrent streams as independent single-sequence loops
  * (mod.rs:137-238), each paying for the whole weight stream.  Every sequence keeps its own cache, RoPE
@@ -272,6 +301,10 @@ int  fl_batch_decode(fl_batch *b, const uint32_t *first_tokens, const size_t *po
  * differ in it.  draws_done lets a request span several calls, as in fl_decode_sample. */
 int  fl_batch_decode_each(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                           const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out);
+
+/* ... with an fl_sampler per sequence (samplers[i]; NULL: ArgMax for all): one batch mixes ArgMax, Sampling::All and top-p / top-k requests */
+int  fl_batch_decode_each_ex(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
+                             const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out);
 
 int fl_synchronize(fl_model *m);
 
@@ -343,6 +376,9 @@ int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *
 /* The token-selection kernel alone, for unit tests: `n_draws` successive selections from one host logits
  * vector (consuming successive words of the seeded stream; ArgMax when temperature < 1e-7). */
 int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out);
+
+/* ... with an fl_sampler; kept_out (optional, [n_draws]): how many tokens each draw kept (V when no filter is on) */
+int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, int64_t n_draws, uint32_t *tokens_out, int64_t *kept_out);
 
 /* The bf16 MFMA attention kernels alone, for unit tests against an fp64 reference (they are otherwise only seen through
  * whole-model logits).  One sequence: q [T][H*d] (RoPE already applied), k / v [s_past + T][Hkv*d], all bf16 row-major; the

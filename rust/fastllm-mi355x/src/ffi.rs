@@ -119,6 +119,20 @@ pub struct fl_sampling {
     pub draws_done: u64,
 }
 
+/// `fl_sampler`: temperature + top_p + top_k (candle's Sampling::TopP / TopK / TopKThenTopP); `struct_size` is
+/// `size_of::<fl_sampler>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fl_sampler {
+    pub struct_size: u32,
+    pub top_k: i32,
+    pub temperature: f64,
+    pub top_p: f64,
+    pub seed: u64,
+    pub draws_done: u64,
+    pub _reserved: [i64; 2],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct fl_kernel_stat {
@@ -211,6 +225,26 @@ extern "C" {
         tokens_out: *mut u32,
         n_out: *mut usize,
     ) -> c_int;
+    pub fn fl_forward_sample_ex(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        ids: *const u32,
+        t: usize,
+        pos: usize,
+        sampler: *const fl_sampler,
+        token_out: *mut u32,
+    ) -> c_int;
+    pub fn fl_decode_sample_ex(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: i64,
+        sampler: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+    ) -> c_int;
 
     pub fn fl_batch_create(m: *mut fl_model, caches: *const *mut fl_cache, n: usize, out: *mut *mut fl_batch) -> c_int;
     pub fn fl_batch_destroy(b: *mut fl_batch);
@@ -233,6 +267,16 @@ extern "C" {
         n_steps: usize,
         eos: *const i64,
         sampling: *const fl_sampling,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+    ) -> c_int;
+    pub fn fl_batch_decode_each_ex(
+        b: *mut fl_batch,
+        first_tokens: *const u32,
+        pos: *const usize,
+        n_steps: usize,
+        eos: *const i64,
+        samplers: *const fl_sampler,
         tokens_out: *mut u32,
         n_out: *mut usize,
     ) -> c_int;
@@ -272,6 +316,7 @@ extern "C" {
         ms_out: *mut f64,
     ) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
+    pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_attention(
         q: *const c_void,
         k: *const c_void,

@@ -15,4 +15,4 @@
 pub mod ffi;
 pub mod safe;
 
-pub use safe::{Batch, Cache, Config, DType, Error, Family, Model, Result, Sampling, TensorView, WeightFormat};
+pub use safe::{op_sample, Batch, Cache, Config, DType, Error, Family, Model, Result, Sampler, Sampling, TensorView, WeightFormat};

@@ -113,6 +113,42 @@ impl Sampling {
     }
 }
 
+/// LogitsProcessor::from_sampling(seed, Sampling::TopP / TopK / TopKThenTopP) on the device (`fl_sampler`).  `top_p` outside
+/// (0, 1) and `top_k` 0 are "off"; both off is `Sampling::All`.  The kept set is a prefix of the order by probability
+/// descending, the lower index first among equals; `top_k = 1` therefore keeps the LOWEST maximal index while ArgMax
+/// (`temperature < 1e-7`) keeps the LAST.
+#[derive(Clone, Copy, Debug)]
+pub struct Sampler {
+    pub temperature: f64,
+    pub top_p: f64,
+    pub top_k: u32,
+    pub seed: u64,
+    pub draws_done: u64,
+}
+impl Sampler {
+    fn to_ffi(self) -> ffi::fl_sampler {
+        ffi::fl_sampler {
+            struct_size: std::mem::size_of::<ffi::fl_sampler>() as u32,
+            top_k: self.top_k.min(i32::MAX as u32) as i32,
+            temperature: self.temperature,
+            top_p: self.top_p,
+            seed: self.seed,
+            draws_done: self.draws_done,
+            _reserved: [0; 2],
+        }
+    }
+}
+
+/// The token-selection kernel alone (`fl_op_sample_ex`): `n_draws` successive draws from one logits vector; returns the
+/// tokens and how many tokens each draw kept.
+pub fn op_sample(logits: &[f32], s: Sampler, n_draws: usize) -> Result<(Vec<u32>, Vec<i64>)> {
+    let mut toks = vec![0u32; n_draws];
+    let mut kept = vec![0i64; n_draws];
+    let sp = s.to_ffi();
+    check(unsafe { ffi::fl_op_sample_ex(logits.as_ptr(), logits.len() as i64, &sp, n_draws as i64, toks.as_mut_ptr(), kept.as_mut_ptr()) })?;
+    Ok((toks, kept))
+}
+
 /// `fl_weight_format`: what the single-stream decode step reads its projection weights as.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 #[repr(i32)]
@@ -217,6 +253,26 @@ impl Model {
         Ok(tok)
     }
 
+    /// `forward_sample` with top-p / top-k.
+    pub fn forward_sample_ex(&self, cache: &mut Cache, ids: &[u32], pos: usize, s: Sampler) -> Result<u32> {
+        let mut tok = 0u32;
+        let sp = s.to_ffi();
+        check(unsafe { ffi::fl_forward_sample_ex(self.raw, cache.raw, ids.as_ptr(), ids.len(), pos, &sp, &mut tok) })?;
+        Ok(tok)
+    }
+
+    /// `decode` with top-p / top-k.
+    pub fn decode_ex(&self, cache: &mut Cache, first_token: u32, pos: usize, n_steps: usize, eos: Option<u32>, s: Sampler) -> Result<Vec<u32>> {
+        let mut toks = vec![0u32; n_steps];
+        let mut n = 0usize;
+        let sp = s.to_ffi();
+        check(unsafe {
+            ffi::fl_decode_sample_ex(self.raw, cache.raw, first_token, pos, n_steps, eos.map(|e| e as i64).unwrap_or(-1), &sp, toks.as_mut_ptr(), &mut n)
+        })?;
+        toks.truncate(n);
+        Ok(toks)
+    }
+
     /// The loop body of `Model<M>::generate` (mod.rs:411-453) kept on the device; returns the tokens sampled after each
     /// step, shorter than `n_steps` when `eos` was sampled (which is not included).
     pub fn decode(&self, cache: &mut Cache, first_token: u32, pos: usize, n_steps: usize, eos: Option<u32>, sampling: Option<Sampling>) -> Result<Vec<u32>> {
@@ -296,6 +352,22 @@ impl<'a> Batch<'a> {
         let spp = sp.as_ref().map(|s| s as *const ffi::fl_sampling).unwrap_or(ptr::null());
         check(unsafe {
             ffi::fl_batch_decode(self.raw, first_tokens.as_ptr(), pos.as_ptr(), n_steps, eos.map(|e| e as i64).unwrap_or(-1), spp, toks.as_mut_ptr(), n_out.as_mut_ptr())
+        })?;
+        Ok((0..self.n).map(|i| toks[i * n_steps..i * n_steps + n_out[i]].to_vec()).collect())
+    }
+
+    /// ... with every sequence's own EOS and sampler (`None`: ArgMax): one batch mixes ArgMax, `Sampling::All` and top-p / top-k.
+    pub fn decode_each(&mut self, first_tokens: &[u32], pos: &[usize], n_steps: usize, eos: &[Option<u32>], samplers: &[Option<Sampler>]) -> Result<Vec<Vec<u32>>> {
+        if first_tokens.len() != self.n || pos.len() != self.n || eos.len() != self.n || samplers.len() != self.n {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("batch of {} sequences: every slice must have that length", self.n) });
+        }
+        let mut toks = vec![0u32; self.n * n_steps.max(1)];
+        let mut n_out = vec![0usize; self.n];
+        let greedy = Sampler { temperature: 0.0, top_p: 0.0, top_k: 0, seed: 0, draws_done: 0 };
+        let sp: Vec<ffi::fl_sampler> = samplers.iter().map(|s| s.unwrap_or(greedy).to_ffi()).collect();
+        let e: Vec<i64> = eos.iter().map(|x| x.map(|v| v as i64).unwrap_or(-1)).collect();
+        check(unsafe {
+            ffi::fl_batch_decode_each_ex(self.raw, first_tokens.as_ptr(), pos.as_ptr(), n_steps, e.as_ptr(), sp.as_ptr(), toks.as_mut_ptr(), n_out.as_mut_ptr())
         })?;
         Ok((0..self.n).map(|i| toks[i * n_steps..i * n_steps + n_out[i]].to_vec()).collect())
     }
