@@ -69,6 +69,22 @@ def make_sampler(temperature, seed=0, draws_done=0, top_p=None, top_k=None):
                      seed, draws_done)
 
 
+class FlLookup(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_draft", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32),
+                ("_pad", C.c_int32), ("_reserved", C.c_int64 * 2)]
+
+
+class FlSpecStats(C.Structure):
+    _fields_ = [("steps", C.c_uint64), ("drafted", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+VERIFY_MAX_DRAFT = 15
+
+
+def make_lookup(max_draft=7, ngram_max=3, ngram_min=1):
+    return FlLookup(C.sizeof(FlLookup), int(max_draft), int(ngram_max), int(ngram_min))
+
+
 class FlKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_double),
                 ("flops", C.c_double)]
@@ -137,6 +153,12 @@ def lib():
                                    C.POINTER(C.c_double)]
         L.fl_op_quantize_rows.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp, vp]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
+        L.fl_cache_truncate.argtypes = [vp, sz]
+        L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
+        L.fl_lookup_draft.argtypes = [vp, sz, C.POINTER(FlLookup), sz, vp, C.POINTER(sz)]
+        L.fl_decode_lookup.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), vp, C.POINTER(sz),
+                                       C.POINTER(FlSpecStats)]
+        L.fl_op_verify_select.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -159,6 +181,28 @@ def op_sample(logits, n_draws, temperature, seed=0, draws_done=0, top_p=None, to
     sp = FlSampling(temperature, seed, draws_done)
     _check(lib().fl_op_sample(a.ctypes.data, a.size, C.byref(sp), n_draws, out.ctypes.data))
     return out
+
+
+def lookup_draft(history, limit, max_draft=7, ngram_max=3, ngram_min=1):
+    """fl_lookup_draft (pure host): the prompt-lookup draft for `history`, at most min(max_draft, limit) ids."""
+    h = np.ascontiguousarray(history, dtype=np.uint32)
+    out = np.zeros(max(int(limit), 1), dtype=np.uint32)
+    n = C.c_size_t(0)
+    o = make_lookup(max_draft, ngram_max, ngram_min)
+    _check(lib().fl_lookup_draft(h.ctypes.data if h.size else None, h.size, C.byref(o), int(limit), out.ctypes.data, C.byref(n)))
+    return out[: n.value]
+
+
+def op_verify_select(logits, draft):
+    """The verify step's selection kernel alone: logits [T, V] float32, draft [T-1] -> (argmax uint32 [T], n_accepted)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    d = np.ascontiguousarray(draft, dtype=np.uint32)
+    assert d.shape == (T - 1,)
+    out = np.zeros(T, dtype=np.uint32)
+    n = C.c_int64(-1)
+    _check(lib().fl_op_verify_select(a.ctypes.data, T, V, d.ctypes.data if d.size else None, out.ctypes.data, C.byref(n)))
+    return out, n.value
 
 
 def abi_version():
@@ -282,6 +326,31 @@ class Model:
         toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
         n = C.c_size_t(0)
         _check(lib().fl_decode_greedy(self._h, cache._h, int(first_token), pos, n_steps, eos, toks.ctypes.data, C.byref(n)))
+        return toks[: n.value]
+
+    def forward_verify(self, cache, token, draft, pos, want_logits=False):
+        """fl_forward_verify: one forward of [token, *draft]; returns (tokens, logits [len(draft) + 1, V] or None) -- the accepted
+        drafts followed by the model's own next token."""
+        d = np.ascontiguousarray(draft, dtype=np.uint32)
+        toks = np.zeros(d.size + 1, dtype=np.uint32)
+        lg = np.empty((d.size + 1, self.V), dtype=np.float32) if want_logits else None
+        n = C.c_size_t(0)
+        _check(lib().fl_forward_verify(self._h, cache._h, int(token), d.ctypes.data if d.size else None, d.size, pos, toks.ctypes.data,
+                                       C.byref(n), lg.ctypes.data if want_logits else None))
+        return toks[: n.value], lg
+
+    def decode_lookup(self, cache, corpus, first_token, pos, n_steps, eos=-1, max_draft=7, ngram_max=3, ngram_min=1, return_stats=False):
+        """fl_decode_lookup: the greedy loop built from verify steps with prompt-lookup drafts out of corpus ++ [first_token] ++ output.
+        return_stats: also a dict(steps, drafted, accepted)."""
+        cp = np.ascontiguousarray(corpus, dtype=np.uint32)
+        toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
+        n = C.c_size_t(0)
+        o = make_lookup(max_draft, ngram_max, ngram_min)
+        st = FlSpecStats()
+        _check(lib().fl_decode_lookup(self._h, cache._h, cp.ctypes.data if cp.size else None, cp.size, int(first_token), pos, n_steps, eos,
+                                      C.byref(o), toks.ctypes.data, C.byref(n), C.byref(st)))
+        if return_stats:
+            return toks[: n.value], dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted)
         return toks[: n.value]
 
     def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None):
@@ -440,6 +509,10 @@ class Cache:
 
     def reset(self):
         lib().fl_cache_reset(self._h)
+
+    def truncate(self, n):
+        """fl_cache_truncate: forget everything from position n on."""
+        _check(lib().fl_cache_truncate(self._h, int(n)))
 
     def __len__(self):
         return lib().fl_cache_len(self._h)

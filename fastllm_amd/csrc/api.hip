@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "model.h"
+#include "lookup.h"
 
 using namespace fl;
 
@@ -189,6 +190,68 @@ int fl_forward(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t p
     return guarded([&]() -> int {
         if (!logits_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null logits_out");
         return forward(M(m), C(c), ids, T, pos, logits_out, nullptr);
+    });
+}
+
+int fl_cache_truncate(fl_cache *c, size_t len) {
+    return guarded([&]() -> int {
+        return cache_truncate(C(c), len);
+    });
+}
+
+int fl_forward_verify(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
+                      size_t *n_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return forward_verify(M(m), C(c), token, draft, n_draft, pos, tokens_out, n_out, logits_out);
+    });
+}
+
+int fl_lookup_draft(const uint32_t *history, size_t n_history, const fl_lookup *opts, size_t limit, uint32_t *draft_out, size_t *n_draft_out) {
+    return guarded([&]() -> int {
+        if (n_draft_out) *n_draft_out = 0;
+        FL_TRY(check_lookup(opts));
+        if (!n_draft_out || (n_history && !history) || (limit && !draft_out)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_lookup_draft: null argument");
+        *n_draft_out = lookup_draft(history, n_history, opts->max_draft, opts->ngram_max, opts->ngram_min, limit, draft_out);
+        return FL_OK;
+    });
+}
+
+int fl_decode_lookup(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos, size_t n_steps,
+                     int64_t eos, const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return guarded([&]() -> int {
+        return decode_lookup(M(m), C(c), corpus, n_corpus, first_token, pos, n_steps, eos, opts, tokens_out, n_out, stats);
+    });
+}
+
+int fl_op_verify_select(const float *logits, int64_t T, int64_t V, const uint32_t *draft, uint32_t *argmax_out, int64_t *n_accepted_out) {
+    return guarded([&]() -> int {
+        if (!logits || !argmax_out || !n_accepted_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || T > kVerifyMaxRows || V <= 0 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size (1 <= T <= %d)", kVerifyMaxRows);
+        if (T > 1 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null draft");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        struct Bufs { float *lg = 0; uint32_t *dr = 0, *out = 0; hipStream_t s = 0;
+                      ~Bufs() { (void)hipFree(lg); (void)hipFree(dr); (void)hipFree(out); if (s) (void)hipStreamDestroy(s); } } B;
+        FL_HIP(hipStreamCreate(&B.s));
+        FL_HIP(hipMalloc((void **)&B.lg, (size_t)T * V * 4));
+        FL_HIP(hipMalloc((void **)&B.dr, (size_t)kVerifyMaxRows * 4));
+        FL_HIP(hipMalloc((void **)&B.out, (size_t)kVerifyWords * 4));
+        FL_HIP(hipMemcpy(B.lg, logits, (size_t)T * V * 4, hipMemcpyHostToDevice));
+        if (T > 1) FL_HIP(hipMemcpy(B.dr, draft, (size_t)(T - 1) * 4, hipMemcpyHostToDevice));
+        FL_HIP(hipMemset(B.out, 0, (size_t)kVerifyWords * 4));
+        Launcher L; L.stream = B.s;
+        uint32_t host[2][kVerifyWords];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the second launch meets the ticket word the first one put back
+            FL_TRY(launch_verify_select(L, B.lg, V, (int)T, B.dr, B.out));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep], B.out, sizeof host[rep], hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0], host[1], sizeof host[0]) || host[1][kVerifyTicket] != 0)
+            FL_FAIL(FL_ERR_HIP, "verify_select: a repeated launch gave another result (ticket %u)", host[1][kVerifyTicket]);
+        for (int64_t t = 0; t < T; t++) argmax_out[t] = host[0][t];
+        *n_accepted_out = (int64_t)host[0][kVerifyNacc];
+        return FL_OK;
     });
 }
 

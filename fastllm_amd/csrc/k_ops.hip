@@ -954,6 +954,38 @@ int launch_select_advance(Launcher &L, const float *logits, int64_t V, StepState
                     scratch, out_tokens, advance, cand, epoch_bump);
 }
 
+// ------------------------------------------------------------------------------- verify step: ArgMax per row + acceptance scan
+// fl_forward_verify: logits [T][V] of the ids [token, draft[0..T-1)].  One workgroup of 1024 lanes per row takes its row's ArgMax
+// with argmax_last (ties -> the last maximal index, NaN as in select_advance) and publishes it; the workgroup that arrives last
+// (one atomic ticket; nobody waits for anybody) scans the at most 16 ids: n_acc = the largest j <= T - 1 with draft[i] == a[i] for
+// all i < j.  out: [0, T) the ArgMax ids, [kVerifyNacc] n_acc, [kVerifyTicket] the ticket, which the last workgroup puts back to 0
+// so that the launch can be repeated (or captured) without a memset.
+// (One workgroup per row, not a candidate pass over several: at V = 152 064 a row is 608 KB, which 1024 lanes fetch in five round
+// trips of eight 16-byte loads -- the 16 rows run on 16 CUs side by side and the launch is a few microseconds next to a forward of
+// milliseconds.)
+__global__ __launch_bounds__(1024) void verify_select_kernel(const float *__restrict__ logits, int V, int T,
+                                                             const uint32_t *__restrict__ draft, uint32_t *__restrict__ out) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int row = blockIdx.x;
+    const int idx = argmax_last(logits + (size_t)row * V, V, bv, bi);
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(&out[row], (uint32_t)idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();                                                   // the id is visible before the ticket is
+    const uint32_t ticket = __hip_atomic_fetch_add(&out[kVerifyTicket], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket != (uint32_t)(T - 1)) return;
+    __threadfence();
+    uint32_t n = 0;
+    while (n < (uint32_t)(T - 1) && draft[n] == __hip_atomic_load(&out[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) n++;
+    out[kVerifyNacc] = n;
+    __hip_atomic_store(&out[kVerifyTicket], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int launch_verify_select(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft, uint32_t *out) {
+    if (T < 1 || T > kVerifyMaxRows || V <= 0 || V > 0x7fffffff) FL_FAIL(FL_ERR_BAD_ARGUMENT, "verify_select: bad shape");
+    return L.launch(KC_ARGMAX, (double)V * 4 * T, 0, verify_select_kernel, dim3((unsigned)T), dim3(1024), 0, logits, (int)V, T, draft, out);
+}
+
 // ------------------------------------------------------------------------------- local shard reduce
 // FL_TP_EMULATED: all shards live on one GPU, so all-reduce(sum) is a local sum written back to
 // every shard's buffer.  Fixed summation order s = 0..n-1 (reproducible).

@@ -352,6 +352,11 @@ int launch_select_advance(Launcher &L, const float *logits, int64_t V, StepState
                           uint32_t *out_tokens, int advance,
                           const ArgmaxCand *cand = nullptr /* the lm_head launch's candidates: ArgMax without reading the vocabulary again */,
                           uint32_t *epoch_bump = nullptr /* the decode engine's tag epoch: += 1 per forward */);
+// fl_forward_verify's selection: logits [T][V] -> out[t] = ArgMax of row t (ties: last max index), out[kVerifyNacc] = how many of
+// draft[0 .. T-1) the rows confirm (draft[i] == out[i] for all i below it).  out: kVerifyWords words, zero before the FIRST launch
+// (the ticket word is put back by the kernel itself)
+constexpr int kVerifyMaxRows = 16, kVerifyNacc = 16, kVerifyTicket = 17, kVerifyWords = 18;
+int launch_verify_select(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft /* [T-1] device */, uint32_t *out);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

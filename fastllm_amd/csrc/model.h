@@ -92,6 +92,8 @@ struct Shard {
     ArgmaxCand *amax = nullptr;      // [kMaxArgmaxCand] ArgMax candidates left by the decode step's lm_head launch (GemvArgs::amax)
     bool amax_valid = false;         // ... and whether the forward enqueued last produced them (host-side, per enqueue)
     float *logits_full = nullptr;    // [V]
+    float *verify_logits = nullptr;  // [kVerifyMaxRows][V] all rows' logits of a verify step (fl_forward_verify); allocated at a model's first one
+    uint32_t *verify_out = nullptr;  // [kVerifyWords] its ArgMax ids, accepted count and arrival ticket (launch_verify_select)
     // the persistent decode engine (k_engine.hip): granule edges of one launch and the tag epoch
     unsigned long long *eng_edge[3] = {};   // o_proj deltas [h] | silu(g)*u pairs [Ip/2] | down_proj deltas [h]
     uint32_t *eng_epoch = nullptr;
@@ -114,6 +116,7 @@ struct Model {
     float **emu_ptrs = nullptr;  // EMULATED: device table of per-shard buffers for the local reduce
     float *host_logits = nullptr;   // pinned staging [V]
     uint32_t *host_tokens = nullptr;
+    uint32_t *host_verify = nullptr;   // pinned [kVerifyWords]: what a verify step brings back
     bool use_graph = true;
     bool fused_decode = true;    // norm / RoPE / KV-append fused into the GEMV kernels
     int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;   // FL_WEIGHTS_E4M3_ROW: the decode step streams e4m3 weights (k_gemv_w8.hip)
@@ -237,6 +240,14 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
             const fl_sampler *sampling = nullptr);
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
                   uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr);
+
+// fl_cache_truncate / fl_forward_verify / fl_decode_lookup (speculative greedy decode)
+int cache_truncate(Cache *c, size_t len);
+int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
+                   size_t *n_out, float *logits_out);
+int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
+int check_lookup(const fl_lookup *opts);     // FL_ERR_BAD_ARGUMENT: null, wrong struct_size, a range error
 
 // most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (model.hip)
 int ksplit_cap(int64_t T);

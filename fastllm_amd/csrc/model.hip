@@ -13,6 +13,7 @@
 //   lm_head [Vs, h], embed [V, h], norms fp32, RoPE cos/sin fp32 [max_pos][d/2]
 //   KV cache [L][Hkvs][max_seq][d] x2, written in place (no Tensor::cat copy)
 #include "model.h"
+#include "lookup.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -314,6 +315,7 @@ Model::~Model() {
     if (emu_ptrs) (void)hipFree(emu_ptrs);
     if (host_logits) (void)hipHostFree(host_logits);
     if (host_tokens) (void)hipHostFree(host_tokens);
+    if (host_verify) (void)hipHostFree(host_verify);
     if (host_state) (void)hipHostFree(host_state);
     for (auto &r : prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
 }
@@ -1290,7 +1292,9 @@ static int enqueue_prefill_tp_overlap(Model *m, Cache *c, int64_t T) {
 
 // Enqueue one forward over T tokens on every local shard.  The step state (pos, len, token) of the
 // cache must already be set on the device.  ids_dev == null: the single token comes from the state.
-static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_scratch, int64_t len_hint) {
+// all_rows (a verify step, one shard): the final norm and lm_head run on EVERY row, logits [T][V] into all_rows, and the last row's
+// logits are NOT left in logits_full; null: the last position only, exactly the launches there have always been.
+static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_scratch, int64_t len_hint, float *all_rows = nullptr) {
     for (auto &sh : m->shards) sh.amax_valid = false;                  // (set by the path whose lm_head launch leaves ArgMax candidates)
     if (T == 1 && !pre && !ids_in_scratch && m->fused_decode) return enqueue_decode_fused(m, c, len_hint);
     if (pre && ids_in_scratch && m->tp > 1 && tune(TK_TP_OVERLAP) && T >= tune(TK_TP_OVERLAP_MIN_T) && !m->profiling &&
@@ -1398,6 +1402,15 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             }
         }
         FL_TRY(all_reduce_delta(m, pre, T * D.h));
+    }
+    if (all_rows) {
+        // every row: the residual epilogue of the last down_proj has left xn and 1/rms of all T rows (norm_done; the last layer's is
+        // always finalized to the vector), or rmsnorm_add produces them here
+        Shard &sh = m->shards[0]; Scratch &sc = SC(sh);
+        FL_HIP(hipSetDevice(sh.device));
+        Launcher L = make_launcher(m, sh);
+        if (!norm_done) FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
+        return launch_linear(L, dt, sh.lm_head, sc.xn, nullptr, all_rows, T, sh.Vs, D.h, EPI_F32, sc.inv_rms);
     }
     // narrow(1, T-1, 1) -> final norm -> lm_head on the last position only (K12)
     for (size_t i = 0; i < ns; i++) {
@@ -1610,6 +1623,143 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
         done += nb;
     }
     if (n_out) *n_out = done;
+    return FL_OK;
+}
+
+// ------------------------------------------------------------------------------- speculative greedy decode
+int cache_truncate(Cache *c, size_t len) {
+    if (!c) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_truncate: null cache");
+    if (len > c->len) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_truncate: %zu is beyond the cached length %zu", len, c->len);
+    c->len = len;                                // (the device StepState is written from this at the start of every call)
+    return FL_OK;
+}
+
+int check_lookup(const fl_lookup *o) {
+    if (!o) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_lookup");
+    if (o->struct_size != sizeof(fl_lookup)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_lookup.struct_size is %u, expected %zu", o->struct_size, sizeof(fl_lookup));
+    if (o->max_draft < 0 || o->max_draft > FL_VERIFY_MAX_DRAFT) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_lookup.max_draft %d outside 0 .. %d", o->max_draft, FL_VERIFY_MAX_DRAFT);
+    if (o->ngram_min < 1 || o->ngram_min > o->ngram_max || o->ngram_max > kLookupMaxNgram)
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_lookup: need 1 <= ngram_min <= ngram_max <= %d (got %d, %d)", kLookupMaxNgram, o->ngram_min, o->ngram_max);
+    return FL_OK;
+}
+
+// what a verify step may and may not be asked: everything here is decided before the device is touched
+static int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos) {
+    if (n_draft > FL_VERIFY_MAX_DRAFT) FL_FAIL(FL_ERR_BAD_ARGUMENT, "n_draft %zu exceeds FL_VERIFY_MAX_DRAFT (%d)", n_draft, FL_VERIFY_MAX_DRAFT);
+    FL_TRY(check_call(m, c, n_draft + 1, pos));
+    if (n_draft > 0 && m->tp > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "the verify step does not run under tensor parallelism (tp_size %d)", m->tp);
+    if (m->D.window >= 0 && (int64_t)n_draft > m->D.window)
+        FL_FAIL(FL_ERR_UNSUPPORTED, "n_draft %zu exceeds sliding_window %lld: the rows would no longer equal successive decode steps", n_draft, (long long)m->D.window);
+    return FL_OK;
+}
+
+// one verify step with the model locked and the arguments checked; host_verify holds the ids and the accepted count afterwards
+static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, float *logits_out) {
+    const Dims &D = m->D;
+    Shard &sh = m->shards[0];
+    const int64_t T = (int64_t)n_draft + 1;
+    FL_HIP(hipSetDevice(sh.device));
+    if (!sh.verify_logits) {
+        FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_out, kVerifyWords * 4, &m->hbm_bytes));
+        FL_HIP(hipMemsetAsync(sh.verify_out, 0, kVerifyWords * 4, sh.stream));
+        FL_HIP(hipHostMalloc((void **)&m->host_verify, kVerifyWords * 4, hipHostMallocDefault));
+        FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_logits, (size_t)kVerifyMaxRows * D.V * 4, &m->hbm_bytes));
+    }
+    if (sh.pre.cap_T < T) FL_TRY(grow_prefill_scratch(m, sh, T));
+    uint32_t *ids = m->host_tokens;                                  // pinned, and idle until this call's sync
+    ids[0] = token;
+    for (size_t i = 0; i < n_draft; i++) ids[1 + i] = draft[i];
+    FL_HIP(hipMemcpyAsync(sh.pre.ids, ids, (size_t)T * 4, hipMemcpyHostToDevice, sh.stream));
+    const SampleState argmax{};
+    FL_TRY(set_state(m, c, token, pos, c->len, 0, -1, c->len, &argmax));
+    FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, sh.verify_logits));
+    Launcher L = make_launcher(m, sh);
+    FL_TRY(launch_verify_select(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));
+    FL_HIP(hipMemcpyAsync(m->host_verify, sh.verify_out, (kVerifyNacc + 1) * 4, hipMemcpyDeviceToHost, sh.stream));
+    FL_HIP(hipMemcpyAsync(m->host_state, c->shards[0].st, sizeof(StepState), hipMemcpyDeviceToHost, sh.stream));
+    FL_TRY(sync_all(m));
+    if (m->host_state->error) FL_FAIL(FL_ERR_HIP, "device-side wait gave up (code 0x%x): kernels did not make progress", m->host_state->error);
+    if (m->host_verify[kVerifyNacc] > n_draft) FL_FAIL(FL_ERR_HIP, "verify step: accepted count %u out of range", m->host_verify[kVerifyNacc]);
+    if (logits_out) FL_HIP(hipMemcpy(logits_out, sh.verify_logits, (size_t)T * D.V * 4, hipMemcpyDeviceToHost));
+    c->len += (size_t)m->host_verify[kVerifyNacc] + 1;               // rejected rows' K/V stay behind the length; the next append overwrites them
+    return FL_OK;
+}
+
+int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
+                   size_t *n_out, float *logits_out) {
+    if (n_out) *n_out = 0;
+    if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null tokens_out or n_out");
+    if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null draft");
+    FL_TRY(check_verify(m, c, n_draft, pos));
+    if ((int64_t)token >= m->D.V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "token id %u out of range (vocab %lld)", token, (long long)m->D.V);
+    for (size_t i = 0; i < n_draft; i++)
+        if ((int64_t)draft[i] >= m->D.V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "draft id %u out of range (vocab %lld)", draft[i], (long long)m->D.V);
+    if (n_draft == 0) {                                              // the decode step itself: its mask, its kernels
+        FL_TRY(forward(m, c, &token, 1, pos, logits_out, tokens_out));
+        *n_out = 1;
+        return FL_OK;
+    }
+    debug_inject("forward");
+    std::lock_guard<std::mutex> lock(m->mu);
+    FL_TRY(verify_step(m, c, token, draft, n_draft, pos, logits_out));
+    const size_t n = (size_t)m->host_verify[kVerifyNacc] + 1;
+    for (size_t i = 0; i < n; i++) tokens_out[i] = m->host_verify[i];
+    *n_out = n;
+    return FL_OK;
+}
+
+int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    if (n_out) *n_out = 0;
+    if (stats) *stats = fl_spec_stats{};
+    FL_TRY(check_lookup(opts));
+    if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null n_out");
+    if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null corpus");
+    if (n_steps == 0) return FL_OK;
+    if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null tokens_out");
+    FL_TRY(check_call(m, c, n_steps, pos));
+    if ((int64_t)first >= m->D.V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "token id %u out of range", first);
+    if (m->tp > 1 && opts->max_draft > 0) FL_FAIL(FL_ERR_UNSUPPORTED, "the verify step does not run under tensor parallelism (tp_size %d)", m->tp);
+    const size_t V = (size_t)m->D.V, L0 = c->len;
+    std::vector<uint32_t> hist;
+    hist.reserve(n_corpus + 1 + n_steps + FL_VERIFY_MAX_DRAFT + 1);
+    for (size_t i = 0; i < n_corpus; i++) hist.push_back(corpus[i]);
+    hist.push_back(first);
+    uint32_t draft[FL_VERIFY_MAX_DRAFT + 1], got[FL_VERIFY_MAX_DRAFT + 1];
+    uint32_t tok = first;
+    size_t emitted = 0;
+    while (emitted < n_steps) {
+        // room: this step caches `tok` and up to n_draft drafts, and every later token still needs its own position
+        size_t limit = n_steps - emitted - 1;
+        limit = std::min(limit, c->max_seq - c->len - 1);
+        limit = std::min(limit, (size_t)m->D.max_pos - (pos + emitted) - 1);
+        if (m->D.window >= 0) limit = std::min(limit, (size_t)m->D.window);
+        size_t nd = lookup_draft(hist.data(), hist.size(), opts->max_draft, opts->ngram_max, opts->ngram_min, limit, draft);
+        for (size_t i = 0; i < nd; i++) if (draft[i] >= V) { nd = i; break; }      // (a corpus id the model does not have ends the draft)
+        size_t n = 0;
+        if (nd == 0) {
+            FL_TRY(forward(m, c, &tok, 1, pos + emitted, nullptr, got));
+            n = 1;
+        } else {
+            std::lock_guard<std::mutex> lock(m->mu);
+            FL_TRY(verify_step(m, c, tok, draft, nd, pos + emitted, nullptr));
+            n = (size_t)m->host_verify[kVerifyNacc] + 1;
+            for (size_t i = 0; i < n; i++) got[i] = m->host_verify[i];
+        }
+        if (stats) { stats->steps += 1; stats->drafted += nd; stats->accepted += n - 1; }
+        for (size_t i = 0; i < n; i++) {
+            if (eos >= 0 && (int64_t)got[i] == eos) {
+                // the forward that produced EOS was needed; what was accepted after it is dropped (fl_decode_greedy's length)
+                c->len = L0 + emitted + 1;
+                *n_out = emitted;
+                return FL_OK;
+            }
+            tokens_out[emitted++] = got[i];
+            hist.push_back(got[i]);
+        }
+        tok = got[n - 1];
+    }
+    *n_out = emitted;
     return FL_OK;
 }
 

@@ -334,6 +334,11 @@ struct LlamaWithConfig {
         logits.shape = {1, logits.owner ? (int64_t)static_cast<std::vector<float> *>(logits.owner.get())->size() : 0};   // [1, V] f32
         return logits;
     }
+    // the handles and the position bookkeeping the prompt-lookup loop needs (Model<M>::generate_ids with LookupOptions)
+    fl_model *raw_model() const { return model->m; }
+    fl_cache *raw_cache(Cache &cache) const { return cache.inner->c; }
+    size_t rope_offset(size_t pos, const Cache &) const { return pos; }
+    void advance(Cache &, size_t) const {}
     static const char *get_family() { return "Llama"; }                                             // llama.rs:153
     static bool supports_architecture(const std::string &a) { return a == "LlamaForCausalLM"; }     // llama.rs:157-159
 
@@ -397,6 +402,12 @@ struct CounterFamily {
         cache.increment_offset();
         return logits;
     }
+    // the prompt-lookup loop (Model<M>::generate_ids with LookupOptions): the cache exists after the prompt's forward; a verify step
+    // of n rows stands for n calls of `forward`, so the per-call counter (quirk C.1) advances by n and row t runs at counter + t
+    fl_model *raw_model() const { return model->m; }
+    fl_cache *raw_cache(Cache &cache) const { return cache.kv->c; }
+    size_t rope_offset(size_t pos, const Cache &cache) const { return pos_mode() == PosMode::Reference ? cache.seqlen_offset : pos; }
+    void advance(Cache &cache, size_t calls) const { cache.seqlen_offset += calls; }
 };
 
 struct MistralWithConfig : CounterFamily<FL_FAMILY_MISTRAL, false> {
@@ -584,6 +595,23 @@ struct SamplingOptions {
     }
 };
 
+// Prompt-lookup drafting for greedy requests (fl_lookup): the continuation that followed the most recent earlier occurrence of the
+// current n-gram is verified in one forward (fl_forward_verify).  New capability; the tokens are those of the plain greedy loop.
+struct LookupOptions {
+    int max_draft = 7, ngram_max = 3, ngram_min = 1;
+    fl_lookup to_ffi() const {
+        fl_lookup o{};
+        o.struct_size = (uint32_t)sizeof(fl_lookup);
+        o.max_draft = max_draft; o.ngram_max = ngram_max; o.ngram_min = ngram_min;
+        return o;
+    }
+};
+inline void require_greedy(float temperature) {
+    if (!(temperature < 1e-7))
+        throw Error(FL_ERR_UNSUPPORTED, "prompt-lookup decoding is greedy only: temperature must be below 1e-7 (speculative sampling would change "
+                                        "how the seeded stream is consumed)");
+}
+
 template <class M>
 struct Model {                                // mod.rs:342-361
     M model;
@@ -620,6 +648,84 @@ struct Model {                                // mod.rs:342-361
             pos += 1;                                                      // mod.rs:452
         }
         return output_ids;
+    }
+
+    // ... a greedy request (temperature < 1e-7, else FL_ERR_UNSUPPORTED) decoded with prompt-lookup drafts: fl_forward for the prompt,
+    // ArgMax of its logits, then fl_decode_lookup for the other max_tokens - 1 tokens with the prompt as the search text.  The ids
+    // are those of the overloads above (up to bf16 near-ties, include/fastllm_mi355x.h); `forwards` counts the prompt's forward and
+    // the verify steps -- the reference's wasted forward behind the last token (C.5) is not run.
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const LookupOptions &lookup, fl_spec_stats *stats = nullptr) {
+        require_greedy(temperature);
+        cache = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        std::vector<uint32_t> output_ids;
+        forwards = 0;
+        if (stats) *stats = fl_spec_stats{};
+        Tensor logits = model.forward(Tensor::from_ids(prompt), 0, cache); forwards++;
+        if (max_tokens == 0) return output_ids;
+        const uint32_t first = argmax_last(logits.f32(), (size_t)logits.elem_count());
+        if (eos && first == *eos) return output_ids;
+        output_ids.assign(max_tokens, 0);
+        output_ids[0] = first;
+        size_t n = 0;
+        if (max_tokens > 1) {
+            const fl_lookup o = lookup.to_ffi();
+            fl_spec_stats st{};
+            fl_cache *c = model.raw_cache(cache);
+            const size_t len0 = fl_cache_len(c);
+            check(fl_decode_lookup(model.raw_model(), c, prompt.data(), prompt.size(), first, model.rope_offset(prompt.size(), cache), max_tokens - 1,
+                                   eos ? (int64_t)*eos : -1, &o, output_ids.data() + 1, &n, &st), "Model forward pass failed");
+            model.advance(cache, fl_cache_len(c) - len0);
+            forwards += (size_t)st.steps;
+            if (stats) *stats = st;
+        }
+        output_ids.resize(1 + n);
+        return output_ids;
+    }
+
+    // ... and as a stream: one fl_lookup_draft + fl_forward_verify step at a time, every token of a step to `on_token` before the
+    // next step (a dropped receiver ends the stream after the step it was in).  Returns the forwards executed.
+    template <class OnToken>
+    size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                               std::optional<uint32_t> eos, const LookupOptions &lookup, OnToken &&on_token) const {
+        require_greedy(temperature);
+        M shared = model;
+        typename M::Cache own = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        size_t n_forwards = 0;
+        Tensor logits = shared.forward(Tensor::from_ids(prompt), 0, own); n_forwards++;
+        if (max_tokens == 0) return n_forwards;
+        uint32_t tok = argmax_last(logits.f32(), (size_t)logits.elem_count());
+        if ((eos && tok == *eos) || !on_token(tok)) return n_forwards;
+        const fl_lookup o = lookup.to_ffi();
+        fl_model_info info; check(fl_model_get_info(shared.raw_model(), &info), "fl_model_get_info");
+        fl_cache *c = shared.raw_cache(own);
+        std::vector<uint32_t> history(prompt);
+        history.push_back(tok);
+        size_t emitted = 1, pos = prompt.size();
+        uint32_t draft[FL_VERIFY_MAX_DRAFT + 1], got[FL_VERIFY_MAX_DRAFT + 1];
+        while (emitted < max_tokens) {
+            const size_t rope = shared.rope_offset(pos, own);
+            size_t limit = max_tokens - emitted - 1;
+            limit = std::min(limit, fl_cache_capacity(c) - fl_cache_len(c) - 1);
+            limit = std::min(limit, (size_t)info.cfg.max_position_embeddings - rope - 1);
+            if (info.cfg.family != FL_FAMILY_LLAMA && info.cfg.sliding_window > 0) limit = std::min(limit, (size_t)info.cfg.sliding_window);
+            size_t nd = 0, n = 0;
+            check(fl_lookup_draft(history.data(), history.size(), &o, limit, draft, &nd), "fl_lookup_draft");
+            check(fl_forward_verify(shared.raw_model(), c, tok, draft, nd, rope, got, &n, nullptr), "Model forward pass failed");
+            n_forwards++;
+            shared.advance(own, n);
+            pos += n;
+            for (size_t i = 0; i < n; i++) {
+                if (eos && got[i] == *eos) return n_forwards;
+                if (!on_token(got[i])) return n_forwards;
+                history.push_back(got[i]);
+                if (++emitted == max_tokens) return n_forwards;
+            }
+            tok = got[n - 1];
+        }
+        return n_forwards;
     }
 
     // ModelWrapper::generate_stream + generate_tokens_inner (mod.rs:137-238, 268-340) on token ids: the model is CLONED (a

@@ -269,6 +269,65 @@ int fl_forward_sample_ex(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T
 int fl_decode_sample_ex(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
                         const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out);
 
+/* ---- speculative greedy decode: a multi-token verify step, cache rollback, prompt-lookup drafts ----------------------------------
+ * New capability (the reference decodes one token per forward, mod.rs:411-453).  A decode step is bound by the read of the weights;
+ * a forward over a few positions reads them once.  fl_forward_verify scores a drafted continuation in ONE forward and keeps the
+ * longest prefix the model itself would have produced, so the output is still the model's own greedy output.
+ *
+ * GUARANTEE: every token these calls emit is the ArgMax (ties -> LAST maximal index, as fl_forward_argmax) of this library's forward
+ * of the preceding tokens -- evaluated as a ROW OF A MULTI-ROW CALL (the prompt kernels), not as a one-row call (the decode kernels).
+ * In bf16 the two paths can separate on a near-tie of the two largest logits, as the batch paths already can; nothing else may
+ * separate them.  A model with FL_WEIGHTS_E4M3_ROW is accepted: its T > 1 rows run on the bf16 image of the same weights, as its
+ * prompts do (and its n_draft == 0 steps on the FP8 stream, as its decode steps do). */
+#define FL_VERIFY_MAX_DRAFT 15          /* T = n_draft + 1 <= 16: the last length before the short-prompt kernels' next tile step */
+
+/* The cache forgets everything from position `len` on; the next call appends at `len`.  len > fl_cache_len(c):
+ * FL_ERR_BAD_ARGUMENT.  A host-side length change (every call writes the device step state from it, and fl_batch_* reads it at the
+ * start of each call, so it also works on a batch member between calls); a captured decode graph stays valid, and the cache's layout
+ * choices, made from its capacity, do not change.  K/V rows beyond `len` stay in memory and are overwritten by the next append;
+ * nothing reads past the length. */
+int fl_cache_truncate(fl_cache *c, size_t len);
+
+/* One forward of the T = n_draft + 1 ids [token, draft[0..n_draft)] at RoPE offset pos, appended at fl_cache_len with the mask of a
+ * single fl_forward call of those ids.  a[t] = ArgMax of row t's logits; n_acc = the largest j <= n_draft with draft[i] == a[i] for
+ * all i < j; tokens_out[0..n_acc] = a[0..n_acc] (the accepted drafts, then the model's own next token); *n_out = n_acc + 1.
+ * Afterwards the cache length is L + n_acc + 1: `token` and the accepted drafts are cached, tokens_out[n_acc] is not -- it is the
+ * `token` of the next call at pos + *n_out, exactly as fl_decode_greedy hands its last token on.  n_draft == 0 is the T = 1 decode
+ * step (its mask, its kernels).  logits_out (host, or NULL) receives all T rows.  Never split into prefill chunks.
+ * FL_ERR_BAD_ARGUMENT (before the device is touched): n_draft > FL_VERIFY_MAX_DRAFT, null tokens_out / n_out, an id >= vocab_size.
+ * FL_ERR_UNSUPPORTED: tp_size > 1 (any mode); n_draft > the resolved sliding_window of a Mistral / Qwen2 model -- a decode step sees
+ * the whole cache (no mask at T = 1) while a T-row call hides new key j from query t when j + window < t, so the rows equal
+ * successive decode steps only while n_draft <= window.  Capacity and position overflow: as for a forward of T ids. */
+int fl_forward_verify(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos,
+                      uint32_t *tokens_out /* [n_draft + 1] */, size_t *n_out, float *logits_out /* [n_draft + 1][V] host, or NULL */);
+
+/* Prompt-lookup drafting: the continuation that followed the most recent earlier occurrence of the current n-gram. */
+typedef struct fl_lookup {
+    uint32_t struct_size;               /* sizeof(fl_lookup) */
+    int32_t  max_draft;                 /* 0 .. FL_VERIFY_MAX_DRAFT; 0 = plain greedy steps */
+    int32_t  ngram_max, ngram_min;      /* 1 <= ngram_min <= ngram_max <= 8 */
+    int32_t  _pad;
+    int64_t  _reserved[2];              /* 0 */
+} fl_lookup;
+typedef struct fl_spec_stats { uint64_t steps, drafted, accepted; } fl_spec_stats;
+
+/* Pure host function, no GPU (like fl_tp_slice).  For n = ngram_max down to ngram_min, with n < n_history: the pattern is the last n
+ * ids of history; s = the largest start with s + n < n_history and history[s .. s+n) == pattern (the most recent earlier occurrence
+ * that has at least one id after it); the draft is history[s+n ..], cut to min(max_draft, limit) ids and to the end of history.  The
+ * first n that matches wins.  No match, max_draft == 0 or limit == 0: *n_draft_out = 0.  A wrong struct_size, a range error in the
+ * options, or null pointers: FL_ERR_BAD_ARGUMENT. */
+int fl_lookup_draft(const uint32_t *history, size_t n_history, const fl_lookup *opts, size_t limit,
+                    uint32_t *draft_out /* [limit] */, size_t *n_draft_out);
+
+/* The loop of fl_decode_greedy (ArgMax only), built from verify steps: history = corpus ++ [first_token] ++ the tokens emitted so
+ * far (the corpus is only the search text: normally the prompt, but it need not be what the cache holds); each step drafts with
+ * limit = min(n_steps - emitted - 1, capacity left - 1, max_pos left - 1, sliding_window), verifies, and appends what the step
+ * returned.  EOS as in fl_decode_greedy: the loop stops at the first emitted token == eos, that token is not written, later tokens
+ * of the same step are dropped and the cache keeps the length fl_decode_greedy leaves.  Needs the room fl_decode_greedy needs and
+ * never more.  One host synchronisation per step.  stats (or NULL): verify steps, drafted ids, accepted ids. */
+int fl_decode_lookup(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos,
+                     size_t n_steps, int64_t eos, const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats /* or NULL */);
+
 /* Batched decode: B <= 64 caches of one model advanced together, one read of the weights per step for all
  * of them.  New capability: the reference runs concurrent streams as independent single-sequence loops
  * (mod.rs:137-238), each paying for the whole weight stream.  Every sequence keeps its own cache, RoPE
@@ -379,6 +438,12 @@ int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, in
 
 /* ... with an fl_sampler; kept_out (optional, [n_draws]): how many tokens each draw kept (V when no filter is on) */
 int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, int64_t n_draws, uint32_t *tokens_out, int64_t *kept_out);
+
+/* The selection kernel of fl_forward_verify alone, on host logits (unit tests): argmax_out[t] = ArgMax of row t (ties -> LAST maximal
+ * index), *n_accepted_out = the largest j <= T - 1 with draft[i] == argmax_out[i] for all i < j.  1 <= T <= FL_VERIFY_MAX_DRAFT + 1;
+ * draft may be NULL when T == 1. */
+int fl_op_verify_select(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *draft /* [T-1] */,
+                        uint32_t *argmax_out /* [T] */, int64_t *n_accepted_out);
 
 /* The bf16 MFMA attention kernels alone, for unit tests against an fp64 reference (they are otherwise only seen through
  * whole-model logits).  One sequence: q [T][H*d] (RoPE already applied), k / v [s_past + T][Hkv*d], all bf16 row-major; the

@@ -8,6 +8,8 @@ use std::os::raw::{c_char, c_int, c_void};
 pub const FL_ABI_VERSION: c_int = 2;
 pub const FL_UNIQUE_ID_BYTES: usize = 128;
 pub const FL_IPC_HANDLE_BYTES: usize = 64;
+/// Most drafted ids one `fl_forward_verify` call scores (T = n_draft + 1 <= 16).
+pub const FL_VERIFY_MAX_DRAFT: usize = 15;
 
 // fl_status
 pub const FL_OK: c_int = 0;
@@ -133,6 +135,27 @@ pub struct fl_sampler {
     pub _reserved: [i64; 2],
 }
 
+/// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fl_lookup {
+    pub struct_size: u32,
+    pub max_draft: i32,
+    pub ngram_max: i32,
+    pub ngram_min: i32,
+    pub _pad: i32,
+    pub _reserved: [i64; 2],
+}
+
+/// `fl_spec_stats`: verify steps, drafted ids and accepted ids of one fl_decode_lookup call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fl_spec_stats {
+    pub steps: u64,
+    pub drafted: u64,
+    pub accepted: u64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct fl_kernel_stat {
@@ -246,6 +269,41 @@ extern "C" {
         n_out: *mut usize,
     ) -> c_int;
 
+    pub fn fl_cache_truncate(c: *mut fl_cache, len: usize) -> c_int;
+    pub fn fl_forward_verify(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        token: u32,
+        draft: *const u32,
+        n_draft: usize,
+        pos: usize,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        logits_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_lookup_draft(
+        history: *const u32,
+        n_history: usize,
+        opts: *const fl_lookup,
+        limit: usize,
+        draft_out: *mut u32,
+        n_draft_out: *mut usize,
+    ) -> c_int;
+    pub fn fl_decode_lookup(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        corpus: *const u32,
+        n_corpus: usize,
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: i64,
+        opts: *const fl_lookup,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        stats: *mut fl_spec_stats,
+    ) -> c_int;
+
     pub fn fl_batch_create(m: *mut fl_model, caches: *const *mut fl_cache, n: usize, out: *mut *mut fl_batch) -> c_int;
     pub fn fl_batch_destroy(b: *mut fl_batch);
     pub fn fl_batch_replace(b: *mut fl_batch, slot: usize, cache: *mut fl_cache) -> c_int;
@@ -317,6 +375,7 @@ extern "C" {
     ) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
+    pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;
     pub fn fl_op_attention(
         q: *const c_void,
         k: *const c_void,

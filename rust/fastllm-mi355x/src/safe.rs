@@ -149,6 +149,55 @@ pub fn op_sample(logits: &[f32], s: Sampler, n_draws: usize) -> Result<(Vec<u32>
     Ok((toks, kept))
 }
 
+/// Prompt-lookup drafting (`fl_lookup`): the continuation that followed the most recent earlier occurrence of the current n-gram.
+/// `max_draft` 0 .. `ffi::FL_VERIFY_MAX_DRAFT` (0: plain greedy steps); 1 <= `ngram_min` <= `ngram_max` <= 8.
+#[derive(Clone, Copy, Debug)]
+pub struct Lookup {
+    pub max_draft: u32,
+    pub ngram_max: u32,
+    pub ngram_min: u32,
+}
+impl Default for Lookup {
+    fn default() -> Self {
+        Lookup { max_draft: 7, ngram_max: 3, ngram_min: 1 }
+    }
+}
+impl Lookup {
+    fn to_ffi(self) -> ffi::fl_lookup {
+        ffi::fl_lookup {
+            struct_size: std::mem::size_of::<ffi::fl_lookup>() as u32,
+            max_draft: self.max_draft.min(i32::MAX as u32) as i32,
+            ngram_max: self.ngram_max.min(i32::MAX as u32) as i32,
+            ngram_min: self.ngram_min.min(i32::MAX as u32) as i32,
+            _pad: 0,
+            _reserved: [0; 2],
+        }
+    }
+}
+
+/// `fl_lookup_draft` (pure host): the draft for `history`, at most `min(max_draft, limit)` ids.
+pub fn lookup_draft(history: &[u32], opts: Lookup, limit: usize) -> Result<Vec<u32>> {
+    let mut out = vec![0u32; limit.max(1)];
+    let mut n = 0usize;
+    let o = opts.to_ffi();
+    check(unsafe { ffi::fl_lookup_draft(history.as_ptr(), history.len(), &o, limit, out.as_mut_ptr(), &mut n) })?;
+    out.truncate(n);
+    Ok(out)
+}
+
+/// The verify step's selection kernel alone (`fl_op_verify_select`): `logits` is `[draft.len() + 1][v]`; returns the ArgMax of every
+/// row and how many drafted ids the rows confirm.
+pub fn op_verify_select(logits: &[f32], v: usize, draft: &[u32]) -> Result<(Vec<u32>, usize)> {
+    let t = draft.len() + 1;
+    if v == 0 || logits.len() != t * v {
+        return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("logits must hold {} rows of {} values", t, v) });
+    }
+    let mut am = vec![0u32; t];
+    let mut n = 0i64;
+    check(unsafe { ffi::fl_op_verify_select(logits.as_ptr(), t as i64, v as i64, draft.as_ptr(), am.as_mut_ptr(), &mut n) })?;
+    Ok((am, n as usize))
+}
+
 /// `fl_weight_format`: what the single-stream decode step reads its projection weights as.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 #[repr(i32)]
@@ -291,6 +340,52 @@ impl Model {
         Ok(toks)
     }
 
+    /// `fl_forward_verify`: one forward of `[token, draft..]`; returns the accepted drafts followed by the model's own next token
+    /// (which is not cached: it is the `token` of the next call at `pos + returned.len()`).
+    pub fn forward_verify(&self, cache: &mut Cache, token: u32, draft: &[u32], pos: usize) -> Result<Vec<u32>> {
+        let mut toks = vec![0u32; draft.len() + 1];
+        let mut n = 0usize;
+        check(unsafe { ffi::fl_forward_verify(self.raw, cache.raw, token, draft.as_ptr(), draft.len(), pos, toks.as_mut_ptr(), &mut n, ptr::null_mut()) })?;
+        toks.truncate(n);
+        Ok(toks)
+    }
+
+    /// `fl_decode_lookup`: the greedy loop of `decode` built from verify steps with prompt-lookup drafts out of
+    /// `corpus ++ [first_token] ++ output`; also returns the step / drafted / accepted counts.
+    pub fn decode_lookup(
+        &self,
+        cache: &mut Cache,
+        corpus: &[u32],
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: Option<u32>,
+        opts: Lookup,
+    ) -> Result<(Vec<u32>, ffi::fl_spec_stats)> {
+        let mut toks = vec![0u32; n_steps.max(1)];
+        let mut n = 0usize;
+        let mut stats = ffi::fl_spec_stats::default();
+        let o = opts.to_ffi();
+        check(unsafe {
+            ffi::fl_decode_lookup(
+                self.raw,
+                cache.raw,
+                corpus.as_ptr(),
+                corpus.len(),
+                first_token,
+                pos,
+                n_steps,
+                eos.map(|e| e as i64).unwrap_or(-1),
+                &o,
+                toks.as_mut_ptr(),
+                &mut n,
+                &mut stats,
+            )
+        })?;
+        toks.truncate(n);
+        Ok((toks, stats))
+    }
+
     pub fn synchronize(&self) -> Result<()> {
         check(unsafe { ffi::fl_synchronize(self.raw) })
     }
@@ -310,6 +405,10 @@ impl Cache {
     /// `clear_kv_cache` (mistral.rs:220, qwen.rs:148).
     pub fn reset(&mut self) {
         unsafe { ffi::fl_cache_reset(self.raw) };
+    }
+    /// `fl_cache_truncate`: forget everything from position `len` on (an error beyond the cached length).
+    pub fn truncate(&mut self, len: usize) -> Result<()> {
+        check(unsafe { ffi::fl_cache_truncate(self.raw, len) })
     }
     pub fn len(&self) -> usize {
         unsafe { ffi::fl_cache_len(self.raw) }
