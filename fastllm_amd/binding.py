@@ -159,6 +159,8 @@ def lib():
         L.fl_decode_lookup.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), vp, C.POINTER(sz),
                                        C.POINTER(FlSpecStats)]
         L.fl_op_verify_select.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
+        L.fl_cache_copy_prefix.argtypes = [vp, vp, sz]
+        L.fl_op_kv_copy.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
         _LIB = L
     return _LIB
 
@@ -514,6 +516,10 @@ class Cache:
         """fl_cache_truncate: forget everything from position n on."""
         _check(lib().fl_cache_truncate(self._h, int(n)))
 
+    def copy_prefix(self, src, n):
+        """fl_cache_copy_prefix: this cache forgets what it holds and takes the first n cached positions of `src` (same model)."""
+        _check(lib().fl_cache_copy_prefix(self._h, src._h if src is not None else None, int(n)))
+
     def __len__(self):
         return lib().fl_cache_len(self._h)
 
@@ -554,6 +560,19 @@ def op_attention(q, k, v, s_past, H, Hkv, d, window=-1, kernel=0, nsplit=0):
     out = np.empty((T, H * d), dtype=np.float32)
     _check(lib().fl_op_attention(q.ctypes.data, k.ctypes.data, v.ctypes.data, T, s_past, H, Hkv, d, window, kernel, nsplit, out.ctypes.data))
     return out
+
+
+def op_kv_copy(src, dst, width_bytes, iters=0):
+    """The K/V prefix copy kernel alone: the first width_bytes bytes of every row of src go to the same row of dst.  src, dst: 2-D
+    uint8 arrays with the same number of rows, C-contiguous (their row lengths are the two pitches).  Returns the new dst (and the ms
+    per launch when iters > 0); dst itself is not modified."""
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    out = np.array(dst, dtype=np.uint8, order="C", copy=True)
+    assert src.ndim == 2 and out.ndim == 2 and src.shape[0] == out.shape[0]
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_kv_copy(src.ctypes.data, out.ctypes.data, src.shape[0], int(width_bytes), src.shape[1], out.shape[1], iters,
+                               C.byref(ms)))
+    return (out, ms.value) if iters else out
 
 
 def op_linear(x, w, bias=None, epilogue=0, iters=0):

@@ -199,6 +199,12 @@ int fl_cache_truncate(fl_cache *c, size_t len) {
     });
 }
 
+int fl_cache_copy_prefix(fl_cache *dst, const fl_cache *src, size_t n) {
+    return guarded([&]() -> int {
+        return cache_copy_prefix(C(dst), C(src), n);
+    });
+}
+
 int fl_forward_verify(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
                       size_t *n_out, float *logits_out) {
     return guarded([&]() -> int {
@@ -720,6 +726,62 @@ int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *
         } else {
             FL_HIP(hipMemcpy(y, B.y, ybytes, hipMemcpyDeviceToHost));
         }
+        return FL_OK;
+    });
+}
+
+int fl_op_kv_copy(const void *src, void *dst, int64_t rows, int64_t width_bytes, int64_t src_pitch, int64_t dst_pitch, int32_t iters,
+                  double *ms_out) {
+    return guarded([&]() -> int {
+        if (!src || !dst) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (rows < 1 || width_bytes < 2 || rows > (int64_t)1 << 31) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (rows >= 1, width_bytes >= 2)");
+        KvCopyJob shape;                                     // width / pitch rules: the launch's own
+        shape.rows = rows; shape.width = width_bytes; shape.spitch = src_pitch; shape.dpitch = dst_pitch;
+        FL_TRY(kv_copy_check(shape));
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        struct Bufs { std::vector<void *> s, d; hipStream_t st = 0; hipEvent_t e0 = 0, e1 = 0;
+                      ~Bufs() { if (st) (void)hipStreamSynchronize(st);
+                                for (void *p : s) (void)hipFree(p);
+                                for (void *p : d) (void)hipFree(p);
+                                if (st) (void)hipStreamDestroy(st);
+                                if (e0) (void)hipEventDestroy(e0);
+                                if (e1) (void)hipEventDestroy(e1); } } B;
+        const size_t sbytes = (size_t)rows * (size_t)src_pitch, dbytes = (size_t)rows * (size_t)dst_pitch;
+        const bool timed = iters > 0 && ms_out;
+        // timed: the launches rotate over buffer pairs that together exceed the 256 MiB Infinity Cache (see fl_op_linear)
+        const int hot = tune(TK_OP_HOT);
+        const int ncopy = !timed ? 1 : hot > 0 ? hot : (int)std::min<size_t>(24, std::max<size_t>(1, (640u << 20) / (sbytes + dbytes) + 1));
+        FL_HIP(hipStreamCreate(&B.st));
+        for (int c = 0; c < ncopy; c++) {
+            void *p = nullptr;
+            FL_HIP(hipMalloc(&p, sbytes)); B.s.push_back(p);
+            FL_HIP(hipMemcpy(p, src, sbytes, hipMemcpyHostToDevice));
+            p = nullptr;
+            FL_HIP(hipMalloc(&p, dbytes)); B.d.push_back(p);
+            FL_HIP(hipMemcpy(p, dst, dbytes, hipMemcpyHostToDevice));
+        }
+        Launcher L; L.stream = B.st;
+        auto run = [&](int c) -> int {
+            KvCopyJob j = shape, none;
+            j.src = B.s[(size_t)c]; j.dst = B.d[(size_t)c];
+            return launch_kv_copy(L, j, none);
+        };
+        FL_TRY(run(0));
+        FL_HIP(hipStreamSynchronize(B.st));
+        if (timed) {
+            for (int c = 0; c < ncopy; c++) FL_TRY(run(c));   // warm
+            FL_HIP(hipStreamSynchronize(B.st));
+            FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+            FL_HIP(hipEventRecord(B.e0, B.st));
+            for (int i = 0; i < iters; i++) FL_TRY(run(i % ncopy));
+            FL_HIP(hipEventRecord(B.e1, B.st));
+            FL_HIP(hipEventSynchronize(B.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+            *ms_out = ms / iters;
+        }
+        FL_HIP(hipMemcpy(dst, B.d[0], dbytes, hipMemcpyDeviceToHost));
         return FL_OK;
     });
 }

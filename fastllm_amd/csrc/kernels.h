@@ -9,7 +9,7 @@ namespace fl {
 // Kernel classes for the measurement hooks (fl_profile_*): one class per kernel symbol family.
 enum KernelClass {
     KC_EMBED = 0, KC_RMSNORM, KC_GEMV, KC_GEMM_MFMA, KC_GEMM_GENERIC, KC_ROPE_KV, KC_ATTN_DECODE,
-    KC_ATTN_COMBINE, KC_ATTN_PREFILL, KC_ARGMAX, KC_REDUCE, KC_CONVERT, KC_ATTN_OPROJ, KC_COMM, KC_COUNT
+    KC_ATTN_COMBINE, KC_ATTN_PREFILL, KC_ARGMAX, KC_REDUCE, KC_CONVERT, KC_ATTN_OPROJ, KC_COMM, KC_KVCOPY, KC_COUNT
 };
 const char *kernel_class_name(int kc);
 
@@ -112,6 +112,13 @@ bool gemv_w8_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgM
 int launch_quantize_rows(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, float *s, void *img_bf16);
 // rows in HF order (gate [0, I) | up [I, 2 I)) -> the 16-interleaved decode layout (test hook)
 int launch_w8_gateup_layout(Launcher &L, const uint8_t *q, const float *s, int64_t I, int64_t K, uint8_t *qo, float *so);
+
+// k_kvcopy.hip: a 2-D byte copy on the device, `rows` rows of `width` bytes (a multiple of 2) with a source and a destination pitch
+// (multiples of 16, >= width; 16-byte aligned bases).  launch_kv_copy moves two such jobs -- the K and the V prefix of a cache -- in
+// ONE launch and writes exactly the bytes [0, width) of every destination row.  kv_copy_check (the shape alone, no pointers): FL_ERR_BAD_ARGUMENT for anything else.
+struct KvCopyJob { const void *src = nullptr; void *dst = nullptr; int64_t rows = 0, width = 0, spitch = 0, dpitch = 0; };
+int kv_copy_check(const KvCopyJob &j);
+int launch_kv_copy(Launcher &L, const KvCopyJob &a, const KvCopyJob &b);
 
 // ---- the persistent decode engine (k_engine.hip): a chain of projections in one launch ---------------------------
 constexpr int ENG_GATHER_WAVES = 4, ENG_STREAM_WAVES = 8, ENG_MAX_OPS = 4;

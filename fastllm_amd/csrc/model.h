@@ -243,6 +243,7 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
 
 // fl_cache_truncate / fl_forward_verify / fl_decode_lookup (speculative greedy decode)
 int cache_truncate(Cache *c, size_t len);
+int cache_copy_prefix(Cache *dst, const Cache *src, size_t n);      // fl_cache_copy_prefix (prefix reuse across caches)
 int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
                    size_t *n_out, float *logits_out);
 int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,

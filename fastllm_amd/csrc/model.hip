@@ -1634,6 +1634,47 @@ int cache_truncate(Cache *c, size_t len) {
     return FL_OK;
 }
 
+// ------------------------------------------------------------------------------- prefix reuse across caches
+// fl_cache_copy_prefix: dst takes the first n cached positions of src.  Two caches of one model differ only in seq_alloc, so per
+// shard the prefix of K (and of a row-major V) is L * Hkvs rows of n * d * es bytes at pitch seq_alloc * d * es, and the prefix of a
+// transposed V is L * Hkvs * d rows of n * es bytes at pitch seq_alloc * es: one launch of k_kvcopy.hip per shard, on the shard's
+// stream and under the model mutex, i.e. behind everything already submitted for either cache and before anything submitted later.
+// Not waited for: ~Cache synchronises every shard's stream under the same mutex before it frees, so src cannot go away under the copy.
+// The length is host state, as in cache_truncate; dst's graph, split counts and layout choices stay as its capacity made them.
+int cache_copy_prefix(Cache *dst, const Cache *src, size_t n) {
+    if (!dst || !src) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_copy_prefix: null cache");
+    if (dst->m != src->m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_copy_prefix: the caches belong to different models");
+    if (src == dst) return cache_truncate(dst, n);
+    if (n > src->len) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_copy_prefix: %zu is beyond the source's cached length %zu", n, src->len);
+    if (n > dst->max_seq) FL_FAIL(FL_ERR_SEQ_OVERFLOW, "fl_cache_copy_prefix: %zu positions exceed the destination's capacity %zu", n, dst->max_seq);
+    if (n == 0) { dst->len = 0; return FL_OK; }
+    if (dst->v_transposed != src->v_transposed)
+        FL_FAIL(FL_ERR_UNSUPPORTED, "fl_cache_copy_prefix: the caches keep V in different layouts (the attention switch changed between their creation)");
+    Model *m = dst->m;
+    debug_inject("cache_copy_prefix");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const int64_t es = (int64_t)m->esize(), d = m->D.d;
+    for (size_t i = 0; i < m->shards.size(); i++) {
+        Shard &sh = m->shards[i];
+        FL_HIP(hipSetDevice(sh.device));
+        const int64_t heads = m->D.L * sh.Hkvs;
+        KvCopyJob k, v;
+        k.src = src->shards[i].k; k.dst = dst->shards[i].k;
+        k.rows = heads; k.width = (int64_t)n * d * es;
+        k.spitch = (int64_t)src->seq_alloc * d * es; k.dpitch = (int64_t)dst->seq_alloc * d * es;
+        v = k;
+        v.src = src->shards[i].v; v.dst = dst->shards[i].v;
+        if (dst->v_transposed) {
+            v.rows = heads * d; v.width = (int64_t)n * es;
+            v.spitch = (int64_t)src->seq_alloc * es; v.dpitch = (int64_t)dst->seq_alloc * es;
+        }
+        Launcher L = make_launcher(m, sh);
+        FL_TRY(launch_kv_copy(L, k, v));
+    }
+    dst->len = n;
+    return FL_OK;
+}
+
 int check_lookup(const fl_lookup *o) {
     if (!o) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_lookup");
     if (o->struct_size != sizeof(fl_lookup)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_lookup.struct_size is %u, expected %zu", o->struct_size, sizeof(fl_lookup));

@@ -24,11 +24,13 @@
 // fastllm::Panic.  There is no CPU fallback: Device::Cpu is rejected by initialize_model.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <exception>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -763,6 +765,117 @@ struct Model {                                // mod.rs:342-361
     }
 };
 
+// ------------------------------------------------------------------------------------ K/V reuse across requests
+// The reference rebuilds the whole conversation into one prompt per request (api/chat.rs: messages -> format_messages -> generate,
+// which takes a fresh cache, mod.rs:370): turn n prefills turns 1 .. n-1 again, and requests that share a system prompt prefill it
+// once each.  fl_cache_copy_prefix carries cached positions from one fl_cache to another; the two classes below decide WHICH.
+//
+// PrefixIndex: pure host code, no GPU.  Up to `entries` id sequences in least-recently-used order (a hit, an insert and an insert
+// that found its ids already stored all count as a use).
+class PrefixIndex {
+  public:
+    static constexpr size_t npos = (size_t)-1;
+    explicit PrefixIndex(size_t entries) : seqs_(entries), used_(entries, 0) {
+        if (entries == 0) throw Error(FL_ERR_BAD_ARGUMENT, "PrefixIndex: at least one entry");
+    }
+    size_t entries() const { return seqs_.size(); }
+    const std::vector<uint32_t> &ids(size_t e) const { return seqs_.at(e); }
+    void clear(size_t e) { seqs_.at(e).clear(); used_.at(e) = 0; }
+
+    // (entry, n): n = the longest common prefix of `prompt` with any stored sequence, capped at prompt.size() - 1 (one token at least
+    // must be forwarded to obtain logits); ties go to the most recently used entry.  n < max(min_match, 1): a miss, (npos, 0).
+    std::pair<size_t, size_t> match(const std::vector<uint32_t> &prompt, size_t min_match) {
+        size_t best = npos, best_n = 0;
+        for (size_t e = 0; e < seqs_.size(); e++) {
+            const size_t n = std::min(common(prompt, seqs_[e]), prompt.empty() ? 0 : prompt.size() - 1);
+            if (n > best_n || (n == best_n && n > 0 && used_[e] > used_[best])) { best = e; best_n = n; }
+        }
+        if (best == npos || best_n < std::max<size_t>(min_match, 1)) return {npos, 0};
+        used_[best] = ++clock_;
+        return {best, best_n};
+    }
+    // the entry whose sequence `ids` replaces (its K/V is to be overwritten by the caller), or npos when nothing is stored:
+    //   ids is a prefix of a stored sequence (or equal to it): nothing is stored (that entry counts as used);
+    //   a stored sequence is a prefix of ids: the longest such entry is extended in place (ties: the most recently used);
+    //   otherwise the least recently used entry is taken (never-used entries first, the lowest index among them).
+    size_t insert(const std::vector<uint32_t> &ids) {
+        if (ids.empty()) return npos;
+        size_t covered = npos, ext = npos, lru = 0;
+        for (size_t e = 0; e < seqs_.size(); e++) {
+            const std::vector<uint32_t> &q = seqs_[e];
+            const size_t c = common(ids, q);
+            if (c == ids.size() && (covered == npos || used_[e] > used_[covered])) covered = e;
+            if (!q.empty() && c == q.size() &&
+                (ext == npos || q.size() > seqs_[ext].size() || (q.size() == seqs_[ext].size() && used_[e] > used_[ext]))) ext = e;
+            if (used_[e] < used_[lru]) lru = e;
+        }
+        if (covered != npos) { used_[covered] = ++clock_; return npos; }
+        const size_t e = ext != npos ? ext : lru;
+        seqs_[e] = ids;
+        used_[e] = ++clock_;
+        return e;
+    }
+
+  private:
+    static size_t common(const std::vector<uint32_t> &a, const std::vector<uint32_t> &b) {
+        const size_t m = std::min(a.size(), b.size());
+        size_t i = 0;
+        while (i < m && a[i] == b[i]) i++;
+        return i;
+    }
+    std::vector<std::vector<uint32_t>> seqs_;
+    std::vector<uint64_t> used_;                 // 0: never used
+    uint64_t clock_ = 0;
+};
+
+// PrefixStore: a PrefixIndex plus one fl_cache per entry, all created up front with one capacity -- nothing is allocated on the
+// serving path.  An entry's sequence is never longer than what its cache holds.
+class PrefixStore {
+  public:
+    PrefixStore(std::shared_ptr<detail::ModelHandle> model, size_t entries, size_t max_seq, size_t min_match)
+        : model_(std::move(model)), index_(entries), cap_(max_seq), min_match_(min_match) {
+        if (!model_ || !model_->m) throw Error(FL_ERR_BAD_ARGUMENT, "PrefixStore: no model");
+        if (cap_ == 0) throw Error(FL_ERR_BAD_ARGUMENT, "PrefixStore: max_seq must be > 0");
+        caches_.resize(entries);
+        for (auto &c : caches_) check(fl_cache_create(model_->m, cap_, &c.c), "fl_cache_create");
+    }
+    size_t capacity() const { return cap_; }
+    const PrefixIndex &index() const { return index_; }
+
+    // dst takes the longest stored prefix of `prompt` (fl_cache_copy_prefix); returns its length n -- the caller forwards prompt[n:]
+    // at position n -- or 0 on a miss (dst is untouched then)
+    size_t lookup_into(fl_cache *dst, const std::vector<uint32_t> &prompt) {
+        auto [e, n] = index_.match(prompt, min_match_);
+        if (e == PrefixIndex::npos) return 0;
+        n = std::min(n, fl_cache_capacity(dst));
+        if (n < std::max<size_t>(min_match_, 1)) return 0;
+        check(fl_cache_copy_prefix(dst, caches_[e].c, n), "fl_cache_copy_prefix");
+        return n;
+    }
+    // `src` holds the K/V of `ids` (its first ids.size() positions): keep min(ids.size(), fl_cache_len(src), capacity) of them
+    void remember(fl_cache *src, const std::vector<uint32_t> &ids) {
+        const size_t n = std::min(std::min(ids.size(), fl_cache_len(src)), cap_);
+        if (n == 0) return;
+        const size_t e = index_.insert(std::vector<uint32_t>(ids.begin(), ids.begin() + (ptrdiff_t)n));
+        if (e == PrefixIndex::npos) return;
+        try { check(fl_cache_copy_prefix(caches_[e].c, src, n), "fl_cache_copy_prefix"); }
+        catch (...) { index_.clear(e); throw; }           // the entry's cache no longer matches any sequence
+    }
+
+  private:
+    std::shared_ptr<detail::ModelHandle> model_;
+    PrefixIndex index_;
+    std::vector<detail::CacheHandle> caches_;
+    size_t cap_, min_match_;
+};
+
+// StreamBatcher option: entries == 0 (default) is the batcher without a store.  min_match: up to 16 tokens a prefill costs one
+// short-prompt tile whatever its length (T <= 16 flat), so a shorter match saves nothing.  max_seq: capacity of the
+// store's caches, 0 = the slots' capacity.
+struct PrefixOptions {
+    size_t entries = 0, min_match = 16, max_seq = 0;
+};
+
 // ------------------------------------------------------------------------------------ concurrent streams, one batched loop
 // The reference serves concurrent requests as independent tasks (ModelWrapper::generate_stream spawns one loop per stream,
 // mod.rs:137-238), each paying for the whole weight read per token.  StreamBatcher gives the same streams ONE decode loop
@@ -773,6 +886,13 @@ struct Model {                                // mod.rs:342-361
 // sampled, EOS checked before the token is emitted (mod.rs:312-316), the callback's `false` is the dropped receiver (mod.rs:323-325).
 // Steps a stream runs past its own end inside a chunk are computed and discarded (its slot's cache is reset on the next admission).
 // Not thread-safe: one thread drives submit() / step() (a server would feed it from a channel).
+//
+// With PrefixOptions.entries > 0 the batcher keeps a PrefixStore: a finished stream leaves the K/V of its prompt and of its reply
+// there, and an admitted request whose prompt starts with a stored sequence (turn n of a chat, a shared system prompt) copies that
+// prefix into its slot and prefills only the rest, at its token position.  The tokens are those of the batcher without a store.
+// Reuse is skipped for a Mistral / Qwen2 prompt longer than the sliding window: within one call the new tokens are masked among
+// themselves but a cached prefix is not (fl_forward_verify's note), so prefix + suffix would no longer equal the single call.
+// Refused together with counter_positions: with call-counter RoPE offsets a result depends on how many calls produced the cache.
 class StreamBatcher {
   public:
     using OnToken = std::function<bool(uint32_t)>;
@@ -781,10 +901,14 @@ class StreamBatcher {
     // counter_positions: the RoPE offset of a stream's k-th forward is k, not its token position -- what Mistral / Qwen streams
     // see in the reference (quirk C.1: mistral.rs:226,234, qwen.rs:142-143; PosMode::Reference); Llama streams and
     // FASTLLM_POS_MODE=tokens pass token positions
-    StreamBatcher(std::shared_ptr<detail::ModelHandle> model, size_t slots, size_t max_seq = 0, size_t chunk = 8, bool counter_positions = false)
+    StreamBatcher(std::shared_ptr<detail::ModelHandle> model, size_t slots, size_t max_seq = 0, size_t chunk = 8, bool counter_positions = false,
+                  PrefixOptions prefix = {})
         : model_(std::move(model)), chunk_(std::max<size_t>(1, chunk)), counter_(counter_positions) {
         if (!model_ || !model_->m) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: no model");
         if (slots < 1 || slots > 64) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: 1 ... 64 slots");
+        if (prefix.entries > 0 && counter_)
+            throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: a prefix store needs token positions (with call-counter RoPE offsets a result depends on how "
+                                             "many calls produced the cache)");
         cap_ = max_seq ? max_seq : detail::default_max_seq(model_->m);
         if (cap_ < chunk_ + 1) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: the caches are shorter than one chunk");
         slots_.resize(slots);
@@ -792,6 +916,12 @@ class StreamBatcher {
         try {
             for (auto &sl : slots_) { check(fl_cache_create(model_->m, cap_, &sl.cache), "fl_cache_create"); cs.push_back(sl.cache); }
             check(fl_batch_create(model_->m, cs.data(), cs.size(), &batch_), "fl_batch_create");
+            if (prefix.entries > 0) {
+                fl_model_info info; check(fl_model_get_info(model_->m, &info), "fl_model_get_info");
+                // the longest prompt a cached prefix may serve: any for Llama, the resolved sliding window for Mistral / Qwen2
+                reuse_limit_ = info.cfg.family == FL_FAMILY_LLAMA ? (size_t)-1 : (size_t)std::max<int64_t>(0, info.cfg.sliding_window);
+                store_ = std::make_unique<PrefixStore>(model_, prefix.entries, prefix.max_seq ? prefix.max_seq : cap_, prefix.min_match);
+            }
         } catch (...) { release(); throw; }
     }
     ~StreamBatcher() { release(); }
@@ -820,11 +950,17 @@ class StreamBatcher {
     size_t waiting() const { return queue_.size(); }
     size_t batch_steps = 0;                                        // decode steps the batch has run (all slots advance together)
     size_t prefills = 0;
+    size_t prefill_tokens = 0;                                     // prompt tokens the admissions forwarded (with a store: the suffixes only)
+    size_t prefix_hits = 0, prefix_tokens_reused = 0;              // admissions that copied a stored prefix, and the positions they copied
 
     // admit waiting requests into free slots, then one chunk for everybody; false: nothing active and nothing waiting
     bool step() {
         for (auto &sl : slots_) {
-            while (!sl.active && !queue_.empty()) { admit(sl, std::move(queue_.front())); queue_.pop_front(); }
+            while (!sl.active && !queue_.empty()) {
+                Request r = std::move(queue_.front());             // out of the queue first: a prefill that throws takes its request with it
+                queue_.pop_front();
+                admit(sl, std::move(r));
+            }
         }
         if (active() == 0) return !queue_.empty();
         const size_t B = slots_.size();
@@ -852,6 +988,7 @@ class StreamBatcher {
             for (size_t k = 0; k < n_out[i]; k++) {
                 if (sl.emitted >= sl.req.max_tokens) { done = true; break; }
                 sl.emitted++;                                      // (tokens handed to the callback, the refused one included)
+                if (store_) sl.held.push_back(out[i * n + k]);
                 if (!sl.req.on_token(out[i * n + k])) { done = true; break; }
             }
             if (!done && sl.emitted >= sl.req.max_tokens) done = true;
@@ -869,29 +1006,51 @@ class StreamBatcher {
         SamplingOptions opt;
         OnToken on_token; OnDone on_done;
     };
-    struct Slot { fl_cache *cache = nullptr; bool active = false; Request req; size_t pos = 0, calls = 0, emitted = 0; uint32_t tok = 0; uint64_t draws = 0; };
+    struct Slot {
+        fl_cache *cache = nullptr; bool active = false; Request req; size_t pos = 0, calls = 0, emitted = 0; uint32_t tok = 0; uint64_t draws = 0;
+        std::vector<uint32_t> held;          // with a store: the prompt and every token handed to the callback
+    };
 
+    // the slot becomes active only after its prefill succeeded: an exception leaves it free (and the request gone, see step())
     void admit(Slot &sl, Request r) {
-        sl.req = std::move(r); sl.emitted = 0; sl.active = true;
+        sl.emitted = 0;
+        sl.held.clear();
         fl_cache_reset(sl.cache);
-        const fl_sampler sp = sl.req.opt.to_ffi((double)sl.req.temperature, 0);
+        size_t n = 0;
+        if (store_ && r.prompt.size() <= reuse_limit_) n = store_->lookup_into(sl.cache, r.prompt);
+        const fl_sampler sp = r.opt.to_ffi((double)r.temperature, 0);
         uint32_t tok = 0;
-        check(fl_forward_sample_ex(model_->m, sl.cache, sl.req.prompt.data(), sl.req.prompt.size(), 0, &sp, &tok), "Model forward pass failed");
+        check(fl_forward_sample_ex(model_->m, sl.cache, r.prompt.data() + n, r.prompt.size() - n, n, &sp, &tok), "Model forward pass failed");
         prefills++;
+        prefill_tokens += r.prompt.size() - n;
+        if (n) { prefix_hits++; prefix_tokens_reused += n; }
+        sl.req = std::move(r); sl.active = true;
+        if (store_) sl.held = sl.req.prompt;
         sl.pos = sl.req.prompt.size(); sl.calls = 1; sl.tok = tok; sl.draws = 1;
         if (sl.req.max_tokens == 0 || (sl.req.eos && tok == *sl.req.eos)) { finish(sl); return; }
         sl.emitted = 1;
+        if (store_) sl.held.push_back(tok);
         if (!sl.req.on_token(tok)) { finish(sl); return; }
         if (sl.emitted >= sl.req.max_tokens || sl.pos >= cap_) finish(sl);
     }
+    // With a store the slot's K/V is remembered under the ids it is KNOWN to hold: the prompt and every emitted token except the
+    // last (a token's K/V is written by the step that takes it as input), never more than fl_cache_len.
     void finish(Slot &sl) {
         sl.active = false;
         OnDone cb = std::move(sl.req.on_done);
         const size_t n = sl.emitted;
         sl.req = Request{};
+        std::exception_ptr failed;
+        if (store_ && !sl.held.empty()) {
+            if (n > 0) sl.held.pop_back();
+            try { store_->remember(sl.cache, sl.held); } catch (...) { failed = std::current_exception(); }
+            sl.held.clear();
+        }
         if (cb) cb(n);
+        if (failed) std::rethrow_exception(failed);
     }
     void release() {
+        store_.reset();
         if (batch_) { fl_batch_destroy(batch_); batch_ = nullptr; }
         for (auto &sl : slots_) if (sl.cache) { fl_cache_destroy(sl.cache); sl.cache = nullptr; }
     }
@@ -899,6 +1058,8 @@ class StreamBatcher {
     std::shared_ptr<detail::ModelHandle> model_;
     size_t chunk_, cap_ = 0;
     bool counter_ = false;
+    std::unique_ptr<PrefixStore> store_;                           // null: no prefix reuse
+    size_t reuse_limit_ = 0;
     std::vector<Slot> slots_;
     std::deque<Request> queue_;
     fl_batch *batch_ = nullptr;

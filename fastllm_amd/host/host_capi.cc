@@ -302,4 +302,55 @@ int flh_batcher_run(void *bv, size_t *batch_steps, size_t *prefills) {
 }
 void flh_batcher_destroy(void *bv) { delete static_cast<BatcherHandle *>(bv); }
 
+// ... with a PrefixStore of `entries` caches (PrefixOptions; entries == 0: flh_batcher_create).  The position mode is flh_batcher_create's:
+// a Mistral / Qwen2 model under FASTLLM_POS_MODE=reference asks for call-counter positions, which a store refuses (FL_ERR_BAD_ARGUMENT).
+int flh_batcher_create_prefix(void *hv, size_t slots, size_t max_seq, size_t chunk, size_t entries, size_t min_match, void **out) {
+    return guard([&] {
+        if (!hv || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto bh = std::make_unique<BatcherHandle>();
+        Handle *h = static_cast<Handle *>(hv);
+        PrefixOptions po; po.entries = entries; po.min_match = min_match;
+        bh->b = std::make_unique<StreamBatcher>(model_of(h), slots, max_seq, chunk, !h->llama && pos_mode() == PosMode::Reference, po);
+        *out = bh.release();
+        return 0;
+    });
+}
+int flh_batcher_prefix_stats(void *bv, size_t *prefix_hits, size_t *prefix_tokens_reused, size_t *prefill_tokens) {
+    return guard([&] {
+        if (!bv) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto *bh = static_cast<BatcherHandle *>(bv);
+        if (prefix_hits) *prefix_hits = bh->b->prefix_hits;
+        if (prefix_tokens_reused) *prefix_tokens_reused = bh->b->prefix_tokens_reused;
+        if (prefill_tokens) *prefill_tokens = bh->b->prefill_tokens;
+        return 0;
+    });
+}
+
+// PrefixIndex alone (pure host, no GPU).  entry_out: the entry, or -1 (match: a miss; insert: nothing stored)
+int flh_prefix_index_create(size_t entries, void **out) {
+    return guard([&] {
+        if (!out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        *out = new PrefixIndex(entries);
+        return 0;
+    });
+}
+int flh_prefix_index_match(void *pv, const uint32_t *prompt, size_t n_prompt, size_t min_match, int64_t *entry_out, size_t *n_out) {
+    return guard([&] {
+        if (!pv || !entry_out || !n_out || (!prompt && n_prompt)) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto r = static_cast<PrefixIndex *>(pv)->match(std::vector<uint32_t>(prompt, prompt + n_prompt), min_match);
+        *entry_out = r.first == PrefixIndex::npos ? -1 : (int64_t)r.first;
+        *n_out = r.second;
+        return 0;
+    });
+}
+int flh_prefix_index_insert(void *pv, const uint32_t *ids, size_t n_ids, int64_t *entry_out) {
+    return guard([&] {
+        if (!pv || !entry_out || (!ids && n_ids)) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        const size_t e = static_cast<PrefixIndex *>(pv)->insert(std::vector<uint32_t>(ids, ids + n_ids));
+        *entry_out = e == PrefixIndex::npos ? -1 : (int64_t)e;
+        return 0;
+    });
+}
+void flh_prefix_index_destroy(void *pv) { delete static_cast<PrefixIndex *>(pv); }
+
 }  // extern "C"

@@ -288,6 +288,24 @@ int fl_decode_sample_ex(fl_model *m, fl_cache *c, uint32_t first_token, size_t p
  * nothing reads past the length. */
 int fl_cache_truncate(fl_cache *c, size_t len);
 
+/* ---- K/V reuse across caches ----------------------------------------------------------------------------------------------------
+ * New capability (the reference takes a fresh cache per request, mod.rs:370, and prefills the whole conversation again on every turn).
+ * dst forgets what it holds and takes the first n cached positions of src (every layer, kv head and local shard); afterwards
+ * fl_cache_len(dst) == n and the next call appends at n, exactly as if dst had computed those positions itself.  src is unchanged.
+ * GUARANTEE: after fl_cache_copy_prefix(dst, src, n) any call on dst gives what the same call gives on src truncated to n -- bit for
+ * bit when the two capacities are equal; when they differ the decode attention splits the keys differently (fl_cache_create picks the
+ * split count from the capacity), and the results agree as those kernel variants agree among themselves.
+ * The length is a host-side change, as in fl_cache_truncate: dst's captured decode graph stays valid, its layout choices (made from
+ * its capacity) do not change, and it works on a batch member between two fl_batch_* calls.  The copy is ONE kernel launch per local
+ * shard (k_kvcopy.hip), enqueued under the model's lock on the shard's stream: behind everything already submitted for either cache,
+ * ahead of everything submitted later; the call does not wait for it (fl_cache_destroy of src does).  Any tp_mode: the copy is local to
+ * each shard, and every rank of an FL_TP_MULTI_PROCESS group makes the same call.
+ *   n == 0: fl_cache_reset(dst).  src == dst: fl_cache_truncate(dst, n).
+ *   FL_ERR_BAD_ARGUMENT: a null cache, caches of different models, n > fl_cache_len(src).  FL_ERR_SEQ_OVERFLOW: n > fl_cache_capacity(dst).
+ *   FL_ERR_UNSUPPORTED: the caches keep V in different layouts (FL_ATTN_MFMA changed between the two fl_cache_create calls).
+ * All of these are decided before the device is touched. */
+int fl_cache_copy_prefix(fl_cache *dst, const fl_cache *src, size_t n);
+
 /* One forward of the T = n_draft + 1 ids [token, draft[0..n_draft)] at RoPE offset pos, appended at fl_cache_len with the mask of a
  * single fl_forward call of those ids.  a[t] = ArgMax of row t's logits; n_acc = the largest j <= n_draft with draft[i] == a[i] for
  * all i < j; tokens_out[0..n_acc] = a[0..n_acc] (the accepted drafts, then the model's own next token); *n_out = n_acc + 1.
@@ -444,6 +462,14 @@ int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, i
  * draft may be NULL when T == 1. */
 int fl_op_verify_select(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *draft /* [T-1] */,
                         uint32_t *argmax_out /* [T] */, int64_t *n_accepted_out);
+
+/* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
+ * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read
+ * back, so the bytes the kernel must not touch -- everything outside [0, width_bytes) of a row -- can be checked.  rows >= 1;
+ * width_bytes >= 2 and a multiple of 2; both pitches multiples of 16 and at least width_bytes; anything else FL_ERR_BAD_ARGUMENT
+ * (before the device is touched).  iters > 0 with ms_out != NULL times `iters` launches over rotating buffer pairs, as fl_op_linear. */
+int fl_op_kv_copy(const void *src, void *dst, int64_t rows, int64_t width_bytes, int64_t src_pitch, int64_t dst_pitch,
+                  int32_t iters, double *ms_out);
 
 /* The bf16 MFMA attention kernels alone, for unit tests against an fp64 reference (they are otherwise only seen through
  * whole-model logits).  One sequence: q [T][H*d] (RoPE already applied), k / v [s_past + T][Hkv*d], all bf16 row-major; the

@@ -270,6 +270,7 @@ extern "C" {
     ) -> c_int;
 
     pub fn fl_cache_truncate(c: *mut fl_cache, len: usize) -> c_int;
+    pub fn fl_cache_copy_prefix(dst: *mut fl_cache, src: *const fl_cache, n: usize) -> c_int;
     pub fn fl_forward_verify(
         m: *mut fl_model,
         c: *mut fl_cache,
@@ -376,6 +377,16 @@ extern "C" {
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;
+    pub fn fl_op_kv_copy(
+        src: *const c_void,
+        dst: *mut c_void,
+        rows: i64,
+        width_bytes: i64,
+        src_pitch: i64,
+        dst_pitch: i64,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
     pub fn fl_op_attention(
         q: *const c_void,
         k: *const c_void,

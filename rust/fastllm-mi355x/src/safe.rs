@@ -410,6 +410,13 @@ impl Cache {
     pub fn truncate(&mut self, len: usize) -> Result<()> {
         check(unsafe { ffi::fl_cache_truncate(self.raw, len) })
     }
+    /// `fl_cache_copy_prefix`: this cache forgets what it holds and takes the first `n` cached positions of `src` (a cache of the
+    /// same model; `src` is unchanged).  Afterwards `len() == n` and the next call appends at `n`, as if this cache had computed
+    /// those positions itself.  Errors: `n` beyond `src.len()` or caches of two models (`FL_ERR_BAD_ARGUMENT`), `n` beyond
+    /// `capacity()` (`FL_ERR_SEQ_OVERFLOW`).
+    pub fn copy_prefix_from(&mut self, src: &Cache, n: usize) -> Result<()> {
+        check(unsafe { ffi::fl_cache_copy_prefix(self.raw, src.raw as *const ffi::fl_cache, n) })
+    }
     pub fn len(&self) -> usize {
         unsafe { ffi::fl_cache_len(self.raw) }
     }
