@@ -85,6 +85,33 @@ def make_lookup(max_draft=7, ngram_max=3, ngram_min=1):
     return FlLookup(C.sizeof(FlLookup), int(max_draft), int(ngram_max), int(ngram_min))
 
 
+class FlEncoderConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("activation", C.c_int32), ("add_token_type0", C.c_int32), ("_pad", C.c_int32),
+                ("hidden_size", C.c_int64), ("intermediate_size", C.c_int64), ("num_hidden_layers", C.c_int64),
+                ("num_attention_heads", C.c_int64), ("max_position_embeddings", C.c_int64), ("vocab_size", C.c_int64),
+                ("max_batch_tokens", C.c_int64), ("layer_norm_eps", C.c_double), ("_reserved", C.c_int64 * 2)]
+
+
+ACTIVATION = {"gelu_tanh": 0, "gelu": 0, "gelu_erf": 1}
+
+
+def make_encoder_config(cfg, activation="gelu_tanh", add_token_type0=False, max_batch_tokens=0):
+    """fl_encoder_config from a BERT config dict (the fields of the reference's BertConfig + vocab_size)."""
+    c = FlEncoderConfig()
+    c.struct_size = C.sizeof(FlEncoderConfig)
+    c.activation = activation if isinstance(activation, int) else ACTIVATION[activation]
+    c.add_token_type0 = int(bool(add_token_type0))
+    c.hidden_size = cfg["hidden_size"]
+    c.intermediate_size = cfg["intermediate_size"]
+    c.num_hidden_layers = cfg["num_hidden_layers"]
+    c.num_attention_heads = cfg["num_attention_heads"]
+    c.max_position_embeddings = cfg["max_position_embeddings"]
+    c.vocab_size = cfg["vocab_size"]
+    c.max_batch_tokens = int(max_batch_tokens)
+    c.layer_norm_eps = cfg["layer_norm_eps"]
+    return c
+
+
 class FlKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_double),
                 ("flops", C.c_double)]
@@ -161,6 +188,12 @@ def lib():
         L.fl_op_verify_select.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
         L.fl_cache_copy_prefix.argtypes = [vp, vp, sz]
         L.fl_op_kv_copy.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
+        L.fl_encoder_create.argtypes = [C.POINTER(FlEncoderConfig), C.POINTER(FlTensor), sz, C.c_int32, C.c_int32, C.POINTER(vp)]
+        L.fl_encoder_release.argtypes = [vp]
+        L.fl_encoder_release.restype = None
+        L.fl_encoder_hidden.argtypes = [vp, vp, sz, vp]
+        L.fl_encoder_embed.argtypes = [vp, vp, vp, sz, vp]
+        L.fl_op_encoder_attention.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.c_int64, C.c_int32, vp]
         _LIB = L
     return _LIB
 
@@ -255,6 +288,83 @@ def _np_dtype_code(a):
     if a.dtype == np.float16:
         return F16
     raise TypeError("unsupported array dtype %s" % a.dtype)
+
+
+def _tensor_array(tensors):
+    """dict name -> numpy array | (device_ptr, dtype_code, shape, device_ordinal)  ->  (FlTensor array, objects to keep alive)"""
+    arr = (FlTensor * len(tensors))()
+    keep = []
+    for i, (name, a) in enumerate(tensors.items()):
+        arr[i].name = name.encode()
+        if isinstance(a, tuple):
+            ptr, code, shape, dev = a
+            arr[i].dtype, arr[i].ndim, arr[i].data, arr[i].device = code, len(shape), ptr, dev
+            for j, s in enumerate(shape):
+                arr[i].shape[j] = s
+        else:
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            arr[i].dtype, arr[i].ndim, arr[i].data, arr[i].device = _np_dtype_code(a), a.ndim, a.ctypes.data, -1
+            for j, s in enumerate(a.shape):
+                arr[i].shape[j] = s
+    return arr, keep
+
+
+class Encoder:
+    """fl_encoder handle: the BERT / MiniLM encoder forward (embeddings).  cfg: dict with hidden_size, intermediate_size,
+    num_hidden_layers, num_attention_heads, max_position_embeddings, vocab_size, layer_norm_eps; tensors as for Model (HF names
+    without the "bert." prefix)."""
+
+    def __init__(self, cfg, tensors, dtype="bf16", activation="gelu_tanh", add_token_type0=False, max_batch_tokens=0, device=0):
+        self.cfg = dict(cfg)
+        self.h = cfg["hidden_size"]
+        arr, keep = _tensor_array(tensors)
+        c = make_encoder_config(cfg, activation, add_token_type0, max_batch_tokens)
+        h = C.c_void_p()
+        _check(lib().fl_encoder_create(C.byref(c), arr, len(tensors), BF16 if dtype == "bf16" else F32, device, C.byref(h)))
+        del keep
+        self._h = h
+
+    def hidden(self, ids):
+        """fl_encoder_hidden: last hidden states [T, h] float32 of one sequence."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = np.empty((ids.size, self.h), dtype=np.float32)
+        _check(lib().fl_encoder_hidden(self._h, ids.ctypes.data, ids.size, out.ctypes.data))
+        return out
+
+    def embed(self, seqs):
+        """fl_encoder_embed: seqs is a list of id lists; returns [len(seqs), h] float32 (mean-pooled, L2-normalised)."""
+        seqs = [np.asarray(s, dtype=np.uint32).reshape(-1) for s in seqs]
+        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([s.size for s in seqs])
+        ids = np.concatenate(seqs) if seqs else np.zeros(0, np.uint32)
+        out = np.empty((len(seqs), self.h), dtype=np.float32)
+        _check(lib().fl_encoder_embed(self._h, ids.ctypes.data if ids.size else None, offs.ctypes.data, len(seqs), out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fl_encoder_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def op_encoder_attention(q, k, v, lengths, H, d):
+    """The encoder's unmasked ragged attention kernel alone.  q / k / v [sum(lengths), H*d], all uint16 (bf16 bits: the MFMA kernel)
+    or all float32 (the VALU kernel); returns [sum(lengths), H*d] float32."""
+    q, k, v = (np.ascontiguousarray(a) for a in (q, k, v))
+    assert q.dtype == k.dtype == v.dtype and q.shape == k.shape == v.shape == (int(sum(lengths)), H * d)
+    offs = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lengths)
+    out = np.empty(q.shape, dtype=np.float32)
+    _check(lib().fl_op_encoder_attention(q.ctypes.data, k.ctypes.data, v.ctypes.data, offs.ctypes.data, len(lengths), H, d,
+                                         _np_dtype_code(q), out.ctypes.data))
+    return out
 
 
 class Model:

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "model.h"
+#include "encoder.h"
 #include "lookup.h"
 
 using namespace fl;
@@ -369,6 +370,74 @@ int fl_synchronize(fl_model *m) {
     return guarded([&]() -> int {
         if (!m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null model");
         for (auto &sh : M(m)->shards) { FL_HIP(hipSetDevice(sh.device)); FL_HIP(hipStreamSynchronize(sh.stream)); }
+        return FL_OK;
+    });
+}
+
+// ---- embeddings: the BERT / MiniLM encoder (encoder.hip) --------------------------------------------------------------------------
+int fl_encoder_create(const fl_encoder_config *cfg, const fl_tensor *tensors, size_t n_tensors, int32_t compute_dtype, int32_t device,
+                      fl_encoder **out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_encoder_create: null out");
+        *out = nullptr;
+        Encoder *e = nullptr;
+        const int rc = encoder_create(cfg, tensors, n_tensors, compute_dtype, device, &e);
+        if (rc == FL_OK) *out = reinterpret_cast<fl_encoder *>(e);
+        return rc;
+    });
+}
+void fl_encoder_release(fl_encoder *e) {
+    guarded_void([&]() { delete reinterpret_cast<Encoder *>(e); });
+}
+int fl_encoder_hidden(fl_encoder *e, const uint32_t *ids, size_t T, float *out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_encoder_hidden: null out");
+        const size_t offsets[2] = {0, T};
+        return encoder_run(reinterpret_cast<Encoder *>(e), ids, offsets, 1, out, nullptr);
+    });
+}
+int fl_encoder_embed(fl_encoder *e, const uint32_t *ids, const size_t *offsets, size_t n_seq, float *out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_encoder_embed: null out");
+        return encoder_run(reinterpret_cast<Encoder *>(e), ids, offsets, n_seq, nullptr, out);
+    });
+}
+
+int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
+                            int32_t dtype, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype must be bf16 or f32");
+        if (H < 1 || H > 65535) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head count");
+        if (!encoder_attention_supported(d)) FL_FAIL(FL_ERR_UNSUPPORTED, "encoder attention: head_dim 32 or 64");
+        int64_t T = 0, longest = 0;
+        FL_TRY(encoder_check_offsets(offsets, n_seq, 1 << 18, 1 << 20, &T, &longest));
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, n = (size_t)T * H * d;
+        struct Bufs { void *q = 0, *k = 0, *v = 0, *o = 0; int32_t *off = 0; hipStream_t s = 0;
+                      ~Bufs() { (void)hipFree(q); (void)hipFree(k); (void)hipFree(v); (void)hipFree(o); (void)hipFree(off); if (s) (void)hipStreamDestroy(s); } } B;
+        std::vector<int32_t> off(n_seq + 1);
+        for (size_t s = 0; s <= n_seq; s++) off[s] = (int32_t)offsets[s];
+        FL_HIP(hipStreamCreate(&B.s));
+        FL_HIP(hipMalloc(&B.q, n * es)); FL_HIP(hipMalloc(&B.k, n * es)); FL_HIP(hipMalloc(&B.v, n * es)); FL_HIP(hipMalloc(&B.o, n * es));
+        FL_HIP(hipMalloc((void **)&B.off, (n_seq + 1) * 4));
+        FL_HIP(hipMemcpy(B.q, q, n * es, hipMemcpyHostToDevice));
+        FL_HIP(hipMemcpy(B.k, k, n * es, hipMemcpyHostToDevice));
+        FL_HIP(hipMemcpy(B.v, v, n * es, hipMemcpyHostToDevice));
+        FL_HIP(hipMemcpy(B.off, off.data(), (n_seq + 1) * 4, hipMemcpyHostToDevice));
+        FL_HIP(hipMemset(B.o, 0xff, n * es));                      // NaN pattern: an element the kernel does not write shows up
+        Launcher L; L.stream = B.s;
+        FL_TRY(launch_encoder_attention(L, dtype, B.q, B.k, B.v, H * d, B.off, (int64_t)n_seq, longest, T, H, d, 1.0f / sqrtf((float)d), B.o));
+        FL_HIP(hipStreamSynchronize(B.s));
+        if (dtype == FL_DTYPE_F32) {
+            FL_HIP(hipMemcpy(out, B.o, n * 4, hipMemcpyDeviceToHost));
+        } else {
+            std::vector<bf16_t> oh(n);
+            FL_HIP(hipMemcpy(oh.data(), B.o, n * 2, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; i++) out[i] = bf16_bits_to_float(oh[i]);
+        }
         return FL_OK;
     });
 }

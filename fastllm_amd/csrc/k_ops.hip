@@ -9,7 +9,8 @@ namespace fl {
 
 static const char *kNames[KC_COUNT] = {
     "embed", "rmsnorm_add", "gemv", "gemm_mfma", "gemm_generic", "rope_kv_append", "attn_decode",
-    "attn_combine", "attn_prefill", "select_advance", "reduce_shards", "convert", "attn_oproj", "comm_oneshot", "kv_copy"};
+    "attn_combine", "attn_prefill", "select_advance", "reduce_shards", "convert", "attn_oproj", "comm_oneshot", "kv_copy",
+    "encoder_embed_ln", "encoder_add_ln", "encoder_bias_gelu", "encoder_attention", "encoder_pool_l2"};
 const char *kernel_class_name(int kc) { return (kc >= 0 && kc < KC_COUNT) ? kNames[kc] : "?"; }
 
 // ------------------------------------------------------------------------------- embedding

@@ -9,7 +9,8 @@ namespace fl {
 // Kernel classes for the measurement hooks (fl_profile_*): one class per kernel symbol family.
 enum KernelClass {
     KC_EMBED = 0, KC_RMSNORM, KC_GEMV, KC_GEMM_MFMA, KC_GEMM_GENERIC, KC_ROPE_KV, KC_ATTN_DECODE,
-    KC_ATTN_COMBINE, KC_ATTN_PREFILL, KC_ARGMAX, KC_REDUCE, KC_CONVERT, KC_ATTN_OPROJ, KC_COMM, KC_KVCOPY, KC_COUNT
+    KC_ATTN_COMBINE, KC_ATTN_PREFILL, KC_ARGMAX, KC_REDUCE, KC_CONVERT, KC_ATTN_OPROJ, KC_COMM, KC_KVCOPY,
+    KC_ENC_EMBED_LN, KC_ENC_ADD_LN, KC_ENC_BIAS_ACT, KC_ENC_ATTN, KC_ENC_POOL, KC_COUNT
 };
 const char *kernel_class_name(int kc);
 
@@ -448,6 +449,29 @@ struct AttnRepArgs {
 };
 bool attn_oproj_rep_supported(int64_t H, int64_t Hkv, int64_t d, int64_t h, int64_t max_seq, bool any_size = false);
 int launch_attn_oproj_rep(Launcher &L, const AttnRepArgs &a);
+
+// ---- the BERT / MiniLM encoder (k_encoder.hip): a packed, ragged batch of sequences -- row r of every [T_total][..] buffer belongs to
+// sequence row_seq[r], which owns rows [offsets[s], offsets[s + 1]) ------------------------------------------------------------------
+enum { ENC_ACT_NONE = -1, ENC_ACT_GELU_TANH = 0, ENC_ACT_GELU_ERF = 1 };
+// LayerNorm with bias, candle_nn::LayerNorm: (x - mean) / sqrt(biased var + eps) * w + b, statistics in fp32
+// x = LN(word[ids[r]] + pos[r - offsets[row_seq[r]]] (+ tt0)) -> x_res fp32 [T][h] and xn (compute dtype) [T][h]; tables in `dtype`
+int launch_encoder_embed_ln(Launcher &L, int dtype, const void *word, const void *pos, const void *tt0 /* [h] or null */, const uint32_t *ids,
+                            const int32_t *row_seq, const int32_t *offsets, const float *w, const float *b, float eps, float *x_res, void *xn,
+                            int64_t T, int64_t h);
+// x_res = LN(x_res + sum of the n_slab split-K slabs of delta (+ bias, when the projection did not add it)) -> x_res and xn
+int launch_encoder_add_ln(Launcher &L, int dtype, float *x_res, const float *delta, int n_slab, int64_t slab_stride, const float *bias,
+                          const float *w, const float *b, float eps, void *xn, int64_t T, int64_t h);
+// out (compute dtype) [T][N] = act(sum of slabs of y fp32 [T][N] (+ bias)); act ENC_ACT_NONE: the conversion alone (Q | K | V)
+int launch_encoder_bias_act(Launcher &L, int dtype, const float *y, int n_slab, int64_t slab_stride, const float *bias, int act, void *out,
+                            int64_t T, int64_t N);
+// unmasked softmax attention of every (sequence, head): q / k / v rows are ld elements apart (a [T][3h] buffer: ld = 3h), out [T][H*d]
+// in the compute dtype.  bf16: MFMA kernel, 64 query rows per workgroup, keys streamed through LDS in tiles of 32; fp32: one wave per
+// query row.  d 32 or 64; ld a multiple of 8.  max_len: the longest sequence (sizes the grid)
+bool encoder_attention_supported(int64_t d);
+int launch_encoder_attention(Launcher &L, int dtype, const void *q, const void *k, const void *v, int64_t ld, const int32_t *offsets, int64_t n_seq,
+                             int64_t max_len, int64_t T_total, int64_t H, int64_t d, float scale, void *out);
+// out[s][:] = mean over the sequence's rows of x (fp32, row order), divided by its L2 norm
+int launch_encoder_pool_l2(Launcher &L, const float *x, const int32_t *offsets, int64_t n_seq, int64_t h, float *out);
 
 // ---- weight conversion at model build ---------------------------------------------------------
 // dst[row_map(r)][c] = cvt(src[r0+r][c0+c]); row_mode 0: dst_row0+r, 1: gate rows, 2: up rows

@@ -18,6 +18,7 @@
 //   generate_stream / generate_tokens_inner (mod.rs:137-340)   Model<M>::generate_stream_ids (per-stream cache, token callback)
 //   Model<M>::generate (mod.rs:363-463)                    Model<M>::generate_ids (token ids in/out;
 //                                                          the tokenizer is outside the hot path)
+//   trait EmbeddingModel, MiniLMModel (embeddings.rs:17-456)   class EmbeddingModel (embed_ids, embed_batch_ids, compute_similarity_ids)
 //
 // Errors: anyhow::Result -> fastllm::Error (exception, carries the fl_status code); config
 // violations that `assert!`/`expect` in the reference (mistral.rs:109-127, qwen.rs:32-37) throw
@@ -1064,6 +1065,115 @@ class StreamBatcher {
     std::deque<Request> queue_;
     fl_batch *batch_ = nullptr;
     uint64_t next_id_ = 0;
+};
+
+// ------------------------------------------------------------------------------------ embeddings.rs
+// trait EmbeddingModel (embeddings.rs:17-38) and its one implementation MiniLMModel (:245-456) on token ids: the tokenizer and
+// do_lower_case stay on the host side of the caller, as for the decoder.  The forward runs on the GPU (fl_encoder_*); Device::Cpu --
+// where the reference runs it (:289) -- is rejected.
+struct BertConfig {                           // embeddings.rs:46-54 (+ vocab_size: the reference takes it from the tokenizer, :301-303)
+    size_t hidden_size = 0, num_attention_heads = 0, num_hidden_layers = 0, intermediate_size = 0, max_position_embeddings = 0;
+    double layer_norm_eps = 0;
+    std::optional<size_t> vocab_size;         // absent: the rows of embeddings.word_embeddings.weight
+    static BertConfig from_json(const std::string &text) {
+        detail::JsonFlat j(text);
+        BertConfig c;
+        c.hidden_size = j.usize("hidden_size");
+        c.num_attention_heads = j.usize("num_attention_heads");
+        c.num_hidden_layers = j.usize("num_hidden_layers");
+        c.intermediate_size = j.usize("intermediate_size");
+        c.max_position_embeddings = j.usize("max_position_embeddings");
+        c.layer_norm_eps = j.num("layer_norm_eps");
+        c.vocab_size = j.opt_usize("vocab_size");
+        return c;
+    }
+};
+
+struct EmbeddingOutput {                      // embeddings.rs:10-15
+    std::vector<float> embeddings;
+    std::string model;
+    size_t token_count = 0;
+};
+
+struct EmbeddingOptions {                     // no counterpart in the reference, whose forward is fixed: tanh GELU, no token-type row
+    fl_activation activation = FL_ACT_GELU_TANH;
+    bool add_token_type0 = false;             // HF's BertModel adds embeddings.token_type_embeddings.weight[0]
+    size_t max_batch_tokens = 0;              // 0: the library's default
+};
+
+class EmbeddingModel {
+  public:
+    EmbeddingModel(const BertConfig &cfg, const TensorMap &tensors, DType dtype, const Device &device, std::string model_id = "",
+                   const EmbeddingOptions &opt = EmbeddingOptions())
+        : model_id_(std::move(model_id)), hidden_(cfg.hidden_size) {
+        if (device.is_cpu())
+            throw Error(FL_ERR_NO_DEVICE, "the MI355X backend has no CPU path: pass Device::mi355x(..) (the reference's MiniLM runs on Device::Cpu, embeddings.rs:289)");
+        if (device.ordinals.size() != 1) throw Error(FL_ERR_UNSUPPORTED, "the encoder runs on one GPU");
+        std::vector<fl_tensor> arr;
+        arr.reserve(tensors.size());
+        size_t vocab = cfg.vocab_size.value_or(0);
+        for (auto &kv : tensors) {
+            fl_tensor t{};
+            t.name = kv.first.c_str(); t.dtype = (int32_t)kv.second.dtype; t.ndim = (int32_t)kv.second.shape.size();
+            if (t.ndim > 4) throw Error(FL_ERR_SHAPE_MISMATCH, "tensor " + kv.first + " has rank > 4");
+            for (int i = 0; i < t.ndim; i++) t.shape[i] = kv.second.shape[i];
+            t.data = kv.second.data; t.device = kv.second.device;
+            arr.push_back(t);
+            if (!cfg.vocab_size && kv.first == "embeddings.word_embeddings.weight" && t.ndim == 2) vocab = (size_t)t.shape[0];
+        }
+        fl_encoder_config c{};
+        c.struct_size = (uint32_t)sizeof c; c.activation = opt.activation; c.add_token_type0 = opt.add_token_type0 ? 1 : 0;
+        c.hidden_size = (int64_t)cfg.hidden_size; c.intermediate_size = (int64_t)cfg.intermediate_size;
+        c.num_hidden_layers = (int64_t)cfg.num_hidden_layers; c.num_attention_heads = (int64_t)cfg.num_attention_heads;
+        c.max_position_embeddings = (int64_t)cfg.max_position_embeddings; c.vocab_size = (int64_t)vocab;
+        c.max_batch_tokens = (int64_t)opt.max_batch_tokens; c.layer_norm_eps = cfg.layer_norm_eps;
+        check(fl_encoder_create(&c, arr.data(), arr.size(), (int32_t)dtype, device.ordinals[0], &enc_), "Failed to initialize embedding model");
+    }
+    ~EmbeddingModel() { if (enc_) fl_encoder_release(enc_); }
+    EmbeddingModel(const EmbeddingModel &) = delete;
+    EmbeddingModel &operator=(const EmbeddingModel &) = delete;
+
+    // EmbeddingModel::embed (embeddings.rs:396-447) behind the tokenizer: forward, mean pooling, L2 normalisation
+    EmbeddingOutput embed_ids(const std::vector<uint32_t> &ids) const {
+        const size_t offsets[2] = {0, ids.size()};
+        EmbeddingOutput out;
+        out.embeddings.resize(hidden_);
+        check(fl_encoder_embed(enc_, ids.data(), offsets, 1, out.embeddings.data()), "Failed to embed");
+        out.model = model_id_; out.token_count = ids.size();
+        return out;
+    }
+    // many texts in one packed call (new capability: the reference embeds one text at a time); result i is embed_ids(seqs[i])
+    std::vector<EmbeddingOutput> embed_batch_ids(const std::vector<std::vector<uint32_t>> &seqs) const {
+        std::vector<uint32_t> ids;
+        std::vector<size_t> offsets{0};
+        for (auto &s : seqs) { ids.insert(ids.end(), s.begin(), s.end()); offsets.push_back(ids.size()); }
+        std::vector<float> flat(seqs.size() * hidden_);
+        check(fl_encoder_embed(enc_, ids.data(), offsets.data(), seqs.size(), flat.data()), "Failed to embed");
+        std::vector<EmbeddingOutput> out(seqs.size());
+        for (size_t i = 0; i < seqs.size(); i++) {
+            out[i].embeddings.assign(flat.begin() + i * hidden_, flat.begin() + (i + 1) * hidden_);
+            out[i].model = model_id_; out[i].token_count = seqs[i].size();
+        }
+        return out;
+    }
+    std::string model_id() const { return model_id_; }
+    size_t embedding_size() const { return hidden_; }           // the model's hidden_size (the reference hard-codes 384, :453-455)
+    // compute_similarity (embeddings.rs:22-37): the cosine, in f32 and in the reference's order of operations
+    float compute_similarity_ids(const std::vector<uint32_t> &a, const std::vector<uint32_t> &b) const {
+        const std::vector<float> v1 = embed_ids(a).embeddings, v2 = embed_ids(b).embeddings;
+        float dot = 0.f, n1 = 0.f, n2 = 0.f;
+        for (size_t i = 0; i < v1.size(); i++) dot += v1[i] * v2[i];
+        for (float x : v1) n1 += x * x;
+        for (float x : v2) n2 += x * x;
+        return dot / (std::sqrt(n1) * std::sqrt(n2));
+    }
+    static const char *get_family() { return "bert"; }          // embeddings.rs:458-466
+    static bool supports_architecture(const std::string &a) { return a == "BertModel" || a == "RobertaModel" || a == "DebertaModel"; }
+
+  private:
+    fl_encoder *enc_ = nullptr;
+    std::string model_id_;
+    size_t hidden_;
 };
 
 }  // namespace fastllm

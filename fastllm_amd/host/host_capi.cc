@@ -353,4 +353,46 @@ int flh_prefix_index_insert(void *pv, const uint32_t *ids, size_t n_ids, int64_t
 }
 void flh_prefix_index_destroy(void *pv) { delete static_cast<PrefixIndex *>(pv); }
 
+// EmbeddingModel (fastllm_host.hpp): the reference's embeddings trait (embeddings.rs:17-38) on token ids
+int flh_embedding_create(const char *config_json, const fl_tensor *tensors, size_t n, int dtype, int device_ordinal, int activation,
+                         int add_token_type0, void **out) {
+    return guard([&] {
+        if (!config_json || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        const BertConfig cfg = BertConfig::from_json(config_json);
+        EmbeddingOptions opt; opt.activation = (fl_activation)activation; opt.add_token_type0 = add_token_type0 != 0;
+        const Device dev = device_ordinal < 0 ? Device::cpu() : Device::mi355x(device_ordinal);
+        *out = new EmbeddingModel(cfg, to_map(tensors, n), (DType)dtype, dev, "synthetic", opt);
+        return 0;
+    });
+}
+void flh_embedding_destroy(void *ev) { delete static_cast<EmbeddingModel *>(ev); }
+size_t flh_embedding_size(void *ev) { return static_cast<EmbeddingModel *>(ev)->embedding_size(); }
+int flh_embed_ids(void *ev, const uint32_t *ids, size_t T, float *out, size_t *token_count) {
+    return guard([&] {
+        if (!ev || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        const EmbeddingOutput r = static_cast<EmbeddingModel *>(ev)->embed_ids(std::vector<uint32_t>(ids, ids + T));
+        std::memcpy(out, r.embeddings.data(), r.embeddings.size() * sizeof(float));
+        if (token_count) *token_count = r.token_count;
+        return 0;
+    });
+}
+int flh_embed_batch_ids(void *ev, const uint32_t *ids, const size_t *offsets, size_t n_seq, float *out) {
+    return guard([&] {
+        if (!ev || !out || !offsets) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        std::vector<std::vector<uint32_t>> seqs;
+        for (size_t s = 0; s < n_seq; s++) seqs.emplace_back(ids + offsets[s], ids + offsets[s + 1]);
+        const auto *em = static_cast<EmbeddingModel *>(ev);
+        const std::vector<EmbeddingOutput> r = em->embed_batch_ids(seqs);
+        for (size_t s = 0; s < n_seq; s++) std::memcpy(out + s * em->embedding_size(), r[s].embeddings.data(), em->embedding_size() * sizeof(float));
+        return 0;
+    });
+}
+int flh_compute_similarity_ids(void *ev, const uint32_t *a, size_t na, const uint32_t *b, size_t nb, float *out) {
+    return guard([&] {
+        if (!ev || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        *out = static_cast<EmbeddingModel *>(ev)->compute_similarity_ids(std::vector<uint32_t>(a, a + na), std::vector<uint32_t>(b, b + nb));
+        return 0;
+    });
+}
+
 }  // extern "C"

@@ -385,6 +385,59 @@ int  fl_batch_decode_each_ex(fl_batch *b, const uint32_t *first_tokens, const si
 
 int fl_synchronize(fl_model *m);
 
+/* ---- embeddings: the BERT / MiniLM encoder forward --------------------------------------------------------------------------------
+ * The reference's second model path: trait EmbeddingModel (src/models/embeddings.rs:17-38), implemented by MiniLMModel on the CPU in
+ * fp32, one text at a time (embeddings.rs:289).  Here the same forward runs on the GPU over a packed batch of sequences.
+ * What is reproduced (line numbers of src/models/embeddings.rs):
+ *   input    x = LayerNorm(word_embeddings[ids] + position_embeddings[0..T)), eps hard-wired to 1e-12 (:315-318); token-type embeddings
+ *            are never added (:370-378) -- HF's BertModel adds row 0, which add_token_type0 = 1 restores.
+ *   layer    post-LN (:130-243): a = softmax(Q K^T / sqrt(d)) V with NO mask (bidirectional; heads hidden_size / num_attention_heads
+ *            wide, :77); x = LN(x + dense(a)); x = LN(x + output(gelu(intermediate(x)))); eps = layer_norm_eps (:104-109, :213-218).
+ *   gelu     candle's Tensor::gelu (:229-231) is the TANH form 0.5 v (1 + tanh(sqrt(2/pi) v (1 + 0.044715 v^2))); gelu_erf is the exact
+ *            one [UPSTREAM-RECALLED: restated from memory of upstream candle, not from a copy].  HF checkpoints of this family were
+ *            trained with the erf form, so both are offered; the reference's is the default.
+ *   LN       candle_nn::LayerNorm: mean and biased variance over hidden_size in fp32, (x - mean) / sqrt(var + eps) * w + b.
+ *   pooling  the attention mask is all ones (:346-368): the mean of the last hidden states over the sequence's tokens (:430-433),
+ *            divided by its L2 norm (:341-344, :436).
+ * Tensor names carry no "bert." prefix (:298-327): embeddings.word_embeddings.weight [V,h], embeddings.position_embeddings.weight
+ * [P,h], embeddings.LayerNorm.{weight,bias}, and per layer encoder.layer.{i}. attention.self.{query,key,value}.{weight,bias},
+ * attention.output.dense.{weight,bias}, attention.output.LayerNorm.{weight,bias}, intermediate.dense.{weight,bias},
+ * output.dense.{weight,bias}, output.LayerNorm.{weight,bias}; with add_token_type0 also embeddings.token_type_embeddings.weight [*,h].
+ * One GPU; submission is serialised per encoder.  compute_dtype FL_DTYPE_F32 is the parity mode; in FL_DTYPE_BF16 the GEMM inputs,
+ * Q / K / V, the attention probabilities and the GELU output are bf16, the residual stream and the LayerNorm statistics fp32.
+ * fl_encoder_create, decided before the device probe: FL_ERR_BAD_CONFIG (a size that is not positive, heads that do not divide
+ * hidden_size); FL_ERR_UNSUPPORTED (head_dim other than 32 or 64 -- so hidden_size is always a multiple of 8 --, intermediate_size not a multiple of 8);
+ * FL_ERR_BAD_ARGUMENT (unknown activation, wrong struct_size, non-zero _pad / _reserved, null cfg / out, compute dtype other than F32 / BF16).  Afterwards:
+ * FL_ERR_NO_DEVICE (there is no CPU path), FL_ERR_MISSING_TENSOR / FL_ERR_SHAPE_MISMATCH.
+ * Per call, decided before any launch: FL_ERR_BAD_ARGUMENT (an empty sequence -- the reference would divide by zero --, offsets that
+ * do not start at 0 or decrease, an id >= vocab_size, null pointers); FL_ERR_SEQ_OVERFLOW (a sequence longer than
+ * max_position_embeddings, more than max_batch_tokens tokens in all).  The encoder stays usable after any of them. */
+typedef enum fl_activation { FL_ACT_GELU_TANH = 0 /* the reference */, FL_ACT_GELU_ERF = 1 } fl_activation;
+typedef struct fl_encoder_config {
+    uint32_t struct_size;            /* sizeof(fl_encoder_config), else FL_ERR_BAD_ARGUMENT */
+    int32_t  activation;             /* fl_activation */
+    int32_t  add_token_type0;        /* 0: as the reference; 1: + embeddings.token_type_embeddings.weight[0] (HF) */
+    int32_t  _pad;
+    int64_t  hidden_size, intermediate_size, num_hidden_layers, num_attention_heads,
+             max_position_embeddings, vocab_size;
+    int64_t  max_batch_tokens;       /* workspace, allocated once at create; 0 -> 4096 */
+    double   layer_norm_eps;
+    int64_t  _reserved[2];           /* 0, else FL_ERR_BAD_ARGUMENT */
+} fl_encoder_config;
+typedef struct fl_encoder fl_encoder;
+int  fl_encoder_create(const fl_encoder_config *cfg, const fl_tensor *tensors, size_t n_tensors,
+                       int32_t compute_dtype /* FL_DTYPE_F32 | FL_DTYPE_BF16 */, int32_t device, fl_encoder **out);
+void fl_encoder_release(fl_encoder *e);
+/* last hidden states of ONE sequence, [T][h] fp32 host: what MiniLMModel::forward returns (embeddings.rs:380-393) */
+int  fl_encoder_hidden(fl_encoder *e, const uint32_t *ids, size_t T, float *out);
+/* n_seq sequences packed back to back: sequence s is ids[offsets[s] .. offsets[s+1]); out [n_seq][h] fp32 host =
+ * L2-normalised mean of each sequence's last hidden states: EmbeddingModel::embed per sequence (embeddings.rs:396-447) */
+int  fl_encoder_embed(fl_encoder *e, const uint32_t *ids, const size_t *offsets /* [n_seq + 1] */, size_t n_seq, float *out);
+/* the unmasked ragged attention kernel alone on host buffers (unit tests): q/k/v [T_total][H*d] of `dtype` (FL_DTYPE_BF16: the MFMA
+ * kernel, its bf16 output widened; FL_DTYPE_F32: the VALU kernel), d 32 or 64, out [T_total][H*d] fp32 */
+int  fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq,
+                             int64_t H, int64_t d, int32_t dtype, float *out);
+
 /* Which slice of a full HF tensor does tp_rank own?  Pure host function (no GPU):
  * out = {row_begin, row_end, col_begin, col_end}.  Column-parallel q/k/v/gate/up/lm_head
  * (rows of the [out,in] matrix), row-parallel o_proj/down_proj (columns), everything else whole. */

@@ -44,6 +44,10 @@ pub const FL_TP_EMULATED: i32 = 3;
 pub const FL_WEIGHTS_COMPUTE_DTYPE: i32 = 0;
 pub const FL_WEIGHTS_E4M3_ROW: i32 = 1;
 
+// fl_activation: the encoder's GELU form (TANH: candle's Tensor::gelu, what the reference runs; ERF: the exact form HF BERT checkpoints were trained with)
+pub const FL_ACT_GELU_TANH: i32 = 0;
+pub const FL_ACT_GELU_ERF: i32 = 1;
+
 /// `fl_config`: the fields of the reference's ConfigFile / BaseModelConfig (config.rs:6-18).  0 in an optional field
 /// = absent from config.json = the reference's default.
 #[repr(C)]
@@ -166,6 +170,26 @@ pub struct fl_kernel_stat {
     pub flops: f64,
 }
 
+/// `fl_encoder_config`: the fields of the reference's BertConfig (src/models/embeddings.rs:46-54) + vocab_size, the GELU form, the
+/// HF token-type option and the workspace size.  `struct_size` must be `size_of::<fl_encoder_config>()`; `_reserved` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct fl_encoder_config {
+    pub struct_size: u32,
+    pub activation: i32,
+    pub add_token_type0: i32,
+    pub _pad: i32,
+    pub hidden_size: i64,
+    pub intermediate_size: i64,
+    pub num_hidden_layers: i64,
+    pub num_attention_heads: i64,
+    pub max_position_embeddings: i64,
+    pub vocab_size: i64,
+    pub max_batch_tokens: i64,
+    pub layer_norm_eps: f64,
+    pub _reserved: [i64; 2],
+}
+
 /// Opaque handles.
 #[repr(C)]
 pub struct fl_model {
@@ -177,6 +201,10 @@ pub struct fl_cache {
 }
 #[repr(C)]
 pub struct fl_batch {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct fl_encoder {
     _private: [u8; 0],
 }
 
@@ -341,6 +369,32 @@ extern "C" {
     ) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;
+
+    /// The BERT / MiniLM encoder (the reference's EmbeddingModel path, src/models/embeddings.rs) on GPU `device`.
+    pub fn fl_encoder_create(
+        cfg: *const fl_encoder_config,
+        tensors: *const fl_tensor,
+        n_tensors: usize,
+        compute_dtype: i32,
+        device: i32,
+        out: *mut *mut fl_encoder,
+    ) -> c_int;
+    pub fn fl_encoder_release(e: *mut fl_encoder);
+    /// Last hidden states of one sequence, `[t][hidden_size]` f32.
+    pub fn fl_encoder_hidden(e: *mut fl_encoder, ids: *const u32, t: usize, out: *mut f32) -> c_int;
+    /// `n_seq` packed sequences (`offsets[n_seq + 1]`) -> `[n_seq][hidden_size]` L2-normalised mean-pooled embeddings.
+    pub fn fl_encoder_embed(e: *mut fl_encoder, ids: *const u32, offsets: *const usize, n_seq: usize, out: *mut f32) -> c_int;
+    pub fn fl_op_encoder_attention(
+        q: *const c_void,
+        k: *const c_void,
+        v: *const c_void,
+        offsets: *const usize,
+        n_seq: usize,
+        h: i64,
+        d: i64,
+        dtype: i32,
+        out: *mut f32,
+    ) -> c_int;
     pub fn fl_tp_slice(cfg: *const fl_config, tensor_name: *const c_char, tp_rank: i32, tp_size: i32, out: *mut i64) -> c_int;
 
     pub fn fl_profile_begin(m: *mut fl_model) -> c_int;

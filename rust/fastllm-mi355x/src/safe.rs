@@ -479,6 +479,148 @@ impl<'a> Batch<'a> {
     }
 }
 
+/// The encoder's GELU form (`fl_activation`).  `Tanh` is candle's `Tensor::gelu`, what the reference runs (embeddings.rs:229-231);
+/// `Erf` is the exact form HF BERT checkpoints were trained with.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum Activation {
+    GeluTanh = ffi::FL_ACT_GELU_TANH,
+    GeluErf = ffi::FL_ACT_GELU_ERF,
+}
+
+/// The fields of the reference's `BertConfig` (src/models/embeddings.rs:46-54) plus what the reference takes from elsewhere or
+/// hard-wires: `vocab_size` (the tokenizer's, :301-303), the GELU form, HF's token-type row 0 (the reference never adds it,
+/// :370-378) and the workspace size (`max_batch_tokens` 0: the library's default, 4096).
+#[derive(Clone, Debug)]
+pub struct EncoderConfig {
+    pub hidden_size: usize,
+    pub num_attention_heads: usize,
+    pub num_hidden_layers: usize,
+    pub intermediate_size: usize,
+    pub max_position_embeddings: usize,
+    pub layer_norm_eps: f64,
+    pub vocab_size: usize,
+    pub activation: Activation,
+    pub add_token_type0: bool,
+    pub max_batch_tokens: usize,
+}
+
+impl EncoderConfig {
+    pub fn to_ffi(&self) -> ffi::fl_encoder_config {
+        ffi::fl_encoder_config {
+            struct_size: std::mem::size_of::<ffi::fl_encoder_config>() as u32,
+            activation: self.activation as i32,
+            add_token_type0: self.add_token_type0 as i32,
+            _pad: 0,
+            hidden_size: self.hidden_size as i64,
+            intermediate_size: self.intermediate_size as i64,
+            num_hidden_layers: self.num_hidden_layers as i64,
+            num_attention_heads: self.num_attention_heads as i64,
+            max_position_embeddings: self.max_position_embeddings as i64,
+            vocab_size: self.vocab_size as i64,
+            max_batch_tokens: self.max_batch_tokens as i64,
+            layer_norm_eps: self.layer_norm_eps,
+            _reserved: [0; 2],
+        }
+    }
+}
+
+/// `fl_encoder*`: the BERT / MiniLM encoder forward on one GPU (the reference's `MiniLMModel`, which runs on the CPU).  The library
+/// serialises submission per encoder, so a shared reference may be used from several threads.
+pub struct Encoder {
+    raw: *mut ffi::fl_encoder,
+    hidden: usize,
+}
+// SAFETY: submission is serialised per encoder and every entry sets its HIP device itself (include/fastllm_mi355x.h).
+unsafe impl Send for Encoder {}
+unsafe impl Sync for Encoder {}
+
+impl Drop for Encoder {
+    fn drop(&mut self) {
+        unsafe { ffi::fl_encoder_release(self.raw) };
+    }
+}
+
+impl Encoder {
+    /// Tensor names as in the checkpoint, without a `bert.` prefix (embeddings.rs:298-327).
+    pub fn new(cfg: &EncoderConfig, tensors: &[TensorView<'_>], compute: DType, device_id: i32) -> Result<Encoder> {
+        let names: Vec<CString> = tensors
+            .iter()
+            .map(|t| CString::new(t.name).map_err(|_| Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("tensor name {:?} contains NUL", t.name) }))
+            .collect::<Result<_>>()?;
+        let mut descr = Vec::with_capacity(tensors.len());
+        for (t, name) in tensors.iter().zip(&names) {
+            if t.shape.len() > 4 {
+                return Err(Error { code: ffi::FL_ERR_SHAPE_MISMATCH, message: format!("tensor {} has rank {}", t.name, t.shape.len()) });
+            }
+            let mut shape = [0i64; 4];
+            for (d, s) in shape.iter_mut().zip(t.shape) {
+                *d = *s as i64;
+            }
+            descr.push(ffi::fl_tensor { name: name.as_ptr(), dtype: t.dtype as i32, ndim: t.shape.len() as i32, shape, data: t.data, device: t.device, _pad: 0 });
+        }
+        let c = cfg.to_ffi();
+        let mut raw: *mut ffi::fl_encoder = ptr::null_mut();
+        // SAFETY: every pointer is valid for the duration of the call; the library copies what it keeps.
+        check(unsafe { ffi::fl_encoder_create(&c, descr.as_ptr(), descr.len(), compute as i32, device_id, &mut raw) })?;
+        Ok(Encoder { raw, hidden: cfg.hidden_size })
+    }
+
+    /// The model's `hidden_size` (the reference's `embedding_size()` hard-codes 384, embeddings.rs:453-455).
+    pub fn embedding_size(&self) -> usize {
+        self.hidden
+    }
+
+    /// `MiniLMModel::forward` (embeddings.rs:380-393): last hidden states of one sequence, row-major `[ids.len()][hidden_size]`.
+    pub fn hidden(&self, ids: &[u32]) -> Result<Vec<f32>> {
+        let mut out = vec![0f32; ids.len() * self.hidden];
+        check(unsafe { ffi::fl_encoder_hidden(self.raw, ids.as_ptr(), ids.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// `EmbeddingModel::embed` (embeddings.rs:396-447) behind the tokenizer, for many sequences in one packed call: the
+    /// L2-normalised mean of each sequence's last hidden states.
+    pub fn embed(&self, seqs: &[&[u32]]) -> Result<Vec<Vec<f32>>> {
+        let mut ids = Vec::new();
+        let mut offsets = vec![0usize];
+        for s in seqs {
+            ids.extend_from_slice(s);
+            offsets.push(ids.len());
+        }
+        let mut flat = vec![0f32; seqs.len() * self.hidden];
+        check(unsafe { ffi::fl_encoder_embed(self.raw, ids.as_ptr(), offsets.as_ptr(), seqs.len(), flat.as_mut_ptr()) })?;
+        Ok(flat.chunks(self.hidden.max(1)).map(|c| c.to_vec()).collect())
+    }
+}
+
+/// The encoder's unmasked ragged attention kernel alone (`fl_op_encoder_attention`) on f32 inputs: `q` / `k` / `v` are
+/// `[sum(lengths)][heads * head_dim]`.
+pub fn op_encoder_attention_f32(q: &[f32], k: &[f32], v: &[f32], lengths: &[usize], heads: usize, head_dim: usize) -> Result<Vec<f32>> {
+    let total: usize = lengths.iter().sum();
+    if q.len() != total * heads * head_dim || k.len() != q.len() || v.len() != q.len() {
+        return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("q / k / v must hold {} rows of {} values", total, heads * head_dim) });
+    }
+    let mut offsets = vec![0usize];
+    for l in lengths {
+        offsets.push(offsets[offsets.len() - 1] + l);
+    }
+    let mut out = vec![0f32; q.len()];
+    check(unsafe {
+        ffi::fl_op_encoder_attention(
+            q.as_ptr() as *const c_void,
+            k.as_ptr() as *const c_void,
+            v.as_ptr() as *const c_void,
+            offsets.as_ptr(),
+            lengths.len(),
+            heads as i64,
+            head_dim as i64,
+            ffi::FL_DTYPE_F32,
+            out.as_mut_ptr(),
+        )
+    })?;
+    Ok(out)
+}
+
 /// Number of HIP devices the library sees (0 without a GPU: `Model::new` then fails with `FL_ERR_NO_DEVICE`; there is
 /// no CPU path).
 pub fn device_count() -> usize {
