@@ -728,19 +728,7 @@ static int launch_pf32(Launcher &L, const void *q, const void *k_cache, const vo
     const int64_t nb = (T + 32 * TB - 1) / (32 * TB);
     const int64_t G = H / Hkv, nsg = gsub > 0 ? (G + gsub - 1) / gsub : 1;
     dim3 grid((unsigned)(paired ? (nb + 1) / 2 : nb), (unsigned)(Hkv * nsg));
-    if (paired == 2) {                                              // one persistent workgroup per CU of the CURRENT device
-        static std::atomic<int> cached[64];
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            cus = cached[dev].load();
-            if (!cus) {
-                hipDeviceProp_t prop;
-                cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-                cached[dev].store(cus);
-            }
-        }
-        grid = dim3((unsigned)cus, 1);
-    }
+    if (paired == 2) grid = dim3((unsigned)device_cu_count(), 1);   // one persistent workgroup per CU of the CURRENT device
     const size_t lds = (KSF == 4 ? 2 : 3) * (size_t)(2 * 32 * D * 2) * KSF;
     const double flops = 2.0 * (double)T * T * H * D;
     Launcher LL = L; LL.tag = KSF == 4 ? "32row,ks4" : KSF == 2 ? "32row,ks2" : "32row";

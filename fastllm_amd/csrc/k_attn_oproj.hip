@@ -280,13 +280,7 @@ bool attn_oproj_plan(int64_t H, int64_t Hkv, int64_t d, int64_t h, int nsplit, i
 int launch_attn_oproj(Launcher &L, const void *q, const void *k_cache, const void *v_cache_T, const StepState *st,
                       StepState *st_rw, float *partials, unsigned *done, int nsplit, int attn_waves, int64_t kv_len_hint,
                       const void *Wo, float *slabs, int64_t H, int64_t Hkv, int64_t d, int64_t h, int64_t seq_alloc, float scale) {
-    static std::atomic<int> cus_cached{0};                // (all shards run on the same kind of GPU)
-    int cus = cus_cached.load();
-    if (!cus) {
-        int dev = 0; hipDeviceProp_t p;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-        cus_cached.store(cus);
-    }
+    const int cus = device_cu_count();
     int nb = 0, ra = 0, ro = 0; size_t lds = 0;
     if (!attn_oproj_plan(H, Hkv, d, h, nsplit, cus, &nb, &ra, &ro, &lds))
         FL_FAIL(FL_ERR_UNSUPPORTED, "fused attention+o_proj launch does not fit this shape");

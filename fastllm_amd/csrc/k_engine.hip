@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "comm_ll.h"
+#include "gemv_parts.h"
 #include "kernels.h"
 
 namespace fl {
@@ -172,7 +173,8 @@ __device__ inline void eng_gather(const EngArgs &a, const EngOp &op, int o, EngC
 
 // ---- streamer side ---------------------------------------------------------------------------------------------------
 template <int R, int U, int OUT>
-__device__ inline void eng_stream(const EngArgs &a, const EngOp &op, int o, EngCtx &c, float &best_v, int &best_i) {
+__device__ inline void eng_stream(const EngArgs &a, const EngOp &op, int o, EngCtx &c, GemvBest &best) {
+    constexpr int EPI = OUT == ENG_OUT_EDGE_ACT ? EPI_GATEUP : (OUT == ENG_OUT_QKV ? EPI_QKV_ROPE : EPI_F32);   // the row map (gemv_parts.h)
     const bf16_t *__restrict__ W = reinterpret_cast<const bf16_t *>(op.W);
     const bf16_t *xs = (o & 1) ? c.xs1 : c.xs0;
     const int N = op.N, K = op.K, lane = c.lane;
@@ -186,11 +188,7 @@ __device__ inline void eng_stream(const EngArgs &a, const EngOp &op, int o, EngC
     const bool ragged = nchunk % (64 * U) != 0;
     typedef RawW Buf[R][U];
 
-    auto row_of = [&](int g, int r) -> int {
-        if (OUT == ENG_OUT_EDGE_ACT) { const int q = g * (R / 2) + (r >> 1); return (q >> 4) * 32 + (q & 15) + ((r & 1) << 4); }
-        if (OUT == ENG_OUT_QKV) { const int q = g * (R / 2) + (r >> 1); const int hd = q / half, j = q - hd * half; return hd * a.d + j + (r & 1) * half; }
-        return g * R + r;
-    };
+    auto row_of = [&](int g, int r) -> int { return gemv_row_of<EPI, R>(g, r, a.d, half); };
     int lg = gw, lb = 0;
     auto load_next = [&](Buf &buf) {
         const int g = min(lg, ngroups - 1);
@@ -220,26 +218,10 @@ __device__ inline void eng_stream(const EngArgs &a, const EngOp &op, int o, EngC
     }
 
     // RoPE operands of this wave's first group (position from the step state): also ahead of the barrier
-    uint32_t rope_p = 0, rope_slot = 0;
-    float rope_c[(R + 1) / 2], rope_s[(R + 1) / 2], rope_b0[(R + 1) / 2], rope_b1[(R + 1) / 2];
-    auto rope_prefetch = [&](int g) {
-#pragma unroll
-        for (int r = 0; r < R; r += 2) {
-            const int q = g * (R / 2) + (r >> 1);
-            const int hd = q / half, j = q - hd * half;
-            const bool rot = hd < a.H + a.Hkv;
-            rope_c[r >> 1] = rot ? a.cos_tab[(size_t)rope_p * half + j] : 1.f;
-            rope_s[r >> 1] = rot ? a.sin_tab[(size_t)rope_p * half + j] : 0.f;
-            const int r0w = row_of(g, r), r1w = row_of(g, r + 1);
-            rope_b0[r >> 1] = op.bias && r1w < N ? op.bias[r0w] : 0.f;
-            rope_b1[r >> 1] = op.bias && r1w < N ? op.bias[r1w] : 0.f;
-        }
-    };
-    if (OUT == ENG_OUT_QKV) {
-        const uint32_t pos = a.st->pos;
-        rope_slot = a.st->len;
-        rope_p = pos < (uint32_t)a.max_pos ? pos : (uint32_t)a.max_pos - 1;
-        if (gw < ngroups) rope_prefetch(gw);
+    GemvRope<bf16_t, R> rope(a, op.bias, N);
+    if constexpr (OUT == ENG_OUT_QKV) {
+        rope.begin(a.st, a.max_pos);
+        if (gw < ngroups) rope.prefetch(gw);
     }
 
     __builtin_amdgcn_s_barrier();                                         // x of this op is in LDS (the gatherers waited for their writes)
@@ -275,54 +257,21 @@ __device__ inline void eng_stream(const EngArgs &a, const EngOp &op, int o, EngC
             // one gate/up pair per item -> one 4-byte {bf16 silu(g)*u, 16-bit tag} granule (the tag's low half: consecutive steps
             // differ in it, and a word only ever holds the last step's value); two-row items keep every wave of the CU streaming
             static_assert(R == 2, "one channel per item");
-            const float a0 = sum[0] / (1.0f + expf(-sum[0])) * sum[1];            // candle silu(g) * u
+            const float a0 = gemv_silu_gate(sum[0], sum[1]);
             if (lane == 0 && row_of(g, 1) < N)
                 __hip_atomic_store((__attribute__((address_space(1))) uint32_t *)(reinterpret_cast<uint32_t *>(op.out_edge) + g),
                                    ((tag & 0xffffu) << 16) | (uint32_t)float_to_bf16_bits(a0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if constexpr (OUT == ENG_OUT_QKV) {
-            if (lane != 0) return;
-            const uint32_t slot = rope_slot;
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int r1w = row_of(g, r + 1);
-                if (r1w >= N) continue;
-                const int q = g * (R / 2) + (r >> 1);
-                const int hd = q / half, j = q - hd * half;
-                float x0 = sum[r], x1 = sum[r + 1];
-                if (op.bias) { x0 += rope_b0[r >> 1]; x1 += rope_b1[r >> 1]; }
-                bf16_t *dst;
-                size_t stride = 1;
-                if (hd < a.H + a.Hkv) {                                   // rotate-half RoPE (App. A.4)
-                    float t0, t1;
-                    rope_rotate(x0, x1, rope_c[r >> 1], rope_s[r >> 1], t0, t1);
-                    x0 = t0; x1 = t1;
-                    dst = hd < a.H ? reinterpret_cast<bf16_t *>(a.q_out) + (size_t)hd * a.d
-                                   : reinterpret_cast<bf16_t *>(a.k_cache) + ((size_t)(hd - a.H) * a.max_seq + slot) * a.d;
-                } else if (a.v_ld > 0) {                                  // transposed value cache [Hkv][d][v_ld]
-                    dst = reinterpret_cast<bf16_t *>(a.v_cache) + (size_t)(hd - a.H - a.Hkv) * a.d * a.v_ld + slot;
-                    stride = (size_t)a.v_ld;
-                } else {
-                    dst = reinterpret_cast<bf16_t *>(a.v_cache) + ((size_t)(hd - a.H - a.Hkv) * a.max_seq + slot) * a.d;
-                }
-                dst[(size_t)j * stride] = float_to_bf16_bits(x0);
-                dst[(size_t)(j + half) * stride] = float_to_bf16_bits(x1);
-            }
+            if (lane == 0) rope.store(g, sum);
         } else {                                                          // ENG_OUT_LOGITS
-            if (lane != 0) return;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int row = g * R + r;
-                if (row < N) {
-                    const float y = sum[r] + (op.bias ? op.bias[row] : 0.f);
-                    reinterpret_cast<float *>(op.dst)[row] = y;
-                    if (a.amax && (best_i < 0 || y > best_v || (y == best_v && row > best_i))) { best_v = y; best_i = row; }
-                }
-            }
+            if (lane == 0) gemv_store_f32<R>(reinterpret_cast<float *>(op.dst), op.bias, N, g, sum, a.amax != nullptr, best);
         }
     };
     int cg = gw, cb = 0;
     auto consume = [&](const Buf &buf) {
-        if (OUT == ENG_OUT_QKV && cb == 0 && cg != gw) rope_prefetch(cg);
+        if constexpr (OUT == ENG_OUT_QKV) {
+            if (cb == 0 && cg != gw) rope.prefetch(cg);
+        }
         const int c0 = lane + 64 * U * cb;
         if (ragged && cb == nb - 1) {                                     // wave-uniform: the partial last block of K
 #pragma unroll
@@ -384,7 +333,7 @@ __global__ __launch_bounds__(E_THREADS) void engine_kernel(const EngArgs a) {
     if (STAMPS && stamp && threadIdx.x == 0) stamp[0] = wall_clock64();
     __syncthreads();
 
-    float best_v = -INFINITY; int best_i = -1;
+    GemvBest best;
     for (int o = 0; o < a.nops; o++) {
         const EngOp &op = a.op[o];
         if (c.wave < E_NG) {
@@ -394,32 +343,21 @@ __global__ __launch_bounds__(E_THREADS) void engine_kernel(const EngArgs a) {
             __builtin_amdgcn_s_barrier();
         } else {
             // 8-KiB blocks everywhere: two rows (a gate/up pair, a RoPE pair) x four 1-KiB chunks
-            if (op.out == ENG_OUT_EDGE_ACT) eng_stream<2, 4, ENG_OUT_EDGE_ACT>(a, op, o, c, best_v, best_i);
+            if (op.out == ENG_OUT_EDGE_ACT) eng_stream<2, 4, ENG_OUT_EDGE_ACT>(a, op, o, c, best);
             else if (op.out == ENG_OUT_EDGE_F32) {
                 // few rows per CU (o_proj, down_proj of a small model): one row per wave, so that every wave of the CU streams
-                if (op.R == 1) eng_stream<1, 4, ENG_OUT_EDGE_F32>(a, op, o, c, best_v, best_i);
-                else eng_stream<2, 4, ENG_OUT_EDGE_F32>(a, op, o, c, best_v, best_i);
+                if (op.R == 1) eng_stream<1, 4, ENG_OUT_EDGE_F32>(a, op, o, c, best);
+                else eng_stream<2, 4, ENG_OUT_EDGE_F32>(a, op, o, c, best);
             }
-            else if (op.out == ENG_OUT_QKV) eng_stream<2, 4, ENG_OUT_QKV>(a, op, o, c, best_v, best_i);
-            else eng_stream<2, 4, ENG_OUT_LOGITS>(a, op, o, c, best_v, best_i);
+            else if (op.out == ENG_OUT_QKV) eng_stream<2, 4, ENG_OUT_QKV>(a, op, o, c, best);
+            else eng_stream<2, 4, ENG_OUT_LOGITS>(a, op, o, c, best);
             if (STAMPS && stamp && threadIdx.x == E_NG * 64) stamp[2 + 4 * o] = wall_clock64();  // streamer wave 0 done with op o
             if (c.lane == 0) __hip_atomic_fetch_add(c.misc + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
     // the workgroup's ArgMax candidate (lm_head as the last op): lane 0 of every streamer wave holds the best of its rows
-    if (a.amax) {
-        float *cv = reinterpret_cast<float *>(c.misc) + 8;
-        int *ci = reinterpret_cast<int *>(c.misc) + 8 + (E_NG + E_NS);
-        if (c.lane == 0) { cv[c.wave] = best_v; ci[c.wave] = best_i; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float bv = -INFINITY; int bi = -1;
-            for (int w = E_NG; w < E_NG + E_NS; w++)
-                if (ci[w] >= 0 && (bi < 0 || cv[w] > bv || (cv[w] == bv && ci[w] > bi))) { bv = cv[w]; bi = ci[w]; }
-            a.amax[1 + blockIdx.x] = ArgmaxCand{bv, bi};
-            if (blockIdx.x == 0) a.amax[0] = ArgmaxCand{0.f, (int)gridDim.x};
-        }
-    }
+    if (a.amax)
+        gemv_leave_candidate(a.amax, reinterpret_cast<float *>(c.misc) + 8, reinterpret_cast<int *>(c.misc) + 8 + (E_NG + E_NS), E_NG, E_NG + E_NS, best);
     if (STAMPS && stamp && threadIdx.x == 0) stamp[31] = wall_clock64();
 }
 
@@ -464,13 +402,7 @@ int launch_engine(Launcher &L, const EngArgs &a_in) {
     a.xs1_bytes = (int)((k1 * 2 + 15) & ~(size_t)15);
     const size_t lds = E_MISC_BYTES + (size_t)a.xs0_bytes + a.xs1_bytes + (size_t)a.h * 4;
     if (lds > 150 * 1024) FL_FAIL(FL_ERR_UNSUPPORTED, "engine: vectors of %zu bytes do not fit the LDS", lds);
-    int dev = 0;
-    FL_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t p;
-    static int cus[64];
-    if (dev < 0 || dev >= 64) FL_FAIL(FL_ERR_HIP, "engine: device index");
-    if (!cus[dev]) { FL_HIP(hipGetDeviceProperties(&p, dev)); cus[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256; }
-    const int blocks = a.grid > 0 ? a.grid : cus[dev];
+    const int blocks = a.grid > 0 ? a.grid : device_cu_count();
     const int delay = tune(TK_ENGINE_DELAY);
     a.gather_delay = delay;
     const int pfb = tune(TK_ENGINE_PF);

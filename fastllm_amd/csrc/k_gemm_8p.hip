@@ -536,7 +536,6 @@ void gemm_8p_release_stream(hipStream_t stream) {
     }
 }
 
-static int cu_count();
 static int streamk_space(hipStream_t stream, int nwg, StreamK *sk) {
     int dev = 0;
     FL_HIP(hipGetDevice(&dev));
@@ -545,7 +544,7 @@ static int streamk_space(hipStream_t stream, int nwg, StreamK *sk) {
     if (sp.nwg < nwg) {
         // sized ONCE for a workgroup per CU (launch_gemm_8p never asks for more): no synchronise-and-free in the middle of a
         // launch sequence; gemm_8p_workspace_bytes() reports it to fl_model_info
-        nwg = std::max(nwg, cu_count());
+        nwg = std::max(nwg, device_cu_count());
         if (sp.part) { FL_HIP(hipStreamSynchronize(stream)); (void)hipFree(sp.part); }
         sp = SkSpace{};
         FL_HIP(hipMalloc(&sp.part, (size_t)nwg * 2 * P_BM * P_BN * sizeof(float)));
@@ -553,15 +552,6 @@ static int streamk_space(hipStream_t stream, int nwg, StreamK *sk) {
     }
     *sk = StreamK{sp.part};
     return FL_OK;
-}
-
-static int cu_count() {
-    static int cached[64] = {0};
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cached[dev]) cached[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-    return cached[dev];
 }
 
 // does the four-wave form take this launch (the rule of the comment in launch_gemm_8p)?
@@ -594,7 +584,7 @@ int launch_gemm_8p(Launcher &L, const void *W, const void *x, const float *bias,
         if (units >= (int64_t)1 << 30) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gemm_8p: stream-K line too long");
         // pieces aligned with the tiles keep the workgroups that share a W or X panel in lock step (its L2 hits): split every
         // tile into the same number of pieces, at most eight, while the grid fits the chip
-        const int64_t nt = (int64_t)tiles_m * tiles_n, cus = cu_count();
+        const int64_t nt = (int64_t)tiles_m * tiles_n, cus = device_cu_count();
         const int sk_minsteps = std::max(2, tune(TK_SK_MINSTEPS));   // K steps per piece, at least (Qwen2-7B 4k QKV tail: piece launch + fix-up 58.2 us at 4, 53.8 at 8, 53.0 at 12)
         const int64_t split = std::max<int64_t>(1, std::min<int64_t>({(int64_t)8, cus / std::max<int64_t>(1, nt), (K / P_BK) / sk_minsteps}));
         const int nwg = (int)std::max<int64_t>(1, std::min<int64_t>(nt * split, units / 2));

@@ -34,16 +34,18 @@
 // the KV cache slot `len`.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <type_traits>
 
 #include "comm_ll.h"
+#include "gemv_geometry.h"
+#include "gemv_parts.h"
 #include "kernels.h"
 
 namespace fl {
 
 constexpr int kGemvMaxThreads = 768;     // 12 waves: 170 VGPRs per lane available
-constexpr int kMaxDevices = 64;
 
 template <typename WT> struct RawChunk { uint4v v[sizeof(WT) == 2 ? 1 : 2]; };
 
@@ -87,7 +89,6 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
     XT *xs = reinterpret_cast<XT *>(lds_raw);
     const WT *__restrict__ W = reinterpret_cast<const WT *>(a.W);
     const int N = a.N, K = a.K;
-    constexpr int epi = EPI;                         // compile-time: the epilogue's operands do not occupy registers of the others
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nthr = blockDim.x, nwv = nthr >> 6;
     const int nchunk = K >> 3;                       // 8-element chunks; K % 8 == 0
@@ -95,11 +96,7 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
     const int ngroups = (N + R - 1) / R;
     const int gw = blockIdx.x * nwv + wave, nw = gridDim.x * nwv;
 
-    auto row_of = [&](int g, int r) -> int {
-        if (epi == EPI_GATEUP) { int q = g * (R / 2) + (r >> 1); return (q >> 4) * 32 + (q & 15) + ((r & 1) << 4); }
-        if (epi == EPI_QKV_ROPE) { int q = g * (R / 2) + (r >> 1); int hd = q / half, j = q - hd * half; return hd * a.d + j + (r & 1) * half; }
-        return g * R + r;
-    };
+    auto row_of = [&](int g, int r) -> int { return gemv_row_of<EPI, R>(g, r, a.d, half); };
     typedef RawChunk<WT> Buf[R][U];
     // first K block of this wave's first row group: requested before x is staged, so HBM is busy
     // during the prologue
@@ -146,6 +143,9 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
     };
     float inv_m = 1.0f;
     if constexpr (PRO == PRO_NORM) {
+        // This is gemv_norm_prologue (gemv_parts.h) written out, plus the sliced delta: called through the header, the bf16 SMALL
+        // forms (the default QKV / o_proj / down_proj launches) took 98-100 VGPRs instead of 94-96 -- 4 waves per SIMD instead of
+        // 5 -- and three fp32 forms spilled 12-16 bytes more (profiles/gemv_parts/README.md)
         constexpr int NCH = SMALL ? 1 : 3;           // nthr * NCH * 8 >= K (host-checked)
         float v[NCH][8], wn[NCH][8], dl[NCH][8];
         const WT *erow = nullptr;
@@ -236,31 +236,14 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
 #pragma unroll
     for (int r = 0; r < R; r++) acc[r] = 0.f;
 
-    // RoPE epilogue operands are requested up front (position from the step state, then this wave's cos/sin
-    // pairs) so that their two dependent round trips overlap the weight stream instead of trailing it
-    uint32_t rope_p = 0, rope_slot = 0;
-    float rope_c[R / 2], rope_s[R / 2], rope_b0[R / 2], rope_b1[R / 2];            // (bias of the pair's two rows: Qwen2)
-    auto rope_prefetch = [&](int g) {
-#pragma unroll
-        for (int r = 0; r < R; r += 2) {
-            const int q = g * (R / 2) + (r >> 1);
-            const int hd = q / half, j = q - hd * half;
-            const bool rot = hd < a.H + a.Hkv;
-            rope_c[r >> 1] = rot ? a.cos_tab[(size_t)rope_p * half + j] : 1.f;
-            rope_s[r >> 1] = rot ? a.sin_tab[(size_t)rope_p * half + j] : 0.f;
-            const int r0w = row_of(g, r), r1w = row_of(g, r + 1);
-            rope_b0[r >> 1] = a.bias && r1w < N ? a.bias[r0w] : 0.f;                // requested with the tables: in the epilogue it was a
-            rope_b1[r >> 1] = a.bias && r1w < N ? a.bias[r1w] : 0.f;                //  round trip at the very end of the launch
-        }
-    };
-    if (epi == EPI_QKV_ROPE) {
-        const uint32_t pos = a.st->pos;
-        rope_slot = a.st->len;
-        rope_p = pos < (uint32_t)a.max_pos ? pos : (uint32_t)a.max_pos - 1;
-        if (gw < ngroups) rope_prefetch(gw);
+    // RoPE epilogue operands are requested up front (gemv_parts.h), and again whenever a row group starts
+    GemvRope<XT, R> rope(a, a.bias, N);
+    if constexpr (EPI == EPI_QKV_ROPE) {
+        rope.begin(a.st, a.max_pos);
+        if (gw < ngroups) rope.prefetch(gw);
     }
 
-    float best_v = -INFINITY; int best_i = -1;                                      // running ArgMax of this wave's rows (lane 0)
+    GemvBest best;                                                                  // running ArgMax of this wave's rows (lane 0)
     auto finish_group = [&](int g) {
         float sum[R];
 #pragma unroll
@@ -270,69 +253,14 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
             return;
         }
         if (lane != 0) return;
-        if (epi == EPI_GATEUP) {
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int q = g * (R / 2) + (r >> 1);
-                if (row_of(g, r + 1) < N) {
-                    const float gt = sum[r], up = sum[r + 1];
-                    const float act = gt / (1.0f + expf(-gt)) * up;          // candle silu(g) * u
-                    elem<XT>::st(reinterpret_cast<XT *>(a.out) + q, act);
-                }
-            }
-        } else if (epi == EPI_QKV_ROPE) {
-            const uint32_t slot = rope_slot;
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int r1w = row_of(g, r + 1);
-                if (r1w >= N) continue;
-                const int q = g * (R / 2) + (r >> 1);
-                const int hd = q / half, j = q - hd * half;
-                float x0 = sum[r], x1 = sum[r + 1];
-                if (a.bias) { x0 += rope_b0[r >> 1]; x1 += rope_b1[r >> 1]; }
-                XT *dst;
-                size_t stride = 1;                                        // element stride between j and j+1
-                if (hd < a.H + a.Hkv) {                                   // rotate-half RoPE (App. A.4)
-                    const float c = rope_c[r >> 1], s = rope_s[r >> 1];
-                    float t0, t1;
-                    rope_rotate(x0, x1, c, s, t0, t1);
-                    x0 = t0; x1 = t1;
-                    dst = hd < a.H ? reinterpret_cast<XT *>(a.q_out) + (size_t)hd * a.d
-                                   : reinterpret_cast<XT *>(a.k_cache) + ((size_t)(hd - a.H) * a.max_seq + slot) * a.d;
-                } else if (a.v_ld > 0) {                                  // transposed value cache [Hkv][d][v_ld]
-                    dst = reinterpret_cast<XT *>(a.v_cache) + (size_t)(hd - a.H - a.Hkv) * a.d * a.v_ld + slot;
-                    stride = (size_t)a.v_ld;
-                } else {
-                    dst = reinterpret_cast<XT *>(a.v_cache) + ((size_t)(hd - a.H - a.Hkv) * a.max_seq + slot) * a.d;
-                }
-                elem<XT>::st(dst + (size_t)j * stride, x0);
-                elem<XT>::st(dst + (size_t)(j + half) * stride, x1);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int row = row_of(g, r);
-                if (row < N) {
-                    const float y = sum[r] + (a.bias ? a.bias[row] : 0.f);
-                    reinterpret_cast<float *>(a.out)[row] = y;
-                    if (a.amax && (best_i < 0 || y > best_v || (y == best_v && row > best_i))) { best_v = y; best_i = row; }   // (lane 0; as argmax_last)
-                }
-            }
-        }
+        if constexpr (EPI == EPI_GATEUP) gemv_store_gateup<XT, R>(reinterpret_cast<XT *>(a.out), N, g, sum);
+        else if constexpr (EPI == EPI_QKV_ROPE) rope.store(g, sum);
+        else gemv_store_f32<R>(reinterpret_cast<float *>(a.out), a.bias, N, g, sum, a.amax != nullptr, best);
     };
-    // the workgroup's ArgMax candidate (EPI_F32 with GemvArgs::amax): lane 0 of every wave holds the best of its rows
+    // the workgroup's ArgMax candidate (EPI_F32 with GemvArgs::amax)
     auto leave_candidate = [&]() {
         if constexpr (EPI != EPI_F32 || FUSE_AR) return;
-        if (!a.amax) return;                                                          // (kernel argument: uniform)
-        if (lane == 0) { cv[wave] = best_v; ci[wave] = best_i; }
-        __syncthreads();
-        if (tid == 0) {
-            float bv = cv[0]; int bi = ci[0];
-            for (int w = 1; w < nwv; w++)
-                if (ci[w] >= 0 && (bi < 0 || cv[w] > bv || (cv[w] == bv && ci[w] > bi))) { bv = cv[w]; bi = ci[w]; }
-            a.amax[1 + blockIdx.x] = ArgmaxCand{bv, bi};
-            if (blockIdx.x == 0) a.amax[0] = ArgmaxCand{0.f, (int)gridDim.x};
-        }
+        if (a.amax) gemv_leave_candidate(a.amax, cv, ci, 0, nwv, best);              // (kernel argument: uniform)
     };
     auto fma_block = [&](const Buf &buf, int c0) {
 #pragma unroll
@@ -377,7 +305,9 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
         int cg = gw_u, cb = 0;                                                      // consume stream
         const bool ragged = nchunk % (64 * U) != 0;
         auto consume = [&](const Buf &buf) {
-            if (epi == EPI_QKV_ROPE && cb == 0 && cg != gw_u) rope_prefetch(cg);
+            if constexpr (EPI == EPI_QKV_ROPE) {
+                if (cb == 0 && cg != gw_u) rope.prefetch(cg);
+            }
             const int c0 = lane + 64 * U * cb;
             if (ragged && cb == nb - 1) {                                           // wave-uniform: the partial last block of K
 #pragma unroll
@@ -413,7 +343,9 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
     }
 #pragma nounroll
     for (int g = gw; g < ngroups; g += nw) {
-        if (epi == EPI_QKV_ROPE && g != gw) rope_prefetch(g);
+        if constexpr (EPI == EPI_QKV_ROPE) {
+            if (g != gw) rope.prefetch(g);
+        }
         const WT *wp[R];
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -512,45 +444,9 @@ bool gemv_supported(int dtype, int64_t N, int64_t K) {
 // smallest workgroup is 256 threads
 bool gemv_norm_supported(int dtype, int64_t N, int64_t K) { return gemv_supported(dtype, N, K) && K <= 6144; }
 
-static int cu_count() {                      // of the current device (the shards of a group may sit on different ones)
-    static std::atomic<int> cached[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 256;
-    int n = cached[dev].load();
-    if (!n) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-        cached[dev].store(n);
-    }
-    return n;
-}
-
-// Pick (workgroups, waves per workgroup): equal row groups per wave, everything resident at once
-// (<= 12 waves per CU at 170 VGPRs), as many waves per CU as that allows.
-static void pick_geometry(int64_t ngroups, size_t lds_bytes, int *blocks_out, int *waves_out) {
-    const int cus = cu_count();
-    int fb = g_force_blocks.load(), fw = g_force_waves.load();
-    if (fb > 0 && fw > 0) { *blocks_out = fb; *waves_out = fw; return; }
-    if (ngroups <= (int64_t)cus * 4) {                 // small matrix: 4-wave workgroups, one group per wave
-        *waves_out = 4; *blocks_out = (int)((ngroups + 3) / 4);
-        return;
-    }
-    static const int kWaves[] = {12, 11, 10, 9, 8, 7, 6, 5, 4};
-    double best = -1.0; int bb = cus, bw = 8;
-    for (int mult = 1; mult <= 2; mult++) {
-        for (int w : kWaves) {
-            if (mult * w > 12) continue;
-            if ((size_t)mult * lds_bytes > 150 * 1024) continue;
-            const int64_t wt = (int64_t)cus * mult * w;
-            const int64_t per = (ngroups + wt - 1) / wt;
-            const double eff = (double)ngroups / (double)(per * wt);
-            // prefer balance, then more waves per CU (latency hiding), then fewer workgroups
-            const double score = eff + 1e-3 * (mult * w) / 12.0 - 1e-4 * mult;
-            if (score > best) { best = score; bb = cus * mult; bw = w; }
-        }
-    }
-    *blocks_out = bb; *waves_out = bw;
+// the grid of an N x K launch with R rows per group (gemv_geometry.h), under the fl_tune grid
+static GemvGeometry tuned_geometry(int64_t N, int64_t K, int R, size_t es) {
+    return gemv_geometry((N + R - 1) / R, ((size_t)K * es + 15) & ~(size_t)15, device_cu_count(), g_force_blocks.load(), g_force_waves.load());
 }
 
 template <typename WT, typename XT, int R, int U, int PRO, int MAXT, bool SMALL, int EPI, bool FUSE_AR = false>
@@ -577,8 +473,8 @@ static int launch_gemv_t(Launcher &L, const GemvArgs &a) {
     const int64_t N = a.N, K = a.K;
     size_t lds = ((size_t)K * sizeof(XT) + 15) & ~(size_t)15;
     const int64_t ngroups = (N + R - 1) / R;
-    int blocks = 1, waves = 4;
-    pick_geometry(ngroups, lds, &blocks, &waves);
+    const GemvGeometry geo = tuned_geometry(N, K, R, sizeof(XT));
+    int blocks = geo.blocks, waves = geo.waves;
     if (a.amax && blocks + 1 > kMaxArgmaxCand) {           // (callers ask gemv_leaves_candidates first; a tuned grid may still get here)
         FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: %d workgroups exceed the ArgMax candidate buffer (gemv_leaves_candidates not consulted)", blocks);
     }
@@ -587,7 +483,9 @@ static int launch_gemv_t(Launcher &L, const GemvArgs &a) {
     const int allow_small = tune(TK_GEMV_SMALL);
     const bool small = allow_small && sizeof(WT) == 2 && ngroups <= (int64_t)blocks * waves && (K >> 3) % (64 * U) == 0 &&
                        (K >> 3) <= 2 * 64 * U && (PRO != PRO_NORM || (int64_t)waves * 64 * 8 >= K);
-    if (small) return launch_gemv_k<WT, XT, R, U, PRO, 768, true>(L, a, blocks, waves, lds);
+    if constexpr (sizeof(WT) == 2) {                        // (fp32 weights never take the SMALL form: it is not instantiated for them)
+        if (small) return launch_gemv_k<WT, XT, R, U, PRO, 768, true>(L, a, blocks, waves, lds);
+    }
     return launch_gemv_k<WT, XT, R, U, PRO, 768, false>(L, a, blocks, waves, lds);
 }
 
@@ -621,19 +519,14 @@ static int launch_gemv_ru(Launcher &L, const GemvArgs &a) {
 bool gemv_leaves_candidates(int dtype, const GemvArgs &a) {
     int R = tune(TK_GEMV_R);
     if (R != 4) R = 2;                                       // (the instantiations launch_gemv_ru picks from)
-    const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
-    int blocks = 1, waves = 4;
-    pick_geometry(((int64_t)a.N + R - 1) / R, ((size_t)a.K * es + 15) & ~(size_t)15, &blocks, &waves);
-    return blocks + 1 <= kMaxArgmaxCand;
+    return tuned_geometry(a.N, a.K, R, dtype == FL_DTYPE_BF16 ? 2 : 4).blocks + 1 <= kMaxArgmaxCand;
 }
 
 int64_t gemv_owner_chunk(int dtype, int64_t N, int64_t K) {
     int R = tune(TK_GEMV_R);
     if (R != 4) R = 2;
     const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
-    int blocks = 1, waves = 4;
-    pick_geometry((N + R - 1) / R, ((size_t)K * es + 15) & ~(size_t)15, &blocks, &waves);
-    if (waves < 4) waves = 4;
+    const int waves = std::max(4, tuned_geometry(N, K, R, es).waves);
     return (int64_t)waves * R * K * (int64_t)es;
 }
 

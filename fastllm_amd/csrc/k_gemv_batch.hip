@@ -20,10 +20,14 @@
 // sequence's current token), x' = bf16(v * w) staged, 1/rms applied to the accumulator (as k_gemv.hip).
 // Epilogues: EPI_F32 (+bias), EPI_GATEUP (silu(gate)*up), EPI_QKV_ROPE with each sequence's own RoPE
 // position and KV slot from its device step state, written into its own cache.
+// The row map of the paired layouts, silu(gate)*up and the RoPE pair's way into the q buffer / a sequence's caches are those of
+// gemv_parts.h, shared with the single-sequence streams (the MFMA kernel writes its QKV row map and store out: see there); the
+// B-row prologue is this file's own.
 #include <stdlib.h>
 
 #include <atomic>
 
+#include "gemv_parts.h"
 #include "kernels.h"
 
 namespace fl {
@@ -38,7 +42,7 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_kernel(const GemvBatchAr
     bf16_t *xs = reinterpret_cast<bf16_t *>(lds_raw);                 // [NB][Ks]
     const bf16_t *__restrict__ W = reinterpret_cast<const bf16_t *>(a.W);
     const int N = a.N, K = a.K, B = a.B;
-    constexpr int epi = EPI;                          // compile-time, like gemv_kernel's: the other epilogues' operands cost no registers
+    constexpr int epi = EPI;                          // compile-time: the other epilogues' operands cost no registers (gemv_parts.h)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int nthr = kBThreads, nwv = kBThreads / 64;
     const int ks = blockIdx.y;
@@ -52,11 +56,7 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_kernel(const GemvBatchAr
     const int ngroups = (N + kBR - 1) / kBR;
     const int nw = gridDim.x * nwv;
 
-    auto row_of = [&](int g, int r) -> int {
-        if (epi == EPI_GATEUP) { int q = g; return (q >> 4) * 32 + (q & 15) + (r << 4); }
-        if (epi == EPI_QKV_ROPE) { int q = g; int hd = q / half, j = q - hd * half; return hd * a.d + j + r * half; }
-        return g * kBR + r;
-    };
+    auto row_of = [&](int g, int r) -> int { return gemv_row_of<EPI, kBR>(g, r, a.d, half); };
     typedef uint4v Buf[kBR][kBU];
     // The wave's (row group, K block) items form ONE stream, requested a block ahead into two register buffers -- the form of the
     // single-sequence kernel (k_gemv.hip, round 2), ported in round 3: while a block is multiplied the next one is in flight, also
@@ -191,13 +191,11 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_kernel(const GemvBatchAr
         if (lane != 0) return;
         const int r0w = row_of(g, 0), r1w = row_of(g, 1);
         if (epi == EPI_GATEUP) {
-            if (r1w >= N) return;
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 if (b >= B) break;
-                const float gt = sum[0][b], up = sum[1][b];
-                const float act = gt / (1.0f + expf(-gt)) * up;              // candle silu(g) * u
-                elem<bf16_t>::st(reinterpret_cast<bf16_t *>(a.out) + (size_t)b * (N / 2) + g, act);
+                const float pair[kBR] = {sum[0][b], sum[1][b]};
+                gemv_store_gateup<bf16_t, kBR>(reinterpret_cast<bf16_t *>(a.out) + (size_t)b * (N / 2), N, g, pair);
             }
         } else if (epi == EPI_QKV_ROPE) {
             if (r1w >= N) return;
@@ -205,26 +203,18 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_kernel(const GemvBatchAr
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 if (b >= B) break;
-                const SeqRef &sq = a.seqs[b];
+                const SeqRef &sq = a.seqs[b];                                 // each sequence's own position, slot and caches
                 float x0 = sum[0][b], x1 = sum[1][b];
                 if (a.bias) { x0 += a.bias[r0w]; x1 += a.bias[r1w]; }
                 const uint32_t pos = sq.st->pos, slot = sq.st->len;
-                bf16_t *dst;
-                size_t stride = 1;
-                if (hd < a.H + a.Hkv) {                                       // rotate-half RoPE (App. A.4)
+                if (qkv_rotates(hd, a.H, a.Hkv)) {                             // (the tables are read only where they are used)
                     const uint32_t p = pos < (uint32_t)a.max_pos ? pos : (uint32_t)a.max_pos - 1;
                     const float c = a.cos_tab[(size_t)p * half + j], s = a.sin_tab[(size_t)p * half + j];
                     float t0, t1;
                     rope_rotate(x0, x1, c, s, t0, t1);
                     x0 = t0; x1 = t1;
-                    dst = hd < a.H ? reinterpret_cast<bf16_t *>(a.q_out) + ((size_t)b * a.H + hd) * a.d
-                                   : reinterpret_cast<bf16_t *>(sq.k) + a.kv_layer_off * sq.seq_alloc + ((size_t)(hd - a.H) * sq.seq_alloc + slot) * a.d;
-                } else {                                                      // transposed value cache [Hkv][d][seq_alloc]
-                    dst = reinterpret_cast<bf16_t *>(sq.v) + a.kv_layer_off * sq.seq_alloc + (size_t)(hd - a.H - a.Hkv) * a.d * sq.seq_alloc + slot;
-                    stride = (size_t)sq.seq_alloc;
                 }
-                elem<bf16_t>::st(dst + (size_t)j * stride, x0);
-                elem<bf16_t>::st(dst + (size_t)(j + half) * stride, x1);
+                QkvDest<bf16_t>::of_seq(a, sq, b).store_pair(hd, j, half, slot, x0, x1);
             }
         } else {
             float *out = reinterpret_cast<float *>(a.out) + (size_t)ks * B * N;
@@ -306,7 +296,7 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_mfma_kernel(const GemvBa
     __shared__ float inv_lds[8];
     const bf16_t *__restrict__ W = reinterpret_cast<const bf16_t *>(a.W);
     const int N = a.N, K = a.K, B = a.B;
-    constexpr int epi = EPI;                          // compile-time, like gemv_kernel's: the other epilogues' operands cost no registers
+    constexpr int epi = EPI;                          // compile-time: the other epilogues' operands cost no registers (gemv_parts.h)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int nthr = kBThreads, nwv = kBThreads / 64;
     const int ks = blockIdx.y;
@@ -401,6 +391,9 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_mfma_kernel(const GemvBa
     const int s0 = min(nsteps, wave * spw), s1 = min(nsteps, s0 + spw);
     const bf16_t *xb = xs + (size_t)(m & 7) * XS + kg * 8;
     float4v ca = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f};
+    // first rows of a unit's two tiles: the row map of gemv_parts.h at channel 16 * unit (half % 16 == 0, host-checked as d % 32),
+    // and the pair's way out below, are written out here: through gemv_row_of / QkvDest the QKV forms of this kernel took 1-4
+    // VGPRs more, and the MU = 2 one fell from 7 to 6 waves per SIMD
     auto unit_rows = [&](int unit, int &ra0, int &rb0) {
         if (epi == EPI_QKV_ROPE) {
             const int upr = half / 16;                                 // units per head
@@ -435,8 +428,7 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_mfma_kernel(const GemvBa
         if (tile == 0 && n < B && rb0 + r < N) {
             float x0 = fin[n * 16 + r], x1 = fin[(16 + n) * 16 + r];
             if (epi == EPI_GATEUP) {
-                const float act = x0 / (1.0f + expf(-x0)) * x1;              // candle silu(g) * u
-                elem<bf16_t>::st(reinterpret_cast<bf16_t *>(a.out) + (size_t)n * (N / 2) + unit * 16 + r, act);
+                elem<bf16_t>::st(reinterpret_cast<bf16_t *>(a.out) + (size_t)n * (N / 2) + unit * 16 + r, gemv_silu_gate(x0, x1));
             } else {
                 const SeqRef &sq = a.seqs[n];
                 const int hd = ra0 / a.d, j = ra0 - hd * a.d + r;
@@ -566,16 +558,6 @@ __global__ __launch_bounds__(kBThreads) void gemv_batch_mfma_kernel(const GemvBa
     }
 }
 
-static int cu_count_b() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0; hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 // K slices: enough that B vectors of one slice fit in LDS (bf16), and -- for the fp32 epilogue, whose
 // slabs the consumer sums anyway -- enough that a short matrix (N / 32 units < CUs) still covers the chip
 int gemv_batch_ksplit(int B, int64_t K, int64_t N, int epi) {
@@ -590,7 +572,7 @@ int gemv_batch_ksplit(int B, int64_t K, int64_t N, int epi) {
     }
     if (epi == EPI_F32 && B >= 3 && N > 0) {
         const int64_t units = (N + 31) / 32;
-        while (units * nks < cu_count_b() && nks < 4 && (K / 8 + nks) / (nks + 1) >= 128) nks++;
+        while (units * nks < device_cu_count() && nks < 4 && (K / 8 + nks) / (nks + 1) >= 128) nks++;
     }
     return nks;
 }
@@ -603,7 +585,7 @@ static int launch_gemv_batch_u(Launcher &L, const GemvBatchArgs &a) {
     FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
     const int64_t ngroups = (a.N + kBR - 1) / kBR;
     const int nwv = kBThreads / 64;
-    int blocks = (int)std::min<int64_t>((ngroups + nwv - 1) / nwv, std::max(1, cu_count_b() / a.nks));
+    int blocks = (int)std::min<int64_t>((ngroups + nwv - 1) / nwv, std::max(1, device_cu_count() / a.nks));
     char tag[32];
     snprintf(tag, sizeof tag, "b%d:%dx%d%s%s", a.B, a.N, a.K, PRO == PRO_NORM ? ",norm" : "", a.epi == EPI_GATEUP ? ",glu" : (a.epi == EPI_QKV_ROPE ? ",rope" : ""));
     Launcher LL = L; LL.tag = tag;
@@ -635,7 +617,7 @@ static int launch_gemv_batch_mfma_e(Launcher &L, const GemvBatchArgs &a) {
     const size_t lds = (size_t)8 * (per * 8 + 8) * 2 + (size_t)(8 * 2 * 256 + 2 * 256) * 4 + (MODE >= 2 ? 8 * 8192 : 0);
     FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
     const int64_t nunits = (a.N + 31) / 32;
-    const int blocks = (int)std::min<int64_t>(nunits, std::max(1, cu_count_b() / a.nks));
+    const int blocks = (int)std::min<int64_t>(nunits, std::max(1, device_cu_count() / a.nks));
     char tag[32];
     snprintf(tag, sizeof tag, "b%dm:%dx%d%s%s", a.B, a.N, a.K, PRO == PRO_NORM ? ",norm" : "", a.epi == EPI_GATEUP ? ",glu" : (a.epi == EPI_QKV_ROPE ? ",rope" : ""));
     Launcher LL = L; LL.tag = tag;

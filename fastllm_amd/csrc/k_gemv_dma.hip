@@ -229,14 +229,6 @@ __global__ __launch_bounds__(D_THREADS) void gemv_dma_kernel(const GemvBatchArgs
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int cu_count_d() {
-    int dev = 0; hipDeviceProp_t p;
-    static int cached[64];
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cached[dev]) cached[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-    return cached[dev];
-}
-
 // K tiles per wave for a slice count; 0 = the shape does not fit the kernel
 static int dma_kt(int64_t K) {                                  // k per ring stage: 128 (256-byte row segments) where K allows it
     const int want = tune(TK_DMA_KT);
@@ -266,7 +258,7 @@ int gemv_dma_ksplit(int64_t K, int64_t N, int epi) {
     while (nks < 16 && dma_tiles_per_wave(K, nks) == 0) nks++;
     if (epi == EPI_F32 && N > 0) {
         const int64_t units = (N + 15) / 16;
-        while (units * nks < cu_count_d() && nks < 4 && (K / 64) / (nks + 1) >= 16) nks++;
+        while (units * nks < device_cu_count() && nks < 4 && (K / 64) / (nks + 1) >= 16) nks++;
     }
     return nks;
 }
@@ -277,7 +269,7 @@ static int launch_dma_e(Launcher &L, const GemvBatchArgs &a) {
     const size_t lds = (size_t)D_RING_BYTES + (size_t)D_RED_FLOATS * 4 * RB;
     FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
     const int64_t nunits = EPI == EPI_F32 ? (a.N + 15) / 16 : a.N / 16;
-    const int cus = cu_count_d();
+    const int cus = device_cu_count();
     // one workgroup per CU; with K slices the slices of a unit run side by side
     const int blocks = (int)std::min<int64_t>(nunits, std::max(1, cus / a.nks));
     char tag[32];

@@ -4,8 +4,8 @@
 // integer with absmax(W[n,:]) / 2^e <= 448 (an all-zero row: s = 1).  The division is by a power of two, so q is defined bit
 // for bit, and s * q is exactly representable in bf16: an FP8 model is the bf16 model whose weights are W'.
 //
-// The kernel is the sibling of k_gemv.hip's bf16 stream (same GemvArgs, same prologues and epilogues, its own file so that the
-// bf16 / fp32 instantiations stay what they are).  What differs:
+// The kernel is the sibling of k_gemv.hip's bf16 stream: same GemvArgs, and the row map, norm prologue and epilogues are the ones
+// of gemv_parts.h; the stream is its own.  What differs:
 //   - a lane's 16-byte load is 16 weights, so a wave instruction (1 KiB, non-temporal, straight to VGPRs) covers 1024 columns of
 //     a row and a row is half as many instructions long; the wave's (row group, K block) items form one stream, a block
 //     (U x R KiB) ahead in a second register buffer, every load unconditional (counted vmcnt waits), as in the bf16 PIPE form.
@@ -20,6 +20,8 @@
 // K must be a multiple of 16 (a lane's load); fl_model_create_opts refuses other shapes in this mode.
 #include <stdlib.h>
 
+#include "gemv_geometry.h"
+#include "gemv_parts.h"
 #include "kernels.h"
 
 namespace fl {
@@ -42,7 +44,6 @@ __global__ __launch_bounds__(kW8MaxThreads) void gemv_w8_kernel(const GemvArgs a
     bf16_t *xs = reinterpret_cast<bf16_t *>(lds_raw);
     const uint8_t *__restrict__ W = reinterpret_cast<const uint8_t *>(a.W);
     const int N = a.N, K = a.K;
-    constexpr int epi = EPI;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nthr = blockDim.x, nwv = nthr >> 6;
     const int nchunk = K >> 4;                       // 16-weight chunks (a lane's load); K % 16 == 0
@@ -53,11 +54,7 @@ __global__ __launch_bounds__(kW8MaxThreads) void gemv_w8_kernel(const GemvArgs a
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int gw = blockIdx.x * nwv + wave_u, nw = gridDim.x * nwv;
 
-    auto row_of = [&](int g, int r) -> int {
-        if (epi == EPI_GATEUP) { int q = g * (R / 2) + (r >> 1); return (q >> 4) * 32 + (q & 15) + ((r & 1) << 4); }
-        if (epi == EPI_QKV_ROPE) { int q = g * (R / 2) + (r >> 1); int hd = q / half, j = q - hd * half; return hd * a.d + j + (r & 1) * half; }
-        return g * R + r;
-    };
+    auto row_of = [&](int g, int r) -> int { return gemv_row_of<EPI, R>(g, r, a.d, half); };
     auto xs_slot = [&](int c8) -> int { return ((c8 & 1) ? hoff : 0) + (c8 >> 1) * 8; };
 
     typedef uint4v Buf[R][U];
@@ -81,42 +78,8 @@ __global__ __launch_bounds__(kW8MaxThreads) void gemv_w8_kernel(const GemvArgs a
 
     float inv_m = 1.0f;
     if constexpr (PRO == PRO_NORM) {
-        constexpr int NCH = 3;                       // nthr * NCH * 8 >= K (host-checked)
-        float v[NCH][8], wn[NCH][8], dl[NCH][8];
-        const bf16_t *erow = nullptr;
-        if (a.embed) erow = reinterpret_cast<const bf16_t *>(a.embed) + (size_t)a.st->token * K;
-#pragma unroll
-        for (int i = 0; i < NCH; i++) {              // requests only: nothing here waits
-            const int c = tid + nthr * i;
-            if (c < nch8) {
-                if (erow) load8(erow + c * 8, v[i]); else load8(a.x_in + c * 8, v[i]);
-                load8(a.norm_w + c * 8, wn[i]);
-                if (a.delta) load8(a.delta + c * 8, dl[i]);
-            }
-        }
-        load_next(pre);                              // the weight stream starts behind the (short) activation loads
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; i++) {
-            const int c = tid + nthr * i;
-            if (c < nch8) {
-                if (a.delta) {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) v[i][j] += dl[i][j];
-                }
-                float o[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) { ss = fmaf(v[i][j], v[i][j], ss); o[j] = v[i][j] * wn[i][j]; }
-                store8(xs + xs_slot(c), o);
-                if (blockIdx.x == 0 && a.x_out) store8(a.x_out + c * 8, v[i]);
-            }
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) red[wave] = ss;
-        __syncthreads();
-        ss = 0.f;
-        for (int w = 0; w < nwv; w++) ss += red[w];
-        inv_m = 1.0f / sqrtf(ss / (float)K + a.eps);
+        // three chunks of 8 per thread (nthr * 3 * 8 >= K, host-checked); the weight stream starts behind the activation loads
+        inv_m = gemv_norm_prologue<3, bf16_t>(a, xs, red, xs_slot, [&]() { load_next(pre); });
     } else {
         const bf16_t *__restrict__ x = reinterpret_cast<const bf16_t *>(a.x);
         constexpr int NXR = 4;
@@ -143,105 +106,33 @@ __global__ __launch_bounds__(kW8MaxThreads) void gemv_w8_kernel(const GemvArgs a
     for (int r = 0; r < R; r++) acc[r] = 0.f;
 
     // operands of the epilogue, requested when a row group starts so that their round trips overlap the stream: the rows'
-    // scales, and for RoPE the position's cos / sin pairs and the bias of the pair's rows
-    uint32_t rope_p = 0, rope_slot = 0;
+    // scales, and for RoPE the position's cos / sin pairs and the bias of the pair's rows (gemv_parts.h)
     float wsc[R];
-    float rope_c[R / 2], rope_s[R / 2], rope_b0[R / 2], rope_b1[R / 2];
+    GemvRope<bf16_t, R> rope(a, a.bias, N);
     auto group_prefetch = [&](int g) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int row = row_of(g, r);
             wsc[r] = row < N ? wscale[row] : 0.f;
         }
-        if (epi == EPI_QKV_ROPE) {
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int q = g * (R / 2) + (r >> 1);
-                const int hd = q / half, j = q - hd * half;
-                const bool rot = hd < a.H + a.Hkv;
-                rope_c[r >> 1] = rot ? a.cos_tab[(size_t)rope_p * half + j] : 1.f;
-                rope_s[r >> 1] = rot ? a.sin_tab[(size_t)rope_p * half + j] : 0.f;
-                const int r0w = row_of(g, r), r1w = row_of(g, r + 1);
-                rope_b0[r >> 1] = a.bias && r1w < N ? a.bias[r0w] : 0.f;
-                rope_b1[r >> 1] = a.bias && r1w < N ? a.bias[r1w] : 0.f;
-            }
-        }
+        if constexpr (EPI == EPI_QKV_ROPE) rope.prefetch(g);
     };
-    if (epi == EPI_QKV_ROPE) {
-        const uint32_t pos = a.st->pos;
-        rope_slot = a.st->len;
-        rope_p = pos < (uint32_t)a.max_pos ? pos : (uint32_t)a.max_pos - 1;
-    }
+    if constexpr (EPI == EPI_QKV_ROPE) rope.begin(a.st, a.max_pos);
     if (gw < ngroups) group_prefetch(gw);
 
-    float best_v = -INFINITY; int best_i = -1;                                      // running ArgMax of this wave's rows (lane 0)
+    GemvBest best;                                                                  // running ArgMax of this wave's rows (lane 0)
     auto finish_group = [&](int g) {
         float sum[R];
 #pragma unroll
         for (int r = 0; r < R; r++) { sum[r] = wave_sum(acc[r]) * inv_m * wsc[r]; acc[r] = 0.f; }
         if (lane != 0) return;
-        if (epi == EPI_GATEUP) {
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int q = g * (R / 2) + (r >> 1);
-                if (row_of(g, r + 1) < N) {
-                    const float gt = sum[r], up = sum[r + 1];
-                    const float act = gt / (1.0f + expf(-gt)) * up;          // candle silu(g) * u
-                    elem<bf16_t>::st(reinterpret_cast<bf16_t *>(a.out) + q, act);
-                }
-            }
-        } else if (epi == EPI_QKV_ROPE) {
-            const uint32_t slot = rope_slot;
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const int r1w = row_of(g, r + 1);
-                if (r1w >= N) continue;
-                const int q = g * (R / 2) + (r >> 1);
-                const int hd = q / half, j = q - hd * half;
-                float x0 = sum[r], x1 = sum[r + 1];
-                if (a.bias) { x0 += rope_b0[r >> 1]; x1 += rope_b1[r >> 1]; }
-                bf16_t *dst;
-                size_t stride = 1;                                        // element stride between j and j+1
-                if (hd < a.H + a.Hkv) {                                   // rotate-half RoPE
-                    const float c = rope_c[r >> 1], s = rope_s[r >> 1];
-                    float t0, t1;
-                    rope_rotate(x0, x1, c, s, t0, t1);
-                    x0 = t0; x1 = t1;
-                    dst = hd < a.H ? reinterpret_cast<bf16_t *>(a.q_out) + (size_t)hd * a.d
-                                   : reinterpret_cast<bf16_t *>(a.k_cache) + ((size_t)(hd - a.H) * a.max_seq + slot) * a.d;
-                } else if (a.v_ld > 0) {                                  // transposed value cache [Hkv][d][v_ld]
-                    dst = reinterpret_cast<bf16_t *>(a.v_cache) + (size_t)(hd - a.H - a.Hkv) * a.d * a.v_ld + slot;
-                    stride = (size_t)a.v_ld;
-                } else {
-                    dst = reinterpret_cast<bf16_t *>(a.v_cache) + ((size_t)(hd - a.H - a.Hkv) * a.max_seq + slot) * a.d;
-                }
-                elem<bf16_t>::st(dst + (size_t)j * stride, x0);
-                elem<bf16_t>::st(dst + (size_t)(j + half) * stride, x1);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int row = row_of(g, r);
-                if (row < N) {
-                    const float y = sum[r] + (a.bias ? a.bias[row] : 0.f);
-                    reinterpret_cast<float *>(a.out)[row] = y;
-                    if (a.amax && (best_i < 0 || y > best_v || (y == best_v && row > best_i))) { best_v = y; best_i = row; }   // (lane 0; as argmax_last)
-                }
-            }
-        }
+        if constexpr (EPI == EPI_GATEUP) gemv_store_gateup<bf16_t, R>(reinterpret_cast<bf16_t *>(a.out), N, g, sum);
+        else if constexpr (EPI == EPI_QKV_ROPE) rope.store(g, sum);
+        else gemv_store_f32<R>(reinterpret_cast<float *>(a.out), a.bias, N, g, sum, a.amax != nullptr, best);
     };
     auto leave_candidate = [&]() {
         if constexpr (EPI != EPI_F32) return;
-        if (!a.amax) return;                                                          // (kernel argument: uniform)
-        if (lane == 0) { cv[wave] = best_v; ci[wave] = best_i; }
-        __syncthreads();
-        if (tid == 0) {
-            float bv = cv[0]; int bi = ci[0];
-            for (int w = 1; w < nwv; w++)
-                if (ci[w] >= 0 && (bi < 0 || cv[w] > bv || (cv[w] == bv && ci[w] > bi))) { bv = cv[w]; bi = ci[w]; }
-            a.amax[1 + blockIdx.x] = ArgmaxCand{bv, bi};
-            if (blockIdx.x == 0) a.amax[0] = ArgmaxCand{0.f, (int)gridDim.x};
-        }
+        if (a.amax) gemv_leave_candidate(a.amax, cv, ci, 0, nwv, best);              // (kernel argument: uniform)
     };
 
     // one chunk of every row against its x: eight converts and eight dots per row
@@ -308,41 +199,13 @@ bool gemv_w8_supported(int64_t N, int64_t K) {
 }
 bool gemv_w8_norm_supported(int64_t N, int64_t K) { return gemv_w8_supported(N, K) && K <= 6144; }
 
-static int w8_cu_count() {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess || p.multiProcessorCount <= 0) return 256;
-    return p.multiProcessorCount;
-}
-
-// (workgroups, waves per workgroup): equal row groups per wave, everything resident at once (<= 12 waves per CU), as many waves
-// per CU as that allows -- the rule of the bf16 stream; a row group is half the bytes, so the same rule leaves half the bytes
-// per wave and the short launches (QKV, o_proj) are one item per wave
-static void w8_geometry(int64_t ngroups, size_t lds_bytes, int *blocks_out, int *waves_out) {
-    static const int cus = w8_cu_count();
-    if (ngroups <= (int64_t)cus * 4) { *waves_out = 4; *blocks_out = (int)((ngroups + 3) / 4); return; }
-    double best = -1.0; int bb = cus, bw = 8;
-    for (int mult = 1; mult <= 2; mult++) {
-        for (int w = 12; w >= 4; w--) {
-            if (mult * w > 12 || (size_t)mult * lds_bytes > 150 * 1024) continue;
-            const int64_t wt = (int64_t)cus * mult * w;
-            const int64_t per = (ngroups + wt - 1) / wt;
-            const double eff = (double)ngroups / (double)(per * wt);
-            const double score = eff + 1e-3 * (mult * w) / 12.0 - 1e-4 * mult;
-            if (score > best) { best = score; bb = cus * mult; bw = w; }
-        }
-    }
-    *blocks_out = bb; *waves_out = bw;
-}
-
 constexpr int kW8R = 2;
 static size_t w8_lds(int64_t K) { return ((size_t)K * 2 + 15) & ~(size_t)15; }
+// the rule of the bf16 stream (gemv_geometry.h) without the fl_tune grid; a row group is half the bytes, so the same rule leaves
+// half the bytes per wave and the short launches (QKV, o_proj) are one item per wave
+static GemvGeometry w8_geometry(int64_t N, int64_t K) { return gemv_geometry((N + kW8R - 1) / kW8R, w8_lds(K), device_cu_count(), 0, 0); }
 
-bool gemv_w8_leaves_candidates(int64_t N, int64_t K) {
-    int blocks = 1, waves = 4;
-    w8_geometry((N + kW8R - 1) / kW8R, w8_lds(K), &blocks, &waves);
-    return blocks + 1 <= kMaxArgmaxCand;
-}
+bool gemv_w8_leaves_candidates(int64_t N, int64_t K) { return w8_geometry(N, K).blocks + 1 <= kMaxArgmaxCand; }
 
 template <int U, int PRO, int EPI>
 static int launch_gemv_w8_ke(Launcher &L, const GemvArgs &a, const float *wscale, int blocks, int waves, size_t lds) {
@@ -373,8 +236,9 @@ int launch_gemv_w8(Launcher &L, const GemvArgs &a, const float *wscale) {
     if (a.ll || a.delta_nslab != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv_w8: no fused all-reduce, no sliced delta");
     if (a.epi == EPI_QKV_ROPE && (a.d <= 0 || a.d % 2 || a.N != (a.H + 2 * a.Hkv) * a.d)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad qkv shape");
     const size_t lds = w8_lds(a.K);
-    int blocks = 1, waves = 4;
-    w8_geometry(((int64_t)a.N + kW8R - 1) / kW8R, lds, &blocks, &waves);
+    const GemvGeometry geo = w8_geometry(a.N, a.K);
+    const int blocks = geo.blocks;
+    int waves = geo.waves;
     if (a.amax && blocks + 1 > kMaxArgmaxCand) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv_w8: %d workgroups exceed the ArgMax candidate buffer", blocks);
     if (a.pro == PRO_NORM && (int64_t)waves * 64 * 3 * 8 < a.K) waves = (int)((a.K + 64 * 3 * 8 - 1) / (64 * 3 * 8));   // staging capacity
     // 1-KiB wave instructions per row, and chunks per block U in {4, 2, 1}: the one that pads the row's instruction count

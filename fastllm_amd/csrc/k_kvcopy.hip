@@ -90,15 +90,6 @@ __global__ __launch_bounds__(kKvCopyThreads) void kv_copy_kernel(KvCopyDev a, Kv
     }
 }
 
-static int kv_cu_count() {
-    static int cached[64] = {};
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cached[dev]) cached[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-    return cached[dev];
-}
-
 int kv_copy_check(const KvCopyJob &j) {
     if (j.rows < 0 || j.width < 0 || (j.width & 1)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "kv copy: rows and width must be >= 0 and width a multiple of 2 (got %lld rows of %lld bytes)", (long long)j.rows, (long long)j.width);
     if (j.width > (int64_t)0xfffffff0u) FL_FAIL(FL_ERR_BAD_ARGUMENT, "kv copy: a row of %lld bytes is too long", (long long)j.width);
@@ -132,7 +123,7 @@ int launch_kv_copy(Launcher &L, const KvCopyJob &ja, const KvCopyJob &jb) {
     const unsigned long long total = a.chunks + b.chunks;
     if (total == 0) return FL_OK;
     const unsigned long long per_pass = (unsigned long long)kKvCopyThreads * kKvCopyUnroll;
-    const unsigned grid = (unsigned)std::min<unsigned long long>((total + per_pass - 1) / per_pass, (unsigned long long)kv_cu_count() * kKvCopyBlocksPerCu);
+    const unsigned grid = (unsigned)std::min<unsigned long long>((total + per_pass - 1) / per_pass, (unsigned long long)device_cu_count() * kKvCopyBlocksPerCu);
     const double bytes = 2.0 * ((double)ja.rows * (double)ja.width + (double)jb.rows * (double)jb.width);     // read + write
     // 32-bit chunk numbers while a whole extra pass beyond `total` still fits (the loop's i + u * stride)
     if (total + (unsigned long long)grid * per_pass < 0xffffffffull)

@@ -48,6 +48,8 @@ struct Launcher {
     }
 };
 
+int device_cu_count();   // CUs of the current device, cached per device (model.hip); 256 where the runtime does not tell
+
 enum { EPI_F32 = 0, EPI_GATEUP = 1, EPI_QKV_ROPE = 2, EPI_RESID = 3 };
 // EPI_RESID (256x256 prefill GEMM only): the o_proj / down_proj epilogue takes over the residual add and the next
 // RMSNorm's first pass -- h += y (fp32, in place), xn = (h + y) * w in the compute dtype, and partial sums of squares of

@@ -42,6 +42,22 @@ const char *last_error() { return g_err; }
 const char *env_str(const char *name) { const char *s = getenv(name); return s && *s ? s : nullptr; }
 int env_int(const char *name, int dflt) { const char *s = env_str(name); return s ? atoi(s) : dflt; }
 
+// ------------------------------------------------------------------------------- the device
+int device_cu_count() {                      // of the current device (the shards of a group may sit on different ones)
+    constexpr int kMaxDevices = 64;
+    static std::atomic<int> cached[kMaxDevices];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 256;
+    int n = cached[dev].load();
+    if (!n) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
+        if (n <= 0) n = 256;
+        cached[dev].store(n);
+    }
+    return n;
+}
+
 // ------------------------------------------------------------------------------- switches (common.h: TuneKey)
 struct TuneEntry { const char *name; int dflt; bool exp_only = false; };   // exp_only: acts in the EXPERIMENTAL build only (Makefile); fl_tune refuses it elsewhere
 static const TuneEntry g_tune_table[TK_COUNT] = {
@@ -1034,6 +1050,23 @@ static bool engine_usable(Model *m, Cache *c) {
     return want == 1;
 }
 
+// The QKV projection of layer l of a decode step on shard i (k_gemv.hip / k_gemv_w8.hip): RMSNorm prologue over the token's
+// embedding row (layer 0) or x_res + delta, RoPE + KV append into the layer's caches as the epilogue.
+static GemvArgs qkv_gemv_args(Model *m, Cache *c, size_t i, int64_t l) {
+    const Dims &D = m->D;
+    Shard &sh = m->shards[i]; Scratch &sc = sh.dec; CacheShard &cs = c->shards[i]; LayerW &ly = sh.layers[l];
+    const size_t kv_layer = (size_t)l * sh.Hkvs * c->seq_alloc * D.d * m->esize();
+    GemvArgs a;
+    a.W = ly.wqkv; a.bias = ly.bqkv; a.N = (int)((sh.Hs + 2 * sh.Hkvs) * D.d); a.K = (int)D.h;
+    a.epi = EPI_QKV_ROPE; a.pro = PRO_NORM; a.norm_w = ly.ln1; a.eps = D.eps; a.st = cs.st;
+    if (l == 0) { a.embed = sh.embed; a.x_out = sc.x_res2; }
+    else { a.x_in = sc.x_res; a.delta = sc.delta; a.x_out = sc.x_res2; }
+    a.cos_tab = sh.cos_tab; a.sin_tab = sh.sin_tab; a.q_out = sc.q; a.k_cache = (char *)cs.k + kv_layer; a.v_cache = (char *)cs.v + kv_layer;
+    a.H = (int)sh.Hs; a.Hkv = (int)sh.Hkvs; a.d = (int)D.d; a.max_seq = (int)c->seq_alloc; a.max_pos = (int)D.max_pos;
+    a.v_ld = c->v_transposed ? (int)c->seq_alloc : 0;
+    return a;
+}
+
 static int enqueue_decode_engine(Model *m, Cache *c, int64_t len_hint) {
     const Dims &D = m->D;
     const int dt = m->dtype;
@@ -1049,16 +1082,7 @@ static int enqueue_decode_engine(Model *m, Cache *c, int64_t len_hint) {
         LayerW &ly = sh.layers[l];
         void *kc, *vc;
         kv_of(l, &kc, &vc);
-        if (l == 0) {                                  // the first QKV projection reads the token's embedding row: the launch of k_gemv.hip
-            GemvArgs a;
-            a.W = ly.wqkv; a.bias = ly.bqkv; a.N = (int)((sh.Hs + 2 * sh.Hkvs) * D.d); a.K = (int)D.h;
-            a.epi = EPI_QKV_ROPE; a.pro = PRO_NORM; a.norm_w = ly.ln1; a.eps = D.eps; a.st = cs.st;
-            a.embed = sh.embed; a.x_out = sc.x_res2;
-            a.cos_tab = sh.cos_tab; a.sin_tab = sh.sin_tab; a.q_out = sc.q; a.k_cache = kc; a.v_cache = vc;
-            a.H = (int)sh.Hs; a.Hkv = (int)sh.Hkvs; a.d = (int)D.d; a.max_seq = (int)c->seq_alloc; a.max_pos = (int)D.max_pos;
-            a.v_ld = (int)c->seq_alloc;
-            FL_TRY(launch_gemv(L, dt, a));
-        }
+        if (l == 0) FL_TRY(launch_gemv(L, dt, qkv_gemv_args(m, c, 0, 0)));   // the first QKV projection reads the token's embedding row: the launch of k_gemv.hip
         AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, len_hint + 1};
         FL_TRY(launch_attn_decode_mfma(L, sc.q, kc, vc, cs.st, sc.ao, as, sh.Hs, sh.Hkvs, D.d, (int64_t)c->seq_alloc, D.scale));
         const bool last = l + 1 == D.L;
@@ -1122,14 +1146,7 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             Launcher L = make_launcher(m, sh);
             const size_t kv_layer = (size_t)l * sh.Hkvs * c->seq_alloc * D.d * m->esize();
             void *kc = (char *)cs.k + kv_layer, *vc = (char *)cs.v + kv_layer;
-            GemvArgs a;
-            a.W = ly.wqkv; a.bias = ly.bqkv; a.N = (int)((sh.Hs + 2 * sh.Hkvs) * D.d); a.K = (int)D.h;
-            a.epi = EPI_QKV_ROPE; a.pro = PRO_NORM; a.norm_w = ly.ln1; a.eps = D.eps; a.st = cs.st;
-            if (l == 0) { a.embed = sh.embed; a.x_out = sc.x_res2; }
-            else { a.x_in = sc.x_res; a.delta = sc.delta; a.x_out = sc.x_res2; }
-            a.cos_tab = sh.cos_tab; a.sin_tab = sh.sin_tab; a.q_out = sc.q; a.k_cache = kc; a.v_cache = vc;
-            a.H = (int)sh.Hs; a.Hkv = (int)sh.Hkvs; a.d = (int)D.d; a.max_seq = (int)c->seq_alloc; a.max_pos = (int)D.max_pos;
-            a.v_ld = c->v_transposed ? (int)c->seq_alloc : 0;
+            GemvArgs a = qkv_gemv_args(m, c, i, l);
             FL_TRY(gemv(L, a, ly.wqkv8, ly.sqkv));
             AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, len_hint + 1};
             if (!w8) {
