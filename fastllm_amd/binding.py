@@ -162,6 +162,8 @@ def lib():
         L.fl_op_sample_ex.argtypes = [vp, C.c_int64, C.POINTER(FlSampler), C.c_int64, vp, vp]
         L.fl_batch_decode_each_ex.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
+        L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
+        L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
         L.fl_batch_create.argtypes = [vp, vp, sz, C.POINTER(vp)]
         L.fl_batch_destroy.argtypes = [vp]
         L.fl_batch_destroy.restype = None
@@ -669,6 +671,55 @@ def op_attention(q, k, v, s_past, H, Hkv, d, window=-1, kernel=0, nsplit=0):
     assert q.shape == (T, H * d) and k.shape == (s_past + T, Hkv * d) and v.shape == k.shape
     out = np.empty((T, H * d), dtype=np.float32)
     _check(lib().fl_op_attention(q.ctypes.data, k.ctypes.data, v.ctypes.data, T, s_past, H, Hkv, d, window, kernel, nsplit, out.ctypes.data))
+    return out
+
+
+def _attn_dtype(*arrays):
+    """uint16 arrays are bf16 bits, float32 arrays fp32: (FL_DTYPE code, numpy dtype) of a set of attention operands."""
+    kinds = set(np.asarray(a).dtype for a in arrays)
+    assert len(kinds) == 1 and kinds <= {np.dtype(np.uint16), np.dtype(np.float32)}, kinds
+    dt = kinds.pop()
+    return (1 if dt == np.uint16 else 0), dt
+
+
+def op_attention_plain(q, k, v, s_past, H, Hkv, d, layout=0, kernel=0, call0=None, capacity=None, window=-1, nsplit=1, pad_value=0.0,
+                       repeat=1):
+    """The single-sequence attention launches on a cache built in the model's layout (fl_op_attention_plain): layout 0 = the plain
+    (VALU) kernels, bf16 (uint16 bits) or float32 by the arrays' dtype; layout 1 = the bf16 MFMA kernels.  q [T, H*d]; k / v
+    [rows, Hkv*d] with rows >= s_past + T (the rows behind s_past + T are stale cache contents); positions from rows to `capacity`
+    hold pad_value.  Returns [repeat, T, H*d] f32: the output of every one of `repeat` launches on the same scratch."""
+    code, dt = _attn_dtype(q, k, v)
+    q, k, v = (np.ascontiguousarray(a, dtype=dt) for a in (q, k, v))
+    T, rows = q.shape[0], k.shape[0]
+    assert q.shape == (T, H * d) and k.shape == (rows, Hkv * d) and v.shape == k.shape
+    out = np.empty((max(repeat, 1), T, H * d), dtype=np.float32)
+    _check(lib().fl_op_attention_plain(q.ctypes.data, k.ctypes.data, v.ctypes.data, code, layout, kernel, T, s_past,
+                                       s_past if call0 is None else call0, rows, rows if capacity is None else capacity, H, Hkv, d, window,
+                                       nsplit, pad_value, repeat, out.ctypes.data))
+    return out
+
+
+def op_attention_batch(q, ks, vs, lens, seq_alloc, nsplit, H, Hkv, d, layout=0, layer=0, pad_value=0.0, repeat=1):
+    """The batched decode attention launches alone (fl_op_attention_batch).  q [B, H*d]; ks[b] / vs[b] [n_layers, rows_b, Hkv*d]
+    (uint16 bf16 bits or float32); lens[b] keys of layer `layer` are visible to sequence b, the rows behind are stale contents.
+    seq_alloc[b]: the cache's row count (a multiple of 32); nsplit[b]: its split count (0: as fl_cache_create).  Returns
+    [repeat, B, H*d] f32."""
+    code, dt = _attn_dtype(q, *ks, *vs)
+    q = np.ascontiguousarray(q, dtype=dt)
+    ks = [np.ascontiguousarray(a, dtype=dt) for a in ks]
+    vs = [np.ascontiguousarray(a, dtype=dt) for a in vs]
+    B, n_layers = q.shape[0], ks[0].shape[0]
+    assert q.shape == (B, H * d) and len(ks) == len(vs) == len(lens) == len(seq_alloc) == len(nsplit) == B
+    for a, b in zip(ks, vs):
+        assert a.ndim == 3 and a.shape[0] == n_layers and a.shape[2] == Hkv * d and a.shape == b.shape
+    kp = (C.c_void_p * B)(*[a.ctypes.data for a in ks])
+    vpp = (C.c_void_p * B)(*[a.ctypes.data for a in vs])
+    i64 = lambda x: np.ascontiguousarray(x, dtype=np.int64)
+    ln, rows, sa, ns = i64(lens), i64([a.shape[1] for a in ks]), i64(seq_alloc), np.ascontiguousarray(nsplit, dtype=np.int32)
+    out = np.empty((max(repeat, 1), B, H * d), dtype=np.float32)
+    _check(lib().fl_op_attention_batch(q.ctypes.data, C.cast(kp, C.c_void_p), C.cast(vpp, C.c_void_p), code, layout, B, ln.ctypes.data,
+                                       rows.ctypes.data, sa.ctypes.data, ns.ctypes.data, n_layers, layer, H, Hkv, d, pad_value, repeat,
+                                       out.ctypes.data))
     return out
 
 

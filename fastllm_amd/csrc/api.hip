@@ -41,6 +41,80 @@ template <typename F> static void guarded_void(F &&body) noexcept {
     (void)guarded([&]() -> int { body(); return FL_OK; });
 }
 
+// ---- fl_op_attention_plain / fl_op_attention_batch: the attention launches on caches built here in the model's layout ----------
+namespace {
+
+struct AttnOpBufs {
+    std::vector<void *> p; hipStream_t s = 0;
+    ~AttnOpBufs() { if (s) (void)hipStreamSynchronize(s);
+                    for (void *x : p) (void)hipFree(x);
+                    if (s) (void)hipStreamDestroy(s); }
+    int alloc(void **out, size_t bytes) { *out = nullptr; FL_HIP(hipMalloc(out, bytes ? bytes : 4)); p.push_back(*out); return FL_OK; }
+    int upload(void **out, const void *src, size_t bytes) { FL_TRY(alloc(out, bytes)); FL_HIP(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice)); return FL_OK; }
+};
+
+// One sequence's K and V as cache_create lays them out: K [L][Hkv][sa][d]; V the same, or transposed [L][Hkv][d][sa] for the MFMA
+// kernels.  Host rows [L][rows][Hkv*d]; every position >= rows holds `pad`.  E: the element's bit pattern (uint16_t / uint32_t).
+template <typename E>
+void attn_op_cache(std::vector<E> &kc, std::vector<E> &vc, const void *k, const void *v, int64_t L, int64_t rows, int64_t Hkv, int64_t sa,
+                   int64_t d, bool v_transposed, E pad) {
+    kc.assign((size_t)(L * Hkv * sa * d), pad); vc.assign((size_t)(L * Hkv * sa * d), pad);
+    const E *kh = reinterpret_cast<const E *>(k), *vh = reinterpret_cast<const E *>(v);
+    for (int64_t l = 0; l < L; l++)
+        for (int64_t s = 0; s < rows; s++)
+            for (int64_t h = 0; h < Hkv; h++)
+                for (int64_t j = 0; j < d; j++) {
+                    const size_t src = (size_t)(((l * rows + s) * Hkv + h) * d + j), head = (size_t)((l * Hkv + h) * sa * d);
+                    kc[head + (size_t)(s * d + j)] = kh[src];
+                    vc[head + (size_t)(v_transposed ? j * sa + s : s * d + j)] = vh[src];
+                }
+}
+
+int attn_op_upload_cache(AttnOpBufs &B, void **kd, void **vd, int32_t dtype, const void *k, const void *v, int64_t L, int64_t rows, int64_t Hkv,
+                         int64_t sa, int64_t d, bool v_transposed, float pad_value) {
+    if (dtype == FL_DTYPE_BF16) {
+        std::vector<uint16_t> kc, vc;
+        attn_op_cache<uint16_t>(kc, vc, k, v, L, rows, Hkv, sa, d, v_transposed, float_to_bf16_bits_host(pad_value));
+        FL_TRY(B.upload(kd, kc.data(), kc.size() * 2)); FL_TRY(B.upload(vd, vc.data(), vc.size() * 2));
+    } else {
+        union { float f; uint32_t u; } pv; pv.f = pad_value;
+        std::vector<uint32_t> kc, vc;
+        attn_op_cache<uint32_t>(kc, vc, k, v, L, rows, Hkv, sa, d, v_transposed, pv.u);
+        FL_TRY(B.upload(kd, kc.data(), kc.size() * 4)); FL_TRY(B.upload(vd, vc.data(), vc.size() * 4));
+    }
+    return FL_OK;
+}
+
+// the split scratch of one cache, sized as cache_create sizes it
+int attn_op_scratch(AttnOpBufs &B, float **pm, float **pl, float **po, unsigned **cnt, int64_t H, int64_t d, int nsplit) {
+    FL_TRY(B.alloc((void **)pm, (size_t)H * nsplit * 4)); FL_TRY(B.alloc((void **)pl, (size_t)H * nsplit * 4));
+    FL_TRY(B.alloc((void **)po, (size_t)H * nsplit * d * 4)); FL_TRY(B.alloc((void **)cnt, (size_t)H * 4));
+    FL_HIP(hipMemset(*cnt, 0, (size_t)H * 4));
+    return FL_OK;
+}
+
+// the launches' outputs, [n] elements of `dtype` on the device, widened to fp32
+int attn_op_download(float *out, const void *dev, size_t n, int32_t dtype) {
+    if (dtype == FL_DTYPE_BF16) {
+        std::vector<bf16_t> oh(n);
+        FL_HIP(hipMemcpy(oh.data(), dev, n * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) out[i] = bf16_bits_to_float(oh[i]);
+    } else {
+        FL_HIP(hipMemcpy(out, dev, n * 4, hipMemcpyDeviceToHost));
+    }
+    return FL_OK;
+}
+
+int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, int64_t d) {
+    if ((dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) || layout < 0 || layout > 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype: bf16 or f32; layout: 0 plain, 1 MFMA");
+    if (H < 1 || Hkv < 1 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head counts (H a multiple of Hkv)");
+    if (d != 64 && d != 128) FL_FAIL(FL_ERR_UNSUPPORTED, "attention: head_dim %lld not supported (64 or 128)", (long long)d);
+    if (layout == 1 && !attn_mfma_supported(dtype, H, Hkv, d)) FL_FAIL(FL_ERR_UNSUPPORTED, "MFMA attention: bf16, head_dim 64 / 128, at most 8 query heads per kv head");
+    return FL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int fl_abi_version(void) { return FL_ABI_VERSION; }
@@ -910,6 +984,118 @@ int fl_op_attention(const void *q, const void *k, const void *v, int64_t T, int6
         FL_HIP(hipMemcpy(oh.data(), B.o, qb, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < oh.size(); i++) out[i] = bf16_bits_to_float(oh[i]);
         return FL_OK;
+    });
+}
+
+
+int fl_op_attention_plain(const void *q, const void *k, const void *v, int32_t dtype, int32_t layout, int32_t kernel, int64_t T, int64_t s_past,
+                          int64_t call0, int64_t k_rows, int64_t capacity, int64_t H, int64_t Hkv, int64_t d, int64_t window, int32_t nsplit,
+                          float pad_value, int32_t repeat, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || s_past < 0 || call0 < 0 || call0 > s_past || kernel < 0 || kernel > 3 || (layout == 0 && kernel == 3) || nsplit < 0 || nsplit > 64 ||
+            repeat < 1 || repeat > 16)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape / kernel (call0 <= s_past, nsplit 0..64, repeat 1..16; the plain layout has one prefill kernel)");
+        if (kernel == 1 && T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "the decode kernel takes one query token");
+        const int64_t S = s_past + T;
+        if (k_rows < S || capacity < k_rows || capacity > (int64_t)1 << 24) FL_FAIL(FL_ERR_BAD_ARGUMENT, "s_past + T <= k_rows <= capacity");
+        if (!(pad_value == pad_value) || pad_value - pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pad_value must be finite");
+        FL_TRY(attn_op_check_heads(dtype, layout, H, Hkv, d));
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        const bool mfma = layout == 1, decode = kernel == 1 || (kernel == 0 && T == 1);
+        const int64_t sa = (capacity + 31) / 32 * 32;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, qn = (size_t)T * H * d;
+        if (nsplit == 0) nsplit = attn_cache_nsplit(mfma, (size_t)capacity, d);
+        AttnOpBufs B;
+        FL_HIP(hipStreamCreate(&B.s));
+        void *qd, *od, *kd, *vd; StepState *std_; float *pm, *pl, *po; unsigned *cnt;
+        FL_TRY(B.upload(&qd, q, qn * es));
+        FL_TRY(B.alloc(&od, qn * es * repeat));
+        FL_HIP(hipMemset(od, 0xff, qn * es * repeat));            // NaN pattern: an element a launch does not write shows up
+        FL_TRY(attn_op_upload_cache(B, &kd, &vd, dtype, k, v, 1, k_rows, Hkv, sa, d, mfma, pad_value));
+        FL_TRY(attn_op_scratch(B, &pm, &pl, &po, &cnt, H, d, nsplit));
+        StepState st{}; st.pos = (uint32_t)s_past; st.len = (uint32_t)s_past; st.call0 = (uint32_t)call0; st.eos = -1;
+        FL_TRY(B.upload((void **)&std_, &st, sizeof st));
+        Launcher L; L.stream = B.s;
+        const float scale = 1.0f / sqrtf((float)d);
+        const int64_t w = window < 0 ? -1 : window;
+        for (int r = 0; r < repeat; r++) {                          // every launch on the same scratch and ticket words
+            void *o = (char *)od + (size_t)r * qn * es;
+            int rc;
+            if (decode) {
+                AttnScratch as{pm, pl, po, cnt, nsplit, S};
+                rc = mfma ? launch_attn_decode_mfma(L, qd, kd, vd, std_, o, as, H, Hkv, d, sa, scale)
+                          : launch_attn_decode(L, dtype, qd, kd, vd, std_, o, as, H, Hkv, d, sa, scale);
+            } else if (mfma) {
+                attn_prefill_force(kernel);
+                rc = launch_attn_prefill_mfma(L, qd, kd, vd, std_, o, T, H, Hkv, d, sa, scale, w);
+                attn_prefill_force(0);
+            } else {
+                rc = launch_attn_prefill(L, dtype, qd, kd, vd, std_, o, T, H, Hkv, d, sa, scale, w);
+            }
+            FL_TRY(rc);
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        return attn_op_download(out, od, qn * repeat, dtype);
+    });
+}
+
+int fl_op_attention_batch(const void *q, const void *const *k, const void *const *v, int32_t dtype, int32_t layout, int64_t B_, const int64_t *lens,
+                          const int64_t *k_rows, const int64_t *seq_alloc, const int32_t *nsplit, int64_t n_layers, int64_t layer, int64_t H,
+                          int64_t Hkv, int64_t d, float pad_value, int32_t repeat, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !lens || !k_rows || !seq_alloc || !nsplit || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (B_ < 1 || B_ > 1023 || n_layers < 1 || n_layers > 64 || layer < 0 || layer >= n_layers || repeat < 1 || repeat > 16)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (1 <= B <= 1023, layer < n_layers <= 64, repeat 1..16)");
+        for (int64_t b = 0; b < B_; b++) {
+            if (!k[b] || !v[b]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument (sequence %lld)", (long long)b);
+            if (lens[b] < 1 || k_rows[b] < lens[b] || seq_alloc[b] < k_rows[b] || seq_alloc[b] % 32 != 0 || seq_alloc[b] > (int64_t)1 << 24)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: 1 <= len <= k_rows <= seq_alloc, seq_alloc a multiple of 32", (long long)b);
+            if (nsplit[b] < 0 || nsplit[b] > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: nsplit 0..64", (long long)b);
+        }
+        if (!(pad_value == pad_value) || pad_value - pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pad_value must be finite");
+        FL_TRY(attn_op_check_heads(dtype, layout, H, Hkv, d));
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        const bool mfma = layout == 1;
+        const int nb = (int)B_;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, qn = (size_t)nb * H * d;
+        AttnOpBufs B;
+        FL_HIP(hipStreamCreate(&B.s));
+        void *qd, *od;
+        FL_TRY(B.upload(&qd, q, qn * es));
+        FL_TRY(B.alloc(&od, qn * es * repeat));
+        FL_HIP(hipMemset(od, 0xff, qn * es * repeat));
+        // every sequence a cache of its own, as fl_batch_create finds them: K / V of all layers, step state, split scratch, ticket
+        // words; the SeqRef fields the attention kernels do not read stay null
+        std::vector<SeqRef> refs((size_t)nb);
+        int max_nsplit = 1;
+        for (int b = 0; b < nb; b++) {
+            SeqRef &r = refs[(size_t)b];
+            r = SeqRef{};
+            r.seq_alloc = (int)seq_alloc[b];
+            r.nsplit = nsplit[b] > 0 ? nsplit[b] : attn_cache_nsplit(mfma, (size_t)seq_alloc[b], d);
+            max_nsplit = std::max(max_nsplit, r.nsplit);
+            FL_TRY(attn_op_upload_cache(B, &r.k, &r.v, dtype, k[b], v[b], n_layers, k_rows[b], Hkv, seq_alloc[b], d, mfma, pad_value));
+            FL_TRY(attn_op_scratch(B, &r.part_m, &r.part_l, &r.part_o, &r.counters, H, d, r.nsplit));
+            StepState st{}; st.pos = (uint32_t)(lens[b] - 1); st.len = (uint32_t)(lens[b] - 1); st.call0 = st.len; st.eos = -1;
+            FL_TRY(B.upload((void **)&r.st, &st, sizeof st));
+        }
+        SeqRef *seqs_dev;
+        FL_TRY(B.upload((void **)&seqs_dev, refs.data(), sizeof(SeqRef) * (size_t)nb));
+        Launcher L; L.stream = B.s;
+        const float scale = 1.0f / sqrtf((float)d);
+        const size_t kv_layer_off = (size_t)(layer * Hkv * d);
+        for (int r = 0; r < repeat; r++) {
+            void *o = (char *)od + (size_t)r * qn * es;
+            if (mfma) FL_TRY(launch_attn_decode_mfma_batch(L, qd, seqs_dev, nb, max_nsplit, kv_layer_off, o, H, Hkv, d, scale, 0.0));
+            else FL_TRY(launch_attn_decode_batch(L, dtype, qd, seqs_dev, nb, max_nsplit, kv_layer_off, o, H, Hkv, d, scale));
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        return attn_op_download(out, od, qn * repeat, dtype);
     });
 }
 

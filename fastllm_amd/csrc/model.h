@@ -205,6 +205,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
                  const fl_parallel *par, const fl_model_options *opts, Model **out);
+int attn_cache_nsplit(bool v_transposed, size_t max_seq, int64_t d);   // the split count cache_create gives a cache (before FL_ATTN_NSPLIT)
 int cache_create(Model *m, size_t max_seq, Cache **out);
 // FL_TP_MULTI_PROCESS: export this rank's inbox / map the peers' (handles: tp x FL_IPC_HANDLE_BYTES in rank order)
 int comm_ipc_export(Model *m, void *handle_out);

@@ -534,6 +534,38 @@ int fl_op_kv_copy(const void *src, void *dst, int64_t rows, int64_t width_bytes,
 int fl_op_attention(const void *q, const void *k, const void *v, int64_t T, int64_t s_past, int64_t H, int64_t Hkv,
                     int64_t d, int64_t window, int32_t kernel, int32_t nsplit, float *out);
 
+/* The attention launches of the model on caches built here from host buffers, for unit tests: the plain-layout (VALU) kernels of
+ * every fp32 model and of the bf16 head shapes the MFMA kernels refuse (layout 0; dtype FL_DTYPE_BF16 or FL_DTYPE_F32), or the bf16
+ * MFMA kernels of fl_op_attention (layout 1: V transposed, FL_DTYPE_BF16, at most 8 query heads per kv head).  One sequence: q
+ * [T][H*d], k / v [k_rows][Hkv*d] of `dtype`, row-major.  The cache gets `capacity` positions (rounded up to 32 as fl_cache_create
+ * does): rows [0, s_past) are the cached prefix, [s_past, s_past + T) the call's tokens, rows [s_past + T, k_rows) are stale
+ * contents behind the cached length (what fl_cache_truncate or a speculative rollback leaves), and every position from k_rows on
+ * holds pad_value (finite).  call0 <= s_past: the cached length when the API call began -- below s_past it is the mask of a later
+ * chunk of a prefill the library cut up: keys below call0 are visible, key j >= call0 is visible to the query at position p iff
+ * j <= p and j + window >= p (window < 0: none; T == 1 through the decode kernel: no mask).  kernel: 0 = what the model would
+ * launch, 1 = decode (T must be 1), 2 = prefill (layout 1: the 16-row kernel), 3 = the 32-row prefill kernel (layout 1 only).
+ * nsplit: key splits of the decode kernel, 1..64, 0 = what fl_cache_create picks for `capacity`; the workgroup width of the plain
+ * decode kernel is the attn_nw switch (fl_tune).  `repeat` (1..16) launches run on ONE split scratch and one set of ticket words;
+ * out [repeat][T][H*d] fp32 holds every launch's output (pre-filled with the 0xff pattern, bf16 widened).  Argument errors are
+ * FL_ERR_BAD_ARGUMENT, head shapes no kernel takes (d other than 64 / 128, layout 1 with fp32 or more than 8 heads per kv head)
+ * FL_ERR_UNSUPPORTED, both before the device is touched. */
+int fl_op_attention_plain(const void *q, const void *k, const void *v, int32_t dtype, int32_t layout, int32_t kernel, int64_t T,
+                          int64_t s_past, int64_t call0, int64_t k_rows, int64_t capacity, int64_t H, int64_t Hkv, int64_t d,
+                          int64_t window, int32_t nsplit, float pad_value, int32_t repeat, float *out);
+
+/* The batched decode attention launches alone (unit tests): layout 0 = the plain-layout kernel (bf16 or fp32), layout 1 = the MFMA
+ * kernel (bf16, V transposed).  B sequences, each with a cache of its own as fl_batch_create finds them: k[b] / v[b] are host rows
+ * [n_layers][k_rows[b]][Hkv*d] of `dtype`; sequence b sees keys [0, lens[b]) of layer `layer` (the last of them is the step's own
+ * token), rows [lens[b], k_rows[b]) are stale contents, positions from k_rows[b] to seq_alloc[b] (a multiple of 32) hold pad_value
+ * in every layer.  nsplit[b]: the sequence's split count, 1..64, 0 = what fl_cache_create picks for a cache of seq_alloc[b]
+ * positions; its split scratch and ticket words are sized for it.  The MFMA launch caps the splits by the attn_batch_wgs switch
+ * (fl_tune) as in the model.  q [B][H*d]; out [repeat][B][H*d] fp32, `repeat` launches on the same scratch as above.  Errors as
+ * fl_op_attention_plain. */
+int fl_op_attention_batch(const void *q, const void *const *k, const void *const *v, int32_t dtype, int32_t layout, int64_t B,
+                          const int64_t *lens, const int64_t *k_rows, const int64_t *seq_alloc, const int32_t *nsplit,
+                          int64_t n_layers, int64_t layer, int64_t H, int64_t Hkv, int64_t d, float pad_value, int32_t repeat,
+                          float *out);
+
 #ifdef __cplusplus
 }
 #endif

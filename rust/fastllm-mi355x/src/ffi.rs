@@ -455,4 +455,45 @@ extern "C" {
         nsplit: i32,
         out: *mut f32,
     ) -> c_int;
+    pub fn fl_op_attention_plain(
+        q: *const c_void,
+        k: *const c_void,
+        v: *const c_void,
+        dtype: i32,
+        layout: i32,
+        kernel: i32,
+        t: i64,
+        s_past: i64,
+        call0: i64,
+        k_rows: i64,
+        capacity: i64,
+        h: i64,
+        hkv: i64,
+        d: i64,
+        window: i64,
+        nsplit: i32,
+        pad_value: f32,
+        repeat: i32,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_attention_batch(
+        q: *const c_void,
+        k: *const *const c_void,
+        v: *const *const c_void,
+        dtype: i32,
+        layout: i32,
+        b: i64,
+        lens: *const i64,
+        k_rows: *const i64,
+        seq_alloc: *const i64,
+        nsplit: *const i32,
+        n_layers: i64,
+        layer: i64,
+        h: i64,
+        hkv: i64,
+        d: i64,
+        pad_value: f32,
+        repeat: i32,
+        out: *mut f32,
+    ) -> c_int;
 }

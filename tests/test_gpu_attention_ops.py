@@ -33,19 +33,24 @@ def make(T, s_past, H, Hkv, d, seed, spike=False):
     return q, k, v
 
 
-def reference(q, k, v, s_past, H, Hkv, d, window):
-    qf = synth.bf16_bits_to_f32(q).astype(np.float64).reshape(-1, H, d)
-    kf = synth.bf16_bits_to_f32(k).astype(np.float64).reshape(-1, Hkv, d)
-    vf = synth.bf16_bits_to_f32(v).astype(np.float64).reshape(-1, Hkv, d)
+def reference(q, k, v, s_past, H, Hkv, d, window, call0=None, dtype=np.float64):
+    """q, k, v: bf16 bits (uint16) or float arrays.  call0 (default s_past): the cached length when the API call began; below s_past
+    it is the mask of a later chunk of a prefill cut into chunks: keys before call0 are visible, key j >= call0 is visible to the
+    query at position p iff j <= p and j + window >= p.  dtype: the precision the whole computation runs in."""
+    def wide(a):
+        a = np.asarray(a)
+        return (synth.bf16_bits_to_f32(a) if a.dtype == np.uint16 else a).astype(dtype)
+    qf, kf, vf = wide(q).reshape(-1, H, d), wide(k).reshape(-1, Hkv, d), wide(v).reshape(-1, Hkv, d)
     T, S, G = qf.shape[0], kf.shape[0], H // Hkv
-    out = np.zeros((T, H, d))
+    c0 = s_past if call0 is None else call0
+    out = np.zeros((T, H, d), dtype=dtype)
     for h in range(H):
         g = h // G                                               # App. A.6: q head h uses kv head h // (H / Hkv)
-        sc = qf[:, h, :] @ kf[:, g, :].T / np.sqrt(d)            # [T, S]
+        sc = qf[:, h, :] @ kf[:, g, :].T / np.sqrt(dtype(d))     # [T, S]
         if T > 1:                                                # App. A.5: no mask at T == 1
-            t = np.arange(T)[:, None]
-            j = np.arange(S)[None, :] - s_past
-            vis = (j < 0) | ((j <= t) & ((window < 0) | (j + window >= t)))
+            p = s_past + np.arange(T)[:, None]
+            j = np.arange(S)[None, :]
+            vis = (j < c0) | ((j <= p) & ((window < 0) | (j + window >= p)))
             sc = np.where(vis, sc, -np.inf)
         sc -= sc.max(axis=1, keepdims=True)
         p = np.exp(sc)
