@@ -26,7 +26,7 @@ const char *last_error();
 int raise_dynamic_lds(const void *fn, size_t lds_bytes);
 
 // ---- process-wide switches -------------------------------------------------------------------
-// Every kernel-selection knob is an int in ONE table (model.hip, g_tune_table): read once from the environment (FL_<NAME>) when first
+// Every kernel-selection knob is an int in ONE table (runtime.hip, g_tune_table): read once from the environment (FL_<NAME>) when first
 // used, afterwards changed only through fl_tune(name, value) ("reload_env" re-reads the environment: tests and A/B tools).
 // No per-launch getenv.
 enum TuneKey {

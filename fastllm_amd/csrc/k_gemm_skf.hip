@@ -389,7 +389,7 @@ static int skf_space(hipStream_t stream, SkfSpace *out) {
     std::lock_guard<std::mutex> lock(g_skf_mu);
     SkfWs &sp = g_skf_spaces[{dev, stream}];
     if (!sp.part) {
-        // (first sliced launch on this stream.  Never inside a stream capture: a decode batch's first step runs eagerly, model.hip)
+        // (first sliced launch on this stream.  Never inside a stream capture: a decode batch's first step runs eagerly, batch.hip)
         FL_HIP(hipMalloc((void **)&sp.part, kSkfPartBytes));
         const hipError_t e = hipMalloc((void **)&sp.cnt, kSkfMaxTiles * sizeof(unsigned));
         if (e != hipSuccess) { (void)hipFree(sp.part); sp.part = nullptr; FL_HIP(e); }

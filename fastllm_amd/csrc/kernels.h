@@ -48,7 +48,7 @@ struct Launcher {
     }
 };
 
-int device_cu_count();   // CUs of the current device, cached per device (model.hip); 256 where the runtime does not tell
+int device_cu_count();   // CUs of the current device, cached per device (runtime.hip); 256 where the runtime does not tell
 
 enum { EPI_F32 = 0, EPI_GATEUP = 1, EPI_QKV_ROPE = 2, EPI_RESID = 3 };
 // EPI_RESID (256x256 prefill GEMM only): the o_proj / down_proj epilogue takes over the residual add and the next
@@ -479,7 +479,7 @@ int launch_encoder_pool_l2(Launcher &L, const float *x, const int32_t *offsets, 
 // dst[row_map(r)][c] = cvt(src[r0+r][c0+c]); row_mode 0: dst_row0+r, 1: gate rows, 2: up rows
 int launch_convert_slice(Launcher &L, int src_dtype, const void *src, int64_t src_ld, int64_t r0, int64_t c0,
                          int64_t rows, int64_t cols, int dst_dtype, void *dst, int64_t dst_ld,
-                         int64_t dst_row0, int row_mode, int head_pad = 0, int64_t dm = 1, int64_t d = 1);   // head_pad: padded head_dim (model.hip)
+                         int64_t dst_row0, int row_mode, int head_pad = 0, int64_t dm = 1, int64_t d = 1);   // head_pad: padded head_dim (weights.hip)
 int launch_convert_vec_f32(Launcher &L, int src_dtype, const void *src, int64_t off, int64_t n, float *dst);
 
 }  // namespace fl

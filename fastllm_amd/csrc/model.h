@@ -1,6 +1,7 @@
 // model.h -- model / cache objects behind the C ABI and the forward-pass orchestration.
 #pragma once
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -16,7 +17,7 @@ struct Dims {                    // resolved config (defaults applied, SURVEY.md
     int family = 0, qkv_bias = 0;
     int64_t h = 0, inter = 0, V = 0, L = 0, H = 0, Hkv = 0, max_pos = 0, window = -1;
     int64_t dm = 0;              // the MODEL's head_dim = hidden_size / num_attention_heads (any even value, config.rs:31-43)
-    int64_t d = 0;               // the head_dim the kernels run: dm padded to 64 or 128 with zero weight rows (model.hip, build_weights)
+    int64_t d = 0;               // the head_dim the kernels run: dm padded to 64 or 128 with zero weight rows (weights.hip, build_weights)
     float eps = 0.f, scale = 0.f;
     double theta = 10000.0;
 };
@@ -212,7 +213,7 @@ int comm_ipc_export(Model *m, void *handle_out);
 int comm_ipc_connect(Model *m, const void *handles);
 bool fused_all_reduce_ready(const Model *m);   // decode all-reduces ride in the GEMV epilogues (comm_ll.h)
 
-// shared by model.hip and comm.hip
+// shared by runtime.hip, weights.hip, model.hip, batch.hip and comm.hip
 #define FL_NCCL(expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) { \
     ::fl::set_error("RCCL error %s at %s:%d (%s)", ncclGetErrorString(r_), __FILE__, __LINE__, #expr); \
     return FL_ERR_RCCL; } } while (0)
@@ -251,7 +252,36 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
                   const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
 int check_lookup(const fl_lookup *opts);     // FL_ERR_BAD_ARGUMENT: null, wrong struct_size, a range error
 
-// most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (model.hip)
+// most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (weights.hip)
+constexpr int kMaxKSplit = 4;
+constexpr int kMaxKSplitMid = 8;
+constexpr int kMidT = 1024;
+constexpr int kMaxQkvSplit = 2;   // QKV projection of a long prompt (its grid leaves CUs idle); rope_kv sums the slabs
+constexpr int kMaxQkvSplitShort = 4;   // ... of a short prompt / a decode batch (T <= 128: the projection is a weight stream)
 int ksplit_cap(int64_t T);
+int qkv_split(int64_t T);                    // K slabs a prompt's QKV projection may leave
+
+// shared by weights.hip, model.hip and batch.hip
+int dev_alloc(std::vector<void *> &owner, void **p, size_t bytes, int64_t *acct);
+int alloc_scratch(Model *m, Shard &sh, Scratch &sc, int64_t T, std::vector<void *> *owner = nullptr);   // owner: who frees the buffers (default: the shard, i.e. at model destruction)
+int grow_prefill_scratch(Model *m, Shard &sh, int64_t T);
+int check_call(Model *m, Cache *c, size_t T, size_t pos);
+int check_token(const Model *m, uint32_t id, const char *what);   // FL_ERR_BAD_ARGUMENT: an id the vocabulary does not have
+struct KvLayer {                             // K and V of layer l in one shard of a cache ([L][Hkvs][seq_alloc][d] each)
+    void *k, *v;
+    KvLayer(const Model *m, const Cache *c, const Shard &sh, const CacheShard &cs, int64_t l) {
+        const size_t off = (size_t)l * sh.Hkvs * c->seq_alloc * m->D.d * m->esize();
+        k = (char *)cs.k + off; v = (char *)cs.v + off;
+    }
+};
+// decode attention of one cache in the layout it was created with: the MFMA kernel (transposed V) or the plain one
+int attend_decode(Launcher &L, const Model *m, const Cache *c, const Shard &sh, const CacheShard &cs, const KvLayer &kv, const void *q, void *ao, const AttnScratch &as);
+ResidEpi resid_epi(const Scratch &sc, const Dims &D, const float *next_norm_w);   // residual epilogue of o_proj / down_proj (kernels.h)
+// the device StepState (and, ss_set, the token selection) of one cache shard, on the shard's stream
+int set_shard_state(Model *m, Shard &sh, CacheShard &cs, uint32_t token, size_t pos, size_t len, size_t call0, uint32_t step, int64_t eos, const SampleState &ss_new, bool ss_set);
+// One step as a hipGraph per slot: replay if there is one; after a warm (eager) step capture `enqueue` on every slot's stream,
+// instantiate and launch; on any failure destroy what was instantiated, remember it in graph_failed and run eagerly from then on.
+struct GraphSlot { int device; hipStream_t stream; hipGraphExec_t *exec; };
+int replay_or_capture(const std::vector<GraphSlot> &slots, bool graphable, bool &graph_failed, int &warm_steps, const std::function<int()> &enqueue);
 
 }  // namespace fl

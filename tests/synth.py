@@ -55,7 +55,7 @@ CONFIGS = {
                       num_hidden_layers=3, num_attention_heads=2, num_key_value_heads=None,
                       rms_norm_eps=1e-5, rope_theta=10000.0, max_position_embeddings=512),
     # head_dim that is not 64 / 128 (the reference takes any even value, config.rs:31-43): 100 (not a multiple of 8; OpenLLaMA-3B's),
-    # 96 with GQA 3 + q/k/v bias, 48 (below 64).  The library runs them padded to 128 / 128 / 64 (model.hip, resolve_config).
+    # 96 with GQA 3 + q/k/v bias, 48 (below 64).  The library runs them padded to 128 / 128 / 64 (weights.hip, resolve_config).
     "llama_d100": dict(family="llama", hidden_size=400, intermediate_size=352, vocab_size=256,
                        num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
                        rms_norm_eps=1e-5, rope_theta=10000.0, max_position_embeddings=512),

@@ -1,4 +1,4 @@
-"""The switch table (common.h `enum TuneKey`, model.hip `g_tune_table`) is indexed by the enum: the two lists must name the same switches
+"""The switch table (common.h `enum TuneKey`, runtime.hip `g_tune_table`) is indexed by the enum: the two lists must name the same switches
 in the same order -- a row added to one and not the other would silently re-label every switch behind it."""
 import os
 import re
@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_enum_and_table_name_the_same_switches_in_the_same_order():
     e = open(os.path.join(ROOT, "fastllm_amd", "csrc", "common.h")).read()
-    t = open(os.path.join(ROOT, "fastllm_amd", "csrc", "model.hip")).read()
+    t = open(os.path.join(ROOT, "fastllm_amd", "csrc", "runtime.hip")).read()
     keys = [k for k in re.findall(r"^\s*(TK_\w+)", re.search(r"enum TuneKey \{(.*?)\};", e, re.S).group(1), re.M) if k != "TK_COUNT"]
     names = re.findall(r'\{"(\w+)",', re.search(r"g_tune_table\[TK_COUNT\] = \{(.*?)\};", t, re.S).group(1))
     assert len(keys) == len(names) and len(keys) > 50
