@@ -69,6 +69,32 @@ def make_sampler(temperature, seed=0, draws_done=0, top_p=None, top_k=None):
                      seed, draws_done)
 
 
+LOGPROBS_MAX_TOP = 20
+
+
+class FlLogprobs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("top_n", C.c_int32), ("token_logprob", C.c_void_p), ("top_ids", C.c_void_p),
+                ("top_logprobs", C.c_void_p), ("_reserved", C.c_int64 * 2)]
+
+
+class _LogprobArrays:
+    """Host arrays of one fl_logprobs: n rows of top_n entries (the arrays stay alive as long as this object does)."""
+
+    def __init__(self, n, top_n):
+        self.top_n = int(top_n)
+        w = max(self.top_n, 0)
+        self.token = np.zeros(max(n, 1), dtype=np.float32)
+        self.ids = np.zeros((max(n, 1), w), dtype=np.uint32)
+        self.lps = np.zeros((max(n, 1), w), dtype=np.float32)
+
+    def struct(self):
+        return FlLogprobs(C.sizeof(FlLogprobs), self.top_n, self.token.ctypes.data, self.ids.ctypes.data if self.top_n > 0 else None,
+                          self.lps.ctypes.data if self.top_n > 0 else None)
+
+    def cut(self, n):
+        return self.token[:n], self.ids[:n], self.lps[:n]
+
+
 class FlLookup(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_draft", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32),
                 ("_pad", C.c_int32), ("_reserved", C.c_int64 * 2)]
@@ -161,6 +187,10 @@ def lib():
         L.fl_decode_sample_ex.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampler), vp, C.POINTER(sz)]
         L.fl_op_sample_ex.argtypes = [vp, C.c_int64, C.POINTER(FlSampler), C.c_int64, vp, vp]
         L.fl_batch_decode_each_ex.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
+        L.fl_forward_sample_lp.argtypes = [vp, vp, vp, sz, sz, C.POINTER(FlSampler), vp, C.POINTER(FlLogprobs)]
+        L.fl_decode_sample_lp.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampler), vp, C.POINTER(sz), C.POINTER(FlLogprobs)]
+        L.fl_batch_decode_each_lp.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.fl_op_logprobs.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp]
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
         L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
         L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
@@ -240,6 +270,19 @@ def op_verify_select(logits, draft):
     n = C.c_int64(-1)
     _check(lib().fl_op_verify_select(a.ctypes.data, T, V, d.ctypes.data if d.size else None, out.ctypes.data, C.byref(n)))
     return out, n.value
+
+
+def op_logprobs(logits, chosen, top_n):
+    """The log-prob kernel alone: logits [T, V] float32, chosen [T] -> (token_logprob float32 [T], top_ids uint32 [T, top_n],
+    top_logprobs float32 [T, top_n])."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    ch = np.ascontiguousarray(chosen, dtype=np.uint32)
+    assert ch.shape == (T,)
+    out = _LogprobArrays(T, top_n)
+    _check(lib().fl_op_logprobs(a.ctypes.data, T, V, ch.ctypes.data, int(top_n), out.token.ctypes.data,
+                                out.ids.ctypes.data if top_n > 0 else None, out.lps.ctypes.data if top_n > 0 else None))
+    return out.cut(T)
 
 
 def abi_version():
@@ -467,9 +510,17 @@ class Model:
             return toks[: n.value], dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted)
         return toks[: n.value]
 
-    def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None):
+    def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None, logprobs=None):
+        """logprobs = N (0: the chosen token's only): returns (token, token_logprob [1], top_ids [1, N], top_logprobs [1, N]) --
+        log-softmax of the model's own logits (temperature 1, nothing masked), computed on the device."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         tok = C.c_uint32(0)
+        if logprobs is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            lp = _LogprobArrays(1, logprobs)
+            st = lp.struct()
+            _check(lib().fl_forward_sample_lp(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok), C.byref(st)))
+            return (tok.value,) + lp.cut(1)
         if top_p is not None or top_k is not None:
             sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
             _check(lib().fl_forward_sample_ex(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok)))
@@ -478,9 +529,19 @@ class Model:
         _check(lib().fl_forward_sample(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok)))
         return tok.value
 
-    def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1, top_p=None, top_k=None):
+    def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1, top_p=None, top_k=None,
+                      logprobs=None):
+        """logprobs = N: returns (tokens, token_logprob [n], top_ids [n, N], top_logprobs [n, N]), n = the tokens emitted; a greedy
+        decode with log-probs is temperature=0."""
         toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
         n = C.c_size_t(0)
+        if logprobs is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            lp = _LogprobArrays(n_steps, logprobs)
+            st = lp.struct()
+            _check(lib().fl_decode_sample_lp(self._h, cache._h, int(first_token), pos, n_steps, eos, C.byref(sp), toks.ctypes.data,
+                                             C.byref(n), C.byref(st)))
+            return (toks[: n.value],) + lp.cut(n.value)
         if top_p is not None or top_k is not None:
             sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
             _check(lib().fl_decode_sample_ex(self._h, cache._h, int(first_token), pos, n_steps, eos, C.byref(sp), toks.ctypes.data,
@@ -577,20 +638,30 @@ class Batch:
                                      out.ctypes.data, n_out.ctypes.data))
         return [out[i, : int(n_out[i])] for i in range(self.n)]
 
-    def decode_each(self, first_tokens, pos, n_steps, eos=None, temperatures=None, seeds=None, draws_done=None, top_p=None, top_k=None):
+    def decode_each(self, first_tokens, pos, n_steps, eos=None, temperatures=None, seeds=None, draws_done=None, top_p=None, top_k=None,
+                    logprobs=None):
         """fl_batch_decode_each: per-sequence EOS ids (None / negative: none) and temperatures (None / < 1e-7: ArgMax).  With top_p /
-        top_k (lists, None entries: off) it is fl_batch_decode_each_ex: one batch mixes ArgMax, Sampling::All and top-p / top-k."""
+        top_k (lists, None entries: off) it is fl_batch_decode_each_ex: one batch mixes ArgMax, Sampling::All and top-p / top-k.
+        logprobs (an int, or one per sequence): fl_batch_decode_each_lp; every sequence's entry is then (tokens, token_logprob,
+        top_ids, top_logprobs)."""
         first = np.ascontiguousarray(first_tokens, dtype=np.uint32)
         pos = np.ascontiguousarray(pos, dtype=np.uint64)
         out = np.zeros((self.n, max(n_steps, 1)), dtype=np.uint32)
         n_out = np.zeros(self.n, dtype=np.uint64)
         e = np.ascontiguousarray([-1 if x is None else int(x) for x in (eos if eos is not None else [None] * self.n)], dtype=np.int64)
-        if top_p is not None or top_k is not None:
+        if top_p is not None or top_k is not None or logprobs is not None:
             spx = (FlSampler * self.n)()
             for i in range(self.n):
                 t = temperatures[i] if temperatures is not None and temperatures[i] is not None else 0.0
                 spx[i] = make_sampler(t, seeds[i] if seeds is not None else 0, draws_done[i] if draws_done is not None else 1,
                                       top_p[i] if top_p is not None else None, top_k[i] if top_k is not None else None)
+            if logprobs is not None:
+                tops = [int(logprobs)] * self.n if np.isscalar(logprobs) else [int(x) for x in logprobs]
+                lps = [_LogprobArrays(n_steps, tops[i]) for i in range(self.n)]
+                lpx = (FlLogprobs * self.n)(*[x.struct() for x in lps])
+                _check(lib().fl_batch_decode_each_lp(self._h, first.ctypes.data, pos.ctypes.data, n_steps, e.ctypes.data, C.cast(spx, C.c_void_p),
+                                                     out.ctypes.data, n_out.ctypes.data, C.cast(lpx, C.c_void_p)))
+                return [(out[i, : int(n_out[i])],) + lps[i].cut(int(n_out[i])) for i in range(self.n)]
             _check(lib().fl_batch_decode_each_ex(self._h, first.ctypes.data, pos.ctypes.data, n_steps, e.ctypes.data, C.cast(spx, C.c_void_p),
                                                  out.ctypes.data, n_out.ctypes.data))
             return [out[i, : int(n_out[i])] for i in range(self.n)]

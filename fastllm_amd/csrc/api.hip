@@ -388,6 +388,79 @@ int fl_decode_sample(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos,
     return fl_decode_sample_ex(m, c, first_token, pos, n_steps, eos, &s, tokens_out, n_out);
 }
 
+// ---- token log-probabilities: the sampled entry points with an fl_logprobs (its errors come first: they need neither model nor device)
+int fl_forward_sample_lp(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_sampler *sampler,
+                         uint32_t *token_out, const fl_logprobs *lp) {
+    return guarded([&]() -> int {
+        FL_TRY(check_logprobs(lp, 0));
+        if (!token_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null token_out");
+        return forward(M(m), C(c), ids, T, pos, nullptr, token_out, sampler, lp);
+    });
+}
+
+int fl_decode_sample_lp(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
+                        const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp) {
+    return guarded([&]() -> int {
+        FL_TRY(check_logprobs(lp, 0));
+        return decode_greedy(M(m), C(c), first_token, pos, n_steps, eos, tokens_out, n_out, sampler, lp);
+    });
+}
+
+int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
+                            const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp) {
+    return guarded([&]() -> int {
+        if (!lp) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_logprobs (lp)");
+        return batch_decode_each(reinterpret_cast<Batch *>(b), first_tokens, pos, n_steps, eos, samplers, tokens_out, n_out, lp);
+    });
+}
+
+int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *chosen, int32_t top_n, float *token_logprob,
+                   uint32_t *top_ids, float *top_logprobs) {
+    return guarded([&]() -> int {
+        if (!logits || !chosen || !token_logprob) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: null logits, chosen or token_logprob");
+        if (T < 1 || T > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: T %lld not in 1..64", (long long)T);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: V %lld not in 1..2^24", (long long)V);
+        if (top_n < 0 || top_n > FL_LOGPROBS_MAX_TOP || top_n > V)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: top_n %d not in 0..min(%d, V = %lld)", top_n, FL_LOGPROBS_MAX_TOP, (long long)V);
+        if (top_n > 0 && (!top_ids || !top_logprobs)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: null top_ids or top_logprobs with top_n %d", top_n);
+        for (int64_t t = 0; t < T; t++)
+            if ((int64_t)chosen[t] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: chosen[%lld] = %u is not below V = %lld", (long long)t, chosen[t], (long long)V);
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+        FL_HIP(hipSetDevice(0));
+        struct Bufs { float *lg = 0; uint32_t *ch = 0; LogprobRec *recs = 0; LogprobCtl *ctl = 0; hipStream_t s = 0;
+                      ~Bufs() { (void)hipFree(lg); (void)hipFree(ch); (void)hipFree(recs); (void)hipFree(ctl); if (s) (void)hipStreamDestroy(s); } } B;
+        FL_HIP(hipStreamCreate(&B.s));
+        FL_HIP(hipMalloc((void **)&B.lg, (size_t)T * V * 4));
+        FL_HIP(hipMalloc((void **)&B.ch, (size_t)T * 4));
+        FL_HIP(hipMalloc((void **)&B.recs, (size_t)T * sizeof(LogprobRec)));
+        FL_HIP(hipMalloc((void **)&B.ctl, sizeof(LogprobCtl)));
+        FL_HIP(hipMemcpy(B.lg, logits, (size_t)T * V * 4, hipMemcpyHostToDevice));
+        FL_HIP(hipMemcpy(B.ch, chosen, (size_t)T * 4, hipMemcpyHostToDevice));
+        Launcher L; L.stream = B.s;
+        FL_TRY(launch_set_logprob_ctl(L, B.ctl, B.recs, (uint32_t)T, top_n));
+        LogprobSrc src;
+        src.ctl = B.ctl; src.chosen = B.ch;
+        std::vector<LogprobRec> host[2];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the gather's order in LDS differs from launch to launch, the result must not
+            host[rep].resize((size_t)T);
+            FL_HIP(hipMemsetAsync(B.recs, 0, (size_t)T * sizeof(LogprobRec), B.s));
+            FL_TRY(launch_token_logprobs(L, B.lg, V, (int)T, src, 0));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep].data(), B.recs, (size_t)T * sizeof(LogprobRec), hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0].data(), host[1].data(), (size_t)T * sizeof(LogprobRec))) FL_FAIL(FL_ERR_HIP, "token_logprobs: a repeated launch gave another result");
+        for (int64_t t = 0; t < T; t++) {
+            token_logprob[t] = host[0][(size_t)t].chosen;
+            for (int j = 0; j < top_n; j++) {
+                top_ids[t * top_n + j] = host[0][(size_t)t].ids[j];
+                top_logprobs[t * top_n + j] = host[0][(size_t)t].lps[j];
+            }
+        }
+        return FL_OK;
+    });
+}
+
 int fl_batch_create(fl_model *m, fl_cache *const *caches, size_t n, fl_batch **out) {
     return guarded([&]() -> int {
         if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null out");

@@ -14,7 +14,9 @@ Batch::~Batch() {
     (void)hipSetDevice(sh.device);
     (void)hipStreamSynchronize(sh.stream);
     if (graph) (void)hipGraphExecDestroy(graph);
+    if (graph_lp) (void)hipGraphExecDestroy(graph_lp);
     for (void *p : allocs) (void)hipFree(p);
+    if (host_lp) (void)hipHostFree(host_lp);
     if (host_tokens) (void)hipHostFree(host_tokens);
     if (host_states) (void)hipHostFree(host_states);
 }
@@ -124,6 +126,7 @@ int batch_replace(Batch *b, size_t slot, Cache *c) {
     const bool regraph = c->nsplit > b->max_nsplit || (b->per_seq && !b->plain);
     b->max_nsplit = std::max(b->max_nsplit, c->nsplit);
     if (regraph && b->graph) { (void)hipGraphExecDestroy(b->graph); b->graph = nullptr; }
+    if (regraph && b->graph_lp) { (void)hipGraphExecDestroy(b->graph_lp); b->graph_lp = nullptr; }
     return FL_OK;
 }
 
@@ -288,18 +291,29 @@ static int enqueue_batch_step_unfused(Batch *b) {
     return launch_select_advance_batch(L, b->logits, D.V, b->seqs_dev, B, 1);
 }
 
-static int batch_step(Batch *b) {
+// with_lp: the step with every sequence's log-prob records written behind token selection (one more launch of B workgroups), as
+// a second graph; `graph` is what it always was
+static int batch_step(Batch *b, bool with_lp = false) {
     Model *m = b->m;
     Shard &sh = m->shards[0];
     const bool graphable = m->use_graph && !m->profiling && !b->graph_failed;
-    return replay_or_capture({{sh.device, sh.stream, &b->graph}}, graphable, b->graph_failed, b->warm_steps, [b] { return enqueue_batch_step(b); });
+    if (!with_lp) return replay_or_capture({{sh.device, sh.stream, &b->graph}}, graphable, b->graph_failed, b->warm_steps, [b] { return enqueue_batch_step(b); });
+    return replay_or_capture({{sh.device, sh.stream, &b->graph_lp}}, graphable, b->graph_failed, b->warm_steps_lp, [b, m, &sh]() -> int {
+        FL_TRY(enqueue_batch_step(b));
+        Launcher L = make_launcher(m, sh);
+        LogprobSrc src;
+        src.seqs = b->seqs_dev; src.ctls = b->lp_ctls;
+        return launch_token_logprobs(L, b->logits, m->D.V, b->B, src, 1);
+    });
 }
 
 // The end of a batch call, per sequence: n_tokens of every cache's token buffer and its StepState come back through the pinned
-// buffers, the stream is waited for, and the error words of the collectives and of each sequence are looked at.
-static int batch_finish(Batch *b, size_t n_tokens) {
+// buffers, the stream is waited for, and the error words of the collectives and of each sequence are looked at.  with_lp: as many
+// log-prob records of every sequence too.
+static int batch_finish(Batch *b, size_t n_tokens, bool with_lp = false) {
     Shard &sh = b->m->shards[0];
     for (int i = 0; i < b->B; i++) {
+        if (with_lp) FL_HIP(hipMemcpyAsync(b->host_lp + (size_t)i * kBatchChunk, b->caches[i]->shards[0].lp_recs, n_tokens * sizeof(LogprobRec), hipMemcpyDeviceToHost, sh.stream));
         FL_HIP(hipMemcpyAsync(b->host_tokens + (size_t)i * kBatchChunk, b->caches[i]->shards[0].out_tokens, n_tokens * 4, hipMemcpyDeviceToHost, sh.stream));
         FL_HIP(hipMemcpyAsync(b->host_states + i, b->caches[i]->shards[0].st, sizeof(StepState), hipMemcpyDeviceToHost, sh.stream));
     }
@@ -328,9 +342,13 @@ int batch_decode(Batch *b, const uint32_t *first, const size_t *pos, size_t n_st
 
 // ... with every sequence's own EOS id and sampler (a request's temperature is its own: chat.rs:24-25; temperature < 1e-7 = ArgMax)
 int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, const int64_t *eos_each,
-                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out) {
+                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp_each) {
     if (!b || !first || !tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
     const int B = b->B;
+    if (lp_each) {
+        for (int i = 0; i < B; i++) FL_TRY(check_logprobs(lp_each + i, b->m->D.V));
+        if (b->m->tp > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "token log-probabilities do not run on a tensor-parallel group's batch (tp_size %d)", b->m->tp);
+    }
     for (int i = 0; i < B; i++) n_out[i] = 0;
     if (n_steps == 0) return FL_OK;
     FL_TRY(batch_check(b, pos, n_steps));
@@ -345,6 +363,21 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
     std::lock_guard<std::mutex> lock(m->mu);
     Shard &sh = m->shards[0];
     FL_HIP(hipSetDevice(sh.device));
+    if (lp_each) {
+        // every member's record buffer (a replaced slot's cache may not have one yet), the table the step's launch reads them from,
+        // and each sequence's top_n -- all ahead of the steps on the stream
+        if (!b->lp_ctls) FL_TRY(dev_alloc(b->allocs, (void **)&b->lp_ctls, sizeof(LogprobCtl *) * (size_t)B, nullptr));
+        if (!b->host_lp) FL_HIP(hipHostMalloc((void **)&b->host_lp, (size_t)B * kBatchChunk * sizeof(LogprobRec), hipHostMallocDefault));
+        std::vector<LogprobCtl *> ctls((size_t)B);
+        Launcher L = make_launcher(m, sh);
+        for (int i = 0; i < B; i++) {
+            FL_TRY(ensure_logprobs(m, b->caches[i]));
+            CacheShard &cs = b->caches[i]->shards[0];
+            ctls[(size_t)i] = cs.lp_ctl;
+            FL_TRY(launch_set_logprob_ctl(L, cs.lp_ctl, cs.lp_recs, (uint32_t)kOutTokensCap, lp_each[i].top_n));
+        }
+        FL_HIP(hipMemcpy(b->lp_ctls, ctls.data(), sizeof(LogprobCtl *) * (size_t)B, hipMemcpyHostToDevice));   // (synchronous: ctls is a stack vector)
+    }
     std::vector<uint32_t> tok(first, first + B);
     std::vector<char> finished(B, 0);
     std::vector<size_t> len0(B);
@@ -354,8 +387,8 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
         const size_t nb = std::min(n_steps - done, kBatchChunk);
         for (int i = 0; i < B; i++)
             FL_TRY(set_shard_state(m, sh, b->caches[i]->shards[0], tok[i], pos[i] + done, len0[i] + done, len0[i] + done, 0u, eoss[(size_t)i], samplers[(size_t)i], done == 0));
-        for (size_t s = 0; s < nb; s++) FL_TRY(batch_step(b));
-        FL_TRY(batch_finish(b, nb));
+        for (size_t s = 0; s < nb; s++) FL_TRY(batch_step(b, lp_each != nullptr));
+        FL_TRY(batch_finish(b, nb, lp_each != nullptr));
         bool all_finished = true;
         for (int i = 0; i < B; i++) {
             if (!finished[i]) {
@@ -367,6 +400,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
                         break;
                     }
                     tokens_out[(size_t)i * n_steps + done + s] = t;
+                    if (lp_each) scatter_logprobs(b->host_lp[(size_t)i * kBatchChunk + s], lp_each + i, done + s);
                     n_out[i] = done + s + 1;
                 }
                 if (!finished[i]) b->caches[i]->len = len0[i] + done + nb;

@@ -245,6 +245,13 @@ struct SampleState {
     uint32_t kept;
 };
 
+// Token log-probabilities (fl_*_lp): one record per decode step, written by token_logprobs_kernel behind the step's token selection.
+// ids / lps: the first top_n entries of the order "logit descending, lower index first"; the rest of a record is not written.
+constexpr int kLogprobsMaxTop = 20;          // FL_LOGPROBS_MAX_TOP
+struct LogprobRec { float chosen; uint32_t ids[kLogprobsMaxTop]; float lps[kLogprobsMaxTop]; };
+// ... and where a cache's records go: read from device memory by the kernel, so one captured graph serves every top_n
+struct LogprobCtl { LogprobRec *recs; uint32_t cap; int32_t top_n; };
+
 // acc += a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (gfx950 VOP2; hipcc has no selectable builtin for it)
 __device__ inline float dot2c_bf16(unsigned a, unsigned b, float acc) {
     asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));

@@ -367,6 +367,20 @@ int launch_select_advance(Launcher &L, const float *logits, int64_t V, StepState
 // (the ticket word is put back by the kernel itself)
 constexpr int kVerifyMaxRows = 16, kVerifyNacc = 16, kVerifyTicket = 17, kVerifyWords = 18;
 int launch_verify_select(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft /* [T-1] device */, uint32_t *out);
+// fl_*_lp: log-softmax (temperature 1, no mask) of `rows` logits rows [rows][V], one workgroup per row -- the chosen token's and the
+// first top_n of "logit descending, lower index first" -- into record `step - advance` of the row's LogprobCtl.  Who a row belongs to:
+//   st + ctl      one sequence (rows == 1): the token select_advance just left in st
+//   seqs + ctls   a batch: row b is sequence b (its SeqRef's StepState, ctls[b])
+//   chosen + ctl  fl_op_logprobs: row t's token is chosen[t], its record ctl->recs[t]
+struct LogprobSrc {
+    const StepState *st = nullptr;
+    const SeqRef *seqs = nullptr;
+    const LogprobCtl *ctl = nullptr;
+    const LogprobCtl *const *ctls = nullptr;
+    const uint32_t *chosen = nullptr;
+};
+int launch_token_logprobs(Launcher &L, const float *logits, int64_t V, int rows, const LogprobSrc &src, int advance);
+int launch_set_logprob_ctl(Launcher &L, LogprobCtl *ctl, LogprobRec *recs, uint32_t cap, int top_n);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

@@ -124,6 +124,7 @@ struct Model {
     int engine = -1;             // persistent decode engine (k_engine.hip): 0 off, 1 on, -1 automatic
     int fuse_oproj = 0;          // decode attention + o_proj in one launch (k_attn_oproj.hip): 0 never (default), 1 wherever it fits, -1 where it pays most
     StepState *host_state = nullptr;   // pinned: device step state read back for the error word
+    LogprobRec *host_lp = nullptr;     // pinned [kOutTokensCap]: a chunk's log-prob records (allocated at the model's first fl_*_lp call)
     std::vector<ProfRecord> prof;
     bool profiling = false;
     int64_t hbm_bytes = 0;
@@ -142,6 +143,10 @@ struct CacheShard {
     unsigned *heads_done = nullptr;      // [L][Hkv] fused attention+o_proj: split partials published per kv head since set_state
     float *ao_part = nullptr;            // ... and the partials: [Hs][ao_nsplit][d + 4] (o, m, l)
     hipGraphExec_t graph = nullptr;
+    // token log-probabilities (fl_*_lp): allocated at the cache's first such call, so a cache that never asks pays nothing
+    LogprobRec *lp_recs = nullptr;       // [kOutTokensCap] one record per step of a chunk
+    LogprobCtl *lp_ctl = nullptr;        // where token_logprobs_kernel finds them, and the call's top_n
+    hipGraphExec_t graph_lp = nullptr;   // the decode step with the log-prob launch behind token selection; `graph` never has it
     std::vector<void *> allocs;
 };
 
@@ -157,6 +162,7 @@ struct Cache {
     int ao_nsplit = 0, ao_waves = 4;   // ... with this many key splits per kv head, 32 * ao_waves keys per split and step
     int nsplit = 1;
     int warm_steps = 0;          // eager decode steps done (graph is captured after the first)
+    int warm_steps_lp = 0;       // ... and of the step with log-probs (graph_lp)
     bool graph_failed = false;
     std::vector<CacheShard> shards;
     ~Cache();
@@ -189,6 +195,12 @@ struct Batch {
     hipGraphExec_t graph = nullptr;
     bool graph_failed = false;
     int warm_steps = 0;
+    // fl_batch_decode_each_lp: the step with the log-prob launch behind token selection, the sequences' LogprobCtl pointers [B]
+    // (written at the start of every such call) and the pinned [B][kBatchChunk] records; allocated at the batch's first such call
+    hipGraphExec_t graph_lp = nullptr;
+    int warm_steps_lp = 0;
+    LogprobCtl **lp_ctls = nullptr;
+    LogprobRec *host_lp = nullptr;
     std::vector<void *> allocs;
     ~Batch();
 };
@@ -202,7 +214,7 @@ int batch_forward(Batch *b, const uint32_t *tokens, const size_t *pos, float *lo
 int batch_decode(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, int64_t eos,
                  const fl_sampler *sampling, uint32_t *tokens_out, size_t *n_out);
 int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, const int64_t *eos_each,
-                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out);
+                      const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp_each = nullptr);
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
                  const fl_parallel *par, const fl_model_options *opts, Model **out);
@@ -238,10 +250,19 @@ int oneshot(Model *m, Shard &sh, bool gather, const float *in, float *out, int64
 // off), <= 0: unknown.  FL_ERR_BAD_ARGUMENT: wrong struct_size, NaN top_p, negative top_k.
 int make_sampler(const fl_sampler *sampling, int64_t V, SampleState *out);
 // sampling == null: ArgMax
+// lp != null: the chosen tokens' (and top_n most likely tokens') log-probabilities too (fl_*_lp)
 int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float *logits_out, uint32_t *token_out,
-            const fl_sampler *sampling = nullptr);
+            const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr);
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
+// fl_logprobs: FL_ERR_BAD_ARGUMENT for null, a wrong struct_size, top_n outside 0..FL_LOGPROBS_MAX_TOP (or above V, where V > 0 is
+// known), a missing array, nonzero _reserved -- no device needed
+int check_logprobs(const fl_logprobs *lp, int64_t V);
+// a model that can report log-probs (FL_ERR_UNSUPPORTED under tensor parallelism), and the device / pinned buffers of one cache
+int logprobs_supported(const Model *m);
+int ensure_logprobs(Model *m, Cache *c);
+// record r of a chunk -> row `at` of the caller's arrays
+void scatter_logprobs(const LogprobRec &r, const fl_logprobs *lp, size_t at);
 
 // fl_cache_truncate / fl_forward_verify / fl_decode_lookup (speculative greedy decode)
 int cache_truncate(Cache *c, size_t len);

@@ -39,6 +39,7 @@ Cache::~Cache() {
         (void)hipSetDevice(m->shards[i].device);
         (void)hipStreamSynchronize(m->shards[i].stream);
         if (shards[i].graph) (void)hipGraphExecDestroy(shards[i].graph);
+        if (shards[i].graph_lp) (void)hipGraphExecDestroy(shards[i].graph_lp);
         for (void *p : shards[i].allocs) (void)hipFree(p);
     }
 }
@@ -655,12 +656,66 @@ static int enqueue_argmax(Model *m, Cache *c, int advance) {
     });
 }
 
+// ---- token log-probabilities (fl_*_lp)
+int check_logprobs(const fl_logprobs *lp, int64_t V) {
+    if (!lp) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_logprobs (lp)");
+    if (lp->struct_size != sizeof(fl_logprobs)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.struct_size is %u, expected %zu", lp->struct_size, sizeof(fl_logprobs));
+    if (lp->top_n < 0 || lp->top_n > FL_LOGPROBS_MAX_TOP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.top_n %d not in 0..%d", lp->top_n, FL_LOGPROBS_MAX_TOP);
+    if (!lp->token_logprob) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.token_logprob is null");
+    if (lp->top_n > 0 && !lp->top_ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.top_ids is null with top_n %d", lp->top_n);
+    if (lp->top_n > 0 && !lp->top_logprobs) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.top_logprobs is null with top_n %d", lp->top_n);
+    if (lp->_reserved[0] || lp->_reserved[1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs._reserved must be 0");
+    if (V > 0 && lp->top_n > V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logprobs.top_n %d exceeds the vocabulary %lld", lp->top_n, (long long)V);
+    return FL_OK;
+}
+
+int logprobs_supported(const Model *m) {
+    if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "token log-probabilities do not run under tensor parallelism (tp_size %d)", m->tp);
+    return FL_OK;
+}
+
+// the cache's record buffer and the model's pinned one, at the first call that asks (never inside a stream capture: the model is
+// locked, and captures begin and end under that lock)
+int ensure_logprobs(Model *m, Cache *c) {
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    FL_HIP(hipSetDevice(sh.device));
+    if (!m->host_lp) FL_HIP(hipHostMalloc((void **)&m->host_lp, kOutTokensCap * sizeof(LogprobRec), hipHostMallocDefault));
+    if (!cs.lp_recs) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.lp_recs, kOutTokensCap * sizeof(LogprobRec), nullptr));
+    if (!cs.lp_ctl) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.lp_ctl, sizeof(LogprobCtl), nullptr));
+    return FL_OK;
+}
+
+void scatter_logprobs(const LogprobRec &r, const fl_logprobs *lp, size_t at) {
+    lp->token_logprob[at] = r.chosen;
+    for (int j = 0; j < lp->top_n; j++) {
+        lp->top_ids[at * (size_t)lp->top_n + (size_t)j] = r.ids[j];
+        lp->top_logprobs[at * (size_t)lp->top_n + (size_t)j] = r.lps[j];
+    }
+}
+
+// this call's top_n and record buffer, on the stream ahead of its steps
+static int set_logprobs(Model *m, Cache *c, const fl_logprobs *lp) {
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    Launcher L = make_launcher(m, sh);
+    return launch_set_logprob_ctl(L, cs.lp_ctl, cs.lp_recs, (uint32_t)kOutTokensCap, lp->top_n);
+}
+
+// right behind enqueue_argmax on the same stream: record `step - advance` of the cache
+static int enqueue_logprobs(Model *m, Cache *c, int advance) {
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    Launcher L = make_launcher(m, sh);
+    LogprobSrc src;
+    src.st = cs.st; src.ctl = cs.lp_ctl;
+    return launch_token_logprobs(L, sh.logits_full, m->D.V, 1, src, advance);
+}
+
 // The end of a call: n_tokens of the cache's token buffer and its StepState come back through the pinned buffers, every shard's
-// stream is waited for, and the error word of the device-side waits and of the collectives is looked at.
-static int finish_call(Model *m, Cache *c, size_t n_tokens) {
+// stream is waited for, and the error word of the device-side waits and of the collectives is looked at.  n_lp: as many log-prob records too.
+static int finish_call(Model *m, Cache *c, size_t n_tokens, size_t n_lp = 0) {
     Shard &s0 = m->shards[0];
     FL_HIP(hipSetDevice(s0.device));
     if (n_tokens) FL_HIP(hipMemcpyAsync(m->host_tokens, c->shards[0].out_tokens, n_tokens * 4, hipMemcpyDeviceToHost, s0.stream));
+    if (n_lp) FL_HIP(hipMemcpyAsync(m->host_lp, c->shards[0].lp_recs, n_lp * sizeof(LogprobRec), hipMemcpyDeviceToHost, s0.stream));
     FL_HIP(hipMemcpyAsync(m->host_state, c->shards[0].st, sizeof(StepState), hipMemcpyDeviceToHost, s0.stream));
     FL_TRY(each_shard(m, c, [](Shard &sh, CacheShard &, Launcher &) -> int { FL_HIP(hipStreamSynchronize(sh.stream)); return FL_OK; }));
     if (m->host_state->error) FL_FAIL(FL_ERR_HIP, "device-side wait gave up (code 0x%x): decode kernels did not make progress", m->host_state->error);
@@ -707,7 +762,9 @@ int replay_or_capture(const std::vector<GraphSlot> &slots, bool graphable, bool 
 // Single-shard models replay it as a hipGraph (the ~11 launches per layer are launch-bound at
 // TinyLlama scale); captured lazily on the second step of a cache so that all lazy module /
 // attribute initialisation has already happened eagerly.
-static int decode_step(Model *m, Cache *c, int64_t len_hint) {
+// with_lp: the step with the log-prob launch behind token selection -- a second graph (graph_lp); `graph` is what it always was,
+// and a cache may alternate between the two kinds of call.
+static int decode_step(Model *m, Cache *c, int64_t len_hint, bool with_lp = false) {
     // Graphs: one shard per process (plain single GPU, or one rank of a multi-process TP group: RCCL collectives are
     // stream-ordered and capturable, every rank captures the same sequence); or all shards of a single-process group
     // whose collectives are one-shot (they synchronise through memory, so each shard's step is its own graph).
@@ -718,10 +775,12 @@ static int decode_step(Model *m, Cache *c, int64_t len_hint) {
                              m->D.h <= m->shards[0].pc.nmax && m->shards[0].Vs <= m->shards[0].pc.nmax;
     const bool graphable = m->use_graph && !m->profiling && (one_shard || local_group) && !c->graph_failed;
     std::vector<GraphSlot> slots;
-    for (size_t i = 0; i < ns && graphable; i++) slots.push_back({m->shards[i].device, m->shards[i].stream, &c->shards[i].graph});
-    return replay_or_capture(slots, graphable, c->graph_failed, c->warm_steps, [&]() -> int {
+    for (size_t i = 0; i < ns && graphable; i++)
+        slots.push_back({m->shards[i].device, m->shards[i].stream, with_lp ? &c->shards[i].graph_lp : &c->shards[i].graph});
+    return replay_or_capture(slots, graphable, c->graph_failed, with_lp ? c->warm_steps_lp : c->warm_steps, [&]() -> int {
         FL_TRY(enqueue_forward(m, c, false, 1, false, len_hint));
-        return enqueue_argmax(m, c, 1);
+        FL_TRY(enqueue_argmax(m, c, 1));
+        return with_lp ? enqueue_logprobs(m, c, 1) : FL_OK;
     });
 }
 
@@ -740,17 +799,19 @@ int check_token(const Model *m, uint32_t id, const char *what) {
 }
 
 int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float *logits_out, uint32_t *token_out,
-            const fl_sampler *sampling) {
+            const fl_sampler *sampling, const fl_logprobs *lp) {
     FL_TRY(check_call(m, c, T, pos));
     debug_inject("forward");
     SampleState sampler;
     FL_TRY(make_sampler(sampling, m->D.V, &sampler));
     if (!ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null ids");
     for (size_t t = 0; t < T; t++) FL_TRY(check_token(m, ids[t], "token"));
+    if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
     std::lock_guard<std::mutex> lock(m->mu);
+    if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
     if (T == 1) {
         FL_TRY(set_state(m, c, ids[0], pos, c->len, 0, -1, (size_t)-1, &sampler));
-        FL_TRY(decode_step(m, c, (int64_t)c->len));
+        FL_TRY(decode_step(m, c, (int64_t)c->len, lp != nullptr));
         c->len += 1;
     } else {
         const int64_t chunk_max = tune(TK_PREFILL_CHUNK);
@@ -775,18 +836,20 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
             done += (size_t)Tc;
         }
         FL_TRY(enqueue_argmax(m, c, 0));
+        if (lp) FL_TRY(enqueue_logprobs(m, c, 0));
     }
     Shard &s0 = m->shards[0];
     FL_HIP(hipSetDevice(s0.device));
     if (logits_out) FL_HIP(hipMemcpyAsync(m->host_logits, s0.logits_full, (size_t)m->D.V * 4, hipMemcpyDeviceToHost, s0.stream));
-    FL_TRY(finish_call(m, c, token_out ? 1 : 0));
+    FL_TRY(finish_call(m, c, token_out ? 1 : 0, lp ? 1 : 0));
     if (logits_out) memcpy(logits_out, m->host_logits, (size_t)m->D.V * 4);
     if (token_out) *token_out = m->host_tokens[0];
+    if (lp) scatter_logprobs(m->host_lp[0], lp, 0);
     return FL_OK;
 }
 
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling) {
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling, const fl_logprobs *lp) {
     if (n_out) *n_out = 0;
     if (n_steps == 0) return FL_OK;
     FL_TRY(check_call(m, c, n_steps, pos));
@@ -794,7 +857,9 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
     FL_TRY(make_sampler(sampling, m->D.V, &sampler));
     if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null tokens_out");
     FL_TRY(check_token(m, first, "token"));
+    if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
     std::lock_guard<std::mutex> lock(m->mu);
+    if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
     size_t done = 0;
     uint32_t tok = first;
     // With an EOS id the host looks at the tokens between chunks of 16, 32, ... 256 steps: the reference's loop breaks at
@@ -805,8 +870,8 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
         const size_t nb = std::min(n_steps - done, chunk);
         if (eos >= 0) chunk = std::min<size_t>(chunk * 2, 256);
         FL_TRY(set_state(m, c, tok, pos + done, c->len, 0, eos, (size_t)-1, done == 0 ? &sampler : nullptr));
-        for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i)));
-        FL_TRY(finish_call(m, c, nb));
+        for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i), lp != nullptr));
+        FL_TRY(finish_call(m, c, nb, lp ? nb : 0));
         for (size_t i = 0; i < nb; i++) {
             const uint32_t t = m->host_tokens[i];
             if (eos >= 0 && (int64_t)t == eos) {
@@ -816,6 +881,7 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
                 return FL_OK;
             }
             tokens_out[done + i] = t;
+            if (lp) scatter_logprobs(m->host_lp[i], lp, done + i);
         }
         c->len += nb;
         tok = m->host_tokens[nb - 1];

@@ -340,6 +340,7 @@ struct LlamaWithConfig {
     // the handles and the position bookkeeping the prompt-lookup loop needs (Model<M>::generate_ids with LookupOptions)
     fl_model *raw_model() const { return model->m; }
     fl_cache *raw_cache(Cache &cache) const { return cache.inner->c; }
+    void prepare(Cache &) const {}            // (the cache object exists from initialize_cache on)
     size_t rope_offset(size_t pos, const Cache &) const { return pos; }
     void advance(Cache &, size_t) const {}
     static const char *get_family() { return "Llama"; }                                             // llama.rs:153
@@ -409,6 +410,14 @@ struct CounterFamily {
     // of n rows stands for n calls of `forward`, so the per-call counter (quirk C.1) advances by n and row t runs at counter + t
     fl_model *raw_model() const { return model->m; }
     fl_cache *raw_cache(Cache &cache) const { return cache.kv->c; }
+    // what `forward` does ahead of its run, for a caller that makes the prompt's call itself (generate_ids with log-probs)
+    void prepare(Cache &cache) const {
+        if (!cache.kv) {
+            cache.kv = std::make_shared<detail::CacheHandle>();
+            check(fl_cache_create(model->m, detail::default_max_seq(model->m), &cache.kv->c), "Failed to initialize model cache");
+        }
+        if (cache.seqlen_offset == 0) fl_cache_reset(cache.kv->c);
+    }
     size_t rope_offset(size_t pos, const Cache &cache) const { return pos_mode() == PosMode::Reference ? cache.seqlen_offset : pos; }
     void advance(Cache &cache, size_t calls) const { cache.seqlen_offset += calls; }
 };
@@ -598,6 +607,16 @@ struct SamplingOptions {
     }
 };
 
+// Per emitted token its log-probability and, row-major [n][top_n], the ids and log-probabilities of the top_n most likely tokens of
+// its step (generate_ids with top_logprobs): log-softmax of the model's own logits -- temperature 1, nothing masked -- computed on the
+// device (fl_*_lp), whatever sampler chose the token.  New capability; the reference reports none.
+struct TokenLogprobs {
+    std::vector<float> token;
+    std::vector<uint32_t> top_ids;
+    std::vector<float> top;
+    int top_n = 0;
+};
+
 // Prompt-lookup drafting for greedy requests (fl_lookup): the continuation that followed the most recent earlier occurrence of the
 // current n-gram is verified in one forward (fl_forward_verify).  New capability; the tokens are those of the plain greedy loop.
 struct LookupOptions {
@@ -650,6 +669,58 @@ struct Model {                                // mod.rs:342-361
             logits = model.forward(next_input, pos, cache); forwards++;    // mod.rs:446-451 (also after the last token)
             pos += 1;                                                      // mod.rs:452
         }
+        return output_ids;
+    }
+
+    // ... with log-probabilities (0 <= top_logprobs <= FL_LOGPROBS_MAX_TOP): token selection stays on the device -- the first token
+    // from fl_forward_sample_lp on the prompt, the other max_tokens - 1 from fl_decode_sample_lp -- so the ids are those of the
+    // overload above (the device sampler is the host LogitsProcessor bit for bit) and `out` holds one record per id.  `forwards`
+    // counts the prompt's forward and the decode steps; the reference's wasted forward behind the last token (C.5) is not run.
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, int top_logprobs, TokenLogprobs *out) {
+        if (!out) throw Error(FL_ERR_BAD_ARGUMENT, "generate_ids: null TokenLogprobs");
+        if (top_logprobs < 0 || top_logprobs > FL_LOGPROBS_MAX_TOP) throw Error(FL_ERR_BAD_ARGUMENT, "generate_ids: top_logprobs out of range");
+        cache = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        *out = TokenLogprobs{};
+        out->top_n = top_logprobs;
+        forwards = 0;
+        std::vector<uint32_t> output_ids;
+        if (max_tokens == 0) { model.forward(Tensor::from_ids(prompt), 0, cache); forwards++; return output_ids; }
+        const size_t w = (size_t)top_logprobs;
+        output_ids.assign(max_tokens, 0);
+        out->token.assign(max_tokens, 0.f);
+        out->top_ids.assign(max_tokens * w, 0);
+        out->top.assign(max_tokens * w, 0.f);
+        auto lp_at = [&](size_t row) {
+            fl_logprobs lp{};
+            lp.struct_size = (uint32_t)sizeof(fl_logprobs);
+            lp.top_n = top_logprobs;
+            lp.token_logprob = out->token.data() + row;
+            lp.top_ids = w ? out->top_ids.data() + row * w : nullptr;
+            lp.top_logprobs = w ? out->top.data() + row * w : nullptr;
+            return lp;
+        };
+        model.prepare(cache);
+        fl_cache *c = model.raw_cache(cache);
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        const fl_logprobs lp0 = lp_at(0);
+        check(fl_forward_sample_lp(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0], &lp0),
+              "Model forward pass failed");
+        model.advance(cache, 1); forwards++;
+        size_t n = 0;
+        const bool ended = eos && output_ids[0] == *eos;
+        if (!ended && max_tokens > 1) {
+            const fl_sampler s1 = opt.to_ffi((double)temperature, 1);
+            const fl_logprobs lp1 = lp_at(1);
+            const size_t len0 = fl_cache_len(c);
+            check(fl_decode_sample_lp(model.raw_model(), c, output_ids[0], model.rope_offset(prompt.size(), cache), max_tokens - 1,
+                                      eos ? (int64_t)*eos : -1, &s1, output_ids.data() + 1, &n, &lp1), "Model forward pass failed");
+            model.advance(cache, fl_cache_len(c) - len0);
+            forwards += fl_cache_len(c) - len0;
+        }
+        const size_t total = ended ? 0 : 1 + n;
+        output_ids.resize(total); out->token.resize(total); out->top_ids.resize(total * w); out->top.resize(total * w);
         return output_ids;
     }
 

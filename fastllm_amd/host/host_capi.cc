@@ -149,6 +149,31 @@ int flh_generate(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, 
     });
 }
 
+// ... with log-probabilities (generate_ids with top_logprobs): token_logprob [max_tokens], top_ids / top_logprobs [max_tokens][top_n]
+// (may be null when top_n == 0); top_p <= 0 and top_k <= 0: off
+int flh_generate_logprobs(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, double top_p,
+                          int64_t top_k, int top_n, uint32_t *out_tokens, size_t *n_out, float *token_logprob, uint32_t *top_ids,
+                          float *top_logprobs, size_t *forwards) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        std::vector<uint32_t> p(prompt, prompt + T), r;
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        SamplingOptions opt;
+        if (top_p > 0) opt.top_p = top_p;
+        if (top_k > 0) opt.top_k = (size_t)top_k;
+        TokenLogprobs lp;
+        size_t fw = 0;
+        if (h->llama) { r = h->llama->generate_ids(p, max_tokens, temperature, e, opt, top_n, &lp); fw = h->llama->forwards; }
+        else if (h->mistral) { r = h->mistral->generate_ids(p, max_tokens, temperature, e, opt, top_n, &lp); fw = h->mistral->forwards; }
+        else { r = h->qwen->generate_ids(p, max_tokens, temperature, e, opt, top_n, &lp); fw = h->qwen->forwards; }
+        for (size_t i = 0; i < r.size(); i++) { out_tokens[i] = r[i]; token_logprob[i] = lp.token[i]; }
+        for (size_t i = 0; i < lp.top_ids.size(); i++) { top_ids[i] = lp.top_ids[i]; top_logprobs[i] = lp.top[i]; }
+        *n_out = r.size();
+        if (forwards) *forwards = fw;
+        return 0;
+    });
+}
+
 // ... a greedy request with prompt-lookup drafts (LookupOptions); stream != 0: through generate_stream_ids' lookup overload.
 // stats (optional): steps, drafted, accepted of the non-stream form
 int flh_generate_lookup(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, int max_draft,

@@ -383,6 +383,46 @@ int  fl_batch_decode_each(fl_batch *b, const uint32_t *first_tokens, const size_
 int  fl_batch_decode_each_ex(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                              const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out);
 
+/* ---- token log-probabilities: the chosen token's, and the N most likely tokens', inside the device decode loop ------------------
+ * New capability (the reference reports none).  What an OpenAI-compatible server is asked for as `logprobs` / `top_logprobs`.  The
+ * values are computed by one more launch behind each step's token selection, inside the same replayed graph; per step 4 + 160 bytes
+ * come back with the token ids at the end of a chunk.  A call without log-probs launches exactly what it launched before.
+ *
+ * For a step whose fp32 logits row is x[0..V) (what fl_forward returns for that step), m = max_j x[j]:
+ *     lp[i] = (x[i] - m) - log(sum_j exp(x[j] - m))                      (natural log)
+ * THE DISTRIBUTION IS THE MODEL'S OWN: temperature 1, no top-p / top-k mask.  It does not depend on the sampler that chose the token:
+ * a greedy request and a temperature = 0.7, top_p = 0.9 request report the same lp for the same row.
+ *   token_logprob[s] = lp[token s], the id the step's selection produced (ArgMax or sampled).
+ *   top_ids[s][0..top_n), top_logprobs[s][..]: the first top_n ids of the order "logit descending, LOWER index first among equal
+ *       values" (the stable order of fl_sampler above), each with its lp.  ArgMax keeps the LAST maximal index, so on an exact tie of
+ *       the maximum the chosen token can differ from top_ids[s][0], as it does between ArgMax and top_k = 1.
+ * Arithmetic: x[j] - m in fp32, precise expf, the sum in fp64, then log and the final subtraction.  -inf entries contribute 0 and have
+ * lp = -inf.  A row without a finite maximum, or with NaN, gives unspecified values (never a fault; every reported id is < V).
+ * EOS as in fl_decode_*: the EOS token is not emitted; only entries [0, *n_out) of the arrays are defined.
+ * The tokens, the cache state and the sampler's draw count after an _lp call are exactly those of the matching _ex call.
+ * FL_ERR_BAD_ARGUMENT (before the device is probed): null lp, wrong struct_size, top_n outside 0 .. FL_LOGPROBS_MAX_TOP or above the
+ * vocabulary, a missing array, nonzero _reserved.  FL_ERR_UNSUPPORTED (before the device is touched): tp_size > 1 in any mode, a
+ * batch on a tensor-parallel group.  Any dtype and weight format otherwise.
+ * Memory: a cache's FIRST log-prob call allocates its record buffer (4096 records of 164 bytes, 656 KB of HBM, freed with the cache);
+ * the model's first one 656 KB of pinned host memory.  Caches that never ask pay nothing. */
+#define FL_LOGPROBS_MAX_TOP 20
+typedef struct fl_logprobs {
+    uint32_t  struct_size;      /* sizeof(fl_logprobs), FL_ERR_BAD_ARGUMENT otherwise */
+    int32_t   top_n;            /* 0 .. FL_LOGPROBS_MAX_TOP */
+    float    *token_logprob;    /* host [n]            : required */
+    uint32_t *top_ids;          /* host [n][top_n]     : required iff top_n > 0 */
+    float    *top_logprobs;     /* host [n][top_n]     : required iff top_n > 0 */
+    int64_t   _reserved[2];     /* 0 */
+} fl_logprobs;
+/* fl_forward_sample_ex / fl_decode_sample_ex / fl_batch_decode_each_ex with log-probs.  sampler(s) NULL: ArgMax.
+ * n = 1 / n_steps / n_steps rows per sequence (lp[i] is sequence i's, with its own top_n and arrays). */
+int fl_forward_sample_lp(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_sampler *sampler,
+                         uint32_t *token_out, const fl_logprobs *lp);
+int fl_decode_sample_lp(fl_model *m, fl_cache *c, uint32_t first_token, size_t pos, size_t n_steps, int64_t eos,
+                        const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp);
+int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
+                            const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp /* [n_seq] */);
+
 int fl_synchronize(fl_model *m);
 
 /* ---- embeddings: the BERT / MiniLM encoder forward --------------------------------------------------------------------------------
@@ -515,6 +555,12 @@ int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, i
  * draft may be NULL when T == 1. */
 int fl_op_verify_select(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *draft /* [T-1] */,
                         uint32_t *argmax_out /* [T] */, int64_t *n_accepted_out);
+
+/* The log-prob kernel of the fl_*_lp calls alone, on host logits (unit tests, micro-benchmarks): row t's chosen token is chosen[t].
+ * 1 <= T <= 64, 0 <= top_n <= min(FL_LOGPROBS_MAX_TOP, V), V <= 1 << 24, chosen[t] < V (FL_ERR_BAD_ARGUMENT otherwise, before the
+ * device is probed); top_ids / top_logprobs may be NULL when top_n == 0.  Launched twice: FL_ERR_HIP if the two results differ. */
+int fl_op_logprobs(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *chosen /* [T] */, int32_t top_n,
+                   float *token_logprob /* [T] */, uint32_t *top_ids /* [T][top_n] or NULL */, float *top_logprobs /* [T][top_n] or NULL */);
 
 /* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
  * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read

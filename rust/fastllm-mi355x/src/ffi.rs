@@ -10,6 +10,7 @@ pub const FL_UNIQUE_ID_BYTES: usize = 128;
 pub const FL_IPC_HANDLE_BYTES: usize = 64;
 /// Most drafted ids one `fl_forward_verify` call scores (T = n_draft + 1 <= 16).
 pub const FL_VERIFY_MAX_DRAFT: usize = 15;
+pub const FL_LOGPROBS_MAX_TOP: usize = 20;
 
 // fl_status
 pub const FL_OK: c_int = 0;
@@ -136,6 +137,20 @@ pub struct fl_sampler {
     pub top_p: f64,
     pub seed: u64,
     pub draws_done: u64,
+    pub _reserved: [i64; 2],
+}
+
+/// `fl_logprobs`: where the log-probabilities of an `fl_*_lp` call go -- the chosen token's per step and, with `top_n > 0`, the
+/// `top_n` most likely tokens' ids and values (host arrays of n and n x top_n entries); `struct_size` is `size_of::<fl_logprobs>()`.
+/// The distribution is the model's own (temperature 1, nothing masked), whatever sampler chose the token.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_logprobs {
+    pub struct_size: u32,
+    pub top_n: i32,
+    pub token_logprob: *mut f32,
+    pub top_ids: *mut u32,
+    pub top_logprobs: *mut f32,
     pub _reserved: [i64; 2],
 }
 
@@ -366,6 +381,52 @@ extern "C" {
         samplers: *const fl_sampler,
         tokens_out: *mut u32,
         n_out: *mut usize,
+    ) -> c_int;
+
+    /// The sampled entry points with log-probabilities (`sampler` null: ArgMax); tokens, cache state and draw count are those of the
+    /// `_ex` calls.
+    pub fn fl_forward_sample_lp(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        ids: *const u32,
+        t: usize,
+        pos: usize,
+        sampler: *const fl_sampler,
+        token_out: *mut u32,
+        lp: *const fl_logprobs,
+    ) -> c_int;
+    pub fn fl_decode_sample_lp(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: i64,
+        sampler: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        lp: *const fl_logprobs,
+    ) -> c_int;
+    pub fn fl_batch_decode_each_lp(
+        b: *mut fl_batch,
+        first_tokens: *const u32,
+        pos: *const usize,
+        n_steps: usize,
+        eos: *const i64,
+        samplers: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        lp: *const fl_logprobs,
+    ) -> c_int;
+    pub fn fl_op_logprobs(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        chosen: *const u32,
+        top_n: i32,
+        token_logprob: *mut f32,
+        top_ids: *mut u32,
+        top_logprobs: *mut f32,
     ) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;

@@ -113,6 +113,17 @@ impl Sampling {
     }
 }
 
+/// What `Model::decode_sample_logprobs` returns: the emitted tokens, each one's log-probability, and row-major `[n][top_n]` ids and
+/// log-probabilities of the most likely tokens of every step.
+#[derive(Clone, Debug, Default)]
+pub struct TokenLogprobs {
+    pub tokens: Vec<u32>,
+    pub token_logprob: Vec<f32>,
+    pub top_ids: Vec<u32>,
+    pub top_logprobs: Vec<f32>,
+    pub top_n: usize,
+}
+
 /// LogitsProcessor::from_sampling(seed, Sampling::TopP / TopK / TopKThenTopP) on the device (`fl_sampler`).  `top_p` outside
 /// (0, 1) and `top_k` 0 are "off"; both off is `Sampling::All`.  The kept set is a prefix of the order by probability
 /// descending, the lower index first among equals; `top_k = 1` therefore keeps the LOWEST maximal index while ArgMax
@@ -320,6 +331,35 @@ impl Model {
         })?;
         toks.truncate(n);
         Ok(toks)
+    }
+
+    /// `decode_ex` with log-probabilities: per emitted token its log-probability under the model's own distribution (temperature 1,
+    /// nothing masked -- whatever `s` is) and, with `top_n > 0` (at most `FL_LOGPROBS_MAX_TOP`), the `top_n` most likely ids and
+    /// theirs, in the order "logit descending, lower index first".  The tokens are those of `decode_ex`.
+    pub fn decode_sample_logprobs(&self, cache: &mut Cache, first_token: u32, pos: usize, n_steps: usize, eos: Option<u32>, s: Sampler,
+                                  top_n: usize) -> Result<TokenLogprobs> {
+        let mut toks = vec![0u32; n_steps.max(1)];
+        let mut token = vec![0f32; n_steps.max(1)];
+        let mut top_ids = vec![0u32; (n_steps * top_n).max(1)];
+        let mut top = vec![0f32; (n_steps * top_n).max(1)];
+        let mut n = 0usize;
+        let sp = s.to_ffi();
+        let lp = ffi::fl_logprobs {
+            struct_size: std::mem::size_of::<ffi::fl_logprobs>() as u32,
+            top_n: top_n as i32,
+            token_logprob: token.as_mut_ptr(),
+            top_ids: if top_n > 0 { top_ids.as_mut_ptr() } else { ptr::null_mut() },
+            top_logprobs: if top_n > 0 { top.as_mut_ptr() } else { ptr::null_mut() },
+            _reserved: [0; 2],
+        };
+        check(unsafe {
+            ffi::fl_decode_sample_lp(self.raw, cache.raw, first_token, pos, n_steps, eos.map(|e| e as i64).unwrap_or(-1), &sp, toks.as_mut_ptr(), &mut n, &lp)
+        })?;
+        toks.truncate(n);
+        token.truncate(n);
+        top_ids.truncate(n * top_n);
+        top.truncate(n * top_n);
+        Ok(TokenLogprobs { tokens: toks, token_logprob: token, top_ids, top_logprobs: top, top_n })
     }
 
     /// The loop body of `Model<M>::generate` (mod.rs:411-453) kept on the device; returns the tokens sampled after each
