@@ -1,0 +1,567 @@
+// api_ops.hip -- the fl_op_* entry points: one kernel (or one launch sequence) on host arrays, for the tests and tools/.  Each is its
+// argument checks, then an OpScope (device 0, a stream, the device buffers), the launches, and the download of the result.
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "api_internal.h"
+#include "encoder.h"
+
+using namespace fl;
+
+namespace {
+
+// What an op body runs in: device 0, a stream of its own, every device allocation made through it and the event pair of a timed run.
+// Leaving the scope -- on an error return too -- waits for the stream before anything it may still be using is freed.
+struct OpScope {
+    hipStream_t s = 0; hipEvent_t e0 = 0, e1 = 0;
+    std::vector<void *> p;
+    Launcher L;
+    int begin() { FL_TRY(require_device()); FL_HIP(hipSetDevice(0)); FL_HIP(hipStreamCreate(&s)); L.stream = s; return FL_OK; }
+    ~OpScope() {
+        // the split-K workspaces the GEMMs keep per stream go before the stream does (no-ops for a stream they never saw)
+        if (s) { (void)hipStreamSynchronize(s); gemm_8p_release_stream(s); gemm_h4_release_stream(s); }
+        for (void *x : p) (void)hipFree(x);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (s) (void)hipStreamDestroy(s);
+    }
+    template <typename T> int alloc(T **out, size_t bytes) { *out = nullptr; FL_HIP(hipMalloc((void **)out, bytes ? bytes : 4)); p.push_back(*out); return FL_OK; }
+    template <typename T> int upload(T **out, const void *src, size_t bytes) { FL_TRY(alloc(out, bytes)); FL_HIP(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice)); return FL_OK; }
+};
+
+// The launches of an op that can be timed.  Always: run(0) once and a synchronise.  With iters > 0 and an ms_out, then: one warming
+// launch per copy, and `iters` launches between two events; *ms_out = ms per launch.
+// The timed launches rotate over `ncopy` copies of the op's working set (`bytes` each; copy 0 is the op's own, make(c) adds copy
+// c >= 1, run(c) launches on copy c) that together exceed the 256 MiB Infinity Cache: in the forward pass a projection's weights
+// always come from HBM, and a back-to-back replay on ONE copy would read them from the cache.  op_hot = 1: one copy (L2 + Infinity
+// Cache); n > 1: n copies (past the L2s, inside the Infinity Cache when n x bytes < 256 MiB).
+template <typename Make, typename Run>
+int op_run(OpScope &B, size_t bytes, int iters, double *ms_out, Make make, Run run) {
+    const bool timed = iters > 0 && ms_out;
+    const int hot = tune(TK_OP_HOT);
+    const int ncopy = !timed ? 1 : hot > 0 ? hot : (int)std::min<size_t>(24, std::max<size_t>(1, (640u << 20) / bytes + 1));
+    for (int c = 1; c < ncopy; c++) FL_TRY(make(c));
+    FL_TRY(run(0));
+    FL_HIP(hipStreamSynchronize(B.s));
+    if (!timed) return FL_OK;
+    for (int c = 0; c < ncopy; c++) FL_TRY(run(c));   // warm
+    FL_HIP(hipStreamSynchronize(B.s));
+    FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+    FL_HIP(hipEventRecord(B.e0, B.s));
+    for (int i = 0; i < iters; i++) FL_TRY(run(i % ncopy));
+    FL_HIP(hipEventRecord(B.e1, B.s));
+    FL_HIP(hipEventSynchronize(B.e1));
+    float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+    *ms_out = ms / iters;
+    return FL_OK;
+}
+
+// a launch's output, [rows][pitch] elements of `dtype` on the device: the first `cols` of every row, widened to fp32, to out [rows][cols]
+int op_download(float *out, const void *dev, size_t rows, size_t cols, size_t pitch, int32_t dtype) {
+    if (dtype != FL_DTYPE_BF16 && cols == pitch) { FL_HIP(hipMemcpy(out, dev, rows * cols * 4, hipMemcpyDeviceToHost)); return FL_OK; }
+    const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+    std::vector<unsigned char> tmp(rows * pitch * es);
+    FL_HIP(hipMemcpy(tmp.data(), dev, tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; r++)
+        for (size_t j = 0; j < cols; j++) {
+            const size_t idx = r * pitch + j;
+            out[r * cols + j] = es == 2 ? bf16_bits_to_float(reinterpret_cast<bf16_t *>(tmp.data())[idx]) : reinterpret_cast<float *>(tmp.data())[idx];
+        }
+    return FL_OK;
+}
+int op_download(float *out, const void *dev, size_t n, int32_t dtype) { return op_download(out, dev, 1, n, n, dtype); }
+
+// ---- the attention ops: the launches on caches built here in the model's layout -------------------------------------------------
+
+// One sequence's K and V as cache_create lays them out: K [L][Hkv][sa][d]; V the same, or transposed [L][Hkv][d][sa] for the MFMA
+// kernels.  Host rows [L][rows][Hkv*d]; every position >= rows holds `pad`.  E: the element's bit pattern (uint16_t / uint32_t).
+template <typename E>
+void attn_op_cache(std::vector<E> &kc, std::vector<E> &vc, const void *k, const void *v, int64_t L, int64_t rows, int64_t Hkv, int64_t sa,
+                   int64_t d, bool v_transposed, E pad) {
+    kc.assign((size_t)(L * Hkv * sa * d), pad); vc.assign((size_t)(L * Hkv * sa * d), pad);
+    const E *kh = reinterpret_cast<const E *>(k), *vh = reinterpret_cast<const E *>(v);
+    for (int64_t l = 0; l < L; l++)
+        for (int64_t s = 0; s < rows; s++)
+            for (int64_t h = 0; h < Hkv; h++)
+                for (int64_t j = 0; j < d; j++) {
+                    const size_t src = (size_t)(((l * rows + s) * Hkv + h) * d + j), head = (size_t)((l * Hkv + h) * sa * d);
+                    kc[head + (size_t)(s * d + j)] = kh[src];
+                    vc[head + (size_t)(v_transposed ? j * sa + s : s * d + j)] = vh[src];
+                }
+}
+
+int attn_op_upload_cache(OpScope &B, void **kd, void **vd, int32_t dtype, const void *k, const void *v, int64_t L, int64_t rows, int64_t Hkv,
+                         int64_t sa, int64_t d, bool v_transposed, float pad_value) {
+    if (dtype == FL_DTYPE_BF16) {
+        std::vector<uint16_t> kc, vc;
+        attn_op_cache<uint16_t>(kc, vc, k, v, L, rows, Hkv, sa, d, v_transposed, float_to_bf16_bits_host(pad_value));
+        FL_TRY(B.upload(kd, kc.data(), kc.size() * 2)); FL_TRY(B.upload(vd, vc.data(), vc.size() * 2));
+    } else {
+        union { float f; uint32_t u; } pv; pv.f = pad_value;
+        std::vector<uint32_t> kc, vc;
+        attn_op_cache<uint32_t>(kc, vc, k, v, L, rows, Hkv, sa, d, v_transposed, pv.u);
+        FL_TRY(B.upload(kd, kc.data(), kc.size() * 4)); FL_TRY(B.upload(vd, vc.data(), vc.size() * 4));
+    }
+    return FL_OK;
+}
+
+// the split scratch of one cache, sized as cache_create sizes it
+int attn_op_scratch(OpScope &B, float **pm, float **pl, float **po, unsigned **cnt, int64_t H, int64_t d, int nsplit) {
+    FL_TRY(B.alloc(pm, (size_t)H * nsplit * 4)); FL_TRY(B.alloc(pl, (size_t)H * nsplit * 4));
+    FL_TRY(B.alloc(po, (size_t)H * nsplit * d * 4)); FL_TRY(B.alloc(cnt, (size_t)H * 4));
+    FL_HIP(hipMemset(*cnt, 0, (size_t)H * 4));
+    return FL_OK;
+}
+
+int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, int64_t d) {
+    if ((dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) || layout < 0 || layout > 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype: bf16 or f32; layout: 0 plain, 1 MFMA");
+    if (H < 1 || Hkv < 1 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head counts (H a multiple of Hkv)");
+    if (d != 64 && d != 128) FL_FAIL(FL_ERR_UNSUPPORTED, "attention: head_dim %lld not supported (64 or 128)", (long long)d);
+    if (layout == 1 && !attn_mfma_supported(dtype, H, Hkv, d)) FL_FAIL(FL_ERR_UNSUPPORTED, "MFMA attention: bf16, head_dim 64 / 128, at most 8 query heads per kv head");
+    return FL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fl_op_verify_select(const float *logits, int64_t T, int64_t V, const uint32_t *draft, uint32_t *argmax_out, int64_t *n_accepted_out) {
+    return guarded([&]() -> int {
+        if (!logits || !argmax_out || !n_accepted_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || T > kVerifyMaxRows || V <= 0 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size (1 <= T <= %d)", kVerifyMaxRows);
+        if (T > 1 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null draft");
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg; uint32_t *dr, *od;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.alloc(&dr, (size_t)kVerifyMaxRows * 4));
+        FL_TRY(B.alloc(&od, (size_t)kVerifyWords * 4));
+        if (T > 1) FL_HIP(hipMemcpy(dr, draft, (size_t)(T - 1) * 4, hipMemcpyHostToDevice));
+        FL_HIP(hipMemset(od, 0, (size_t)kVerifyWords * 4));
+        uint32_t host[2][kVerifyWords];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the second launch meets the ticket word the first one put back
+            FL_TRY(launch_verify_select(B.L, lg, V, (int)T, dr, od));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep], od, sizeof host[rep], hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0], host[1], sizeof host[0]) || host[1][kVerifyTicket] != 0)
+            FL_FAIL(FL_ERR_HIP, "verify_select: a repeated launch gave another result (ticket %u)", host[1][kVerifyTicket]);
+        for (int64_t t = 0; t < T; t++) argmax_out[t] = host[0][t];
+        *n_accepted_out = (int64_t)host[0][kVerifyNacc];
+        return FL_OK;
+    });
+}
+
+int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *chosen, int32_t top_n, float *token_logprob,
+                   uint32_t *top_ids, float *top_logprobs) {
+    return guarded([&]() -> int {
+        if (!logits || !chosen || !token_logprob) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: null logits, chosen or token_logprob");
+        if (T < 1 || T > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: T %lld not in 1..64", (long long)T);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: V %lld not in 1..2^24", (long long)V);
+        if (top_n < 0 || top_n > FL_LOGPROBS_MAX_TOP || top_n > V)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: top_n %d not in 0..min(%d, V = %lld)", top_n, FL_LOGPROBS_MAX_TOP, (long long)V);
+        if (top_n > 0 && (!top_ids || !top_logprobs)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: null top_ids or top_logprobs with top_n %d", top_n);
+        for (int64_t t = 0; t < T; t++)
+            if ((int64_t)chosen[t] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logprobs: chosen[%lld] = %u is not below V = %lld", (long long)t, chosen[t], (long long)V);
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg; uint32_t *ch; LogprobRec *recs; LogprobCtl *ctl;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.upload(&ch, chosen, (size_t)T * 4));
+        FL_TRY(B.alloc(&recs, (size_t)T * sizeof(LogprobRec)));
+        FL_TRY(B.alloc(&ctl, sizeof(LogprobCtl)));
+        FL_TRY(launch_set_logprob_ctl(B.L, ctl, recs, (uint32_t)T, top_n));
+        LogprobSrc src;
+        src.ctl = ctl; src.chosen = ch;
+        std::vector<LogprobRec> host[2];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the gather's order in LDS differs from launch to launch, the result must not
+            host[rep].resize((size_t)T);
+            FL_HIP(hipMemsetAsync(recs, 0, (size_t)T * sizeof(LogprobRec), B.s));
+            FL_TRY(launch_token_logprobs(B.L, lg, V, (int)T, src, 0));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep].data(), recs, (size_t)T * sizeof(LogprobRec), hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0].data(), host[1].data(), (size_t)T * sizeof(LogprobRec))) FL_FAIL(FL_ERR_HIP, "token_logprobs: a repeated launch gave another result");
+        for (int64_t t = 0; t < T; t++) {
+            token_logprob[t] = host[0][(size_t)t].chosen;
+            for (int j = 0; j < top_n; j++) {
+                top_ids[t * top_n + j] = host[0][(size_t)t].ids[j];
+                top_logprobs[t * top_n + j] = host[0][(size_t)t].lps[j];
+            }
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
+                            int32_t dtype, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype must be bf16 or f32");
+        if (H < 1 || H > 65535) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head count");
+        if (!encoder_attention_supported(d)) FL_FAIL(FL_ERR_UNSUPPORTED, "encoder attention: head_dim 32 or 64");
+        int64_t T = 0, longest = 0;
+        FL_TRY(encoder_check_offsets(offsets, n_seq, 1 << 18, 1 << 20, &T, &longest));
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, n = (size_t)T * H * d;
+        std::vector<int32_t> off(n_seq + 1);
+        for (size_t s = 0; s <= n_seq; s++) off[s] = (int32_t)offsets[s];
+        void *qd, *kd, *vd, *od; int32_t *offd;
+        FL_TRY(B.upload(&qd, q, n * es)); FL_TRY(B.upload(&kd, k, n * es)); FL_TRY(B.upload(&vd, v, n * es));
+        FL_TRY(B.upload(&offd, off.data(), (n_seq + 1) * 4));
+        FL_TRY(B.alloc(&od, n * es));
+        FL_HIP(hipMemset(od, 0xff, n * es));                       // NaN pattern: an element the kernel does not write shows up
+        FL_TRY(launch_encoder_attention(B.L, dtype, qd, kd, vd, H * d, offd, (int64_t)n_seq, longest, T, H, d, 1.0f / sqrtf((float)d), od));
+        FL_HIP(hipStreamSynchronize(B.s));
+        return op_download(out, od, n, dtype);
+    });
+}
+
+int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, int64_t n_draws, uint32_t *tokens_out, int64_t *kept_out) {
+    return guarded([&]() -> int {
+        if (!logits || !sampler || !tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (V <= 0 || V > (1 << 24) || n_draws <= 0 || n_draws > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size");
+        SampleState ss;
+        FL_TRY(make_sampler(sampler, V, &ss));
+        OpScope B;
+        FL_TRY(B.begin());
+        const bool kept_dev = kept_out && ss.filter;       // (no filter: every token is kept)
+        StepState st{}; st.eos = -1;
+        float *lg, *sc; StepState *std_; SampleState *ssd; uint32_t *od, *kept = nullptr;
+        FL_TRY(B.upload(&lg, logits, (size_t)V * 4));
+        FL_TRY(B.alloc(&sc, (size_t)V * 4));
+        FL_TRY(B.upload(&std_, &st, sizeof st));
+        FL_TRY(B.upload(&ssd, &ss, sizeof ss));
+        FL_TRY(B.alloc(&od, (size_t)n_draws * 4));
+        if (kept_dev) FL_TRY(B.alloc(&kept, (size_t)n_draws * 4));
+        for (int64_t i = 0; i < n_draws; i++) {
+            FL_TRY(launch_select_advance(B.L, lg, V, std_, ssd, sc, od, 1));
+            if (kept_dev) FL_HIP(hipMemcpyAsync(kept + i, &ssd->kept, 4, hipMemcpyDeviceToDevice, B.s));
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(tokens_out, od, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+        if (kept_out) {
+            std::vector<uint32_t> k((size_t)n_draws, (uint32_t)V);
+            if (kept_dev) FL_HIP(hipMemcpy(k.data(), kept, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < n_draws; i++) kept_out[i] = (int64_t)k[(size_t)i];
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out) {
+    if (!sampling) return fl_op_sample_ex(logits, V, nullptr, n_draws, tokens_out, nullptr);
+    const fl_sampler s = widen(*sampling);
+    return fl_op_sample_ex(logits, V, &s, n_draws, tokens_out, nullptr);
+}
+
+int fl_op_linear(const void *x, const void *w, const float *bias, int64_t T, int64_t N, int64_t K, int32_t dtype,
+                 int32_t epilogue, float *y, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!x || !w || !y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+        if (T <= 0 || N <= 0 || K <= 0 || K % 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (K must be a multiple of 8)");
+        if (epilogue == EPI_GATEUP && (N % 2)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count");
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+        const int64_t I = N / 2, Ip = (I + 15) / 16 * 16;
+        const int64_t Nw = epilogue == EPI_GATEUP ? 2 * Ip : N;          // rows of the device matrix
+        const int64_t Ny = epilogue == EPI_GATEUP ? Ip : N;              // columns of the device output
+        const size_t wbytes = (size_t)Nw * K * es, ybytes = (size_t)T * Ny * (epilogue == EPI_GATEUP ? es : 4);
+        const int op_split = tune(TK_OP_MAXSPLIT);
+        const int max_split = (epilogue == EPI_F32 && !bias) ? (op_split > 0 ? op_split : std::max(4, ksplit_cap(T))) : 1;      // exercise split-K where the model would
+        int nsplit = 1;
+        void *xd, *wd, *yd; float *bd = nullptr;
+        FL_TRY(B.upload(&xd, x, (size_t)T * K * es));
+        FL_TRY(B.alloc(&wd, wbytes));
+        FL_TRY(B.alloc(&yd, ybytes * max_split));
+        if (epilogue == EPI_GATEUP) {
+            void *ws;
+            FL_TRY(B.upload(&ws, w, (size_t)N * K * es));
+            FL_HIP(hipMemsetAsync(wd, 0, wbytes, B.s));
+            FL_TRY(launch_convert_slice(B.L, dtype, ws, K, 0, 0, I, K, dtype, wd, K, 0, 1));
+            FL_TRY(launch_convert_slice(B.L, dtype, ws, K, I, 0, I, K, dtype, wd, K, 0, 2));
+        } else {
+            FL_HIP(hipMemcpy(wd, w, (size_t)N * K * es, hipMemcpyHostToDevice));
+            if (bias) FL_TRY(B.upload(&bd, bias, (size_t)N * 4));
+        }
+        // FL_OP_LINEAR_DMA=1: T <= 8 rows go through the batched-decode projection kernel (k_gemv_dma.hip) instead, so that
+        // its weight-streaming rate can be measured (and its arithmetic tested) without a model around it
+        const bool use_dma = tune(TK_OP_LINEAR_DMA) == 1;
+        const bool dma = use_dma && dtype == FL_DTYPE_BF16 && T <= 32 && !bd && gemv_dma_supported((int)T, Nw, K, epilogue, 0) &&
+                         gemv_dma_ksplit(K, Nw, epilogue) <= max_split;
+        std::vector<const void *> W{wd};                                 // the copies of the device matrix a timed run rotates over
+        auto make = [&](int) -> int {
+            void *p;
+            FL_TRY(B.alloc(&p, wbytes));
+            FL_HIP(hipMemcpyAsync(p, wd, wbytes, hipMemcpyDeviceToDevice, B.s));
+            W.push_back(p);
+            return FL_OK;
+        };
+        auto run = [&](int c) -> int {
+            if (!dma) return launch_linear(B.L, dtype, W[(size_t)c], xd, bd, yd, T, Nw, K, epilogue, nullptr, max_split, &nsplit);
+            GemvBatchArgs ga;
+            ga.W = W[(size_t)c]; ga.x = xd; ga.out = yd; ga.N = (int)Nw; ga.K = (int)K; ga.epi = epilogue; ga.pro = PRO_X; ga.B = (int)T;
+            ga.nks = epilogue == EPI_F32 ? gemv_dma_ksplit(K, Nw, epilogue) : 1;
+            nsplit = ga.nks;
+            return launch_gemv_dma(B.L, ga);
+        };
+        FL_TRY(op_run(B, wbytes, iters, ms_out, make, run));
+        if (epilogue == EPI_GATEUP) return op_download(y, yd, (size_t)T, (size_t)I, (size_t)Ip, dtype);      // without the padding columns
+        FL_HIP(hipMemcpy(y, yd, ybytes, hipMemcpyDeviceToHost));
+        if (nsplit > 1) {                                   // sum the split-K slabs in slab order, like rmsnorm_add does
+            std::unique_ptr<float[]> tmp(new float[(size_t)T * Ny]);
+            for (int sl = 1; sl < nsplit; sl++) {
+                FL_HIP(hipMemcpy(tmp.get(), (char *)yd + (size_t)sl * ybytes, ybytes, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < (size_t)T * Ny; i++) y[i] += tmp[i];
+            }
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint8_t *q_out, float *s_out) {
+    return guarded([&]() -> int {
+        if (!w || !q_out || !s_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+        if (N <= 0 || K <= 0 || K % 4 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (K must be a multiple of 4)");
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+        void *wd; uint8_t *qd; float *sd;
+        FL_TRY(B.upload(&wd, w, (size_t)N * K * es));
+        FL_TRY(B.alloc(&qd, (size_t)N * K));
+        FL_TRY(B.alloc(&sd, (size_t)N * 4));
+        FL_TRY(launch_quantize_rows(B.L, dtype, wd, N, K, qd, sd, nullptr));
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(q_out, qd, (size_t)N * K, hipMemcpyDeviceToHost));
+        FL_HIP(hipMemcpy(s_out, sd, (size_t)N * 4, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
+                  float *y, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!x || !q || !s || !y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (N <= 0 || K <= 0 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape");
+        if (epilogue != EPI_F32 && epilogue != EPI_GATEUP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "epilogue must be 0 or 1");
+        if (epilogue == EPI_GATEUP && ((N % 2) || bias)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count and takes no bias");
+        if (!gemv_w8_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "K must be a multiple of 16 (a lane of the FP8 stream loads 16 weights), at most 81792");
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t I = N / 2, Ip = (I + 15) / 16 * 16;
+        const int64_t Nw = epilogue == EPI_GATEUP ? 2 * Ip : N;          // rows of the device matrix
+        const int64_t Ny = epilogue == EPI_GATEUP ? Ip : N;
+        const size_t wbytes = (size_t)Nw * K, ybytes = (size_t)Ny * (epilogue == EPI_GATEUP ? 2 : 4);
+        void *xd, *yd; uint8_t *qd; float *sd, *bd = nullptr;
+        FL_TRY(B.upload(&xd, x, (size_t)K * 2));
+        FL_TRY(B.alloc(&qd, wbytes));
+        FL_TRY(B.alloc(&sd, (size_t)Nw * 4));
+        FL_TRY(B.alloc(&yd, ybytes));
+        if (epilogue == EPI_GATEUP) {
+            uint8_t *qs; float *ss;
+            FL_TRY(B.upload(&qs, q, (size_t)N * K));
+            FL_TRY(B.upload(&ss, s, (size_t)N * 4));
+            FL_HIP(hipMemsetAsync(qd, 0, wbytes, B.s));
+            FL_HIP(hipMemsetAsync(sd, 0, (size_t)Nw * 4, B.s));
+            FL_TRY(launch_w8_gateup_layout(B.L, qs, ss, I, K, qd, sd));
+        } else {
+            FL_HIP(hipMemcpy(qd, q, (size_t)N * K, hipMemcpyHostToDevice));
+            FL_HIP(hipMemcpy(sd, s, (size_t)N * 4, hipMemcpyHostToDevice));
+            if (bias) FL_TRY(B.upload(&bd, bias, (size_t)N * 4));
+        }
+        std::vector<const uint8_t *> Q{qd};                              // the copies of q a timed run rotates over
+        auto make = [&](int) -> int {
+            uint8_t *p;
+            FL_TRY(B.alloc(&p, wbytes));
+            FL_HIP(hipMemcpyAsync(p, qd, wbytes, hipMemcpyDeviceToDevice, B.s));
+            Q.push_back(p);
+            return FL_OK;
+        };
+        auto run = [&](int c) -> int {
+            GemvArgs a;
+            a.W = Q[(size_t)c]; a.x = xd; a.bias = bd; a.out = yd; a.N = (int)Nw; a.K = (int)K; a.epi = epilogue; a.pro = PRO_X;
+            return launch_gemv_w8(B.L, a, sd);
+        };
+        FL_TRY(op_run(B, wbytes, iters, ms_out, make, run));
+        if (epilogue == EPI_GATEUP) return op_download(y, yd, (size_t)I, FL_DTYPE_BF16);                    // without the padding columns
+        FL_HIP(hipMemcpy(y, yd, ybytes, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_kv_copy(const void *src, void *dst, int64_t rows, int64_t width_bytes, int64_t src_pitch, int64_t dst_pitch, int32_t iters,
+                  double *ms_out) {
+    return guarded([&]() -> int {
+        if (!src || !dst) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (rows < 1 || width_bytes < 2 || rows > (int64_t)1 << 31) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (rows >= 1, width_bytes >= 2)");
+        KvCopyJob shape;                                     // width / pitch rules: the launch's own
+        shape.rows = rows; shape.width = width_bytes; shape.spitch = src_pitch; shape.dpitch = dst_pitch;
+        FL_TRY(kv_copy_check(shape));
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t sbytes = (size_t)rows * (size_t)src_pitch, dbytes = (size_t)rows * (size_t)dst_pitch;
+        std::vector<void *> sd, dd;                          // the buffer pairs a timed run rotates over
+        auto make = [&](int) -> int {
+            void *p;
+            FL_TRY(B.upload(&p, src, sbytes)); sd.push_back(p);
+            FL_TRY(B.upload(&p, dst, dbytes)); dd.push_back(p);
+            return FL_OK;
+        };
+        auto run = [&](int c) -> int {
+            KvCopyJob j = shape, none;
+            j.src = sd[(size_t)c]; j.dst = dd[(size_t)c];
+            return launch_kv_copy(B.L, j, none);
+        };
+        FL_TRY(make(0));
+        FL_TRY(op_run(B, sbytes + dbytes, iters, ms_out, make, run));
+        FL_HIP(hipMemcpy(dst, dd[0], dbytes, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_attention(const void *q, const void *k, const void *v, int64_t T, int64_t s_past, int64_t H, int64_t Hkv, int64_t d,
+                    int64_t window, int32_t kernel, int32_t nsplit, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || s_past < 0 || H < 1 || Hkv < 1 || kernel < 0 || kernel > 3 || nsplit < 0 || nsplit > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape / kernel");
+        if (!attn_mfma_supported(FL_DTYPE_BF16, H, Hkv, d)) FL_FAIL(FL_ERR_UNSUPPORTED, "MFMA attention: head_dim 64 / 128, at most 8 query heads per kv head");
+        if (kernel == 1 && T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "the decode kernel takes one query token");
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t S = s_past + T, sa = (S + 31) / 32 * 32;
+        const size_t qn = (size_t)T * H * d;
+        if (nsplit == 0) nsplit = (int)std::max<int64_t>(1, std::min<int64_t>((S + 127) / 128, 48));
+        void *qd, *od, *kd, *vd; StepState *std_; float *pm, *pl, *po; unsigned *cnt;
+        FL_TRY(B.upload(&qd, q, qn * 2));
+        FL_TRY(B.alloc(&od, qn * 2));
+        FL_HIP(hipMemset(od, 0xff, qn * 2));                      // NaN pattern: an element the kernel does not write shows up
+        // the cache layout of the model: K [Hkv][sa][d], V transposed [Hkv][d][sa], zero padding
+        FL_TRY(attn_op_upload_cache(B, &kd, &vd, FL_DTYPE_BF16, k, v, 1, S, Hkv, sa, d, true, 0.f));
+        FL_TRY(attn_op_scratch(B, &pm, &pl, &po, &cnt, H, d, nsplit));
+        StepState st{}; st.pos = (uint32_t)s_past; st.len = (uint32_t)s_past; st.call0 = (uint32_t)s_past; st.eos = -1;
+        FL_TRY(B.upload(&std_, &st, sizeof st));
+        const float scale = 1.0f / sqrtf((float)d);
+        int rc;
+        if (kernel == 1 || (kernel == 0 && T == 1)) {
+            AttnScratch as{pm, pl, po, cnt, nsplit, S};
+            rc = launch_attn_decode_mfma(B.L, qd, kd, vd, std_, od, as, H, Hkv, d, sa, scale);
+        } else {
+            attn_prefill_force(kernel);
+            rc = launch_attn_prefill_mfma(B.L, qd, kd, vd, std_, od, T, H, Hkv, d, sa, scale, window < 0 ? -1 : window);
+            attn_prefill_force(0);
+        }
+        FL_TRY(rc);
+        FL_HIP(hipStreamSynchronize(B.s));
+        return op_download(out, od, qn, FL_DTYPE_BF16);
+    });
+}
+
+int fl_op_attention_plain(const void *q, const void *k, const void *v, int32_t dtype, int32_t layout, int32_t kernel, int64_t T, int64_t s_past,
+                          int64_t call0, int64_t k_rows, int64_t capacity, int64_t H, int64_t Hkv, int64_t d, int64_t window, int32_t nsplit,
+                          float pad_value, int32_t repeat, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || s_past < 0 || call0 < 0 || call0 > s_past || kernel < 0 || kernel > 3 || (layout == 0 && kernel == 3) || nsplit < 0 || nsplit > 64 ||
+            repeat < 1 || repeat > 16)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape / kernel (call0 <= s_past, nsplit 0..64, repeat 1..16; the plain layout has one prefill kernel)");
+        if (kernel == 1 && T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "the decode kernel takes one query token");
+        const int64_t S = s_past + T;
+        if (k_rows < S || capacity < k_rows || capacity > (int64_t)1 << 24) FL_FAIL(FL_ERR_BAD_ARGUMENT, "s_past + T <= k_rows <= capacity");
+        if (!(pad_value == pad_value) || pad_value - pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pad_value must be finite");
+        FL_TRY(attn_op_check_heads(dtype, layout, H, Hkv, d));
+        OpScope B;
+        FL_TRY(B.begin());
+        const bool mfma = layout == 1, decode = kernel == 1 || (kernel == 0 && T == 1);
+        const int64_t sa = (capacity + 31) / 32 * 32;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, qn = (size_t)T * H * d;
+        if (nsplit == 0) nsplit = attn_cache_nsplit(mfma, (size_t)capacity, d);
+        void *qd, *od, *kd, *vd; StepState *std_; float *pm, *pl, *po; unsigned *cnt;
+        FL_TRY(B.upload(&qd, q, qn * es));
+        FL_TRY(B.alloc(&od, qn * es * repeat));
+        FL_HIP(hipMemset(od, 0xff, qn * es * repeat));            // NaN pattern: an element a launch does not write shows up
+        FL_TRY(attn_op_upload_cache(B, &kd, &vd, dtype, k, v, 1, k_rows, Hkv, sa, d, mfma, pad_value));
+        FL_TRY(attn_op_scratch(B, &pm, &pl, &po, &cnt, H, d, nsplit));
+        StepState st{}; st.pos = (uint32_t)s_past; st.len = (uint32_t)s_past; st.call0 = (uint32_t)call0; st.eos = -1;
+        FL_TRY(B.upload(&std_, &st, sizeof st));
+        const float scale = 1.0f / sqrtf((float)d);
+        const int64_t w = window < 0 ? -1 : window;
+        for (int r = 0; r < repeat; r++) {                          // every launch on the same scratch and ticket words
+            void *o = (char *)od + (size_t)r * qn * es;
+            int rc;
+            if (decode) {
+                AttnScratch as{pm, pl, po, cnt, nsplit, S};
+                rc = mfma ? launch_attn_decode_mfma(B.L, qd, kd, vd, std_, o, as, H, Hkv, d, sa, scale)
+                          : launch_attn_decode(B.L, dtype, qd, kd, vd, std_, o, as, H, Hkv, d, sa, scale);
+            } else if (mfma) {
+                attn_prefill_force(kernel);
+                rc = launch_attn_prefill_mfma(B.L, qd, kd, vd, std_, o, T, H, Hkv, d, sa, scale, w);
+                attn_prefill_force(0);
+            } else {
+                rc = launch_attn_prefill(B.L, dtype, qd, kd, vd, std_, o, T, H, Hkv, d, sa, scale, w);
+            }
+            FL_TRY(rc);
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        return op_download(out, od, qn * repeat, dtype);
+    });
+}
+
+int fl_op_attention_batch(const void *q, const void *const *k, const void *const *v, int32_t dtype, int32_t layout, int64_t B_, const int64_t *lens,
+                          const int64_t *k_rows, const int64_t *seq_alloc, const int32_t *nsplit, int64_t n_layers, int64_t layer, int64_t H,
+                          int64_t Hkv, int64_t d, float pad_value, int32_t repeat, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !lens || !k_rows || !seq_alloc || !nsplit || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (B_ < 1 || B_ > 1023 || n_layers < 1 || n_layers > 64 || layer < 0 || layer >= n_layers || repeat < 1 || repeat > 16)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (1 <= B <= 1023, layer < n_layers <= 64, repeat 1..16)");
+        for (int64_t b = 0; b < B_; b++) {
+            if (!k[b] || !v[b]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument (sequence %lld)", (long long)b);
+            if (lens[b] < 1 || k_rows[b] < lens[b] || seq_alloc[b] < k_rows[b] || seq_alloc[b] % 32 != 0 || seq_alloc[b] > (int64_t)1 << 24)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: 1 <= len <= k_rows <= seq_alloc, seq_alloc a multiple of 32", (long long)b);
+            if (nsplit[b] < 0 || nsplit[b] > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: nsplit 0..64", (long long)b);
+        }
+        if (!(pad_value == pad_value) || pad_value - pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pad_value must be finite");
+        FL_TRY(attn_op_check_heads(dtype, layout, H, Hkv, d));
+        OpScope B;
+        FL_TRY(B.begin());
+        const bool mfma = layout == 1;
+        const int nb = (int)B_;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, qn = (size_t)nb * H * d;
+        void *qd, *od;
+        FL_TRY(B.upload(&qd, q, qn * es));
+        FL_TRY(B.alloc(&od, qn * es * repeat));
+        FL_HIP(hipMemset(od, 0xff, qn * es * repeat));
+        // every sequence a cache of its own, as fl_batch_create finds them: K / V of all layers, step state, split scratch, ticket
+        // words; the SeqRef fields the attention kernels do not read stay null
+        std::vector<SeqRef> refs((size_t)nb);
+        int max_nsplit = 1;
+        for (int b = 0; b < nb; b++) {
+            SeqRef &r = refs[(size_t)b];
+            r = SeqRef{};
+            r.seq_alloc = (int)seq_alloc[b];
+            r.nsplit = nsplit[b] > 0 ? nsplit[b] : attn_cache_nsplit(mfma, (size_t)seq_alloc[b], d);
+            max_nsplit = std::max(max_nsplit, r.nsplit);
+            FL_TRY(attn_op_upload_cache(B, &r.k, &r.v, dtype, k[b], v[b], n_layers, k_rows[b], Hkv, seq_alloc[b], d, mfma, pad_value));
+            FL_TRY(attn_op_scratch(B, &r.part_m, &r.part_l, &r.part_o, &r.counters, H, d, r.nsplit));
+            StepState st{}; st.pos = (uint32_t)(lens[b] - 1); st.len = (uint32_t)(lens[b] - 1); st.call0 = st.len; st.eos = -1;
+            FL_TRY(B.upload(&r.st, &st, sizeof st));
+        }
+        SeqRef *seqs_dev;
+        FL_TRY(B.upload(&seqs_dev, refs.data(), sizeof(SeqRef) * (size_t)nb));
+        const float scale = 1.0f / sqrtf((float)d);
+        const size_t kv_layer_off = (size_t)(layer * Hkv * d);
+        for (int r = 0; r < repeat; r++) {
+            void *o = (char *)od + (size_t)r * qn * es;
+            if (mfma) FL_TRY(launch_attn_decode_mfma_batch(B.L, qd, seqs_dev, nb, max_nsplit, kv_layer_off, o, H, Hkv, d, scale, 0.0));
+            else FL_TRY(launch_attn_decode_batch(B.L, dtype, qd, seqs_dev, nb, max_nsplit, kv_layer_off, o, H, Hkv, d, scale));
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        return op_download(out, od, qn * repeat, dtype);
+    });
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 #include <unordered_map>
 
 #include "encoder.h"
+#include "model.h"     // require_device
 
 namespace fl {
 
@@ -121,7 +122,7 @@ int encoder_create(const fl_encoder_config *cfg, const fl_tensor *tensors, size_
         FL_FAIL(FL_ERR_UNSUPPORTED, "encoder config beyond the kernels' index range (max_batch_tokens <= 2^20, max_position_embeddings <= 2^18)");
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path"); }
+    FL_TRY(require_device(&ndev));
     if (device >= ndev) FL_FAIL(FL_ERR_NO_DEVICE, "device %d not present (%d visible)", device, ndev);
     {
         hipDeviceProp_t prop;

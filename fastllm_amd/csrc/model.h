@@ -230,6 +230,7 @@ bool fused_all_reduce_ready(const Model *m);   // decode all-reduces ride in the
     ::fl::set_error("RCCL error %s at %s:%d (%s)", ncclGetErrorString(r_), __FILE__, __LINE__, #expr); \
     return FL_ERR_RCCL; } } while (0)
 int env_int(const char *name, int dflt);
+int require_device(int *count = nullptr);   // FL_ERR_NO_DEVICE unless a HIP device is visible (*count: how many); sets no device
 void debug_inject(const char *site);     // FL_DEBUG_THROW fault injection (tests of the ABI exception barrier)
 Launcher make_launcher(Model *m, Shard &sh);
 // comm.hip: inbox / LL region of one shard, its table entries, and the group-level steps

@@ -1,5 +1,5 @@
-// runtime.hip -- what the rest of the library stands on: the error text, the reads of the environment, the CU count of the
-// current device and the one table of integer switches (common.h: TuneKey).
+// runtime.hip -- what the rest of the library stands on: the error text, the reads of the environment, the device check, the CU
+// count of the current device and the one table of integer switches (common.h: TuneKey).
 #include "model.h"
 
 #include <ctype.h>
@@ -25,6 +25,16 @@ const char *env_str(const char *name) { const char *s = getenv(name); return s &
 int env_int(const char *name, int dflt) { const char *s = env_str(name); return s ? atoi(s) : dflt; }
 
 // ------------------------------------------------------------------------------- the device
+int require_device(int *count) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();             // the failed query must not stay behind as the thread's sticky error
+        FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+    }
+    if (count) *count = n;
+    return FL_OK;
+}
+
 int device_cu_count() {                      // of the current device (the shards of a group may sit on different ones)
     constexpr int kMaxDevices = 64;
     static std::atomic<int> cached[kMaxDevices];

@@ -435,8 +435,7 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
     debug_inject("model_create");
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        FL_FAIL(FL_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU path");
+    FL_TRY(require_device(&ndev));
 
     fl_parallel P{};
     if (par) P = *par;
