@@ -194,6 +194,8 @@ def lib():
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
         L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
         L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
+        L.fl_op_attention_packed.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 6 + [C.c_float, vp]
+        L.fl_batch_prefill.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
         L.fl_batch_create.argtypes = [vp, vp, sz, C.POINTER(vp)]
         L.fl_batch_destroy.argtypes = [vp]
         L.fl_batch_destroy.restype = None
@@ -529,6 +531,31 @@ class Model:
         _check(lib().fl_forward_sample(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(sp), C.byref(tok)))
         return tok.value
 
+    def prefill_packed(self, caches, prompts, pos=None, temperatures=None, seeds=None, top_p=None, top_k=None, want_logits=False):
+        """fl_batch_prefill: prompts[i] appended to caches[i] at RoPE offset pos[i] (None: 0 for all), all in ONE forward.  Per member
+        the result of forward_sample(caches[i], prompts[i], pos[i], ..): temperatures / seeds / top_p / top_k are lists (None, or a None
+        entry: ArgMax / 0 / off).  Returns the tokens [n], or (tokens, logits [n, V]) with want_logits."""
+        n = len(caches)
+        assert len(prompts) == n
+        ps = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in prompts]
+        ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(0, np.uint32), dtype=np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([p.size for p in ps])]), dtype=np.uint64)
+        pos = np.ascontiguousarray([0] * n if pos is None else pos, dtype=np.uint64)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        spx = None
+        if temperatures is not None or top_p is not None or top_k is not None:
+            spx = (FlSampler * max(n, 1))()
+            for i in range(n):
+                t = temperatures[i] if temperatures is not None and temperatures[i] is not None else 0.0
+                spx[i] = make_sampler(t, seeds[i] if seeds is not None and seeds[i] is not None else 0, 0,
+                                      top_p[i] if top_p is not None else None, top_k[i] if top_k is not None else None)
+        toks = np.zeros(max(n, 1), dtype=np.uint32)
+        lg = np.empty((n, self.V), dtype=np.float32) if want_logits else None
+        _check(lib().fl_batch_prefill(self._h, C.cast(arr, C.c_void_p), n, ids.ctypes.data, offsets.ctypes.data, pos.ctypes.data,
+                                      C.cast(spx, C.c_void_p) if spx is not None else None, toks.ctypes.data,
+                                      lg.ctypes.data if want_logits else None))
+        return (toks[:n], lg) if want_logits else toks[:n]
+
     def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1, top_p=None, top_k=None,
                       logprobs=None):
         """logprobs = N: returns (tokens, token_logprob [n], top_ids [n, N], top_logprobs [n, N]), n = the tokens emitted; a greedy
@@ -791,6 +818,29 @@ def op_attention_batch(q, ks, vs, lens, seq_alloc, nsplit, H, Hkv, d, layout=0, 
     _check(lib().fl_op_attention_batch(q.ctypes.data, C.cast(kp, C.c_void_p), C.cast(vpp, C.c_void_p), code, layout, B, ln.ctypes.data,
                                        rows.ctypes.data, sa.ctypes.data, ns.ctypes.data, n_layers, layer, H, Hkv, d, pad_value, repeat,
                                        out.ctypes.data))
+    return out
+
+
+def op_attention_packed(q, ks, vs, counts, s_past, seq_alloc, H, Hkv, d, layer=0, window=-1, pad_value=0.0):
+    """The packed prefill attention launch alone (fl_op_attention_packed; bf16 bits, MFMA layout).  q [sum(counts), H*d], member s's
+    rows back to back; ks[s] / vs[s] [n_layers, rows_s, Hkv*d]: rows [0, s_past[s]) its cached prefix, the next counts[s] its new
+    tokens, the rest stale contents; seq_alloc[s]: its cache's row count (a multiple of 32).  Returns [sum(counts), H*d] f32."""
+    q = np.ascontiguousarray(q, dtype=np.uint16)
+    ks = [np.ascontiguousarray(a, dtype=np.uint16) for a in ks]
+    vs = [np.ascontiguousarray(a, dtype=np.uint16) for a in vs]
+    n, n_layers = len(ks), ks[0].shape[0]
+    i64 = lambda x: np.ascontiguousarray(x, dtype=np.int64)
+    off = i64(np.concatenate([[0], np.cumsum(counts)]))
+    T = int(off[-1])
+    assert q.shape == (T, H * d) and len(vs) == len(counts) == len(s_past) == len(seq_alloc) == n
+    for a, b in zip(ks, vs):
+        assert a.ndim == 3 and a.shape[0] == n_layers and a.shape[2] == Hkv * d and a.shape == b.shape
+    kp = (C.c_void_p * n)(*[a.ctypes.data for a in ks])
+    vpp = (C.c_void_p * n)(*[a.ctypes.data for a in vs])
+    sp, rows, sa = i64(s_past), i64([a.shape[1] for a in ks]), i64(seq_alloc)
+    out = np.empty((T, H * d), dtype=np.float32)
+    _check(lib().fl_op_attention_packed(q.ctypes.data, C.cast(kp, C.c_void_p), C.cast(vpp, C.c_void_p), n, off.ctypes.data, sp.ctypes.data,
+                                        rows.ctypes.data, sa.ctypes.data, n_layers, layer, H, Hkv, d, window, pad_value, out.ctypes.data))
     return out
 
 

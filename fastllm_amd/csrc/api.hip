@@ -300,6 +300,12 @@ int fl_batch_forward(fl_batch *b, const uint32_t *tokens, const size_t *pos, flo
         return batch_forward(reinterpret_cast<Batch *>(b), tokens, pos, logits_out, argmax_out);
     });
 }
+int fl_batch_prefill(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                     const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return batch_prefill(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, samplers, tokens_out, logits_out);
+    });
+}
 int fl_batch_decode(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, int64_t eos,
                     const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {

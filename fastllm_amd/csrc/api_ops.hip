@@ -564,4 +564,53 @@ int fl_op_attention_batch(const void *q, const void *const *k, const void *const
     });
 }
 
+int fl_op_attention_packed(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets, const int64_t *s_past,
+                           const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer, int64_t H, int64_t Hkv, int64_t d,
+                           int64_t window, float pad_value, float *out) {
+    return guarded([&]() -> int {
+        if (!q || !k || !v || !offsets || !s_past || !k_rows || !seq_alloc || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (n_seq < 1 || n_seq > 1023 || n_layers < 1 || n_layers > 64 || layer < 0 || layer >= n_layers)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (1 <= n_seq <= 1023, layer < n_layers <= 64)");
+        if (offsets[0] != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "offsets[0] must be 0");
+        for (int64_t s = 0; s < n_seq; s++) {
+            if (!k[s] || !v[s]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument (sequence %lld)", (long long)s);
+            const int64_t cnt = offsets[s + 1] - offsets[s];
+            if (cnt < 1 || cnt > (int64_t)1 << 24 || s_past[s] < 0 || s_past[s] > (int64_t)1 << 24) FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: at least one new token, s_past >= 0", (long long)s);
+            if (k_rows[s] < s_past[s] + cnt || seq_alloc[s] < k_rows[s] || seq_alloc[s] % 32 != 0 || seq_alloc[s] > (int64_t)1 << 24)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "sequence %lld: s_past + new tokens <= k_rows <= seq_alloc, seq_alloc a multiple of 32", (long long)s);
+        }
+        if (offsets[n_seq] > (int64_t)1 << 24) FL_FAIL(FL_ERR_BAD_ARGUMENT, "too many rows");
+        if (!(pad_value == pad_value) || pad_value - pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pad_value must be finite");
+        FL_TRY(attn_op_check_heads(FL_DTYPE_BF16, 1, H, Hkv, d));
+        OpScope B;
+        FL_TRY(B.begin());
+        const int ns = (int)n_seq;
+        const size_t qn = (size_t)offsets[n_seq] * H * d;
+        void *qd, *od;
+        FL_TRY(B.upload(&qd, q, qn * 2));
+        FL_TRY(B.alloc(&od, qn * 2));
+        FL_HIP(hipMemset(od, 0xff, qn * 2));                      // NaN pattern: an element the kernel does not write shows up
+        // every sequence a cache of its own, as fl_batch_prefill finds them: K / V^T of all layers and the step state of the call
+        std::vector<SeqRef> refs((size_t)ns);
+        std::vector<int> counts((size_t)ns), vt((size_t)ns, 1);
+        for (int s = 0; s < ns; s++) {
+            SeqRef &r = refs[(size_t)s];
+            r = SeqRef{};
+            r.seq_alloc = (int)seq_alloc[s]; r.nsplit = 1;
+            counts[(size_t)s] = (int)(offsets[s + 1] - offsets[s]);
+            FL_TRY(attn_op_upload_cache(B, &r.k, &r.v, FL_DTYPE_BF16, k[s], v[s], n_layers, k_rows[s], Hkv, seq_alloc[s], d, true, pad_value));
+            StepState st{}; st.pos = (uint32_t)s_past[s]; st.len = (uint32_t)s_past[s]; st.call0 = st.len; st.eos = -1;
+            FL_TRY(B.upload(&r.st, &st, sizeof st));
+        }
+        PackedHost ph;
+        packed_table_build(refs.data(), counts.data(), vt.data(), ns, H, Hkv, d, &ph);
+        void *tabd;
+        FL_TRY(B.upload(&tabd, ph.bytes.data(), ph.bytes.size()));
+        const float scale = 1.0f / sqrtf((float)d);
+        FL_TRY(launch_attn_prefill_packed_mfma(B.L, qd, ph.at(tabd), ph.n_items, ph.TT, ph.ks, (size_t)(layer * Hkv * d), od, H, Hkv, d, scale, window < 0 ? -1 : window));
+        FL_HIP(hipStreamSynchronize(B.s));
+        return op_download(out, od, qn, FL_DTYPE_BF16);
+    });
+}
+
 }  // extern "C"

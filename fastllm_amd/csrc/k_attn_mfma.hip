@@ -268,44 +268,7 @@ int launch_attn_decode_mfma_batch(Launcher &L, const void *q, const SeqRef *seqs
 // so every K/V byte fetched from L2 feeds G*TT x 16 query rows instead of 16.
 // Mask (App. A.5): cached prefix [0,len) visible; in-call key j visible to token t iff j <= t and
 // (window < 0 or j + window >= t).
-__device__ inline void glds16(const void *g, unsigned char *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n (the instruction takes an immediate)
-__device__ inline void wait_vmcnt(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // always safe
-    }
-}
-
-// every wave issues the same number of 1-KiB pieces, per = ceil((NK + NV) / nwv) (wrapping: a duplicate piece writes
-// the same bytes), so that a counted vmcnt can tell which tiles have landed
-template <int D>
-__device__ inline void stage_kv(const bf16_t *__restrict__ kb, const bf16_t *__restrict__ vT, int ldv, int kbase,
-                                unsigned char *buf, int wave, int nwv, int lane, int per) {
-    constexpr int CPR = D / 8, NK = CPR / 2, NV = D / 16;          // wave-instructions (1 KiB each) per tile
-    unsigned char *kt = buf, *vt = buf + 32 * D * 2;
-    for (int k = 0; k < per; k++) {
-        const int e = (wave + k * nwv) % (NK + NV);
-        if (e < NK) {
-            const int p = e * 64 + lane, row = p / CPR, pc = p % CPR, c = pc ^ (row & (CPR - 1));
-            glds16(kb + (size_t)(kbase + row) * D + c * 8, kt + e * 1024);
-        } else {
-            const int ev = e - NK, p = ev * 64 + lane, row = p >> 2, pc = p & 3, c = pc ^ ((row >> 2) & 3);
-            glds16(vT + (size_t)row * ldv + kbase + c * 8, vt + ev * 1024);
-        }
-    }
-}
-
+// (glds16, wait_vmcnt and stage_kv, the LDS-DMA staging of a K / V^T tile: attn_mfma.h)
 template <int D>
 __global__ __launch_bounds__(1024) void attn_prefill_mfma_kernel(const bf16_t *__restrict__ q, const bf16_t *__restrict__ kc,
                                                                 const bf16_t *__restrict__ vT, const StepState *__restrict__ st,

@@ -220,6 +220,50 @@ int launch_rope_kv_batch(Launcher &L, const float *qkv, const SeqRef *seqs_dev, 
 int launch_unshard_logits(Launcher &L, const float *in, float *out, int tp, int B, int64_t Vs);   // [tp][B][Vs] -> [B][tp * Vs]
 int launch_select_advance_batch(Launcher &L, const float *logits, int64_t V, const SeqRef *seqs_dev, int B, int advance);
 
+// ---- packed prefill (k_prefill_packed.hip): several prompts' tokens back to back in one [T_total][..] forward -------------------------
+// The device table of one call, built by the host: who a row is, which 16 * TT tokens an attention workgroup serves, the members'
+// caches and their row ranges.  Passed by value as kernarg; every pointer is device memory.
+struct PackedRow { int seq, t; };       // row r: token t (0-based among the call's new tokens) of sequence seq
+struct PackedItem { int seq, t0; };     // attention item: tokens [t0, t0 + 16 * TT) of sequence seq (t0 a multiple of 16 * TT)
+struct PackedTable {
+    const PackedRow *rows = nullptr;    // [T_total]
+    const PackedItem *items = nullptr;  // [n_items]
+    const SeqRef *seqs = nullptr;       // [n_seq]
+    const int *seq_off = nullptr;       // [n_seq] first row of the sequence
+    const int *seq_cnt = nullptr;       // [n_seq] its new tokens
+    const int *seq_vt = nullptr;        // [n_seq] 1: its value cache is transposed (the MFMA attention layout)
+};
+// one member's step state at the start of the call (what set_shard_state sets for one cache), and its fused-attention tickets
+struct PackedSeqInit { unsigned *heads_done; uint32_t token, pos, len, _pad; SampleState ss; };
+// every member's StepState / SampleState / tickets (n_tickets words each) in one launch; init_dev: device array [n_seq]
+int launch_packed_set_states(Launcher &L, const PackedTable &tb, const PackedSeqInit *init_dev, int n_seq, int n_tickets);
+// out_dev [2 * n_seq]: every member's token (left by token selection) and error word, for one copy to the host
+int launch_packed_collect(Launcher &L, const PackedTable &tb, uint32_t *out_dev, int n_seq);
+// qkv fp32 [n_slab][T_total][(H+2Hkv)*d] -> slabs summed, bias, RoPE at st->pos + t -> q_out [T_total][H*d], k / v appended at slot
+// st->len + t of each row's own cache; dtype: the model's (q_out and the caches)
+int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const PackedTable &tb, const float *cos_tab, const float *sin_tab,
+                          int64_t max_pos, void *q_out, size_t kv_layer_off, int64_t T_total, int64_t H, int64_t Hkv, int64_t d, int n_slab = 1,
+                          const float *bias = nullptr);
+// bf16, MFMA layout: causal / sliding-window attention of every item's tokens over their own sequence's cache (mask as
+// launch_attn_prefill_mfma, per sequence); q / out [T_total][H*d].  TT, ks: what attn_packed_geometry chose (tb.items were cut for
+// TT); ks 2: the 16-row kernel's wave-pair key split, 1: its plain ring
+void attn_packed_geometry(int64_t H, int64_t Hkv, int64_t d, const int *counts, int n, int *TT_out, int *ks_out);
+int launch_attn_prefill_packed_mfma(Launcher &L, const void *q, const PackedTable &tb, int n_items, int TT, int ks, size_t kv_layer_off, void *out,
+                                    int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops = 0);
+// The host image of one call's table: the arrays back to back (SeqRef first: it holds pointers), and where each begins.  Items are
+// cut, 16 * TT tokens each, for the members with vt[s] != 0 only (the others' attention runs per sequence); TT and ks from
+// attn_packed_geometry over those members.
+struct PackedHost {
+    std::vector<unsigned char> bytes;
+    size_t off_seqs = 0, off_rows = 0, off_items = 0, off_off = 0, off_cnt = 0, off_vt = 0;
+    int n_seq = 0, n_items = 0, T_total = 0, TT = 1, ks = 1;
+    PackedTable at(const void *dev_base) const;           // the table of this image once it lies at dev_base
+};
+void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, int n, int64_t H, int64_t Hkv, int64_t d, PackedHost *out);
+// dst [n_slab][n_seq][h] = the sequences' last rows of src [n_slab][..][h] (slabs src_slab / dst_slab floats apart)
+int launch_gather_last_rows(Launcher &L, const float *src, const PackedTable &tb, float *dst, int n_seq, int64_t h, int n_slab, int64_t src_slab,
+                            int64_t dst_slab);
+
 // dst row of gate/up pair q in the 16-interleaved fused layout: 16 gate rows then 16 up rows
 __host__ __device__ inline int64_t gateup_row(int64_t q, int is_up) { return (q / 16) * 32 + (q % 16) + (is_up ? 16 : 0); }
 

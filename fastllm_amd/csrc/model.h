@@ -74,6 +74,21 @@ struct PeerComm {
     bool shares_device = false;  // a peer lives on this same GPU (rehearsals): full-chip grids that wait for each other cannot co-reside
 };
 
+// fl_batch_prefill (prefill_packed.hip): the per-call device table and the last rows' buffers of a packed prefill.  They belong
+// to the model, grow with the largest call seen and are freed with it.
+struct PackedScratch {
+    void *tab = nullptr; size_t tab_bytes = 0;     // device image of the call's PackedHost, the members' PackedSeqInit behind it
+    unsigned char *host_tab = nullptr; size_t host_tab_bytes = 0;   // ... and its pinned source
+    int cap_n = 0;                                 // sequences the buffers below hold
+    float *xl = nullptr;                           // [n][h] the members' last residual rows
+    float *dl = nullptr;                           // [kMaxKSplitMid][n][h] ... and their delta slabs
+    void *xnl = nullptr; float *inv_rms = nullptr; // [n][h] / [n] the final norm over them
+    float *logits = nullptr;                       // [n][V]
+    uint32_t *result = nullptr;                    // [64][2] the members' tokens and error words, gathered for one copy
+    uint32_t *host_result = nullptr;               // ... pinned
+    std::vector<void *> allocs;
+};
+
 struct Shard {
     int device = 0;
     int rank = 0;                // TP rank this shard plays
@@ -89,6 +104,7 @@ struct Shard {
     float *lm_head_s = nullptr;
     float *cos_tab = nullptr, *sin_tab = nullptr;   // [max_pos][d/2]
     Scratch dec, pre;
+    PackedScratch packed;
     float *logits_local = nullptr;   // [Vs]
     ArgmaxCand *amax = nullptr;      // [kMaxArgmaxCand] ArgMax candidates left by the decode step's lm_head launch (GemvArgs::amax)
     bool amax_valid = false;         // ... and whether the forward enqueued last produced them (host-side, per enqueue)
@@ -215,6 +231,11 @@ int batch_decode(Batch *b, const uint32_t *first, const size_t *pos, size_t n_st
                  const fl_sampler *sampling, uint32_t *tokens_out, size_t *n_out);
 int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t n_steps, const int64_t *eos_each,
                       const fl_sampler *sampling_each, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp_each = nullptr);
+
+// fl_batch_prefill: n prompts in one forward, sequence i = ids[offsets[i] .. offsets[i+1]) appended to caches[i] at RoPE offset pos[i];
+// per sequence the results of forward(m, caches[i], ..); samplers [n] or null (ArgMax), tokens_out [n] / logits_out [n][V] or null
+int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                  const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out);
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
                  const fl_parallel *par, const fl_model_options *opts, Model **out);

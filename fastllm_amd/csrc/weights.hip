@@ -114,6 +114,10 @@ Model::~Model() {
         if (s.pc.err) (void)hipHostFree(s.pc.err);
         for (void *p : s.allocs) (void)hipFree(p);
         for (void *p : s.pre_allocs) (void)hipFree(p);
+        for (void *p : s.packed.allocs) (void)hipFree(p);
+        if (s.packed.tab) (void)hipFree(s.packed.tab);
+        if (s.packed.host_tab) (void)hipHostFree(s.packed.host_tab);
+        if (s.packed.host_result) (void)hipHostFree(s.packed.host_result);
         if (s.stream && std::find(closed.begin(), closed.end(), s.stream) == closed.end()) {
             closed.push_back(s.stream);
             gemm_8p_release_stream(s.stream);

@@ -948,6 +948,15 @@ struct PrefixOptions {
     size_t entries = 0, min_match = 16, max_seq = 0;
 };
 
+// StreamBatcher option: on == false (default) admits every request with a forward of its own, exactly as before.  With `on`, the
+// requests admitted in one step() whose prompts (with a store: the suffixes behind the reused prefix) have at most max_prompt
+// tokens are forwarded together, up to max_tokens tokens (at most 8192, the library's limit) per fl_batch_prefill call: up to about
+// 128 rows a forward is one stream of the weights whatever its rows, so n short prompts cost about one.  Longer prompts keep the
+// single call.
+struct PackedAdmit {
+    bool on = false; size_t max_prompt = 256; size_t max_tokens = 2048;
+};
+
 // ------------------------------------------------------------------------------------ concurrent streams, one batched loop
 // The reference serves concurrent requests as independent tasks (ModelWrapper::generate_stream spawns one loop per stream,
 // mod.rs:137-238), each paying for the whole weight read per token.  StreamBatcher gives the same streams ONE decode loop
@@ -965,6 +974,9 @@ struct PrefixOptions {
 // Reuse is skipped for a Mistral / Qwen2 prompt longer than the sliding window: within one call the new tokens are masked among
 // themselves but a cached prefix is not (fl_forward_verify's note), so prefix + suffix would no longer equal the single call.
 // Refused together with counter_positions: with call-counter RoPE offsets a result depends on how many calls produced the cache.
+//
+// With PackedAdmit.on the admissions of one step() share forwards (fl_batch_prefill); per stream the tokens are those of the single
+// admission (the same logits up to fp32 summation order), and every counter but packed_calls / prefill_calls keeps its value.
 class StreamBatcher {
   public:
     using OnToken = std::function<bool(uint32_t)>;
@@ -974,8 +986,8 @@ class StreamBatcher {
     // see in the reference (quirk C.1: mistral.rs:226,234, qwen.rs:142-143; PosMode::Reference); Llama streams and
     // FASTLLM_POS_MODE=tokens pass token positions
     StreamBatcher(std::shared_ptr<detail::ModelHandle> model, size_t slots, size_t max_seq = 0, size_t chunk = 8, bool counter_positions = false,
-                  PrefixOptions prefix = {})
-        : model_(std::move(model)), chunk_(std::max<size_t>(1, chunk)), counter_(counter_positions) {
+                  PrefixOptions prefix = {}, PackedAdmit packed = {})
+        : model_(std::move(model)), chunk_(std::max<size_t>(1, chunk)), counter_(counter_positions), packed_(packed) {
         if (!model_ || !model_->m) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: no model");
         if (slots < 1 || slots > 64) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: 1 ... 64 slots");
         if (prefix.entries > 0 && counter_)
@@ -1024,9 +1036,12 @@ class StreamBatcher {
     size_t prefills = 0;
     size_t prefill_tokens = 0;                                     // prompt tokens the admissions forwarded (with a store: the suffixes only)
     size_t prefix_hits = 0, prefix_tokens_reused = 0;              // admissions that copied a stored prefix, and the positions they copied
+    size_t prefill_calls = 0;                                      // forwards the admissions took (without PackedAdmit: == prefills)
+    size_t packed_calls = 0;                                       // ... of them fl_batch_prefill calls
 
     // admit waiting requests into free slots, then one chunk for everybody; false: nothing active and nothing waiting
     bool step() {
+        if (packed_.on) admit_packed();
         for (auto &sl : slots_) {
             while (!sl.active && !queue_.empty()) {
                 Request r = std::move(queue_.front());             // out of the queue first: a prefill that throws takes its request with it
@@ -1085,14 +1100,24 @@ class StreamBatcher {
 
     // the slot becomes active only after its prefill succeeded: an exception leaves it free (and the request gone, see step())
     void admit(Slot &sl, Request r) {
+        const size_t n = admit_begin(sl, r);
+        const fl_sampler sp = r.opt.to_ffi((double)r.temperature, 0);
+        uint32_t tok = 0;
+        check(fl_forward_sample_ex(model_->m, sl.cache, r.prompt.data() + n, r.prompt.size() - n, n, &sp, &tok), "Model forward pass failed");
+        prefill_calls++;
+        admit_end(sl, std::move(r), n, tok);
+    }
+    // before the forward: an empty slot cache, or (with a store) the longest stored prefix of the prompt in it; returns its length
+    size_t admit_begin(Slot &sl, const Request &r) {
         sl.emitted = 0;
         sl.held.clear();
         fl_cache_reset(sl.cache);
         size_t n = 0;
         if (store_ && r.prompt.size() <= reuse_limit_) n = store_->lookup_into(sl.cache, r.prompt);
-        const fl_sampler sp = r.opt.to_ffi((double)r.temperature, 0);
-        uint32_t tok = 0;
-        check(fl_forward_sample_ex(model_->m, sl.cache, r.prompt.data() + n, r.prompt.size() - n, n, &sp, &tok), "Model forward pass failed");
+        return n;
+    }
+    // after it: the counters, the slot's stream state, the first token's EOS / max_tokens / callback cases
+    void admit_end(Slot &sl, Request r, size_t n, uint32_t tok) {
         prefills++;
         prefill_tokens += r.prompt.size() - n;
         if (n) { prefix_hits++; prefix_tokens_reused += n; }
@@ -1104,6 +1129,85 @@ class StreamBatcher {
         if (store_) sl.held.push_back(tok);
         if (!sl.req.on_token(tok)) { finish(sl); return; }
         if (sl.emitted >= sl.req.max_tokens || sl.pos >= cap_) finish(sl);
+    }
+    // PackedAdmit: waiting requests are paired with free slots, every slot gets its stored prefix as in admit(), the suffixes of at
+    // most max_prompt tokens (and never more than one call holds) go through fl_batch_prefill in groups of at most max_tokens tokens,
+    // the longer ones through the single call; then admit()'s bookkeeping per slot.  Repeated while an immediate finish freed a slot
+    // and requests still wait.  What throws takes its own requests with it and leaves their slots free, as admit() does: a failed
+    // prefix lookup its one request, a failed forward the requests of that call; a request whose bookkeeping throws (its callback, the
+    // store) does not keep the other members of its call from theirs.  The requests of the step that were not yet looked at or
+    // forwarded go back to the queue's head before the exception leaves.
+    void admit_packed() {
+        struct Pair { Slot *sl; Request r; size_t n; };
+        const size_t max_call = std::min<size_t>(std::max<size_t>(packed_.max_tokens, 1), 8192);
+        const size_t max_member = std::min(packed_.max_prompt, max_call);
+        for (;;) {
+            std::vector<Pair> pairs;
+            for (auto &sl : slots_) {
+                if (sl.active || queue_.empty()) continue;
+                pairs.push_back(Pair{&sl, std::move(queue_.front()), 0});
+                queue_.pop_front();
+            }
+            if (pairs.empty()) return;
+            size_t next = 0;                                          // pairs[next ..) still hold their requests
+            auto requeue_rest = [&] { for (size_t i = pairs.size(); i > next; i--) queue_.push_front(std::move(pairs[i - 1].r)); };
+            for (size_t i = 0; i < pairs.size(); i++) {
+                try { pairs[i].n = admit_begin(*pairs[i].sl, pairs[i].r); }
+                catch (...) {                                         // this request is gone; nothing has been forwarded yet
+                    pairs.erase(pairs.begin() + (std::ptrdiff_t)i);
+                    requeue_rest();
+                    throw;
+                }
+            }
+            auto suffix = [](const Pair &p) { return p.r.prompt.size() - p.n; };
+            std::stable_partition(pairs.begin(), pairs.end(), [&](const Pair &p) { return suffix(p) <= max_member; });   // the packable pairs first, in slot order
+            size_t n_packable = 0;
+            while (n_packable < pairs.size() && suffix(pairs[n_packable]) <= max_member) n_packable++;
+            std::exception_ptr failed;                                // the first bookkeeping failure of a packed call, thrown once its other members are done
+            try {
+                while (next < n_packable && !failed) {
+                    size_t end = next, total = 0;
+                    while (end < n_packable && (end == next || total + suffix(pairs[end]) <= max_call)) total += suffix(pairs[end++]);
+                    std::vector<fl_cache *> caches;
+                    std::vector<uint32_t> ids;
+                    std::vector<size_t> offsets{0}, pos;
+                    std::vector<fl_sampler> sp;
+                    for (size_t i = next; i < end; i++) {
+                        const Pair &p = pairs[i];
+                        caches.push_back(p.sl->cache);
+                        ids.insert(ids.end(), p.r.prompt.begin() + (std::ptrdiff_t)p.n, p.r.prompt.end());
+                        offsets.push_back(ids.size());
+                        pos.push_back(p.n);
+                        sp.push_back(p.r.opt.to_ffi((double)p.r.temperature, 0));
+                    }
+                    std::vector<uint32_t> toks(end - next, 0);
+                    const size_t first = next;
+                    next = end;                                       // (forwarded or failed: these requests do not go back)
+                    check(fl_batch_prefill(model_->m, caches.data(), caches.size(), ids.data(), offsets.data(), pos.data(), sp.data(), toks.data(), nullptr),
+                          "Model forward pass failed");
+                    prefill_calls++; packed_calls++;
+                    for (size_t i = first; i < end; i++) {
+                        try { admit_end(*pairs[i].sl, std::move(pairs[i].r), pairs[i].n, toks[i - first]); }
+                        catch (...) { if (!failed) failed = std::current_exception(); }
+                    }
+                }
+                while (next < pairs.size() && !failed) {
+                    Pair &p = pairs[next++];
+                    const fl_sampler sp = p.r.opt.to_ffi((double)p.r.temperature, 0);
+                    uint32_t tok = 0;
+                    check(fl_forward_sample_ex(model_->m, p.sl->cache, p.r.prompt.data() + p.n, p.r.prompt.size() - p.n, p.n, &sp, &tok), "Model forward pass failed");
+                    prefill_calls++;
+                    admit_end(*p.sl, std::move(p.r), p.n, tok);
+                }
+            } catch (...) {
+                requeue_rest();
+                throw;
+            }
+            if (failed) { requeue_rest(); std::rethrow_exception(failed); }
+            bool freed = false;
+            for (auto &sl : slots_) freed = freed || !sl.active;
+            if (!freed || queue_.empty()) return;
+        }
     }
     // With a store the slot's K/V is remembered under the ids it is KNOWN to hold: the prompt and every emitted token except the
     // last (a token's K/V is written by the step that takes it as input), never more than fl_cache_len.
@@ -1130,6 +1234,7 @@ class StreamBatcher {
     std::shared_ptr<detail::ModelHandle> model_;
     size_t chunk_, cap_ = 0;
     bool counter_ = false;
+    PackedAdmit packed_;
     std::unique_ptr<PrefixStore> store_;                           // null: no prefix reuse
     size_t reuse_limit_ = 0;
     std::vector<Slot> slots_;

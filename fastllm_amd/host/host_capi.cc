@@ -351,6 +351,47 @@ int flh_batcher_prefix_stats(void *bv, size_t *prefix_hits, size_t *prefix_token
     });
 }
 
+// ... and with PackedAdmit (the admissions of one step share fl_batch_prefill calls): flh_batcher_create_prefix plus the three option
+// values; packed_on == 0 is flh_batcher_create_prefix
+int flh_batcher_create_packed(void *hv, size_t slots, size_t max_seq, size_t chunk, size_t entries, size_t min_match, int packed_on,
+                              size_t max_prompt, size_t max_tokens, void **out) {
+    return guard([&] {
+        if (!hv || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto bh = std::make_unique<BatcherHandle>();
+        Handle *h = static_cast<Handle *>(hv);
+        PrefixOptions po; po.entries = entries; po.min_match = min_match;
+        PackedAdmit pa; pa.on = packed_on != 0; pa.max_prompt = max_prompt; pa.max_tokens = max_tokens;
+        bh->b = std::make_unique<StreamBatcher>(model_of(h), slots, max_seq, chunk, !h->llama && pos_mode() == PosMode::Reference, po, pa);
+        *out = bh.release();
+        return 0;
+    });
+}
+// ... on an fl_model the caller already holds (flh_batcher_create_on), no store
+int flh_batcher_create_on_packed(void *fl_model_ptr, size_t slots, size_t max_seq, size_t chunk, int counter_positions, int packed_on,
+                                 size_t max_prompt, size_t max_tokens, void **out) {
+    return guard([&] {
+        if (!fl_model_ptr || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        fl_model *m = static_cast<fl_model *>(fl_model_ptr);
+        fl_model_retain(m);
+        auto mh = std::make_shared<detail::ModelHandle>(m);          // (releases the reference)
+        auto bh = std::make_unique<BatcherHandle>();
+        PackedAdmit pa; pa.on = packed_on != 0; pa.max_prompt = max_prompt; pa.max_tokens = max_tokens;
+        bh->b = std::make_unique<StreamBatcher>(mh, slots, max_seq, chunk, counter_positions != 0, PrefixOptions{}, pa);
+        *out = bh.release();
+        return 0;
+    });
+}
+// forwards the admissions took, and how many of them were packed calls
+int flh_batcher_packed_stats(void *bv, size_t *prefill_calls, size_t *packed_calls) {
+    return guard([&] {
+        if (!bv) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto *bh = static_cast<BatcherHandle *>(bv);
+        if (prefill_calls) *prefill_calls = bh->b->prefill_calls;
+        if (packed_calls) *packed_calls = bh->b->packed_calls;
+        return 0;
+    });
+}
+
 // PrefixIndex alone (pure host, no GPU).  entry_out: the entry, or -1 (match: a miss; insert: nothing stored)
 int flh_prefix_index_create(size_t entries, void **out) {
     return guard([&] {

@@ -383,6 +383,24 @@ int  fl_batch_decode_each(fl_batch *b, const uint32_t *first_tokens, const size_
 int  fl_batch_decode_each_ex(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                              const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out);
 
+/* Packed prefill: n <= 64 prompts of one model in ONE forward.  New capability: the reference (and fl_forward*) forwards every
+ * prompt on its own, and up to about 128 tokens a prompt's projections are a weight stream -- n short prompts read the weights n times.
+ * Sequence i owns ids[offsets[i] .. offsets[i+1]) (at least one id), is appended to
+ * caches[i] at its cached length, with RoPE offset pos[i] for its first id.  Per sequence the result is that of
+ * fl_forward_sample_ex(m, caches[i], its ids, its count, pos[i], &samplers[i], &tokens_out[i]): the cache contents and length,
+ * the sampler state (one draw), the token; logits_out [n][V] fp32 or NULL is what fl_forward would have returned for it.
+ * samplers NULL: ArgMax for all.  The mask is fl_forward's, per sequence: the keys a cache held before the call are an unmasked
+ * prefix, the causal and sliding-window mask runs over the sequence's own new tokens.  bf16 and fp32 models; caches in either layout,
+ * also mixed (members outside the MFMA attention layout: attention per sequence, the projections still once for all rows).
+ * FL_ERR_BAD_ARGUMENT, before the device or any cache is touched: a null m / caches / ids / offsets / pos, n == 0 or n > 64,
+ * offsets[0] != 0 or offsets that do not increase (an empty sequence), the same cache twice, a cache of another model, an id outside
+ * the vocabulary.  FL_ERR_SEQ_OVERFLOW per sequence as fl_forward.  FL_ERR_UNSUPPORTED: tp_size > 1 in any mode; more than
+ * FL_PREFILL_CHUNK (8192) tokens in all -- the caller splits, this call never chunks.  A refused call modifies nothing: no cache
+ * length, no sampler state. */
+int fl_batch_prefill(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
+                     const size_t *pos /* [n] */, const fl_sampler *samplers /* [n] or NULL */,
+                     uint32_t *tokens_out /* [n] or NULL */, float *logits_out /* [n][V] or NULL */);
+
 /* ---- token log-probabilities: the chosen token's, and the N most likely tokens', inside the device decode loop ------------------
  * New capability (the reference reports none).  What an OpenAI-compatible server is asked for as `logprobs` / `top_logprobs`.  The
  * values are computed by one more launch behind each step's token selection, inside the same replayed graph; per step 4 + 160 bytes
@@ -611,6 +629,16 @@ int fl_op_attention_batch(const void *q, const void *const *k, const void *const
                           const int64_t *lens, const int64_t *k_rows, const int64_t *seq_alloc, const int32_t *nsplit,
                           int64_t n_layers, int64_t layer, int64_t H, int64_t Hkv, int64_t d, float pad_value, int32_t repeat,
                           float *out);
+
+/* The packed prefill attention launch alone (unit tests), in the style of fl_op_attention_batch: bf16, MFMA layout (V transposed).
+ * q [T_total][H*d] packed by offsets; sequence s has a cache of its own, built here from host rows k[s] / v[s]
+ * [n_layers][k_rows[s]][Hkv*d]: rows [0, s_past[s]) are its cached prefix, the next (offsets[s+1]-offsets[s]) its new tokens, rows
+ * up to k_rows[s] stale contents, positions from k_rows[s] to seq_alloc[s] (a multiple of 32) hold pad_value in every layer.
+ * window < 0: none.  out [T_total][H*d] fp32 (bf16 widened, pre-filled with the 0xff pattern).  1 <= n_seq <= 1023.  Errors as
+ * fl_op_attention_batch. */
+int fl_op_attention_packed(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets,
+                           const int64_t *s_past, const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer,
+                           int64_t H, int64_t Hkv, int64_t d, int64_t window, float pad_value, float *out);
 
 #ifdef __cplusplus
 }

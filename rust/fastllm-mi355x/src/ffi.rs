@@ -352,6 +352,17 @@ extern "C" {
     pub fn fl_batch_destroy(b: *mut fl_batch);
     pub fn fl_batch_replace(b: *mut fl_batch, slot: usize, cache: *mut fl_cache) -> c_int;
     pub fn fl_batch_forward(b: *mut fl_batch, tokens: *const u32, pos: *const usize, logits_out: *mut f32, argmax_out: *mut u32) -> c_int;
+    pub fn fl_batch_prefill(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        ids: *const u32,
+        offsets: *const usize,
+        pos: *const usize,
+        samplers: *const fl_sampler,
+        tokens_out: *mut u32,
+        logits_out: *mut f32,
+    ) -> c_int;
     pub fn fl_batch_decode(
         b: *mut fl_batch,
         first_tokens: *const u32,
@@ -555,6 +566,24 @@ extern "C" {
         d: i64,
         pad_value: f32,
         repeat: i32,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_attention_packed(
+        q: *const c_void,
+        k: *const *const c_void,
+        v: *const *const c_void,
+        n_seq: i64,
+        offsets: *const i64,
+        s_past: *const i64,
+        k_rows: *const i64,
+        seq_alloc: *const i64,
+        n_layers: i64,
+        layer: i64,
+        h: i64,
+        hkv: i64,
+        d: i64,
+        window: i64,
+        pad_value: f32,
         out: *mut f32,
     ) -> c_int;
 }

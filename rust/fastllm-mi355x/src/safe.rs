@@ -321,6 +321,29 @@ impl Model {
         Ok(tok)
     }
 
+    /// `fl_batch_prefill`: `prompts[i]` appended to `caches[i]` at RoPE offset `pos[i]`, all in ONE forward -- per member the result of
+    /// `forward_sample_ex` (`None`: ArgMax).  Returns every member's token.  At most 64 members and `FL_PREFILL_CHUNK` tokens in all.
+    pub fn prefill_packed(&self, caches: &mut [&mut Cache], prompts: &[&[u32]], pos: &[usize], samplers: &[Option<Sampler>]) -> Result<Vec<u32>> {
+        let n = caches.len();
+        if prompts.len() != n || pos.len() != n || samplers.len() != n {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("packed prefill of {} caches: every slice must have that length", n) });
+        }
+        let raws: Vec<*mut ffi::fl_cache> = caches.iter().map(|c| c.raw).collect();
+        let mut ids: Vec<u32> = Vec::new();
+        let mut offsets = vec![0usize; n + 1];
+        for (i, p) in prompts.iter().enumerate() {
+            ids.extend_from_slice(p);
+            offsets[i + 1] = ids.len();
+        }
+        let greedy = Sampler { temperature: 0.0, top_p: 0.0, top_k: 0, seed: 0, draws_done: 0 };
+        let sp: Vec<ffi::fl_sampler> = samplers.iter().map(|s| s.unwrap_or(greedy).to_ffi()).collect();
+        let mut toks = vec![0u32; n];
+        check(unsafe {
+            ffi::fl_batch_prefill(self.raw, raws.as_ptr(), n, ids.as_ptr(), offsets.as_ptr(), pos.as_ptr(), sp.as_ptr(), toks.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok(toks)
+    }
+
     /// `decode` with top-p / top-k.
     pub fn decode_ex(&self, cache: &mut Cache, first_token: u32, pos: usize, n_steps: usize, eos: Option<u32>, s: Sampler) -> Result<Vec<u32>> {
         let mut toks = vec![0u32; n_steps];
