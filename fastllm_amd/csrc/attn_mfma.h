@@ -48,7 +48,7 @@ struct LdsKV {
     }
 };
 
-// ---- staging of one 32-key K tile + V^T tile into LDS by LDS-DMA (the prefill kernels: k_attn_mfma.hip, k_prefill_packed.hip)
+// ---- staging of one 32-key K tile + V^T tile into LDS by LDS-DMA (the prefill kernels: attn_prefill16.h, k_attn_mfma.hip)
 __device__ inline void glds16(const void *g, unsigned char *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                      (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
@@ -155,13 +155,18 @@ struct RegKV {
     __device__ bf16x8 v_frag(int db) const { return v[db]; }
 };
 
+// a column's l: the sum of the partial sums its four lane groups hold
+__device__ __forceinline__ float mfma_l_total(float l) {
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    return l;
+}
+
 // wave slab -> LDS in the shared format [wave][head][o[D], m, l] (attn_common.h)
 template <int D, int GMAX>
 __device__ __forceinline__ void mfma_state_to_lds(const MfmaAttnState<D> &s, float *lds, int wave, int G, int lane) {
     const int i = lane & 15, g4 = lane >> 4;
-    float lt = s.l;
-    lt += __shfl_xor(lt, 16, 64);
-    lt += __shfl_xor(lt, 32, 64);
+    const float lt = mfma_l_total(s.l);
     constexpr int STR = D + 2;
 #pragma unroll
     for (int r = 0; r < 4; r++) {

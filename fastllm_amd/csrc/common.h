@@ -271,4 +271,54 @@ __device__ inline void rope_rotate(float x0, float x1, float c, float s, float &
     t1 = __fadd_rn(__fmul_rn(x0, s), __fmul_rn(x1, c));
 }
 
+// ---- the scalar RoPE + KV append, one thread per (row, head, j < d/2) pair.  rope_kv_kernel, rope_kv_batch_kernel (k_ops.hip) and
+// rope_kv_packed_kernel (k_prefill_packed.hip) differ in where a row's position, cache slot and destinations come from: each loads
+// its pair, resolves the row and stores.
+struct RopeKvPair { int r, hd, j; float a, b; };
+
+// thread idx -> row r, head hd (q heads, then k, then v) and pair j of qkv [n_slab][rows][(H + 2 Hkv) * d], with the projection's
+// fp32 K slabs summed in slab order and its (Qwen2) bias added; false: idx is past the end
+__device__ __forceinline__ bool rope_kv_load(const float *__restrict__ qkv, long long idx, int rows, int H, int Hkv, int d, int n_slab,
+                                             const float *__restrict__ bias, RopeKvPair &p) {
+    const int half = d >> 1, nheads = H + 2 * Hkv, per_row = nheads * half;
+    if (idx >= (long long)rows * per_row) return false;
+    const int rem = (int)(idx % per_row);
+    p.r = (int)(idx / per_row); p.hd = rem / half; p.j = rem % half;
+    const float *src = qkv + (size_t)p.r * nheads * d + (size_t)p.hd * d;
+    p.a = src[p.j]; p.b = src[p.j + half];
+    for (int s = 1; s < n_slab; s++) {
+        const float *ss = src + (size_t)s * rows * nheads * d;
+        p.a += ss[p.j]; p.b += ss[p.j + half];
+    }
+    if (bias) { p.a += bias[(size_t)p.hd * d + p.j]; p.b += bias[(size_t)p.hd * d + p.j + half]; }
+    return true;
+}
+
+// q_row: the row's [H][d] in the q buffer; *k_base / *v_base + layer: the layer's K [Hkv][sa][d] and V ([Hkv][d][sa] if
+// *v_transposed, the MFMA attention layout, else [Hkv][sa][d]) of the row's cache.  The bases and the flag are taken by address: a
+// thread loads only the one its head stores through (per row they sit in a table: three more loads per thread cost the packed
+// kernel 7 %, profiles/attn_prefill16/README.md).
+struct RopeKvDst { void *q_row; void *const *k_base, *const *v_base; size_t layer, sa; const int *v_transposed; };
+
+// rotate-half RoPE (candle_nn::rotary_emb::rope, App. A.4) at pos on q and k heads, v as it is; k and v go to cache slot `slot`
+template <typename CT>
+__device__ __forceinline__ void rope_kv_store(const RopeKvPair &p, uint32_t pos, uint32_t slot, const float *__restrict__ cos_tab,
+                                              const float *__restrict__ sin_tab, int max_pos, int H, int Hkv, int d, const RopeKvDst &dst) {
+    const int half = d >> 1, hd = p.hd, j = p.j;
+    if (hd < H + Hkv) {
+        const uint32_t pp = pos < (uint32_t)max_pos ? pos : (uint32_t)max_pos - 1;   // host validates range
+        float ra, rb;
+        rope_rotate(p.a, p.b, cos_tab[(size_t)pp * half + j], sin_tab[(size_t)pp * half + j], ra, rb);
+        CT *o = hd < H ? static_cast<CT *>(dst.q_row) + (size_t)hd * d
+                       : static_cast<CT *>(*dst.k_base) + dst.layer + ((size_t)(hd - H) * dst.sa + slot) * d;
+        elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);
+    } else if (*dst.v_transposed) {                       // one key column per token
+        CT *o = static_cast<CT *>(*dst.v_base) + dst.layer + (size_t)(hd - H - Hkv) * d * dst.sa + slot;
+        elem<CT>::st(o + (size_t)j * dst.sa, p.a); elem<CT>::st(o + (size_t)(j + half) * dst.sa, p.b);
+    } else {
+        CT *o = static_cast<CT *>(*dst.v_base) + dst.layer + ((size_t)(hd - H - Hkv) * dst.sa + slot) * d;
+        elem<CT>::st(o + j, p.a); elem<CT>::st(o + j + half, p.b);
+    }
+}
+
 }  // namespace fl

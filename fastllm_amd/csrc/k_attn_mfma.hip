@@ -24,7 +24,9 @@
 #include <algorithm>
 #include <atomic>
 
-#include "attn_mfma.h"
+#include "attn_prefill16.h"
+#include "attn_prefill_plan.h"
+#include "kernels.h"
 
 namespace fl {
 
@@ -262,147 +264,19 @@ int launch_attn_decode_mfma_batch(Launcher &L, const void *q, const SeqRef *seqs
 }
 
 // ------------------------------------------------------------------------------- prefill
-// grid (ceil(T / (16*TT)), Hkv); workgroup = G*TT waves: wave w serves query head g = w % G of kv head
-// blockIdx.y for the 16 tokens of sub-tile w / G.  All waves walk the same key tiles, which are staged
-// ONCE per workgroup in LDS (K tile + V^T tile, 16 KB per 32 keys at d = 128, double-buffered LDS-DMA),
-// so every K/V byte fetched from L2 feeds G*TT x 16 query rows instead of 16.
-// Mask (App. A.5): cached prefix [0,len) visible; in-call key j visible to token t iff j <= t and
-// (window < 0 or j + window >= t).
-// (glds16, wait_vmcnt and stage_kv, the LDS-DMA staging of a K / V^T tile: attn_mfma.h)
-template <int D>
+// grid (ceil(T / (16*TT)), Hkv); workgroup = G*TT (x KS) waves.  The body -- staging, mask, key split, merge, write-out -- is
+// prefill16_body (attn_prefill16.h), shared with the packed kernel (k_prefill_packed.hip); here the sequence is the launch's one
+// prompt, and the wave pair of KS = 2 alternates from the workgroup's first staged tile.
+template <int D, int KS>
 __global__ __launch_bounds__(1024) void attn_prefill_mfma_kernel(const bf16_t *__restrict__ q, const bf16_t *__restrict__ kc,
                                                                 const bf16_t *__restrict__ vT, const StepState *__restrict__ st,
                                                                 bf16_t *__restrict__ out, int T, int H, int Hkv, int seq_alloc,
-                                                                float scale, int window, int TT, int nst, int ks) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // nst x (K tile | V^T tile)
-    constexpr int TILE = 2 * 32 * D * 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-    const int i = lane & 15, g4 = lane >> 4;
-    const int G = H / Hkv, hk = blockIdx.y;
-    // ks == 2 (short prompts): two waves per (head, token sub-tile) take alternate key tiles and merge at the end --
-    // a key step is a chain of dependent latencies, and this puts two such chains on every SIMD
-    const int wq = wave % (G * TT), half = wave / (G * TT);
-    const int hq = hk * G + wq % G;
-    const int tb0 = blockIdx.x * TT * 16;                        // first token of the workgroup
-    const int t0 = tb0 + (wq / G) * 16;                          // first token of this wave
-    const int len = (int)st->len;
-    const int t = t0 + i;                                        // this lane's column
-    const bool col_ok = t < T;
-
-    bf16x8 qf[D / 32];
-#pragma unroll
-    for (int dk = 0; dk < D / 32; dk++) {
-        if (col_ok) qf[dk] = ld_bf16x8(q + ((size_t)t * H + hq) * D + dk * 32 + g4 * 8);
-        else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) qf[dk][j] = (__bf16)0.f;
-        }
-    }
-    // keys cached before the API call are an unmasked prefix; the causal + sliding-window mask runs over
-    // the call's own tokens even when the library cut the call into chunks (call0 <= len)
-    const int c0 = (int)st->call0;
-    int lo = c0;
-    if (window >= 0 && len + t - window > c0) lo = len + t - window;
-    const int lo_q = col_ok ? lo : 0, hi_q = col_ok ? len + t + 1 : 0;
-    const int pre_hi = col_ok ? c0 : 0;
-    // this wave's useful key range (uniform per wave): tiles outside are skipped, staging is not
-    int wstart = 0;
-    if (c0 == 0 && window >= 0 && len + t0 - window > 0) wstart = ((len + t0 - window) / 32) * 32;
-    const int wend = t0 < T ? len + min(T, t0 + 16) : 0;
-
-    MfmaAttnState<D> s; s.init();
-    const bf16_t *kb = kc + (size_t)hk * seq_alloc * D;
-    const bf16_t *vb = vT + (size_t)hk * D * seq_alloc;
-    int kstart = 0;
-    if (c0 == 0 && window >= 0 && len + tb0 - window > 0) kstart = ((len + tb0 - window) / 32) * 32;
-    const int kend = len + min(T, tb0 + 16 * TT);
-    const int nsteps = (kend - kstart + 31) / 32;
-    // ring of nst tiles, nst - 1 of them in flight
-    constexpr int NI = D / 16 + D / 16;
-    const int per = (NI + nwv - 1) / nwv;
-    if (ks == 2) {
-        // super-steps of two tiles (buffers [stage][half]); one barrier per super-step, two LDS stages
-        const int nsuper = (nsteps + 1) / 2;
-        auto stage2 = [&](int ss, int stg) {
-            const int k0 = kstart + 64 * ss;
-            stage_kv<D>(kb, vb, seq_alloc, k0, lds + (stg * 2) * TILE, wave, nwv, lane, per);
-            if (k0 + 32 < kend) stage_kv<D>(kb, vb, seq_alloc, k0 + 32, lds + (stg * 2 + 1) * TILE, wave, nwv, lane, per);
-        };
-        stage2(0, 0);
-        for (int ss = 0; ss < nsuper; ss++) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (ss + 1 < nsuper) stage2(ss + 1, (ss + 1) & 1);
-            const int kbase = kstart + 64 * ss + 32 * half;
-            if (kbase < kend && kbase + 32 > wstart && kbase < wend) {               // wave-uniform
-                const unsigned char *cur = lds + ((ss & 1) * 2 + half) * TILE;
-                const LdsKV<D> kv{cur, cur + 32 * D * 2, i, g4};
-                attn_tile<D>(s, qf, kv, kbase, pre_hi, lo_q, hi_q, scale, lane);
-            }
-        }
-        // merge the two key halves through LDS (the tiles are dead after the barrier)
-        __syncthreads();
-        float *slab = reinterpret_cast<float *>(lds) + (size_t)wq * (16 * D + 32);
-        float lt1 = s.l;
-        lt1 += __shfl_xor(lt1, 16, 64);
-        lt1 += __shfl_xor(lt1, 32, 64);
-        if (half == 1) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int db = 0; db < D / 16; db++) slab[(4 * g4 + r) * D + db * 16 + i] = s.O[db][r];
-            if (g4 == 0) { slab[16 * D + i] = s.m; slab[16 * D + 16 + i] = lt1; }
-        }
-        __syncthreads();
-        if (half == 1) return;
-        const float m1 = slab[16 * D + i], l1 = slab[16 * D + 16 + i];
-        const float mm = fmaxf(s.m, m1);
-        const float w0 = s.m == -INFINITY ? 0.f : __expf(s.m - mm), w1 = m1 == -INFINITY ? 0.f : __expf(m1 - mm);
-        const float ltot = lt1 * w0 + l1 * w1;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int qq = 4 * g4 + r;
-            const float lr = __shfl(ltot, qq, 64), a0 = __shfl(w0, qq, 64), a1 = __shfl(w1, qq, 64);
-            const int tt = t0 + qq;
-            if (tt < T) {
-                const float inv = 1.0f / lr;
-                bf16_t *o = out + ((size_t)tt * H + hq) * D;
-#pragma unroll
-                for (int db = 0; db < D / 16; db++)
-                    o[db * 16 + i] = float_to_bf16_bits((s.O[db][r] * a0 + slab[qq * D + db * 16 + i] * a1) * inv);
-            }
-        }
-        return;
-    }
-    for (int a = 0; a < nst - 1 && a < nsteps; a++) stage_kv<D>(kb, vb, seq_alloc, kstart + 32 * a, lds + a * TILE, wave, nwv, lane, per);
-    for (int sidx = 0; sidx < nsteps; sidx++) {
-        wait_vmcnt(per * min(nst - 2, nsteps - 1 - sidx));       // tile sidx has landed; the younger ones may still fly
-        __builtin_amdgcn_s_barrier();
-        const int kbase = kstart + 32 * sidx;
-        if (sidx + nst - 1 < nsteps)
-            stage_kv<D>(kb, vb, seq_alloc, kbase + 32 * (nst - 1), lds + ((sidx + nst - 1) % nst) * TILE, wave, nwv, lane, per);
-        if (kbase + 32 > wstart && kbase < wend) {               // wave-uniform
-            const unsigned char *cur = lds + (sidx % nst) * TILE;
-            const LdsKV<D> kv{cur, cur + 32 * D * 2, i, g4};
-            attn_tile<D>(s, qf, kv, kbase, pre_hi, lo_q, hi_q, scale, lane);
-        }
-    }
-
-    float lt = s.l;
-    lt += __shfl_xor(lt, 16, 64);
-    lt += __shfl_xor(lt, 32, 64);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int qq = 4 * g4 + r;
-        const float lr = __shfl(lt, qq, 64);
-        const int tt = t0 + qq;
-        if (tt < T) {
-            const float inv = 1.0f / lr;
-            bf16_t *o = out + ((size_t)tt * H + hq) * D;
-#pragma unroll
-            for (int db = 0; db < D / 16; db++) o[db * 16 + i] = float_to_bf16_bits(s.O[db][r] * inv);
-        }
-    }
+                                                                float scale, int window, int TT, int nst) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // nst x KS x (K tile | V^T tile)
+    const int hk = blockIdx.y;
+    const Prefill16Seq v{q, kc + (size_t)hk * seq_alloc * D, vT + (size_t)hk * D * seq_alloc, out, T, (int)st->len, (int)st->call0,
+                         seq_alloc, (int)blockIdx.x * TT * 16};
+    prefill16_body<D, KS, false>(v, hk, H, Hkv, scale, window, TT, nst, lds);
 }
 
 // ------------------------------------------------------------------------------- prefill, 32 query rows per wave
@@ -685,115 +559,50 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill32_kernel(const bf16_t *_
     }
 }
 
-template <int D, int NW, int KSF = 1>
-static int launch_pf32(Launcher &L, const void *q, const void *k_cache, const void *v_cache_T, const StepState *st, void *out,
-                       int64_t T, int64_t H, int64_t Hkv, int64_t seq_alloc, float scale, int64_t window, int TB, int paired, int gsub = 0) {
-    const int64_t nb = (T + 32 * TB - 1) / (32 * TB);
-    const int64_t G = H / Hkv, nsg = gsub > 0 ? (G + gsub - 1) / gsub : 1;
-    dim3 grid((unsigned)(paired ? (nb + 1) / 2 : nb), (unsigned)(Hkv * nsg));
-    if (paired == 2) grid = dim3((unsigned)device_cu_count(), 1);   // one persistent workgroup per CU of the CURRENT device
-    const size_t lds = (KSF == 4 ? 2 : 3) * (size_t)(2 * 32 * D * 2) * KSF;
+template <int D, int NW, int KSF>
+static int launch_pf32(Launcher &L, const AttnPrefillPlan &p, const void *q, const void *k_cache, const void *v_cache_T, const StepState *st,
+                       void *out, int64_t T, int64_t H, int64_t Hkv, int64_t seq_alloc, float scale, int64_t window) {
     const double flops = 2.0 * (double)T * T * H * D;
-    Launcher LL = L; LL.tag = KSF == 4 ? "32row,ks4" : KSF == 2 ? "32row,ks2" : "32row";
-    FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(attn_prefill32_kernel<D, NW, KSF>), lds));
-    return LL.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill32_kernel<D, NW, KSF>, grid, dim3(NW * 64), lds, (const bf16_t *)q,
-                     (const bf16_t *)k_cache, (const bf16_t *)v_cache_T, st, (bf16_t *)out, (int)T, (int)H, (int)Hkv, (int)seq_alloc,
-                     scale * 1.44269504088896340736f, (int)window, paired, gsub);
+    Launcher LL = L; LL.tag = p.tag;
+    FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(attn_prefill32_kernel<D, NW, KSF>), p.lds));
+    return LL.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill32_kernel<D, NW, KSF>, dim3(p.grid_x, p.grid_y), dim3(NW * 64), p.lds,
+                     (const bf16_t *)q, (const bf16_t *)k_cache, (const bf16_t *)v_cache_T, st, (bf16_t *)out, (int)T, (int)H, (int)Hkv,
+                     (int)seq_alloc, scale * 1.44269504088896340736f, (int)window, p.paired, p.gsub);
 }
 
 static std::atomic<int> g_prefill_force{0};
 void attn_prefill_force(int which) { g_prefill_force = which; }
 
+AttnPrefillTune attn_prefill_tune() {
+    return {tune(TK_ATTN_PF32_MIN_T), tune(TK_ATTN_PF32_KS2), tune(TK_ATTN_PF32_PAIRED), tune(TK_ATTN_PF_WAVES), tune(TK_ATTN_PF_STAGES),
+            tune(TK_ATTN_PF_KSPLIT)};
+}
+
+// The choice and its launch geometry are plan_attn_prefill's (attn_prefill_plan.h); here a plan meets its template instantiation.
 int launch_attn_prefill_mfma(Launcher &L, const void *q, const void *k_cache, const void *v_cache_T, const StepState *st,
                              void *out, int64_t T, int64_t H, int64_t Hkv, int64_t d, int64_t seq_alloc, float scale,
                              int64_t window) {
-    const int G = (int)(H / Hkv);
-    if (G > 8) FL_FAIL(FL_ERR_UNSUPPORTED, "mfma prefill attention: at most 8 query heads per kv head");
-    // 32-row waves (attn_prefill32_kernel) once the prompt is long enough to fill the chip with their workgroups
-    // (with wave pairs from 640 tokens for G = 1, 2, 4: Mistral-7B T = 768 31.9 -> 24.8 us per layer, T = 512 a tie, below slower;
-    // from 256 tokens for the groups dealt as subgroups of four heads: Qwen2-7B T = 512 23.2 -> 18.3, TinyLlama 16.5 -> 13.2, T = 256 a tie)
-    const int pf32_min_env = tune(TK_ATTN_PF32_MIN_T);
-    // (since round 4, with four waves per (head, block) up to 576 tokens: from 352 tokens for G = 1, 2, 4 as well)
-    const int pf32_min_t = pf32_min_env > 0 ? pf32_min_env : ((G == 1 || G == 2 || G == 4) ? 352 : (G > 4 ? 256 : 1024));
-    const int force = g_prefill_force.load();                        // fl_op_attention pins one kernel (unit tests)
-    // (577-639 tokens, G = 1, 2, 4: the four-wave form ends at 576 tokens, the wave pairs pay from 640: the 16-row kernel in between)
-    const bool gap = pf32_min_env <= 0 && (G == 1 || G == 2 || G == 4) && T > 576 && T < 640;
-    if ((force == 3 || (force == 0 && T >= pf32_min_t && !gap)) && scale > 0.f) {
-        // waves per workgroup: 8 (G = 1, 2, 4), 6 (G = 3), else G.  Paired (balanced) grids win as soon as they cover
-        // ~3/4 of the chip -- Mistral-7B per layer: T = 3072 134 us paired (192 workgroups) vs 197 unpaired, T = 4096
-        // 177 vs 305, T = 8192 681 vs 693; T = 2048 (128 paired workgroups) 98 vs 85.  4-wave workgroups (half the K/V
-        // reuse, one wave per SIMD) lost everywhere: T = 2048 105 / 180 us, T = 4096 371 / 515.
-        const int NW = G <= 4 ? (8 / G) * G : G;
-        int TB = NW / G;
-        // too few (block, kv head) items to balance: halve the token blocks and split every block's keys over a wave pair
-        const int ks2_mode = tune(TK_ATTN_PF32_KS2);
-        bool ks2 = NW == 8 && TB % 2 == 0 && (ks2_mode >= 0 ? ks2_mode != 0 : ((T + 32 * TB - 1) / (32 * TB)) * Hkv < 2 * 256);
-        // groups of 5..8 heads: wave pairs only fit when the group is dealt in subgroups of four heads (8 waves = 4 heads x a pair)
-        int gsub = 0;
-        if (!ks2 && G > 4 && (ks2_mode >= 0 ? ks2_mode != 0 : ((T + 31) / 32) * Hkv < 2 * 256)) { ks2 = true; gsub = 4; TB = 2; }
-        if (ks2) TB /= 2;
-        // ... and when even the wave pairs leave fewer than two rounds of items: FOUR waves per (head, block), groups of four or more
-        // heads dealt two heads at a time -- twice the items again, the longest block's chain a quarter (attn_pf32_ks2 = 4 forces it)
-        int ksf = ks2 ? 2 : 1;
-        if (ks2 && G != 3) {
-            const int64_t items2 = ((T + 32 * TB - 1) / (32 * TB)) * Hkv * (gsub ? (G + gsub - 1) / gsub : 1);
-            // Whole prefills, wave pairs / four waves: Mistral-7B 384 / 512 tokens x 0.994 / 0.988 (against the 16-row kernel it replaces
-            // there), 600-1536 a tie, 2048 x 1.019; Qwen2-7B 257-512 x 0.986-0.993, 640-1024 a tie; TinyLlama 300 / 512 x 0.986 / 0.972,
-            // 640 a tie: on up to 576 tokens.  (Per launch at 512 tokens, Mistral-7B: 16-row kernel 18.6 us, wave pairs 19.2, four waves 15.6.)
-            if (ks2_mode == 4 || (ks2_mode < 0 && items2 < 2 * 256 && T <= 576)) {
-                ksf = 4;
-                gsub = G >= 4 ? 2 : 0;
-                TB = 8 / (gsub ? gsub : G) / 4;
-            }
-        }
-        const int64_t nb = (T + 32 * TB - 1) / (32 * TB);
-        const int64_t nhs = Hkv * (gsub ? (G + gsub - 1) / gsub : 1);
-        const int force_pair = tune(TK_ATTN_PF32_PAIRED);
-        // two rounds or more of (block, kv head) items: persistent workgroups, snake order (launch_pf32)
-        const int paired = force_pair >= 0 ? force_pair : (nb * nhs >= 2 * 256 ? 2 : ((nb + 1) / 2 * nhs >= 180 ? 1 : 0));
-        if (ksf == 4 && d == 128) return launch_pf32<128, 8, 4>(L, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window, TB, paired, gsub);
-        if (ksf == 4 && d == 64) return launch_pf32<64, 8, 4>(L, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window, TB, paired, gsub);
-        if (ks2 && d == 128) return launch_pf32<128, 8, 2>(L, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window, TB, paired, gsub);
-        if (ks2 && d == 64) return launch_pf32<64, 8, 2>(L, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window, TB, paired, gsub);
-#define FL_PF32(DD, WW) if (d == DD && NW == WW) return launch_pf32<DD, WW>(L, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window, TB, paired);
-        FL_PF32(128, 8) FL_PF32(128, 7) FL_PF32(128, 6) FL_PF32(128, 5) FL_PF32(64, 8) FL_PF32(64, 7) FL_PF32(64, 6) FL_PF32(64, 5)
-#undef FL_PF32
+    if (H / Hkv > 8) FL_FAIL(FL_ERR_UNSUPPORTED, "mfma prefill attention: at most 8 query heads per kv head");
+    if (d != 64 && d != 128) FL_FAIL(FL_ERR_UNSUPPORTED, "mfma attention: head_dim %lld", (long long)d);
+    // (force: fl_op_attention pins one kernel, unit tests; the snake grid: one persistent workgroup per CU of the CURRENT device)
+    const AttnPrefillPlan p = plan_attn_prefill(T, H, Hkv, d, g_prefill_force.load(), scale > 0.f, device_cu_count(), attn_prefill_tune());
+#define FL_PF32(DD, WW, KK) \
+    if (d == DD && p.nw == WW && p.ksf == KK) return launch_pf32<DD, WW, KK>(L, p, q, k_cache, v_cache_T, st, out, T, H, Hkv, seq_alloc, scale, window);
+    if (p.rows == 32) {
+        FL_PF32(128, 8, 4) FL_PF32(128, 8, 2) FL_PF32(128, 8, 1) FL_PF32(128, 7, 1) FL_PF32(128, 6, 1) FL_PF32(128, 5, 1)
+        FL_PF32(64, 8, 4) FL_PF32(64, 8, 2) FL_PF32(64, 8, 1) FL_PF32(64, 7, 1) FL_PF32(64, 6, 1) FL_PF32(64, 5, 1)
+        FL_FAIL(FL_ERR_UNSUPPORTED, "mfma prefill attention: no 32-row kernel of %d waves, key split %d", p.nw, p.ksf);
     }
-    // token sub-tiles per workgroup: every staged K/V tile then serves TT x G x 16 query rows.  Measured: G = 4
-    // (Mistral, T = 2048) 4.75 ms with 4 waves, 4.25 with 8, 4.06 with 16; G = 7 (Qwen2, T = 4096) 10.8 ms with 7
-    // waves, 12.3 with 14 (126 VGPRs: 16 waves per CU either way, and a longer token block is more lopsided under
-    // the causal mask)
-    // ... but only while the grid still covers the chip: at T = 512 (Mistral) 4-wave workgroups (256 of them) take
-    // 26 us per layer against 36 us for 64 16-wave ones; at T = 1024 8 waves 49 us against 57 (4) and 67 (16)
-    const int tt_waves = tune(TK_ATTN_PF_WAVES);
-    int TT = tt_waves > 0 ? std::max(1, std::min(16, tt_waves) / G) : (G <= 4 ? 16 / G : 1);
-    if (tt_waves <= 0)
-        while (TT > 1 && ((T + 16 * TT - 1) / (16 * TT)) * Hkv < 256) TT >>= 1;
-    dim3 grid((unsigned)((T + 16 * TT - 1) / (16 * TT)), (unsigned)Hkv);
-    dim3 block((unsigned)(G * TT * 64));
-    // LDS tiles in the ring (FL_ATTN_PF_STAGES, 2..4).  Measured: a deeper ring buys nothing -- Mistral T = 512 25 / 26 /
-    // 25 us per layer with 2 / 3 / 4 tiles, T = 768 41 / 40 / 42: with one wave per SIMD a key step is a chain of
-    // dependent LDS read -> MFMA -> shuffle -> exp -> MFMA latencies (~1.5 us), not a wait for the tile
-    const int pf_stages = tune(TK_ATTN_PF_STAGES);
-    int nst = std::max(2, std::min(4, G * TT <= 8 ? pf_stages : 2));
-    // key split (two waves per head and token sub-tile) while the workgroup stays within 8 waves: short prompts
-    const int pf_ksplit = tune(TK_ATTN_PF_KSPLIT);
-    // (four waves per query tile measured slower than two: Mistral T = 512 23 vs 18 us per layer, T = 768 45 vs 33)
-    // ... while the workgroup stays within 16 waves and its merge slabs within the 64 KB of LDS a launch gets by default
-    const size_t slabs = (size_t)G * TT * (16 * d + 32) * 4;
-    const int ks = (pf_ksplit >= 2 && G * TT * 2 <= 16 && slabs <= 64 * 1024) ? 2 : 1;
-    if (ks == 2) { nst = 2; block = dim3((unsigned)(G * TT * 2 * 64)); }
-    const size_t lds = std::max((size_t)nst * ks * (size_t)(2 * 32 * d * 2), ks == 2 ? slabs : (size_t)0);
-    double flops = 2.0 * (double)T * T * H * d;
-    if (d == 128)
-        return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_mfma_kernel<128>, grid, block, lds, (const bf16_t *)q,
-                        (const bf16_t *)k_cache, (const bf16_t *)v_cache_T, st, (bf16_t *)out, (int)T, (int)H, (int)Hkv,
-                        (int)seq_alloc, scale, (int)window, TT, nst, ks);
-    if (d == 64)
-        return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_mfma_kernel<64>, grid, block, lds, (const bf16_t *)q,
-                        (const bf16_t *)k_cache, (const bf16_t *)v_cache_T, st, (bf16_t *)out, (int)T, (int)H, (int)Hkv,
-                        (int)seq_alloc, scale, (int)window, TT, nst, ks);
-    FL_FAIL(FL_ERR_UNSUPPORTED, "mfma attention: head_dim %lld", (long long)d);
+#undef FL_PF32
+    const double flops = 2.0 * (double)T * T * H * d;
+#define FL_PF16(DD, KK)                                                                                                               \
+    if (d == DD && p.ks == KK)                                                                                                        \
+        return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_mfma_kernel<DD, KK>, dim3(p.grid_x, p.grid_y), dim3((unsigned)p.block), \
+                        p.lds, (const bf16_t *)q, (const bf16_t *)k_cache, (const bf16_t *)v_cache_T, st, (bf16_t *)out, (int)T, (int)H, \
+                        (int)Hkv, (int)seq_alloc, scale, (int)window, p.TT, p.nst);
+    FL_PF16(128, 2) FL_PF16(128, 1) FL_PF16(64, 2) FL_PF16(64, 1)
+#undef FL_PF16
+    FL_FAIL(FL_ERR_UNSUPPORTED, "mfma prefill attention: no 16-row kernel with key split %d", p.ks);
 }
 
 }  // namespace fl

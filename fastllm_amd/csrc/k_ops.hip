@@ -122,47 +122,18 @@ int launch_rms_finalize(Launcher &L, const float *part, int np, float eps, float
 // candle_nn::rotary_emb::rope (rotate-half, App. A.4) on q and k, then the new K/V rows are
 // written in place at cache index len+t (the reference's Tensor::cat copies the whole cache every
 // step, K5).  One thread per (t, head, j < d/2) pair.  cos/sin come from host-built fp32 tables.
+// The arithmetic is rope_kv_load / rope_kv_store (common.h), shared with the batched and the packed form: a kernel resolves its row.
 template <typename CT>
 __global__ __launch_bounds__(256) void rope_kv_kernel(const float *__restrict__ qkv, const StepState *__restrict__ st,
                                                       const float *__restrict__ cos_tab, const float *__restrict__ sin_tab,
                                                       int max_pos, CT *__restrict__ q_out, CT *__restrict__ kc,
                                                       CT *__restrict__ vc, int T, int H, int Hkv, int d, int max_seq,
-                                                      int v_transposed, int nslab, long long slab_stride,
-                                                      const float *__restrict__ bias) {
-    const int half = d >> 1;
-    const int nheads = H + 2 * Hkv;
-    const int per_t = nheads * half;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)T * per_t) return;
-    const int t = (int)(idx / per_t), rem = (int)(idx % per_t);
-    const int hd = rem / half, j = rem % half;
-    const float *src = qkv + (size_t)t * nheads * d + (size_t)hd * d;
-    float a = src[j], b = src[j + half];
-    for (int sl = 1; sl < nslab; sl++) {             // split-K slabs of the projection, summed in slab order
-        a += src[(size_t)sl * slab_stride + j];
-        b += src[(size_t)sl * slab_stride + j + half];
-    }
-    if (bias) { a += bias[(size_t)hd * d + j]; b += bias[(size_t)hd * d + j + half]; }     // (the projection ran in K slices: its bias comes here)
-    const uint32_t pos = st->pos + (uint32_t)t, slot = st->len + (uint32_t)t;
-    if (hd < H + Hkv) {
-        const uint32_t p = pos < (uint32_t)max_pos ? pos : (uint32_t)max_pos - 1;   // host validates range
-        const float c = cos_tab[(size_t)p * half + j], s = sin_tab[(size_t)p * half + j];
-        float ra, rb;
-        rope_rotate(a, b, c, s, ra, rb);
-        if (hd < H) {
-            CT *o = q_out + ((size_t)t * H + hd) * d;
-            elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);
-        } else {
-            CT *o = kc + ((size_t)(hd - H) * max_seq + slot) * d;
-            elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);
-        }
-    } else if (v_transposed) {                     // [Hkv][d][max_seq]: one key column per token
-        CT *o = vc + (size_t)(hd - H - Hkv) * d * max_seq + slot;
-        elem<CT>::st(o + (size_t)j * max_seq, a); elem<CT>::st(o + (size_t)(j + half) * max_seq, b);
-    } else {
-        CT *o = vc + ((size_t)(hd - H - Hkv) * max_seq + slot) * d;
-        elem<CT>::st(o + j, a); elem<CT>::st(o + j + half, b);
-    }
+                                                      int v_transposed, int nslab, const float *__restrict__ bias) {
+    RopeKvPair p;
+    if (!rope_kv_load(qkv, (long long)blockIdx.x * 256 + threadIdx.x, T, H, Hkv, d, nslab, bias, p)) return;
+    void *const k = kc, *const v = vc;
+    const RopeKvDst dst{q_out + (size_t)p.r * H * d, &k, &v, 0, (size_t)max_seq, &v_transposed};
+    rope_kv_store<CT>(p, st->pos + (uint32_t)p.r, st->len + (uint32_t)p.r, cos_tab, sin_tab, max_pos, H, Hkv, d, dst);
 }
 
 // The prompt-sized form (bf16, transposed value cache, T > 1): 8 pairs per thread with 16-byte loads / stores for q and k,
@@ -261,10 +232,10 @@ int launch_rope_kv(Launcher &L, int dtype, const float *qkv, const StepState *st
     if (dtype == FL_DTYPE_BF16)
         return L.launch(KC_ROPE_KV, bytes, 0, rope_kv_kernel<bf16_t>, dim3(blocks), dim3(256), 0, qkv, st, cos_tab,
                         sin_tab, (int)max_pos, (bf16_t *)q_out, (bf16_t *)k_cache, (bf16_t *)v_cache, (int)T, (int)H,
-                        (int)Hkv, (int)d, (int)max_seq, (int)v_transposed, nslab, slab_stride, bias);
+                        (int)Hkv, (int)d, (int)max_seq, (int)v_transposed, nslab, bias);
     return L.launch(KC_ROPE_KV, bytes, 0, rope_kv_kernel<float>, dim3(blocks), dim3(256), 0, qkv, st, cos_tab,
                     sin_tab, (int)max_pos, (float *)q_out, (float *)k_cache, (float *)v_cache, (int)T, (int)H,
-                    (int)Hkv, (int)d, (int)max_seq, (int)v_transposed, nslab, slab_stride, bias);
+                    (int)Hkv, (int)d, (int)max_seq, (int)v_transposed, nslab, bias);
 }
 
 // ------------------------------------------------------------------------------- batched variants (row N4)
@@ -296,38 +267,13 @@ __global__ __launch_bounds__(256) void rope_kv_batch_kernel(const float *__restr
                                                             const float *__restrict__ cos_tab, const float *__restrict__ sin_tab,
                                                             int max_pos, CT *__restrict__ q_out, size_t kv_layer_off, int B,
                                                             int H, int Hkv, int d, int n_slab, const float *__restrict__ bias) {
-    const int half = d >> 1;
-    const int nheads = H + 2 * Hkv;
-    const int per_t = nheads * half;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)B * per_t) return;
-    const int b = (int)(idx / per_t), rem = (int)(idx % per_t);
-    const int hd = rem / half, j = rem % half;
-    const SeqRef &sq = seqs[b];
-    const float *src = qkv + (size_t)b * nheads * d + (size_t)hd * d;
-    float a = src[j], bb = src[j + half];
-    for (int s = 1; s < n_slab; s++) {                    // K slices of the projection, summed in slab order
-        const float *ss = src + (size_t)s * B * nheads * d;
-        a += ss[j]; bb += ss[j + half];
-    }
-    if (bias) { a += bias[hd * d + j]; bb += bias[hd * d + j + half]; }
-    const uint32_t pos = sq.st->pos, slot = sq.st->len;
+    RopeKvPair p;
+    if (!rope_kv_load(qkv, (long long)blockIdx.x * 256 + threadIdx.x, B, H, Hkv, d, n_slab, bias, p)) return;
+    const SeqRef &sq = seqs[p.r];
     const size_t sa = (size_t)sq.seq_alloc;
-    if (hd < H + Hkv) {
-        const uint32_t p = pos < (uint32_t)max_pos ? pos : (uint32_t)max_pos - 1;
-        const float c = cos_tab[(size_t)p * half + j], s = sin_tab[(size_t)p * half + j];
-        float ra, rb;
-        rope_rotate(a, bb, c, s, ra, rb);
-        CT *o = hd < H ? q_out + ((size_t)b * H + hd) * d
-                       : reinterpret_cast<CT *>(sq.k) + kv_layer_off * sa + ((size_t)(hd - H) * sa + slot) * d;
-        elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);
-    } else if (VT) {                                      // V transposed [Hkv][d][seq_alloc]: the MFMA attention layout
-        CT *o = reinterpret_cast<CT *>(sq.v) + kv_layer_off * sa + (size_t)(hd - H - Hkv) * d * sa + slot;
-        elem<CT>::st(o + (size_t)j * sa, a); elem<CT>::st(o + (size_t)(j + half) * sa, bb);
-    } else {                                              // V [Hkv][seq_alloc][d]
-        CT *o = reinterpret_cast<CT *>(sq.v) + kv_layer_off * sa + ((size_t)(hd - H - Hkv) * sa + slot) * d;
-        elem<CT>::st(o + j, a); elem<CT>::st(o + j + half, bb);
-    }
+    const int vt = VT;
+    const RopeKvDst dst{q_out + (size_t)p.r * H * d, &sq.k, &sq.v, kv_layer_off * sa, sa, &vt};
+    rope_kv_store<CT>(p, sq.st->pos, sq.st->len, cos_tab, sin_tab, max_pos, H, Hkv, d, dst);
 }
 
 int launch_rope_kv_batch(Launcher &L, const float *qkv, const SeqRef *seqs_dev, const float *cos_tab, const float *sin_tab,

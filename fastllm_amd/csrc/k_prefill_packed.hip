@@ -5,7 +5,8 @@
 // Both read a small device table the host builds per call (PackedTable, kernels.h).  No kernel waits for another workgroup, there
 // are no tickets, spins or atomics, and no sum is ever formed over rows of two sequences: a sequence's output rows depend on that
 // sequence alone, whatever else the pack holds and wherever in the pack it sits.
-#include "attn_mfma.h"
+#include "attn_prefill16.h"
+#include "attn_prefill_plan.h"
 #include "kernels.h"
 
 #include <algorithm>
@@ -13,48 +14,21 @@
 namespace fl {
 
 // ------------------------------------------------------------------------------- RoPE + KV append
-// The arithmetic of rope_kv_kernel / rope_kv_batch_kernel, in their order: the projection's fp32 K slabs summed in slab order, the
-// (Qwen2) bias, rotate-half RoPE at st->pos + t, the store in the cache's element type.  q goes to the packed [T_total][H*d] buffer;
-// k and v to slot st->len + t of the row's own cache (layer offset kv_layer_off * seq_alloc of that sequence, V transposed or
-// row-major as the sequence's cache is laid out).  One thread per (row, head, j < d/2) pair.
+// rope_kv_load / rope_kv_store (common.h), the body of rope_kv_kernel and rope_kv_batch_kernel too, on row r of the pack: RoPE at
+// st->pos + t of the row's sequence; q goes to the packed [T_total][H*d] buffer, k and v to slot st->len + t of the row's own cache
+// (layer offset kv_layer_off * seq_alloc of that sequence, V transposed or row-major as the sequence's cache is laid out).
 template <typename CT>
 __global__ __launch_bounds__(256) void rope_kv_packed_kernel(const float *__restrict__ qkv, const PackedTable tb,
                                                              const float *__restrict__ cos_tab, const float *__restrict__ sin_tab,
                                                              int max_pos, CT *__restrict__ q_out, size_t kv_layer_off, int T_total,
                                                              int H, int Hkv, int d, int n_slab, const float *__restrict__ bias) {
-    const int half = d >> 1;
-    const int nheads = H + 2 * Hkv;
-    const int per_t = nheads * half;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)T_total * per_t) return;
-    const int r = (int)(idx / per_t), rem = (int)(idx % per_t);
-    const int hd = rem / half, j = rem % half;
-    const PackedRow row = tb.rows[r];
+    RopeKvPair p;
+    if (!rope_kv_load(qkv, (long long)blockIdx.x * 256 + threadIdx.x, T_total, H, Hkv, d, n_slab, bias, p)) return;
+    const PackedRow row = tb.rows[p.r];
     const SeqRef &sq = tb.seqs[row.seq];
-    const float *src = qkv + (size_t)r * nheads * d + (size_t)hd * d;
-    float a = src[j], b = src[j + half];
-    for (int s = 1; s < n_slab; s++) {                    // K slices of the projection, summed in slab order
-        const float *ss = src + (size_t)s * T_total * nheads * d;
-        a += ss[j]; b += ss[j + half];
-    }
-    if (bias) { a += bias[(size_t)hd * d + j]; b += bias[(size_t)hd * d + j + half]; }
-    const uint32_t pos = sq.st->pos + (uint32_t)row.t, slot = sq.st->len + (uint32_t)row.t;
     const size_t sa = (size_t)sq.seq_alloc;
-    if (hd < H + Hkv) {
-        const uint32_t p = pos < (uint32_t)max_pos ? pos : (uint32_t)max_pos - 1;   // host validates range
-        const float c = cos_tab[(size_t)p * half + j], s = sin_tab[(size_t)p * half + j];
-        float ra, rb;
-        rope_rotate(a, b, c, s, ra, rb);
-        CT *o = hd < H ? q_out + ((size_t)r * H + hd) * d
-                       : reinterpret_cast<CT *>(sq.k) + kv_layer_off * sa + ((size_t)(hd - H) * sa + slot) * d;
-        elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);
-    } else if (tb.seq_vt[row.seq]) {                      // V transposed [Hkv][d][seq_alloc]: the MFMA attention layout
-        CT *o = reinterpret_cast<CT *>(sq.v) + kv_layer_off * sa + (size_t)(hd - H - Hkv) * d * sa + slot;
-        elem<CT>::st(o + (size_t)j * sa, a); elem<CT>::st(o + (size_t)(j + half) * sa, b);
-    } else {                                              // V [Hkv][seq_alloc][d]
-        CT *o = reinterpret_cast<CT *>(sq.v) + kv_layer_off * sa + ((size_t)(hd - H - Hkv) * sa + slot) * d;
-        elem<CT>::st(o + j, a); elem<CT>::st(o + j + half, b);
-    }
+    const RopeKvDst dst{q_out + (size_t)p.r * H * d, &sq.k, &sq.v, kv_layer_off * sa, sa, &tb.seq_vt[row.seq]};
+    rope_kv_store<CT>(p, sq.st->pos + (uint32_t)row.t, sq.st->len + (uint32_t)row.t, cos_tab, sin_tab, max_pos, H, Hkv, d, dst);
 }
 
 int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const PackedTable &tb, const float *cos_tab, const float *sin_tab,
@@ -72,180 +46,29 @@ int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const Packed
 }
 
 // ------------------------------------------------------------------------------- ragged causal attention
-// attn_prefill_mfma_kernel (k_attn_mfma.hip) with the workgroup's sequence looked up instead of passed in:
-// grid (items, Hkv); item = 16 * TT consecutive tokens of ONE sequence, starting at its token t0 (a multiple of 16 * TT); workgroup =
-// G * TT waves, wave w serving query head w % G for the 16 tokens of sub-tile w / G.  The sequence's K / V^T tiles of 32 keys go
-// through the LDS ring by LDS-DMA once per workgroup; len, call0, the cache bases and seq_alloc come from the item's SeqRef.
-// Columns past the sequence's end carry q = 0 and are not stored.  A wave skips the tiles wholly outside its own visible range
-// (wstart / wend), staging is never skipped.
-// KS == 2: the wave-pair key split of the 16-row kernel, which is what a single short prompt runs (FL_ATTN_PF_KSPLIT): two waves per
-// (head, sub-tile) take alternate key tiles and merge through LDS at the end, so a packed member gets the arithmetic -- and the bits
-// -- of its single forward.  Which of the pair takes a tile is counted from the WAVE's own first useful tile (wstart), not from the
-// workgroup's first staged tile.
-// Either way the tiles a wave computes on, their order and their split over the pair depend on its own 16 tokens, its sequence's
-// lengths and the head shape only -- not on TT, the ring depth or the rest of the pack.
+// prefill16_body (attn_prefill16.h), the body of attn_prefill_mfma_kernel (k_attn_mfma.hip) too, with the workgroup's sequence looked
+// up instead of passed in: grid (items, Hkv); item = 16 * TT consecutive tokens of ONE sequence, starting at its token t0 (a multiple
+// of 16 * TT); T, len, call0 (== len: a packed call is never chunked), the cache bases and seq_alloc come from the item's SeqRef.
+// KS == 2 is the wave-pair key split a single short prompt runs, so a packed member gets the arithmetic -- and at TT = 1, where the
+// single prompt's alternation starts at the same tile, the bits -- of its single forward.  Here the pair's alternation is counted from
+// the WAVE's own first useful tile (OWN_ORIGIN): the tiles a wave computes on, their order and their split over the pair depend on
+// its own 16 tokens, its sequence's lengths and the head shape only -- not on TT, the ring depth or the rest of the pack.
 template <int D, int KS>
 __global__ __launch_bounds__(1024) void attn_prefill_packed_mfma_kernel(const bf16_t *__restrict__ q, const PackedTable tb, size_t kv_layer_off,
                                                                        bf16_t *__restrict__ out, int H, int Hkv, float scale, int window,
                                                                        int TT, int nst) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // nst x (K tile | V^T tile)
-    constexpr int TILE = 2 * 32 * D * 2;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
-    const int i = lane & 15, g4 = lane >> 4;
-    const int G = H / Hkv, hk = blockIdx.y;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // nst x KS x (K tile | V^T tile)
+    const int hk = blockIdx.y;
     const PackedItem item = tb.items[blockIdx.x];
     const SeqRef &sq = tb.seqs[item.seq];
-    const int T = __builtin_amdgcn_readfirstlane(tb.seq_cnt[item.seq]);   // the sequence's new tokens (everything of the item is wave-uniform)
-    const size_t row0 = (size_t)tb.seq_off[item.seq];            // ... and its first row in the packed buffers
-    q += row0 * H * D; out += row0 * H * D;                      // (from here on q / out are the sequence's own rows)
-    const int seq_alloc = __builtin_amdgcn_readfirstlane(sq.seq_alloc);
-    const int wq = wave % (G * TT), half = wave / (G * TT);      // (half: KS == 2 only)
-    const int hq = hk * G + wq % G;
-    const int tb0 = __builtin_amdgcn_readfirstlane(item.t0);     // first token of the workgroup
-    const int t0 = tb0 + (wq / G) * 16;                          // first token of this wave
-    const int len = __builtin_amdgcn_readfirstlane((int)sq.st->len);
-    const int t = t0 + i;                                        // this lane's column
-    const bool col_ok = t < T;
-
-    bf16x8 qf[D / 32];
-#pragma unroll
-    for (int dk = 0; dk < D / 32; dk++) {
-        if (col_ok) qf[dk] = ld_bf16x8(q + ((size_t)t * H + hq) * D + dk * 32 + g4 * 8);
-        else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) qf[dk][j] = (__bf16)0.f;
-        }
-    }
-    // the keys cached before the call are an unmasked prefix (call0 == len: a packed call is never chunked); the causal +
-    // sliding-window mask runs over the sequence's own new tokens
-    const int c0 = __builtin_amdgcn_readfirstlane((int)sq.st->call0);
-    int lo = c0;
-    if (window >= 0 && len + t - window > c0) lo = len + t - window;
-    const int lo_q = col_ok ? lo : 0, hi_q = col_ok ? len + t + 1 : 0;
-    const int pre_hi = col_ok ? c0 : 0;
-    int wstart = 0;
-    if (c0 == 0 && window >= 0 && len + t0 - window > 0) wstart = ((len + t0 - window) / 32) * 32;
-    const int wend = t0 < T ? len + min(T, t0 + 16) : 0;
-
-    MfmaAttnState<D> s; s.init();
-    const bf16_t *kb = reinterpret_cast<const bf16_t *>(sq.k) + kv_layer_off * (size_t)seq_alloc + (size_t)hk * seq_alloc * D;
-    const bf16_t *vb = reinterpret_cast<const bf16_t *>(sq.v) + kv_layer_off * (size_t)seq_alloc + (size_t)hk * D * seq_alloc;
-    int kstart = 0;
-    if (c0 == 0 && window >= 0 && len + tb0 - window > 0) kstart = ((len + tb0 - window) / 32) * 32;
-    const int kend = len + min(T, tb0 + 16 * TT);                // <= the cache's capacity <= seq_alloc (a multiple of 32)
-    const int nsteps = (kend - kstart + 31) / 32;
-    constexpr int NI = D / 16 + D / 16;
-    const int per = (NI + nwv - 1) / nwv;
-    if constexpr (KS == 2) {
-        // super-steps of two tiles (buffers [stage][tile]); one barrier per super-step, two LDS stages
-        const int nsuper = (nsteps + 1) / 2;
-        const int mine = half ^ (((max(wstart, kstart) - kstart) >> 5) & 1);     // this wave's tile of every super-step
-        auto stage2 = [&](int ss, int stg) {
-            const int k0 = kstart + 64 * ss;
-            stage_kv<D>(kb, vb, seq_alloc, k0, lds + (stg * 2) * TILE, wave, nwv, lane, per);
-            if (k0 + 32 < kend) stage_kv<D>(kb, vb, seq_alloc, k0 + 32, lds + (stg * 2 + 1) * TILE, wave, nwv, lane, per);
-        };
-        stage2(0, 0);
-        for (int ss = 0; ss < nsuper; ss++) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (ss + 1 < nsuper) stage2(ss + 1, (ss + 1) & 1);
-            const int kbase = kstart + 64 * ss + 32 * mine;
-            if (kbase < kend && kbase + 32 > wstart && kbase < wend) {               // wave-uniform
-                const unsigned char *cur = lds + ((ss & 1) * 2 + mine) * TILE;
-                const LdsKV<D> kv{cur, cur + 32 * D * 2, i, g4};
-                attn_tile<D>(s, qf, kv, kbase, pre_hi, lo_q, hi_q, scale, lane);
-            }
-        }
-        // merge the two key halves through LDS (the tiles are dead after the barrier), as the 16-row kernel does
-        __syncthreads();
-        float *slab = reinterpret_cast<float *>(lds) + (size_t)wq * (16 * D + 32);
-        float lt1 = s.l;
-        lt1 += __shfl_xor(lt1, 16, 64);
-        lt1 += __shfl_xor(lt1, 32, 64);
-        if (half == 1) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int db = 0; db < D / 16; db++) slab[(4 * g4 + r) * D + db * 16 + i] = s.O[db][r];
-            if (g4 == 0) { slab[16 * D + i] = s.m; slab[16 * D + 16 + i] = lt1; }
-        }
-        __syncthreads();
-        if (half == 1) return;
-        const float m1 = slab[16 * D + i], l1 = slab[16 * D + 16 + i];
-        const float mm = fmaxf(s.m, m1);
-        const float w0 = s.m == -INFINITY ? 0.f : __expf(s.m - mm), w1 = m1 == -INFINITY ? 0.f : __expf(m1 - mm);
-        const float ltot = lt1 * w0 + l1 * w1;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int qq = 4 * g4 + r;
-            const float lr = __shfl(ltot, qq, 64), a0 = __shfl(w0, qq, 64), a1 = __shfl(w1, qq, 64);
-            const int tt = t0 + qq;
-            if (tt < T) {
-                const float inv = 1.0f / lr;
-                bf16_t *o = out + ((size_t)tt * H + hq) * D;
-#pragma unroll
-                for (int db = 0; db < D / 16; db++)
-                    o[db * 16 + i] = float_to_bf16_bits((s.O[db][r] * a0 + slab[qq * D + db * 16 + i] * a1) * inv);
-            }
-        }
-        return;
-    } else {
-        // the plain ring of nst tiles, nst - 1 of them in flight
-        for (int a = 0; a < nst - 1 && a < nsteps; a++) stage_kv<D>(kb, vb, seq_alloc, kstart + 32 * a, lds + a * TILE, wave, nwv, lane, per);
-        for (int sidx = 0; sidx < nsteps; sidx++) {
-            wait_vmcnt(per * min(nst - 2, nsteps - 1 - sidx));       // tile sidx has landed; the younger ones may still fly
-            __builtin_amdgcn_s_barrier();
-            const int kbase = kstart + 32 * sidx;
-            if (sidx + nst - 1 < nsteps)
-                stage_kv<D>(kb, vb, seq_alloc, kbase + 32 * (nst - 1), lds + ((sidx + nst - 1) % nst) * TILE, wave, nwv, lane, per);
-            if (kbase + 32 > wstart && kbase < wend) {               // wave-uniform
-                const unsigned char *cur = lds + (sidx % nst) * TILE;
-                const LdsKV<D> kv{cur, cur + 32 * D * 2, i, g4};
-                attn_tile<D>(s, qf, kv, kbase, pre_hi, lo_q, hi_q, scale, lane);
-            }
-        }
-
-        float lt = s.l;
-        lt += __shfl_xor(lt, 16, 64);
-        lt += __shfl_xor(lt, 32, 64);
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int qq = 4 * g4 + r;
-            const float lr = __shfl(lt, qq, 64);
-            const int tt = t0 + qq;
-            if (tt < T) {
-                const float inv = 1.0f / lr;
-                bf16_t *o = out + ((size_t)tt * H + hq) * D;
-#pragma unroll
-                for (int db = 0; db < D / 16; db++) o[db * 16 + i] = float_to_bf16_bits(s.O[db][r] * inv);
-            }
-        }
-    }
-}
-
-// Token sub-tiles per workgroup and the key split.  ks: the wave pairs of the 16-row kernel wherever ONE sub-tile's pairs and merge
-// slabs fit (its own rule at TT = 1, what a single short prompt gets) -- a function of the head shape alone, so that a member's
-// arithmetic never depends on the pack.  TT: as the 16-row kernel picks it (every staged tile then serves TT x G x 16 query rows),
-// within what ks allows, halved while the items do not cover the chip or while half the sub-tiles still hold the longest member.
-// counts: the new tokens of the members the launch serves.
-void attn_packed_geometry(int64_t H, int64_t Hkv, int64_t d, const int *counts, int n, int *TT_out, int *ks_out) {
-    const int G = (int)(H / Hkv);
-    const int tt_waves = tune(TK_ATTN_PF_WAVES);
-    auto fits2 = [&](int tt) { return tune(TK_ATTN_PF_KSPLIT) >= 2 && G * tt * 2 <= 16 && (size_t)G * tt * (16 * d + 32) * 4 <= 64 * 1024; };
-    if (tt_waves > 0) {
-        *TT_out = std::max(1, std::min(16, tt_waves) / G);
-        *ks_out = fits2(*TT_out) ? 2 : 1;
-        return;
-    }
-    const int ks = fits2(1) ? 2 : 1;
-    int TT = G <= 4 ? 16 / G : 1;
-    while (ks == 2 && TT > 1 && !fits2(TT)) TT >>= 1;
-    int longest = 0;
-    for (int s = 0; s < n; s++) longest = std::max(longest, counts[s]);
-    auto items = [&](int tt) { int64_t k = 0; for (int s = 0; s < n; s++) k += (counts[s] + 16 * tt - 1) / (16 * tt); return k; };
-    while (TT > 1 && (items(TT) * Hkv < 256 || 16 * (TT >> 1) >= longest)) TT >>= 1;
-    *TT_out = TT; *ks_out = ks;
+    const size_t row0 = (size_t)tb.seq_off[item.seq];            // the sequence's first row in the packed buffers
+    const int seq_alloc = __builtin_amdgcn_readfirstlane(sq.seq_alloc);      // (everything of the item is wave-uniform)
+    const size_t layer = kv_layer_off * (size_t)seq_alloc;
+    const Prefill16Seq v{q + row0 * H * D, reinterpret_cast<const bf16_t *>(sq.k) + layer + (size_t)hk * seq_alloc * D,
+                         reinterpret_cast<const bf16_t *>(sq.v) + layer + (size_t)hk * D * seq_alloc, out + row0 * H * D,
+                         __builtin_amdgcn_readfirstlane(tb.seq_cnt[item.seq]), __builtin_amdgcn_readfirstlane((int)sq.st->len),
+                         __builtin_amdgcn_readfirstlane((int)sq.st->call0), seq_alloc, __builtin_amdgcn_readfirstlane(item.t0)};
+    prefill16_body<D, KS, true>(v, hk, H, Hkv, scale, window, TT, nst, lds);
 }
 
 PackedTable PackedHost::at(const void *dev_base) const {
@@ -263,7 +86,10 @@ void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, in
     for (int s = 0; s < n; s++) if (vt[s]) mfma_counts.push_back(counts[s]);
     p.n_seq = n;
     p.TT = 1; p.ks = 1;
-    if (!mfma_counts.empty()) attn_packed_geometry(H, Hkv, d, mfma_counts.data(), (int)mfma_counts.size(), &p.TT, &p.ks);
+    if (!mfma_counts.empty()) {
+        const AttnPackedPlan g = plan_attn_prefill_packed(H, Hkv, d, mfma_counts.data(), (int)mfma_counts.size(), attn_prefill_tune());
+        p.TT = g.TT; p.ks = g.ks;
+    }
     std::vector<PackedRow> rows;
     std::vector<PackedItem> items;
     std::vector<int> off((size_t)n);
@@ -292,16 +118,14 @@ int launch_attn_prefill_packed_mfma(Launcher &L, const void *q, const PackedTabl
                                     int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops) {
     const int G = (int)(H / Hkv);
     if (!attn_mfma_supported(FL_DTYPE_BF16, H, Hkv, d)) FL_FAIL(FL_ERR_UNSUPPORTED, "packed mfma attention: head_dim 64 / 128, at most 8 query heads per kv head");
-    const size_t slabs = (size_t)G * TT * (16 * d + 32) * 4;     // ks == 2: the merge slabs, in the tiles' place
-    if (TT < 1 || (ks != 1 && ks != 2) || G * TT * ks > 16 || (ks == 2 && slabs > 64 * 1024))
+    if (TT < 1 || (ks != 1 && ks != 2) || G * TT * ks > 16 || (ks == 2 && prefill16_slab_bytes(G, d, TT) > kPfDefaultLds))
         FL_FAIL(FL_ERR_BAD_ARGUMENT, "packed mfma attention: %d x %d x %d waves per workgroup", G, TT, ks);
-    const dim3 grid((unsigned)n_items, (unsigned)Hkv), block((unsigned)(G * TT * ks * 64));
-    // ring depth and LDS of the 16-row kernel at this TT (launch_attn_prefill_mfma): never more LDS than it takes there
-    const int nst = ks == 2 ? 2 : std::max(2, std::min(4, G * TT <= 8 ? tune(TK_ATTN_PF_STAGES) : 2));
-    const size_t lds = std::max((size_t)nst * ks * (size_t)(2 * 32 * d * 2), ks == 2 ? slabs : (size_t)0);
+    // ring depth, LDS and block of the 16-row kernel at this TT: never more LDS than the single prompt takes there
+    const Prefill16Launch l = prefill16_launch(G, d, TT, ks, attn_prefill_tune());
+    const dim3 grid((unsigned)n_items, (unsigned)Hkv), block((unsigned)l.block);
 #define FL_PACKED(DD, KK)                                                                                                                  \
-    return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_packed_mfma_kernel<DD, KK>, grid, block, lds, (const bf16_t *)q, tb, kv_layer_off, \
-                    (bf16_t *)out, (int)H, (int)Hkv, scale, (int)window, TT, nst);
+    return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_packed_mfma_kernel<DD, KK>, grid, block, l.lds, (const bf16_t *)q, tb, kv_layer_off, \
+                    (bf16_t *)out, (int)H, (int)Hkv, scale, (int)window, TT, l.nst);
     if (d == 128) { if (ks == 2) { FL_PACKED(128, 2) } FL_PACKED(128, 1) }
     if (ks == 2) { FL_PACKED(64, 2) }
     FL_PACKED(64, 1)

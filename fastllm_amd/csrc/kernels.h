@@ -245,14 +245,15 @@ int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const Packed
                           int64_t max_pos, void *q_out, size_t kv_layer_off, int64_t T_total, int64_t H, int64_t Hkv, int64_t d, int n_slab = 1,
                           const float *bias = nullptr);
 // bf16, MFMA layout: causal / sliding-window attention of every item's tokens over their own sequence's cache (mask as
-// launch_attn_prefill_mfma, per sequence); q / out [T_total][H*d].  TT, ks: what attn_packed_geometry chose (tb.items were cut for
-// TT); ks 2: the 16-row kernel's wave-pair key split, 1: its plain ring
-void attn_packed_geometry(int64_t H, int64_t Hkv, int64_t d, const int *counts, int n, int *TT_out, int *ks_out);
+// launch_attn_prefill_mfma, per sequence); q / out [T_total][H*d].  TT, ks: what plan_attn_prefill_packed (attn_prefill_plan.h) chose
+// (tb.items were cut for TT); ks 2: the 16-row kernel's wave-pair key split, 1: its plain ring
+struct AttnPrefillTune;
+AttnPrefillTune attn_prefill_tune();   // the prefill attention plans' switches as tune() has them now (k_attn_mfma.hip)
 int launch_attn_prefill_packed_mfma(Launcher &L, const void *q, const PackedTable &tb, int n_items, int TT, int ks, size_t kv_layer_off, void *out,
                                     int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops = 0);
 // The host image of one call's table: the arrays back to back (SeqRef first: it holds pointers), and where each begins.  Items are
 // cut, 16 * TT tokens each, for the members with vt[s] != 0 only (the others' attention runs per sequence); TT and ks from
-// attn_packed_geometry over those members.
+// plan_attn_prefill_packed over those members.
 struct PackedHost {
     std::vector<unsigned char> bytes;
     size_t off_seqs = 0, off_rows = 0, off_items = 0, off_off = 0, off_cnt = 0, off_vt = 0;

@@ -81,13 +81,20 @@ def test_decode_kernel(fa, d, H, Hkv, S, nsplit):
     check(got, reference(q, k, v, S - 1, H, Hkv, d, -1), "decode d=%d G=%d S=%d nsplit=%d" % (d, H // Hkv, S, nsplit))
 
 
+PREFILL_CASES = [(2, 0, -1), (16, 0, -1), (33, 0, -1), (100, 0, 5), (130, 0, 32), (257, 0, -1), (64, 40, -1), (70, 129, 17)]   # (T, s_past, window)
+
+
+def prefill_inputs(T, s_past, H, Hkv, d, kernel):
+    """q, k, v of one test_prefill_kernels case (tools/output_digests.py runs the same cases)"""
+    return make(T, s_past, H, Hkv, d, seed=T * 3 + s_past + d + H + kernel)
+
+
 @pytest.mark.parametrize("d", [64, 128])
 @pytest.mark.parametrize("H,Hkv", GROUPS)
 @pytest.mark.parametrize("kernel", [2, 3])
-@pytest.mark.parametrize("T,s_past,window", [(2, 0, -1), (16, 0, -1), (33, 0, -1), (100, 0, 5), (130, 0, 32), (257, 0, -1),
-                                             (64, 40, -1), (70, 129, 17)])
+@pytest.mark.parametrize("T,s_past,window", PREFILL_CASES)
 def test_prefill_kernels(fa, d, H, Hkv, kernel, T, s_past, window):
-    q, k, v = make(T, s_past, H, Hkv, d, seed=T * 3 + s_past + d + H + kernel)
+    q, k, v = prefill_inputs(T, s_past, H, Hkv, d, kernel)
     got = fa.op_attention(q, k, v, s_past, H, Hkv, d, window=window, kernel=kernel)
     check(got, reference(q, k, v, s_past, H, Hkv, d, window), "prefill%d d=%d G=%d T=%d past=%d w=%d" % (kernel, d, H // Hkv, T, s_past, window))
 

@@ -2,13 +2,14 @@
 against the fp64 reference of the single-sequence op tests per sequence, under the bound those tests use (test_gpu_attention_ops.check:
 max error <= 1.2e-2 * scale, rel. L2 <= 5e-3).  Cache geometry that catches a wrong base or stride: seq_alloc differs per member,
 the launch reads layer 1 of two (layer 0 holds other data), two stale rows follow every member's keys, everything behind holds 1e4.
-Isolation: a member's output rows are bit-identical packed alone and packed among the others, wherever in the pack it sits."""
+Isolation: a member's output rows are bit-identical packed alone and packed among the others, wherever in the pack it sits.
+The shared body (attn_prefill16.h): a member packed alone has the bits of the single-prompt 16-row kernel on the same sequence."""
 import numpy as np
 import pytest
 
 import attn_cases
 import synth
-from test_gpu_attention_ops import check
+from test_gpu_attention_ops import check, make, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +29,7 @@ PACKS = {
 
 
 def expected_tt(H, Hkv, d, counts):
-    """attn_packed_geometry (k_prefill_packed.hip) restated: token sub-tiles per workgroup at the default switches"""
+    """plan_attn_prefill_packed (attn_prefill_plan.h) restated: token sub-tiles per workgroup at the default switches"""
     G = H // Hkv
     fits2 = lambda tt: G * tt * 2 <= 16 and G * tt * (16 * d + 32) * 4 <= 64 * 1024
     tt = 16 // G if G <= 4 else 1
@@ -119,3 +120,18 @@ def test_a_member_does_not_depend_on_the_pack(fa, pack, H, Hkv, d):
     for i in range(n):                                                  # ... and alone
         alone = run(fa, c, [i], H, Hkv, d)
         assert alone[i].tobytes() == full[i].tobytes(), "%s member %d differs packed alone" % (pack, i)
+
+
+@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("H,Hkv", [(2, 2), (6, 2), (8, 1), (32, 8)])
+@pytest.mark.parametrize("T,cached,window", [(17, 0, -1), (48, 37, -1), (100, 0, 5), (70, 129, 17)])
+def test_a_member_alone_has_the_bits_of_the_single_prompt_kernel(fa, T, cached, window, H, Hkv, d):
+    """fl_op_attention's 16-row kernel (kernel=2) and fl_op_attention_packed on one sequence: one device body, and at these lengths one
+    plan -- both run one token sub-tile per workgroup (TT = 1) with the same key split and ring depth, and at TT = 1 a wave's first
+    useful tile is the workgroup's first staged tile, so the two origins of the wave pair's alternation agree for any window."""
+    q, k, v = make(T, cached, H, Hkv, d, seed=4000 + 13 * T + H + d)
+    single = fa.op_attention(q, k, v, cached, H, Hkv, d, window=window, kernel=2)
+    alone = fa.op_attention_packed(q, [k[None]], [v[None]], [T], [cached], [-(-(cached + T) // 32) * 32], H, Hkv, d, layer=0, window=window)
+    assert not np.isnan(single).any() and not np.isnan(alone).any()
+    check(single, reference(q, k, v, cached, H, Hkv, d, window), "single T=%d cached=%d window=%d" % (T, cached, window))
+    assert single.tobytes() == alone.tobytes(), "max difference %g" % np.abs(single - alone).max()
