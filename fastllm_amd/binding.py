@@ -95,6 +95,22 @@ class _LogprobArrays:
         return self.token[:n], self.ids[:n], self.lps[:n]
 
 
+class FlLogitRules(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_bias", C.c_uint32), ("bias_ids", C.c_void_p), ("bias_values", C.c_void_p),
+                ("repetition_penalty", C.c_float), ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("_reserved", C.c_int64 * 2)]
+
+
+def make_logit_rules(logit_bias=None, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
+    """fl_logit_rules from a {id: bias} mapping (or a list of pairs) and the three penalties; returns (struct, arrays to keep alive)."""
+    pairs = list(logit_bias.items()) if hasattr(logit_bias, "items") else list(logit_bias or ())
+    ids = np.ascontiguousarray([p[0] for p in pairs], dtype=np.uint32)
+    vals = np.ascontiguousarray([p[1] for p in pairs], dtype=np.float32)
+    st = FlLogitRules(C.sizeof(FlLogitRules), len(pairs), ids.ctypes.data if len(pairs) else None, vals.ctypes.data if len(pairs) else None,
+                      repetition_penalty, frequency_penalty, presence_penalty)
+    return st, (ids, vals)
+
+
 class FlLookup(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_draft", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32),
                 ("_pad", C.c_int32), ("_reserved", C.c_int64 * 2)]
@@ -191,6 +207,9 @@ def lib():
         L.fl_decode_sample_lp.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampler), vp, C.POINTER(sz), C.POINTER(FlLogprobs)]
         L.fl_batch_decode_each_lp.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
         L.fl_op_logprobs.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        L.fl_cache_set_logit_rules.argtypes = [vp, vp, C.POINTER(FlLogitRules), vp, sz, vp, sz]
+        L.fl_cache_logit_counts.argtypes = [vp, vp, vp]
+        L.fl_op_logit_rules.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp]
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
         L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
         L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
@@ -285,6 +304,23 @@ def op_logprobs(logits, chosen, top_n):
     _check(lib().fl_op_logprobs(a.ctypes.data, T, V, ch.ctypes.data, int(top_n), out.token.ctypes.data,
                                 out.ids.ctypes.data if top_n > 0 else None, out.lps.ctypes.data if top_n > 0 else None))
     return out.cut(T)
+
+
+def op_logit_rules(logits, words, biases, scalars, tokens, count_input=True, has_rules=None):
+    """The logit-rules kernel alone (batch form): logits float32 [B, V], words uint32 [B, V], biases float32 [B, V], scalars [B, 3]
+    (repetition, frequency, presence penalty), tokens [B] (an id >= V: none) -> (adjusted rows float32 [B, V], words after the
+    launch uint32 [B, V]).  has_rules [B]: a false entry makes the row's table entry null (the row is copied through)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    B, V = a.shape
+    w = np.array(words, dtype=np.uint32, order="C").reshape(B, V)
+    bs = np.ascontiguousarray(biases, dtype=np.float32).reshape(B, V)
+    sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(B, 3)
+    tk = np.ascontiguousarray(tokens, dtype=np.uint32).reshape(B)
+    hr = None if has_rules is None else np.ascontiguousarray(has_rules, dtype=np.uint8).reshape(B)
+    out = np.empty((B, V), dtype=np.float32)
+    _check(lib().fl_op_logit_rules(a.ctypes.data, B, V, w.ctypes.data, bs.ctypes.data, sc.ctypes.data, tk.ctypes.data, 1 if count_input else 0,
+                                   hr.ctypes.data if hr is not None else None, out.ctypes.data))
+    return out, w
 
 
 def abi_version():
@@ -729,6 +765,27 @@ class Cache:
     def copy_prefix(self, src, n):
         """fl_cache_copy_prefix: this cache forgets what it holds and takes the first n cached positions of `src` (same model)."""
         _check(lib().fl_cache_copy_prefix(self._h, src._h if src is not None else None, int(n)))
+
+    def set_logit_rules(self, prompt_ids=(), output_ids=(), logit_bias=None, repetition_penalty=1.0, frequency_penalty=0.0,
+                        presence_penalty=0.0):
+        """fl_cache_set_logit_rules: logit_bias {id: bias} (-inf bans an id) and the three penalties, applied on the device to every
+        row this cache's calls select a token from; prompt_ids mark "seen in the prompt", output_ids seed the output counts, which
+        the decode loops then keep themselves."""
+        st, keep = make_logit_rules(logit_bias, repetition_penalty, frequency_penalty, presence_penalty)
+        p = np.ascontiguousarray(prompt_ids, dtype=np.uint32).reshape(-1)
+        o = np.ascontiguousarray(output_ids, dtype=np.uint32).reshape(-1)
+        _check(lib().fl_cache_set_logit_rules(self._model._h, self._h, C.byref(st), p.ctypes.data if p.size else None, p.size,
+                                              o.ctypes.data if o.size else None, o.size))
+        del keep
+
+    def clear_logit_rules(self):
+        _check(lib().fl_cache_set_logit_rules(self._model._h, self._h, None, None, 0, None, 0))
+
+    def logit_counts(self):
+        """fl_cache_logit_counts: the table words uint32 [V] -- bit 31 "in the prompt", bits 0..30 the output count."""
+        out = np.zeros(self._model.V, dtype=np.uint32)
+        _check(lib().fl_cache_logit_counts(self._model._h, self._h, out.ctypes.data))
+        return out
 
     def __len__(self):
         return lib().fl_cache_len(self._h)

@@ -272,6 +272,20 @@ int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const siz
     });
 }
 
+// ---- logit rules: every argument error is decided before the model, the cache or the device is looked at
+int fl_cache_set_logit_rules(fl_model *m, fl_cache *c, const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt,
+                             const uint32_t *output_ids, size_t n_output) {
+    return guarded([&]() -> int {
+        return cache_set_logit_rules(M(m), C(c), rules, prompt_ids, n_prompt, output_ids, n_output);
+    });
+}
+
+int fl_cache_logit_counts(fl_model *m, fl_cache *c, uint32_t *words_out) {
+    return guarded([&]() -> int {
+        return cache_logit_counts(M(m), C(c), words_out);
+    });
+}
+
 int fl_batch_create(fl_model *m, fl_cache *const *caches, size_t n, fl_batch **out) {
     return guarded([&]() -> int {
         if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null out");

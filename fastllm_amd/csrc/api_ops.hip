@@ -194,6 +194,45 @@ int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *ch
     });
 }
 
+int fl_op_logit_rules(const float *logits, int64_t B, int64_t V, uint32_t *words, const float *biases, const float *scalars,
+                      const uint32_t *tokens, int32_t count_input, const uint8_t *has_rules, float *out) {
+    return guarded([&]() -> int {
+        if (!logits || !words || !biases || !scalars || !tokens || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logit_rules: null argument");
+        if (B < 1 || B > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logit_rules: B %lld not in 1..64", (long long)B);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_logit_rules: V %lld not in 1..2^24", (long long)V);
+        OpScope S;
+        FL_TRY(S.begin());
+        // the rows back to back as a batch keeps them ([B][V]: with an odd V the rows b > 0 start off a 16-byte boundary); every
+        // row's table an allocation of its own, as every cache's is
+        float *lg, *od; uint32_t *tk; LogitRulesCtl *ctl; LogitRulesCtl **ctls;
+        FL_TRY(S.upload(&lg, logits, (size_t)B * V * 4));
+        FL_TRY(S.alloc(&od, (size_t)B * V * 4));
+        FL_TRY(S.upload(&tk, tokens, (size_t)B * 4));
+        FL_TRY(S.alloc(&ctl, (size_t)B * sizeof(LogitRulesCtl)));
+        std::vector<LogitRuleEntry *> tabs((size_t)B);
+        std::vector<LogitRulesCtl *> ptrs((size_t)B, nullptr);
+        std::vector<LogitRuleEntry> img((size_t)V);
+        for (int64_t b = 0; b < B; b++) {
+            for (int64_t j = 0; j < V; j++) img[(size_t)j] = LogitRuleEntry{words[b * V + j], biases[b * V + j]};
+            FL_TRY(S.upload(&tabs[(size_t)b], img.data(), (size_t)V * sizeof(LogitRuleEntry)));
+            const LogitRulesCtl value{scalars[3 * b], scalars[3 * b + 1], scalars[3 * b + 2], count_input ? 1u : 0u, tabs[(size_t)b], nullptr};
+            FL_TRY(launch_set_logit_rules_ctl(S.L, ctl + b, value));
+            if (!has_rules || has_rules[b]) ptrs[(size_t)b] = ctl + b;
+        }
+        FL_TRY(S.upload(&ctls, ptrs.data(), (size_t)B * sizeof(LogitRulesCtl *)));
+        LogitRulesSrc src;
+        src.ctls = ctls; src.tokens = tk; src.out = od;
+        FL_TRY(launch_logit_rules(S.L, lg, V, (int)B, src));
+        FL_HIP(hipStreamSynchronize(S.s));
+        FL_HIP(hipMemcpy(out, od, (size_t)B * V * 4, hipMemcpyDeviceToHost));
+        for (int64_t b = 0; b < B; b++) {
+            FL_HIP(hipMemcpy(img.data(), tabs[(size_t)b], (size_t)V * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+            for (int64_t j = 0; j < V; j++) words[b * V + j] = img[(size_t)j].word;
+        }
+        return FL_OK;
+    });
+}
+
 int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
                             int32_t dtype, float *out) {
     return guarded([&]() -> int {

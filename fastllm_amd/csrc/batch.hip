@@ -13,8 +13,7 @@ Batch::~Batch() {
     Shard &sh = m->shards[0];
     (void)hipSetDevice(sh.device);
     (void)hipStreamSynchronize(sh.stream);
-    if (graph) (void)hipGraphExecDestroy(graph);
-    if (graph_lp) (void)hipGraphExecDestroy(graph_lp);
+    for (auto g : graph) if (g) (void)hipGraphExecDestroy(g);
     for (void *p : allocs) (void)hipFree(p);
     if (host_lp) (void)hipHostFree(host_lp);
     if (host_tokens) (void)hipHostFree(host_tokens);
@@ -125,16 +124,30 @@ int batch_replace(Batch *b, size_t slot, Cache *c) {
     b->caches[slot] = c;
     const bool regraph = c->nsplit > b->max_nsplit || (b->per_seq && !b->plain);
     b->max_nsplit = std::max(b->max_nsplit, c->nsplit);
-    if (regraph && b->graph) { (void)hipGraphExecDestroy(b->graph); b->graph = nullptr; }
-    if (regraph && b->graph_lp) { (void)hipGraphExecDestroy(b->graph_lp); b->graph_lp = nullptr; }
+    for (auto &g : b->graph) if (regraph && g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    if (b->rule_ctls) {                                           // the rules launch finds the new member's control block (null: none)
+        LogitRulesCtl *ctl = c->rules_on ? cs.rule_ctl : nullptr;
+        FL_HIP(hipMemcpy(b->rule_ctls + slot, &ctl, sizeof ctl, hipMemcpyHostToDevice));
+    }
     return FL_OK;
 }
 
-static int enqueue_batch_step_unfused(Batch *b);
+static int enqueue_batch_step_unfused(Batch *b, bool rules);
+
+// Token selection of every sequence.  rules: a member has logit rules -- one launch first leaves every row adjusted by its own
+// member's rules (copied through for a member without) in logits_adj, which the selection then reads; off: the launch there always was
+static int batch_select(Batch *b, Launcher &L, bool rules) {
+    const int64_t V = b->m->D.V;
+    if (!rules) return launch_select_advance_batch(L, b->logits, V, b->seqs_dev, b->B, 1);
+    LogitRulesSrc src;
+    src.seqs = b->seqs_dev; src.ctls = b->rule_ctls; src.out = b->logits_adj;
+    FL_TRY(launch_logit_rules(L, b->logits, V, b->B, src));
+    return launch_select_advance_batch(L, b->logits_adj, V, b->seqs_dev, b->B, 1);
+}
 
 // One decode step of the whole batch: the 5-launch layer of enqueue_decode_fused with B activation rows.
-static int enqueue_batch_step(Batch *b) {
-    if (b->unfused) return enqueue_batch_step_unfused(b);
+static int enqueue_batch_step(Batch *b, bool rules = false) {
+    if (b->unfused) return enqueue_batch_step_unfused(b, rules);
     Model *m = b->m;
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
@@ -169,12 +182,12 @@ static int enqueue_batch_step(Batch *b) {
     h.B = B; h.seqs = b->seqs_dev; h.W = sh.lm_head; h.out = b->logits; h.N = (int)D.V; h.K = (int)D.h; h.pro = PRO_NORM;
     h.x_in = b->x_res; h.delta = b->delta; h.n_slab = b->nks_down; h.slab_stride = slab; h.norm_w = sh.norm; h.eps = D.eps;
     FL_TRY(launch_gemv_batch(L, h));
-    return launch_select_advance_batch(L, b->logits, D.V, b->seqs_dev, B, 1);
+    return batch_select(b, L, rules);
 }
 
 // The same step as 8 launches per layer: rmsnorm_add -> QKV GEMM -> RoPE / KV append -> attention -> o_proj GEMM (K
 // slabs) -> rmsnorm_add (sums them) -> gate/up GEMM -> down GEMM (K slabs); launch_linear picks gemm_skinny_kernel.
-static int enqueue_batch_step_unfused(Batch *b) {
+static int enqueue_batch_step_unfused(Batch *b, bool rules) {
     Model *m = b->m;
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
@@ -247,7 +260,7 @@ static int enqueue_batch_step_unfused(Batch *b) {
         }
         FL_TRY(launch_rms_finalize(L, sc.rs_part, np, D.eps, sc.inv_rms, T, D.h));
         FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
-        return launch_select_advance_batch(L, b->logits, D.V, b->seqs_dev, B, 1);
+        return batch_select(b, L, rules);
     }
     for (int64_t l = 0; l < D.L; l++) {
         LayerW &ly = sh.layers[l];
@@ -288,18 +301,19 @@ static int enqueue_batch_step_unfused(Batch *b) {
     } else {
         FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
     }
-    return launch_select_advance_batch(L, b->logits, D.V, b->seqs_dev, B, 1);
+    return batch_select(b, L, rules);
 }
 
-// with_lp: the step with every sequence's log-prob records written behind token selection (one more launch of B workgroups), as
-// a second graph; `graph` is what it always was
-static int batch_step(Batch *b, bool with_lp = false) {
+// kind (kStepLp | kStepRules): the step with every sequence's log-prob records written behind token selection (one more launch of B
+// workgroups) and / or the logit-rules launch in front of it, each kind a graph of its own; graph[0] is what it always was
+static int batch_step(Batch *b, int kind = 0) {
     Model *m = b->m;
     Shard &sh = m->shards[0];
     const bool graphable = m->use_graph && !m->profiling && !b->graph_failed;
-    if (!with_lp) return replay_or_capture({{sh.device, sh.stream, &b->graph}}, graphable, b->graph_failed, b->warm_steps, [b] { return enqueue_batch_step(b); });
-    return replay_or_capture({{sh.device, sh.stream, &b->graph_lp}}, graphable, b->graph_failed, b->warm_steps_lp, [b, m, &sh]() -> int {
-        FL_TRY(enqueue_batch_step(b));
+    const bool rules = (kind & kStepRules) != 0;
+    if (!(kind & kStepLp)) return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, rules] { return enqueue_batch_step(b, rules); });
+    return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, m, &sh, rules]() -> int {
+        FL_TRY(enqueue_batch_step(b, rules));
         Launcher L = make_launcher(m, sh);
         LogprobSrc src;
         src.seqs = b->seqs_dev; src.ctls = b->lp_ctls;
@@ -378,6 +392,22 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
         }
         FL_HIP(hipMemcpy(b->lp_ctls, ctls.data(), sizeof(LogprobCtl *) * (size_t)B, hipMemcpyHostToDevice));   // (synchronous: ctls is a stack vector)
     }
+    bool rules = false;
+    for (int i = 0; i < B; i++) rules = rules || b->caches[i]->rules_on;
+    if (rules) {
+        // the adjusted rows and the members' control blocks (null: no rules -- the row is copied through), and each ruled member's
+        // scalars with count_input set: every step's input token is one more output -- all ahead of the steps on the stream
+        if (!b->rule_ctls) FL_TRY(dev_alloc(b->allocs, (void **)&b->rule_ctls, sizeof(LogitRulesCtl *) * (size_t)B, nullptr));
+        if (!b->logits_adj) FL_TRY(dev_alloc(b->allocs, (void **)&b->logits_adj, (size_t)B * m->D.V * 4, nullptr));
+        std::vector<LogitRulesCtl *> ctls((size_t)B, nullptr);
+        for (int i = 0; i < B; i++) {
+            if (!b->caches[i]->rules_on) continue;
+            FL_TRY(set_logit_rules_ctl(m, b->caches[i], true));
+            ctls[(size_t)i] = b->caches[i]->shards[0].rule_ctl;
+        }
+        FL_HIP(hipMemcpy(b->rule_ctls, ctls.data(), sizeof(LogitRulesCtl *) * (size_t)B, hipMemcpyHostToDevice));   // (synchronous: ctls is a stack vector)
+    }
+    const int kind = (lp_each ? kStepLp : 0) | (rules ? kStepRules : 0);
     std::vector<uint32_t> tok(first, first + B);
     std::vector<char> finished(B, 0);
     std::vector<size_t> len0(B);
@@ -387,7 +417,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
         const size_t nb = std::min(n_steps - done, kBatchChunk);
         for (int i = 0; i < B; i++)
             FL_TRY(set_shard_state(m, sh, b->caches[i]->shards[0], tok[i], pos[i] + done, len0[i] + done, len0[i] + done, 0u, eoss[(size_t)i], samplers[(size_t)i], done == 0));
-        for (size_t s = 0; s < nb; s++) FL_TRY(batch_step(b, lp_each != nullptr));
+        for (size_t s = 0; s < nb; s++) FL_TRY(batch_step(b, kind));
         FL_TRY(batch_finish(b, nb, lp_each != nullptr));
         bool all_finished = true;
         for (int i = 0; i < B; i++) {
@@ -420,6 +450,7 @@ int batch_forward(Batch *b, const uint32_t *tokens, const size_t *pos, float *lo
     Model *m = b->m;
     const int B = b->B;
     for (int i = 0; i < B; i++) FL_TRY(check_token(m, tokens[i], "token"));
+    if (tokens_out) for (int i = 0; i < B; i++) FL_TRY(refuse_logit_rules(b->caches[i], "fl_batch_forward with argmax_out"));   // (its ArgMax reads the raw rows)
     const SampleState sampler{};
     std::lock_guard<std::mutex> lock(m->mu);
     Shard &sh = m->shards[0];

@@ -252,6 +252,18 @@ struct LogprobRec { float chosen; uint32_t ids[kLogprobsMaxTop]; float lps[kLogp
 // ... and where a cache's records go: read from device memory by the kernel, so one captured graph serves every top_n
 struct LogprobCtl { LogprobRec *recs; uint32_t cap; int32_t top_n; };
 
+// Logit rules of a cache (fl_cache_set_logit_rules): one table entry per vocabulary id -- word bit 31 "occurred in the prompt", bits
+// 0..30 the times the id was produced as output -- and the control block logit_rules_kernel (k_logit_rules.hip) reads from device
+// memory, so one captured graph serves every setting
+constexpr uint32_t kRulePromptBit = 0x80000000u;
+struct LogitRuleEntry { uint32_t word; float bias; };
+struct LogitRulesCtl {
+    float rp, fp, pp;            // repetition / frequency / presence penalty (1, 0, 0: off)
+    uint32_t count_input;        // decode loops: the step's input token is one more output
+    LogitRuleEntry *table;       // [V]
+    float *out;                  // [V] the adjusted row of a single sequence (a batch's rows go to the batch's own buffer)
+};
+
 // acc += a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (gfx950 VOP2; hipcc has no selectable builtin for it)
 __device__ inline float dot2c_bf16(unsigned a, unsigned b, float acc) {
     asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));

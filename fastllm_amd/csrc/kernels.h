@@ -426,6 +426,22 @@ struct LogprobSrc {
 };
 int launch_token_logprobs(Launcher &L, const float *logits, int64_t V, int rows, const LogprobSrc &src, int advance);
 int launch_set_logprob_ctl(Launcher &L, LogprobCtl *ctl, LogprobRec *recs, uint32_t cap, int top_n);
+// Logit rules (k_logit_rules.hip): out row b = the rules of row b's control block applied to logits row b ([rows][V], fp32), one
+// launch between lm_head and token selection.  The thread that owns element `token` of a row first counts it (count_input).  Who a
+// row belongs to:
+//   st + ctl          one sequence (rows == 1): token st->token, output ctl->out
+//   seqs + ctls + out a batch: row b is sequence b (its SeqRef's StepState, ctls[b]; a null entry copies the row through), out [B][V]
+//   tokens + ctls + out   fl_op_logit_rules: row b's token is tokens[b] (>= V: none)
+struct LogitRulesSrc {
+    const StepState *st = nullptr;
+    const SeqRef *seqs = nullptr;
+    const LogitRulesCtl *ctl = nullptr;
+    const LogitRulesCtl *const *ctls = nullptr;
+    const uint32_t *tokens = nullptr;
+    float *out = nullptr;
+};
+int launch_logit_rules(Launcher &L, const float *logits, int64_t V, int rows, const LogitRulesSrc &src);
+int launch_set_logit_rules_ctl(Launcher &L, LogitRulesCtl *ctl, const LogitRulesCtl &value);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

@@ -158,15 +158,21 @@ struct CacheShard {
     unsigned *counters = nullptr;        // split-S arrival tickets, [Hkvs * q-groups]
     unsigned *heads_done = nullptr;      // [L][Hkv] fused attention+o_proj: split partials published per kv head since set_state
     float *ao_part = nullptr;            // ... and the partials: [Hs][ao_nsplit][d + 4] (o, m, l)
-    hipGraphExec_t graph = nullptr;
+    // the decode step as a graph, one per kind (kStepRules | kStepLp): [0] is the plain step and never has the launches of the others
+    hipGraphExec_t graph[4] = {};
     // token log-probabilities (fl_*_lp): allocated at the cache's first such call, so a cache that never asks pays nothing
     LogprobRec *lp_recs = nullptr;       // [kOutTokensCap] one record per step of a chunk
     LogprobCtl *lp_ctl = nullptr;        // where token_logprobs_kernel finds them, and the call's top_n
-    hipGraphExec_t graph_lp = nullptr;   // the decode step with the log-prob launch behind token selection; `graph` never has it
+    // logit rules (fl_cache_set_logit_rules): allocated at the cache's first install
+    LogitRuleEntry *rule_tab = nullptr;  // [V] prompt bit + output count, bias
+    LogitRulesCtl *rule_ctl = nullptr;   // the call's scalars and count_input flag, where logit_rules_kernel reads them
+    float *logits_adj = nullptr;         // [V] the adjusted row: what token selection reads while rules are installed
+    LogitRuleEntry *rule_image = nullptr;   // pinned [V]: the table as an install builds it, source of its one async copy
     std::vector<void *> allocs;
 };
 
 constexpr size_t kOutTokensCap = 4096;
+enum { kStepLp = 1, kStepRules = 2 };    // kinds of decode step: index into the graph / warm_steps slots
 
 struct Cache {
     Model *m = nullptr;
@@ -177,9 +183,10 @@ struct Cache {
     bool fuse_oproj = false;     // this cache's decode steps use the fused attention+o_proj launch
     int ao_nsplit = 0, ao_waves = 4;   // ... with this many key splits per kv head, 32 * ao_waves keys per split and step
     int nsplit = 1;
-    int warm_steps = 0;          // eager decode steps done (graph is captured after the first)
-    int warm_steps_lp = 0;       // ... and of the step with log-probs (graph_lp)
+    int warm_steps[4] = {};      // eager decode steps done, per kind of step (its graph is captured after the first)
     bool graph_failed = false;
+    bool rules_on = false;       // logit rules installed: the steps run logit_rules_kernel and select from logits_adj
+    float rule_rp = 1.f, rule_fp = 0.f, rule_pp = 0.f;
     std::vector<CacheShard> shards;
     ~Cache();
 };
@@ -208,15 +215,17 @@ struct Batch {
     float *logits_local = nullptr, *logits_ranks = nullptr;   // tensor-parallel rank: its [B][Vs] block, and the gathered [tp][B][Vs]
     uint32_t *host_tokens = nullptr;             // pinned [B][kBatchChunk]
     StepState *host_states = nullptr;            // pinned [B]
-    hipGraphExec_t graph = nullptr;
+    hipGraphExec_t graph[4] = {};                // the step per kind (kStepRules | kStepLp), as a cache's
     bool graph_failed = false;
-    int warm_steps = 0;
+    int warm_steps[4] = {};
     // fl_batch_decode_each_lp: the step with the log-prob launch behind token selection, the sequences' LogprobCtl pointers [B]
     // (written at the start of every such call) and the pinned [B][kBatchChunk] records; allocated at the batch's first such call
-    hipGraphExec_t graph_lp = nullptr;
-    int warm_steps_lp = 0;
     LogprobCtl **lp_ctls = nullptr;
     LogprobRec *host_lp = nullptr;
+    // logit rules: the members' control blocks [B] (null: no rules; written at the start of every decode call with a ruled member and
+    // by fl_batch_replace) and the adjusted rows [B][V]; allocated at the batch's first step with a ruled member
+    LogitRulesCtl **rule_ctls = nullptr;
+    float *logits_adj = nullptr;
     std::vector<void *> allocs;
     ~Batch();
 };
@@ -285,6 +294,14 @@ int logprobs_supported(const Model *m);
 int ensure_logprobs(Model *m, Cache *c);
 // record r of a chunk -> row `at` of the caller's arrays
 void scatter_logprobs(const LogprobRec &r, const fl_logprobs *lp, size_t at);
+// fl_cache_set_logit_rules / fl_cache_logit_counts.  check_logit_rules: the struct and the lists alone (V <= 0: not known), no device
+int check_logit_rules(const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt, const uint32_t *output_ids, size_t n_output, int64_t V);
+int cache_set_logit_rules(Model *m, Cache *c, const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt, const uint32_t *output_ids, size_t n_output);
+int cache_logit_counts(Model *m, Cache *c, uint32_t *words_out);
+// this call's scalars and count_input flag into the cache's control block, on the stream ahead of the call's steps
+int set_logit_rules_ctl(Model *m, Cache *c, bool count_input);
+// FL_ERR_UNSUPPORTED for an entry point that does not honour a cache's installed rules
+int refuse_logit_rules(const Cache *c, const char *what);
 
 // fl_cache_truncate / fl_forward_verify / fl_decode_lookup (speculative greedy decode)
 int cache_truncate(Cache *c, size_t len);

@@ -38,9 +38,9 @@ Cache::~Cache() {
     for (size_t i = 0; i < shards.size(); i++) {
         (void)hipSetDevice(m->shards[i].device);
         (void)hipStreamSynchronize(m->shards[i].stream);
-        if (shards[i].graph) (void)hipGraphExecDestroy(shards[i].graph);
-        if (shards[i].graph_lp) (void)hipGraphExecDestroy(shards[i].graph_lp);
+        for (auto g : shards[i].graph) if (g) (void)hipGraphExecDestroy(g);
         for (void *p : shards[i].allocs) (void)hipFree(p);
+        if (shards[i].rule_image) (void)hipHostFree(shards[i].rule_image);
     }
 }
 
@@ -650,10 +650,106 @@ static int set_state(Model *m, Cache *c, uint32_t token, size_t pos, size_t len,
     });
 }
 
-static int enqueue_argmax(Model *m, Cache *c, int advance) {
-    return each_shard(m, c, [&](Shard &sh, CacheShard &cs, Launcher &L) {
+// rules: the cache's logit rules are on -- logit_rules_kernel leaves the adjusted row in logits_adj, and the selection reads that, as
+// a full pass (the lm_head epilogue's ArgMax candidates belong to the raw row); off: exactly the launch there has always been
+static int enqueue_argmax(Model *m, Cache *c, int advance, bool rules = false) {
+    return each_shard(m, c, [&](Shard &sh, CacheShard &cs, Launcher &L) -> int {
+        if (rules) {
+            LogitRulesSrc src;
+            src.st = cs.st; src.ctl = cs.rule_ctl;
+            FL_TRY(launch_logit_rules(L, sh.logits_full, m->D.V, 1, src));
+            return launch_select_advance(L, cs.logits_adj, m->D.V, cs.st, cs.ss, cs.sel_scratch, cs.out_tokens, advance, nullptr, sh.eng_epoch);
+        }
         return launch_select_advance(L, sh.logits_full, m->D.V, cs.st, cs.ss, cs.sel_scratch, cs.out_tokens, advance, sh.amax_valid ? sh.amax : nullptr, sh.eng_epoch);
     });
+}
+
+// ---- logit rules (fl_cache_set_logit_rules)
+int check_logit_rules(const fl_logit_rules *r, const uint32_t *prompt_ids, size_t n_prompt, const uint32_t *output_ids, size_t n_output, int64_t V) {
+    if (!r) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_logit_rules (rules)");
+    if (r->struct_size != sizeof(fl_logit_rules)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.struct_size is %u, expected %zu", r->struct_size, sizeof(fl_logit_rules));
+    if (r->_reserved[0] || r->_reserved[1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules._reserved must be 0");
+    if (!isfinite(r->repetition_penalty) || !(r->repetition_penalty > 0.f)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.repetition_penalty must be finite and > 0");
+    if (!isfinite(r->frequency_penalty)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.frequency_penalty must be finite");
+    if (!isfinite(r->presence_penalty)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.presence_penalty must be finite");
+    if (r->n_bias && (!r->bias_ids || !r->bias_values)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.bias_ids / bias_values is null with n_bias %u", r->n_bias);
+    if (n_prompt && !prompt_ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null prompt_ids with n_prompt %zu", n_prompt);
+    if (n_output && !output_ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null output_ids with n_output %zu", n_output);
+    for (uint32_t i = 0; i < r->n_bias; i++) {
+        const float v = r->bias_values[i];
+        if (v != v || v == INFINITY) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.bias_values[%u] is NaN or +inf", i);
+    }
+    if (V > 0) {
+        if ((int64_t)r->n_bias > V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.n_bias %u exceeds the vocabulary %lld", r->n_bias, (long long)V);
+        for (uint32_t i = 0; i < r->n_bias; i++)
+            if ((int64_t)r->bias_ids[i] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.bias_ids[%u] = %u out of range (vocab %lld)", i, r->bias_ids[i], (long long)V);
+        for (size_t i = 0; i < n_prompt; i++)
+            if ((int64_t)prompt_ids[i] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "prompt_ids[%zu] = %u out of range (vocab %lld)", i, prompt_ids[i], (long long)V);
+        for (size_t i = 0; i < n_output; i++)
+            if ((int64_t)output_ids[i] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "output_ids[%zu] = %u out of range (vocab %lld)", i, output_ids[i], (long long)V);
+    }
+    std::vector<uint32_t> sorted(r->bias_ids, r->bias_ids + r->n_bias);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < sorted.size(); i++)
+        if (sorted[i] == sorted[i - 1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_logit_rules.bias_ids: duplicate id %u", sorted[i]);
+    return FL_OK;
+}
+
+int refuse_logit_rules(const Cache *c, const char *what) {
+    if (c && c->rules_on) FL_FAIL(FL_ERR_UNSUPPORTED, "%s does not honour logit rules: remove them from the cache first (fl_cache_set_logit_rules with NULL)", what);
+    return FL_OK;
+}
+
+int cache_set_logit_rules(Model *m, Cache *c, const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt, const uint32_t *output_ids, size_t n_output) {
+    if (rules) FL_TRY(check_logit_rules(rules, prompt_ids, n_prompt, output_ids, n_output, 0));
+    if (!m || !c) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null model or cache");
+    if (c->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "cache belongs to another model");
+    if (!rules) {                                                     // removal: the buffers stay (freed with the cache), the old graphs run again
+        std::lock_guard<std::mutex> lock(m->mu);
+        c->rules_on = false;
+        return FL_OK;
+    }
+    const int64_t V = m->D.V;
+    FL_TRY(check_logit_rules(rules, prompt_ids, n_prompt, output_ids, n_output, V));
+    if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "logit rules do not run under tensor parallelism (tp_size %d)", m->tp);
+    if (n_output > 0x7fffffffu) FL_FAIL(FL_ERR_BAD_ARGUMENT, "n_output %zu exceeds the 31-bit count", n_output);
+    std::lock_guard<std::mutex> lock(m->mu);
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    FL_HIP(hipSetDevice(sh.device));
+    if (!cs.rule_image) FL_HIP(hipHostMalloc((void **)&cs.rule_image, (size_t)V * sizeof(LogitRuleEntry), hipHostMallocDefault));
+    else FL_HIP(hipStreamSynchronize(sh.stream));                     // (the previous install's copy reads the image)
+    if (!cs.rule_tab) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.rule_tab, (size_t)V * sizeof(LogitRuleEntry), nullptr));
+    if (!cs.rule_ctl) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.rule_ctl, sizeof(LogitRulesCtl), nullptr));
+    if (!cs.logits_adj) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.logits_adj, (size_t)V * 4, nullptr));
+    LogitRuleEntry *img = cs.rule_image;
+    for (int64_t j = 0; j < V; j++) img[j] = LogitRuleEntry{0u, 0.f};
+    for (size_t i = 0; i < n_prompt; i++) img[prompt_ids[i]].word |= kRulePromptBit;
+    for (size_t i = 0; i < n_output; i++) img[output_ids[i]].word += 1;          // (n_output < 2^31: no carry into the prompt bit)
+    for (uint32_t i = 0; i < rules->n_bias; i++) img[rules->bias_ids[i]].bias = rules->bias_values[i];
+    FL_HIP(hipMemcpyAsync(cs.rule_tab, img, (size_t)V * sizeof(LogitRuleEntry), hipMemcpyHostToDevice, sh.stream));
+    c->rule_rp = rules->repetition_penalty; c->rule_fp = rules->frequency_penalty; c->rule_pp = rules->presence_penalty;
+    c->rules_on = true;
+    return FL_OK;
+}
+
+int cache_logit_counts(Model *m, Cache *c, uint32_t *words_out) {
+    if (!m || !c || !words_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_logit_counts: null argument");
+    if (c->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "cache belongs to another model");
+    if (!c->rules_on) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_logit_counts: the cache has no logit rules installed");
+    std::lock_guard<std::mutex> lock(m->mu);
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    FL_HIP(hipSetDevice(sh.device));
+    FL_HIP(hipStreamSynchronize(sh.stream));
+    std::vector<LogitRuleEntry> tab((size_t)m->D.V);
+    FL_HIP(hipMemcpy(tab.data(), cs.rule_tab, tab.size() * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < tab.size(); j++) words_out[j] = tab[j].word;
+    return FL_OK;
+}
+
+int set_logit_rules_ctl(Model *m, Cache *c, bool count_input) {
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    Launcher L = make_launcher(m, sh);
+    return launch_set_logit_rules_ctl(L, cs.rule_ctl, LogitRulesCtl{c->rule_rp, c->rule_fp, c->rule_pp, count_input ? 1u : 0u, cs.rule_tab, cs.logits_adj});
 }
 
 // ---- token log-probabilities (fl_*_lp)
@@ -762,9 +858,9 @@ int replay_or_capture(const std::vector<GraphSlot> &slots, bool graphable, bool 
 // Single-shard models replay it as a hipGraph (the ~11 launches per layer are launch-bound at
 // TinyLlama scale); captured lazily on the second step of a cache so that all lazy module /
 // attribute initialisation has already happened eagerly.
-// with_lp: the step with the log-prob launch behind token selection -- a second graph (graph_lp); `graph` is what it always was,
-// and a cache may alternate between the two kinds of call.
-static int decode_step(Model *m, Cache *c, int64_t len_hint, bool with_lp = false) {
+// kind (kStepLp | kStepRules): the step with the log-prob launch behind token selection and / or the logit-rules launch in front of
+// it -- a graph of its own per kind; graph[0] is what it always was, and a cache may alternate between the kinds of call.
+static int decode_step(Model *m, Cache *c, int64_t len_hint, int kind = 0) {
     // Graphs: one shard per process (plain single GPU, or one rank of a multi-process TP group: RCCL collectives are
     // stream-ordered and capturable, every rank captures the same sequence); or all shards of a single-process group
     // whose collectives are one-shot (they synchronise through memory, so each shard's step is its own graph).
@@ -776,11 +872,11 @@ static int decode_step(Model *m, Cache *c, int64_t len_hint, bool with_lp = fals
     const bool graphable = m->use_graph && !m->profiling && (one_shard || local_group) && !c->graph_failed;
     std::vector<GraphSlot> slots;
     for (size_t i = 0; i < ns && graphable; i++)
-        slots.push_back({m->shards[i].device, m->shards[i].stream, with_lp ? &c->shards[i].graph_lp : &c->shards[i].graph});
-    return replay_or_capture(slots, graphable, c->graph_failed, with_lp ? c->warm_steps_lp : c->warm_steps, [&]() -> int {
+        slots.push_back({m->shards[i].device, m->shards[i].stream, &c->shards[i].graph[kind]});
+    return replay_or_capture(slots, graphable, c->graph_failed, c->warm_steps[kind], [&]() -> int {
         FL_TRY(enqueue_forward(m, c, false, 1, false, len_hint));
-        FL_TRY(enqueue_argmax(m, c, 1));
-        return with_lp ? enqueue_logprobs(m, c, 1) : FL_OK;
+        FL_TRY(enqueue_argmax(m, c, 1, (kind & kStepRules) != 0));
+        return (kind & kStepLp) ? enqueue_logprobs(m, c, 1) : FL_OK;
     });
 }
 
@@ -809,9 +905,12 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
     if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
     std::lock_guard<std::mutex> lock(m->mu);
     if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
+    const bool rules = c->rules_on;                  // (a forward's ids are prompt: the rules are applied, nothing is counted)
+    if (rules) FL_TRY(set_logit_rules_ctl(m, c, false));
+    const int kind = (lp ? kStepLp : 0) | (rules ? kStepRules : 0);
     if (T == 1) {
         FL_TRY(set_state(m, c, ids[0], pos, c->len, 0, -1, (size_t)-1, &sampler));
-        FL_TRY(decode_step(m, c, (int64_t)c->len, lp != nullptr));
+        FL_TRY(decode_step(m, c, (int64_t)c->len, kind));
         c->len += 1;
     } else {
         const int64_t chunk_max = tune(TK_PREFILL_CHUNK);
@@ -835,7 +934,7 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
             c->len += (size_t)Tc;
             done += (size_t)Tc;
         }
-        FL_TRY(enqueue_argmax(m, c, 0));
+        FL_TRY(enqueue_argmax(m, c, 0, rules));
         if (lp) FL_TRY(enqueue_logprobs(m, c, 0));
     }
     Shard &s0 = m->shards[0];
@@ -860,6 +959,8 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
     if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
     std::lock_guard<std::mutex> lock(m->mu);
     if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
+    if (c->rules_on) FL_TRY(set_logit_rules_ctl(m, c, true));      // every step's input token is one more output
+    const int kind = (lp ? kStepLp : 0) | (c->rules_on ? kStepRules : 0);
     size_t done = 0;
     uint32_t tok = first;
     // With an EOS id the host looks at the tokens between chunks of 16, 32, ... 256 steps: the reference's loop breaks at
@@ -870,7 +971,7 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
         const size_t nb = std::min(n_steps - done, chunk);
         if (eos >= 0) chunk = std::min<size_t>(chunk * 2, 256);
         FL_TRY(set_state(m, c, tok, pos + done, c->len, 0, eos, (size_t)-1, done == 0 ? &sampler : nullptr));
-        for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i), lp != nullptr));
+        for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i), kind));
         FL_TRY(finish_call(m, c, nb, lp ? nb : 0));
         for (size_t i = 0; i < nb; i++) {
             const uint32_t t = m->host_tokens[i];
@@ -994,6 +1095,7 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
     if (n_out) *n_out = 0;
     if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null tokens_out or n_out");
     if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null draft");
+    FL_TRY(refuse_logit_rules(c, "fl_forward_verify"));
     FL_TRY(check_verify(m, c, n_draft, pos));
     FL_TRY(check_token(m, token, "token"));
     for (size_t i = 0; i < n_draft; i++) FL_TRY(check_token(m, draft[i], "draft"));
@@ -1018,6 +1120,7 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
     FL_TRY(check_lookup(opts));
     if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null n_out");
     if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null corpus");
+    FL_TRY(refuse_logit_rules(c, "fl_decode_lookup"));
     if (n_steps == 0) return FL_OK;
     if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null tokens_out");
     FL_TRY(check_call(m, c, n_steps, pos));

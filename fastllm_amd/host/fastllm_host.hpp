@@ -617,6 +617,26 @@ struct TokenLogprobs {
     int top_n = 0;
 };
 
+// A request's logit_bias and repetition / frequency / presence penalties (fl_logit_rules): installed on the request's cache, applied
+// on the device to every row a token is selected from, the output counts kept by the decode loop itself.  New capability; the
+// reference has none.  repetition_penalty 1 and the other two 0 are off; a bias of -inf bans an id.
+struct LogitRules {
+    std::vector<std::pair<uint32_t, float>> logit_bias;
+    float repetition_penalty = 1.f, frequency_penalty = 0.f, presence_penalty = 0.f;
+    // on cache `c`: prompt marks its ids as seen, output seeds the counts (a request that resumes)
+    void install(fl_model *m, fl_cache *c, const std::vector<uint32_t> &prompt, const std::vector<uint32_t> &output = {}) const {
+        std::vector<uint32_t> ids; std::vector<float> values;
+        for (auto &b : logit_bias) { ids.push_back(b.first); values.push_back(b.second); }
+        fl_logit_rules r{};
+        r.struct_size = (uint32_t)sizeof(fl_logit_rules);
+        r.n_bias = (uint32_t)ids.size(); r.bias_ids = ids.empty() ? nullptr : ids.data(); r.bias_values = values.empty() ? nullptr : values.data();
+        r.repetition_penalty = repetition_penalty; r.frequency_penalty = frequency_penalty; r.presence_penalty = presence_penalty;
+        check(fl_cache_set_logit_rules(m, c, &r, prompt.empty() ? nullptr : prompt.data(), prompt.size(), output.empty() ? nullptr : output.data(), output.size()),
+              "fl_cache_set_logit_rules");
+    }
+    static void remove(fl_model *m, fl_cache *c) { check(fl_cache_set_logit_rules(m, c, nullptr, nullptr, 0, nullptr, 0), "fl_cache_set_logit_rules"); }
+};
+
 // Prompt-lookup drafting for greedy requests (fl_lookup): the continuation that followed the most recent earlier occurrence of the
 // current n-gram is verified in one forward (fl_forward_verify).  New capability; the tokens are those of the plain greedy loop.
 struct LookupOptions {
@@ -721,6 +741,38 @@ struct Model {                                // mod.rs:342-361
         }
         const size_t total = ended ? 0 : 1 + n;
         output_ids.resize(total); out->token.resize(total); out->top_ids.resize(total * w); out->top.resize(total * w);
+        return output_ids;
+    }
+
+    // ... with logit rules: installed on the fresh cache (the prompt's ids marked as seen) before the first fl_forward_sample_ex, so
+    // the first token is already selected from the adjusted row; the other max_tokens - 1 come from fl_decode_sample_ex, which counts
+    // every token it is fed.  Token selection stays on the device throughout.  `forwards` as in the log-prob overload.
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, const LogitRules &rules) {
+        cache = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        forwards = 0;
+        std::vector<uint32_t> output_ids;
+        if (max_tokens == 0) { model.forward(Tensor::from_ids(prompt), 0, cache); forwards++; return output_ids; }
+        output_ids.assign(max_tokens, 0);
+        model.prepare(cache);
+        fl_cache *c = model.raw_cache(cache);
+        rules.install(model.raw_model(), c, prompt);
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        check(fl_forward_sample_ex(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0]),
+              "Model forward pass failed");
+        model.advance(cache, 1); forwards++;
+        size_t n = 0;
+        const bool ended = eos && output_ids[0] == *eos;
+        if (!ended && max_tokens > 1) {
+            const fl_sampler s1 = opt.to_ffi((double)temperature, 1);
+            const size_t len0 = fl_cache_len(c);
+            check(fl_decode_sample_ex(model.raw_model(), c, output_ids[0], model.rope_offset(prompt.size(), cache), max_tokens - 1,
+                                      eos ? (int64_t)*eos : -1, &s1, output_ids.data() + 1, &n), "Model forward pass failed");
+            model.advance(cache, fl_cache_len(c) - len0);
+            forwards += fl_cache_len(c) - len0;
+        }
+        output_ids.resize(ended ? 0 : 1 + n);
         return output_ids;
     }
 
@@ -1019,12 +1071,19 @@ class StreamBatcher {
     // ... with the request's own top_p / top_k: one batch mixes ArgMax, Sampling::All and top-p / top-k streams
     uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, const SamplingOptions &opt,
                     OnToken on_token, OnDone on_done = {}) {
+        return submit(std::move(prompt), max_tokens, temperature, eos, opt, std::nullopt, std::move(on_token), std::move(on_done));
+    }
+    // ... and its own logit rules (logit_bias, penalties): installed on the slot's cache for the request's lifetime.  Such a request is
+    // admitted with a forward of its own even with PackedAdmit on (fl_batch_prefill's selection does not honour rules), and its rules
+    // are removed before the slot's cache is handed back or its K/V goes into the PrefixStore.
+    uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, const SamplingOptions &opt,
+                    std::optional<LogitRules> rules, OnToken on_token, OnDone on_done = {}) {
         if (opt.top_p && *opt.top_p != *opt.top_p) throw Error(FL_ERR_BAD_ARGUMENT, "top_p is NaN");
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         if (prompt.size() + 1 > cap_) throw Error(FL_ERR_BAD_ARGUMENT, "the prompt does not fit a slot's cache");
         if (!on_token) throw Error(FL_ERR_BAD_ARGUMENT, "null token callback");
         Request r;
-        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos; r.opt = opt;
+        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos; r.opt = opt; r.rules = std::move(rules);
         r.on_token = std::move(on_token); r.on_done = std::move(on_done);
         queue_.push_back(std::move(r));
         return next_id_;
@@ -1091,26 +1150,40 @@ class StreamBatcher {
     struct Request {
         uint64_t id = 0; std::vector<uint32_t> prompt; size_t max_tokens = 0; float temperature = 0.f; std::optional<uint32_t> eos;
         SamplingOptions opt;
+        std::optional<LogitRules> rules;
         OnToken on_token; OnDone on_done;
     };
     struct Slot {
         fl_cache *cache = nullptr; bool active = false; Request req; size_t pos = 0, calls = 0, emitted = 0; uint32_t tok = 0; uint64_t draws = 0;
+        bool ruled = false;                  // the cache has logit rules installed (removed in finish, or by the next admission)
         std::vector<uint32_t> held;          // with a store: the prompt and every token handed to the callback
     };
 
     // the slot becomes active only after its prefill succeeded: an exception leaves it free (and the request gone, see step())
     void admit(Slot &sl, Request r) {
         const size_t n = admit_begin(sl, r);
+        admit_single(sl, std::move(r), n);
+    }
+    // the single-prompt forward of an admission; a request's logit rules go onto the slot's cache first (the whole prompt marked as
+    // seen, a reused prefix included), so its first token is already selected under them
+    void admit_single(Slot &sl, Request r, size_t n) {
+        if (r.rules) { r.rules->install(model_->m, sl.cache, r.prompt); sl.ruled = true; }
         const fl_sampler sp = r.opt.to_ffi((double)r.temperature, 0);
         uint32_t tok = 0;
         check(fl_forward_sample_ex(model_->m, sl.cache, r.prompt.data() + n, r.prompt.size() - n, n, &sp, &tok), "Model forward pass failed");
         prefill_calls++;
         admit_end(sl, std::move(r), n, tok);
     }
+    void drop_rules(Slot &sl) {
+        if (!sl.ruled) return;
+        sl.ruled = false;
+        LogitRules::remove(model_->m, sl.cache);
+    }
     // before the forward: an empty slot cache, or (with a store) the longest stored prefix of the prompt in it; returns its length
     size_t admit_begin(Slot &sl, const Request &r) {
         sl.emitted = 0;
         sl.held.clear();
+        drop_rules(sl);                                            // (left behind only by an admission whose forward threw)
         fl_cache_reset(sl.cache);
         size_t n = 0;
         if (store_ && r.prompt.size() <= reuse_limit_) n = store_->lookup_into(sl.cache, r.prompt);
@@ -1160,9 +1233,10 @@ class StreamBatcher {
                 }
             }
             auto suffix = [](const Pair &p) { return p.r.prompt.size() - p.n; };
-            std::stable_partition(pairs.begin(), pairs.end(), [&](const Pair &p) { return suffix(p) <= max_member; });   // the packable pairs first, in slot order
+            auto packable = [&](const Pair &p) { return suffix(p) <= max_member && !p.r.rules; };   // (a ruled request takes the single call)
+            std::stable_partition(pairs.begin(), pairs.end(), packable);   // the packable pairs first, in slot order
             size_t n_packable = 0;
-            while (n_packable < pairs.size() && suffix(pairs[n_packable]) <= max_member) n_packable++;
+            while (n_packable < pairs.size() && packable(pairs[n_packable])) n_packable++;
             std::exception_ptr failed;                                // the first bookkeeping failure of a packed call, thrown once its other members are done
             try {
                 while (next < n_packable && !failed) {
@@ -1193,11 +1267,7 @@ class StreamBatcher {
                 }
                 while (next < pairs.size() && !failed) {
                     Pair &p = pairs[next++];
-                    const fl_sampler sp = p.r.opt.to_ffi((double)p.r.temperature, 0);
-                    uint32_t tok = 0;
-                    check(fl_forward_sample_ex(model_->m, p.sl->cache, p.r.prompt.data() + p.n, p.r.prompt.size() - p.n, p.n, &sp, &tok), "Model forward pass failed");
-                    prefill_calls++;
-                    admit_end(*p.sl, std::move(p.r), p.n, tok);
+                    admit_single(*p.sl, std::move(p.r), p.n);
                 }
             } catch (...) {
                 requeue_rest();
@@ -1217,9 +1287,10 @@ class StreamBatcher {
         const size_t n = sl.emitted;
         sl.req = Request{};
         std::exception_ptr failed;
+        try { drop_rules(sl); } catch (...) { failed = std::current_exception(); }
         if (store_ && !sl.held.empty()) {
             if (n > 0) sl.held.pop_back();
-            try { store_->remember(sl.cache, sl.held); } catch (...) { failed = std::current_exception(); }
+            try { store_->remember(sl.cache, sl.held); } catch (...) { if (!failed) failed = std::current_exception(); }
             sl.held.clear();
         }
         if (cb) cb(n);

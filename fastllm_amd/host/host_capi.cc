@@ -174,6 +174,38 @@ int flh_generate_logprobs(void *hv, const uint32_t *prompt, size_t T, size_t max
     });
 }
 
+namespace {
+LogitRules make_rules(size_t n_bias, const uint32_t *bias_ids, const float *bias_values, float rp, float fp, float pp) {
+    LogitRules r;
+    for (size_t i = 0; i < n_bias; i++) r.logit_bias.emplace_back(bias_ids[i], bias_values[i]);
+    r.repetition_penalty = rp; r.frequency_penalty = fp; r.presence_penalty = pp;
+    return r;
+}
+}  // namespace
+
+// ... with logit rules (generate_ids with LogitRules): n_bias (id, value) pairs and the three penalties; top_p <= 0 and top_k <= 0: off
+int flh_generate_rules(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, double top_p,
+                       int64_t top_k, size_t n_bias, const uint32_t *bias_ids, const float *bias_values, float repetition_penalty,
+                       float frequency_penalty, float presence_penalty, uint32_t *out_tokens, size_t *n_out, size_t *forwards) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        std::vector<uint32_t> p(prompt, prompt + T), r;
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        SamplingOptions opt;
+        if (top_p > 0) opt.top_p = top_p;
+        if (top_k > 0) opt.top_k = (size_t)top_k;
+        const LogitRules rules = make_rules(n_bias, bias_ids, bias_values, repetition_penalty, frequency_penalty, presence_penalty);
+        size_t fw = 0;
+        if (h->llama) { r = h->llama->generate_ids(p, max_tokens, temperature, e, opt, rules); fw = h->llama->forwards; }
+        else if (h->mistral) { r = h->mistral->generate_ids(p, max_tokens, temperature, e, opt, rules); fw = h->mistral->forwards; }
+        else { r = h->qwen->generate_ids(p, max_tokens, temperature, e, opt, rules); fw = h->qwen->forwards; }
+        for (size_t i = 0; i < r.size(); i++) out_tokens[i] = r[i];
+        *n_out = r.size();
+        if (forwards) *forwards = fw;
+        return 0;
+    });
+}
+
 // ... a greedy request with prompt-lookup drafts (LookupOptions); stream != 0: through generate_stream_ids' lookup overload.
 // stats (optional): steps, drafted, accepted of the non-stream form
 int flh_generate_lookup(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, int max_draft,
@@ -310,6 +342,25 @@ int flh_batcher_submit(void *bv, const uint32_t *prompt, size_t T, size_t max_to
         StreamBatcher::OnDone done;
         if (on_done) done = [=](size_t n) { on_done(*id, n, user); };
         *id = bh->b->submit(std::vector<uint32_t>(prompt, prompt + T), max_tokens, temperature, e,
+                            [=](uint32_t t) { return on_token(*id, t, user) != 0; }, done);
+        if (id_out) *id_out = *id;
+        return 0;
+    });
+}
+// ... a request with logit rules of its own (StreamBatcher::submit with LogitRules), as flh_generate_rules takes them
+int flh_batcher_submit_rules(void *bv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, size_t n_bias,
+                             const uint32_t *bias_ids, const float *bias_values, float repetition_penalty, float frequency_penalty,
+                             float presence_penalty, int (*on_token)(uint64_t id, uint32_t token, void *user),
+                             void (*on_done)(uint64_t id, size_t n_tokens, void *user), void *user, uint64_t *id_out) {
+    return guard([&] {
+        if (!bv || !on_token || (!prompt && T) || (n_bias && (!bias_ids || !bias_values))) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto *bh = static_cast<BatcherHandle *>(bv);
+        auto id = std::make_shared<uint64_t>(0);
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        StreamBatcher::OnDone done;
+        if (on_done) done = [=](size_t n) { on_done(*id, n, user); };
+        *id = bh->b->submit(std::vector<uint32_t>(prompt, prompt + T), max_tokens, temperature, e, SamplingOptions{},
+                            make_rules(n_bias, bias_ids, bias_values, repetition_penalty, frequency_penalty, presence_penalty),
                             [=](uint32_t t) { return on_token(*id, t, user) != 0; }, done);
         if (id_out) *id_out = *id;
         return 0;

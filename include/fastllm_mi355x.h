@@ -441,6 +441,53 @@ int fl_decode_sample_lp(fl_model *m, fl_cache *c, uint32_t first_token, size_t p
 int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                             const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp /* [n_seq] */);
 
+/* ---- logit rules: logit_bias and repetition / frequency / presence penalties inside the device decode loop -------------------------
+ * New capability (the reference has none).  What an OpenAI-compatible server is asked for as `logit_bias`, `frequency_penalty`,
+ * `presence_penalty`, and the `repetition_penalty` of the open-source servers.  The rules belong to a cache: installing them gives
+ * the cache a table of V entries {word, bias} -- word bit 31 "the id occurred in the prompt", bits 0..30 c, the times the id was
+ * produced as output -- that the decode step itself keeps up to date, by one more launch between lm_head and token selection inside
+ * the same replayed graph.  A cache that never installs rules runs exactly what it ran before.
+ *
+ * For a step whose fp32 logits row is x[0..V) (what fl_forward returns for it) the selection sees y; every operation is rounded to
+ * fp32 on its own, in this order, nothing contracted into an FMA (a numpy float32 restatement reproduces the bits):
+ *     y = x[j]
+ *     if word != 0 and repetition_penalty != 1:  y = (y > 0) ? y / rp : y * rp        (HF / vLLM form; y == 0 stays 0)
+ *     if c > 0:                                  y = y - (float)c * frequency_penalty
+ *                                                y = y - presence_penalty
+ *     y = y + bias                                                        (0 for ids without one; -inf bans an id)
+ * ArgMax (still the LAST maximal index), temperature, top-p and top-k then run on y exactly as they run on x without rules.
+ * Counting: the install seeds the table -- prompt_ids set bit 31, output_ids are counted.  Afterwards fl_decode_* and
+ * fl_batch_decode* count the INPUT token of every step as one more output before that step's row is adjusted (a decode step's input
+ * is the previous step's output, also across chunks and calls): at the step that produces output s the table holds outputs 0..s-1,
+ * each once.  fl_forward_* calls (any T) count nothing: their ids are prompt, which the seed covers.  After a decode call that
+ * stopped at its EOS the table is unspecified until the next install (the steps behind the EOS ran and were discarded).
+ * Log-probs (fl_*_lp) keep reporting the model's own distribution from the raw row; fl_forward / fl_batch_forward logits stay raw.
+ * Honoured by fl_forward_argmax, fl_forward_sample{,_ex,_lp}, fl_decode_greedy, fl_decode_sample{,_ex,_lp}, fl_batch_decode,
+ * fl_batch_decode_each{,_ex,_lp}.  FL_ERR_UNSUPPORTED, before the device or any cache is touched, while a cache involved has rules:
+ * fl_forward_verify, fl_decode_lookup, fl_batch_prefill with tokens_out, fl_batch_forward with argmax_out; and the install itself on
+ * a model with tp_size > 1.  fl_cache_truncate, fl_cache_copy_prefix and fl_cache_reset leave the rules and the table alone: a caller
+ * that rolls a request back installs again.
+ * FL_ERR_BAD_ARGUMENT, before the device is probed and with the cache as it was: wrong struct_size, nonzero _reserved, a NaN or
+ * out-of-range scalar, an id >= V in any list, n_bias > V or a duplicate bias id, a null list with a nonzero count.
+ * Memory: a cache's first install allocates V x 12 bytes of HBM + a control block (1.8 MB at V = 152 064) and V x 8 bytes of pinned
+ * host memory, freed with the cache; a batch's first step with a ruled member B x V x 4 bytes. */
+typedef struct fl_logit_rules {
+    uint32_t        struct_size;          /* sizeof(fl_logit_rules), FL_ERR_BAD_ARGUMENT otherwise */
+    uint32_t        n_bias;               /* 0 .. V entries below, ids distinct */
+    const uint32_t *bias_ids;             /* [n_bias] */
+    const float    *bias_values;          /* [n_bias] not NaN, not +inf; -inf allowed */
+    float           repetition_penalty;   /* finite, > 0; 1: off */
+    float           frequency_penalty;    /* finite; 0: off */
+    float           presence_penalty;     /* finite; 0: off */
+    int64_t         _reserved[2];         /* 0 */
+} fl_logit_rules;
+/* rules NULL: remove (the lists are ignored; the cache runs its old graphs again).  Otherwise install: the table is built on the host
+ * and sent with one asynchronous copy on the model's stream, ahead of whatever is submitted next. */
+int fl_cache_set_logit_rules(fl_model *m, fl_cache *c, const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt,
+                             const uint32_t *output_ids, size_t n_output);
+/* The table words [V] (bit 31: prompt, bits 0..30: output count) once the stream is idle.  FL_ERR_BAD_ARGUMENT: no rules installed. */
+int fl_cache_logit_counts(fl_model *m, fl_cache *c, uint32_t *words_out);
+
 int fl_synchronize(fl_model *m);
 
 /* ---- embeddings: the BERT / MiniLM encoder forward --------------------------------------------------------------------------------
@@ -579,6 +626,15 @@ int fl_op_verify_select(const float *logits /* [T][V] */, int64_t T, int64_t V, 
  * device is probed); top_ids / top_logprobs may be NULL when top_n == 0.  Launched twice: FL_ERR_HIP if the two results differ. */
 int fl_op_logprobs(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *chosen /* [T] */, int32_t top_n,
                    float *token_logprob /* [T] */, uint32_t *top_ids /* [T][top_n] or NULL */, float *top_logprobs /* [T][top_n] or NULL */);
+
+/* The logit-rules kernel alone, on host arrays (unit tests): the batch form on B rows of V logits.  Row b has its own table
+ * (words / biases [B][V]; words in/out: the counted word comes back) and scalars scalars[b] = {repetition, frequency, presence
+ * penalty}; tokens[b] is the row's input token, counted when count_input != 0 (an id >= V: none).  has_rules (optional, [B]): 0 makes
+ * row b's table entry null, and the row is copied through.  1 <= B <= 64, 1 <= V <= 1 << 24, FL_ERR_BAD_ARGUMENT otherwise (before
+ * the device is probed). */
+int fl_op_logit_rules(const float *logits /* [B][V] */, int64_t B, int64_t V, uint32_t *words /* [B][V] */, const float *biases /* [B][V] */,
+                      const float *scalars /* [B][3] */, const uint32_t *tokens /* [B] */, int32_t count_input,
+                      const uint8_t *has_rules /* [B] or NULL */, float *out /* [B][V] */);
 
 /* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
  * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read

@@ -154,6 +154,22 @@ pub struct fl_logprobs {
     pub _reserved: [i64; 2],
 }
 
+/// `fl_logit_rules`: `logit_bias` entries and the repetition / frequency / presence penalties a cache applies on the device to every
+/// row it selects a token from (fl_cache_set_logit_rules); `struct_size` is `size_of::<fl_logit_rules>()`.  `repetition_penalty` 1 and
+/// the other two 0 are off; a bias of negative infinity bans an id.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_logit_rules {
+    pub struct_size: u32,
+    pub n_bias: u32,
+    pub bias_ids: *const u32,
+    pub bias_values: *const f32,
+    pub repetition_penalty: f32,
+    pub frequency_penalty: f32,
+    pub presence_penalty: f32,
+    pub _reserved: [i64; 2],
+}
+
 /// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -438,6 +454,28 @@ extern "C" {
         token_logprob: *mut f32,
         top_ids: *mut u32,
         top_logprobs: *mut f32,
+    ) -> c_int;
+    pub fn fl_cache_set_logit_rules(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        rules: *const fl_logit_rules,
+        prompt_ids: *const u32,
+        n_prompt: usize,
+        output_ids: *const u32,
+        n_output: usize,
+    ) -> c_int;
+    pub fn fl_cache_logit_counts(m: *mut fl_model, c: *mut fl_cache, words_out: *mut u32) -> c_int;
+    pub fn fl_op_logit_rules(
+        logits: *const f32,
+        b: i64,
+        v: i64,
+        words: *mut u32,
+        biases: *const f32,
+        scalars: *const f32,
+        tokens: *const u32,
+        count_input: i32,
+        has_rules: *const u8,
+        out: *mut f32,
     ) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;

@@ -150,6 +150,21 @@ impl Sampler {
     }
 }
 
+/// `fl_logit_rules`: an OpenAI-style request's `logit_bias` (id, bias) pairs -- ids distinct, `f32::NEG_INFINITY` bans one -- and its
+/// penalties.  `repetition_penalty` 1 and the other two 0 are off.  Installed on a cache with [`Cache::set_logit_rules`].
+#[derive(Clone, Debug)]
+pub struct LogitRules {
+    pub logit_bias: Vec<(u32, f32)>,
+    pub repetition_penalty: f32,
+    pub frequency_penalty: f32,
+    pub presence_penalty: f32,
+}
+impl Default for LogitRules {
+    fn default() -> Self {
+        LogitRules { logit_bias: Vec::new(), repetition_penalty: 1.0, frequency_penalty: 0.0, presence_penalty: 0.0 }
+    }
+}
+
 /// The token-selection kernel alone (`fl_op_sample_ex`): `n_draws` successive draws from one logits vector; returns the
 /// tokens and how many tokens each draw kept.
 pub fn op_sample(logits: &[f32], s: Sampler, n_draws: usize) -> Result<(Vec<u32>, Vec<i64>)> {
@@ -479,6 +494,31 @@ impl Cache {
     /// `capacity()` (`FL_ERR_SEQ_OVERFLOW`).
     pub fn copy_prefix_from(&mut self, src: &Cache, n: usize) -> Result<()> {
         check(unsafe { ffi::fl_cache_copy_prefix(self.raw, src.raw as *const ffi::fl_cache, n) })
+    }
+    /// `fl_cache_set_logit_rules`: from now on every call that selects a token for this cache applies `rules` on the device -- inside
+    /// the replayed decode step -- to the row it selects from.  `prompt_ids` mark ids as "seen in the prompt" (repetition penalty),
+    /// `output_ids` seed the output counts, which `decode*` and the batch decode loops then keep themselves.  Log-probs and
+    /// `forward` logits stay the model's own.  Errors: an id beyond the vocabulary, a duplicate bias id, a NaN or out-of-range
+    /// scalar (`FL_ERR_BAD_ARGUMENT`); a tensor-parallel model (`FL_ERR_UNSUPPORTED`).
+    pub fn set_logit_rules(&mut self, model: &Model, rules: &LogitRules, prompt_ids: &[u32], output_ids: &[u32]) -> Result<()> {
+        let (ids, values): (Vec<u32>, Vec<f32>) = rules.logit_bias.iter().copied().unzip();
+        let r = ffi::fl_logit_rules {
+            struct_size: std::mem::size_of::<ffi::fl_logit_rules>() as u32,
+            n_bias: ids.len() as u32,
+            bias_ids: if ids.is_empty() { ptr::null() } else { ids.as_ptr() },
+            bias_values: if values.is_empty() { ptr::null() } else { values.as_ptr() },
+            repetition_penalty: rules.repetition_penalty,
+            frequency_penalty: rules.frequency_penalty,
+            presence_penalty: rules.presence_penalty,
+            _reserved: [0; 2],
+        };
+        let p = if prompt_ids.is_empty() { ptr::null() } else { prompt_ids.as_ptr() };
+        let o = if output_ids.is_empty() { ptr::null() } else { output_ids.as_ptr() };
+        check(unsafe { ffi::fl_cache_set_logit_rules(model.raw, self.raw, &r, p, prompt_ids.len(), o, output_ids.len()) })
+    }
+    /// Removes the rules: the cache runs exactly what it ran before they were installed.
+    pub fn clear_logit_rules(&mut self, model: &Model) -> Result<()> {
+        check(unsafe { ffi::fl_cache_set_logit_rules(model.raw, self.raw, ptr::null(), ptr::null(), 0, ptr::null(), 0) })
     }
     pub fn len(&self) -> usize {
         unsafe { ffi::fl_cache_len(self.raw) }
