@@ -111,6 +111,21 @@ def make_logit_rules(logit_bias=None, repetition_penalty=1.0, frequency_penalty=
     return st, (ids, vals)
 
 
+class FlGuideDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_states", C.c_uint32), ("row_ptr", C.c_void_p), ("tokens", C.c_void_p),
+                ("next", C.c_void_p), ("_reserved", C.c_int64 * 2)]
+
+
+def make_guide_desc(row_ptr, tokens, next):
+    """fl_guide_desc from the CSR arrays of a token-level automaton; returns (struct, arrays to keep alive)."""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.uint64).reshape(-1)
+    tk = np.ascontiguousarray(tokens, dtype=np.uint32).reshape(-1)
+    nx = np.ascontiguousarray(next, dtype=np.uint32).reshape(-1)
+    assert rp.size >= 1 and tk.size == nx.size
+    st = FlGuideDesc(C.sizeof(FlGuideDesc), rp.size - 1, rp.ctypes.data, tk.ctypes.data if tk.size else None, nx.ctypes.data if nx.size else None)
+    return st, (rp, tk, nx)
+
+
 class FlLookup(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_draft", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32),
                 ("_pad", C.c_int32), ("_reserved", C.c_int64 * 2)]
@@ -210,6 +225,12 @@ def lib():
         L.fl_cache_set_logit_rules.argtypes = [vp, vp, C.POINTER(FlLogitRules), vp, sz, vp, sz]
         L.fl_cache_logit_counts.argtypes = [vp, vp, vp]
         L.fl_op_logit_rules.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp]
+        L.fl_guide_create.argtypes = [vp, C.POINTER(FlGuideDesc), C.POINTER(vp)]
+        L.fl_guide_destroy.argtypes = [vp]
+        L.fl_guide_destroy.restype = None
+        L.fl_cache_set_guide.argtypes = [vp, vp, vp, C.c_uint32]
+        L.fl_cache_guide_state.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.fl_op_guide_mask.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(FlGuideDesc), vp, vp, vp, vp, vp]
         L.fl_op_attention.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]
         L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
         L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
@@ -321,6 +342,25 @@ def op_logit_rules(logits, words, biases, scalars, tokens, count_input=True, has
     _check(lib().fl_op_logit_rules(a.ctypes.data, B, V, w.ctypes.data, bs.ctypes.data, sc.ctypes.data, tk.ctypes.data, 1 if count_input else 0,
                                    hr.ctypes.data if hr is not None else None, out.ctypes.data))
     return out, w
+
+
+def op_guide_mask(logits, row_ptr, tokens, next, states, input_tokens, has_guide=None):
+    """The guided-decoding kernel alone (batch form): logits float32 [B, V], one automaton (CSR row_ptr / tokens / next), states [B]
+    and input_tokens [B] (row b first moves from states[b] along input_tokens[b]; no such edge, or an id >= V: it stays)
+    -> (masked rows float32 [B, V], the states the rows were masked in uint32 [B]).  has_guide [B]: a false entry makes the row's
+    control block null (the row is copied through)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    B, V = a.shape
+    st, keep = make_guide_desc(row_ptr, tokens, next)
+    ss = np.ascontiguousarray(states, dtype=np.uint32).reshape(B)
+    tk = np.ascontiguousarray(input_tokens, dtype=np.uint32).reshape(B)
+    hg = None if has_guide is None else np.ascontiguousarray(has_guide, dtype=np.uint8).reshape(B)
+    out = np.empty((B, V), dtype=np.float32)
+    nxt = np.zeros(B, dtype=np.uint32)
+    _check(lib().fl_op_guide_mask(a.ctypes.data, B, V, C.byref(st), ss.ctypes.data, tk.ctypes.data, hg.ctypes.data if hg is not None else None,
+                                  out.ctypes.data, nxt.ctypes.data))
+    del keep
+    return out, nxt
 
 
 def abi_version():
@@ -666,6 +706,32 @@ class Model:
             pass
 
 
+class Guide:
+    """fl_guide: an immutable token-level automaton of one model (CSR: state s allows tokens[row_ptr[s]:row_ptr[s + 1]], tokens[e]
+    leads to state next[e]), shareable by any number of its caches (Cache.set_guide)."""
+
+    def __init__(self, model, row_ptr, tokens, next):
+        st, keep = make_guide_desc(row_ptr, tokens, next)
+        h = C.c_void_p()
+        _check(lib().fl_guide_create(model._h, C.byref(st), C.byref(h)))
+        del keep
+        self._h = h
+        self._model = model
+        self.n_states = int(st.n_states)
+
+    def close(self):
+        """fl_guide_destroy: drops this handle's reference (a cache that has the guide installed keeps its own)."""
+        if getattr(self, "_h", None):
+            lib().fl_guide_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """fl_batch: up to 64 caches of one model decoded together."""
 
@@ -786,6 +852,20 @@ class Cache:
         out = np.zeros(self._model.V, dtype=np.uint32)
         _check(lib().fl_cache_logit_counts(self._model._h, self._h, out.ctypes.data))
         return out
+
+    def set_guide(self, guide, state=0):
+        """fl_cache_set_guide: every token this cache's calls select comes from the list of the automaton's current state, and moves
+        the cache along its edge.  truncate / reset / copy_prefix leave the state alone: set it again after a rollback."""
+        _check(lib().fl_cache_set_guide(self._model._h, self._h, guide._h, int(state)))
+
+    def clear_guide(self):
+        _check(lib().fl_cache_set_guide(self._model._h, self._h, None, 0))
+
+    def guide_state(self):
+        """fl_cache_guide_state: the state in which the next selected token is looked up."""
+        out = C.c_uint32(0)
+        _check(lib().fl_cache_guide_state(self._h, C.byref(out)))
+        return int(out.value)
 
     def __len__(self):
         return lib().fl_cache_len(self._h)

@@ -286,6 +286,36 @@ int fl_cache_logit_counts(fl_model *m, fl_cache *c, uint32_t *words_out) {
     });
 }
 
+// ---- guided decoding: the automaton's argument errors are decided before the model or the device is looked at
+int fl_guide_create(fl_model *m, const fl_guide_desc *desc, fl_guide **out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_create: null out");
+        *out = nullptr;
+        Guide *g = nullptr;
+        FL_TRY(guide_create(M(m), desc, &g));
+        *out = reinterpret_cast<fl_guide *>(g);
+        return FL_OK;
+    });
+}
+
+void fl_guide_destroy(fl_guide *g) {
+    guarded_void([&]() {
+        guide_release(reinterpret_cast<Guide *>(g));
+    });
+}
+
+int fl_cache_set_guide(fl_model *m, fl_cache *c, fl_guide *g, uint32_t state) {
+    return guarded([&]() -> int {
+        return cache_set_guide(M(m), C(c), reinterpret_cast<Guide *>(g), state);
+    });
+}
+
+int fl_cache_guide_state(const fl_cache *c, uint32_t *state_out) {
+    return guarded([&]() -> int {
+        return cache_guide_state(C(c), state_out);
+    });
+}
+
 int fl_batch_create(fl_model *m, fl_cache *const *caches, size_t n, fl_batch **out) {
     return guarded([&]() -> int {
         if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null out");

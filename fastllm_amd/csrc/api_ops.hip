@@ -233,6 +233,54 @@ int fl_op_logit_rules(const float *logits, int64_t B, int64_t V, uint32_t *words
     });
 }
 
+int fl_op_guide_mask(const float *logits, int64_t B, int64_t V, const fl_guide_desc *desc, const uint32_t *states, const uint32_t *tokens,
+                     const uint8_t *has_guide, float *out, uint32_t *next_states) {
+    return guarded([&]() -> int {
+        if (!logits || !states || !tokens || !out || !next_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_guide_mask: null argument");
+        if (B < 1 || B > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_guide_mask: B %lld not in 1..64", (long long)B);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_guide_mask: V %lld not in 1..2^24", (long long)V);
+        FL_TRY(check_guide(desc, V));
+        for (int64_t b = 0; b < B; b++)
+            if (states[b] >= desc->n_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_guide_mask: states[%lld] = %u is not below n_states %u", (long long)b, states[b], desc->n_states);
+        OpScope S;
+        FL_TRY(S.begin());
+        const size_t ns = desc->n_states, nnz = (size_t)desc->row_ptr[ns];
+        float *lg, *od; uint32_t *tk, *ltok, *lnext; uint64_t *rp; GuideCtl *ctl; GuideCtl **ctls;
+        FL_TRY(S.upload(&lg, logits, (size_t)B * V * 4));              // the rows back to back as a batch keeps them
+        FL_TRY(S.alloc(&od, (size_t)B * V * 4));
+        FL_TRY(S.upload(&tk, tokens, (size_t)B * 4));
+        FL_TRY(S.upload(&rp, desc->row_ptr, (ns + 1) * 8));
+        FL_TRY(S.upload(&ltok, desc->tokens, nnz * 4));
+        FL_TRY(S.upload(&lnext, desc->next, nnz * 4));
+        FL_TRY(S.alloc(&ctl, (size_t)B * sizeof(GuideCtl)));
+        std::vector<GuideCtl *> ptrs((size_t)B, nullptr);
+        for (int64_t b = 0; b < B; b++) if (!has_guide || has_guide[b]) ptrs[(size_t)b] = ctl + b;
+        FL_TRY(S.upload(&ctls, ptrs.data(), (size_t)B * sizeof(GuideCtl *)));
+        GuideSrc src;
+        src.ctls = ctls; src.tokens = tk; src.out = od;
+        std::vector<float> rows[2];
+        std::vector<GuideCtl> back[2];
+        for (int rep = 0; rep < 2; rep++) {                               // twice: workgroups search and fill in any order, the result must not depend on it
+            rows[rep].resize((size_t)B * V);
+            back[rep].resize((size_t)B);
+            for (int64_t b = 0; b < B; b++)
+                FL_TRY(launch_set_guide_ctl(S.L, ctl + b, GuideCtl{rp, ltok, lnext, nullptr, {states[b], states[b]}}));
+            FL_HIP(hipMemsetAsync(od, 0x55, (size_t)B * V * 4, S.s));
+            FL_TRY(launch_guide_mask(S.L, lg, V, (int)B, src));
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipMemcpy(rows[rep].data(), od, (size_t)B * V * 4, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(back[rep].data(), ctl, (size_t)B * sizeof(GuideCtl), hipMemcpyDeviceToHost));
+        }
+        if (memcmp(rows[0].data(), rows[1].data(), (size_t)B * V * 4)) FL_FAIL(FL_ERR_HIP, "guide_mask: a repeated launch gave another row");
+        for (int64_t b = 0; b < B; b++) {
+            if (back[0][(size_t)b].state[0] != back[1][(size_t)b].state[0]) FL_FAIL(FL_ERR_HIP, "guide_mask: a repeated launch gave another state");
+            next_states[b] = back[0][(size_t)b].state[0];                 // (a row without a guide: the state the block was set to)
+        }
+        memcpy(out, rows[0].data(), (size_t)B * V * 4);
+        return FL_OK;
+    });
+}
+
 int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
                             int32_t dtype, float *out) {
     return guarded([&]() -> int {

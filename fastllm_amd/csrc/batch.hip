@@ -129,25 +129,40 @@ int batch_replace(Batch *b, size_t slot, Cache *c) {
         LogitRulesCtl *ctl = c->rules_on ? cs.rule_ctl : nullptr;
         FL_HIP(hipMemcpy(b->rule_ctls + slot, &ctl, sizeof ctl, hipMemcpyHostToDevice));
     }
+    if (b->guide_ctls) {                                          // ... and the guide launch
+        GuideCtl *ctl = c->guide ? cs.guide_ctl : nullptr;
+        FL_HIP(hipMemcpy(b->guide_ctls + slot, &ctl, sizeof ctl, hipMemcpyHostToDevice));
+    }
     return FL_OK;
 }
 
-static int enqueue_batch_step_unfused(Batch *b, bool rules);
+static int enqueue_batch_step_unfused(Batch *b, int kind);
 
-// Token selection of every sequence.  rules: a member has logit rules -- one launch first leaves every row adjusted by its own
-// member's rules (copied through for a member without) in logits_adj, which the selection then reads; off: the launch there always was
-static int batch_select(Batch *b, Launcher &L, bool rules) {
+// Token selection of every sequence.  kStepRules: a member has logit rules -- one launch first leaves every row adjusted by its own
+// member's rules (copied through for a member without) in logits_adj; kStepGuide: a member has a guide -- one launch then leaves every
+// row (adjusted or raw) masked under its own member's state (copied through for a member without) in logits_guided; the selection
+// reads the last of them.  Neither: the launch there always was
+static int batch_select(Batch *b, Launcher &L, int kind) {
     const int64_t V = b->m->D.V;
-    if (!rules) return launch_select_advance_batch(L, b->logits, V, b->seqs_dev, b->B, 1);
-    LogitRulesSrc src;
-    src.seqs = b->seqs_dev; src.ctls = b->rule_ctls; src.out = b->logits_adj;
-    FL_TRY(launch_logit_rules(L, b->logits, V, b->B, src));
-    return launch_select_advance_batch(L, b->logits_adj, V, b->seqs_dev, b->B, 1);
+    const float *rows = b->logits;
+    if (kind & kStepRules) {
+        LogitRulesSrc src;
+        src.seqs = b->seqs_dev; src.ctls = b->rule_ctls; src.out = b->logits_adj;
+        FL_TRY(launch_logit_rules(L, rows, V, b->B, src));
+        rows = b->logits_adj;
+    }
+    if (kind & kStepGuide) {
+        GuideSrc src;
+        src.seqs = b->seqs_dev; src.ctls = b->guide_ctls; src.out = b->logits_guided;
+        FL_TRY(launch_guide_mask(L, rows, V, b->B, src));
+        rows = b->logits_guided;
+    }
+    return launch_select_advance_batch(L, rows, V, b->seqs_dev, b->B, 1);
 }
 
 // One decode step of the whole batch: the 5-launch layer of enqueue_decode_fused with B activation rows.
-static int enqueue_batch_step(Batch *b, bool rules = false) {
-    if (b->unfused) return enqueue_batch_step_unfused(b, rules);
+static int enqueue_batch_step(Batch *b, int kind = 0) {
+    if (b->unfused) return enqueue_batch_step_unfused(b, kind);
     Model *m = b->m;
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
@@ -182,12 +197,12 @@ static int enqueue_batch_step(Batch *b, bool rules = false) {
     h.B = B; h.seqs = b->seqs_dev; h.W = sh.lm_head; h.out = b->logits; h.N = (int)D.V; h.K = (int)D.h; h.pro = PRO_NORM;
     h.x_in = b->x_res; h.delta = b->delta; h.n_slab = b->nks_down; h.slab_stride = slab; h.norm_w = sh.norm; h.eps = D.eps;
     FL_TRY(launch_gemv_batch(L, h));
-    return batch_select(b, L, rules);
+    return batch_select(b, L, kind);
 }
 
 // The same step as 8 launches per layer: rmsnorm_add -> QKV GEMM -> RoPE / KV append -> attention -> o_proj GEMM (K
 // slabs) -> rmsnorm_add (sums them) -> gate/up GEMM -> down GEMM (K slabs); launch_linear picks gemm_skinny_kernel.
-static int enqueue_batch_step_unfused(Batch *b, bool rules) {
+static int enqueue_batch_step_unfused(Batch *b, int kind) {
     Model *m = b->m;
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
@@ -260,7 +275,7 @@ static int enqueue_batch_step_unfused(Batch *b, bool rules) {
         }
         FL_TRY(launch_rms_finalize(L, sc.rs_part, np, D.eps, sc.inv_rms, T, D.h));
         FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
-        return batch_select(b, L, rules);
+        return batch_select(b, L, kind);
     }
     for (int64_t l = 0; l < D.L; l++) {
         LayerW &ly = sh.layers[l];
@@ -301,19 +316,19 @@ static int enqueue_batch_step_unfused(Batch *b, bool rules) {
     } else {
         FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
     }
-    return batch_select(b, L, rules);
+    return batch_select(b, L, kind);
 }
 
-// kind (kStepLp | kStepRules): the step with every sequence's log-prob records written behind token selection (one more launch of B
-// workgroups) and / or the logit-rules launch in front of it, each kind a graph of its own; graph[0] is what it always was
+// kind (kStepLp | kStepRules | kStepGuide): the step with every sequence's log-prob records written behind token selection (one more
+// launch of B workgroups) and / or the logit-rules and guide launches in front of it, each kind a graph of its own; graph[0] is what it
+// always was
 static int batch_step(Batch *b, int kind = 0) {
     Model *m = b->m;
     Shard &sh = m->shards[0];
     const bool graphable = m->use_graph && !m->profiling && !b->graph_failed;
-    const bool rules = (kind & kStepRules) != 0;
-    if (!(kind & kStepLp)) return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, rules] { return enqueue_batch_step(b, rules); });
-    return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, m, &sh, rules]() -> int {
-        FL_TRY(enqueue_batch_step(b, rules));
+    if (!(kind & kStepLp)) return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, kind] { return enqueue_batch_step(b, kind); });
+    return replay_or_capture({{sh.device, sh.stream, &b->graph[kind]}}, graphable, b->graph_failed, b->warm_steps[kind], [b, m, &sh, kind]() -> int {
+        FL_TRY(enqueue_batch_step(b, kind));
         Launcher L = make_launcher(m, sh);
         LogprobSrc src;
         src.seqs = b->seqs_dev; src.ctls = b->lp_ctls;
@@ -407,7 +422,18 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
         }
         FL_HIP(hipMemcpy(b->rule_ctls, ctls.data(), sizeof(LogitRulesCtl *) * (size_t)B, hipMemcpyHostToDevice));   // (synchronous: ctls is a stack vector)
     }
-    const int kind = (lp_each ? kStepLp : 0) | (rules ? kStepRules : 0);
+    bool guided = false;
+    for (int i = 0; i < B; i++) guided = guided || b->caches[i]->guide;
+    if (guided) {
+        // the masked rows and the members' control blocks (null: no guide -- the row is copied through); each guided member's state is
+        // written per chunk below
+        if (!b->guide_ctls) FL_TRY(dev_alloc(b->allocs, (void **)&b->guide_ctls, sizeof(GuideCtl *) * (size_t)B, nullptr));
+        if (!b->logits_guided) FL_TRY(dev_alloc(b->allocs, (void **)&b->logits_guided, (size_t)B * m->D.V * 4, nullptr));
+        std::vector<GuideCtl *> ctls((size_t)B, nullptr);
+        for (int i = 0; i < B; i++) if (b->caches[i]->guide) ctls[(size_t)i] = b->caches[i]->shards[0].guide_ctl;
+        FL_HIP(hipMemcpy(b->guide_ctls, ctls.data(), sizeof(GuideCtl *) * (size_t)B, hipMemcpyHostToDevice));   // (synchronous: ctls is a stack vector)
+    }
+    const int kind = (lp_each ? kStepLp : 0) | (rules ? kStepRules : 0) | (guided ? kStepGuide : 0);
     std::vector<uint32_t> tok(first, first + B);
     std::vector<char> finished(B, 0);
     std::vector<size_t> len0(B);
@@ -417,6 +443,8 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
         const size_t nb = std::min(n_steps - done, kBatchChunk);
         for (int i = 0; i < B; i++)
             FL_TRY(set_shard_state(m, sh, b->caches[i]->shards[0], tok[i], pos[i] + done, len0[i] + done, len0[i] + done, 0u, eoss[(size_t)i], samplers[(size_t)i], done == 0));
+        for (int i = 0; i < B; i++)
+            if (b->caches[i]->guide) FL_TRY(set_guide_ctl(m, b->caches[i]));   // the host's state: the device advances it inside the chunk
         for (size_t s = 0; s < nb; s++) FL_TRY(batch_step(b, kind));
         FL_TRY(batch_finish(b, nb, lp_each != nullptr));
         bool all_finished = true;
@@ -424,6 +452,7 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
             if (!finished[i]) {
                 for (size_t s = 0; s < nb; s++) {
                     const uint32_t t = b->host_tokens[(size_t)i * kBatchChunk + s];
+                    if (const Guide *g = b->caches[i]->guide) b->caches[i]->guide_state = g->walk(b->caches[i]->guide_state, t);   // (the EOS's edge too; the walk stops there)
                     if (eoss[(size_t)i] >= 0 && (int64_t)t == eoss[(size_t)i]) {   // as fl_decode_greedy: the EOS forward counts, the token does not
                         finished[i] = 1;
                         b->caches[i]->len = len0[i] + done + s + 1;
@@ -450,7 +479,10 @@ int batch_forward(Batch *b, const uint32_t *tokens, const size_t *pos, float *lo
     Model *m = b->m;
     const int B = b->B;
     for (int i = 0; i < B; i++) FL_TRY(check_token(m, tokens[i], "token"));
-    if (tokens_out) for (int i = 0; i < B; i++) FL_TRY(refuse_logit_rules(b->caches[i], "fl_batch_forward with argmax_out"));   // (its ArgMax reads the raw rows)
+    if (tokens_out) for (int i = 0; i < B; i++) {                    // (its ArgMax reads the raw rows)
+        FL_TRY(refuse_logit_rules(b->caches[i], "fl_batch_forward with argmax_out"));
+        FL_TRY(refuse_guide(b->caches[i], "fl_batch_forward with argmax_out"));
+    }
     const SampleState sampler{};
     std::lock_guard<std::mutex> lock(m->mu);
     Shard &sh = m->shards[0];

@@ -264,6 +264,18 @@ struct LogitRulesCtl {
     float *out;                  // [V] the adjusted row of a single sequence (a batch's rows go to the batch's own buffer)
 };
 
+// Guided decoding (fl_cache_set_guide): the control block of a guided cache, read by guide_mask_kernel (k_guide.hip) from device memory,
+// so one captured graph serves every guide.  The CSR arrays are the installed guide's device copy; state[] is the automaton state by
+// step parity: the step with StepState.step == s reads state[s & 1] and writes state[(s + 1) & 1] (the host writes both at the start
+// of every call and chunk).
+struct GuideCtl {
+    const uint64_t *row_ptr;     // [n_states + 1]
+    const uint32_t *tokens;      // [nnz] ascending within a state, < V
+    const uint32_t *next;        // [nnz] < n_states
+    float *out;                  // [V] the masked row of a single sequence (a batch's rows go to the batch's own buffer)
+    uint32_t state[2];
+};
+
 // acc += a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (gfx950 VOP2; hipcc has no selectable builtin for it)
 __device__ inline float dot2c_bf16(unsigned a, unsigned b, float acc) {
     asm("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));

@@ -442,6 +442,23 @@ struct LogitRulesSrc {
 };
 int launch_logit_rules(Launcher &L, const float *logits, int64_t V, int rows, const LogitRulesSrc &src);
 int launch_set_logit_rules_ctl(Launcher &L, LogitRulesCtl *ctl, const LogitRulesCtl &value);
+// Guided decoding (k_guide.hip): out row b = logits row b with -inf outside the token list of row b's automaton state, one launch
+// between lm_head (or the rules launch) and token selection; logits and out must be different buffers.  At a step > 0 the state first
+// moves along the edge of the row's input token.  Who a row belongs to:
+//   st + ctl          one sequence (rows == 1): step and token of st, output ctl->out
+//   seqs + ctls + out a batch: row b is sequence b (its SeqRef's StepState, ctls[b]; a null entry copies the row through), out [B][V]
+//   tokens + ctls + out   fl_op_guide_mask: row b moves from ctls[b]->state[1] along tokens[b] (no edge, or >= V: it stays); the state
+//                     the row was masked in comes back in ctls[b]->state[0]
+struct GuideSrc {
+    const StepState *st = nullptr;
+    const SeqRef *seqs = nullptr;
+    GuideCtl *ctl = nullptr;
+    GuideCtl *const *ctls = nullptr;
+    const uint32_t *tokens = nullptr;
+    float *out = nullptr;
+};
+int launch_guide_mask(Launcher &L, const float *logits, int64_t V, int rows, const GuideSrc &src);
+int launch_set_guide_ctl(Launcher &L, GuideCtl *ctl, const GuideCtl &value);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

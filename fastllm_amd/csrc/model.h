@@ -158,8 +158,8 @@ struct CacheShard {
     unsigned *counters = nullptr;        // split-S arrival tickets, [Hkvs * q-groups]
     unsigned *heads_done = nullptr;      // [L][Hkv] fused attention+o_proj: split partials published per kv head since set_state
     float *ao_part = nullptr;            // ... and the partials: [Hs][ao_nsplit][d + 4] (o, m, l)
-    // the decode step as a graph, one per kind (kStepRules | kStepLp): [0] is the plain step and never has the launches of the others
-    hipGraphExec_t graph[4] = {};
+    // the decode step as a graph, one per kind (kStepGuide | kStepRules | kStepLp): [0] is the plain step and never has the launches of the others
+    hipGraphExec_t graph[8] = {};
     // token log-probabilities (fl_*_lp): allocated at the cache's first such call, so a cache that never asks pays nothing
     LogprobRec *lp_recs = nullptr;       // [kOutTokensCap] one record per step of a chunk
     LogprobCtl *lp_ctl = nullptr;        // where token_logprobs_kernel finds them, and the call's top_n
@@ -168,11 +168,30 @@ struct CacheShard {
     LogitRulesCtl *rule_ctl = nullptr;   // the call's scalars and count_input flag, where logit_rules_kernel reads them
     float *logits_adj = nullptr;         // [V] the adjusted row: what token selection reads while rules are installed
     LogitRuleEntry *rule_image = nullptr;   // pinned [V]: the table as an install builds it, source of its one async copy
+    // guided decoding (fl_cache_set_guide): allocated at the cache's first install
+    GuideCtl *guide_ctl = nullptr;       // the installed guide's arrays and the two state words, where guide_mask_kernel reads them
+    float *logits_guided = nullptr;      // [V] the masked row: what token selection reads while a guide is installed
     std::vector<void *> allocs;
 };
 
 constexpr size_t kOutTokensCap = 4096;
-enum { kStepLp = 1, kStepRules = 2 };    // kinds of decode step: index into the graph / warm_steps slots
+enum { kStepLp = 1, kStepRules = 2, kStepGuide = 4 };    // kinds of decode step: index into the graph / warm_steps slots
+
+// fl_guide: an immutable token-level automaton of one model in CSR form -- the host copy (the host walks a call's tokens through it:
+// it is authoritative for a cache's state) and one device copy, 8 bytes per edge + 8 per state each.  Reference-counted: the creator
+// holds one reference, every cache that has it installed another.
+struct Guide {
+    Model *m = nullptr;
+    std::atomic<int> refs{1};
+    uint32_t n_states = 0;
+    std::vector<uint64_t> row_ptr;
+    std::vector<uint32_t> tokens, next;
+    uint64_t *row_ptr_dev = nullptr;
+    uint32_t *tokens_dev = nullptr, *next_dev = nullptr;
+    // the state after selecting token t in state s (no edge: s)
+    uint32_t walk(uint32_t s, uint32_t t) const;
+    ~Guide();
+};
 
 struct Cache {
     Model *m = nullptr;
@@ -183,10 +202,12 @@ struct Cache {
     bool fuse_oproj = false;     // this cache's decode steps use the fused attention+o_proj launch
     int ao_nsplit = 0, ao_waves = 4;   // ... with this many key splits per kv head, 32 * ao_waves keys per split and step
     int nsplit = 1;
-    int warm_steps[4] = {};      // eager decode steps done, per kind of step (its graph is captured after the first)
+    int warm_steps[8] = {};      // eager decode steps done, per kind of step (its graph is captured after the first)
     bool graph_failed = false;
     bool rules_on = false;       // logit rules installed: the steps run logit_rules_kernel and select from logits_adj
     float rule_rp = 1.f, rule_fp = 0.f, rule_pp = 0.f;
+    Guide *guide = nullptr;      // guided decoding: the installed automaton (a reference of this cache's own) and the state in which the
+    uint32_t guide_state = 0;    // next selected token is looked up -- host state, like len; written to the device per call and chunk
     std::vector<CacheShard> shards;
     ~Cache();
 };
@@ -215,9 +236,9 @@ struct Batch {
     float *logits_local = nullptr, *logits_ranks = nullptr;   // tensor-parallel rank: its [B][Vs] block, and the gathered [tp][B][Vs]
     uint32_t *host_tokens = nullptr;             // pinned [B][kBatchChunk]
     StepState *host_states = nullptr;            // pinned [B]
-    hipGraphExec_t graph[4] = {};                // the step per kind (kStepRules | kStepLp), as a cache's
+    hipGraphExec_t graph[8] = {};                // the step per kind (kStepGuide | kStepRules | kStepLp), as a cache's
     bool graph_failed = false;
-    int warm_steps[4] = {};
+    int warm_steps[8] = {};
     // fl_batch_decode_each_lp: the step with the log-prob launch behind token selection, the sequences' LogprobCtl pointers [B]
     // (written at the start of every such call) and the pinned [B][kBatchChunk] records; allocated at the batch's first such call
     LogprobCtl **lp_ctls = nullptr;
@@ -226,6 +247,9 @@ struct Batch {
     // by fl_batch_replace) and the adjusted rows [B][V]; allocated at the batch's first step with a ruled member
     LogitRulesCtl **rule_ctls = nullptr;
     float *logits_adj = nullptr;
+    // guided decoding: the same pair -- the members' GuideCtl [B] (null: no guide, the row is copied through) and the masked rows [B][V]
+    GuideCtl **guide_ctls = nullptr;
+    float *logits_guided = nullptr;
     std::vector<void *> allocs;
     ~Batch();
 };
@@ -302,6 +326,18 @@ int cache_logit_counts(Model *m, Cache *c, uint32_t *words_out);
 int set_logit_rules_ctl(Model *m, Cache *c, bool count_input);
 // FL_ERR_UNSUPPORTED for an entry point that does not honour a cache's installed rules
 int refuse_logit_rules(const Cache *c, const char *what);
+
+// fl_guide_create / fl_guide_destroy / fl_cache_set_guide / fl_cache_guide_state.  check_guide: the struct and the arrays alone
+// (V <= 0: not known), no device
+int check_guide(const fl_guide_desc *desc, int64_t V);
+int guide_create(Model *m, const fl_guide_desc *desc, Guide **out);
+void guide_release(Guide *g);
+int cache_set_guide(Model *m, Cache *c, Guide *g, uint32_t state);
+int cache_guide_state(const Cache *c, uint32_t *state_out);
+// the cache's guide arrays and its host state into its control block, on the stream ahead of a call's (or chunk's) steps
+int set_guide_ctl(Model *m, Cache *c);
+// FL_ERR_UNSUPPORTED for an entry point that does not honour a cache's installed guide
+int refuse_guide(const Cache *c, const char *what);
 
 // fl_cache_truncate / fl_forward_verify / fl_decode_lookup (speculative greedy decode)
 int cache_truncate(Cache *c, size_t len);

@@ -34,14 +34,17 @@ int attn_cache_nsplit(bool v_transposed, size_t max_seq, int64_t d) {
 
 Cache::~Cache() {
     if (!m) return;
-    std::lock_guard<std::mutex> lock(m->mu);       // not while another thread captures on the model's stream
-    for (size_t i = 0; i < shards.size(); i++) {
-        (void)hipSetDevice(m->shards[i].device);
-        (void)hipStreamSynchronize(m->shards[i].stream);
-        for (auto g : shards[i].graph) if (g) (void)hipGraphExecDestroy(g);
-        for (void *p : shards[i].allocs) (void)hipFree(p);
-        if (shards[i].rule_image) (void)hipHostFree(shards[i].rule_image);
+    {
+        std::lock_guard<std::mutex> lock(m->mu);   // not while another thread captures on the model's stream
+        for (size_t i = 0; i < shards.size(); i++) {
+            (void)hipSetDevice(m->shards[i].device);
+            (void)hipStreamSynchronize(m->shards[i].stream);
+            for (auto g : shards[i].graph) if (g) (void)hipGraphExecDestroy(g);
+            for (void *p : shards[i].allocs) (void)hipFree(p);
+            if (shards[i].rule_image) (void)hipHostFree(shards[i].rule_image);
+        }
     }
+    if (guide) guide_release(guide);               // (outside the lock: the last reference frees the device copy under it)
 }
 
 int cache_create(Model *m, size_t max_seq, Cache **out) {
@@ -652,13 +655,24 @@ static int set_state(Model *m, Cache *c, uint32_t token, size_t pos, size_t len,
 
 // rules: the cache's logit rules are on -- logit_rules_kernel leaves the adjusted row in logits_adj, and the selection reads that, as
 // a full pass (the lm_head epilogue's ArgMax candidates belong to the raw row); off: exactly the launch there has always been
-static int enqueue_argmax(Model *m, Cache *c, int advance, bool rules = false) {
+// guide: a guide is installed too -- guide_mask_kernel then leaves that row (or the raw one) masked in logits_guided, the last word
+static int enqueue_argmax(Model *m, Cache *c, int advance, bool rules = false, bool guide = false) {
     return each_shard(m, c, [&](Shard &sh, CacheShard &cs, Launcher &L) -> int {
-        if (rules) {
-            LogitRulesSrc src;
-            src.st = cs.st; src.ctl = cs.rule_ctl;
-            FL_TRY(launch_logit_rules(L, sh.logits_full, m->D.V, 1, src));
-            return launch_select_advance(L, cs.logits_adj, m->D.V, cs.st, cs.ss, cs.sel_scratch, cs.out_tokens, advance, nullptr, sh.eng_epoch);
+        if (rules || guide) {
+            const float *row = sh.logits_full;
+            if (rules) {
+                LogitRulesSrc src;
+                src.st = cs.st; src.ctl = cs.rule_ctl;
+                FL_TRY(launch_logit_rules(L, row, m->D.V, 1, src));
+                row = cs.logits_adj;
+            }
+            if (guide) {
+                GuideSrc src;
+                src.st = cs.st; src.ctl = cs.guide_ctl;
+                FL_TRY(launch_guide_mask(L, row, m->D.V, 1, src));
+                row = cs.logits_guided;
+            }
+            return launch_select_advance(L, row, m->D.V, cs.st, cs.ss, cs.sel_scratch, cs.out_tokens, advance, nullptr, sh.eng_epoch);
         }
         return launch_select_advance(L, sh.logits_full, m->D.V, cs.st, cs.ss, cs.sel_scratch, cs.out_tokens, advance, sh.amax_valid ? sh.amax : nullptr, sh.eng_epoch);
     });
@@ -750,6 +764,137 @@ int set_logit_rules_ctl(Model *m, Cache *c, bool count_input) {
     Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
     Launcher L = make_launcher(m, sh);
     return launch_set_logit_rules_ctl(L, cs.rule_ctl, LogitRulesCtl{c->rule_rp, c->rule_fp, c->rule_pp, count_input ? 1u : 0u, cs.rule_tab, cs.logits_adj});
+}
+
+// ---- guided decoding (fl_guide_create, fl_cache_set_guide)
+int check_guide(const fl_guide_desc *d, int64_t V) {
+    if (!d) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_guide_desc (desc)");
+    if (d->struct_size != sizeof(fl_guide_desc)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.struct_size is %u, expected %zu", d->struct_size, sizeof(fl_guide_desc));
+    if (d->_reserved[0] || d->_reserved[1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc._reserved must be 0");
+    if (d->n_states == 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.n_states is 0");
+    if (!d->row_ptr || !d->tokens || !d->next) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.row_ptr / tokens / next is null");
+    if (d->row_ptr[0] != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.row_ptr[0] is %llu, not 0", (unsigned long long)d->row_ptr[0]);
+    for (uint32_t s = 0; s < d->n_states; s++) {                      // row_ptr as a whole first: it says how long the other two are
+        const uint64_t r0 = d->row_ptr[s], r1 = d->row_ptr[s + 1];
+        if (r1 < r0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.row_ptr decreases at state %u", s);
+        if (r1 == r0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc: state %u has no edge (every logit would be -inf)", s);
+        if (r1 - r0 > 0x7fffffffull) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.row_ptr: state %u has more than 2^31 - 1 edges", s);
+    }
+    for (uint32_t s = 0; s < d->n_states; s++) {
+        const uint64_t r0 = d->row_ptr[s], r1 = d->row_ptr[s + 1];
+        for (uint64_t e = r0; e < r1; e++) {
+            if (e > r0 && d->tokens[e] <= d->tokens[e - 1])
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.tokens of state %u are not strictly ascending (%u after %u)", s, d->tokens[e], d->tokens[e - 1]);
+            if (V > 0 && (int64_t)d->tokens[e] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.tokens: id %u of state %u out of range (vocab %lld)", d->tokens[e], s, (long long)V);
+            if (d->next[e] >= d->n_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_desc.next: %u of state %u is not below n_states %u", d->next[e], s, d->n_states);
+        }
+    }
+    return FL_OK;
+}
+
+uint32_t Guide::walk(uint32_t s, uint32_t t) const {
+    const uint32_t *b = tokens.data() + row_ptr[s], *e = tokens.data() + row_ptr[s + 1];
+    const uint32_t *it = std::lower_bound(b, e, t);
+    return it != e && *it == t ? next[(size_t)(it - tokens.data())] : s;
+}
+
+Guide::~Guide() {
+    if (!m) return;
+    {
+        std::lock_guard<std::mutex> lock(m->mu);
+        (void)hipSetDevice(m->shards[0].device);
+        (void)hipStreamSynchronize(m->shards[0].stream);
+        if (row_ptr_dev) (void)hipFree(row_ptr_dev);
+        if (tokens_dev) (void)hipFree(tokens_dev);
+        if (next_dev) (void)hipFree(next_dev);
+    }
+    if (m->refs.fetch_sub(1) == 1) delete m;
+}
+
+void guide_release(Guide *g) {
+    if (g && g->refs.fetch_sub(1) == 1) delete g;
+}
+
+int guide_create(Model *m, const fl_guide_desc *desc, Guide **out) {
+    if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_guide_create: null out");
+    *out = nullptr;
+    FL_TRY(check_guide(desc, 0));
+    if (!m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null model");
+    FL_TRY(check_guide(desc, m->D.V));
+    if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "guided decoding does not run under tensor parallelism (tp_size %d)", m->tp);
+    const size_t ns = desc->n_states, nnz = (size_t)desc->row_ptr[ns];
+    std::unique_ptr<Guide> g(new Guide);
+    g->n_states = desc->n_states;
+    g->row_ptr.assign(desc->row_ptr, desc->row_ptr + ns + 1);
+    g->tokens.assign(desc->tokens, desc->tokens + nnz);
+    g->next.assign(desc->next, desc->next + nnz);
+    {
+        std::lock_guard<std::mutex> lock(m->mu);
+        Shard &sh = m->shards[0];
+        FL_HIP(hipSetDevice(sh.device));
+        void *rp = nullptr, *tk = nullptr, *nx = nullptr;
+        hipError_t e = hipMalloc(&rp, (ns + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc(&tk, nnz * 4);
+        if (e == hipSuccess) e = hipMalloc(&nx, nnz * 4);
+        if (e == hipSuccess) e = hipMemcpy(rp, g->row_ptr.data(), (ns + 1) * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(tk, g->tokens.data(), nnz * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(nx, g->next.data(), nnz * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (rp) (void)hipFree(rp);
+            if (tk) (void)hipFree(tk);
+            if (nx) (void)hipFree(nx);
+            FL_FAIL(e == hipErrorOutOfMemory ? FL_ERR_OOM : FL_ERR_HIP, "fl_guide_create: %s (%zu states, %zu edges)", hipGetErrorString(e), ns, nnz);
+        }
+        g->row_ptr_dev = (uint64_t *)rp; g->tokens_dev = (uint32_t *)tk; g->next_dev = (uint32_t *)nx;
+    }
+    g->m = m;                                                         // (from here ~Guide frees the device copy and drops the model reference)
+    m->refs.fetch_add(1);
+    *out = g.release();
+    return FL_OK;
+}
+
+int refuse_guide(const Cache *c, const char *what) {
+    if (c && c->guide) FL_FAIL(FL_ERR_UNSUPPORTED, "%s does not honour a guide: remove it from the cache first (fl_cache_set_guide with NULL)", what);
+    return FL_OK;
+}
+
+int cache_set_guide(Model *m, Cache *c, Guide *g, uint32_t state) {
+    if (!m || !c) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null model or cache");
+    if (c->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "cache belongs to another model");
+    Guide *old = nullptr;
+    if (!g) {                                                         // removal: the buffers stay (freed with the cache), the old graphs run again
+        std::lock_guard<std::mutex> lock(m->mu);
+        old = c->guide;
+        c->guide = nullptr;
+    } else {
+        if (g->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "the guide belongs to another model");
+        if (state >= g->n_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "state %u is not below the guide's n_states %u", state, g->n_states);
+        if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "guided decoding does not run under tensor parallelism (tp_size %d)", m->tp);
+        std::lock_guard<std::mutex> lock(m->mu);
+        Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+        FL_HIP(hipSetDevice(sh.device));
+        if (!cs.guide_ctl) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.guide_ctl, sizeof(GuideCtl), nullptr));
+        if (!cs.logits_guided) FL_TRY(dev_alloc(cs.allocs, (void **)&cs.logits_guided, (size_t)m->D.V * 4, nullptr));
+        if (c->guide != g) { old = c->guide; g->refs.fetch_add(1); c->guide = g; }
+        c->guide_state = state;
+    }
+    if (old) guide_release(old);                                      // (outside the lock: the last reference frees under it)
+    return FL_OK;
+}
+
+int cache_guide_state(const Cache *c, uint32_t *state_out) {
+    if (!c || !state_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_guide_state: null argument");
+    if (!c->guide) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_guide_state: the cache has no guide installed");
+    *state_out = c->guide_state;
+    return FL_OK;
+}
+
+int set_guide_ctl(Model *m, Cache *c) {
+    Shard &sh = m->shards[0]; CacheShard &cs = c->shards[0];
+    const Guide *g = c->guide;
+    Launcher L = make_launcher(m, sh);
+    return launch_set_guide_ctl(L, cs.guide_ctl, GuideCtl{g->row_ptr_dev, g->tokens_dev, g->next_dev, cs.logits_guided, {c->guide_state, c->guide_state}});
 }
 
 // ---- token log-probabilities (fl_*_lp)
@@ -858,8 +1003,8 @@ int replay_or_capture(const std::vector<GraphSlot> &slots, bool graphable, bool 
 // Single-shard models replay it as a hipGraph (the ~11 launches per layer are launch-bound at
 // TinyLlama scale); captured lazily on the second step of a cache so that all lazy module /
 // attribute initialisation has already happened eagerly.
-// kind (kStepLp | kStepRules): the step with the log-prob launch behind token selection and / or the logit-rules launch in front of
-// it -- a graph of its own per kind; graph[0] is what it always was, and a cache may alternate between the kinds of call.
+// kind (kStepLp | kStepRules | kStepGuide): the step with the log-prob launch behind token selection and / or the logit-rules and
+// guide launches in front of it -- a graph of its own per kind; graph[0] is what it always was, and a cache may alternate between the kinds of call.
 static int decode_step(Model *m, Cache *c, int64_t len_hint, int kind = 0) {
     // Graphs: one shard per process (plain single GPU, or one rank of a multi-process TP group: RCCL collectives are
     // stream-ordered and capturable, every rank captures the same sequence); or all shards of a single-process group
@@ -875,7 +1020,7 @@ static int decode_step(Model *m, Cache *c, int64_t len_hint, int kind = 0) {
         slots.push_back({m->shards[i].device, m->shards[i].stream, &c->shards[i].graph[kind]});
     return replay_or_capture(slots, graphable, c->graph_failed, c->warm_steps[kind], [&]() -> int {
         FL_TRY(enqueue_forward(m, c, false, 1, false, len_hint));
-        FL_TRY(enqueue_argmax(m, c, 1, (kind & kStepRules) != 0));
+        FL_TRY(enqueue_argmax(m, c, 1, (kind & kStepRules) != 0, (kind & kStepGuide) != 0));
         return (kind & kStepLp) ? enqueue_logprobs(m, c, 1) : FL_OK;
     });
 }
@@ -907,7 +1052,9 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
     if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
     const bool rules = c->rules_on;                  // (a forward's ids are prompt: the rules are applied, nothing is counted)
     if (rules) FL_TRY(set_logit_rules_ctl(m, c, false));
-    const int kind = (lp ? kStepLp : 0) | (rules ? kStepRules : 0);
+    const bool guide = c->guide && token_out;        // (fl_forward selects nothing: it runs the step without the guide launch)
+    if (guide) FL_TRY(set_guide_ctl(m, c));
+    const int kind = (lp ? kStepLp : 0) | (rules ? kStepRules : 0) | (guide ? kStepGuide : 0);
     if (T == 1) {
         FL_TRY(set_state(m, c, ids[0], pos, c->len, 0, -1, (size_t)-1, &sampler));
         FL_TRY(decode_step(m, c, (int64_t)c->len, kind));
@@ -934,7 +1081,7 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
             c->len += (size_t)Tc;
             done += (size_t)Tc;
         }
-        FL_TRY(enqueue_argmax(m, c, 0, rules));
+        FL_TRY(enqueue_argmax(m, c, 0, rules, guide));
         if (lp) FL_TRY(enqueue_logprobs(m, c, 0));
     }
     Shard &s0 = m->shards[0];
@@ -943,6 +1090,7 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
     FL_TRY(finish_call(m, c, token_out ? 1 : 0, lp ? 1 : 0));
     if (logits_out) memcpy(logits_out, m->host_logits, (size_t)m->D.V * 4);
     if (token_out) *token_out = m->host_tokens[0];
+    if (guide) c->guide_state = c->guide->walk(c->guide_state, m->host_tokens[0]);
     if (lp) scatter_logprobs(m->host_lp[0], lp, 0);
     return FL_OK;
 }
@@ -960,7 +1108,8 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
     std::lock_guard<std::mutex> lock(m->mu);
     if (lp) { FL_TRY(ensure_logprobs(m, c)); FL_TRY(set_logprobs(m, c, lp)); }
     if (c->rules_on) FL_TRY(set_logit_rules_ctl(m, c, true));      // every step's input token is one more output
-    const int kind = (lp ? kStepLp : 0) | (c->rules_on ? kStepRules : 0);
+    const Guide *guide = c->guide;
+    const int kind = (lp ? kStepLp : 0) | (c->rules_on ? kStepRules : 0) | (guide ? kStepGuide : 0);
     size_t done = 0;
     uint32_t tok = first;
     // With an EOS id the host looks at the tokens between chunks of 16, 32, ... 256 steps: the reference's loop breaks at
@@ -971,10 +1120,12 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
         const size_t nb = std::min(n_steps - done, chunk);
         if (eos >= 0) chunk = std::min<size_t>(chunk * 2, 256);
         FL_TRY(set_state(m, c, tok, pos + done, c->len, 0, eos, (size_t)-1, done == 0 ? &sampler : nullptr));
+        if (guide) FL_TRY(set_guide_ctl(m, c));                     // the host's state: the device advances it inside the chunk
         for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i), kind));
         FL_TRY(finish_call(m, c, nb, lp ? nb : 0));
         for (size_t i = 0; i < nb; i++) {
             const uint32_t t = m->host_tokens[i];
+            if (guide) c->guide_state = guide->walk(c->guide_state, t);      // (the EOS's edge too; what ran behind it is discarded)
             if (eos >= 0 && (int64_t)t == eos) {
                 // the forward that produced EOS was needed; what ran after it is discarded
                 c->len += i + 1;
@@ -1096,6 +1247,7 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
     if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null tokens_out or n_out");
     if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null draft");
     FL_TRY(refuse_logit_rules(c, "fl_forward_verify"));
+    FL_TRY(refuse_guide(c, "fl_forward_verify"));
     FL_TRY(check_verify(m, c, n_draft, pos));
     FL_TRY(check_token(m, token, "token"));
     for (size_t i = 0; i < n_draft; i++) FL_TRY(check_token(m, draft[i], "draft"));
@@ -1121,6 +1273,7 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
     if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null n_out");
     if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null corpus");
     FL_TRY(refuse_logit_rules(c, "fl_decode_lookup"));
+    FL_TRY(refuse_guide(c, "fl_decode_lookup"));
     if (n_steps == 0) return FL_OK;
     if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null tokens_out");
     FL_TRY(check_call(m, c, n_steps, pos));

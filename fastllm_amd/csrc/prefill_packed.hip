@@ -67,6 +67,7 @@ int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids,
         if (!caches[i] || caches[i]->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "cache %zu is null or belongs to another model", i);
         for (size_t j = 0; j < i; j++) if (caches[j] == caches[i]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "cache %zu appears twice in the call", i);
         if (tokens_out) FL_TRY(refuse_logit_rules(caches[i], "fl_batch_prefill with tokens_out"));   // (its selection reads the raw rows)
+        if (tokens_out) FL_TRY(refuse_guide(caches[i], "fl_batch_prefill with tokens_out"));
     }
     const size_t T_total = offsets[n];
     for (size_t r = 0; r < T_total; r++) FL_TRY(check_token(m, ids[r], "token"));

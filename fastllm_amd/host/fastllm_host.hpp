@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/fastllm_mi355x.h"
+#include "guide_compile.hpp"
 
 namespace fastllm {
 
@@ -637,6 +638,41 @@ struct LogitRules {
     static void remove(fl_model *m, fl_cache *c) { check(fl_cache_set_logit_rules(m, c, nullptr, nullptr, 0, nullptr, 0), "fl_cache_set_logit_rules"); }
 };
 
+// Guided decoding (fl_guide): a token-level automaton -- what compile_guide (guide_compile.hpp) makes of a grammar compiler's byte
+// DFA, or any index over token ids -- on the device, shared by every request that uses the same response format.  New capability; the
+// reference has none.  The handle is reference-counted: copies share one fl_guide, and a cache that has it installed keeps it alive.
+class Guide {
+  public:
+    Guide() = default;
+    Guide(fl_model *m, const std::vector<uint64_t> &row_ptr, const std::vector<uint32_t> &tokens, const std::vector<uint32_t> &next) {
+        if (row_ptr.empty() || tokens.size() != next.size() || row_ptr.back() != tokens.size())
+            throw Error(FL_ERR_BAD_ARGUMENT, "Guide: row_ptr, tokens and next do not describe one CSR");
+        fl_guide_desc d{};
+        d.struct_size = (uint32_t)sizeof(fl_guide_desc);
+        d.n_states = (uint32_t)(row_ptr.size() - 1);
+        d.row_ptr = row_ptr.data(); d.tokens = tokens.data(); d.next = next.data();
+        fl_guide *g = nullptr;
+        check(fl_guide_create(m, &d, &g), "fl_guide_create");
+        g_ = std::shared_ptr<fl_guide>(g, [](fl_guide *x) { fl_guide_destroy(x); });
+    }
+    Guide(fl_model *m, const GuideTable &t) : Guide(m, t.row_ptr, t.tokens, t.next) {}
+    fl_guide *raw() const { return g_.get(); }
+    explicit operator bool() const { return (bool)g_; }
+
+  private:
+    std::shared_ptr<fl_guide> g_;
+};
+// A request's guide and the state its first token is selected in (GuideTable::start_state).
+struct GuideOptions {
+    Guide guide;
+    uint32_t start_state = 0;
+    void install(fl_model *m, fl_cache *c) const {
+        if (!guide) throw Error(FL_ERR_BAD_ARGUMENT, "GuideOptions: no guide");
+        check(fl_cache_set_guide(m, c, guide.raw(), start_state), "fl_cache_set_guide");
+    }
+    static void remove(fl_model *m, fl_cache *c) { check(fl_cache_set_guide(m, c, nullptr, 0), "fl_cache_set_guide"); }
+};
+
 // Prompt-lookup drafting for greedy requests (fl_lookup): the continuation that followed the most recent earlier occurrence of the
 // current n-gram is verified in one forward (fl_forward_verify).  New capability; the tokens are those of the plain greedy loop.
 struct LookupOptions {
@@ -749,6 +785,17 @@ struct Model {                                // mod.rs:342-361
     // every token it is fed.  Token selection stays on the device throughout.  `forwards` as in the log-prob overload.
     std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
                                        std::optional<uint32_t> eos, const SamplingOptions &opt, const LogitRules &rules) {
+        return generate_ids(prompt, max_tokens, temperature, eos, opt, &rules, nullptr);
+    }
+    // ... with a guide (and optionally rules beside it: rules first, mask last): installed on the fresh cache at its start state, so
+    // the first token is already selected among the ids the automaton allows; the library advances the state with every token.
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, const GuideOptions &guide,
+                                       const LogitRules *rules = nullptr) {
+        return generate_ids(prompt, max_tokens, temperature, eos, opt, rules, &guide);
+    }
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, const LogitRules *rules, const GuideOptions *guide) {
         cache = M::initialize_cache(device, dtype);
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         forwards = 0;
@@ -757,7 +804,8 @@ struct Model {                                // mod.rs:342-361
         output_ids.assign(max_tokens, 0);
         model.prepare(cache);
         fl_cache *c = model.raw_cache(cache);
-        rules.install(model.raw_model(), c, prompt);
+        if (rules) rules->install(model.raw_model(), c, prompt);
+        if (guide) guide->install(model.raw_model(), c);
         const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
         check(fl_forward_sample_ex(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0]),
               "Model forward pass failed");
@@ -861,6 +909,37 @@ struct Model {                                // mod.rs:342-361
     // (mod.rs:323-325); `on_token` returning false is the dropped receiver (`tx.send(..).is_err()` -> break).  EOS stops the
     // stream before the token is emitted (mod.rs:312-316).  Returns the number of forwards executed (the one behind the last
     // emitted token included, as in the reference's loop).
+    // ... a guided stream (and optionally rules beside the guide): the stream's own cache carries them, every token is selected on the
+    // device (fl_forward_sample_ex, one call per token, the draw position passed along) and handed to `on_token` before the next
+    // forward.  The ids are those of generate_ids with the same options.  Returns the forwards executed.
+    template <class OnToken>
+    size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos,
+                               const SamplingOptions &opt, const GuideOptions &guide, const LogitRules *rules, OnToken &&on_token) const {
+        M shared = model;
+        typename M::Cache own = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        shared.prepare(own);
+        fl_cache *c = shared.raw_cache(own);
+        if (rules) rules->install(shared.raw_model(), c, prompt);
+        guide.install(shared.raw_model(), c);
+        size_t pos = 0, n_forwards = 0;
+        std::vector<uint32_t> input = prompt, output;
+        for (size_t i = 0; i < max_tokens; i++) {
+            const fl_sampler sp = opt.to_ffi((double)temperature, i);
+            uint32_t next = 0;
+            // (rules count decode inputs only: the stream re-installs them with the outputs so far, as a resumed request does)
+            if (rules && i > 0) rules->install(shared.raw_model(), c, prompt, output);
+            check(fl_forward_sample_ex(shared.raw_model(), c, input.data(), input.size(), shared.rope_offset(pos, own), &sp, &next), "Model forward pass failed");
+            shared.advance(own, input.size()); n_forwards++;
+            pos += input.size();
+            if (eos && next == *eos) break;
+            if (!on_token(next)) break;
+            output.push_back(next);
+            input.assign(1, next);
+        }
+        return n_forwards;
+    }
+
     template <class OnToken>
     size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
                                std::optional<uint32_t> eos, OnToken &&on_token) const {
@@ -1078,12 +1157,19 @@ class StreamBatcher {
     // are removed before the slot's cache is handed back or its K/V goes into the PrefixStore.
     uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, const SamplingOptions &opt,
                     std::optional<LogitRules> rules, OnToken on_token, OnDone on_done = {}) {
+        return submit(std::move(prompt), max_tokens, temperature, eos, opt, std::move(rules), std::nullopt, std::move(on_token), std::move(on_done));
+    }
+    // ... and its own guide: installed on the slot's cache at admission, with the first token selected under it, and removed when the
+    // slot is released.  Like a ruled request it is admitted with a forward of its own (fl_batch_prefill's selection honours neither).
+    uint64_t submit(std::vector<uint32_t> prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos, const SamplingOptions &opt,
+                    std::optional<LogitRules> rules, std::optional<GuideOptions> guide, OnToken on_token, OnDone on_done = {}) {
+        if (guide && !guide->guide) throw Error(FL_ERR_BAD_ARGUMENT, "GuideOptions: no guide");
         if (opt.top_p && *opt.top_p != *opt.top_p) throw Error(FL_ERR_BAD_ARGUMENT, "top_p is NaN");
         if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
         if (prompt.size() + 1 > cap_) throw Error(FL_ERR_BAD_ARGUMENT, "the prompt does not fit a slot's cache");
         if (!on_token) throw Error(FL_ERR_BAD_ARGUMENT, "null token callback");
         Request r;
-        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos; r.opt = opt; r.rules = std::move(rules);
+        r.id = ++next_id_; r.prompt = std::move(prompt); r.max_tokens = max_tokens; r.temperature = temperature; r.eos = eos; r.opt = opt; r.rules = std::move(rules); r.guide = std::move(guide);
         r.on_token = std::move(on_token); r.on_done = std::move(on_done);
         queue_.push_back(std::move(r));
         return next_id_;
@@ -1151,11 +1237,13 @@ class StreamBatcher {
         uint64_t id = 0; std::vector<uint32_t> prompt; size_t max_tokens = 0; float temperature = 0.f; std::optional<uint32_t> eos;
         SamplingOptions opt;
         std::optional<LogitRules> rules;
+        std::optional<GuideOptions> guide;
         OnToken on_token; OnDone on_done;
     };
     struct Slot {
         fl_cache *cache = nullptr; bool active = false; Request req; size_t pos = 0, calls = 0, emitted = 0; uint32_t tok = 0; uint64_t draws = 0;
         bool ruled = false;                  // the cache has logit rules installed (removed in finish, or by the next admission)
+        bool guided = false;                 // ... a guide
         std::vector<uint32_t> held;          // with a store: the prompt and every token handed to the callback
     };
 
@@ -1168,6 +1256,7 @@ class StreamBatcher {
     // seen, a reused prefix included), so its first token is already selected under them
     void admit_single(Slot &sl, Request r, size_t n) {
         if (r.rules) { r.rules->install(model_->m, sl.cache, r.prompt); sl.ruled = true; }
+        if (r.guide) { r.guide->install(model_->m, sl.cache); sl.guided = true; }
         const fl_sampler sp = r.opt.to_ffi((double)r.temperature, 0);
         uint32_t tok = 0;
         check(fl_forward_sample_ex(model_->m, sl.cache, r.prompt.data() + n, r.prompt.size() - n, n, &sp, &tok), "Model forward pass failed");
@@ -1175,6 +1264,7 @@ class StreamBatcher {
         admit_end(sl, std::move(r), n, tok);
     }
     void drop_rules(Slot &sl) {
+        if (sl.guided) { sl.guided = false; GuideOptions::remove(model_->m, sl.cache); }
         if (!sl.ruled) return;
         sl.ruled = false;
         LogitRules::remove(model_->m, sl.cache);
@@ -1233,7 +1323,7 @@ class StreamBatcher {
                 }
             }
             auto suffix = [](const Pair &p) { return p.r.prompt.size() - p.n; };
-            auto packable = [&](const Pair &p) { return suffix(p) <= max_member && !p.r.rules; };   // (a ruled request takes the single call)
+            auto packable = [&](const Pair &p) { return suffix(p) <= max_member && !p.r.rules && !p.r.guide; };   // (a ruled or guided request takes the single call)
             std::stable_partition(pairs.begin(), pairs.end(), packable);   // the packable pairs first, in slot order
             size_t n_packable = 0;
             while (n_packable < pairs.size() && packable(pairs[n_packable])) n_packable++;

@@ -366,6 +366,60 @@ int flh_batcher_submit_rules(void *bv, const uint32_t *prompt, size_t T, size_t 
         return 0;
     });
 }
+// ... a guided request (generate_ids with GuideOptions; stream != 0: generate_stream_ids' guided overload): the automaton as the CSR
+// arrays of fl_guide_desc, start_state the state of the first token; top_p <= 0 and top_k <= 0: off
+int flh_generate_guide(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, double top_p,
+                       int64_t top_k, uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next,
+                       uint32_t start_state, int stream, uint32_t *out_tokens, size_t *n_out) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        if (!h || !row_ptr || !tokens || !next || !out_tokens || !n_out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        std::vector<uint32_t> p(prompt, prompt + T), r;
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        SamplingOptions opt;
+        if (top_p > 0) opt.top_p = top_p;
+        if (top_k > 0) opt.top_k = (size_t)top_k;
+        const size_t nnz = (size_t)row_ptr[n_states];
+        GuideOptions g;
+        g.guide = Guide(model_of(h)->m, std::vector<uint64_t>(row_ptr, row_ptr + n_states + 1), std::vector<uint32_t>(tokens, tokens + nnz),
+                        std::vector<uint32_t>(next, next + nnz));
+        g.start_state = start_state;
+        if (stream) {
+            auto on = [&](uint32_t t) { r.push_back(t); return true; };
+            if (h->llama) h->llama->generate_stream_ids(p, max_tokens, temperature, e, opt, g, nullptr, on);
+            else if (h->mistral) h->mistral->generate_stream_ids(p, max_tokens, temperature, e, opt, g, nullptr, on);
+            else h->qwen->generate_stream_ids(p, max_tokens, temperature, e, opt, g, nullptr, on);
+        } else if (h->llama) r = h->llama->generate_ids(p, max_tokens, temperature, e, opt, g);
+        else if (h->mistral) r = h->mistral->generate_ids(p, max_tokens, temperature, e, opt, g);
+        else r = h->qwen->generate_ids(p, max_tokens, temperature, e, opt, g);
+        for (size_t i = 0; i < r.size(); i++) out_tokens[i] = r[i];
+        *n_out = r.size();
+        return 0;
+    });
+}
+// ... a request with a guide of its own (StreamBatcher::submit with GuideOptions); hv: the model the batcher was made for
+int flh_batcher_submit_guide(void *bv, void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
+                             uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,
+                             int (*on_token)(uint64_t id, uint32_t token, void *user), void (*on_done)(uint64_t id, size_t n_tokens, void *user),
+                             void *user, uint64_t *id_out) {
+    return guard([&] {
+        if (!bv || !hv || !on_token || (!prompt && T) || !row_ptr || !tokens || !next) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto *bh = static_cast<BatcherHandle *>(bv);
+        auto id = std::make_shared<uint64_t>(0);
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        const size_t nnz = (size_t)row_ptr[n_states];
+        GuideOptions g;
+        g.guide = Guide(model_of(static_cast<Handle *>(hv))->m, std::vector<uint64_t>(row_ptr, row_ptr + n_states + 1),
+                        std::vector<uint32_t>(tokens, tokens + nnz), std::vector<uint32_t>(next, next + nnz));
+        g.start_state = start_state;
+        StreamBatcher::OnDone done;
+        if (on_done) done = [=](size_t n) { on_done(*id, n, user); };
+        *id = bh->b->submit(std::vector<uint32_t>(prompt, prompt + T), max_tokens, temperature, e, SamplingOptions{}, std::nullopt, g,
+                            [=](uint32_t t) { return on_token(*id, t, user) != 0; }, done);
+        if (id_out) *id_out = *id;
+        return 0;
+    });
+}
 int flh_batcher_run(void *bv, size_t *batch_steps, size_t *prefills) {
     return guard([&] {
         if (!bv) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");

@@ -488,6 +488,57 @@ int fl_cache_set_logit_rules(fl_model *m, fl_cache *c, const fl_logit_rules *rul
 /* The table words [V] (bit 31: prompt, bits 0..30: output count) once the stream is idle.  FL_ERR_BAD_ARGUMENT: no rules installed. */
 int fl_cache_logit_counts(fl_model *m, fl_cache *c, uint32_t *words_out);
 
+/* ---- guided decoding: a token-level automaton inside the device decode loop ---------------------------------------------------------
+ * New capability (the reference has none).  What an OpenAI-compatible server is asked for as `response_format` (JSON mode, JSON
+ * schema), strict tool calls, regex or choice constraints: requests whose allowed tokens depend on what has been produced so far.
+ * The library takes the constraint in the form the open-source servers hand to their GPUs, a finite automaton over token ids
+ * (Outlines' index, vLLM's guided decoding); it needs no tokenizer and no grammar (fastllm_host.hpp has compile_guide, from a
+ * byte-level DFA and a vocabulary).  An fl_guide is immutable, belongs to one model and may be installed in any number of its caches.
+ *
+ * The automaton is CSR: state s allows the ids tokens[row_ptr[s] .. row_ptr[s + 1]), and tokens[e] leads to state next[e].
+ * While a guide is installed in a cache at state s, every call that selects a token on that cache selects from y:
+ *     y[j] = x[j]   bit for bit, if j is in the list of s
+ *     y[j] = -inf   otherwise
+ * where x is the row the selection would otherwise have read: the raw fp32 logits, or the rule-adjusted row when logit rules are
+ * installed too (rules first, mask last: a positive bias does not bring a disallowed id back).  The selected token t moves the cache
+ * to next(s, t); a t without an edge (possible only for a row with NaN) leaves the state where it is.  One more launch between lm_head
+ * and token selection inside the same replayed graph does both, the advance from the step's input token; a cache without a guide runs
+ * exactly what it ran before.  The state of a guided cache is the state in which the NEXT selected token is looked up.
+ * The host is authoritative for the state, as it is for the cached length: the library writes it to the device at the start of every
+ * call and of every chunk of a decode call, the device advances it inside a chunk, and the host walks the tokens that came back (the
+ * emitted ones, and the EOS if one ended the call) through its own copy.  Steps that ran behind an EOS are discarded for the state as
+ * they are for the length.  fl_cache_truncate, fl_cache_reset and fl_cache_copy_prefix touch neither the guide nor the state: a
+ * caller that rolls a request back sets the state again (fl_cache_set_guide with the same guide).
+ * Honoured by fl_forward_argmax, fl_forward_sample{,_ex,_lp}, fl_decode_greedy, fl_decode_sample{,_ex,_lp}, fl_batch_decode,
+ * fl_batch_decode_each{,_ex,_lp}.  Log-probs (fl_*_lp) keep reporting the model's own distribution from the raw row; fl_forward /
+ * fl_batch_forward logits stay raw, and fl_forward (which selects nothing) leaves the state alone.
+ * FL_ERR_UNSUPPORTED, before the device or any cache is touched: fl_guide_create and fl_cache_set_guide on a model with tp_size > 1
+ * (any mode, so no member of a tensor-parallel batch can be guided); a guided cache in fl_forward_verify, fl_decode_lookup,
+ * fl_batch_prefill with tokens_out, fl_batch_forward with argmax_out.
+ * FL_ERR_BAD_ARGUMENT from fl_guide_create, before the device is probed: wrong struct_size, nonzero _reserved, n_states == 0, a null
+ * array, row_ptr not starting at 0 or decreasing, a state without an edge (it would make every logit -inf), tokens not strictly
+ * ascending within a state, an id >= V, a next >= n_states.  Creation validates all of that so that the kernel need not.
+ * Memory: 8 bytes per edge + 8 per state, once in HBM and once on the host, per guide (an automaton over V = 152 064 with a few hundred
+ * dense states is hundreds of MB: the known cost of this representation); per guided cache V x 4 bytes + a control block, per batch
+ * with a guided member B x V x 4 bytes. */
+typedef struct fl_guide fl_guide;
+typedef struct fl_guide_desc {
+    uint32_t        struct_size;          /* sizeof(fl_guide_desc), FL_ERR_BAD_ARGUMENT otherwise */
+    uint32_t        n_states;             /* >= 1 */
+    const uint64_t *row_ptr;              /* [n_states + 1] row_ptr[0] == 0, non-decreasing; nnz = row_ptr[n_states] */
+    const uint32_t *tokens;               /* [nnz] strictly ascending within a state, < V */
+    const uint32_t *next;                 /* [nnz] < n_states */
+    int64_t         _reserved[2];         /* 0 */
+} fl_guide_desc;
+int  fl_guide_create(fl_model *m, const fl_guide_desc *desc, fl_guide **out);
+/* Drops the creator's reference; a cache that has the guide installed holds one of its own and keeps working. */
+void fl_guide_destroy(fl_guide *g);
+/* Installs g at `state` (< n_states, FL_ERR_BAD_ARGUMENT otherwise), replacing whatever was installed; g NULL: removes the guide
+ * (state is ignored; the cache runs its old graphs again). */
+int  fl_cache_set_guide(fl_model *m, fl_cache *c, fl_guide *g, uint32_t state);
+/* The state in which the next selected token is looked up.  FL_ERR_BAD_ARGUMENT: no guide installed. */
+int  fl_cache_guide_state(const fl_cache *c, uint32_t *state_out);
+
 int fl_synchronize(fl_model *m);
 
 /* ---- embeddings: the BERT / MiniLM encoder forward --------------------------------------------------------------------------------
@@ -635,6 +686,16 @@ int fl_op_logprobs(const float *logits /* [T][V] */, int64_t T, int64_t V, const
 int fl_op_logit_rules(const float *logits /* [B][V] */, int64_t B, int64_t V, uint32_t *words /* [B][V] */, const float *biases /* [B][V] */,
                       const float *scalars /* [B][3] */, const uint32_t *tokens /* [B] */, int32_t count_input,
                       const uint8_t *has_rules /* [B] or NULL */, float *out /* [B][V] */);
+
+/* The guided-decoding kernel alone, on host arrays (unit tests): the batch form on B rows of V logits and one automaton (the CSR
+ * arrays of fl_guide_desc, validated as fl_guide_create validates them against this V).  Row b enters in states[b] (< n_states), first
+ * moves along the edge of tokens[b] as a decode step moves along its input token (no such edge, or an id >= V: it stays), and is masked
+ * in the state it reached, which comes back in next_states[b].  has_guide (optional, [B]): 0 makes row b's control block null, and the
+ * row is copied through (next_states[b] = states[b]).  1 <= B <= 64, 1 <= V <= 1 << 24, FL_ERR_BAD_ARGUMENT otherwise (before the
+ * device is probed).  Launched twice: FL_ERR_HIP if the two results differ. */
+int fl_op_guide_mask(const float *logits /* [B][V] */, int64_t B, int64_t V, const fl_guide_desc *desc, const uint32_t *states /* [B] */,
+                     const uint32_t *tokens /* [B] */, const uint8_t *has_guide /* [B] or NULL */, float *out /* [B][V] */,
+                     uint32_t *next_states /* [B] */);
 
 /* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
  * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read

@@ -170,6 +170,19 @@ pub struct fl_logit_rules {
     pub _reserved: [i64; 2],
 }
 
+/// `fl_guide_desc`: a token-level automaton in CSR form (fl_guide_create); `struct_size` is `size_of::<fl_guide_desc>()`.  State `s`
+/// allows `tokens[row_ptr[s] .. row_ptr[s + 1]]` (strictly ascending, below the vocabulary), and `tokens[e]` leads to `next[e]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_guide_desc {
+    pub struct_size: u32,
+    pub n_states: u32,
+    pub row_ptr: *const u64,
+    pub tokens: *const u32,
+    pub next: *const u32,
+    pub _reserved: [i64; 2],
+}
+
 /// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -232,6 +245,10 @@ pub struct fl_cache {
 }
 #[repr(C)]
 pub struct fl_batch {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct fl_guide {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -476,6 +493,21 @@ extern "C" {
         count_input: i32,
         has_rules: *const u8,
         out: *mut f32,
+    ) -> c_int;
+    pub fn fl_guide_create(m: *mut fl_model, desc: *const fl_guide_desc, out: *mut *mut fl_guide) -> c_int;
+    pub fn fl_guide_destroy(g: *mut fl_guide);
+    pub fn fl_cache_set_guide(m: *mut fl_model, c: *mut fl_cache, g: *mut fl_guide, state: u32) -> c_int;
+    pub fn fl_cache_guide_state(c: *const fl_cache, state_out: *mut u32) -> c_int;
+    pub fn fl_op_guide_mask(
+        logits: *const f32,
+        b: i64,
+        v: i64,
+        desc: *const fl_guide_desc,
+        states: *const u32,
+        tokens: *const u32,
+        has_guide: *const u8,
+        out: *mut f32,
+        next_states: *mut u32,
     ) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;

@@ -165,6 +165,46 @@ impl Default for LogitRules {
     }
 }
 
+/// `fl_guide`: an immutable token-level automaton of one model -- what a grammar, JSON-schema or regex compiler emits as an index
+/// over token ids.  State `s` allows `tokens[row_ptr[s] .. row_ptr[s + 1]]` (strictly ascending), and `tokens[e]` leads to state
+/// `next[e]`.  Shareable by any number of the model's caches ([`Cache::set_guide`]); a cache that has it installed keeps it alive.
+pub struct Guide {
+    raw: *mut ffi::fl_guide,
+    n_states: u32,
+}
+// SAFETY: immutable after creation and reference-counted inside the library
+unsafe impl Send for Guide {}
+unsafe impl Sync for Guide {}
+impl Drop for Guide {
+    fn drop(&mut self) {
+        unsafe { ffi::fl_guide_destroy(self.raw) };
+    }
+}
+impl Guide {
+    /// `fl_guide_create`.  Errors (`FL_ERR_BAD_ARGUMENT`, before the device is probed): a state without an edge, a list that is not
+    /// strictly ascending, an id beyond the vocabulary, a `next` beyond the states, a `row_ptr` that does not start at 0 or decreases;
+    /// `FL_ERR_UNSUPPORTED`: a tensor-parallel model.
+    pub fn new(model: &Model, row_ptr: &[u64], tokens: &[u32], next: &[u32]) -> Result<Guide> {
+        if row_ptr.is_empty() || tokens.len() != next.len() || row_ptr[row_ptr.len() - 1] != tokens.len() as u64 {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: "guide: row_ptr, tokens and next do not describe one CSR".to_string() });
+        }
+        let d = ffi::fl_guide_desc {
+            struct_size: std::mem::size_of::<ffi::fl_guide_desc>() as u32,
+            n_states: (row_ptr.len() - 1) as u32,
+            row_ptr: row_ptr.as_ptr(),
+            tokens: tokens.as_ptr(),
+            next: next.as_ptr(),
+            _reserved: [0; 2],
+        };
+        let mut raw = ptr::null_mut();
+        check(unsafe { ffi::fl_guide_create(model.raw, &d, &mut raw) })?;
+        Ok(Guide { raw, n_states: d.n_states })
+    }
+    pub fn n_states(&self) -> u32 {
+        self.n_states
+    }
+}
+
 /// The token-selection kernel alone (`fl_op_sample_ex`): `n_draws` successive draws from one logits vector; returns the
 /// tokens and how many tokens each draw kept.
 pub fn op_sample(logits: &[f32], s: Sampler, n_draws: usize) -> Result<(Vec<u32>, Vec<i64>)> {
@@ -519,6 +559,23 @@ impl Cache {
     /// Removes the rules: the cache runs exactly what it ran before they were installed.
     pub fn clear_logit_rules(&mut self, model: &Model) -> Result<()> {
         check(unsafe { ffi::fl_cache_set_logit_rules(model.raw, self.raw, ptr::null(), ptr::null(), 0, ptr::null(), 0) })
+    }
+    /// `fl_cache_set_guide`: from now on every call that selects a token for this cache selects among the ids the automaton allows in
+    /// its current state -- masked on the device, inside the replayed decode step -- and moves along the selected token's edge.
+    /// `state` is the state in which the next selected token is looked up.  `truncate`, `reset` and `copy_prefix_from` leave guide and
+    /// state alone: after a rollback set the state again.  `FL_ERR_UNSUPPORTED`: a tensor-parallel model.
+    pub fn set_guide(&mut self, model: &Model, guide: &Guide, state: u32) -> Result<()> {
+        check(unsafe { ffi::fl_cache_set_guide(model.raw, self.raw, guide.raw, state) })
+    }
+    /// Removes the guide: the cache runs exactly what it ran before one was installed.
+    pub fn clear_guide(&mut self, model: &Model) -> Result<()> {
+        check(unsafe { ffi::fl_cache_set_guide(model.raw, self.raw, ptr::null_mut(), 0) })
+    }
+    /// `fl_cache_guide_state`.
+    pub fn guide_state(&self) -> Result<u32> {
+        let mut s = 0u32;
+        check(unsafe { ffi::fl_cache_guide_state(self.raw as *const ffi::fl_cache, &mut s) })?;
+        Ok(s)
     }
     pub fn len(&self) -> usize {
         unsafe { ffi::fl_cache_len(self.raw) }
