@@ -260,6 +260,11 @@ def lib():
         L.fl_decode_lookup.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), vp, C.POINTER(sz),
                                        C.POINTER(FlSpecStats)]
         L.fl_op_verify_select.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
+        L.fl_forward_verify_ex.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, C.POINTER(FlSampler), vp, C.POINTER(sz), vp]
+        L.fl_decode_lookup_ex.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), C.POINTER(FlSampler), vp,
+                                          C.POINTER(sz), C.POINTER(FlSpecStats)]
+        L.fl_op_verify_sample.argtypes = [vp, C.c_int64, C.c_int64, vp, C.POINTER(FlSampler), vp, C.POINTER(C.c_int64), vp]
+        L.fl_op_verify_sample_time.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(FlSampler), vp, vp]
         L.fl_cache_copy_prefix.argtypes = [vp, vp, sz]
         L.fl_op_kv_copy.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
         L.fl_encoder_create.argtypes = [C.POINTER(FlEncoderConfig), C.POINTER(FlTensor), sz, C.c_int32, C.c_int32, C.POINTER(vp)]
@@ -312,6 +317,34 @@ def op_verify_select(logits, draft):
     n = C.c_int64(-1)
     _check(lib().fl_op_verify_select(a.ctypes.data, T, V, d.ctypes.data if d.size else None, out.ctypes.data, C.byref(n)))
     return out, n.value
+
+
+def op_verify_sample(logits, draft, temperature, seed=0, draws_done=0, top_p=None, top_k=None, return_kept=False):
+    """The sampled verify step's selection kernel alone: logits [T, V] float32, draft [T-1] -> (tokens uint32 [T], n_accepted); row i
+    is drawn with word draws_done + i.  return_kept: also how many tokens each row's filter kept (int64 [T])."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    d = np.ascontiguousarray(draft, dtype=np.uint32)
+    assert d.shape == (T - 1,)
+    out = np.zeros(T, dtype=np.uint32)
+    kept = np.zeros(T, dtype=np.int64)
+    n = C.c_int64(-1)
+    sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+    _check(lib().fl_op_verify_sample(a.ctypes.data, T, V, d.ctypes.data if d.size else None, C.byref(sp), out.ctypes.data, C.byref(n),
+                                     kept.ctypes.data if return_kept else None))
+    return (out, n.value, kept) if return_kept else (out, n.value)
+
+
+def op_verify_sample_time(logits, temperature, iters, seed=0, top_p=None, top_k=None):
+    """(ms per verify_sample launch on the T rows, ms per T one-row select_advance launches of the same rows), event-bracketed;
+    iters = (repetitions of the first form, of the second), 0 skips a form."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    ms = (C.c_double * 2)()
+    sp = make_sampler(temperature, seed, 0, top_p, top_k)
+    it = (C.c_int32 * 2)(int(iters[0]), int(iters[1]))
+    _check(lib().fl_op_verify_sample_time(a.ctypes.data, T, V, C.byref(sp), it, ms))
+    return ms[0], ms[1]
 
 
 def op_logprobs(logits, chosen, top_n):
@@ -563,27 +596,40 @@ class Model:
         _check(lib().fl_decode_greedy(self._h, cache._h, int(first_token), pos, n_steps, eos, toks.ctypes.data, C.byref(n)))
         return toks[: n.value]
 
-    def forward_verify(self, cache, token, draft, pos, want_logits=False):
+    def forward_verify(self, cache, token, draft, pos, want_logits=False, temperature=None, top_p=None, top_k=None, seed=0, draws_done=0):
         """fl_forward_verify: one forward of [token, *draft]; returns (tokens, logits [len(draft) + 1, V] or None) -- the accepted
-        drafts followed by the model's own next token."""
+        drafts followed by the model's own next token.  With a temperature (fl_forward_verify_ex): row i is DRAWN with word
+        draws_done + i of the seeded stream; the request has consumed len(tokens) words afterwards."""
         d = np.ascontiguousarray(draft, dtype=np.uint32)
         toks = np.zeros(d.size + 1, dtype=np.uint32)
         lg = np.empty((d.size + 1, self.V), dtype=np.float32) if want_logits else None
         n = C.c_size_t(0)
+        if temperature is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            _check(lib().fl_forward_verify_ex(self._h, cache._h, int(token), d.ctypes.data if d.size else None, d.size, pos, C.byref(sp),
+                                              toks.ctypes.data, C.byref(n), lg.ctypes.data if want_logits else None))
+            return toks[: n.value], lg
         _check(lib().fl_forward_verify(self._h, cache._h, int(token), d.ctypes.data if d.size else None, d.size, pos, toks.ctypes.data,
                                        C.byref(n), lg.ctypes.data if want_logits else None))
         return toks[: n.value], lg
 
-    def decode_lookup(self, cache, corpus, first_token, pos, n_steps, eos=-1, max_draft=7, ngram_max=3, ngram_min=1, return_stats=False):
+    def decode_lookup(self, cache, corpus, first_token, pos, n_steps, eos=-1, max_draft=7, ngram_max=3, ngram_min=1, return_stats=False,
+                      temperature=None, top_p=None, top_k=None, seed=0, draws_done=0):
         """fl_decode_lookup: the greedy loop built from verify steps with prompt-lookup drafts out of corpus ++ [first_token] ++ output.
-        return_stats: also a dict(steps, drafted, accepted)."""
+        return_stats: also a dict(steps, drafted, accepted).  With a temperature (fl_decode_lookup_ex): the loop of decode_sample, token
+        k drawn with word draws_done + k."""
         cp = np.ascontiguousarray(corpus, dtype=np.uint32)
         toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
         n = C.c_size_t(0)
         o = make_lookup(max_draft, ngram_max, ngram_min)
         st = FlSpecStats()
-        _check(lib().fl_decode_lookup(self._h, cache._h, cp.ctypes.data if cp.size else None, cp.size, int(first_token), pos, n_steps, eos,
-                                      C.byref(o), toks.ctypes.data, C.byref(n), C.byref(st)))
+        if temperature is not None:
+            sp = make_sampler(temperature, seed, draws_done, top_p, top_k)
+            _check(lib().fl_decode_lookup_ex(self._h, cache._h, cp.ctypes.data if cp.size else None, cp.size, int(first_token), pos, n_steps,
+                                             eos, C.byref(o), C.byref(sp), toks.ctypes.data, C.byref(n), C.byref(st)))
+        else:
+            _check(lib().fl_decode_lookup(self._h, cache._h, cp.ctypes.data if cp.size else None, cp.size, int(first_token), pos, n_steps, eos,
+                                          C.byref(o), toks.ctypes.data, C.byref(n), C.byref(st)))
         if return_stats:
             return toks[: n.value], dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted)
         return toks[: n.value]

@@ -202,6 +202,20 @@ int fl_decode_lookup(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_
     });
 }
 
+int fl_forward_verify_ex(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, const fl_sampler *sampler,
+                         uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return forward_verify(M(m), C(c), token, draft, n_draft, pos, tokens_out, n_out, logits_out, sampler);
+    });
+}
+
+int fl_decode_lookup_ex(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos, size_t n_steps,
+                        int64_t eos, const fl_lookup *opts, const fl_sampler *sampler, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return guarded([&]() -> int {
+        return decode_lookup(M(m), C(c), corpus, n_corpus, first_token, pos, n_steps, eos, opts, tokens_out, n_out, stats, sampler);
+    });
+}
+
 int fl_forward_argmax(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, uint32_t *token_out) {
     return guarded([&]() -> int {
         if (!token_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null token_out");

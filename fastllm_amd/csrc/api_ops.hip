@@ -153,6 +153,85 @@ int fl_op_verify_select(const float *logits, int64_t T, int64_t V, const uint32_
     });
 }
 
+int fl_op_verify_sample(const float *logits, int64_t T, int64_t V, const uint32_t *draft, const fl_sampler *sampler, uint32_t *tokens_out,
+                        int64_t *n_accepted_out, int64_t *kept_out) {
+    return guarded([&]() -> int {
+        if (!logits || !sampler || !tokens_out || !n_accepted_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || T > kVerifyMaxRows || V <= 0 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size (1 <= T <= %d)", kVerifyMaxRows);
+        if (T > 1 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null draft");
+        SampleState ss;
+        FL_TRY(make_sampler(sampler, V, &ss));
+        if (!ss.on) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_sample: temperature below 1e-7 is ArgMax (fl_op_verify_select)");
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg, *sc; uint32_t *dr, *od, *kd;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.alloc(&sc, (size_t)T * V * 4));
+        FL_TRY(B.alloc(&dr, (size_t)kVerifyMaxRows * 4));
+        FL_TRY(B.alloc(&od, (size_t)kVerifyWords * 4));
+        FL_TRY(B.alloc(&kd, (size_t)kVerifyMaxRows * 4));
+        if (T > 1) FL_HIP(hipMemcpy(dr, draft, (size_t)(T - 1) * 4, hipMemcpyHostToDevice));
+        FL_HIP(hipMemset(od, 0, (size_t)kVerifyWords * 4));
+        uint32_t host[2][kVerifyWords], kept[2][kVerifyMaxRows];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the second launch meets the ticket word the first one put back
+            FL_HIP(hipMemsetAsync(kd, 0, (size_t)kVerifyMaxRows * 4, B.s));
+            FL_TRY(launch_verify_sample(B.L, lg, V, (int)T, dr, ss, sc, od, kd));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep], od, sizeof host[rep], hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(kept[rep], kd, sizeof kept[rep], hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0], host[1], sizeof host[0]) || memcmp(kept[0], kept[1], sizeof kept[0]) || host[1][kVerifyTicket] != 0)
+            FL_FAIL(FL_ERR_HIP, "verify_sample: a repeated launch gave another result (ticket %u)", host[1][kVerifyTicket]);
+        for (int64_t t = 0; t < T; t++) tokens_out[t] = host[0][t];
+        if (kept_out) for (int64_t t = 0; t < T; t++) kept_out[t] = (int64_t)kept[0][t];
+        *n_accepted_out = (int64_t)host[0][kVerifyNacc];
+        return FL_OK;
+    });
+}
+
+int fl_op_verify_sample_time(const float *logits, int64_t T, int64_t V, const fl_sampler *sampler, const int32_t *iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!logits || !sampler || !iters || !ms_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T < 1 || T > kVerifyMaxRows || V <= 0 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad size");
+        for (int f = 0; f < 2; f++) if (iters[f] < 0 || iters[f] > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad iteration count");
+        SampleState ss;
+        FL_TRY(make_sampler(sampler, V, &ss));
+        if (!ss.on) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_sample_time: temperature below 1e-7 is ArgMax");
+        OpScope B;
+        FL_TRY(B.begin());
+        StepState st{}; st.eos = -1;
+        float *lg, *sc; uint32_t *dr, *od; StepState *std_; SampleState *ssd;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.alloc(&sc, (size_t)T * V * 4));
+        FL_TRY(B.alloc(&dr, (size_t)kVerifyMaxRows * 4));
+        FL_TRY(B.alloc(&od, (size_t)kVerifyWords * 4));
+        FL_TRY(B.upload(&std_, &st, sizeof st));
+        FL_TRY(B.upload(&ssd, &ss, sizeof ss));
+        FL_HIP(hipMemset(dr, 0, (size_t)kVerifyMaxRows * 4));
+        FL_HIP(hipMemset(od, 0, (size_t)kVerifyWords * 4));
+        FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+        // form 0: the T rows in one launch; form 1: T one-row selection launches of the same rows (the step state does not advance)
+        for (int form = 0; form < 2; form++) {
+            ms_out[form] = 0.0;
+            if (iters[form] == 0) continue;
+            auto run = [&]() -> int {
+                if (form == 0) return launch_verify_sample(B.L, lg, V, (int)T, dr, ss, sc, od, nullptr);
+                for (int64_t t = 0; t < T; t++) FL_TRY(launch_select_advance(B.L, lg + (size_t)t * V, V, std_, ssd, sc + (size_t)t * V, od, 0));
+                return FL_OK;
+            };
+            FL_TRY(run());                                      // warm
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipEventRecord(B.e0, B.s));
+            for (int i = 0; i < iters[form]; i++) FL_TRY(run());
+            FL_HIP(hipEventRecord(B.e1, B.s));
+            FL_HIP(hipEventSynchronize(B.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+            ms_out[form] = ms / iters[form];
+        }
+        return FL_OK;
+    });
+}
+
 int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *chosen, int32_t top_n, float *token_logprob,
                    uint32_t *top_ids, float *top_logprobs) {
     return guarded([&]() -> int {

@@ -412,6 +412,11 @@ int launch_select_advance(Launcher &L, const float *logits, int64_t V, StepState
 // (the ticket word is put back by the kernel itself)
 constexpr int kVerifyMaxRows = 16, kVerifyNacc = 16, kVerifyTicket = 17, kVerifyWords = 18;
 int launch_verify_select(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft /* [T-1] device */, uint32_t *out);
+// fl_forward_verify_ex's selection: out[t] = the draw of row t -- select_advance's sampler with word (ss.draw_hi:draw_lo) + t of the
+// seeded stream -- and the same acceptance scan, ticket and out block.  ss.on != 0 (ArgMax is launch_verify_select's); scratch:
+// [T][V] floats; kept (device, or null): [T] what the top-p / top-k filter kept per row (V without one).
+int launch_verify_sample(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft /* [T-1] device */, const SampleState &ss,
+                         float *scratch, uint32_t *out, uint32_t *kept);
 // fl_*_lp: log-softmax (temperature 1, no mask) of `rows` logits rows [rows][V], one workgroup per row -- the chosen token's and the
 // first top_n of "logit descending, lower index first" -- into record `step - advance` of the row's LogprobCtl.  Who a row belongs to:
 //   st + ctl      one sequence (rows == 1): the token select_advance just left in st

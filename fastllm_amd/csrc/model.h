@@ -111,6 +111,7 @@ struct Shard {
     float *logits_full = nullptr;    // [V]
     float *verify_logits = nullptr;  // [kVerifyMaxRows][V] all rows' logits of a verify step (fl_forward_verify); allocated at a model's first one
     uint32_t *verify_out = nullptr;  // [kVerifyWords] its ArgMax ids, accepted count and arrival ticket (launch_verify_select)
+    float *verify_scratch = nullptr; // [kVerifyMaxRows][V] the rows' probabilities of a SAMPLED verify step (launch_verify_sample); allocated at a model's first one
     // the persistent decode engine (k_engine.hip): granule edges of one launch and the tag epoch
     unsigned long long *eng_edge[3] = {};   // o_proj deltas [h] | silu(g)*u pairs [Ip/2] | down_proj deltas [h]
     uint32_t *eng_epoch = nullptr;
@@ -343,9 +344,9 @@ int refuse_guide(const Cache *c, const char *what);
 int cache_truncate(Cache *c, size_t len);
 int cache_copy_prefix(Cache *dst, const Cache *src, size_t n);      // fl_cache_copy_prefix (prefix reuse across caches)
 int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
-                   size_t *n_out, float *logits_out);
+                   size_t *n_out, float *logits_out, const fl_sampler *sampling = nullptr);
 int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
+                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling = nullptr);
 int check_lookup(const fl_lookup *opts);     // FL_ERR_BAD_ARGUMENT: null, wrong struct_size, a range error
 
 // most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (weights.hip)

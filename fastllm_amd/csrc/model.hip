@@ -1211,8 +1211,11 @@ static int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos) {
     return FL_OK;
 }
 
-// one verify step with the model locked and the arguments checked; host_verify holds the ids and the accepted count afterwards
-static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, float *logits_out) {
+// one verify step with the model locked and the arguments checked; host_verify holds the ids and the accepted count afterwards.
+// sampler (null or on == 0: ArgMax, the launches there have always been): row i is drawn with word sampler->draw + i, and the host
+// stays authoritative for the draw count as it is for the cache length -- every call brings the state, nothing is left behind.
+static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, float *logits_out,
+                       const SampleState *sampler = nullptr) {
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
     const int64_t T = (int64_t)n_draft + 1;
@@ -1223,6 +1226,8 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
         FL_HIP(hipHostMalloc((void **)&m->host_verify, kVerifyWords * 4, hipHostMallocDefault));
         FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_logits, (size_t)kVerifyMaxRows * D.V * 4, &m->hbm_bytes));
     }
+    const bool sampled = sampler && sampler->on;
+    if (sampled && !sh.verify_scratch) FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_scratch, (size_t)kVerifyMaxRows * D.V * 4, &m->hbm_bytes));
     if (sh.pre.cap_T < T) FL_TRY(grow_prefill_scratch(m, sh, T));
     uint32_t *ids = m->host_tokens;                                  // pinned, and idle until this call's sync
     ids[0] = token;
@@ -1232,7 +1237,8 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     FL_TRY(set_state(m, c, token, pos, c->len, 0, -1, c->len, &argmax));
     FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, sh.verify_logits));
     Launcher L = make_launcher(m, sh);
-    FL_TRY(launch_verify_select(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));
+    if (sampled) FL_TRY(launch_verify_sample(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, *sampler, sh.verify_scratch, sh.verify_out, nullptr));
+    else FL_TRY(launch_verify_select(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));
     FL_HIP(hipMemcpyAsync(m->host_verify, sh.verify_out, (kVerifyNacc + 1) * 4, hipMemcpyDeviceToHost, sh.stream));
     FL_TRY(finish_call(m, c, 0));
     if (m->host_verify[kVerifyNacc] > n_draft) FL_FAIL(FL_ERR_HIP, "verify step: accepted count %u out of range", m->host_verify[kVerifyNacc]);
@@ -1242,8 +1248,10 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
 }
 
 int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
-                   size_t *n_out, float *logits_out) {
+                   size_t *n_out, float *logits_out, const fl_sampler *sampling) {
     if (n_out) *n_out = 0;
+    SampleState sampler;
+    FL_TRY(make_sampler(sampling, 0, &sampler));                     // its argument errors, before the handles are looked at
     if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null tokens_out or n_out");
     if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null draft");
     FL_TRY(refuse_logit_rules(c, "fl_forward_verify"));
@@ -1252,13 +1260,14 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
     FL_TRY(check_token(m, token, "token"));
     for (size_t i = 0; i < n_draft; i++) FL_TRY(check_token(m, draft[i], "draft"));
     if (n_draft == 0) {                                              // the decode step itself: its mask, its kernels
-        FL_TRY(forward(m, c, &token, 1, pos, logits_out, tokens_out));
+        FL_TRY(forward(m, c, &token, 1, pos, logits_out, tokens_out, sampler.on ? sampling : nullptr));
         *n_out = 1;
         return FL_OK;
     }
+    FL_TRY(make_sampler(sampling, m->D.V, &sampler));                // (with the vocabulary: a top_k >= V is off)
     debug_inject("forward");
     std::lock_guard<std::mutex> lock(m->mu);
-    FL_TRY(verify_step(m, c, token, draft, n_draft, pos, logits_out));
+    FL_TRY(verify_step(m, c, token, draft, n_draft, pos, logits_out, &sampler));
     const size_t n = (size_t)m->host_verify[kVerifyNacc] + 1;
     for (size_t i = 0; i < n; i++) tokens_out[i] = m->host_verify[i];
     *n_out = n;
@@ -1266,10 +1275,13 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
 }
 
 int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling) {
     if (n_out) *n_out = 0;
     if (stats) *stats = fl_spec_stats{};
     FL_TRY(check_lookup(opts));
+    SampleState sampler;
+    FL_TRY(make_sampler(sampling, 0, &sampler));                     // its argument errors, before the handles are looked at
+    const bool sampled = sampler.on != 0;                            // false: the greedy loop, launch for launch
     if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null n_out");
     if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null corpus");
     FL_TRY(refuse_logit_rules(c, "fl_decode_lookup"));
@@ -1280,6 +1292,11 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
     FL_TRY(check_token(m, first, "token"));
     if (m->tp > 1 && opts->max_draft > 0) FL_FAIL(FL_ERR_UNSUPPORTED, "the verify step does not run under tensor parallelism (tp_size %d)", m->tp);
     const size_t V = (size_t)m->D.V, L0 = c->len;
+    if (sampled && opts->max_draft == 0) {                           // nothing to verify: the plain sampled loop itself
+        FL_TRY(decode_greedy(m, c, first, pos, n_steps, eos, tokens_out, n_out, sampling));
+        if (stats) stats->steps = c->len - L0;
+        return FL_OK;
+    }
     std::vector<uint32_t> hist;
     hist.reserve(n_corpus + 1 + n_steps + FL_VERIFY_MAX_DRAFT + 1);
     for (size_t i = 0; i < n_corpus; i++) hist.push_back(corpus[i]);
@@ -1296,12 +1313,16 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
         size_t nd = lookup_draft(hist.data(), hist.size(), opts->max_draft, opts->ngram_max, opts->ngram_min, limit, draft);
         for (size_t i = 0; i < nd; i++) if (draft[i] >= V) { nd = i; break; }      // (a corpus id the model does not have ends the draft)
         size_t n = 0;
+        // token k of the request is drawn with word k: this step's row i with word draws_done + emitted + i, whatever was rejected before
+        fl_sampler sp{};
+        if (sampled) { sp = *sampling; sp.draws_done += emitted; }
         if (nd == 0) {
-            FL_TRY(forward(m, c, &tok, 1, pos + emitted, nullptr, got));
+            FL_TRY(forward(m, c, &tok, 1, pos + emitted, nullptr, got, sampled ? &sp : nullptr));
             n = 1;
         } else {
+            if (sampled) FL_TRY(make_sampler(&sp, m->D.V, &sampler));
             std::lock_guard<std::mutex> lock(m->mu);
-            FL_TRY(verify_step(m, c, tok, draft, nd, pos + emitted, nullptr));
+            FL_TRY(verify_step(m, c, tok, draft, nd, pos + emitted, nullptr, &sampler));
             n = (size_t)m->host_verify[kVerifyNacc] + 1;
             for (size_t i = 0; i < n; i++) got[i] = m->host_verify[i];
         }

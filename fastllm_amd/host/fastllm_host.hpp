@@ -902,6 +902,90 @@ struct Model {                                // mod.rs:342-361
         return n_forwards;
     }
 
+    // ... a SAMPLED request decoded with prompt-lookup drafts (fl_decode_lookup_ex): the first token is drawn from the prompt's forward
+    // with word 0 (fl_forward_sample_ex), the other max_tokens - 1 by verify steps whose row i is drawn with word 1 + emitted + i and
+    // accepted while the draws equal the drafts -- the seeded stream of the SamplingOptions overload above, token k with word k (up to
+    // draws that land within the last bits of a boundary, include/fastllm_mi355x.h).  temperature < 1e-7 is the greedy overload's loop.
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, const LookupOptions &lookup,
+                                       fl_spec_stats *stats = nullptr) {
+        cache = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        forwards = 0;
+        if (stats) *stats = fl_spec_stats{};
+        std::vector<uint32_t> output_ids;
+        if (max_tokens == 0) { model.forward(Tensor::from_ids(prompt), 0, cache); forwards++; return output_ids; }
+        output_ids.assign(max_tokens, 0);
+        model.prepare(cache);
+        fl_cache *c = model.raw_cache(cache);
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        check(fl_forward_sample_ex(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0]),
+              "Model forward pass failed");
+        model.advance(cache, 1); forwards++;
+        size_t n = 0;
+        const bool ended = eos && output_ids[0] == *eos;
+        if (!ended && max_tokens > 1) {
+            const fl_sampler s1 = opt.to_ffi((double)temperature, 1);
+            const fl_lookup o = lookup.to_ffi();
+            fl_spec_stats st{};
+            const size_t len0 = fl_cache_len(c);
+            check(fl_decode_lookup_ex(model.raw_model(), c, prompt.data(), prompt.size(), output_ids[0], model.rope_offset(prompt.size(), cache),
+                                      max_tokens - 1, eos ? (int64_t)*eos : -1, &o, &s1, output_ids.data() + 1, &n, &st), "Model forward pass failed");
+            model.advance(cache, fl_cache_len(c) - len0);
+            forwards += (size_t)st.steps;
+            if (stats) *stats = st;
+        }
+        output_ids.resize(ended ? 0 : 1 + n);
+        return output_ids;
+    }
+
+    // ... and as a stream: one fl_lookup_draft + fl_forward_verify_ex step at a time, the draw position (tokens emitted so far) passed
+    // along with every call.  Returns the forwards executed.
+    template <class OnToken>
+    size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos,
+                               const SamplingOptions &opt, const LookupOptions &lookup, OnToken &&on_token) const {
+        M shared = model;
+        typename M::Cache own = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        size_t n_forwards = 0;
+        if (max_tokens == 0) { shared.forward(Tensor::from_ids(prompt), 0, own); return 1; }
+        shared.prepare(own);
+        fl_cache *c = shared.raw_cache(own);
+        uint32_t tok = 0;
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        check(fl_forward_sample_ex(shared.raw_model(), c, prompt.data(), prompt.size(), shared.rope_offset(0, own), &s0, &tok), "Model forward pass failed");
+        shared.advance(own, 1); n_forwards++;
+        if ((eos && tok == *eos) || !on_token(tok)) return n_forwards;
+        const fl_lookup o = lookup.to_ffi();
+        fl_model_info info; check(fl_model_get_info(shared.raw_model(), &info), "fl_model_get_info");
+        std::vector<uint32_t> history(prompt);
+        history.push_back(tok);
+        size_t emitted = 1, pos = prompt.size();
+        uint32_t draft[FL_VERIFY_MAX_DRAFT + 1], got[FL_VERIFY_MAX_DRAFT + 1];
+        while (emitted < max_tokens) {
+            const size_t rope = shared.rope_offset(pos, own);
+            size_t limit = max_tokens - emitted - 1;
+            limit = std::min(limit, fl_cache_capacity(c) - fl_cache_len(c) - 1);
+            limit = std::min(limit, (size_t)info.cfg.max_position_embeddings - rope - 1);
+            if (info.cfg.family != FL_FAMILY_LLAMA && info.cfg.sliding_window > 0) limit = std::min(limit, (size_t)info.cfg.sliding_window);
+            size_t nd = 0, n = 0;
+            check(fl_lookup_draft(history.data(), history.size(), &o, limit, draft, &nd), "fl_lookup_draft");
+            const fl_sampler sp = opt.to_ffi((double)temperature, emitted);     // token k is drawn with word k
+            check(fl_forward_verify_ex(shared.raw_model(), c, tok, draft, nd, rope, &sp, got, &n, nullptr), "Model forward pass failed");
+            n_forwards++;
+            shared.advance(own, n);
+            pos += n;
+            for (size_t i = 0; i < n; i++) {
+                if (eos && got[i] == *eos) return n_forwards;
+                if (!on_token(got[i])) return n_forwards;
+                history.push_back(got[i]);
+                if (++emitted == max_tokens) return n_forwards;
+            }
+            tok = got[n - 1];
+        }
+        return n_forwards;
+    }
+
     // ModelWrapper::generate_stream + generate_tokens_inner (mod.rs:137-238, 268-340) on token ids: the model is CLONED (a
     // reference-count bump, mod.rs:155), the stream gets a FRESH cache of its own (mod.rs:156: this object's `cache` is not
     // touched, so several streams may run on one model at once, each from its own thread -- the reference spawns a task per

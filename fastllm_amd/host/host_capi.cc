@@ -233,6 +233,37 @@ int flh_generate_lookup(void *hv, const uint32_t *prompt, size_t T, size_t max_t
     });
 }
 
+// ... a SAMPLED request with prompt-lookup drafts (SamplingOptions + LookupOptions); top_p <= 0 and top_k <= 0: off; stream != 0: through
+// generate_stream_ids' overload.  stats (optional): steps, drafted, accepted of the non-stream form
+int flh_generate_lookup_sample(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, double top_p,
+                               int64_t top_k, int max_draft, int ngram_max, int ngram_min, int stream, uint32_t *out_tokens, size_t *n_out,
+                               size_t *forwards, uint64_t stats[3]) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        std::vector<uint32_t> p(prompt, prompt + T), r;
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        SamplingOptions opt;
+        if (top_p > 0) opt.top_p = top_p;
+        if (top_k > 0) opt.top_k = (size_t)top_k;
+        LookupOptions lk; lk.max_draft = max_draft; lk.ngram_max = ngram_max; lk.ngram_min = ngram_min;
+        fl_spec_stats st{};
+        size_t fw = 0;
+        auto cb = [&](uint32_t t) { r.push_back(t); return true; };
+        if (stream) {
+            if (h->llama) fw = h->llama->generate_stream_ids(p, max_tokens, temperature, e, opt, lk, cb);
+            else if (h->mistral) fw = h->mistral->generate_stream_ids(p, max_tokens, temperature, e, opt, lk, cb);
+            else fw = h->qwen->generate_stream_ids(p, max_tokens, temperature, e, opt, lk, cb);
+        } else if (h->llama) { r = h->llama->generate_ids(p, max_tokens, temperature, e, opt, lk, &st); fw = h->llama->forwards; }
+        else if (h->mistral) { r = h->mistral->generate_ids(p, max_tokens, temperature, e, opt, lk, &st); fw = h->mistral->forwards; }
+        else { r = h->qwen->generate_ids(p, max_tokens, temperature, e, opt, lk, &st); fw = h->qwen->forwards; }
+        for (size_t i = 0; i < r.size(); i++) out_tokens[i] = r[i];
+        *n_out = r.size();
+        if (forwards) *forwards = fw;
+        if (stats) { stats[0] = st.steps; stats[1] = st.drafted; stats[2] = st.accepted; }
+        return 0;
+    });
+}
+
 // ModelWrapper::generate_stream / generate_tokens_inner on token ids (mod.rs:137-238, 268-340): a stream of its own on the shared
 // model -- fresh cache, seed-0 sampler, one callback per token; the callback returning 0 is the dropped receiver.
 // Thread-safe for concurrent calls on one handle (each call owns its cache).

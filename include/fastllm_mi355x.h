@@ -346,6 +346,34 @@ int fl_lookup_draft(const uint32_t *history, size_t n_history, const fl_lookup *
 int fl_decode_lookup(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos,
                      size_t n_steps, int64_t eos, const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats /* or NULL */);
 
+/* ---- the same two calls for a SAMPLED request: exact multi-row verify ------------------------------------------------------------
+ * The sampler of fl_forward_sample_ex is a pure function of (logits row, settings, index of the word of the seeded stream), and a
+ * prompt-lookup draft is deterministic, so "accept draft d with probability p(d)" is the event "the draw of this row, with this row's
+ * word, is d".  A sampled verify step draws row i with word sampler->draws_done + i (one more launch of the selection kernel's own
+ * code, a workgroup per row) and keeps the longest prefix where the draws equal the drafts: acceptance is what rejection sampling
+ * gives for a deterministic draft, and the output is the seeded stream of the plain loop -- token k is drawn with word k.
+ *   sampler == NULL or temperature < 1e-7: the call IS fl_forward_verify / fl_decode_lookup, with the same launches.
+ *   words: after a verify call the request has consumed *n_out words; the next call passes draws_done + *n_out.  Words of rejected
+ *          rows are not consumed.  The library keeps no counter: every call brings draws_done, as it brings pos.
+ *   n_draft == 0: the one-row sampled decode step (fl_forward_sample_ex of [token]): its kernels, bit for bit.
+ *   fl_decode_lookup_ex is the loop of fl_decode_sample_ex: the EOS rule of fl_decode_lookup (the EOS token is not written, later
+ *          tokens of that step are dropped, the cache keeps the length the plain loop leaves); it consumes the same words -- one per
+ *          emitted token, plus the one that drew EOS -- and needs the same room and never more.  With max_draft == 0 it is
+ *          fl_decode_sample_ex, bit for bit.
+ * GUARANTEE: every emitted token is this library's sampler applied to this library's logits of the preceding tokens -- evaluated as
+ * a ROW OF A MULTI-ROW CALL -- with the word the plain loop would use.  Logits of a multi-row call and of a one-row call differ in
+ * the last bits (more so in bf16), and a draw that lands that close to a boundary of its cumulative interval can come out
+ * differently in the two loops: the sampled form of the greedy step's near-tie sentence.  Nothing else may separate them.
+ * Refusals: those of the greedy calls (tensor parallelism, n_draft > sliding_window, a cache with logit rules or a guide, sizes and
+ * null pointers) plus the sampler's (a wrong struct_size, a NaN top_p, a negative top_k: FL_ERR_BAD_ARGUMENT), all decided before
+ * the device is touched.  Not built: logit rules, guides and log-probs inside verify steps, tensor parallelism, batches. */
+int fl_forward_verify_ex(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos,
+                         const fl_sampler *sampler /* or NULL */, uint32_t *tokens_out /* [n_draft + 1] */, size_t *n_out,
+                         float *logits_out /* [n_draft + 1][V] host, or NULL */);
+int fl_decode_lookup_ex(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos,
+                        size_t n_steps, int64_t eos, const fl_lookup *opts, const fl_sampler *sampler /* or NULL */,
+                        uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats /* or NULL */);
+
 /* Batched decode: B <= 64 caches of one model advanced together, one read of the weights per step for all
  * of them.  New capability: the reference runs concurrent streams as independent single-sequence loops
  * (mod.rs:137-238), each paying for the whole weight stream.  Every sequence keeps its own cache, RoPE
@@ -671,6 +699,18 @@ int fl_op_sample_ex(const float *logits, int64_t V, const fl_sampler *sampler, i
  * draft may be NULL when T == 1. */
 int fl_op_verify_select(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *draft /* [T-1] */,
                         uint32_t *argmax_out /* [T] */, int64_t *n_accepted_out);
+
+/* The selection kernel of a sampled fl_forward_verify_ex alone, on host logits (unit tests, tools): tokens_out[t] = the draw of row t
+ * with word sampler->draws_done + t -- what fl_op_sample_ex gives for that row with that draws_done -- and *n_accepted_out as above.
+ * kept_out (or NULL, [T]): how many tokens each row's filter kept (V when none is on).  temperature < 1e-7: FL_ERR_BAD_ARGUMENT
+ * (that is fl_op_verify_select).  Launched twice on the same buffers: FL_ERR_HIP if the two results differ. */
+int fl_op_verify_sample(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *draft /* [T-1] */, const fl_sampler *sampler,
+                        uint32_t *tokens_out /* [T] */, int64_t *n_accepted_out, int64_t *kept_out /* [T] or NULL */);
+/* ... and timed (tools/verify_sample_cost.py): ms_out[0] = ms per launch of that kernel on the T rows, ms_out[1] = ms per T one-row
+ * selection launches (select_advance) of the same rows, each the mean of iters[form] back-to-back repetitions between two events
+ * (0: that form is not run, ms_out[form] = 0). */
+int fl_op_verify_sample_time(const float *logits /* [T][V] */, int64_t T, int64_t V, const fl_sampler *sampler,
+                             const int32_t *iters /* [2] */, double *ms_out /* [2] */);
 
 /* The log-prob kernel of the fl_*_lp calls alone, on host logits (unit tests, micro-benchmarks): row t's chosen token is chosen[t].
  * 1 <= T <= 64, 0 <= top_n <= min(FL_LOGPROBS_MAX_TOP, V), V <= 1 << 24, chosen[t] < V (FL_ERR_BAD_ARGUMENT otherwise, before the

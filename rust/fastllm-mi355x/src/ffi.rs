@@ -380,6 +380,33 @@ extern "C" {
         n_out: *mut usize,
         stats: *mut fl_spec_stats,
     ) -> c_int;
+    pub fn fl_forward_verify_ex(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        token: u32,
+        draft: *const u32,
+        n_draft: usize,
+        pos: usize,
+        sampler: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        logits_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_decode_lookup_ex(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        corpus: *const u32,
+        n_corpus: usize,
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: i64,
+        opts: *const fl_lookup,
+        sampler: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        stats: *mut fl_spec_stats,
+    ) -> c_int;
 
     pub fn fl_batch_create(m: *mut fl_model, caches: *const *mut fl_cache, n: usize, out: *mut *mut fl_batch) -> c_int;
     pub fn fl_batch_destroy(b: *mut fl_batch);
@@ -573,6 +600,17 @@ extern "C" {
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;
+    pub fn fl_op_verify_sample(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        draft: *const u32,
+        sampler: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_accepted_out: *mut i64,
+        kept_out: *mut i64,
+    ) -> c_int;
+    pub fn fl_op_verify_sample_time(logits: *const f32, t: i64, v: i64, sampler: *const fl_sampler, iters: *const i32, ms_out: *mut f64) -> c_int;
     pub fn fl_op_kv_copy(
         src: *const c_void,
         dst: *mut c_void,

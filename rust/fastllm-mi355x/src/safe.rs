@@ -504,6 +504,46 @@ impl Model {
         Ok((toks, stats))
     }
 
+    /// `fl_decode_lookup_ex`: the sampled loop of `decode_ex` built from verify steps -- row `i` of a step is drawn with word
+    /// `s.draws_done + emitted + i` of the seeded stream and accepted while the draws equal the drafts, so token `k` is drawn with
+    /// word `k` as in the plain loop.  `s.temperature < 1e-7` is `decode_lookup`.
+    pub fn decode_lookup_sampled(
+        &self,
+        cache: &mut Cache,
+        corpus: &[u32],
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: Option<u32>,
+        opts: Lookup,
+        s: Sampler,
+    ) -> Result<(Vec<u32>, ffi::fl_spec_stats)> {
+        let mut toks = vec![0u32; n_steps.max(1)];
+        let mut n = 0usize;
+        let mut stats = ffi::fl_spec_stats::default();
+        let o = opts.to_ffi();
+        let sp = s.to_ffi();
+        check(unsafe {
+            ffi::fl_decode_lookup_ex(
+                self.raw,
+                cache.raw,
+                corpus.as_ptr(),
+                corpus.len(),
+                first_token,
+                pos,
+                n_steps,
+                eos.map(|e| e as i64).unwrap_or(-1),
+                &o,
+                &sp,
+                toks.as_mut_ptr(),
+                &mut n,
+                &mut stats,
+            )
+        })?;
+        toks.truncate(n);
+        Ok((toks, stats))
+    }
+
     pub fn synchronize(&self) -> Result<()> {
         check(unsafe { ffi::fl_synchronize(self.raw) })
     }
