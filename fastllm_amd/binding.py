@@ -2,6 +2,7 @@
 
 Loading fails loudly when the HIP library has not been built: there is no fallback path.
 """
+import collections
 import ctypes as C
 import os
 
@@ -93,6 +94,42 @@ class _LogprobArrays:
 
     def cut(self, n):
         return self.token[:n], self.ids[:n], self.lps[:n]
+
+
+class FlScore(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("top_n", C.c_int32), ("targets", C.c_void_p), ("target_logprob", C.c_void_p),
+                ("target_rank", C.c_void_p), ("top_ids", C.c_void_p), ("top_logprobs", C.c_void_p), ("logits_out", C.c_void_p),
+                ("_reserved", C.c_int64 * 2)]
+
+
+SCORE_NO_TARGET = 0xFFFFFFFF
+# one scoring call's result: target_logprob float32 [T] (NaN: no target), target_rank uint32 [T] (0: no target), top_ids uint32
+# [T, top_n], top_logprobs float32 [T, top_n], logits float32 [T, V] or None
+ScoreResult = collections.namedtuple("ScoreResult", ["target_logprob", "target_rank", "top_ids", "top_logprobs", "logits"])
+
+
+class _ScoreArrays:
+    """Host arrays of one fl_score over T rows (they stay alive as long as this object does)."""
+
+    def __init__(self, T, top_n, targets=None, V=None):
+        self.T, self.top_n = int(T), int(top_n)
+        w = max(self.top_n, 0)
+        self.targets = None if targets is None else np.ascontiguousarray(targets, dtype=np.uint32).reshape(-1)
+        assert self.targets is None or self.targets.size == self.T
+        self.lp = np.zeros(max(self.T, 1), dtype=np.float32)
+        self.rank = np.zeros(max(self.T, 1), dtype=np.uint32)
+        self.ids = np.zeros((max(self.T, 1), w), dtype=np.uint32)
+        self.lps = np.zeros((max(self.T, 1), w), dtype=np.float32)
+        self.logits = None if V is None else np.empty((max(self.T, 1), V), dtype=np.float32)
+
+    def struct(self):
+        return FlScore(C.sizeof(FlScore), self.top_n, None if self.targets is None else self.targets.ctypes.data, self.lp.ctypes.data,
+                       self.rank.ctypes.data, self.ids.ctypes.data if self.top_n > 0 else None,
+                       self.lps.ctypes.data if self.top_n > 0 else None, None if self.logits is None else self.logits.ctypes.data)
+
+    def result(self):
+        T = self.T
+        return ScoreResult(self.lp[:T], self.rank[:T], self.ids[:T], self.lps[:T], None if self.logits is None else self.logits[:T])
 
 
 class FlLogitRules(C.Structure):
@@ -222,6 +259,10 @@ def lib():
         L.fl_decode_sample_lp.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlSampler), vp, C.POINTER(sz), C.POINTER(FlLogprobs)]
         L.fl_batch_decode_each_lp.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
         L.fl_op_logprobs.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        L.fl_forward_score.argtypes = [vp, vp, vp, sz, sz, C.POINTER(FlScore)]
+        L.fl_batch_score.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(FlScore)]
+        L.fl_op_score.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, vp, vp, vp]
+        L.fl_op_score_time.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_set_logit_rules.argtypes = [vp, vp, C.POINTER(FlLogitRules), vp, sz, vp, sz]
         L.fl_cache_logit_counts.argtypes = [vp, vp, vp]
         L.fl_op_logit_rules.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp]
@@ -358,6 +399,27 @@ def op_logprobs(logits, chosen, top_n):
     _check(lib().fl_op_logprobs(a.ctypes.data, T, V, ch.ctypes.data, int(top_n), out.token.ctypes.data,
                                 out.ids.ctypes.data if top_n > 0 else None, out.lps.ctypes.data if top_n > 0 else None))
     return out.cut(T)
+
+
+def op_score(logits, targets, top_n):
+    """The scoring kernel alone: logits [T, V] float32, targets [T] (SCORE_NO_TARGET: none) -> ScoreResult (logits None)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    out = _ScoreArrays(T, top_n, targets)
+    _check(lib().fl_op_score(a.ctypes.data, T, V, out.targets.ctypes.data, int(top_n), out.lp.ctypes.data, out.rank.ctypes.data,
+                             out.ids.ctypes.data if top_n > 0 else None, out.lps.ctypes.data if top_n > 0 else None))
+    return out.result()
+
+
+def op_score_time(logits, targets, top_n, iters):
+    """ms per score_rows launch on the T rows: the mean of `iters` back-to-back launches between two events."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    tg = np.ascontiguousarray(targets, dtype=np.uint32)
+    assert tg.shape == (T,)
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_score_time(a.ctypes.data, T, V, tg.ctypes.data, int(top_n), int(iters), C.byref(ms)))
+    return ms.value
 
 
 def op_logit_rules(logits, words, biases, scalars, tokens, count_input=True, has_rules=None):
@@ -677,6 +739,36 @@ class Model:
                                       C.cast(spx, C.c_void_p) if spx is not None else None, toks.ctypes.data,
                                       lg.ctypes.data if want_logits else None))
         return (toks[:n], lg) if want_logits else toks[:n]
+
+    def forward_score(self, cache, ids, pos, top_n=0, targets=None, want_logits=False):
+        """fl_forward_score: forward(cache, ids, pos) with every row scored on the device; nothing is selected.  targets None: row i's
+        target is ids[i + 1], the last row has none; else [T] ids (SCORE_NO_TARGET: none).  Returns a ScoreResult; want_logits: with
+        the [T, V] rows the kernel read (a diagnostic)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = _ScoreArrays(ids.size, top_n, targets, self.V if want_logits else None)
+        st = out.struct()
+        _check(lib().fl_forward_score(self._h, cache._h, ids.ctypes.data, ids.size, pos, C.byref(st)))
+        return out.result()
+
+    def score_packed(self, caches, seqs, pos=None, top_n=0, targets=None, want_logits=False):
+        """fl_batch_score: seqs[i] appended to caches[i] at RoPE offset pos[i] (None: 0 for all) in ONE forward, every row scored.
+        targets None: next-token scoring per member (every member's last row has none); else one list of ids per member.  Returns one
+        ScoreResult per member (views of the call's arrays)."""
+        n = len(caches)
+        assert len(seqs) == n
+        ps = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in seqs]
+        ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(0, np.uint32), dtype=np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([p.size for p in ps])]), dtype=np.uint64)
+        pos = np.ascontiguousarray([0] * n if pos is None else pos, dtype=np.uint64)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        tg = None if targets is None else np.concatenate([np.asarray(t, dtype=np.uint32).reshape(-1) for t in targets])
+        out = _ScoreArrays(ids.size, top_n, tg, self.V if want_logits else None)
+        st = out.struct()
+        _check(lib().fl_batch_score(self._h, C.cast(arr, C.c_void_p), n, ids.ctypes.data, offsets.ctypes.data, pos.ctypes.data, C.byref(st)))
+        r = out.result()
+        cut = [slice(int(offsets[i]), int(offsets[i + 1])) for i in range(n)]
+        return [ScoreResult(r.target_logprob[c], r.target_rank[c], r.top_ids[c], r.top_logprobs[c], None if r.logits is None else r.logits[c])
+                for c in cut]
 
     def decode_sample(self, cache, first_token, pos, n_steps, temperature, seed=0, draws_done=1, eos=-1, top_p=None, top_k=None,
                       logprobs=None):

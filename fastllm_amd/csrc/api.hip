@@ -286,6 +286,19 @@ int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const siz
     });
 }
 
+// ---- prompt log-probabilities: the fl_score's own errors come first (they need neither model nor device)
+int fl_forward_score(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_score *sc) {
+    return guarded([&]() -> int {
+        return forward_score(M(m), C(c), ids, T, pos, sc);
+    });
+}
+
+int fl_batch_score(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos, const fl_score *sc) {
+    return guarded([&]() -> int {
+        return batch_score(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, sc);
+    });
+}
+
 // ---- logit rules: every argument error is decided before the model, the cache or the device is looked at
 int fl_cache_set_logit_rules(fl_model *m, fl_cache *c, const fl_logit_rules *rules, const uint32_t *prompt_ids, size_t n_prompt,
                              const uint32_t *output_ids, size_t n_output) {

@@ -273,6 +273,76 @@ int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *ch
     });
 }
 
+// the argument checks of fl_op_score / fl_op_score_time
+static int op_score_check(const char *who, const float *logits, int64_t T, int64_t V, const uint32_t *targets, int32_t top_n) {
+    if (!logits || !targets) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null logits or targets", who);
+    if (T < 1 || T > 1024) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: T %lld not in 1..1024", who, (long long)T);
+    if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: V %lld not in 1..2^24", who, (long long)V);
+    if (top_n < 0 || top_n > FL_LOGPROBS_MAX_TOP || top_n > V)
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: top_n %d not in 0..min(%d, V = %lld)", who, top_n, FL_LOGPROBS_MAX_TOP, (long long)V);
+    for (int64_t t = 0; t < T; t++)
+        if (targets[t] != FL_SCORE_NO_TARGET && (int64_t)targets[t] >= V)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: targets[%lld] = %u is not below V = %lld", who, (long long)t, targets[t], (long long)V);
+    return FL_OK;
+}
+
+int fl_op_score(const float *logits, int64_t T, int64_t V, const uint32_t *targets, int32_t top_n, float *target_logprob, uint32_t *target_rank,
+                uint32_t *top_ids, float *top_logprobs) {
+    return guarded([&]() -> int {
+        FL_TRY(op_score_check("fl_op_score", logits, T, V, targets, top_n));
+        if (!target_logprob) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_score: null target_logprob");
+        if (top_n > 0 && (!top_ids || !top_logprobs)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_score: null top_ids or top_logprobs with top_n %d", top_n);
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg; uint32_t *tg; ScoreRec *recs;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.upload(&tg, targets, (size_t)T * 4));
+        FL_TRY(B.alloc(&recs, (size_t)T * sizeof(ScoreRec)));
+        std::vector<ScoreRec> host[2];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the gather's order in LDS differs from launch to launch, the result must not
+            host[rep].resize((size_t)T);
+            FL_HIP(hipMemsetAsync(recs, 0, (size_t)T * sizeof(ScoreRec), B.s));
+            FL_TRY(launch_score_rows(B.L, lg, V, (int)T, tg, top_n, recs));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep].data(), recs, (size_t)T * sizeof(ScoreRec), hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0].data(), host[1].data(), (size_t)T * sizeof(ScoreRec))) FL_FAIL(FL_ERR_HIP, "score_rows: a repeated launch gave another result");
+        for (int64_t t = 0; t < T; t++) {
+            const ScoreRec &r = host[0][(size_t)t];
+            target_logprob[t] = r.lp.chosen;
+            if (target_rank) target_rank[t] = r.rank;
+            for (int j = 0; j < top_n; j++) {
+                top_ids[t * top_n + j] = r.lp.ids[j];
+                top_logprobs[t * top_n + j] = r.lp.lps[j];
+            }
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_score_time(const float *logits, int64_t T, int64_t V, const uint32_t *targets, int32_t top_n, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        FL_TRY(op_score_check("fl_op_score_time", logits, T, V, targets, top_n));
+        if (!ms_out || iters < 1 || iters > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_score_time: null ms_out or a bad iteration count");
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg; uint32_t *tg; ScoreRec *recs;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(B.upload(&tg, targets, (size_t)T * 4));
+        FL_TRY(B.alloc(&recs, (size_t)T * sizeof(ScoreRec)));
+        FL_TRY(launch_score_rows(B.L, lg, V, (int)T, tg, top_n, recs));     // warm
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+        FL_HIP(hipEventRecord(B.e0, B.s));
+        for (int i = 0; i < iters; i++) FL_TRY(launch_score_rows(B.L, lg, V, (int)T, tg, top_n, recs));
+        FL_HIP(hipEventRecord(B.e1, B.s));
+        FL_HIP(hipEventSynchronize(B.e1));
+        float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+        *ms_out = ms / iters;
+        return FL_OK;
+    });
+}
+
 int fl_op_logit_rules(const float *logits, int64_t B, int64_t V, uint32_t *words, const float *biases, const float *scalars,
                       const uint32_t *tokens, int32_t count_input, const uint8_t *has_rules, float *out) {
     return guarded([&]() -> int {

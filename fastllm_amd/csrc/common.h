@@ -122,6 +122,7 @@ enum TuneKey {
     TK_ONESHOT_WIDE,   // one-shot collectives of 16384 floats and more (a decode batch's deltas and logits, a short prompt's span) over up to 256 workgroups (N > 1: at most N); 0: the one-workgroup kernel
     TK_F32_ROWS_MAX,   // fp32 mode: projections of 2 ... this many token rows (short prompts, decode batches; at most 64) as a weight stream with the x rows in LDS (gemv_f32_rows_kernel); 0: the MFMA tiles
     TK_GATEUP_ROWSPLIT,   // gate/up of a prompt 1-96 tokens past an EVEN number of 256-row tiles (513-608, 1025-1120 ...): whole rounds on the 224-column kernel + the last rows as a launch of their own; 0: one launch
+    TK_SCORE_ROWS,   // fl_forward_score / fl_batch_score: rows per lm_head + score_rows block (1..1024); its [rows][V] fp32 scratch is allocated at a model's first scoring call
     TK_COUNT
 };
 int tune(TuneKey k);
@@ -251,6 +252,10 @@ constexpr int kLogprobsMaxTop = 20;          // FL_LOGPROBS_MAX_TOP
 struct LogprobRec { float chosen; uint32_t ids[kLogprobsMaxTop]; float lps[kLogprobsMaxTop]; };
 // ... and where a cache's records go: read from device memory by the kernel, so one captured graph serves every top_n
 struct LogprobCtl { LogprobRec *recs; uint32_t cap; int32_t top_n; };
+// Prompt log-probabilities (fl_forward_score / fl_batch_score): one record per scored row, written by score_rows_kernel (k_score.hip).
+// lp.chosen: the row's target's log-prob (a quiet NaN without one); rank: its 1-based place in the order above (0 without one).
+constexpr uint32_t kScoreNoTarget = 0xffffffffu;   // FL_SCORE_NO_TARGET
+struct ScoreRec { LogprobRec lp; uint32_t rank; };
 
 // Logit rules of a cache (fl_cache_set_logit_rules): one table entry per vocabulary id -- word bit 31 "occurred in the prompt", bits
 // 0..30 the times the id was produced as output -- and the control block logit_rules_kernel (k_logit_rules.hip) reads from device

@@ -431,6 +431,9 @@ struct LogprobSrc {
 };
 int launch_token_logprobs(Launcher &L, const float *logits, int64_t V, int rows, const LogprobSrc &src, int advance);
 int launch_set_logprob_ctl(Launcher &L, LogprobCtl *ctl, LogprobRec *recs, uint32_t cap, int top_n);
+// fl_forward_score / fl_batch_score / fl_op_score (k_score.hip): the same log-softmax of `rows` logits rows [rows][V], one workgroup per
+// row, against targets[row] (device; >= V: no target) -- its log-prob, its rank in the order, and the first top_n -- into recs[row]
+int launch_score_rows(Launcher &L, const float *logits, int64_t V, int rows, const uint32_t *targets, int top_n, ScoreRec *recs);
 // Logit rules (k_logit_rules.hip): out row b = the rules of row b's control block applied to logits row b ([rows][V], fp32), one
 // launch between lm_head and token selection.  The thread that owns element `token` of a row first counts it (count_input).  Who a
 // row belongs to:

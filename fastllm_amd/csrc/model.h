@@ -89,6 +89,20 @@ struct PackedScratch {
     std::vector<void *> allocs;
 };
 
+// fl_forward_score / fl_batch_score: the [R][V] block the rows' logits land in, and a call's targets and records.  They belong to
+// the model, are allocated at its first scoring call (and grow with the largest switch value / call seen), are counted in hbm_bytes
+// and freed with it.
+struct ScoreScratch {
+    int64_t cap_R = 0;
+    float *rows = nullptr;                         // [cap_R][V] fp32: one lm_head block
+    size_t cap_T = 0;                              // rows of one call the buffers below hold
+    uint32_t *targets = nullptr;                   // [cap_T] device
+    ScoreRec *recs = nullptr;                      // [cap_T] device
+    uint32_t *host_targets = nullptr;              // ... and their pinned images: one copy each way per call
+    ScoreRec *host_recs = nullptr;
+    int64_t bytes = 0;                             // HBM counted in hbm_bytes
+};
+
 struct Shard {
     int device = 0;
     int rank = 0;                // TP rank this shard plays
@@ -105,6 +119,7 @@ struct Shard {
     float *cos_tab = nullptr, *sin_tab = nullptr;   // [max_pos][d/2]
     Scratch dec, pre;
     PackedScratch packed;
+    ScoreScratch score;
     float *logits_local = nullptr;   // [Vs]
     ArgmaxCand *amax = nullptr;      // [kMaxArgmaxCand] ArgMax candidates left by the decode step's lm_head launch (GemvArgs::amax)
     bool amax_valid = false;         // ... and whether the forward enqueued last produced them (host-side, per enqueue)
@@ -311,6 +326,31 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
             const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
                   uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
+// fl_forward_score / fl_batch_score (prompt log-probabilities).  check_score: the struct alone plus, where V > 0 is known, the
+// targets -- no device needed; the error names the field
+int check_score(const fl_score *sc, size_t T, int64_t V);
+int forward_score(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_score *sc);
+int batch_score(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos, const fl_score *sc);
+// A forward whose final norm and lm_head run on every row: lm_head in blocks of at most R rows into out ([R][V] fp32), `each`
+// enqueued behind every block (rows r0 .. r0 + n of the forward are in out)
+struct AllRows {
+    float *out;
+    int64_t R;
+    std::function<int(Launcher &, int64_t r0, int64_t n)> each;
+};
+int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows);
+// One scoring call's rows -> records (shared by the single and the packed path): begin sizes the model's buffers for T rows and
+// sends the targets (tg[T], kScoreNoTarget: none); sink() is the AllRows of a forward whose row 0 is row `row0` of the call, one
+// score_rows launch (and, with logits_out, one copy of the block) per lm_head block; one() scores a single row another buffer
+// holds (a decode step's logits_full); end() -- after the stream was waited for -- scatters the records into the caller's arrays.
+struct ScoreCall {
+    Model *m; Shard &sh; const fl_score *sc; size_t T;
+    int begin(const uint32_t *tg);
+    AllRows sink(size_t row0);
+    int one(Launcher &L, const float *row, size_t at);
+    int fetch();                                   // the records' copy to the pinned buffer, on the stream
+    void end();
+};
 // fl_logprobs: FL_ERR_BAD_ARGUMENT for null, a wrong struct_size, top_n outside 0..FL_LOGPROBS_MAX_TOP (or above V, where V > 0 is
 // known), a missing array, nonzero _reserved -- no device needed
 int check_logprobs(const fl_logprobs *lp, int64_t V);

@@ -529,11 +529,24 @@ ResidEpi resid_epi(const Scratch &sc, const Dims &D, const float *next_norm_w) {
     return re;
 }
 
+// lm_head on the T rows whose xn and 1/rms the final norm has left in sc, in blocks of at most rows.R rows into rows.out; rows.each
+// (if any) is enqueued behind every block, before the next one overwrites it
+int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows) {
+    const Dims &D = m->D;
+    for (int64_t r0 = 0; r0 < T; r0 += rows.R) {
+        const int64_t n = std::min<int64_t>(rows.R, T - r0);
+        FL_TRY(launch_linear(L, m->dtype, sh.lm_head, (char *)sc.xn + (size_t)r0 * D.h * m->esize(), nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
+        if (rows.each) FL_TRY(rows.each(L, r0, n));
+    }
+    return FL_OK;
+}
+
 // Enqueue one forward over T tokens on every local shard.  The step state (pos, len, token) of the
 // cache must already be set on the device.  ids_dev == null: the single token comes from the state.
-// all_rows (a verify step, one shard): the final norm and lm_head run on EVERY row, logits [T][V] into all_rows, and the last row's
-// logits are NOT left in logits_full; null: the last position only, exactly the launches there have always been.
-static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_scratch, int64_t len_hint, float *all_rows = nullptr) {
+// all_rows (a verify step or a scored forward, one shard): the final norm and lm_head run on EVERY row (lm_head_rows: in blocks of
+// all_rows->R rows into all_rows->out, a verify step's one block being all of its rows), and the last row's logits are NOT left in
+// logits_full; null: the last position only, exactly the launches there have always been.
+static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_scratch, int64_t len_hint, const AllRows *all_rows = nullptr) {
     for (auto &sh : m->shards) sh.amax_valid = false;                  // (set by the path whose lm_head launch leaves ArgMax candidates)
     if (T == 1 && !pre && !ids_in_scratch && m->fused_decode) return enqueue_decode_fused(m, c, len_hint);
     if (pre && ids_in_scratch && m->tp > 1 && tune(TK_TP_OVERLAP) && T >= tune(TK_TP_OVERLAP_MIN_T) && !m->profiling &&
@@ -638,7 +651,7 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
         FL_HIP(hipSetDevice(sh.device));
         Launcher L = make_launcher(m, sh);
         if (!norm_done) FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
-        return launch_linear(L, dt, sh.lm_head, sc.xn, nullptr, all_rows, T, sh.Vs, D.h, EPI_F32, sc.inv_rms);
+        return lm_head_rows(m, sh, L, sc, T, *all_rows);
     }
     FL_TRY(each_shard(m, c, [&](Shard &sh, CacheShard &, Launcher &L) { return last_row_logits(L, m, sh, SC(sh), T, norm_done, nslab, slab); }));
     return gather_logits(m);
@@ -1143,6 +1156,154 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
     return FL_OK;
 }
 
+// ------------------------------------------------------------------------------- prompt log-probabilities (fl_forward_score, fl_batch_score)
+int check_score(const fl_score *sc, size_t T, int64_t V) {
+    if (!sc) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_score (sc)");
+    if (sc->struct_size != sizeof(fl_score)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.struct_size is %u, expected %zu", sc->struct_size, sizeof(fl_score));
+    if (sc->top_n < 0 || sc->top_n > FL_LOGPROBS_MAX_TOP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.top_n %d not in 0..%d", sc->top_n, FL_LOGPROBS_MAX_TOP);
+    if (!sc->target_logprob) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.target_logprob is null");
+    if (sc->top_n > 0 && !sc->top_ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.top_ids is null with top_n %d", sc->top_n);
+    if (sc->top_n > 0 && !sc->top_logprobs) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.top_logprobs is null with top_n %d", sc->top_n);
+    if (sc->_reserved[0] || sc->_reserved[1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score._reserved must be 0");
+    if (V > 0 && sc->top_n > V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.top_n %d exceeds the vocabulary %lld", sc->top_n, (long long)V);
+    if (V > 0 && sc->targets)
+        for (size_t t = 0; t < T; t++)
+            if (sc->targets[t] != FL_SCORE_NO_TARGET && (int64_t)sc->targets[t] >= V)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_score.targets[%zu] = %u out of range (vocab %lld)", t, sc->targets[t], (long long)V);
+    return FL_OK;
+}
+
+static int score_supported(const Model *m) {
+    if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "prompt log-probabilities do not run under tensor parallelism (tp_size %d)", m->tp);
+    return FL_OK;
+}
+
+static int score_block_rows() { return std::max(1, std::min(1024, tune(TK_SCORE_ROWS))); }
+
+// (never inside a stream capture: the model is locked and scoring launches eagerly)
+int ScoreCall::begin(const uint32_t *tg) {
+    ScoreScratch &ss = sh.score;
+    const int64_t R = score_block_rows(), V = m->D.V;
+    FL_HIP(hipSetDevice(sh.device));
+    if (ss.cap_R < R || ss.cap_T < T) FL_HIP(hipStreamSynchronize(sh.stream));           // (idle anyway: every call ends with a synchronise)
+    if (ss.cap_R < R) {
+        if (ss.rows) { (void)hipFree(ss.rows); ss.rows = nullptr; }
+        m->hbm_bytes -= ss.cap_R * V * 4; ss.bytes -= ss.cap_R * V * 4; ss.cap_R = 0;
+        std::vector<void *> own;
+        FL_TRY(dev_alloc(own, (void **)&ss.rows, (size_t)(R * V) * 4, nullptr));
+        m->hbm_bytes += R * V * 4; ss.bytes += R * V * 4; ss.cap_R = R;
+    }
+    if (ss.cap_T < T) {
+        const size_t per = 4 + sizeof(ScoreRec);
+        if (ss.targets) (void)hipFree(ss.targets);
+        if (ss.recs) (void)hipFree(ss.recs);
+        if (ss.host_targets) (void)hipHostFree(ss.host_targets);
+        if (ss.host_recs) (void)hipHostFree(ss.host_recs);
+        ss.targets = nullptr; ss.recs = nullptr; ss.host_targets = nullptr; ss.host_recs = nullptr;
+        m->hbm_bytes -= (int64_t)(ss.cap_T * per); ss.bytes -= (int64_t)(ss.cap_T * per); ss.cap_T = 0;
+        const size_t cap = std::max<size_t>(T + T / 2, 256);
+        std::vector<void *> own;
+        FL_TRY(dev_alloc(own, (void **)&ss.targets, cap * 4, nullptr));
+        FL_TRY(dev_alloc(own, (void **)&ss.recs, cap * sizeof(ScoreRec), nullptr));
+        FL_HIP(hipHostMalloc((void **)&ss.host_targets, cap * 4, hipHostMallocDefault));
+        FL_HIP(hipHostMalloc((void **)&ss.host_recs, cap * sizeof(ScoreRec), hipHostMallocDefault));
+        m->hbm_bytes += (int64_t)(cap * per); ss.bytes += (int64_t)(cap * per); ss.cap_T = cap;
+    }
+    memcpy(ss.host_targets, tg, T * 4);
+    FL_HIP(hipMemcpyAsync(ss.targets, ss.host_targets, T * 4, hipMemcpyHostToDevice, sh.stream));
+    return FL_OK;
+}
+
+int ScoreCall::one(Launcher &L, const float *row, size_t at) {
+    ScoreScratch &ss = sh.score;
+    FL_TRY(launch_score_rows(L, row, m->D.V, 1, ss.targets + at, sc->top_n, ss.recs + at));
+    if (sc->logits_out) FL_HIP(hipMemcpyAsync(sc->logits_out + at * (size_t)m->D.V, row, (size_t)m->D.V * 4, hipMemcpyDeviceToHost, sh.stream));
+    return FL_OK;
+}
+
+AllRows ScoreCall::sink(size_t row0) {
+    ScoreScratch &ss = sh.score;
+    ScoreCall self = *this;
+    return AllRows{ss.rows, std::min<int64_t>(ss.cap_R, score_block_rows()), [self, row0](Launcher &L, int64_t r0, int64_t n) -> int {
+        ScoreScratch &s2 = self.sh.score;
+        const size_t at = row0 + (size_t)r0, V = (size_t)self.m->D.V;
+        FL_TRY(launch_score_rows(L, s2.rows, (int64_t)V, (int)n, s2.targets + at, self.sc->top_n, s2.recs + at));
+        // (the diagnostic copy: stream-ordered, so the next block's lm_head overwrites the rows only behind it)
+        if (self.sc->logits_out) FL_HIP(hipMemcpyAsync(self.sc->logits_out + at * V, s2.rows, (size_t)n * V * 4, hipMemcpyDeviceToHost, self.sh.stream));
+        return FL_OK;
+    }};
+}
+
+int ScoreCall::fetch() {
+    ScoreScratch &ss = sh.score;
+    FL_HIP(hipMemcpyAsync(ss.host_recs, ss.recs, T * sizeof(ScoreRec), hipMemcpyDeviceToHost, sh.stream));
+    return FL_OK;
+}
+
+void ScoreCall::end() {
+    const ScoreRec *r = sh.score.host_recs;
+    const size_t n = (size_t)sc->top_n;
+    for (size_t t = 0; t < T; t++) {
+        sc->target_logprob[t] = r[t].lp.chosen;
+        if (sc->target_rank) sc->target_rank[t] = r[t].rank;
+        for (size_t j = 0; j < n; j++) { sc->top_ids[t * n + j] = r[t].lp.ids[j]; sc->top_logprobs[t * n + j] = r[t].lp.lps[j]; }
+    }
+}
+
+// fl_forward with every row scored: the same chunks, the same mask, the same per-layer launches; behind each chunk's layers the final
+// norm runs on all its rows and lm_head in blocks of score_rows rows, each followed by one score_rows launch.  Nothing is selected,
+// and a cache's logit rules or guide are neither applied nor counted: the distribution is the model's own.
+int forward_score(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_score *sc) {
+    FL_TRY(check_score(sc, T, 0));
+    FL_TRY(check_call(m, c, T, pos));
+    debug_inject("forward");
+    if (!ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null ids");
+    for (size_t t = 0; t < T; t++) FL_TRY(check_token(m, ids[t], "token"));
+    FL_TRY(check_score(sc, T, m->D.V));
+    FL_TRY(score_supported(m));
+    std::vector<uint32_t> tg(T, kScoreNoTarget);
+    for (size_t t = 0; t < T; t++) if (sc->targets ? true : t + 1 < T) tg[t] = sc->targets ? sc->targets[t] : ids[t + 1];
+    std::lock_guard<std::mutex> lock(m->mu);
+    Shard &sh = m->shards[0];
+    ScoreCall call{m, sh, sc, T};
+    FL_TRY(call.begin(tg.data()));
+    const SampleState argmax{};
+    if (T == 1) {
+        // the decode step's forward (its mask, its kernels); the row is the one it leaves in logits_full
+        FL_TRY(set_state(m, c, ids[0], pos, c->len, 0, -1, (size_t)-1, &argmax));
+        FL_TRY(enqueue_forward(m, c, false, 1, false, (int64_t)c->len));
+        Launcher L = make_launcher(m, sh);
+        FL_TRY(call.one(L, sh.logits_full, 0));
+        c->len += 1;
+    } else {
+        const int64_t chunk_max = tune(TK_PREFILL_CHUNK);
+        size_t done = 0;
+        const size_t call0 = c->len;                 // the mask of every chunk is that of the single call
+        while (done < T) {
+            int64_t Tc = (int64_t)std::min<size_t>(T - done, (size_t)chunk_max);
+            if (T - done - (size_t)Tc == 1 && Tc > 2) Tc -= 1;      // never leave a 1-token tail (it would take the decode mask)
+            FL_HIP(hipSetDevice(sh.device));
+            if (sh.pre.cap_T < Tc) FL_TRY(grow_prefill_scratch(m, sh, Tc));
+            FL_HIP(hipMemcpyAsync(sh.pre.ids, ids + done, (size_t)Tc * 4, hipMemcpyHostToDevice, sh.stream));
+            FL_TRY(set_state(m, c, ids[done], pos + done, c->len, 0, -1, call0, &argmax));
+            if (Tc == 1) {
+                FL_TRY(enqueue_forward(m, c, false, 1, false, (int64_t)c->len));
+                Launcher L = make_launcher(m, sh);
+                FL_TRY(call.one(L, sh.logits_full, done));
+            } else {
+                const AllRows rows = call.sink(done);
+                FL_TRY(enqueue_forward(m, c, true, Tc, true, (int64_t)c->len, &rows));
+            }
+            c->len += (size_t)Tc;
+            done += (size_t)Tc;
+        }
+    }
+    FL_TRY(call.fetch());
+    FL_TRY(finish_call(m, c, 0));
+    call.end();
+    return FL_OK;
+}
+
 // ------------------------------------------------------------------------------- speculative greedy decode
 int cache_truncate(Cache *c, size_t len) {
     if (!c) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_cache_truncate: null cache");
@@ -1235,7 +1396,8 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     FL_HIP(hipMemcpyAsync(sh.pre.ids, ids, (size_t)T * 4, hipMemcpyHostToDevice, sh.stream));
     const SampleState argmax{};
     FL_TRY(set_state(m, c, token, pos, c->len, 0, -1, c->len, &argmax));
-    FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, sh.verify_logits));
+    const AllRows rows{sh.verify_logits, T, nullptr};
+    FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, &rows));
     Launcher L = make_launcher(m, sh);
     if (sampled) FL_TRY(launch_verify_sample(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, *sampler, sh.verify_scratch, sh.verify_out, nullptr));
     else FL_TRY(launch_verify_select(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));

@@ -53,10 +53,10 @@ struct StreamDrain {            // an early return leaves nothing in flight that
     ~StreamDrain() { (void)hipStreamSynchronize(s); }
 };
 
-}  // namespace
-
-int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
-                  const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out) {
+// batch_prefill, or -- score != null -- batch_score: the same checks and the same layers; behind them either the n last rows go through
+// the final norm, lm_head and token selection, or ALL rows go through the final norm and lm_head in blocks, each scored (model.h: ScoreCall)
+int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                   const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out, const fl_score *score) {
     // ---- everything that can be refused is refused here, before the device or any cache is touched
     if (!m || !caches || !ids || !offsets || !pos) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
     if (n < 1 || n > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%zu sequences: a packed prefill takes 1..%d", n, kMaxBatch);
@@ -76,6 +76,16 @@ int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids,
     for (size_t i = 0; i < n; i++) FL_TRY(check_call(m, caches[i], offsets[i + 1] - offsets[i], pos[i]));
     std::vector<SampleState> sampler(n);
     for (size_t i = 0; i < n; i++) FL_TRY(make_sampler(samplers ? samplers + i : nullptr, m->D.V, &sampler[i]));
+    std::vector<uint32_t> tg;
+    if (score) {
+        FL_TRY(check_score(score, T_total, m->D.V));
+        // targets NULL: next-token scoring per sequence -- the last row of every member has no target
+        tg.assign(T_total, kScoreNoTarget);
+        for (size_t i = 0; i < n; i++)
+            for (size_t r = offsets[i]; r < offsets[i + 1]; r++)
+                if (score->targets) tg[r] = score->targets[r];
+                else if (r + 1 < offsets[i + 1]) tg[r] = ids[r + 1];
+    }
     debug_inject("batch_prefill");
 
     const Dims &D = m->D;
@@ -159,14 +169,23 @@ int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids,
         FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
     }
 
-    // ---- the n last rows: gather, final norm (residual + delta slabs), lm_head once at T = n, token selection per sequence
     const int nn = (int)n;
-    const int64_t lslab = (int64_t)nn * D.h;
-    FL_TRY(launch_gather_last_rows(L, sc.x_res, tb, ps.xl, nn, D.h, 1, 0, 0));
-    FL_TRY(launch_gather_last_rows(L, sc.delta, tb, ps.dl, nn, D.h, nslab, slab, lslab));
-    FL_TRY(launch_rmsnorm_add(L, dt, ps.xl, ps.dl, sh.norm, D.eps, ps.xnl, ps.inv_rms, nn, D.h, nslab, lslab));
-    FL_TRY(launch_linear(L, dt, sh.lm_head, ps.xnl, nullptr, ps.logits, nn, D.V, D.h, EPI_F32, ps.inv_rms));
-    FL_TRY(launch_select_advance_batch(L, ps.logits, D.V, tb.seqs, nn, 0));
+    ScoreCall call{m, sh, score, T_total};
+    if (score) {
+        // ---- every row: final norm (residual + delta slabs) at T = T_total, lm_head in blocks, one score_rows launch behind each
+        FL_TRY(call.begin(tg.data()));
+        FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
+        FL_TRY(lm_head_rows(m, sh, L, sc, T, call.sink(0)));
+        FL_TRY(call.fetch());
+    } else {
+        // ---- the n last rows: gather, final norm (residual + delta slabs), lm_head once at T = n, token selection per sequence
+        const int64_t lslab = (int64_t)nn * D.h;
+        FL_TRY(launch_gather_last_rows(L, sc.x_res, tb, ps.xl, nn, D.h, 1, 0, 0));
+        FL_TRY(launch_gather_last_rows(L, sc.delta, tb, ps.dl, nn, D.h, nslab, slab, lslab));
+        FL_TRY(launch_rmsnorm_add(L, dt, ps.xl, ps.dl, sh.norm, D.eps, ps.xnl, ps.inv_rms, nn, D.h, nslab, lslab));
+        FL_TRY(launch_linear(L, dt, sh.lm_head, ps.xnl, nullptr, ps.logits, nn, D.V, D.h, EPI_F32, ps.inv_rms));
+        FL_TRY(launch_select_advance_batch(L, ps.logits, D.V, tb.seqs, nn, 0));
+    }
 
     // ---- back to the host (tokens and error words gathered for one copy); only when every member's step state is clean do the caches grow
     FL_TRY(launch_packed_collect(L, tb, ps.result, nn));
@@ -179,7 +198,20 @@ int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids,
         caches[i]->len += (size_t)counts[i];
         if (tokens_out) tokens_out[i] = ps.host_result[2 * i];
     }
+    if (score) call.end();
     return FL_OK;
+}
+
+}  // namespace
+
+int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                  const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out) {
+    return packed_forward(m, caches, n, ids, offsets, pos, samplers, tokens_out, logits_out, nullptr);
+}
+
+int batch_score(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos, const fl_score *sc) {
+    FL_TRY(check_score(sc, 0, 0));              // the struct's own errors first: they need neither model nor device
+    return packed_forward(m, caches, n, ids, offsets, pos, nullptr, nullptr, nullptr, sc);
 }
 
 }  // namespace fl

@@ -118,6 +118,11 @@ Model::~Model() {
         if (s.packed.tab) (void)hipFree(s.packed.tab);
         if (s.packed.host_tab) (void)hipHostFree(s.packed.host_tab);
         if (s.packed.host_result) (void)hipHostFree(s.packed.host_result);
+        if (s.score.rows) (void)hipFree(s.score.rows);
+        if (s.score.targets) (void)hipFree(s.score.targets);
+        if (s.score.recs) (void)hipFree(s.score.recs);
+        if (s.score.host_targets) (void)hipHostFree(s.score.host_targets);
+        if (s.score.host_recs) (void)hipHostFree(s.score.host_recs);
         if (s.stream && std::find(closed.begin(), closed.end(), s.stream) == closed.end()) {
             closed.push_back(s.stream);
             gemm_8p_release_stream(s.stream);

@@ -618,6 +618,18 @@ struct TokenLogprobs {
     int top_n = 0;
 };
 
+// Prompt log-probabilities (score_ids): per row of a scored forward the log-probability of the NEXT id of the text (NaN for the last
+// row, which has none), its rank in the order "logit descending, lower index first" (1 = the most likely id; 0: none) and, row-major
+// [n][top_n], the most likely ids and theirs -- TokenLogprobs' shape with ranks.  Computed on the device (fl_forward_score) from the
+// model's own distribution.  New capability; the reference reports none.
+struct ScoredTokens {
+    std::vector<float> token;
+    std::vector<uint32_t> rank;
+    std::vector<uint32_t> top_ids;
+    std::vector<float> top;
+    int top_n = 0;
+};
+
 // A request's logit_bias and repetition / frequency / presence penalties (fl_logit_rules): installed on the request's cache, applied
 // on the device to every row a token is selected from, the output counts kept by the decode loop itself.  New capability; the
 // reference has none.  repetition_penalty 1 and the other two 0 are off; a bias of -inf bans an id.
@@ -778,6 +790,31 @@ struct Model {                                // mod.rs:342-361
         const size_t total = ended ? 0 : 1 + n;
         output_ids.resize(total); out->token.resize(total); out->top_ids.resize(total * w); out->top.resize(total * w);
         return output_ids;
+    }
+
+    // What an `echo` + `logprobs` request, a `loglikelihood` evaluation or a reranker asks for: every id of a text scored under the
+    // model, from a fresh cache, in ONE forward (fl_forward_score) -- row i against ids[i + 1].  The cache afterwards is the one a
+    // forward of the ids leaves.
+    ScoredTokens score_ids(const std::vector<uint32_t> &ids, int top_logprobs) {
+        if (top_logprobs < 0 || top_logprobs > FL_LOGPROBS_MAX_TOP) throw Error(FL_ERR_BAD_ARGUMENT, "score_ids: top_logprobs out of range");
+        cache = M::initialize_cache(device, dtype);
+        if (ids.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        ScoredTokens out;
+        out.top_n = top_logprobs;
+        const size_t w = (size_t)top_logprobs, n = ids.size();
+        out.token.assign(n, 0.f); out.rank.assign(n, 0); out.top_ids.assign(n * w, 0); out.top.assign(n * w, 0.f);
+        fl_score sc{};
+        sc.struct_size = (uint32_t)sizeof(fl_score);
+        sc.top_n = top_logprobs;
+        sc.target_logprob = out.token.data();
+        sc.target_rank = out.rank.data();
+        sc.top_ids = w ? out.top_ids.data() : nullptr;
+        sc.top_logprobs = w ? out.top.data() : nullptr;
+        model.prepare(cache);
+        check(fl_forward_score(model.raw_model(), model.raw_cache(cache), ids.data(), n, model.rope_offset(0, cache), &sc), "Model forward pass failed");
+        model.advance(cache, 1);                                          // (one forward call, as behind the prompt in generate_ids)
+        forwards = 1;
+        return out;
     }
 
     // ... with logit rules: installed on the fresh cache (the prompt's ids marked as seen) before the first fl_forward_sample_ex, so

@@ -174,6 +174,19 @@ int flh_generate_logprobs(void *hv, const uint32_t *prompt, size_t T, size_t max
     });
 }
 
+// Model<M>::score_ids: target_logprob / target_rank [T], top_ids / top_logprobs [T][top_n] (may be null when top_n == 0)
+int flh_score_ids(void *hv, const uint32_t *ids, size_t T, int top_n, float *target_logprob, uint32_t *target_rank, uint32_t *top_ids,
+                  float *top_logprobs) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        std::vector<uint32_t> p(ids, ids + T);
+        const ScoredTokens r = h->llama ? h->llama->score_ids(p, top_n) : h->mistral ? h->mistral->score_ids(p, top_n) : h->qwen->score_ids(p, top_n);
+        for (size_t i = 0; i < r.token.size(); i++) { target_logprob[i] = r.token[i]; target_rank[i] = r.rank[i]; }
+        for (size_t i = 0; i < r.top_ids.size(); i++) { top_ids[i] = r.top_ids[i]; top_logprobs[i] = r.top[i]; }
+        return 0;
+    });
+}
+
 namespace {
 LogitRules make_rules(size_t n_bias, const uint32_t *bias_ids, const float *bias_values, float rp, float fp, float pp) {
     LogitRules r;

@@ -469,6 +469,56 @@ int fl_decode_sample_lp(fl_model *m, fl_cache *c, uint32_t first_token, size_t p
 int fl_batch_decode_each_lp(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, const int64_t *eos,
                             const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, const fl_logprobs *lp /* [n_seq] */);
 
+/* ---- prompt log-probabilities: every row of a forward scored on the device ---------------------------------------------------------
+ * New capability (the reference reports none).  What an OpenAI-compatible server is asked for as `echo` + `logprobs`, the open-source
+ * servers as `prompt_logprobs`, an evaluation harness as `loglikelihood`: the log-probability of tokens the model did NOT generate.
+ * fl_forward_score is fl_forward with every row scored: the cache ends up exactly as fl_forward leaves it (the same chunks of
+ * FL_PREFILL_CHUNK, the same mask, the same per-layer launches; T = 1 takes the decode step), but behind each chunk's layers the final
+ * norm runs on all its rows, lm_head runs in blocks of FL_SCORE_ROWS rows (default 256; fl_tune "score_rows", 1 .. 1024) into one
+ * [rows][V] fp32 scratch, and each block is followed by one launch that scores its rows.  T x V logits never exist at once; per row
+ * 168 bytes come back, in one copy per call.  No token is selected.  Logit rules and a guide installed on the cache are neither
+ * applied nor counted: THE DISTRIBUTION IS THE MODEL'S OWN, as for fl_logprobs.
+ *
+ * Row t (the position of ids[t]) has the fp32 logits x[0..V) that a prefill of ids[0 .. t] would return, and lp as defined for
+ * fl_logprobs above -- the same arithmetic (x[j] - m in fp32, precise expf, the sum in fp64, then log and the final fp32 subtraction),
+ * the same kernel code.  Its target is targets[t]; targets == NULL means next-token scoring: row t's target is ids[t + 1] and the
+ * last row has none.  FL_SCORE_NO_TARGET: the row has none.
+ *   target_logprob[t] = lp[target]; a quiet NaN where the row has no target.
+ *   target_rank[t]    = 1 + the number of ids that precede the target in the order "logit descending, LOWER index first among equal
+ *                       values" (so: 1 = it is top_ids[t][0]; whenever rank <= top_n, top_ids[t][rank - 1] == target); 0 where the row
+ *                       has no target.  Defined for a -inf target too.
+ *   top_ids[t][0..top_n), top_logprobs[t][..]: as for fl_logprobs, reported whether or not the row has a target.
+ * A row with NaN, or without a finite maximum, gives unspecified values (never a fault; every reported id is < V).
+ * logits_out (or NULL): host [T][V], the rows the scoring kernel read -- a DIAGNOSTIC like fl_forward_verify's (T x V x 4 bytes cross
+ * the bus): for tests and tools, not for production use.
+ * fl_batch_score is fl_batch_prefill (without tokens_out) with every row scored: the same checks and limits, the same layers, the
+ * caches as it leaves them; ONE fl_score whose arrays run over all offsets[n] rows; with targets == NULL the shift is per sequence
+ * (the last row of every member has no target).
+ * FL_ERR_BAD_ARGUMENT, before the device or a cache is touched, naming the field: null sc, wrong struct_size, top_n outside
+ * 0 .. FL_LOGPROBS_MAX_TOP or above the vocabulary, a missing required array, a target >= V other than FL_SCORE_NO_TARGET, nonzero
+ * _reserved; then the errors of fl_forward / fl_batch_prefill.  FL_ERR_UNSUPPORTED: tp_size > 1 in any mode.  Any dtype and weight
+ * format otherwise.
+ * Memory: a model's FIRST scoring call allocates the block scratch (FL_SCORE_ROWS x V x 4 bytes of HBM: 33 MB at V = 32 000, 156 MB at
+ * V = 152 064 with the default 256) and the target / record buffers (172 bytes of HBM and of pinned host memory per row of the largest
+ * call seen); they are counted in fl_model_hbm_bytes and freed with the model.  Models that never score pay nothing.
+ * Not here: scoring under tensor parallelism, inside verify / lookup steps, echoed log-probs in StreamBatcher, prompt log-probs under
+ * logit rules or a guide, a softmax reduction fused into the lm_head GEMM (no logits in memory at top_n = 0). */
+#define FL_SCORE_NO_TARGET 4294967295u   /* 0xffffffff */
+typedef struct fl_score {
+    uint32_t  struct_size;      /* sizeof(fl_score), FL_ERR_BAD_ARGUMENT otherwise */
+    int32_t   top_n;            /* 0 .. FL_LOGPROBS_MAX_TOP */
+    const uint32_t *targets;    /* host [T] or NULL (next-token scoring); an entry is < V or FL_SCORE_NO_TARGET */
+    float    *target_logprob;   /* host [T]            : required */
+    uint32_t *target_rank;      /* host [T]            : optional */
+    uint32_t *top_ids;          /* host [T][top_n]     : required iff top_n > 0 */
+    float    *top_logprobs;     /* host [T][top_n]     : required iff top_n > 0 */
+    float    *logits_out;       /* host [T][V]         : optional, diagnostic */
+    int64_t   _reserved[2];     /* 0 */
+} fl_score;
+int fl_forward_score(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, const fl_score *sc);
+int fl_batch_score(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
+                   const size_t *pos /* [n] */, const fl_score *sc /* ONE struct, arrays over offsets[n] rows */);
+
 /* ---- logit rules: logit_bias and repetition / frequency / presence penalties inside the device decode loop -------------------------
  * New capability (the reference has none).  What an OpenAI-compatible server is asked for as `logit_bias`, `frequency_penalty`,
  * `presence_penalty`, and the `repetition_penalty` of the open-source servers.  The rules belong to a cache: installing them gives
@@ -717,6 +767,17 @@ int fl_op_verify_sample_time(const float *logits /* [T][V] */, int64_t T, int64_
  * device is probed); top_ids / top_logprobs may be NULL when top_n == 0.  Launched twice: FL_ERR_HIP if the two results differ. */
 int fl_op_logprobs(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *chosen /* [T] */, int32_t top_n,
                    float *token_logprob /* [T] */, uint32_t *top_ids /* [T][top_n] or NULL */, float *top_logprobs /* [T][top_n] or NULL */);
+
+/* The scoring kernel of fl_forward_score / fl_batch_score alone, on host logits (unit tests, micro-benchmarks): row t's target is
+ * targets[t] (FL_SCORE_NO_TARGET: none).  1 <= T <= 1024, 0 <= top_n <= min(FL_LOGPROBS_MAX_TOP, V), V <= 1 << 24, targets[t] < V or
+ * the sentinel (FL_ERR_BAD_ARGUMENT otherwise, before the device is probed); target_rank may be NULL, top_ids / top_logprobs when
+ * top_n == 0.  Launched twice: FL_ERR_HIP if the two results differ. */
+int fl_op_score(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *targets /* [T] */, int32_t top_n,
+                float *target_logprob /* [T] */, uint32_t *target_rank /* [T] or NULL */, uint32_t *top_ids /* [T][top_n] or NULL */,
+                float *top_logprobs /* [T][top_n] or NULL */);
+/* ... and timed (tools/score_cost.py): *ms_out = ms per launch on the T rows, the mean of `iters` back-to-back launches between two events */
+int fl_op_score_time(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *targets /* [T] */, int32_t top_n, int32_t iters,
+                     double *ms_out);
 
 /* The logit-rules kernel alone, on host arrays (unit tests): the batch form on B rows of V logits.  Row b has its own table
  * (words / biases [B][V]; words in/out: the counted word comes back) and scalars scalars[b] = {repetition, frequency, presence

@@ -154,6 +154,26 @@ pub struct fl_logprobs {
     pub _reserved: [i64; 2],
 }
 
+/// `FL_SCORE_NO_TARGET`: a row of a scoring call without a target.
+pub const FL_SCORE_NO_TARGET: u32 = 4294967295;
+
+/// `fl_score`: what a scoring call (`fl_forward_score`, `fl_batch_score`) scores every row against and where the results go -- host
+/// arrays over the call's T rows.  `targets` null: next-token scoring (row i's target is `ids[i + 1]`, a sequence's last row has none).
+/// `target_rank` and `logits_out` (a diagnostic, `[T][V]`) are optional; `struct_size` is `size_of::<fl_score>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_score {
+    pub struct_size: u32,
+    pub top_n: i32,
+    pub targets: *const u32,
+    pub target_logprob: *mut f32,
+    pub target_rank: *mut u32,
+    pub top_ids: *mut u32,
+    pub top_logprobs: *mut f32,
+    pub logits_out: *mut f32,
+    pub _reserved: [i64; 2],
+}
+
 /// `fl_logit_rules`: `logit_bias` entries and the repetition / frequency / presence penalties a cache applies on the device to every
 /// row it selects a token from (fl_cache_set_logit_rules); `struct_size` is `size_of::<fl_logit_rules>()`.  `repetition_penalty` 1 and
 /// the other two 0 are off; a bias of negative infinity bans an id.
@@ -499,6 +519,29 @@ extern "C" {
         top_ids: *mut u32,
         top_logprobs: *mut f32,
     ) -> c_int;
+    /// `fl_forward` / `fl_batch_prefill` with every row scored on the device (prompt log-probabilities); nothing is selected.
+    pub fn fl_forward_score(m: *mut fl_model, c: *mut fl_cache, ids: *const u32, t: usize, pos: usize, sc: *const fl_score) -> c_int;
+    pub fn fl_batch_score(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        ids: *const u32,
+        offsets: *const usize,
+        pos: *const usize,
+        sc: *const fl_score,
+    ) -> c_int;
+    pub fn fl_op_score(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        targets: *const u32,
+        top_n: i32,
+        target_logprob: *mut f32,
+        target_rank: *mut u32,
+        top_ids: *mut u32,
+        top_logprobs: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_score_time(logits: *const f32, t: i64, v: i64, targets: *const u32, top_n: i32, iters: i32, ms_out: *mut f64) -> c_int;
     pub fn fl_cache_set_logit_rules(
         m: *mut fl_model,
         c: *mut fl_cache,

@@ -18,4 +18,4 @@
 pub mod ffi;
 pub mod safe;
 
-pub use safe::{op_sample, Activation, Batch, Cache, Config, DType, Encoder, EncoderConfig, Error, Family, Guide, LogitRules, Model, Result, Sampler, Sampling, TensorView, TokenLogprobs, WeightFormat};
+pub use safe::{op_sample, Activation, Batch, Cache, Config, DType, Encoder, EncoderConfig, Error, Family, Guide, LogitRules, Model, Result, Sampler, Sampling, ScoredTokens, TensorView, TokenLogprobs, WeightFormat};

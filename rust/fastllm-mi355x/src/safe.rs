@@ -124,6 +124,17 @@ pub struct TokenLogprobs {
     pub top_n: usize,
 }
 
+/// What `Model::forward_score` returns, one entry per row of the call: the target's log-probability (NaN: the row has none), its
+/// rank in the order "logit descending, lower index first" (0: none), and row-major `[T][top_n]` ids and log-probabilities.
+#[derive(Clone, Debug, Default)]
+pub struct ScoredTokens {
+    pub target_logprob: Vec<f32>,
+    pub target_rank: Vec<u32>,
+    pub top_ids: Vec<u32>,
+    pub top_logprobs: Vec<f32>,
+    pub top_n: usize,
+}
+
 /// LogitsProcessor::from_sampling(seed, Sampling::TopP / TopK / TopKThenTopP) on the device (`fl_sampler`).  `top_p` outside
 /// (0, 1) and `top_k` 0 are "off"; both off is `Sampling::All`.  The kept set is a prefix of the order by probability
 /// descending, the lower index first among equals; `top_k = 1` therefore keeps the LOWEST maximal index while ArgMax
@@ -351,6 +362,39 @@ impl Model {
         let mut logits = vec![0f32; self.vocab];
         check(unsafe { ffi::fl_forward(self.raw, cache.raw, ids.as_ptr(), ids.len(), pos, logits.as_mut_ptr()) })?;
         Ok(logits)
+    }
+
+    /// `forward` with every row scored on the device (prompt log-probabilities): row i against `targets[i]` (`FL_SCORE_NO_TARGET`:
+    /// none), or -- `targets` `None` -- against `ids[i + 1]`, the last row having none.  The cache ends up as `forward` leaves it; no
+    /// token is selected; the distribution is the model's own.
+    pub fn forward_score(&self, cache: &mut Cache, ids: &[u32], pos: usize, top_n: usize, targets: Option<&[u32]>) -> Result<ScoredTokens> {
+        let t = ids.len();
+        if let Some(tg) = targets {
+            if tg.len() != t {
+                return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: "forward_score: one target per id".into() });
+            }
+        }
+        let mut lp = vec![0f32; t.max(1)];
+        let mut rank = vec![0u32; t.max(1)];
+        let mut top_ids = vec![0u32; (t * top_n).max(1)];
+        let mut top = vec![0f32; (t * top_n).max(1)];
+        let sc = ffi::fl_score {
+            struct_size: std::mem::size_of::<ffi::fl_score>() as u32,
+            top_n: top_n as i32,
+            targets: targets.map(|x| x.as_ptr()).unwrap_or(ptr::null()),
+            target_logprob: lp.as_mut_ptr(),
+            target_rank: rank.as_mut_ptr(),
+            top_ids: if top_n > 0 { top_ids.as_mut_ptr() } else { ptr::null_mut() },
+            top_logprobs: if top_n > 0 { top.as_mut_ptr() } else { ptr::null_mut() },
+            logits_out: ptr::null_mut(),
+            _reserved: [0; 2],
+        };
+        check(unsafe { ffi::fl_forward_score(self.raw, cache.raw, ids.as_ptr(), t, pos, &sc) })?;
+        lp.truncate(t);
+        rank.truncate(t);
+        top_ids.truncate(t * top_n);
+        top.truncate(t * top_n);
+        Ok(ScoredTokens { target_logprob: lp, target_rank: rank, top_ids, top_logprobs: top, top_n })
     }
 
     /// The same forward with ArgMax on the device (ties -> last index, Rust `max_by`).
