@@ -153,6 +153,26 @@ class FlGuideDesc(C.Structure):
                 ("next", C.c_void_p), ("_reserved", C.c_int64 * 2)]
 
 
+class FlNormLinearArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int32), ("dtype", C.c_int32), ("epilogue", C.c_int32), ("pro", C.c_int32),
+                ("T", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("x_res", C.c_void_p), ("x", C.c_void_p), ("delta", C.c_void_p),
+                ("norm_w", C.c_void_p), ("embed", C.c_void_p), ("tokens", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p),
+                ("bias", C.c_void_p), ("vocab", C.c_int64), ("n_slab", C.c_int32), ("repeat", C.c_int32), ("eps", C.c_float),
+                ("reserved", C.c_float), ("y", C.c_void_p), ("x_out", C.c_void_p), ("kernels_out", C.c_void_p)]
+
+
+class FlLinearResidArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("T", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("N2", C.c_int64), ("x", C.c_void_p),
+                ("w", C.c_void_p), ("bias", C.c_void_p), ("h_in", C.c_void_p), ("w_next", C.c_void_p), ("w2", C.c_void_p),
+                ("eps", C.c_float), ("lazy", C.c_int32), ("epi2", C.c_int32), ("repeat", C.c_int32), ("h_out", C.c_void_p),
+                ("xn_out", C.c_void_p), ("inv_rms_out", C.c_void_p), ("part_out", C.c_void_p), ("y2_out", C.c_void_p),
+                ("kernels_out", C.c_void_p)]
+
+
+# kernel codes in the kernels_out arrays of op_norm_linear / op_linear_resid (FL_LK_* of the header)
+LK_NAMES = ("none", "gemv", "h4", "w14", "skf", "dma", "skinny", "8p", "8p_streamk", "256", "128", "4w_rope", "generic", "f32_rows", "f32_mfma")
+
+
 def make_guide_desc(row_ptr, tokens, next):
     """fl_guide_desc from the CSR arrays of a token-level automaton; returns (struct, arrays to keep alive)."""
     rp = np.ascontiguousarray(row_ptr, dtype=np.uint64).reshape(-1)
@@ -294,6 +314,9 @@ def lib():
         L.fl_op_linear.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32,
                                    C.POINTER(C.c_double)]
         L.fl_op_quantize_rows.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp, vp]
+        L.fl_op_rmsnorm_add.argtypes = [vp, vp, C.c_int32, vp, C.c_float, C.c_int64, C.c_int64, C.c_int32, vp, vp]
+        L.fl_op_norm_linear.argtypes = [C.POINTER(FlNormLinearArgs)]
+        L.fl_op_linear_resid.argtypes = [C.POINTER(FlLinearResidArgs)]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
@@ -1173,3 +1196,100 @@ def op_gemv_w8(x, q, s, bias=None, epilogue=0, iters=0):
     _check(lib().fl_op_gemv_w8(x.ctypes.data, q.ctypes.data, s.ctypes.data, b.ctypes.data if b is not None else None, N, K,
                                epilogue, y.ctypes.data, iters, C.byref(ms)))
     return (y, ms.value) if iters else y
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def op_rmsnorm_add(x_res, delta, w, eps, dtype):
+    """launch_rmsnorm_add alone (fl_op_rmsnorm_add).  x_res [T, h] float32; delta [n_slab, T, h] float32 or None; w [h]; dtype "bf16"
+    or "f32": the type xs is rounded to.  Returns (the updated x_res, xs widened to float32, inv_rms [T])."""
+    x = np.array(x_res, dtype=np.float32, order="C", copy=True)
+    T, h = x.shape
+    d = _f32(delta) if delta is not None else None
+    assert d is None or d.shape[1:] == (T, h)
+    w = _f32(w)
+    assert w.shape == (h,)
+    xs, inv = np.empty((T, h), np.float32), np.empty(T, np.float32)
+    _check(lib().fl_op_rmsnorm_add(x.ctypes.data, _ptr(d), 0 if d is None else d.shape[0], w.ctypes.data, eps, T, h,
+                                   BF16 if dtype == "bf16" else F32, xs.ctypes.data, inv.ctypes.data))
+    return x, xs, inv
+
+
+def op_norm_linear(form, w, norm_w=None, eps=0.0, x_res=None, delta=None, embed=None, tokens=None, x=None, bias=None, w_scale=None,
+                   epilogue=0, pro=1, dtype=None, repeat=1):
+    """Residual add -> RMSNorm -> one projection in the fused form `form` (fl_op_norm_linear; 0: rmsnorm_add + launch_linear with the
+    row scale, 1: the single-sequence stream's norm prologue, 2: the same over FP8 weights (w uint8 [N, K] + w_scale), 3: the batched
+    stream; pro=0 (form 3): no norm, x [T, K] uint16 instead).  w [N, K] float32 or uint16 (bf16 bits); x_res [T, K] float32 with
+    delta [n_slab, T, K] or None -- or embed [V, K] (w's dtype) with tokens [T].  Returns (y, x_out or None, kernels [4])."""
+    w = np.ascontiguousarray(w)
+    N, K = w.shape
+    code = (BF16 if dtype == "bf16" else F32) if dtype is not None else (BF16 if form == 2 else _np_dtype_code(w))
+    a = FlNormLinearArgs()
+    a.struct_size = C.sizeof(FlNormLinearArgs)
+    a.form, a.dtype, a.epilogue, a.pro, a.repeat, a.eps = form, code, epilogue, pro, repeat, eps
+    keep = [w]
+    if embed is not None:
+        embed = np.ascontiguousarray(embed)
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        T = tokens.shape[0]
+        a.embed, a.tokens, a.vocab = embed.ctypes.data, tokens.ctypes.data, embed.shape[0]
+        assert embed.shape[1] == K
+    elif pro == 0:
+        x = np.ascontiguousarray(x, dtype=np.uint16)
+        T = x.shape[0]
+        a.x = x.ctypes.data
+    else:
+        x_res = _f32(x_res)
+        T = x_res.shape[0]
+        assert x_res.shape == (T, K)
+        a.x_res = x_res.ctypes.data
+    keep += [embed, tokens, x, x_res]
+    if delta is not None:
+        delta = _f32(delta)
+        assert delta.shape[1:] == (T, K)
+        a.delta, a.n_slab = delta.ctypes.data, delta.shape[0]
+    norm_w = _f32(norm_w) if norm_w is not None else None
+    bias = _f32(bias) if bias is not None else None
+    w_scale = _f32(w_scale) if w_scale is not None else None
+    a.norm_w, a.bias, a.w_scale, a.w = _ptr(norm_w), _ptr(bias), _ptr(w_scale), w.ctypes.data
+    a.T, a.N, a.K = T, N, K
+    y = np.empty((T, N // 2 if epilogue == 1 else N), np.float32)
+    x_out = np.empty((T, K), np.float32) if pro == 1 else None
+    kernels = np.zeros(4, np.int32)
+    a.y, a.x_out, a.kernels_out = y.ctypes.data, _ptr(x_out), kernels.ctypes.data
+    keep += [delta, norm_w, bias, w_scale]
+    _check(lib().fl_op_norm_linear(C.byref(a)))
+    return y, x_out, kernels
+
+
+def op_linear_resid(x, w, h_in, w_next, eps, bias=None, w2=None, epi2=0, lazy=False, repeat=1):
+    """A bf16 projection with the residual + next-norm epilogue, and optionally the projection that consumes it (fl_op_linear_resid).
+    x [T, K], w [N, K], w2 [N2, N]: uint16 (bf16 bits); h_in [T, N], w_next [N] float32.  Returns a dict: h, xn (widened), inv_rms,
+    part [T, np], y2 (or None) and kernels = {kernel, ks, tail, tail_ks, consumer, consumer_reads_parts} (names of LK_NAMES)."""
+    x, w = np.ascontiguousarray(x, dtype=np.uint16), np.ascontiguousarray(w, dtype=np.uint16)
+    h_in, w_next = _f32(h_in), _f32(w_next)
+    (T, K), N = x.shape, w.shape[0]
+    assert w.shape == (N, K) and h_in.shape == (T, N) and w_next.shape == (N,)
+    bias = _f32(bias) if bias is not None else None
+    w2 = np.ascontiguousarray(w2, dtype=np.uint16) if w2 is not None else None
+    a = FlLinearResidArgs()
+    a.struct_size = C.sizeof(FlLinearResidArgs)
+    a.T, a.N, a.K, a.N2 = T, N, K, 0 if w2 is None else w2.shape[0]
+    a.x, a.w, a.bias, a.h_in, a.w_next, a.w2 = x.ctypes.data, w.ctypes.data, _ptr(bias), h_in.ctypes.data, w_next.ctypes.data, _ptr(w2)
+    a.eps, a.lazy, a.epi2, a.repeat = eps, int(bool(lazy)), epi2, repeat
+    np_ = (N + 255) // 256 * 4
+    h, xn, inv, part = np.empty((T, N), np.float32), np.empty((T, N), np.float32), np.empty(T, np.float32), np.empty((T, np_), np.float32)
+    y2 = np.empty((T, w2.shape[0] // 2 if epi2 == 1 else w2.shape[0]), np.float32) if w2 is not None else None
+    kernels = np.zeros(6, np.int32)
+    a.h_out, a.xn_out, a.inv_rms_out, a.part_out, a.y2_out, a.kernels_out = (h.ctypes.data, xn.ctypes.data, inv.ctypes.data, part.ctypes.data,
+                                                                               _ptr(y2), kernels.ctypes.data)
+    _check(lib().fl_op_linear_resid(C.byref(a)))
+    k = dict(kernel=LK_NAMES[kernels[0]], ks=int(kernels[1]), tail=LK_NAMES[kernels[2]], tail_ks=int(kernels[3]), consumer=LK_NAMES[kernels[4]],
+             consumer_reads_parts=bool(kernels[5]))
+    return dict(h=h, xn=xn, inv_rms=inv, part=part, y2=y2, kernels=k)

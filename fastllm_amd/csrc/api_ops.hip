@@ -20,7 +20,7 @@ struct OpScope {
     int begin() { FL_TRY(require_device()); FL_HIP(hipSetDevice(0)); FL_HIP(hipStreamCreate(&s)); L.stream = s; return FL_OK; }
     ~OpScope() {
         // the split-K workspaces the GEMMs keep per stream go before the stream does (no-ops for a stream they never saw)
-        if (s) { (void)hipStreamSynchronize(s); gemm_8p_release_stream(s); gemm_h4_release_stream(s); }
+        if (s) { (void)hipStreamSynchronize(s); gemm_8p_release_stream(s); gemm_h4_release_stream(s); gemm_skf_release_stream(s); }
         for (void *x : p) (void)hipFree(x);
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
@@ -111,6 +111,71 @@ int attn_op_scratch(OpScope &B, float **pm, float **pl, float **po, unsigned **c
     FL_TRY(B.alloc(pm, (size_t)H * nsplit * 4)); FL_TRY(B.alloc(pl, (size_t)H * nsplit * 4));
     FL_TRY(B.alloc(po, (size_t)H * nsplit * d * 4)); FL_TRY(B.alloc(cnt, (size_t)H * 4));
     FL_HIP(hipMemset(*cnt, 0, (size_t)H * 4));
+    return FL_OK;
+}
+
+// ---- the norm ops ---------------------------------------------------------------------------------------------------------------
+
+static_assert(FL_LK_NONE == LK_NONE && FL_LK_GEMV == LK_GEMV && FL_LK_H4 == LK_H4 && FL_LK_W14 == LK_W14 && FL_LK_SKF == LK_SKF && FL_LK_DMA == LK_DMA &&
+              FL_LK_SKINNY == LK_SKINNY && FL_LK_8P == LK_8P && FL_LK_8P_STREAMK == LK_8P_STREAMK && FL_LK_256 == LK_256 && FL_LK_128 == LK_128 &&
+              FL_LK_4W_ROPE == LK_4W_ROPE && FL_LK_GENERIC == LK_GENERIC && FL_LK_F32_ROWS == LK_F32_ROWS && FL_LK_F32_MFMA == LK_F32_MFMA,
+              "the header's FL_LK_* codes are kernels.h's LK_*");
+
+// The device image of a host matrix w [N][K] of `dtype`: as it is, or (gate/up: rows gate | up in HF order) in the 16-interleaved
+// layout with the pairs padded to whole groups of 16, as fl_op_linear lays it out.  *Nw: its rows; *Ip: the padded pair count.
+int op_upload_matrix(OpScope &B, int32_t dtype, const void *w, int64_t N, int64_t K, int epi, void **wd, int64_t *Nw, int64_t *Ip) {
+    const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+    const int64_t I = N / 2;
+    *Ip = (I + 15) / 16 * 16;
+    *Nw = epi == EPI_GATEUP ? 2 * *Ip : N;
+    if (epi != EPI_GATEUP) return B.upload(wd, w, (size_t)N * K * es);
+    void *ws;
+    FL_TRY(B.upload(&ws, w, (size_t)N * K * es));
+    FL_TRY(B.alloc(wd, (size_t)*Nw * K * es));
+    FL_HIP(hipMemsetAsync(*wd, 0, (size_t)*Nw * K * es, B.s));
+    FL_TRY(launch_convert_slice(B.L, dtype, ws, K, 0, 0, I, K, dtype, *wd, K, 0, 1));
+    return launch_convert_slice(B.L, dtype, ws, K, I, 0, I, K, dtype, *wd, K, 0, 2);
+}
+
+// the fl_op_norm_linear checks that need no device
+int norm_linear_check(const fl_norm_linear_args *a) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_norm_linear: null args");
+    if (a->struct_size != sizeof(fl_norm_linear_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_norm_linear: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_norm_linear_args));
+    if (a->form < 0 || a->form > 3) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_norm_linear: form %d not in 0..3", a->form);
+    if (a->dtype != FL_DTYPE_BF16 && a->dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+    if (a->epilogue != EPI_F32 && a->epilogue != EPI_GATEUP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "epilogue must be 0 or 1");
+    if (a->pro != PRO_X && a->pro != PRO_NORM) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pro must be 0 or 1");
+    if (a->pro == PRO_X && a->form != 3) FL_FAIL(FL_ERR_BAD_ARGUMENT, "pro 0 (no norm) is the batched stream's (form 3)");
+    if (!a->w || !a->y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument (w, y)");
+    if (a->T <= 0 || a->N <= 0 || a->K <= 0 || a->K % 8 || a->N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (K must be a multiple of 8)");
+    if (a->epilogue == EPI_GATEUP && ((a->N % 2) || a->bias)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count and takes no bias");
+    if (a->repeat < 1 || a->repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "repeat %d not in 1..8", a->repeat);
+    if (a->pro == PRO_NORM) {
+        if (!a->norm_w) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null norm_w");
+        if (a->n_slab < 0 || a->n_slab > 64 || (a->n_slab > 0) != (a->delta != nullptr)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "n_slab 0..64, with delta exactly when it is not 0");
+        if (a->embed) {
+            if (a->x_res || a->delta || !a->tokens || a->vocab < 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "embed takes tokens and a vocab size, and neither x_res nor delta");
+            for (int64_t t = 0; t < a->T; t++)
+                if ((int64_t)a->tokens[t] >= a->vocab) FL_FAIL(FL_ERR_BAD_ARGUMENT, "tokens[%lld] = %u is not below vocab %lld", (long long)t, a->tokens[t], (long long)a->vocab);
+        } else if (!a->x_res) {
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "null x_res (and no embed)");
+        }
+    } else if (!a->x) {
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "null x");
+    }
+    const int64_t Nw = a->epilogue == EPI_GATEUP ? (a->N / 2 + 15) / 16 * 32 : a->N;
+    if (a->form == 1) {
+        if (a->T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "form 1: the single-sequence stream takes one row");
+        if (!gemv_norm_supported(a->dtype, Nw, a->K)) FL_FAIL(FL_ERR_UNSUPPORTED, "form 1: the norm prologue needs K <= 6144");
+    } else if (a->form == 2) {
+        if (a->T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "form 2: the single-sequence stream takes one row");
+        if (!a->w_scale) FL_FAIL(FL_ERR_BAD_ARGUMENT, "form 2: null w_scale");
+        if (a->dtype != FL_DTYPE_BF16 || a->n_slab > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "form 2: bf16 activations, at most one delta vector");
+        if (!gemv_w8_norm_supported(Nw, a->K)) FL_FAIL(FL_ERR_UNSUPPORTED, "form 2: K a multiple of 16, at most 6144");
+    } else if (a->form == 3) {
+        if (a->T > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "form 3: at most 8 rows");
+        if (a->dtype != FL_DTYPE_BF16) FL_FAIL(FL_ERR_UNSUPPORTED, "form 3: bf16");
+    }
     return FL_OK;
 }
 
@@ -846,6 +911,258 @@ int fl_op_attention_packed(const void *q, const void *const *k, const void *cons
         FL_TRY(launch_attn_prefill_packed_mfma(B.L, qd, ph.at(tabd), ph.n_items, ph.TT, ph.ks, (size_t)(layer * Hkv * d), od, H, Hkv, d, scale, window < 0 ? -1 : window));
         FL_HIP(hipStreamSynchronize(B.s));
         return op_download(out, od, qn, FL_DTYPE_BF16);
+    });
+}
+
+int fl_op_rmsnorm_add(float *x_res, const float *delta, int32_t n_slab, const float *w, float eps, int64_t T, int64_t h, int32_t dtype,
+                      float *xs_out, float *inv_rms_out) {
+    return guarded([&]() -> int {
+        if (!x_res || !w || !xs_out || !inv_rms_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+        if (T <= 0 || T > (1 << 20) || h <= 0 || h % 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (h must be a multiple of 8)");
+        if (n_slab < 0 || n_slab > 64 || (n_slab > 0) != (delta != nullptr)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "n_slab 0..64, with delta exactly when it is not 0");
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t n = (size_t)T * h, es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+        float *xd, *dd = nullptr, *wd, *inv; void *xs;
+        FL_TRY(B.upload(&xd, x_res, n * 4));
+        if (delta) FL_TRY(B.upload(&dd, delta, n * 4 * n_slab));
+        FL_TRY(B.upload(&wd, w, (size_t)h * 4));
+        FL_TRY(B.alloc(&xs, n * es));
+        FL_TRY(B.alloc(&inv, (size_t)T * 4));
+        FL_HIP(hipMemset(xs, 0xff, n * es));                       // NaN pattern: an element the kernel does not write shows up
+        FL_HIP(hipMemset(inv, 0xff, (size_t)T * 4));
+        FL_TRY(launch_rmsnorm_add(B.L, dtype, xd, dd, wd, eps, xs, inv, T, h, std::max(n_slab, 1), (int64_t)n));
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(x_res, xd, n * 4, hipMemcpyDeviceToHost));
+        FL_HIP(hipMemcpy(inv_rms_out, inv, (size_t)T * 4, hipMemcpyDeviceToHost));
+        return op_download(xs_out, xs, n, dtype);
+    });
+}
+
+int fl_op_norm_linear(const fl_norm_linear_args *args) {
+    return guarded([&]() -> int {
+        FL_TRY(norm_linear_check(args));
+        const fl_norm_linear_args &a = *args;
+        OpScope B;
+        FL_TRY(B.begin());
+        const int dtype = a.dtype, epi = a.epilogue, form = a.form;
+        const int64_t T = a.T, N = a.N, K = a.K, I = N / 2;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, nx = (size_t)T * K;
+        const bool norm = a.pro == PRO_NORM;
+        // the weights: e4m3 bytes + row scales (form 2), else a matrix of the compute dtype
+        int64_t Nw = N, Ip = (I + 15) / 16 * 16;
+        void *wd = nullptr; float *sd = nullptr, *bd = nullptr;
+        if (form == 2) {
+            Nw = epi == EPI_GATEUP ? 2 * Ip : N;
+            if (epi == EPI_GATEUP) {
+                uint8_t *qs, *qd; float *ss;
+                FL_TRY(B.upload(&qs, a.w, (size_t)N * K));
+                FL_TRY(B.upload(&ss, a.w_scale, (size_t)N * 4));
+                FL_TRY(B.alloc(&qd, (size_t)Nw * K));
+                FL_TRY(B.alloc(&sd, (size_t)Nw * 4));
+                FL_HIP(hipMemsetAsync(qd, 0, (size_t)Nw * K, B.s));
+                FL_HIP(hipMemsetAsync(sd, 0, (size_t)Nw * 4, B.s));
+                FL_TRY(launch_w8_gateup_layout(B.L, qs, ss, I, K, qd, sd));
+                wd = qd;
+            } else {
+                FL_TRY(B.upload(&wd, a.w, (size_t)N * K));
+                FL_TRY(B.upload(&sd, a.w_scale, (size_t)N * 4));
+            }
+        } else {
+            FL_TRY(op_upload_matrix(B, dtype, a.w, N, K, epi, &wd, &Nw, &Ip));
+        }
+        if (a.bias) FL_TRY(B.upload(&bd, a.bias, (size_t)N * 4));
+        const int64_t Ny = epi == EPI_GATEUP ? Ip : N;               // columns of the device output
+        const size_t ybytes = (size_t)T * Ny * (epi == EPI_GATEUP ? es : 4);
+        // the norm's inputs: the residual rows (a pristine copy: form 0 updates them in place), or the embedding matrix and one
+        // step state per row holding its token
+        float *xr0 = nullptr, *xr = nullptr, *xo = nullptr, *dd = nullptr, *nw = nullptr, *inv = nullptr;
+        void *xs = nullptr, *xp = nullptr, *ed = nullptr; uint32_t *ids = nullptr; StepState *std_ = nullptr; SeqRef *seqs = nullptr;
+        if (norm) {
+            FL_TRY(B.upload(&nw, a.norm_w, (size_t)K * 4));
+            FL_TRY(B.alloc(&xo, nx * 4));
+            if (a.delta) FL_TRY(B.upload(&dd, a.delta, nx * 4 * a.n_slab));
+            if (a.embed) {
+                FL_TRY(B.upload(&ed, a.embed, (size_t)a.vocab * K * es));
+                FL_TRY(B.upload(&ids, a.tokens, (size_t)T * 4));
+                std::vector<StepState> st((size_t)T);
+                std::vector<SeqRef> refs((size_t)T);
+                for (int64_t t = 0; t < T; t++) { st[(size_t)t] = StepState{}; st[(size_t)t].token = a.tokens[t]; st[(size_t)t].eos = -1; }
+                FL_TRY(B.upload(&std_, st.data(), sizeof(StepState) * (size_t)T));
+                for (int64_t t = 0; t < T; t++) { refs[(size_t)t] = SeqRef{}; refs[(size_t)t].st = std_ + t; }
+                FL_TRY(B.upload(&seqs, refs.data(), sizeof(SeqRef) * (size_t)T));
+            } else {
+                FL_TRY(B.upload(&xr0, a.x_res, nx * 4));
+            }
+            if (form == 0) {
+                FL_TRY(B.alloc(&xr, nx * 4));
+                FL_TRY(B.alloc(&xs, nx * es));
+                FL_TRY(B.alloc(&inv, (size_t)T * 4));
+            }
+        } else {
+            FL_TRY(B.upload(&xp, a.x, nx * 2));
+        }
+        // form 0: K slabs as fl_op_linear allows them, and its FL_OP_LINEAR_DMA route; form 3: the batched stream's K slices
+        const int op_split = tune(TK_OP_MAXSPLIT);
+        const int max_split = form == 0 && epi == EPI_F32 && !bd ? (op_split > 0 ? op_split : std::max(4, ksplit_cap(T))) : 1;
+        const int nks = form == 3 ? gemv_batch_ksplit((int)T, K, Nw, epi) : 1;
+        const bool dma = form == 0 && tune(TK_OP_LINEAR_DMA) == 1 && dtype == FL_DTYPE_BF16 && T <= 32 && !bd && gemv_dma_supported((int)T, Nw, K, epi, 0) &&
+                         gemv_dma_ksplit(K, Nw, epi) <= max_split;
+        int nsplit = 1;
+        void *yd;
+        FL_TRY(B.alloc(&yd, ybytes * std::max(max_split, nks)));
+        if (a.kernels_out) {
+            const LinearPlan p = form == 0 ? plan_linear(dtype, T, Nw, K, epi, B.L.tp, max_split, bd != nullptr, true, false) : LinearPlan{};
+            a.kernels_out[0] = dma ? (int)LK_DMA : p.kernel; a.kernels_out[1] = form == 3 ? nks : dma ? gemv_dma_ksplit(K, Nw, epi) : p.ks;
+            a.kernels_out[2] = dma ? (int)LK_NONE : p.tail; a.kernels_out[3] = dma ? (int)LK_NONE : p.rest;
+        }
+        auto run = [&]() -> int {
+            FL_HIP(hipMemsetAsync(yd, 0xff, ybytes * std::max(max_split, nks), B.s));      // NaN pattern: an element no launch writes shows up
+            if (xo) FL_HIP(hipMemsetAsync(xo, 0xff, nx * 4, B.s));
+            if (form == 0) {
+                if (a.embed) FL_TRY(launch_embed(B.L, dtype, ed, ids, nullptr, xr, T, K));
+                else FL_HIP(hipMemcpyAsync(xr, xr0, nx * 4, hipMemcpyDeviceToDevice, B.s));
+                FL_TRY(launch_rmsnorm_add(B.L, dtype, xr, dd, nw, a.eps, xs, inv, T, K, std::max(a.n_slab, 1), (int64_t)nx));
+                if (!dma) return launch_linear(B.L, dtype, wd, xs, bd, yd, T, Nw, K, epi, inv, max_split, &nsplit);
+                GemvBatchArgs ga;
+                ga.W = wd; ga.x = xs; ga.x_scale = inv; ga.out = yd; ga.N = (int)Nw; ga.K = (int)K; ga.epi = epi; ga.pro = PRO_X; ga.B = (int)T;
+                ga.nks = epi == EPI_F32 ? gemv_dma_ksplit(K, Nw, epi) : 1;
+                nsplit = ga.nks;
+                return launch_gemv_dma(B.L, ga);
+            }
+            if (form == 3) {
+                GemvBatchArgs ga;
+                ga.W = wd; ga.bias = bd; ga.out = yd; ga.N = (int)Nw; ga.K = (int)K; ga.epi = epi; ga.pro = a.pro; ga.B = (int)T; ga.nks = nks;
+                ga.x = xp; ga.x_in = xr0; ga.delta = dd; ga.norm_w = nw; ga.n_slab = std::max(a.n_slab, 1); ga.slab_stride = (long long)nx; ga.eps = a.eps;
+                ga.x_out = xo; ga.embed = ed; ga.seqs = seqs;
+                nsplit = nks;
+                return launch_gemv_batch(B.L, ga);
+            }
+            GemvArgs ga;
+            ga.W = wd; ga.bias = bd; ga.out = yd; ga.N = (int)Nw; ga.K = (int)K; ga.epi = epi; ga.pro = PRO_NORM;
+            ga.x_in = xr0; ga.delta = dd; ga.delta_nslab = std::max(a.n_slab, 1); ga.norm_w = nw; ga.eps = a.eps; ga.x_out = xo; ga.embed = ed; ga.st = std_;
+            return form == 1 ? launch_gemv(B.L, dtype, ga) : launch_gemv_w8(B.L, ga, sd);
+        };
+        std::vector<unsigned char> first, again;
+        std::vector<float> xfirst(norm ? nx : 0), xagain(norm ? nx : 0);
+        for (int rep = 0; rep < a.repeat; rep++) {
+            FL_TRY(run());
+            FL_HIP(hipStreamSynchronize(B.s));
+            std::vector<unsigned char> &yb = rep ? again : first;
+            std::vector<float> &xb = rep ? xagain : xfirst;
+            yb.resize(ybytes * (size_t)nsplit);
+            FL_HIP(hipMemcpy(yb.data(), yd, yb.size(), hipMemcpyDeviceToHost));
+            if (norm) FL_HIP(hipMemcpy(xb.data(), form == 0 ? xr : xo, nx * 4, hipMemcpyDeviceToHost));
+            if (rep && (first != again || (norm && memcmp(xfirst.data(), xagain.data(), nx * 4))))
+                FL_FAIL(FL_ERR_HIP, "fl_op_norm_linear: launch %d of form %d gave another result than the first", rep, form);
+        }
+        if (a.x_out && norm) memcpy(a.x_out, xfirst.data(), nx * 4);
+        if (epi == EPI_GATEUP) {                                     // without the padding columns
+            for (int64_t t = 0; t < T; t++)
+                for (int64_t j = 0; j < I; j++) {
+                    const size_t idx = (size_t)(t * Ip + j);
+                    a.y[t * I + j] = es == 2 ? bf16_bits_to_float(reinterpret_cast<const bf16_t *>(first.data())[idx]) : reinterpret_cast<const float *>(first.data())[idx];
+                }
+            return FL_OK;
+        }
+        const float *slabs = reinterpret_cast<const float *>(first.data());
+        for (size_t i = 0; i < (size_t)T * N; i++) {                 // the K slabs summed in slab order, like rmsnorm_add does
+            float s = slabs[i];
+            for (int sl = 1; sl < nsplit; sl++) s += slabs[(size_t)sl * T * N + i];
+            a.y[i] = s;
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_linear_resid(const fl_linear_resid_args *args) {
+    return guarded([&]() -> int {
+        if (!args) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_linear_resid: null args");
+        const fl_linear_resid_args &a = *args;
+        if (a.struct_size != sizeof(fl_linear_resid_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_linear_resid: struct_size %zu, expected %zu", a.struct_size, sizeof(fl_linear_resid_args));
+        if (!a.x || !a.w || !a.h_in || !a.w_next || !a.h_out || !a.xn_out || !a.inv_rms_out || !a.part_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (a.T <= 0 || a.N <= 0 || a.K <= 0 || a.K % 8 || a.N % 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (N and K must be multiples of 8)");
+        if (a.repeat < 1 || a.repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "repeat %d not in 1..8", a.repeat);
+        if (a.w2 && (!a.y2_out || a.N2 <= 0 || (a.epi2 != EPI_F32 && a.epi2 != EPI_GATEUP) || (a.epi2 == EPI_GATEUP && a.N2 % 2)))
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "the consumer: y2_out, N2 > 0 (even for gate/up), epi2 0 or 1");
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t T = a.T, N = a.N, K = a.K;
+        const LinearPlan p = plan_resid(FL_DTYPE_BF16, T, N, K, ksplit_cap(T), false);
+        if (p.kernel == LK_NONE) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_linear_resid: no kernel takes the residual epilogue at T %lld, N %lld, K %lld", (long long)T, (long long)N, (long long)K);
+        const int np = gemm_resid_partials(N);
+        const size_t nh = (size_t)T * N, npart = (size_t)T * np;
+        void *xd, *wd, *xn, *w2d = nullptr, *y2 = nullptr; float *bd = nullptr, *h0, *h, *wn, *part, *inv;
+        FL_TRY(B.upload(&xd, a.x, (size_t)T * K * 2));
+        FL_TRY(B.upload(&wd, a.w, (size_t)N * K * 2));
+        if (a.bias) FL_TRY(B.upload(&bd, a.bias, (size_t)N * 4));
+        FL_TRY(B.upload(&h0, a.h_in, nh * 4));
+        FL_TRY(B.upload(&wn, a.w_next, (size_t)N * 4));
+        FL_TRY(B.alloc(&h, nh * 4));
+        FL_TRY(B.alloc(&xn, nh * 2));
+        FL_TRY(B.alloc(&part, npart * 4));
+        FL_TRY(B.alloc(&inv, (size_t)T * 4));
+        int64_t N2w = 0, I2p = 0;
+        size_t y2bytes = 0;
+        LinearPlan cp;
+        if (a.w2) {
+            FL_TRY(op_upload_matrix(B, FL_DTYPE_BF16, a.w2, a.N2, N, a.epi2, &w2d, &N2w, &I2p));
+            y2bytes = a.epi2 == EPI_GATEUP ? (size_t)T * I2p * 2 : (size_t)T * a.N2 * 4;
+            FL_TRY(B.alloc(&y2, y2bytes));
+            cp = plan_linear(FL_DTYPE_BF16, T, N2w, N, a.epi2, B.L.tp, 1, false, false, false);
+        }
+        if (a.kernels_out) {
+            a.kernels_out[0] = p.kernel; a.kernels_out[1] = p.ks; a.kernels_out[2] = p.n_main < N ? p.tail : (int)LK_NONE; a.kernels_out[3] = p.tail_ks;
+            a.kernels_out[4] = cp.kernel; a.kernels_out[5] = cp.reads_rs_parts ? 1 : 0;
+        }
+        ResidEpi re;                                                 // as resid_epi (model.hip) lays it out
+        re.h = h; re.w = wn; re.xn = xn; re.part = part; re.np = np;
+        // what one launch sequence left, as bytes: h | xn | part | y2 | inv
+        const size_t off_xn = nh * 4, off_part = off_xn + nh * 2, off_y2 = off_part + npart * 4, off_inv = off_y2 + y2bytes, total = off_inv + (size_t)T * 4;
+        std::vector<unsigned char> first(total), again(total);
+        for (int rep = 0; rep < a.repeat; rep++) {
+            // NaN patterns: a slot, an element or a row scale nobody writes shows up
+            FL_HIP(hipMemcpyAsync(h, h0, nh * 4, hipMemcpyDeviceToDevice, B.s));
+            FL_HIP(hipMemsetAsync(xn, 0xff, nh * 2, B.s));
+            FL_HIP(hipMemsetAsync(part, 0xff, npart * 4, B.s));
+            FL_HIP(hipMemsetAsync(inv, 0xff, (size_t)T * 4, B.s));
+            if (y2) FL_HIP(hipMemsetAsync(y2, 0xff, y2bytes, B.s));
+            FL_TRY(launch_plan(B.L, p, FL_DTYPE_BF16, wd, xd, bd, nullptr, T, N, K, EPI_RESID, nullptr, &re));
+            if (!a.lazy) FL_TRY(launch_rms_finalize(B.L, part, np, a.eps, inv, T, N));
+            else if (a.w2) B.L.rsp = RsParts{part, np, a.eps, 1.0f / (float)N};          // what with_parts does in enqueue_forward
+            if (a.w2) {
+                const int rc = launch_linear(B.L, FL_DTYPE_BF16, w2d, xn, nullptr, y2, T, N2w, N, a.epi2, inv);
+                B.L.rsp = RsParts{};
+                FL_TRY(rc);
+            }
+            FL_HIP(hipStreamSynchronize(B.s));
+            unsigned char *o = (rep ? again : first).data();
+            FL_HIP(hipMemcpy(o, h, nh * 4, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(o + off_xn, xn, nh * 2, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(o + off_part, part, npart * 4, hipMemcpyDeviceToHost));
+            if (y2) FL_HIP(hipMemcpy(o + off_y2, y2, y2bytes, hipMemcpyDeviceToHost));
+            if (a.lazy && !a.w2) {                                   // nobody consumed the partial sums: the vector they finish into
+                FL_TRY(launch_rms_finalize(B.L, part, np, a.eps, inv, T, N));
+                FL_HIP(hipStreamSynchronize(B.s));
+            }
+            FL_HIP(hipMemcpy(o + off_inv, inv, (size_t)T * 4, hipMemcpyDeviceToHost));
+            if (rep && first != again) FL_FAIL(FL_ERR_HIP, "fl_op_linear_resid: launch %d gave another result than the first", rep);
+        }
+        memcpy(a.h_out, first.data(), nh * 4);
+        const bf16_t *xb = reinterpret_cast<const bf16_t *>(first.data() + off_xn);
+        for (size_t i = 0; i < nh; i++) a.xn_out[i] = bf16_bits_to_float(xb[i]);
+        memcpy(a.part_out, first.data() + off_part, npart * 4);
+        memcpy(a.inv_rms_out, first.data() + off_inv, (size_t)T * 4);
+        if (y2 && a.epi2 == EPI_GATEUP) {
+            const bf16_t *yb = reinterpret_cast<const bf16_t *>(first.data() + off_y2);
+            const int64_t I2 = a.N2 / 2;
+            for (int64_t t = 0; t < T; t++)
+                for (int64_t j = 0; j < I2; j++) a.y2_out[t * I2 + j] = bf16_bits_to_float(yb[t * I2p + j]);
+        } else if (y2) {
+            memcpy(a.y2_out, first.data() + off_y2, y2bytes);
+        }
+        return FL_OK;
     });
 }
 

@@ -163,6 +163,12 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
 #pragma unroll                                                              // does wait before the weights are requested
                         for (int u = 0; u < 7; u++)
                             if (s0 + u < a.delta_nslab) load8(a.delta + (size_t)(s0 + u) * K + c * 8, ds[u]);
+                        // slab by slab onto the residual, ((x + d0) + d1) + ... -- the order rmsnorm_add and the batched stream
+                        // sum slabs in, so that the same slabs give the same residual bits on every path
+                        if (s0 == 1) {
+#pragma unroll
+                            for (int j = 0; j < 8; j++) dl[i][j] = v[i][j] + dl[i][j];
+                        }
 #pragma unroll
                         for (int u = 0; u < 7; u++)
                             if (s0 + u < a.delta_nslab) {
@@ -182,8 +188,9 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
             const int c = tid + nthr * i;
             if (c < nchunk) {
                 if (a.delta) {
+                    const bool folded = a.delta_nslab > 1;               // (several slabs: dl already holds x + their sum, above)
 #pragma unroll
-                    for (int j = 0; j < 8; j++) v[i][j] += dl[i][j];
+                    for (int j = 0; j < 8; j++) v[i][j] = folded ? dl[i][j] : v[i][j] + dl[i][j];
                 }
                 float o[8];
 #pragma unroll

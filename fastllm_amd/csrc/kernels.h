@@ -78,7 +78,7 @@ struct GemvArgs {
     int N = 0, K = 0, epi = EPI_F32, pro = PRO_X;
     // PRO_NORM: x = rmsnorm(x_in + delta) * norm_w, or of the embedding row of st->token
     const float *x_in = nullptr, *delta = nullptr, *norm_w = nullptr;
-    int delta_nslab = 1;            // delta is the sum of this many [K] vectors, K floats apart (the fused attention + o_proj launch leaves one per kv head)
+    int delta_nslab = 1;            // delta is this many [K] vectors, K floats apart, added to x_in one by one in order (the fused attention + o_proj launch leaves one per kv head)
     float eps = 0.f;
     float *x_out = nullptr;         // updated residual, written by workgroup 0 (must differ from x_in)
     const void *embed = nullptr;    // [V,K] compute dtype, or null

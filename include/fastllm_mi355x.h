@@ -737,6 +737,77 @@ int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint
 int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
                   float *y, int32_t iters, double *ms_out);
 
+/* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
+
+/* launch_rmsnorm_add alone: x_res [T][h] fp32 (updated in place: += the n_slab slabs of delta, summed in slab order), delta
+ * [n_slab][T][h] fp32 (NULL with n_slab 0: x_res stays as it is), w [h] fp32.  xs_out [T][h] = x_res * w in `dtype`, widened to
+ * fp32; inv_rms_out [T] = 1 / sqrt(mean(x_res^2) + eps).  h a multiple of 8; 0 <= n_slab <= 64. */
+int fl_op_rmsnorm_add(float *x_res, const float *delta, int32_t n_slab, const float *w, float eps, int64_t T, int64_t h, int32_t dtype,
+                      float *xs_out, float *inv_rms_out);
+
+/* Kernel codes in the kernels_out arrays of the two calls below (fastllm_amd/csrc/kernels.h, enum LK_*). */
+enum {
+    FL_LK_NONE = 0, FL_LK_GEMV = 1, FL_LK_H4 = 2, FL_LK_W14 = 3, FL_LK_SKF = 4, FL_LK_DMA = 5, FL_LK_SKINNY = 6, FL_LK_8P = 7,
+    FL_LK_8P_STREAMK = 8, FL_LK_256 = 9, FL_LK_128 = 10, FL_LK_4W_ROPE = 11, FL_LK_GENERIC = 12, FL_LK_F32_ROWS = 13, FL_LK_F32_MFMA = 14
+};
+
+/* The norm and ONE projection behind it, in the form the caller names -- never another one: a form that cannot run the request
+ * returns FL_ERR_UNSUPPORTED.
+ *   form 0  launch_rmsnorm_add, then launch_linear with row_scale = 1/rms (any T, bf16 / f32; every fl_tune switch as fl_op_linear)
+ *   form 1  the single-sequence weight stream with its norm prologue (T = 1, bf16 / f32, K <= 6144)
+ *   form 2  the same over FP8 weights: w = e4m3fn bytes [N][K], w_scale [N] as fl_op_quantize_rows gives them (T = 1, bf16, n_slab <= 1)
+ *   form 3  the batched stream, T = B <= 8 rows, bf16; pro 0 runs its plain form on x instead of the norm
+ * The normed vector is v = x_res + the delta slabs, added slab by slab in slab order in every form, or row
+ * tokens[t] of embed when embed is given (x_res and delta NULL).  y [T][N] fp32, or [T][N/2] for epilogue 1 (w rows gate | up in HF
+ * order, no bias), the kernel's output widened; x_out [T][K] (or NULL) = v.  repeat launches (1..8) run on the same buffers:
+ * FL_ERR_HIP if one of them gives other bits.  kernels_out [4] (or NULL): form 0: {kernel, K slices, tail kernel, rest kernel} of the
+ * plan (FL_LK_*; FL_LK_DMA for the FL_OP_LINEAR_DMA route); form 3: {0, K slices, 0, 0}. */
+typedef struct fl_norm_linear_args {
+    size_t struct_size;             /* sizeof(fl_norm_linear_args) */
+    int32_t form, dtype, epilogue, pro;
+    int64_t T, N, K;
+    const float *x_res;             /* [T][K] fp32 */
+    const void *x;                  /* form 3, pro 0: [T][K] bf16 */
+    const float *delta;             /* [n_slab][T][K] fp32, or NULL */
+    const float *norm_w;            /* [K] fp32 */
+    const void *embed;              /* [vocab][K] in dtype, or NULL */
+    const uint32_t *tokens;         /* [T], with embed */
+    const void *w;                  /* [N][K] in dtype (form 2: e4m3fn bytes) */
+    const float *w_scale;           /* form 2: [N] */
+    const float *bias;              /* [N] or NULL */
+    int64_t vocab;
+    int32_t n_slab, repeat;
+    float eps, reserved;
+    float *y, *x_out;
+    int32_t *kernels_out;
+} fl_norm_linear_args;
+int fl_op_norm_linear(const fl_norm_linear_args *args);
+
+/* A projection with the residual epilogue (bf16): h = h_in + x . w^T (+bias), xn = bf16(h * w_next), partial sums of squares of h per
+ * row -- on the kernel plan_resid picks under the current switches (FL_ERR_UNSUPPORTED when it picks none) -- then 1/rms by
+ * launch_rms_finalize, or (lazy) left to the consumer as partial sums exactly as the forward pass leaves them.  The consumer
+ * (optional): y2 = (xn . w2^T) * 1/rms through launch_linear, epi2 0 -> y2 [T][N2], epi2 1 (w2 rows gate | up in HF order) -> [T][N2/2].
+ * h_out [T][N], xn_out [T][N] (widened), part_out [T][np] (np = 4 * ceil(N / 256)), inv_rms_out [T]: the finalized vector; lazy
+ * with a consumer: whatever the consumer left there (NaN where it read the partial sums itself); lazy without one: finalized after
+ * everything else was read.  repeat launches (1..8) run from the same h_in on the same buffers and workspaces: FL_ERR_HIP if one
+ * gives other bits.  kernels_out [6] (or NULL) = {kernel, K slices, tail kernel, tail K slices, consumer kernel, consumer reads the
+ * partial sums (0 / 1)} as FL_LK_* codes. */
+typedef struct fl_linear_resid_args {
+    size_t struct_size;             /* sizeof(fl_linear_resid_args) */
+    int64_t T, N, K, N2;
+    const void *x;                  /* [T][K] bf16 */
+    const void *w;                  /* [N][K] bf16 */
+    const float *bias;              /* [N] or NULL */
+    const float *h_in;              /* [T][N] fp32 */
+    const float *w_next;            /* [N] fp32 */
+    const void *w2;                 /* [N2][N] bf16, or NULL: no consumer */
+    float eps;
+    int32_t lazy, epi2, repeat;
+    float *h_out, *xn_out, *inv_rms_out, *part_out, *y2_out;
+    int32_t *kernels_out;
+} fl_linear_resid_args;
+int fl_op_linear_resid(const fl_linear_resid_args *args);
+
 /* The token-selection kernel alone, for unit tests: `n_draws` successive selections from one host logits
  * vector (consuming successive words of the seeded stream; ArgMax when temperature < 1e-7). */
 int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out);

@@ -203,6 +203,83 @@ pub struct fl_guide_desc {
     pub _reserved: [i64; 2],
 }
 
+// kernel codes in the kernels_out arrays of fl_op_norm_linear / fl_op_linear_resid
+pub const FL_LK_NONE: i32 = 0;
+pub const FL_LK_GEMV: i32 = 1;
+pub const FL_LK_H4: i32 = 2;
+pub const FL_LK_W14: i32 = 3;
+pub const FL_LK_SKF: i32 = 4;
+pub const FL_LK_DMA: i32 = 5;
+pub const FL_LK_SKINNY: i32 = 6;
+pub const FL_LK_8P: i32 = 7;
+pub const FL_LK_8P_STREAMK: i32 = 8;
+pub const FL_LK_256: i32 = 9;
+pub const FL_LK_128: i32 = 10;
+pub const FL_LK_4W_ROPE: i32 = 11;
+pub const FL_LK_GENERIC: i32 = 12;
+pub const FL_LK_F32_ROWS: i32 = 13;
+pub const FL_LK_F32_MFMA: i32 = 14;
+
+/// `fl_norm_linear_args`: residual add -> RMSNorm -> one projection in a named fused form (fl_op_norm_linear, unit tests);
+/// `struct_size` is `size_of::<fl_norm_linear_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_norm_linear_args {
+    pub struct_size: usize,
+    pub form: i32,
+    pub dtype: i32,
+    pub epilogue: i32,
+    pub pro: i32,
+    pub t: i64,
+    pub n: i64,
+    pub k: i64,
+    pub x_res: *const f32,
+    pub x: *const c_void,
+    pub delta: *const f32,
+    pub norm_w: *const f32,
+    pub embed: *const c_void,
+    pub tokens: *const u32,
+    pub w: *const c_void,
+    pub w_scale: *const f32,
+    pub bias: *const f32,
+    pub vocab: i64,
+    pub n_slab: i32,
+    pub repeat: i32,
+    pub eps: f32,
+    pub reserved: f32,
+    pub y: *mut f32,
+    pub x_out: *mut f32,
+    pub kernels_out: *mut i32,
+}
+
+/// `fl_linear_resid_args`: a projection with the residual + next-norm epilogue and, optionally, its consumer (fl_op_linear_resid,
+/// unit tests); `struct_size` is `size_of::<fl_linear_resid_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_linear_resid_args {
+    pub struct_size: usize,
+    pub t: i64,
+    pub n: i64,
+    pub k: i64,
+    pub n2: i64,
+    pub x: *const c_void,
+    pub w: *const c_void,
+    pub bias: *const f32,
+    pub h_in: *const f32,
+    pub w_next: *const f32,
+    pub w2: *const c_void,
+    pub eps: f32,
+    pub lazy: i32,
+    pub epi2: i32,
+    pub repeat: i32,
+    pub h_out: *mut f32,
+    pub xn_out: *mut f32,
+    pub inv_rms_out: *mut f32,
+    pub part_out: *mut f32,
+    pub y2_out: *mut f32,
+    pub kernels_out: *mut i32,
+}
+
 /// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -640,6 +717,20 @@ extern "C" {
         iters: i32,
         ms_out: *mut f64,
     ) -> c_int;
+    pub fn fl_op_rmsnorm_add(
+        x_res: *mut f32,
+        delta: *const f32,
+        n_slab: i32,
+        w: *const f32,
+        eps: f32,
+        t: i64,
+        h: i64,
+        dtype: i32,
+        xs_out: *mut f32,
+        inv_rms_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_norm_linear(args: *const fl_norm_linear_args) -> c_int;
+    pub fn fl_op_linear_resid(args: *const fl_linear_resid_args) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;
