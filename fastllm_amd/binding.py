@@ -329,6 +329,9 @@ def lib():
                                           C.POINTER(sz), C.POINTER(FlSpecStats)]
         L.fl_op_verify_sample.argtypes = [vp, C.c_int64, C.c_int64, vp, C.POINTER(FlSampler), vp, C.POINTER(C.c_int64), vp]
         L.fl_op_verify_sample_time.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(FlSampler), vp, vp]
+        L.fl_batch_verify.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.fl_batch_decode_lookup.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(FlLookup), vp, vp, vp, vp]
+        L.fl_op_verify_packed.argtypes = [vp, C.c_int64, C.c_int64, sz, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_copy_prefix.argtypes = [vp, vp, sz]
         L.fl_op_kv_copy.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
         L.fl_encoder_create.argtypes = [C.POINTER(FlEncoderConfig), C.POINTER(FlTensor), sz, C.c_int32, C.c_int32, C.POINTER(vp)]
@@ -397,6 +400,43 @@ def op_verify_sample(logits, draft, temperature, seed=0, draws_done=0, top_p=Non
     _check(lib().fl_op_verify_sample(a.ctypes.data, T, V, d.ctypes.data if d.size else None, C.byref(sp), out.ctypes.data, C.byref(n),
                                      kept.ctypes.data if return_kept else None))
     return (out, n.value, kept) if return_kept else (out, n.value)
+
+
+def _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done):
+    """an fl_sampler array for n members out of per-member lists (None, or a None entry: ArgMax / 0 / off), or None: ArgMax for all"""
+    if temperatures is None and top_p is None and top_k is None:
+        return None
+    spx = (FlSampler * max(n, 1))()
+    for i in range(n):
+        t = temperatures[i] if temperatures is not None and temperatures[i] is not None else 0.0
+        spx[i] = make_sampler(t, seeds[i] if seeds is not None and seeds[i] is not None else 0,
+                              draws_done[i] if draws_done is not None and draws_done[i] is not None else 0,
+                              top_p[i] if top_p is not None else None, top_k[i] if top_k is not None else None)
+    return spx
+
+
+def op_verify_packed(logits, members, temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None, block_rows=0, return_kept=False,
+                     iters=0):
+    """The packed verify step's selection kernel alone: logits [T, V] float32; members: one id list [token, *draft] per member, their
+    rows back to back; per-member sampler lists as in Model.verify_packed (None: ArgMax).  The rows are cut into launches of block_rows
+    rows (0: one).  Returns (tokens uint32 [T], n_accepted int64 [n]), + kept int64 [T] with return_kept, + ms per pass with iters > 0."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    ms_ = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in members]
+    n = len(ms_)
+    ids = np.ascontiguousarray(np.concatenate(ms_), dtype=np.uint32)
+    offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.size for x in ms_])]), dtype=np.uint64)
+    assert ids.size == T
+    spx = _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done)
+    out = np.zeros(T, dtype=np.uint32)
+    acc = np.full(n, -1, dtype=np.int64)
+    kept = np.zeros(T, dtype=np.int64)
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_verify_packed(a.ctypes.data, T, V, n, offsets.ctypes.data, ids.ctypes.data, C.cast(spx, C.c_void_p) if spx is not None else None,
+                                     int(block_rows), out.ctypes.data, acc.ctypes.data, kept.ctypes.data if return_kept else None, int(iters),
+                                     C.byref(ms)))
+    res = (out, acc) + ((kept,) if return_kept else ())
+    return res + (ms.value,) if iters > 0 else res
 
 
 def op_verify_sample_time(logits, temperature, iters, seed=0, top_p=None, top_k=None):
@@ -718,6 +758,59 @@ class Model:
         if return_stats:
             return toks[: n.value], dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted)
         return toks[: n.value]
+
+    def verify_packed(self, caches, tokens, drafts, pos, temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None, want_logits=False):
+        """fl_batch_verify: the verify steps [tokens[i], *drafts[i]] of caches[i] at RoPE offset pos[i], all in ONE forward.  Per member
+        the result of forward_verify(caches[i], tokens[i], drafts[i], pos[i], ..): temperatures / seeds / top_p / top_k / draws_done are
+        lists (None, or a None entry: ArgMax / 0 / off / 0).  Returns a list of per-member id arrays -- the accepted drafts followed by
+        the model's own next token -- or (that list, logits [total rows, V] in pack order) with want_logits."""
+        n = len(caches)
+        assert len(tokens) == n and len(drafts) == n
+        ms = [np.concatenate([[int(tokens[i])], np.asarray(drafts[i], dtype=np.uint32).reshape(-1)]).astype(np.uint32) for i in range(n)]
+        ids = np.ascontiguousarray(np.concatenate(ms) if ms else np.zeros(0, np.uint32), dtype=np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.size for x in ms])]), dtype=np.uint64)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        assert pos.shape == (n,)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        spx = _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done)
+        toks = np.zeros(max(ids.size, 1), dtype=np.uint32)
+        cnt = np.zeros(max(n, 1), dtype=np.uint64)
+        lg = np.empty((ids.size, self.V), dtype=np.float32) if want_logits else None
+        _check(lib().fl_batch_verify(self._h, C.cast(arr, C.c_void_p), n, ids.ctypes.data, offsets.ctypes.data, pos.ctypes.data,
+                                     C.cast(spx, C.c_void_p) if spx is not None else None, toks.ctypes.data, cnt.ctypes.data,
+                                     lg.ctypes.data if want_logits else None))
+        got = [toks[int(offsets[i]): int(offsets[i]) + int(cnt[i])].copy() for i in range(n)]
+        return (got, lg) if want_logits else got
+
+    def decode_lookup_packed(self, caches, corpora, first_tokens, pos, n_steps, eos=None, max_draft=7, ngram_max=3, ngram_min=1,
+                             temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None, return_stats=False):
+        """fl_batch_decode_lookup: decode_lookup for every member, each iteration ONE packed verify step over the unfinished members.
+        corpora / first_tokens / pos / n_steps: one entry per member; eos: a list (None or a negative entry: none).  Returns a list of
+        per-member id arrays, or (that list, [dict(steps, drafted, accepted)] per member) with return_stats."""
+        n = len(caches)
+        cps = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in corpora]
+        assert len(cps) == n and len(first_tokens) == n and len(pos) == n and len(n_steps) == n
+        corpus = np.ascontiguousarray(np.concatenate(cps) if cps else np.zeros(0, np.uint32), dtype=np.uint32)
+        coff = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.size for x in cps])]), dtype=np.uint64)
+        first = np.ascontiguousarray(first_tokens, dtype=np.uint32)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        steps = np.ascontiguousarray(n_steps, dtype=np.uint64)
+        eos_a = None if eos is None else np.ascontiguousarray([-1 if e is None else e for e in eos], dtype=np.int64)
+        stride = int(steps.max()) if n else 0
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        spx = _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done)
+        o = make_lookup(max_draft, ngram_max, ngram_min)
+        toks = np.zeros((max(n, 1), max(stride, 1)), dtype=np.uint32)
+        cnt = np.zeros(max(n, 1), dtype=np.uint64)
+        st = (FlSpecStats * max(n, 1))()
+        _check(lib().fl_batch_decode_lookup(self._h, C.cast(arr, C.c_void_p), n, corpus.ctypes.data if corpus.size else None, coff.ctypes.data,
+                                            first.ctypes.data, pos.ctypes.data, steps.ctypes.data, eos_a.ctypes.data if eos_a is not None else None,
+                                            C.byref(o), C.cast(spx, C.c_void_p) if spx is not None else None, toks.ctypes.data, cnt.ctypes.data,
+                                            C.cast(st, C.c_void_p)))
+        got = [toks[i, : int(cnt[i])].copy() for i in range(n)]
+        if return_stats:
+            return got, [dict(steps=st[i].steps, drafted=st[i].drafted, accepted=st[i].accepted) for i in range(n)]
+        return got
 
     def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None, logprobs=None):
         """logprobs = N (0: the chosen token's only): returns (token, token_logprob [1], top_ids [1, N], top_logprobs [1, N]) --

@@ -377,6 +377,20 @@ int fl_batch_prefill(fl_model *m, fl_cache *const *caches, size_t n, const uint3
         return batch_prefill(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, samplers, tokens_out, logits_out);
     });
 }
+int fl_batch_verify(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                    const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return batch_verify(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, samplers, tokens_out, n_out, logits_out);
+    });
+}
+int fl_batch_decode_lookup(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets,
+                           const uint32_t *first_tokens, const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts,
+                           const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return guarded([&]() -> int {
+        return batch_decode_lookup(M(m), reinterpret_cast<Cache *const *>(caches), n, corpus, corpus_offsets, first_tokens, pos, n_steps, eos, opts,
+                                   samplers, tokens_out, n_out, stats);
+    });
+}
 int fl_batch_decode(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, int64_t eos,
                     const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {

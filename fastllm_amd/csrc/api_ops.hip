@@ -297,6 +297,82 @@ int fl_op_verify_sample_time(const float *logits, int64_t T, int64_t V, const fl
     });
 }
 
+int fl_op_verify_packed(const float *logits, int64_t T, int64_t V, size_t n_seq, const size_t *offsets, const uint32_t *ids, const fl_sampler *samplers,
+                        int64_t block_rows, uint32_t *tokens_out, int64_t *n_acc_out, int64_t *kept_out, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!logits || !offsets || !ids || !tokens_out || !n_acc_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: null argument");
+        if (T < 1 || T > kVerifyPackedMaxRows || V <= 0 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: bad size (1 <= T <= %d)", kVerifyPackedMaxRows);
+        if (n_seq < 1 || n_seq > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: n_seq %zu not in 1..%d", n_seq, kMaxBatch);
+        if (block_rows < 0 || iters < 0 || iters > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: negative block_rows or a bad iteration count");
+        if (offsets[0] != 0 || offsets[n_seq] != (size_t)T) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: offsets must run from 0 to T");
+        std::vector<PackedRow> rows;
+        std::vector<int> off(n_seq), cnt(n_seq);
+        std::vector<SampleState> ss(n_seq);
+        bool any_sampled = false;
+        for (size_t s = 0; s < n_seq; s++) {
+            if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > (size_t)kVerifyMaxRows || offsets[s + 1] > (size_t)T)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: member %zu must have 1..%d rows", s, kVerifyMaxRows);
+            off[s] = (int)offsets[s]; cnt[s] = (int)(offsets[s + 1] - offsets[s]);
+            for (int t = 0; t < cnt[s]; t++) rows.push_back(PackedRow{(int)s, t});
+            FL_TRY(make_sampler(samplers ? samplers + s : nullptr, V, &ss[s]));
+            any_sampled |= ss[s].on != 0;
+        }
+        for (int64_t r = 0; r < T; r++) if ((int64_t)ids[r] >= V) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_packed: ids[%lld] = %u is not below V = %lld", (long long)r, ids[r], (long long)V);
+        const int64_t R = block_rows == 0 ? T : std::min<int64_t>(block_rows, T);
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg, *sc = nullptr; uint32_t *od, *kd;
+        VerifyPackedArgs a;
+        FL_TRY(B.upload(&lg, logits, (size_t)T * V * 4));
+        if (any_sampled) FL_TRY(B.alloc(&sc, (size_t)R * V * 4));
+        PackedRow *rd; int *ofd, *cnd; SampleState *ssd; uint32_t *idd;
+        FL_TRY(B.upload(&rd, rows.data(), rows.size() * sizeof(PackedRow)));
+        FL_TRY(B.upload(&ofd, off.data(), n_seq * 4));
+        FL_TRY(B.upload(&cnd, cnt.data(), n_seq * 4));
+        FL_TRY(B.upload(&ssd, ss.data(), n_seq * sizeof(SampleState)));
+        FL_TRY(B.upload(&idd, ids, (size_t)T * 4));
+        FL_TRY(B.alloc(&od, (size_t)kVerifyPackedWords * 4));
+        FL_TRY(B.alloc(&kd, (size_t)T * 4));
+        FL_HIP(hipMemset(od, 0, (size_t)kVerifyPackedWords * 4));
+        a.rows = rd; a.seq_off = ofd; a.seq_cnt = cnd; a.ss = ssd; a.ids = idd; a.out = od; a.kept = kd;
+        auto pass = [&]() -> int {
+            for (int64_t r0 = 0; r0 < T; r0 += R) {
+                const int64_t n = std::min<int64_t>(R, T - r0);
+                FL_TRY(launch_verify_packed(B.L, lg + (size_t)r0 * V, V, (int)r0, (int)n, (int)T, a, sc, any_sampled));
+            }
+            return FL_OK;
+        };
+        std::vector<uint32_t> host[2], kept[2];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the second pass meets the ticket words the first one put back
+            host[rep].resize(kVerifyPackedWords); kept[rep].resize((size_t)T);
+            FL_HIP(hipMemsetAsync(kd, 0, (size_t)T * 4, B.s));
+            FL_TRY(pass());
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep].data(), od, (size_t)kVerifyPackedWords * 4, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(kept[rep].data(), kd, (size_t)T * 4, hipMemcpyDeviceToHost));
+        }
+        if (host[0] != host[1] || kept[0] != kept[1]) FL_FAIL(FL_ERR_HIP, "verify_packed: a repeated pass gave another result");
+        for (size_t s = 0; s < n_seq; s++)
+            if (host[1][kVerifyPackedTicket + s] != 0 || host[1][kVerifyPackedNacc + s] >= (uint32_t)cnt[s])
+                FL_FAIL(FL_ERR_HIP, "verify_packed: member %zu ended with ticket %u, accepted count %u", s, host[1][kVerifyPackedTicket + s], host[1][kVerifyPackedNacc + s]);
+        for (int64_t t = 0; t < T; t++) tokens_out[t] = host[0][t];
+        if (kept_out) for (int64_t t = 0; t < T; t++) kept_out[t] = (int64_t)kept[0][t];
+        for (size_t s = 0; s < n_seq; s++) n_acc_out[s] = (int64_t)host[0][kVerifyPackedNacc + s];
+        if (iters > 0 && ms_out) {
+            FL_TRY(pass());                                     // warm
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+            FL_HIP(hipEventRecord(B.e0, B.s));
+            for (int i = 0; i < iters; i++) FL_TRY(pass());
+            FL_HIP(hipEventRecord(B.e1, B.s));
+            FL_HIP(hipEventSynchronize(B.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+            *ms_out = ms / iters;
+        }
+        return FL_OK;
+    });
+}
+
 int fl_op_logprobs(const float *logits, int64_t T, int64_t V, const uint32_t *chosen, int32_t top_n, float *token_logprob,
                    uint32_t *top_ids, float *top_logprobs) {
     return guarded([&]() -> int {

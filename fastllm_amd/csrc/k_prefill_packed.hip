@@ -80,7 +80,8 @@ PackedTable PackedHost::at(const void *dev_base) const {
     return t;
 }
 
-void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, int n, int64_t H, int64_t Hkv, int64_t d, PackedHost *out) {
+void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, int n, int64_t H, int64_t Hkv, int64_t d, PackedHost *out,
+                        int pad_rows) {
     PackedHost &p = *out;
     std::vector<int> mfma_counts;
     for (int s = 0; s < n; s++) if (vt[s]) mfma_counts.push_back(counts[s]);
@@ -99,6 +100,7 @@ void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, in
         if (vt[s]) for (int t0 = 0; t0 < counts[s]; t0 += 16 * p.TT) items.push_back(PackedItem{s, t0});
     }
     p.T_total = (int)rows.size(); p.n_items = (int)items.size();
+    for (int r = 0; r < pad_rows && !rows.empty(); r++) rows.push_back(rows[(size_t)p.T_total - 1]);
     p.off_seqs = 0;
     p.off_rows = sizeof(SeqRef) * (size_t)n;
     p.off_items = p.off_rows + sizeof(PackedRow) * rows.size();

@@ -260,7 +260,10 @@ struct PackedHost {
     int n_seq = 0, n_items = 0, T_total = 0, TT = 1, ks = 1;
     PackedTable at(const void *dev_base) const;           // the table of this image once it lies at dev_base
 };
-void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, int n, int64_t H, int64_t Hkv, int64_t d, PackedHost *out);
+// pad_rows: that many copies of the last row's entry behind the rows (fl_batch_verify's one-row pack); they belong to no member's count
+// and to no attention item
+void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, int n, int64_t H, int64_t Hkv, int64_t d, PackedHost *out,
+                        int pad_rows = 0);
 // dst [n_slab][n_seq][h] = the sequences' last rows of src [n_slab][..][h] (slabs src_slab / dst_slab floats apart)
 int launch_gather_last_rows(Launcher &L, const float *src, const PackedTable &tb, float *dst, int n_seq, int64_t h, int n_slab, int64_t src_slab,
                             int64_t dst_slab);
@@ -417,6 +420,27 @@ int launch_verify_select(Launcher &L, const float *logits, int64_t V, int T, con
 // [T][V] floats; kept (device, or null): [T] what the top-p / top-k filter kept per row (V without one).
 int launch_verify_sample(Launcher &L, const float *logits, int64_t V, int T, const uint32_t *draft /* [T-1] device */, const SampleState &ss,
                          float *scratch, uint32_t *out, uint32_t *kept);
+// fl_batch_verify's selection (k_verify_packed.hip): the verify steps of up to 64 members, 1..16 rows each, as the rows of ONE pack of
+// T_total <= 1024 rows.  logits [R][V] holds rows r0 .. r0 + R of the pack (one lm_head block); row r is token rows[r].t of member
+// rows[r].seq and is selected as that member's SampleState says -- on == 0: ArgMax as launch_verify_select; else the draw of
+// launch_verify_sample with word (draw_hi:draw_lo) + t -- so one launch may mix the two.  Each member has its own acceptance scan and
+// ticket word in out, and a member whose rows straddle two launches is completed by the later one (same stream).
+// out: [0, T_total) the ids | [kVerifyPackedNacc + s] member s's accepted count | [kVerifyPackedAux ..) free for the caller (the
+// members' error words, fl_batch_verify) | [kVerifyPackedTicket + s] its ticket; kVerifyPackedWords words, zero before the FIRST launch.
+constexpr int kVerifyPackedMaxRows = 1024, kVerifyPackedNacc = 1024, kVerifyPackedAux = 1088, kVerifyPackedTicket = 1216, kVerifyPackedWords = 1280;
+struct VerifyPackedArgs {                // every pointer is device memory
+    const PackedRow *rows = nullptr;     // [T_total]
+    const int *seq_off = nullptr;        // [n_seq] a member's first row
+    const int *seq_cnt = nullptr;        // [n_seq] its rows, 1..16
+    const SampleState *ss = nullptr;     // member s's state lies s * ss_stride BYTES behind this one (an array of SampleState or of PackedSeqInit)
+    size_t ss_stride = sizeof(SampleState);
+    const uint32_t *ids = nullptr;       // [T_total] the pack's ids: a member's token, then its draft
+    uint32_t *out = nullptr;
+    uint32_t *kept = nullptr;            // [T_total] or null: what the top-p / top-k filter kept per row (V without one, and for ArgMax rows)
+};
+// scratch: [R][V] floats, needed (any_sampled) when a member of the pack samples
+int launch_verify_packed(Launcher &L, const float *logits, int64_t V, int r0, int R, int T_total, const VerifyPackedArgs &a, float *scratch,
+                         bool any_sampled);
 // fl_*_lp: log-softmax (temperature 1, no mask) of `rows` logits rows [rows][V], one workgroup per row -- the chosen token's and the
 // first top_n of "logit descending, lower index first" -- into record `step - advance` of the row's LogprobCtl.  Who a row belongs to:
 //   st + ctl      one sequence (rows == 1): the token select_advance just left in st

@@ -86,6 +86,12 @@ struct PackedScratch {
     float *logits = nullptr;                       // [n][V]
     uint32_t *result = nullptr;                    // [64][2] the members' tokens and error words, gathered for one copy
     uint32_t *host_result = nullptr;               // ... pinned
+    // fl_batch_verify: the selection launches' block (launch_verify_packed: ids, accepted counts, the members' error words, tickets;
+    // zeroed once at allocation; memset again only on a failed call's way out), its pinned image, and -- allocated at a model's first SAMPLED
+    // packed verify, regrown with the score_rows switch, counted in hbm_bytes -- the rows' probabilities [verify_prob_R][V]
+    uint32_t *verify_out = nullptr;
+    uint32_t *host_verify = nullptr;
+    float *verify_prob = nullptr; int64_t verify_prob_R = 0;
     std::vector<void *> allocs;
 };
 
@@ -337,8 +343,14 @@ struct AllRows {
     float *out;
     int64_t R;
     std::function<int(Launcher &, int64_t r0, int64_t n)> each;
+    // never leave a one-row last block where R >= 3 allows it (the block before it gives up a row): a one-row lm_head launch is the
+    // planner's T = 1 kernel, another summation order than the rows of every other block see
+    bool no_one_row_tail = false;
 };
 int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows);
+// the model's [R][V] fp32 block scratch of such a forward (ScoreScratch::rows; R: the score_rows switch now), allocated -- or regrown,
+// after waiting for the stream -- by whichever call needs it first: the scoring calls and fl_batch_verify share it
+int score_block_scratch(Model *m, Shard &sh, float **rows, int64_t *R);
 // One scoring call's rows -> records (shared by the single and the packed path): begin sizes the model's buffers for T rows and
 // sends the targets (tg[T], kScoreNoTarget: none); sink() is the AllRows of a forward whose row 0 is row `row0` of the call, one
 // score_rows launch (and, with logits_out, one copy of the block) per lm_head block; one() scores a single row another buffer
@@ -388,6 +400,14 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
 int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
                   const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling = nullptr);
 int check_lookup(const fl_lookup *opts);     // FL_ERR_BAD_ARGUMENT: null, wrong struct_size, a range error
+// what a verify step may and may not be asked of one cache (sizes, room, tensor parallelism, the sliding window): no device needed
+int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos);
+// fl_batch_verify / fl_batch_decode_lookup (prefill_packed.hip): the verify steps of n streams as the rows of one packed forward
+int batch_verify(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                 const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, float *logits_out);
+int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
+                        const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
+                        uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
 
 // most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (weights.hip)
 constexpr int kMaxKSplit = 4;

@@ -533,8 +533,9 @@ ResidEpi resid_epi(const Scratch &sc, const Dims &D, const float *next_norm_w) {
 // (if any) is enqueued behind every block, before the next one overwrites it
 int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows) {
     const Dims &D = m->D;
-    for (int64_t r0 = 0; r0 < T; r0 += rows.R) {
-        const int64_t n = std::min<int64_t>(rows.R, T - r0);
+    for (int64_t r0 = 0, n = 0; r0 < T; r0 += n) {
+        n = std::min<int64_t>(rows.R, T - r0);
+        if (rows.no_one_row_tail && T - r0 - n == 1 && n > 2) n -= 1;
         FL_TRY(launch_linear(L, m->dtype, sh.lm_head, (char *)sc.xn + (size_t)r0 * D.h * m->esize(), nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
         if (rows.each) FL_TRY(rows.each(L, r0, n));
     }
@@ -1181,19 +1182,28 @@ static int score_supported(const Model *m) {
 static int score_block_rows() { return std::max(1, std::min(1024, tune(TK_SCORE_ROWS))); }
 
 // (never inside a stream capture: the model is locked and scoring launches eagerly)
-int ScoreCall::begin(const uint32_t *tg) {
+int score_block_scratch(Model *m, Shard &sh, float **rows, int64_t *R_out) {
     ScoreScratch &ss = sh.score;
     const int64_t R = score_block_rows(), V = m->D.V;
-    FL_HIP(hipSetDevice(sh.device));
-    if (ss.cap_R < R || ss.cap_T < T) FL_HIP(hipStreamSynchronize(sh.stream));           // (idle anyway: every call ends with a synchronise)
     if (ss.cap_R < R) {
+        FL_HIP(hipStreamSynchronize(sh.stream));                                         // (idle anyway: every call ends with a synchronise)
         if (ss.rows) { (void)hipFree(ss.rows); ss.rows = nullptr; }
         m->hbm_bytes -= ss.cap_R * V * 4; ss.bytes -= ss.cap_R * V * 4; ss.cap_R = 0;
         std::vector<void *> own;
         FL_TRY(dev_alloc(own, (void **)&ss.rows, (size_t)(R * V) * 4, nullptr));
         m->hbm_bytes += R * V * 4; ss.bytes += R * V * 4; ss.cap_R = R;
     }
+    if (rows) *rows = ss.rows;
+    if (R_out) *R_out = R;
+    return FL_OK;
+}
+
+int ScoreCall::begin(const uint32_t *tg) {
+    ScoreScratch &ss = sh.score;
+    FL_HIP(hipSetDevice(sh.device));
+    FL_TRY(score_block_scratch(m, sh, nullptr, nullptr));
     if (ss.cap_T < T) {
+        FL_HIP(hipStreamSynchronize(sh.stream));                                         // (idle anyway: every call ends with a synchronise)
         const size_t per = 4 + sizeof(ScoreRec);
         if (ss.targets) (void)hipFree(ss.targets);
         if (ss.recs) (void)hipFree(ss.recs);
@@ -1363,7 +1373,7 @@ int check_lookup(const fl_lookup *o) {
 }
 
 // what a verify step may and may not be asked: everything here is decided before the device is touched
-static int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos) {
+int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos) {
     if (n_draft > FL_VERIFY_MAX_DRAFT) FL_FAIL(FL_ERR_BAD_ARGUMENT, "n_draft %zu exceeds FL_VERIFY_MAX_DRAFT (%d)", n_draft, FL_VERIFY_MAX_DRAFT);
     FL_TRY(check_call(m, c, n_draft + 1, pos));
     if (n_draft > 0 && m->tp > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "the verify step does not run under tensor parallelism (tp_size %d)", m->tp);

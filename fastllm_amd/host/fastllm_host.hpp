@@ -1209,6 +1209,16 @@ struct PackedAdmit {
     bool on = false; size_t max_prompt = 256; size_t max_tokens = 2048;
 };
 
+// StreamBatcher option: on == false (default) is the batcher exactly as before.  With `on`, every step() drafts for each active
+// stream from prompt ++ emitted (fl_lookup_draft; the limit covers the stream's remaining max_tokens, its slot's capacity and the
+// model's sliding window), and when no active stream has logit rules or a guide and at least min_drafted ids were drafted in all, the
+// step is ONE fl_batch_verify over the active slots -- every stream advances by its accepted drafts + 1 for one read of the weights --
+// instead of a chunk of one-token steps.  Per stream the tokens are those of the plain batcher: ArgMax, or the seeded stream with the
+// word of each token's index (fl_forward_verify_ex's GUARANTEE).  Where nothing was drafted the step is the existing chunk.
+struct BatchLookup {
+    bool on = false; LookupOptions lookup; size_t min_drafted = 1;
+};
+
 // ------------------------------------------------------------------------------------ concurrent streams, one batched loop
 // The reference serves concurrent requests as independent tasks (ModelWrapper::generate_stream spawns one loop per stream,
 // mod.rs:137-238), each paying for the whole weight read per token.  StreamBatcher gives the same streams ONE decode loop
@@ -1229,6 +1239,9 @@ struct PackedAdmit {
 //
 // With PackedAdmit.on the admissions of one step() share forwards (fl_batch_prefill); per stream the tokens are those of the single
 // admission (the same logits up to fp32 summation order), and every counter but packed_calls / prefill_calls keeps its value.
+//
+// With BatchLookup.on a step with drafts is one packed verify step (fl_batch_verify) over the active slots; verify_steps / drafted /
+// accepted count them.  Refused together with counter_positions, like the prefix store: a verify step's rows sit at token positions.
 class StreamBatcher {
   public:
     using OnToken = std::function<bool(uint32_t)>;
@@ -1238,13 +1251,26 @@ class StreamBatcher {
     // see in the reference (quirk C.1: mistral.rs:226,234, qwen.rs:142-143; PosMode::Reference); Llama streams and
     // FASTLLM_POS_MODE=tokens pass token positions
     StreamBatcher(std::shared_ptr<detail::ModelHandle> model, size_t slots, size_t max_seq = 0, size_t chunk = 8, bool counter_positions = false,
-                  PrefixOptions prefix = {}, PackedAdmit packed = {})
-        : model_(std::move(model)), chunk_(std::max<size_t>(1, chunk)), counter_(counter_positions), packed_(packed) {
+                  PrefixOptions prefix = {}, PackedAdmit packed = {}, BatchLookup lookup = {})
+        : model_(std::move(model)), chunk_(std::max<size_t>(1, chunk)), counter_(counter_positions), packed_(packed), lookup_(lookup) {
         if (!model_ || !model_->m) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: no model");
         if (slots < 1 || slots > 64) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: 1 ... 64 slots");
         if (prefix.entries > 0 && counter_)
             throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: a prefix store needs token positions (with call-counter RoPE offsets a result depends on how "
                                              "many calls produced the cache)");
+        if (lookup_.on && counter_)
+            throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: batched prompt-lookup needs token positions (the rows of a verify step sit at token positions, "
+                                             "not at call-counter RoPE offsets)");
+        if (lookup_.on) {
+            const fl_lookup o = lookup_.lookup.to_ffi();
+            size_t nd = 0;
+            check(fl_lookup_draft(nullptr, 0, &o, 0, nullptr, &nd), "BatchLookup");     // the options' own range errors, now and not at the first step
+            fl_model_info info; check(fl_model_get_info(model_->m, &info), "fl_model_get_info");
+            // the resolved sliding window of a Mistral / Qwen2 model (none, or not positive: no limit), as fl_batch_decode_lookup takes it
+            draft_limit_ = info.cfg.family != FL_FAMILY_LLAMA && info.cfg.sliding_window > 0 ? (size_t)info.cfg.sliding_window : (size_t)-1;
+            vocab_ = (size_t)info.cfg.vocab_size;
+            max_pos_ = (size_t)std::max<int64_t>(0, info.cfg.max_position_embeddings);
+        }
         cap_ = max_seq ? max_seq : detail::default_max_seq(model_->m);
         if (cap_ < chunk_ + 1) throw Error(FL_ERR_BAD_ARGUMENT, "StreamBatcher: the caches are shorter than one chunk");
         slots_.resize(slots);
@@ -1304,6 +1330,7 @@ class StreamBatcher {
     size_t prefix_hits = 0, prefix_tokens_reused = 0;              // admissions that copied a stored prefix, and the positions they copied
     size_t prefill_calls = 0;                                      // forwards the admissions took (without PackedAdmit: == prefills)
     size_t packed_calls = 0;                                       // ... of them fl_batch_prefill calls
+    size_t verify_steps = 0, drafted = 0, accepted = 0;            // BatchLookup: packed verify steps, and the ids drafted / accepted in them
 
     // admit waiting requests into free slots, then one chunk for everybody; false: nothing active and nothing waiting
     bool step() {
@@ -1316,6 +1343,7 @@ class StreamBatcher {
             }
         }
         if (active() == 0) return !queue_.empty();
+        if (lookup_.on && verify_step()) return true;
         const size_t B = slots_.size();
         size_t n = chunk_, want = 0;
         for (auto &sl : slots_)
@@ -1342,6 +1370,7 @@ class StreamBatcher {
                 if (sl.emitted >= sl.req.max_tokens) { done = true; break; }
                 sl.emitted++;                                      // (tokens handed to the callback, the refused one included)
                 if (store_) sl.held.push_back(out[i * n + k]);
+                if (lookup_.on) sl.hist.push_back(out[i * n + k]);
                 if (!sl.req.on_token(out[i * n + k])) { done = true; break; }
             }
             if (!done && sl.emitted >= sl.req.max_tokens) done = true;
@@ -1366,7 +1395,73 @@ class StreamBatcher {
         bool ruled = false;                  // the cache has logit rules installed (removed in finish, or by the next admission)
         bool guided = false;                 // ... a guide
         std::vector<uint32_t> held;          // with a store: the prompt and every token handed to the callback
+        std::vector<uint32_t> hist;          // with BatchLookup: the same ids, the text the drafts are looked up in
     };
+
+    // BatchLookup: draft for every active slot; false (and nothing done) when the step has to be the plain chunk -- a ruled or guided
+    // stream is active, or fewer than min_drafted ids were drafted in all.  Otherwise ONE fl_batch_verify over the active slots and the
+    // plain step's bookkeeping per returned id: an EOS, max_tokens or a refused callback finishes the slot and drops the ids behind it.
+    bool verify_step() {
+        const fl_lookup o = lookup_.lookup.to_ffi();
+        std::vector<Slot *> who;
+        std::vector<fl_cache *> caches;
+        std::vector<uint32_t> ids;
+        std::vector<size_t> offsets{0}, pos;
+        std::vector<fl_sampler> sp;
+        size_t total = 0;
+        for (auto &sl : slots_) {
+            if (!sl.active) continue;
+            if (sl.ruled || sl.guided) return false;
+            // room: this step caches the slot's token and its drafts, and hands back at most one id more than it drafted
+            size_t limit = std::min(sl.req.max_tokens - sl.emitted, cap_ - sl.pos) - 1;
+            limit = std::min(limit, draft_limit_);
+            limit = std::min(limit, max_pos_ > sl.pos ? max_pos_ - sl.pos - 1 : 0);     // ... and every row needs a RoPE position
+            uint32_t draft[FL_VERIFY_MAX_DRAFT + 1];
+            size_t nd = 0;
+            check(fl_lookup_draft(sl.hist.data(), sl.hist.size(), &o, limit, draft, &nd), "fl_lookup_draft");
+            for (size_t k = 0; k < nd; k++) if (draft[k] >= vocab_) { nd = k; break; }      // (a prompt id the model does not have ends the draft)
+            who.push_back(&sl); caches.push_back(sl.cache);
+            ids.push_back(sl.tok);
+            ids.insert(ids.end(), draft, draft + nd);
+            offsets.push_back(ids.size());
+            pos.push_back(sl.pos);
+            sp.push_back(sl.req.opt.to_ffi((double)sl.req.temperature, sl.draws));
+            total += nd;
+        }
+        if (total < std::max<size_t>(lookup_.min_drafted, 1)) return false;
+        std::vector<uint32_t> out(ids.size(), 0);
+        std::vector<size_t> n_out(who.size(), 0);
+        check(fl_batch_verify(model_->m, caches.data(), caches.size(), ids.data(), offsets.data(), pos.data(), sp.data(), out.data(), n_out.data(), nullptr),
+              "Model forward pass failed");
+        verify_steps++; drafted += total;
+        for (size_t i = 0; i < who.size(); i++) accepted += n_out[i] - 1;
+        std::exception_ptr failed;                                 // a callback that throws does not keep the other streams from their ids
+        for (size_t i = 0; i < who.size(); i++) {
+            Slot &sl = *who[i];
+            const uint32_t *got = out.data() + offsets[i];
+            const size_t n = n_out[i];
+            bool done = false;
+            try {
+                for (size_t k = 0; k < n; k++) {
+                    if (sl.req.eos && got[k] == *sl.req.eos) { done = true; break; }      // EOS is checked before the token is emitted
+                    if (sl.emitted >= sl.req.max_tokens) { done = true; break; }
+                    sl.emitted++;
+                    if (store_) sl.held.push_back(got[k]);
+                    sl.hist.push_back(got[k]);
+                    if (!sl.req.on_token(got[k])) { done = true; break; }
+                }
+                if (!done && sl.emitted >= sl.req.max_tokens) done = true;
+                sl.pos += n; sl.calls += n; sl.draws += n; sl.tok = got[n - 1];
+                if (!done && sl.pos >= cap_) done = true;           // the slot's cache is full: the stream ends here
+                if (done) finish(sl);
+            } catch (...) {
+                if (!failed) failed = std::current_exception();
+                if (sl.active) { try { finish(sl); } catch (...) {} }
+            }
+        }
+        if (failed) std::rethrow_exception(failed);
+        return true;
+    }
 
     // the slot becomes active only after its prefill succeeded: an exception leaves it free (and the request gone, see step())
     void admit(Slot &sl, Request r) {
@@ -1407,6 +1502,7 @@ class StreamBatcher {
         if (n) { prefix_hits++; prefix_tokens_reused += n; }
         sl.req = std::move(r); sl.active = true;
         if (store_) sl.held = sl.req.prompt;
+        if (lookup_.on) { sl.hist = sl.req.prompt; sl.hist.push_back(tok); }
         sl.pos = sl.req.prompt.size(); sl.calls = 1; sl.tok = tok; sl.draws = 1;
         if (sl.req.max_tokens == 0 || (sl.req.eos && tok == *sl.req.eos)) { finish(sl); return; }
         sl.emitted = 1;
@@ -1517,6 +1613,8 @@ class StreamBatcher {
     size_t chunk_, cap_ = 0;
     bool counter_ = false;
     PackedAdmit packed_;
+    BatchLookup lookup_;
+    size_t draft_limit_ = 0, vocab_ = 0, max_pos_ = 0;             // BatchLookup: the model's sliding window (none: no limit), vocabulary and max_position_embeddings
     std::unique_ptr<PrefixStore> store_;                           // null: no prefix reuse
     size_t reuse_limit_ = 0;
     std::vector<Slot> slots_;

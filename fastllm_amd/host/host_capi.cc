@@ -530,6 +530,34 @@ int flh_batcher_create_on_packed(void *fl_model_ptr, size_t slots, size_t max_se
         return 0;
     });
 }
+// ... with BatchLookup (a step with drafts is one fl_batch_verify over the active slots): flh_batcher_create_on plus the option's values;
+// lookup_on == 0 is flh_batcher_create_on
+int flh_batcher_create_on_lookup(void *fl_model_ptr, size_t slots, size_t max_seq, size_t chunk, int counter_positions, int lookup_on, int max_draft,
+                                 int ngram_max, int ngram_min, size_t min_drafted, void **out) {
+    return guard([&] {
+        if (!fl_model_ptr || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        fl_model *m = static_cast<fl_model *>(fl_model_ptr);
+        fl_model_retain(m);
+        auto mh = std::make_shared<detail::ModelHandle>(m);          // (releases the reference)
+        auto bh = std::make_unique<BatcherHandle>();
+        BatchLookup bl; bl.on = lookup_on != 0; bl.lookup.max_draft = max_draft; bl.lookup.ngram_max = ngram_max; bl.lookup.ngram_min = ngram_min;
+        bl.min_drafted = min_drafted;
+        bh->b = std::make_unique<StreamBatcher>(mh, slots, max_seq, chunk, counter_positions != 0, PrefixOptions{}, PackedAdmit{}, bl);
+        *out = bh.release();
+        return 0;
+    });
+}
+// packed verify steps the batcher ran, and the ids drafted / accepted in them
+int flh_batcher_lookup_stats(void *bv, size_t *verify_steps, size_t *drafted, size_t *accepted) {
+    return guard([&] {
+        if (!bv) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        auto *bh = static_cast<BatcherHandle *>(bv);
+        if (verify_steps) *verify_steps = bh->b->verify_steps;
+        if (drafted) *drafted = bh->b->drafted;
+        if (accepted) *accepted = bh->b->accepted;
+        return 0;
+    });
+}
 // forwards the admissions took, and how many of them were packed calls
 int flh_batcher_packed_stats(void *bv, size_t *prefill_calls, size_t *packed_calls) {
     return guard([&] {

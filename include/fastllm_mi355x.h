@@ -374,6 +374,57 @@ int fl_decode_lookup_ex(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t
                         size_t n_steps, int64_t eos, const fl_lookup *opts, const fl_sampler *sampler /* or NULL */,
                         uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats /* or NULL */);
 
+/* ---- packed verify: the verify steps of n <= 64 streams in ONE forward ------------------------------------------------------------
+ * New capability: fl_forward_verify{,_ex} take one cache and read the weights once per stream; here the rows of every member's step
+ * are the rows of one packed forward (fl_batch_prefill's: member i is appended to its own cache at its own RoPE offset, the cached
+ * prefix unmasked, its new rows causal among themselves -- the mask of a verify step), the final norm and lm_head run on ALL rows in
+ * blocks of FL_SCORE_ROWS rows (fl_tune "score_rows"; a last block of one row is avoided where the switch is 3 or more: the block
+ * before it gives up a row), and one selection launch behind each block selects every row as its member's sampler says and scans
+ * every member's drafts (k_verify_packed.hip).
+ * Member i owns ids[offsets[i] .. offsets[i+1]) = [token, draft[0 .. n_draft_i)], n_draft_i <= FL_VERIFY_MAX_DRAFT.  Per member the
+ * result is that of fl_forward_verify_ex(m, caches[i], token, draft, n_draft_i, pos[i], &samplers[i], ..) in the sense of its
+ * GUARANTEE: every returned id is ArgMax, or this library's sampler with word draws_done_i + row, applied to this library's logits of
+ * the preceding ids evaluated as a row of a multi-row call; tokens_out[offsets[i] ..] holds a[0 .. n_acc_i], n_out[i] = n_acc_i + 1,
+ * the cache length becomes L_i + n_acc_i + 1, rejected rows' K/V stay behind the length.  Two differences: a member with n_draft_i == 0
+ * is a row of this packed forward, not the one-row decode step; EOS is not interpreted (as in the single call).
+ * WHAT A MEMBER'S RESULT DEPENDS ON.  Attention, RoPE and the K/V append see a member's own cache only.  The projections and lm_head
+ * are planned by ROW COUNT -- the pack's total rows, and for lm_head the block's -- and the planner changes kernel or K slicing (i.e.
+ * the fp32 summation order) at several counts: 1 -> 2, 32 -> 33 (wide gate/up), 128 -> 129, 256 / 512 / 768 .. in bf16, 64 -> 65 in
+ * fp32.  So: among packs, and among score_rows values, that the planner serves with the same kernels and K split, a member's ids,
+ * logits and cache contents are bit-identical wherever it sits and whoever its neighbours are; across such a threshold they are equal
+ * up to fp32 summation order -- logits differ in the last bits, and at a near-tie of the two largest (more often in bf16) so can an
+ * id: the GUARANTEE's sentence, nothing more.  Two thresholds are taken out: a pack of ONE row is forwarded as the row and a copy of
+ * it (a stream left alone in a batcher equals the same stream among a few others), and fp32 models keep lm_head blocks within the
+ * 2 .. 64 rows of one kernel (blocks capped at 64 rows, no one-row tail), so that there the score_rows switch changes nothing.
+ * samplers NULL: ArgMax for all; one pack may mix ArgMax and sampled members.  logits_out (or NULL): the raw rows in pack order,
+ * diagnostic -- one copy per block.  One host synchronisation per call; the ids and counts come back in one copy.
+ * Memory: the [FL_SCORE_ROWS][V] fp32 block scratch is the scoring calls' (allocated at whichever call comes first, counted in
+ * hbm_bytes_allocated: 33 MB at V = 32 000, 156 MB at V = 152 064 with the default 256 rows); a model's first SAMPLED packed verify
+ * allocates a probability scratch of the same size (another 33 MB / 156 MB).
+ * Refusals, all decided before the device or any cache is touched (a refused call modifies nothing; *n_out is zeroed):
+ *   FL_ERR_BAD_ARGUMENT  those of fl_batch_prefill (nulls, n outside 1..64, offsets[0] != 0 or an empty member, the same cache twice,
+ *                        a cache of another model, an id outside the vocabulary); a member with more than FL_VERIFY_MAX_DRAFT + 1
+ *                        rows; a sampler error (struct_size, a NaN top_p, a negative top_k); null tokens_out / n_out
+ *   FL_ERR_SEQ_OVERFLOW  per member, as fl_forward
+ *   FL_ERR_UNSUPPORTED   tp_size > 1; n_draft_i above the sliding window of a Mistral / Qwen2 model; a member with logit rules or a guide
+ * Not built: rules, guides and log-probs inside a packed verify, tensor parallelism, capturing the packed step in a graph. */
+int fl_batch_verify(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
+                    const size_t *pos /* [n] */, const fl_sampler *samplers /* [n] or NULL: ArgMax for all */,
+                    uint32_t *tokens_out /* [offsets[n]]: member i's ids at offsets[i] .. */, size_t *n_out /* [n] */,
+                    float *logits_out /* [offsets[n]][V] or NULL, diagnostic, the raw rows in pack order */);
+/* The loop of fl_decode_lookup_ex for n streams, built from packed verify steps.  Member i: search text corpus[corpus_offsets[i] ..
+ * corpus_offsets[i+1]), first_tokens[i] at RoPE offset pos[i], n_steps[i] tokens wanted, eos[i] (< 0: none; eos NULL: none for all),
+ * samplers[i] (NULL: ArgMax for all).  Per member it is fl_decode_lookup_ex in the GUARANTEE sense: the same drafting rule with the
+ * same limit, the same EOS rule (the EOS is not written, later ids of that step are dropped, the cache keeps the length the plain
+ * loop leaves), the same words (token k is drawn with word draws_done_i + k), the same room.  Each iteration drafts for every
+ * unfinished member, packs those members only and runs ONE fl_batch_verify step with one host synchronisation; a member that has
+ * its n_steps or its EOS leaves the pack.  opts->max_draft == 0 is allowed: every step is then a pack of one-row members.
+ * tokens_out: [n][max over i of n_steps[i]], row-major; n_out [n]; stats [n] or NULL.  Refusals: fl_batch_verify's and fl_lookup's. */
+int fl_batch_decode_lookup(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets /* [n+1] */,
+                           const uint32_t *first_tokens, const size_t *pos, const size_t *n_steps /* [n] */, const int64_t *eos /* [n] or NULL */,
+                           const fl_lookup *opts, const fl_sampler *samplers /* [n] or NULL */,
+                           uint32_t *tokens_out /* [n][max n_steps] */, size_t *n_out /* [n] */, fl_spec_stats *stats /* [n] or NULL */);
+
 /* Batched decode: B <= 64 caches of one model advanced together, one read of the weights per step for all
  * of them.  New capability: the reference runs concurrent streams as independent single-sequence loops
  * (mod.rs:137-238), each paying for the whole weight stream.  Every sequence keeps its own cache, RoPE
@@ -832,6 +883,19 @@ int fl_op_verify_sample(const float *logits /* [T][V] */, int64_t T, int64_t V, 
  * (0: that form is not run, ms_out[form] = 0). */
 int fl_op_verify_sample_time(const float *logits /* [T][V] */, int64_t T, int64_t V, const fl_sampler *sampler,
                              const int32_t *iters /* [2] */, double *ms_out /* [2] */);
+
+/* The selection kernel of fl_batch_verify alone, on host logits (unit tests, tools): a pack of n_seq members, member s = rows
+ * offsets[s] .. offsets[s+1] with ids [token, draft ..]; samplers[s] (NULL: ArgMax for all; temperature < 1e-7: ArgMax) selects its
+ * rows -- row i of a sampled member is what fl_op_sample_ex gives for that row with draws_done + i.  The rows are cut into launches
+ * of block_rows rows (0: one launch), so a member may straddle launches.  tokens_out[r]: row r's id; n_acc_out[s]: the largest
+ * j <= count_s - 1 with ids[offsets[s] + 1 + k] == tokens_out[offsets[s] + k] for all k < j; kept_out (or NULL): what each row's
+ * filter kept (V without one).  1 <= T <= 1024, 1 <= n_seq <= 64, members of 1 .. 16 rows, offsets[n_seq] == T, ids < V
+ * (FL_ERR_BAD_ARGUMENT otherwise, before the device is probed).  Everything runs twice on the same buffers: FL_ERR_HIP if the two
+ * results differ.  iters > 0 with ms_out: the launches of one pass timed between two events, ms per pass. */
+int fl_op_verify_packed(const float *logits /* [T][V] */, int64_t T, int64_t V, size_t n_seq, const size_t *offsets /* [n_seq+1] */,
+                        const uint32_t *ids /* [T] */, const fl_sampler *samplers /* [n_seq] or NULL */, int64_t block_rows /* 0: one launch */,
+                        uint32_t *tokens_out /* [T] */, int64_t *n_acc_out /* [n_seq] */, int64_t *kept_out /* [T] or NULL */,
+                        int32_t iters, double *ms_out);
 
 /* The log-prob kernel of the fl_*_lp calls alone, on host logits (unit tests, micro-benchmarks): row t's chosen token is chosen[t].
  * 1 <= T <= 64, 0 <= top_n <= min(FL_LOGPROBS_MAX_TOP, V), V <= 1 << 24, chosen[t] < V (FL_ERR_BAD_ARGUMENT otherwise, before the

@@ -504,6 +504,50 @@ extern "C" {
         n_out: *mut usize,
         stats: *mut fl_spec_stats,
     ) -> c_int;
+    /// The verify steps of up to 64 streams as the rows of one packed forward, and the lookup loop built from such steps.
+    pub fn fl_batch_verify(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        ids: *const u32,
+        offsets: *const usize,
+        pos: *const usize,
+        samplers: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        logits_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_batch_decode_lookup(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        corpus: *const u32,
+        corpus_offsets: *const usize,
+        first_tokens: *const u32,
+        pos: *const usize,
+        n_steps: *const usize,
+        eos: *const i64,
+        opts: *const fl_lookup,
+        samplers: *const fl_sampler,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        stats: *mut fl_spec_stats,
+    ) -> c_int;
+    pub fn fl_op_verify_packed(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        n_seq: usize,
+        offsets: *const usize,
+        ids: *const u32,
+        samplers: *const fl_sampler,
+        block_rows: i64,
+        tokens_out: *mut u32,
+        n_acc_out: *mut i64,
+        kept_out: *mut i64,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
 
     pub fn fl_batch_create(m: *mut fl_model, caches: *const *mut fl_cache, n: usize, out: *mut *mut fl_batch) -> c_int;
     pub fn fl_batch_destroy(b: *mut fl_batch);

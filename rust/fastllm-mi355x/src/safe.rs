@@ -443,6 +443,50 @@ impl Model {
         Ok(toks)
     }
 
+    /// `fl_batch_verify`: the verify steps `[tokens[i], drafts[i]..]` of `caches[i]` at RoPE offset `pos[i]`, all in ONE forward -- per
+    /// member the result of `forward_verify` / its sampled form (`None`: ArgMax; a sampler's `draws_done` is the member's own).  Returns
+    /// every member's ids: the accepted drafts followed by the model's own next token.  At most 64 members of at most 15 drafts each.
+    pub fn verify_packed(
+        &self,
+        caches: &mut [&mut Cache],
+        tokens: &[u32],
+        drafts: &[&[u32]],
+        pos: &[usize],
+        samplers: &[Option<Sampler>],
+    ) -> Result<Vec<Vec<u32>>> {
+        let n = caches.len();
+        if tokens.len() != n || drafts.len() != n || pos.len() != n || samplers.len() != n {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("packed verify of {} caches: every slice must have that length", n) });
+        }
+        let raws: Vec<*mut ffi::fl_cache> = caches.iter().map(|c| c.raw).collect();
+        let mut ids: Vec<u32> = Vec::new();
+        let mut offsets = vec![0usize; n + 1];
+        for i in 0..n {
+            ids.push(tokens[i]);
+            ids.extend_from_slice(drafts[i]);
+            offsets[i + 1] = ids.len();
+        }
+        let greedy = Sampler { temperature: 0.0, top_p: 0.0, top_k: 0, seed: 0, draws_done: 0 };
+        let sp: Vec<ffi::fl_sampler> = samplers.iter().map(|s| s.unwrap_or(greedy).to_ffi()).collect();
+        let mut toks = vec![0u32; ids.len().max(1)];
+        let mut counts = vec![0usize; n.max(1)];
+        check(unsafe {
+            ffi::fl_batch_verify(
+                self.raw,
+                raws.as_ptr(),
+                n,
+                ids.as_ptr(),
+                offsets.as_ptr(),
+                pos.as_ptr(),
+                sp.as_ptr(),
+                toks.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                ptr::null_mut(),
+            )
+        })?;
+        Ok((0..n).map(|i| toks[offsets[i]..offsets[i] + counts[i]].to_vec()).collect())
+    }
+
     /// `decode` with top-p / top-k.
     pub fn decode_ex(&self, cache: &mut Cache, first_token: u32, pos: usize, n_steps: usize, eos: Option<u32>, s: Sampler) -> Result<Vec<u32>> {
         let mut toks = vec![0u32; n_steps];
