@@ -183,6 +183,21 @@ def make_guide_desc(row_ptr, tokens, next):
     return st, (rp, tk, nx)
 
 
+class FlEmbed(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pooling", C.c_int32), ("mask", C.c_int32), ("normalize", C.c_int32),
+                ("dimensions", C.c_int64), ("_reserved", C.c_int64 * 2)]
+
+
+POOLING = {"last": 0, "mean": 1, "first": 2, "none": 3}
+ATTN_MASK = {"causal": 0, "full": 1}
+
+
+def make_embed(pooling="last", mask="causal", normalize=True, dimensions=0):
+    """fl_embed; pooling / mask by name (POOLING, ATTN_MASK) or by their integer codes."""
+    return FlEmbed(C.sizeof(FlEmbed), pooling if isinstance(pooling, int) else POOLING[pooling],
+                   mask if isinstance(mask, int) else ATTN_MASK[mask], int(normalize), int(dimensions))
+
+
 class FlLookup(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_draft", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32),
                 ("_pad", C.c_int32), ("_reserved", C.c_int64 * 2)]
@@ -296,7 +311,11 @@ def lib():
         L.fl_op_attention_plain.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 9 + [C.c_int32, C.c_float, C.c_int32, vp]
         L.fl_op_attention_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 5 + [C.c_float, C.c_int32, vp]
         L.fl_op_attention_packed.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 6 + [C.c_float, vp]
+        L.fl_op_attention_packed_ex.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp] + [C.c_int64] * 6 + [C.c_float, C.c_int32, vp]
         L.fl_batch_prefill.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.fl_batch_embed.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(FlEmbed), vp]
+        L.fl_op_pool_rows.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.POINTER(FlEmbed), vp]
+        L.fl_op_pool_rows_time.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.POINTER(FlEmbed), C.c_int32, C.POINTER(C.c_double)]
         L.fl_batch_create.argtypes = [vp, vp, sz, C.POINTER(vp)]
         L.fl_batch_destroy.argtypes = [vp]
         L.fl_batch_destroy.restype = None
@@ -856,6 +875,27 @@ class Model:
                                       lg.ctypes.data if want_logits else None))
         return (toks[:n], lg) if want_logits else toks[:n]
 
+    def embed_packed(self, caches, seqs, pos=None, pooling="last", mask="causal", normalize=True, dimensions=0):
+        """fl_batch_embed: seqs[i] appended to caches[i] at RoPE offset pos[i] (None: 0 for all) in ONE forward; instead of logits the
+        pooled final hidden states come back: [n, dims] f32 for pooling "last" / "mean" / "first", [total tokens, dims] for "none"
+        (dims = dimensions or the hidden size).  mask "full": every token sees its whole sequence; the caches must be empty, and are
+        to be reset before anything decodes from them."""
+        n = len(caches)
+        assert len(seqs) == n
+        ps = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in seqs]
+        ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(0, np.uint32), dtype=np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([p.size for p in ps])]), dtype=np.uint64)
+        pos = np.ascontiguousarray([0] * n if pos is None else pos, dtype=np.uint64)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        st = make_embed(pooling, mask, normalize, dimensions)
+        h = int(self.cfg["hidden_size"])
+        dims = int(dimensions) if 0 < int(dimensions) <= h else h
+        rows = int(offsets[-1]) if st.pooling == POOLING["none"] else n
+        out = np.empty((max(rows, 1), dims), dtype=np.float32)
+        _check(lib().fl_batch_embed(self._h, C.cast(arr, C.c_void_p), n, ids.ctypes.data, offsets.ctypes.data, pos.ctypes.data, C.byref(st),
+                                    out.ctypes.data))
+        return out[:rows]
+
     def forward_score(self, cache, ids, pos, top_n=0, targets=None, want_logits=False):
         """fl_forward_score: forward(cache, ids, pos) with every row scored on the device; nothing is selected.  targets None: row i's
         target is ids[i + 1], the last row has none; else [T] ids (SCORE_NO_TARGET: none).  Returns a ScoreResult; want_logits: with
@@ -1212,8 +1252,9 @@ def op_attention_batch(q, ks, vs, lens, seq_alloc, nsplit, H, Hkv, d, layout=0, 
     return out
 
 
-def op_attention_packed(q, ks, vs, counts, s_past, seq_alloc, H, Hkv, d, layer=0, window=-1, pad_value=0.0):
-    """The packed prefill attention launch alone (fl_op_attention_packed; bf16 bits, MFMA layout).  q [sum(counts), H*d], member s's
+def op_attention_packed(q, ks, vs, counts, s_past, seq_alloc, H, Hkv, d, layer=0, window=-1, pad_value=0.0, mask=0, ex=True):
+    """The packed prefill attention launch alone (fl_op_attention_packed_ex; ex=False: fl_op_attention_packed, mask 0 only; bf16 bits,
+    MFMA layout).  mask 1: every new token sees all of its sequence's keys, the window is ignored.  q [sum(counts), H*d], member s's
     rows back to back; ks[s] / vs[s] [n_layers, rows_s, Hkv*d]: rows [0, s_past[s]) its cached prefix, the next counts[s] its new
     tokens, the rest stale contents; seq_alloc[s]: its cache's row count (a multiple of 32).  Returns [sum(counts), H*d] f32."""
     q = np.ascontiguousarray(q, dtype=np.uint16)
@@ -1230,8 +1271,36 @@ def op_attention_packed(q, ks, vs, counts, s_past, seq_alloc, H, Hkv, d, layer=0
     vpp = (C.c_void_p * n)(*[a.ctypes.data for a in vs])
     sp, rows, sa = i64(s_past), i64([a.shape[1] for a in ks]), i64(seq_alloc)
     out = np.empty((T, H * d), dtype=np.float32)
+    if ex:
+        _check(lib().fl_op_attention_packed_ex(q.ctypes.data, C.cast(kp, C.c_void_p), C.cast(vpp, C.c_void_p), n, off.ctypes.data, sp.ctypes.data,
+                                               rows.ctypes.data, sa.ctypes.data, n_layers, layer, H, Hkv, d, window, pad_value, int(mask), out.ctypes.data))
+        return out
+    assert mask == 0
     _check(lib().fl_op_attention_packed(q.ctypes.data, C.cast(kp, C.c_void_p), C.cast(vpp, C.c_void_p), n, off.ctypes.data, sp.ctypes.data,
                                         rows.ctypes.data, sa.ctypes.data, n_layers, layer, H, Hkv, d, window, pad_value, out.ctypes.data))
+    return out
+
+
+def op_pool_rows(x, inv_rms, w, counts, pooling="last", normalize=False, dimensions=0, iters=0):
+    """The pool launch of fl_batch_embed alone (fl_op_pool_rows): x [T, h] f32 residual rows, inv_rms [T], w [h]; member s owns
+    counts[s] consecutive rows.  Returns [n, dims] f32 ([T, dims] for pooling "none"); iters > 0: the ms per pool instead
+    (fl_op_pool_rows_time)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    inv_rms = np.ascontiguousarray(inv_rms, dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    T, h = x.shape
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), dtype=np.uint64)
+    assert int(off[-1]) == T and inv_rms.size == T and w.size == h
+    st = make_embed(pooling, 0, normalize, dimensions)
+    if iters > 0:
+        ms = C.c_double(0.0)
+        _check(lib().fl_op_pool_rows_time(x.ctypes.data, inv_rms.ctypes.data, w.ctypes.data, off.ctypes.data, len(counts), h, C.byref(st), iters,
+                                          C.byref(ms)))
+        return ms.value
+    dims = int(dimensions) if 0 < int(dimensions) <= h else h
+    rows = T if st.pooling == POOLING["none"] else len(counts)
+    out = np.empty((rows, dims), dtype=np.float32)
+    _check(lib().fl_op_pool_rows(x.ctypes.data, inv_rms.ctypes.data, w.ctypes.data, off.ctypes.data, len(counts), h, C.byref(st), out.ctypes.data))
     return out
 
 

@@ -383,6 +383,12 @@ int fl_batch_verify(fl_model *m, fl_cache *const *caches, size_t n, const uint32
         return batch_verify(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, samplers, tokens_out, n_out, logits_out);
     });
 }
+int fl_batch_embed(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                   const fl_embed *opts, float *out) {
+    return guarded([&]() -> int {
+        return batch_embed(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, opts, out);
+    });
+}
 int fl_batch_decode_lookup(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets,
                            const uint32_t *first_tokens, const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts,
                            const fl_sampler *samplers, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {

@@ -944,7 +944,14 @@ int fl_op_attention_batch(const void *q, const void *const *k, const void *const
 int fl_op_attention_packed(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets, const int64_t *s_past,
                            const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer, int64_t H, int64_t Hkv, int64_t d,
                            int64_t window, float pad_value, float *out) {
+    return fl_op_attention_packed_ex(q, k, v, n_seq, offsets, s_past, k_rows, seq_alloc, n_layers, layer, H, Hkv, d, window, pad_value, FL_MASK_CAUSAL, out);
+}
+
+int fl_op_attention_packed_ex(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets, const int64_t *s_past,
+                              const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer, int64_t H, int64_t Hkv, int64_t d,
+                              int64_t window, float pad_value, int32_t mask, float *out) {
     return guarded([&]() -> int {
+        if (mask != FL_MASK_CAUSAL && mask != FL_MASK_FULL) FL_FAIL(FL_ERR_BAD_ARGUMENT, "mask %d is neither FL_MASK_CAUSAL nor FL_MASK_FULL", mask);
         if (!q || !k || !v || !offsets || !s_past || !k_rows || !seq_alloc || !out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
         if (n_seq < 1 || n_seq > 1023 || n_layers < 1 || n_layers > 64 || layer < 0 || layer >= n_layers)
             FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape (1 <= n_seq <= 1023, layer < n_layers <= 64)");
@@ -984,9 +991,84 @@ int fl_op_attention_packed(const void *q, const void *const *k, const void *cons
         void *tabd;
         FL_TRY(B.upload(&tabd, ph.bytes.data(), ph.bytes.size()));
         const float scale = 1.0f / sqrtf((float)d);
-        FL_TRY(launch_attn_prefill_packed_mfma(B.L, qd, ph.at(tabd), ph.n_items, ph.TT, ph.ks, (size_t)(layer * Hkv * d), od, H, Hkv, d, scale, window < 0 ? -1 : window));
+        FL_TRY(launch_attn_prefill_packed_mfma(B.L, qd, ph.at(tabd), ph.n_items, ph.TT, ph.ks, (size_t)(layer * Hkv * d), od, H, Hkv, d, scale, window < 0 ? -1 : window, 0, mask));
         FL_HIP(hipStreamSynchronize(B.s));
         return op_download(out, od, qn, FL_DTYPE_BF16);
+    });
+}
+
+// ---- the pooling op: fl_batch_embed's pool launch on host rows --------------------------------------------------------------------
+
+namespace {
+struct PoolOp { float *xd, *id, *wd, *part, *od; int *off, *cnt; int n_out, T; int64_t dims; };
+
+int pool_op_setup(OpScope &B, const char *who, const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h,
+                  const fl_embed *opts, PoolOp *p) {
+    FL_TRY(check_embed(opts, 0));
+    if (!x || !inv_rms || !w || !offsets) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null argument", who);
+    if (h < 1 || h > 65536) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: h %lld not in 1..65536", who, (long long)h);
+    FL_TRY(check_embed(opts, h));
+    if (n_seq < 1 || n_seq > ((size_t)1 << 20) || offsets[0] != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: 1 <= n_seq <= 2^20, offsets[0] == 0", who);
+    for (size_t s = 0; s < n_seq; s++)
+        if (offsets[s + 1] <= offsets[s] || offsets[s + 1] > ((size_t)1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: offsets must increase, up to T <= 2^20", who);
+    const size_t T = offsets[n_seq];
+    p->T = (int)T;
+    p->dims = opts->dimensions ? opts->dimensions : h;
+    p->n_out = opts->pooling == FL_POOL_NONE ? (int)T : (int)n_seq;
+    std::vector<int> off(n_seq), cnt(n_seq);
+    for (size_t s = 0; s < n_seq; s++) { off[s] = (int)offsets[s]; cnt[s] = (int)(offsets[s + 1] - offsets[s]); }
+    FL_TRY(B.begin());
+    FL_TRY(B.upload(&p->xd, x, T * (size_t)h * 4));
+    FL_TRY(B.upload(&p->id, inv_rms, T * 4));
+    FL_TRY(B.upload(&p->wd, w, (size_t)h * 4));
+    FL_TRY(B.upload(&p->off, off.data(), n_seq * 4));
+    FL_TRY(B.upload(&p->cnt, cnt.data(), n_seq * 4));
+    FL_TRY(B.alloc(&p->part, (size_t)p->n_out * pool_rows_chunks(p->dims) * 4));
+    FL_TRY(B.alloc(&p->od, (size_t)p->n_out * p->dims * 4));
+    return FL_OK;
+}
+}  // namespace
+
+int fl_op_pool_rows(const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h, const fl_embed *opts,
+                    float *out) {
+    return guarded([&]() -> int {
+        if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_pool_rows: null out");
+        OpScope B;
+        PoolOp p{};
+        FL_TRY(pool_op_setup(B, "fl_op_pool_rows", x, inv_rms, w, offsets, n_seq, h, opts, &p));
+        const size_t bytes = (size_t)p.n_out * p.dims * 4;
+        std::vector<float> host[2];
+        for (int rep = 0; rep < 2; rep++) {                     // twice: the same launch must give the same bits
+            host[rep].resize(bytes / 4);
+            FL_HIP(hipMemsetAsync(p.od, 0xff, bytes, B.s));      // NaN pattern: an element the kernel does not write shows up
+            FL_TRY(launch_pool_rows(B.L, p.xd, p.id, p.wd, p.off, p.cnt, p.n_out, h, p.dims, opts->pooling, opts->normalize != 0, p.part, p.od));
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(host[rep].data(), p.od, bytes, hipMemcpyDeviceToHost));
+        }
+        if (memcmp(host[0].data(), host[1].data(), bytes)) FL_FAIL(FL_ERR_HIP, "pool_rows: a repeated launch gave another result");
+        memcpy(out, host[0].data(), bytes);
+        return FL_OK;
+    });
+}
+
+int fl_op_pool_rows_time(const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h, const fl_embed *opts,
+                         int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!ms_out || iters < 1 || iters > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_pool_rows_time: null ms_out or a bad iteration count");
+        OpScope B;
+        PoolOp p{};
+        FL_TRY(pool_op_setup(B, "fl_op_pool_rows_time", x, inv_rms, w, offsets, n_seq, h, opts, &p));
+        auto run = [&]() { return launch_pool_rows(B.L, p.xd, p.id, p.wd, p.off, p.cnt, p.n_out, h, p.dims, opts->pooling, opts->normalize != 0, p.part, p.od); };
+        FL_TRY(run());                                           // warm
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipEventCreate(&B.e0)); FL_HIP(hipEventCreate(&B.e1));
+        FL_HIP(hipEventRecord(B.e0, B.s));
+        for (int i = 0; i < iters; i++) FL_TRY(run());
+        FL_HIP(hipEventRecord(B.e1, B.s));
+        FL_HIP(hipEventSynchronize(B.e1));
+        float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, B.e0, B.e1));
+        *ms_out = ms / iters;
+        return FL_OK;
     });
 }
 

@@ -34,7 +34,11 @@ __device__ __forceinline__ void prefill16_store_row(bf16_t *out, int tt, int T, 
 // workgroup's first staged tile (kstart; OWN_ORIGIN false, the single prompt) or from the WAVE's own first useful tile (wstart;
 // OWN_ORIGIN true, the pack: the split then depends on the wave's own 16 tokens only, not on TT or the rest of the pack).  At TT = 1
 // wstart == kstart and the two agree.
-template <int D, int KS, bool OWN_ORIGIN>
+// FULL (the packed kernel's full-mask instantiations only, fl_batch_embed's FL_MASK_FULL): every token of the sequence sees all of
+// its keys [0, len + T) and the window is ignored -- hi_q, wend and kend become len + T, lo stays c0, wstart = kstart = 0.  The keys
+// past len + T inside the last 32-key tile stay masked by hi_q.  Every wave walks all tiles, so the pair's alternation starts at
+// tile 0 for every wave.
+template <int D, int KS, bool OWN_ORIGIN, bool FULL = false>
 __device__ __forceinline__ void prefill16_body(const Prefill16Seq v, int hk, int H, int Hkv, float scale, int window, int TT, int nst,
                                                unsigned char *lds) {      // lds: nst x KS x (K tile | V^T tile)
     constexpr int TILE = 2 * 32 * D * 2;
@@ -58,19 +62,19 @@ __device__ __forceinline__ void prefill16_body(const Prefill16Seq v, int hk, int
         }
     }
     int lo = c0;
-    if (window >= 0 && len + t - window > c0) lo = len + t - window;
-    const int lo_q = col_ok ? lo : 0, hi_q = col_ok ? len + t + 1 : 0;
+    if (!FULL && window >= 0 && len + t - window > c0) lo = len + t - window;
+    const int lo_q = col_ok ? lo : 0, hi_q = col_ok ? (FULL ? len + T : len + t + 1) : 0;
     const int pre_hi = col_ok ? c0 : 0;
     // this wave's useful key range (uniform per wave): tiles outside are skipped, staging is not
     int wstart = 0;
-    if (c0 == 0 && window >= 0 && len + t0 - window > 0) wstart = ((len + t0 - window) / 32) * 32;
-    const int wend = t0 < T ? len + min(T, t0 + 16) : 0;
+    if (!FULL && c0 == 0 && window >= 0 && len + t0 - window > 0) wstart = ((len + t0 - window) / 32) * 32;
+    const int wend = t0 < T ? len + (FULL ? T : min(T, t0 + 16)) : 0;
 
     MfmaAttnState<D> s; s.init();
     const bf16_t *kb = v.kb, *vb = v.vb;
     int kstart = 0;
-    if (c0 == 0 && window >= 0 && len + tb0 - window > 0) kstart = ((len + tb0 - window) / 32) * 32;
-    const int kend = len + min(T, tb0 + 16 * TT);                // <= the cache's capacity <= seq_alloc (a multiple of 32)
+    if (!FULL && c0 == 0 && window >= 0 && len + tb0 - window > 0) kstart = ((len + tb0 - window) / 32) * 32;
+    const int kend = len + (FULL ? T : min(T, tb0 + 16 * TT));   // <= the cache's capacity <= seq_alloc (a multiple of 32)
     const int nsteps = (kend - kstart + 31) / 32;
     constexpr int NI = D / 16 + D / 16;
     const int per = (NI + nwv - 1) / nwv;

@@ -278,8 +278,8 @@ int launch_attn_decode(Launcher &L, int dtype, const void *q, const void *k_cach
 // ------------------------------------------------------------------------------- prefill (T > 1)
 // grid (Hkv, T, ceil(G/GMAX)): one workgroup per (kv head, query row).  Mask (App. A.5): the
 // cached prefix [0,len) is fully visible; in-call key j is visible to query t iff j <= t and
-// (no window or j + window >= t).
-template <typename CT, int D, int GMAX>
+// (no window or j + window >= t).  FULL (fl_batch_embed's FL_MASK_FULL): every query sees all keys [0, len + T), no window.
+template <typename CT, int D, int GMAX, bool FULL = false>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(const CT *__restrict__ q, const CT *__restrict__ kc,
                                                            const CT *__restrict__ vc, const StepState *__restrict__ st,
                                                            CT *__restrict__ out, int T, int H, int Hkv, int max_seq,
@@ -300,7 +300,9 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const CT *__restrict_
     const int c0 = (int)st->call0;
     int lo = c0;
     if (window >= 0 && len + t - window > c0) lo = len + t - window;
-    if (lo == c0) {
+    if (FULL) {
+        attend_range<CT, D, GMAX, 4, 2>(s, qv, G, kb, vb, 0, len + T, wave, lane);
+    } else if (lo == c0) {
         attend_range<CT, D, GMAX, 4, 2>(s, qv, G, kb, vb, 0, len + t + 1, wave, lane);
     } else {
         if (c0 > 0) attend_range<CT, D, GMAX, 4, 2>(s, qv, G, kb, vb, 0, c0, wave, lane);
@@ -319,10 +321,14 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const CT *__restrict_
 
 template <typename CT, int D, int GMAX>
 static int launch_prefill_t(Launcher &L, const void *q, const void *kc, const void *vc, const StepState *st, void *out,
-                            int64_t T, int64_t H, int64_t Hkv, int64_t max_seq, float scale, int64_t window) {
+                            int64_t T, int64_t H, int64_t Hkv, int64_t max_seq, float scale, int64_t window, int mask) {
     const int G = (int)(H / Hkv);
     dim3 grid((unsigned)Hkv, (unsigned)T, (unsigned)((G + GMAX - 1) / GMAX));
     double flops = 2.0 * (double)T * T * H * D;       // QK^T + PV over the causal half
+    if (mask == 1)
+        return L.launch(KC_ATTN_PREFILL, 0, 2 * flops, attn_prefill_kernel<CT, D, GMAX, true>, grid, dim3(256), 0, (const CT *)q,
+                        (const CT *)kc, (const CT *)vc, st, (CT *)out, (int)T, (int)H, (int)Hkv, (int)max_seq, scale,
+                        (int)window);
     return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_kernel<CT, D, GMAX>, grid, dim3(256), 0, (const CT *)q,
                     (const CT *)kc, (const CT *)vc, st, (CT *)out, (int)T, (int)H, (int)Hkv, (int)max_seq, scale,
                     (int)window);
@@ -330,14 +336,15 @@ static int launch_prefill_t(Launcher &L, const void *q, const void *kc, const vo
 
 int launch_attn_prefill(Launcher &L, int dtype, const void *q, const void *k_cache, const void *v_cache,
                         const StepState *st, void *out, int64_t T, int64_t H, int64_t Hkv, int64_t d,
-                        int64_t max_seq, float scale, int64_t window) {
+                        int64_t max_seq, float scale, int64_t window, int mask) {
     const int G = (int)(H / Hkv);
     const bool small = G <= 4;
+    if (mask != 0 && mask != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "attention: mask %d is neither causal (0) nor full (1)", mask);
 #define FL_DISPATCH(CT)                                                                                             \
-    if (d == 128) return small ? launch_prefill_t<CT, 128, 4>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window) \
-                               : launch_prefill_t<CT, 128, 8>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window); \
-    if (d == 64) return small ? launch_prefill_t<CT, 64, 4>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window)   \
-                              : launch_prefill_t<CT, 64, 8>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window);
+    if (d == 128) return small ? launch_prefill_t<CT, 128, 4>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window, mask) \
+                               : launch_prefill_t<CT, 128, 8>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window, mask); \
+    if (d == 64) return small ? launch_prefill_t<CT, 64, 4>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window, mask)   \
+                              : launch_prefill_t<CT, 64, 8>(L, q, k_cache, v_cache, st, out, T, H, Hkv, max_seq, scale, window, mask);
     if (dtype == FL_DTYPE_BF16) { FL_DISPATCH(bf16_t) }
     else { FL_DISPATCH(float) }
 #undef FL_DISPATCH

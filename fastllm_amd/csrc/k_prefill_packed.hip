@@ -53,7 +53,8 @@ int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const Packed
 // single prompt's alternation starts at the same tile, the bits -- of its single forward.  Here the pair's alternation is counted from
 // the WAVE's own first useful tile (OWN_ORIGIN): the tiles a wave computes on, their order and their split over the pair depend on
 // its own 16 tokens, its sequence's lengths and the head shape only -- not on TT, the ring depth or the rest of the pack.
-template <int D, int KS>
+// FULL: the unmasked instantiations (attn_prefill16.h) -- items, TT, ks and the launch geometry are the causal plan's.
+template <int D, int KS, bool FULL = false>
 __global__ __launch_bounds__(1024) void attn_prefill_packed_mfma_kernel(const bf16_t *__restrict__ q, const PackedTable tb, size_t kv_layer_off,
                                                                        bf16_t *__restrict__ out, int H, int Hkv, float scale, int window,
                                                                        int TT, int nst) {
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(1024) void attn_prefill_packed_mfma_kernel(const bf
                          reinterpret_cast<const bf16_t *>(sq.v) + layer + (size_t)hk * D * seq_alloc, out + row0 * H * D,
                          __builtin_amdgcn_readfirstlane(tb.seq_cnt[item.seq]), __builtin_amdgcn_readfirstlane((int)sq.st->len),
                          __builtin_amdgcn_readfirstlane((int)sq.st->call0), seq_alloc, __builtin_amdgcn_readfirstlane(item.t0)};
-    prefill16_body<D, KS, true>(v, hk, H, Hkv, scale, window, TT, nst, lds);
+    prefill16_body<D, KS, true, FULL>(v, hk, H, Hkv, scale, window, TT, nst, lds);
 }
 
 PackedTable PackedHost::at(const void *dev_base) const {
@@ -117,20 +118,26 @@ void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, in
 }
 
 int launch_attn_prefill_packed_mfma(Launcher &L, const void *q, const PackedTable &tb, int n_items, int TT, int ks, size_t kv_layer_off, void *out,
-                                    int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops) {
+                                    int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops, int mask) {
     const int G = (int)(H / Hkv);
+    if (mask != 0 && mask != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "packed mfma attention: mask %d is neither causal (0) nor full (1)", mask);
     if (!attn_mfma_supported(FL_DTYPE_BF16, H, Hkv, d)) FL_FAIL(FL_ERR_UNSUPPORTED, "packed mfma attention: head_dim 64 / 128, at most 8 query heads per kv head");
     if (TT < 1 || (ks != 1 && ks != 2) || G * TT * ks > 16 || (ks == 2 && prefill16_slab_bytes(G, d, TT) > kPfDefaultLds))
         FL_FAIL(FL_ERR_BAD_ARGUMENT, "packed mfma attention: %d x %d x %d waves per workgroup", G, TT, ks);
     // ring depth, LDS and block of the 16-row kernel at this TT: never more LDS than the single prompt takes there
     const Prefill16Launch l = prefill16_launch(G, d, TT, ks, attn_prefill_tune());
     const dim3 grid((unsigned)n_items, (unsigned)Hkv), block((unsigned)l.block);
-#define FL_PACKED(DD, KK)                                                                                                                  \
-    return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_packed_mfma_kernel<DD, KK>, grid, block, l.lds, (const bf16_t *)q, tb, kv_layer_off, \
+#define FL_PACKED(DD, KK, FF)                                                                                                              \
+    return L.launch(KC_ATTN_PREFILL, 0, flops, attn_prefill_packed_mfma_kernel<DD, KK, FF>, grid, block, l.lds, (const bf16_t *)q, tb, kv_layer_off, \
                     (bf16_t *)out, (int)H, (int)Hkv, scale, (int)window, TT, l.nst);
-    if (d == 128) { if (ks == 2) { FL_PACKED(128, 2) } FL_PACKED(128, 1) }
-    if (ks == 2) { FL_PACKED(64, 2) }
-    FL_PACKED(64, 1)
+    if (mask == 1) {
+        if (d == 128) { if (ks == 2) { FL_PACKED(128, 2, true) } FL_PACKED(128, 1, true) }
+        if (ks == 2) { FL_PACKED(64, 2, true) }
+        FL_PACKED(64, 1, true)
+    }
+    if (d == 128) { if (ks == 2) { FL_PACKED(128, 2, false) } FL_PACKED(128, 1, false) }
+    if (ks == 2) { FL_PACKED(64, 2, false) }
+    FL_PACKED(64, 1, false)
 #undef FL_PACKED
 }
 

@@ -250,7 +250,7 @@ int launch_rope_kv_packed(Launcher &L, int dtype, const float *qkv, const Packed
 struct AttnPrefillTune;
 AttnPrefillTune attn_prefill_tune();   // the prefill attention plans' switches as tune() has them now (k_attn_mfma.hip)
 int launch_attn_prefill_packed_mfma(Launcher &L, const void *q, const PackedTable &tb, int n_items, int TT, int ks, size_t kv_layer_off, void *out,
-                                    int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops = 0);
+                                    int64_t H, int64_t Hkv, int64_t d, float scale, int64_t window, double flops = 0, int mask = 0);   // mask 1: full (every token sees all of its sequence's keys, no window)
 // The host image of one call's table: the arrays back to back (SeqRef first: it holds pointers), and where each begins.  Items are
 // cut, 16 * TT tokens each, for the members with vt[s] != 0 only (the others' attention runs per sequence); TT and ks from
 // plan_attn_prefill_packed over those members.
@@ -267,6 +267,16 @@ void packed_table_build(const SeqRef *refs, const int *counts, const int *vt, in
 // dst [n_slab][n_seq][h] = the sequences' last rows of src [n_slab][..][h] (slabs src_slab / dst_slab floats apart)
 int launch_gather_last_rows(Launcher &L, const float *src, const PackedTable &tb, float *dst, int n_seq, int64_t h, int n_slab, int64_t src_slab,
                             int64_t dst_slab);
+
+// Decoder-model embeddings (k_pool.hip, fl_batch_embed / fl_op_pool_rows): the pooled final hidden states of a pack.
+//   hid[t][j] = (x[t][j] * inv_rms[t]) * w[j]      (x, inv_rms: what the final launch_rmsnorm_add leaves; both products rounded)
+// pooling FL_POOL_LAST / FIRST: member s's last / first row; MEAN: the sum over its rows in row order from +0, one rounded add per
+// row, then one rounded division by (float)count; NONE: every row its own member (seq_off / seq_cnt are not read, n_out = T).
+// out [n_out][dims] fp32, dims <= h.  normalize: a second small launch divides every vector by the root of its sum of squares, the
+// column chunks' partial sums (part, [n_out][pool_rows_chunks(dims)] floats) added in chunk order; a zero vector stays zero.
+int pool_rows_chunks(int64_t dims);
+int launch_pool_rows(Launcher &L, const float *x, const float *inv_rms, const float *w, const int *seq_off, const int *seq_cnt, int n_out,
+                     int64_t h, int64_t dims, int pooling, bool normalize, float *part, float *out);
 
 // dst row of gate/up pair q in the 16-interleaved fused layout: 16 gate rows then 16 up rows
 __host__ __device__ inline int64_t gateup_row(int64_t q, int is_up) { return (q / 16) * 32 + (q % 16) + (is_up ? 16 : 0); }
@@ -540,7 +550,7 @@ int launch_attn_decode(Launcher &L, int dtype, const void *q, const void *k_cach
 // prefill: T queries; key kj visible to query t iff kj < len, or (j=kj-len) j<=t and j+window>=t
 int launch_attn_prefill(Launcher &L, int dtype, const void *q, const void *k_cache, const void *v_cache,
                         const StepState *st, void *out, int64_t T, int64_t H, int64_t Hkv, int64_t d,
-                        int64_t max_seq, float scale, int64_t window);
+                        int64_t max_seq, float scale, int64_t window, int mask = 0);   // mask 1: full -- every query sees all len + T keys, no window
 
 // bf16 MFMA attention (k_attn_mfma.hip): needs the transposed value cache [Hkv][d][seq_alloc], seq_alloc % 32 == 0
 bool attn_mfma_supported(int dtype, int64_t H, int64_t Hkv, int64_t d);

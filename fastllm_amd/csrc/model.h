@@ -92,6 +92,9 @@ struct PackedScratch {
     uint32_t *verify_out = nullptr;
     uint32_t *host_verify = nullptr;
     float *verify_prob = nullptr; int64_t verify_prob_R = 0;
+    // fl_batch_embed: the pooled vectors [embed_rows][h] fp32 and the column chunks' partial sums of squares [embed_rows][chunks];
+    // allocated at a model's first embed call, regrown with the largest call, counted in hbm_bytes
+    float *embed_out = nullptr, *embed_part = nullptr; size_t embed_rows = 0;
     std::vector<void *> allocs;
 };
 
@@ -291,6 +294,12 @@ int batch_decode_each(Batch *b, const uint32_t *first, const size_t *pos, size_t
 // per sequence the results of forward(m, caches[i], ..); samplers [n] or null (ArgMax), tokens_out [n] / logits_out [n][V] or null
 int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
                   const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out);
+// fl_batch_embed: the same pack, the same layers (under opts->mask), and behind them the pooled final hidden states instead of
+// lm_head and token selection; out [n][dims] or, FL_POOL_NONE, [offsets[n]][dims].  check_embed: the struct alone plus, where
+// h > 0 is known, `dimensions` -- no device needed
+int check_embed(const fl_embed *opts, int64_t h);
+int batch_embed(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                const fl_embed *opts, float *out);
 
 int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int compute_dtype,
                  const fl_parallel *par, const fl_model_options *opts, Model **out);

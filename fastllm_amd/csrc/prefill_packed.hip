@@ -71,6 +71,24 @@ int grow_verify(Model *m, Shard &sh, bool any_sampled, float **rows, int64_t *R)
     return FL_OK;
 }
 
+// fl_batch_embed's buffers: the pooled vectors of `rows` outputs and the column chunks' partial sums of squares.  Allocated at a
+// model's first embed call and regrown with the largest one; models that never embed pay nothing.
+int grow_embed(Model *m, Shard &sh, size_t rows) {
+    PackedScratch &ps = sh.packed;
+    if (ps.embed_rows >= rows) return FL_OK;
+    const size_t h = (size_t)m->D.h, nch = (size_t)pool_rows_chunks(m->D.h);
+    FL_HIP(hipStreamSynchronize(sh.stream));                     // (idle anyway: every call ends with a synchronise)
+    if (ps.embed_out) { (void)hipFree(ps.embed_out); ps.embed_out = nullptr; }
+    if (ps.embed_part) { (void)hipFree(ps.embed_part); ps.embed_part = nullptr; }
+    m->hbm_bytes -= (int64_t)(ps.embed_rows * (h + nch) * 4); ps.embed_rows = 0;
+    const size_t cap = std::min<size_t>(std::max<size_t>(rows + rows / 2, 64), std::max<size_t>(rows, (size_t)tune(TK_PREFILL_CHUNK)));
+    std::vector<void *> own;
+    FL_TRY(dev_alloc(own, (void **)&ps.embed_out, cap * h * 4, nullptr));
+    FL_TRY(dev_alloc(own, (void **)&ps.embed_part, cap * nch * 4, nullptr));
+    m->hbm_bytes += (int64_t)(cap * (h + nch) * 4); ps.embed_rows = cap;
+    return FL_OK;
+}
+
 // The ticket words of the selection block are zeroed once and put back by the kernel itself.  A call that fails between two lm_head
 // blocks, or whose tickets did not come back 0, would leave a straddling member's ticket behind for every later call: unless the call
 // ended well, the 64 words are zeroed again on the way out (enqueued ahead of StreamDrain's wait: declare it after the drain).
@@ -85,9 +103,9 @@ struct StreamDrain {            // an early return leaves nothing in flight that
 };
 
 // How a call names itself in its refusals: fl_batch_prefill and fl_batch_score keep the words they always had (and share them: one
-// message for one fault), a packed verify says that it is one.
+// message for one fault), a packed verify and a packed embed say what they are.
 struct PackWords { const char *prefix, *noun; };
-constexpr PackWords kWordsPrefill{"", "packed prefill"}, kWordsVerify{"fl_batch_verify: ", "packed verify"};
+constexpr PackWords kWordsPrefill{"", "packed prefill"}, kWordsVerify{"fl_batch_verify: ", "packed verify"}, kWordsEmbed{"fl_batch_embed: ", "packed embed"};
 
 // What a pack must look like whoever forwards it, decided without the model or a cache being looked at: n, the offsets, at most
 // max_rows rows per member (0: any), no null cache, no cache twice.
@@ -109,11 +127,13 @@ struct VerifyMode { uint32_t *tokens_out; size_t *n_out; };
 
 // batch_prefill, or -- score != null -- batch_score, or -- vf != null -- batch_verify: the same checks and the same layers; behind them
 // either the n last rows go through the final norm, lm_head and token selection, or ALL rows go through the final norm and lm_head in
-// blocks, each scored (model.h: ScoreCall) or each selected and scanned per member (launch_verify_packed)
+// blocks, each scored (model.h: ScoreCall) or each selected and scanned per member (launch_verify_packed); or -- emb != null --
+// batch_embed: the layers under emb->mask, the final norm on all rows and the pool launch (k_pool.hip): no lm_head, no selection
 int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
-                   const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out, const fl_score *score, const VerifyMode *vf = nullptr) {
+                   const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out, const fl_score *score, const VerifyMode *vf = nullptr,
+                   const fl_embed *emb = nullptr, float *emb_out = nullptr) {
     // ---- everything that can be refused is refused here, before the device or any cache is touched
-    const PackWords &w = vf ? kWordsVerify : kWordsPrefill;
+    const PackWords &w = vf ? kWordsVerify : emb ? kWordsEmbed : kWordsPrefill;
     if (!m || !caches || !ids || !offsets || !pos) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
     if (n < 1 || n > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s%zu sequences: a %s takes 1..%d", w.prefix, n, w.noun, kMaxBatch);
     if (m->tp > 1 || m->shards.size() != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "%sa %s runs on one GPU (tp_size %d)", w.prefix, w.noun, m->tp);
@@ -125,6 +145,12 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         if (vf) FL_TRY(refuse_logit_rules(caches[i], "fl_batch_verify"));
         if (vf) FL_TRY(refuse_guide(caches[i], "fl_batch_verify"));
     }
+    if (emb) FL_TRY(check_embed(emb, m->D.h));
+    const int mask = emb ? emb->mask : FL_MASK_CAUSAL;
+    if (mask == FL_MASK_FULL)
+        for (size_t i = 0; i < n; i++)
+            if (caches[i]->len != 0)
+                FL_FAIL(FL_ERR_UNSUPPORTED, "fl_batch_embed: FL_MASK_FULL needs an empty cache, cache %zu holds %zu tokens (a prefix computed causally is not the full-mask model's)", i, caches[i]->len);
     const size_t T_total = offsets[n];
     for (size_t r = 0; r < T_total; r++) FL_TRY(check_token(m, ids[r], "token"));
     const size_t chunk_max = (size_t)tune(TK_PREFILL_CHUNK);
@@ -192,6 +218,7 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
     float *vrows = nullptr;
     int64_t vR = 0;
     if (vf) FL_TRY(grow_verify(m, sh, any_sampled, &vrows, &vR));
+    if (emb) FL_TRY(grow_embed(m, sh, T_total));
     StreamDrain drain{sh.stream};
     memcpy(ps.host_tab, ph.bytes.data(), ph.bytes.size());
     PackedSeqInit *init = reinterpret_cast<PackedSeqInit *>(ps.host_tab + init_off);
@@ -218,7 +245,7 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qkv_slabs));
         FL_TRY(launch_rope_kv_packed(L, dt, sc.qkv, tb, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kv_layer_off, T, sh.Hs, sh.Hkvs, D.d, qkv_slabs, ly.bqkv));
         if (any_mfma)
-            FL_TRY(launch_attn_prefill_packed_mfma(L, sc.q, tb, ph.n_items, ph.TT, ph.ks, kv_layer_off, sc.ao, sh.Hs, sh.Hkvs, D.d, D.scale, D.window, attn_flops));
+            FL_TRY(launch_attn_prefill_packed_mfma(L, sc.q, tb, ph.n_items, ph.TT, ph.ks, kv_layer_off, sc.ao, sh.Hs, sh.Hkvs, D.d, D.scale, D.window, attn_flops, mask));
         if (any_plain) {
             // members outside the MFMA layout (fp32 models, bf16 head shapes the MFMA kernels refuse): the single-sequence attention
             // launches on their rows of q / ao
@@ -231,10 +258,11 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
                 const void *qi = (const char *)sc.q + roff;
                 void *aoi = (char *)sc.ao + roff;
                 if (counts[i] == 1) {
+                    // (one token over len + 1 keys, unmasked: what both masks ask for)
                     const AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, (int64_t)c->len + 1};
                     FL_TRY(attend_decode(L, m, c, sh, cs, kv, qi, aoi, as));
                 } else {
-                    FL_TRY(launch_attn_prefill(L, dt, qi, kv.k, kv.v, cs.st, aoi, counts[i], sh.Hs, sh.Hkvs, D.d, (int64_t)c->seq_alloc, D.scale, D.window));
+                    FL_TRY(launch_attn_prefill(L, dt, qi, kv.k, kv.v, cs.st, aoi, counts[i], sh.Hs, sh.Hkvs, D.d, (int64_t)c->seq_alloc, D.scale, D.window, mask));
                 }
             }
         }
@@ -255,6 +283,22 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
         FL_TRY(lm_head_rows(m, sh, L, sc, T, call.sink(0)));
         FL_TRY(call.fetch());
+    } else if (emb) {
+        // ---- every row: final norm at T = T_total, which leaves the fp32 residual stream and 1/rms of every row; the pool launch
+        // reads those (not the compute-dtype xn), one copy brings the vectors back
+        const int64_t dims = emb->dimensions ? emb->dimensions : D.h;
+        const size_t n_out = emb->pooling == FL_POOL_NONE ? T_total : n;
+        FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
+        FL_TRY(launch_pool_rows(L, sc.x_res, sc.inv_rms, sh.norm, tb.seq_off, tb.seq_cnt, (int)n_out, D.h, dims, emb->pooling, emb->normalize != 0,
+                                ps.embed_part, ps.embed_out));
+        FL_TRY(launch_packed_collect(L, tb, ps.result, nn));     // (the members' error words; nothing was selected)
+        FL_HIP(hipMemcpyAsync(emb_out, ps.embed_out, n_out * (size_t)dims * 4, hipMemcpyDeviceToHost, sh.stream));
+        FL_HIP(hipMemcpyAsync(ps.host_result, ps.result, n * 8, hipMemcpyDeviceToHost, sh.stream));
+        FL_HIP(hipStreamSynchronize(sh.stream));
+        for (size_t i = 0; i < n; i++)
+            if (ps.host_result[2 * i + 1]) FL_FAIL(FL_ERR_HIP, "device-side wait gave up (code 0x%x) in sequence %zu", ps.host_result[2 * i + 1], i);
+        for (size_t i = 0; i < n; i++) caches[i]->len += (size_t)counts[i];
+        return FL_OK;
     } else if (vf) {
         // ---- every row: final norm at T = T_total, lm_head in blocks of the scoring calls' block scratch, one selection launch behind
         // each -- every row by its member's sampler (the table image's copy of it), every member's scan by whoever brings its last row
@@ -329,6 +373,25 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
 int batch_prefill(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
                   const fl_sampler *samplers, uint32_t *tokens_out, float *logits_out) {
     return packed_forward(m, caches, n, ids, offsets, pos, samplers, tokens_out, logits_out, nullptr);
+}
+
+int check_embed(const fl_embed *e, int64_t h) {
+    if (!e) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null fl_embed (opts)");
+    if (e->struct_size != sizeof(fl_embed)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.struct_size is %u, expected %zu", e->struct_size, sizeof(fl_embed));
+    if (e->pooling < FL_POOL_LAST || e->pooling > FL_POOL_NONE) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.pooling %d is not an fl_pooling", e->pooling);
+    if (e->mask != FL_MASK_CAUSAL && e->mask != FL_MASK_FULL) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.mask %d is not an fl_attn_mask", e->mask);
+    if (e->normalize != 0 && e->normalize != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.normalize is %d, not 0 or 1", e->normalize);
+    if (e->dimensions < 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.dimensions %lld is negative", (long long)e->dimensions);
+    if (e->_reserved[0] || e->_reserved[1]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed._reserved must be 0");
+    if (h > 0 && e->dimensions > h) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_embed.dimensions %lld exceeds the hidden size %lld", (long long)e->dimensions, (long long)h);
+    return FL_OK;
+}
+
+int batch_embed(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos, const fl_embed *opts,
+                float *out) {
+    FL_TRY(check_embed(opts, 0));               // the struct's own errors first: they need neither model nor device
+    if (!out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_embed: null out");
+    return packed_forward(m, caches, n, ids, offsets, pos, nullptr, nullptr, nullptr, nullptr, nullptr, opts, out);
 }
 
 int batch_score(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos, const fl_score *sc) {

@@ -120,6 +120,8 @@ Model::~Model() {
         if (s.packed.host_result) (void)hipHostFree(s.packed.host_result);
         if (s.packed.host_verify) (void)hipHostFree(s.packed.host_verify);
         if (s.packed.verify_prob) (void)hipFree(s.packed.verify_prob);
+        if (s.packed.embed_out) (void)hipFree(s.packed.embed_out);
+        if (s.packed.embed_part) (void)hipFree(s.packed.embed_part);
         if (s.score.rows) (void)hipFree(s.score.rows);
         if (s.score.targets) (void)hipFree(s.score.targets);
         if (s.score.recs) (void)hipFree(s.score.recs);

@@ -1732,4 +1732,95 @@ class EmbeddingModel {
     size_t hidden_;
 };
 
+// ------------------------------------------------------------------------------------ decoder-model embeddings
+// The same surface over an fl_model (fl_batch_embed): the embedding checkpoints that are decoder models -- e5-mistral / SFR /
+// Linq-Embed-Mistral (LAST + CAUSAL), gte-Qwen2 (LAST + FULL), LLM2Vec Llama (MEAN + FULL).  No counterpart in the reference, whose
+// /v1/embeddings serves MiniLM only.  Tokenising (and appending EOS where the checkpoint wants it) is the caller's.  The object owns
+// its caches: one caller at a time.
+struct DecoderEmbeddingOptions {
+    fl_pooling pooling = FL_POOL_LAST;        // LAST / MEAN / FIRST (one vector per text; FL_POOL_NONE is the C ABI's)
+    fl_attn_mask mask = FL_MASK_CAUSAL;
+    bool normalize = true;
+    size_t dimensions = 0;                    // 0: hidden_size
+    size_t slots = 64;                        // caches in the pool = texts per fl_batch_embed call, 1..64
+    size_t max_seq = 0;                       // capacity of each; 0: detail::default_max_seq
+};
+
+class DecoderEmbeddingModel {
+  public:
+    static constexpr size_t kMaxMembers = 64, kMaxTokens = 8192;      // fl_batch_embed's limits per call
+    DecoderEmbeddingModel(std::shared_ptr<detail::ModelHandle> model, const DecoderEmbeddingOptions &opt = DecoderEmbeddingOptions(),
+                          std::string model_id = "")
+        : model_(std::move(model)), opt_(opt), model_id_(std::move(model_id)) {
+        if (!model_ || !model_->m) throw Error(FL_ERR_BAD_ARGUMENT, "null model");
+        fl_model_info info; check(fl_model_get_info(model_->m, &info), "fl_model_get_info");
+        hidden_ = (size_t)info.cfg.hidden_size;
+        if (opt_.pooling == FL_POOL_NONE) throw Error(FL_ERR_BAD_ARGUMENT, "DecoderEmbeddingModel returns one vector per text: FL_POOL_NONE is fl_batch_embed's");
+        if (opt_.slots < 1 || opt_.slots > kMaxMembers) throw Error(FL_ERR_BAD_ARGUMENT, "DecoderEmbeddingModel: 1..64 slots");
+        if (opt_.dimensions > hidden_) throw Error(FL_ERR_BAD_ARGUMENT, "DecoderEmbeddingModel: dimensions exceeds the hidden size");
+        const size_t cap = opt_.max_seq ? opt_.max_seq : detail::default_max_seq(model_->m);
+        caches_.resize(opt_.slots);
+        for (auto &c : caches_) check(fl_cache_create(model_->m, cap, &c.c), "Failed to create an embedding cache");
+    }
+    DecoderEmbeddingModel(const DecoderEmbeddingModel &) = delete;
+    DecoderEmbeddingModel &operator=(const DecoderEmbeddingModel &) = delete;
+
+    EmbeddingOutput embed_ids(const std::vector<uint32_t> &ids) { return embed_batch_ids({ids})[0]; }
+    // Any number of texts: cut into calls of at most `slots` members and 8192 tokens, in order; the pool's caches are reset per call.
+    // Result i agrees with embed_ids(seqs[i]): bit-identical where both calls fall into one of the planner's row-count regimes, else as
+    // two runs that sum in different orders agree (the row-wise projections are chosen by a call's total rows, as in fl_batch_prefill).
+    std::vector<EmbeddingOutput> embed_batch_ids(const std::vector<std::vector<uint32_t>> &seqs) {
+        const size_t dims = embedding_size();
+        std::vector<EmbeddingOutput> out(seqs.size());
+        fl_embed e{};
+        e.struct_size = (uint32_t)sizeof e; e.pooling = opt_.pooling; e.mask = opt_.mask; e.normalize = opt_.normalize ? 1 : 0;
+        e.dimensions = (int64_t)opt_.dimensions;
+        size_t i = 0;
+        while (i < seqs.size()) {
+            std::vector<uint32_t> ids;
+            std::vector<size_t> offsets{0};
+            size_t j = i;
+            // (a text beyond 8192 tokens goes alone and the library says why it cannot be embedded)
+            while (j < seqs.size() && j - i < caches_.size() && (j == i || ids.size() + seqs[j].size() <= kMaxTokens)) {
+                ids.insert(ids.end(), seqs[j].begin(), seqs[j].end());
+                offsets.push_back(ids.size());
+                j++;
+            }
+            const size_t n = j - i;
+            std::vector<fl_cache *> cs(n);
+            for (size_t k = 0; k < n; k++) { cs[k] = caches_[k].c; fl_cache_reset(cs[k]); }
+            const std::vector<size_t> pos(n, 0);
+            std::vector<float> flat(n * dims);
+            check(fl_batch_embed(model_->m, cs.data(), n, ids.data(), offsets.data(), pos.data(), &e, flat.data()), "Failed to embed");
+            // (under FL_MASK_FULL the caches now hold the full-mask model's K/V: they are reset before their next use, above)
+            for (size_t k = 0; k < n; k++) {
+                out[i + k].embeddings.assign(flat.begin() + k * dims, flat.begin() + (k + 1) * dims);
+                out[i + k].model = model_id_; out[i + k].token_count = seqs[i + k].size();
+            }
+            calls_++;
+            i = j;
+        }
+        return out;
+    }
+    std::string model_id() const { return model_id_; }
+    size_t embedding_size() const { return opt_.dimensions ? opt_.dimensions : hidden_; }
+    size_t calls() const { return calls_; }                       // fl_batch_embed calls so far
+    // the cosine, as EmbeddingModel::compute_similarity_ids forms it
+    float compute_similarity_ids(const std::vector<uint32_t> &a, const std::vector<uint32_t> &b) {
+        const std::vector<float> v1 = embed_ids(a).embeddings, v2 = embed_ids(b).embeddings;
+        float dot = 0.f, n1 = 0.f, n2 = 0.f;
+        for (size_t i = 0; i < v1.size(); i++) dot += v1[i] * v2[i];
+        for (float x : v1) n1 += x * x;
+        for (float x : v2) n2 += x * x;
+        return dot / (std::sqrt(n1) * std::sqrt(n2));
+    }
+
+  private:
+    std::shared_ptr<detail::ModelHandle> model_;
+    DecoderEmbeddingOptions opt_;
+    std::string model_id_;
+    size_t hidden_ = 0, calls_ = 0;
+    std::vector<detail::CacheHandle> caches_;
+};
+
 }  // namespace fastllm

@@ -638,4 +638,50 @@ int flh_compute_similarity_ids(void *ev, const uint32_t *a, size_t na, const uin
     });
 }
 
+// DecoderEmbeddingModel (fastllm_host.hpp): the same surface over an fl_model the caller already holds (a reference is taken)
+int flh_decoder_embedding_create_on(void *fl_model_ptr, int pooling, int mask, int normalize, size_t dimensions, size_t slots, size_t max_seq,
+                                    void **out) {
+    return guard([&] {
+        if (!fl_model_ptr || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        fl_model *m = static_cast<fl_model *>(fl_model_ptr);
+        fl_model_retain(m);
+        auto mh = std::make_shared<detail::ModelHandle>(m);          // (releases the reference)
+        DecoderEmbeddingOptions opt;
+        opt.pooling = (fl_pooling)pooling; opt.mask = (fl_attn_mask)mask; opt.normalize = normalize != 0;
+        opt.dimensions = dimensions; opt.slots = slots; opt.max_seq = max_seq;
+        *out = new DecoderEmbeddingModel(mh, opt, "synthetic");
+        return 0;
+    });
+}
+void flh_decoder_embedding_destroy(void *ev) { delete static_cast<DecoderEmbeddingModel *>(ev); }
+size_t flh_decoder_embedding_size(void *ev) { return static_cast<DecoderEmbeddingModel *>(ev)->embedding_size(); }
+size_t flh_decoder_embedding_calls(void *ev) { return static_cast<DecoderEmbeddingModel *>(ev)->calls(); }
+int flh_decoder_embed_batch_ids(void *ev, const uint32_t *ids, const size_t *offsets, size_t n_seq, float *out) {
+    return guard([&] {
+        if (!ev || !out || !offsets) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        std::vector<std::vector<uint32_t>> seqs;
+        for (size_t s = 0; s < n_seq; s++) seqs.emplace_back(ids + offsets[s], ids + offsets[s + 1]);
+        auto *em = static_cast<DecoderEmbeddingModel *>(ev);
+        const std::vector<EmbeddingOutput> r = em->embed_batch_ids(seqs);
+        for (size_t s = 0; s < n_seq; s++) std::memcpy(out + s * em->embedding_size(), r[s].embeddings.data(), em->embedding_size() * sizeof(float));
+        return 0;
+    });
+}
+int flh_decoder_embed_ids(void *ev, const uint32_t *ids, size_t T, float *out, size_t *token_count) {
+    return guard([&] {
+        if (!ev || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        const EmbeddingOutput r = static_cast<DecoderEmbeddingModel *>(ev)->embed_ids(std::vector<uint32_t>(ids, ids + T));
+        std::memcpy(out, r.embeddings.data(), r.embeddings.size() * sizeof(float));
+        if (token_count) *token_count = r.token_count;
+        return 0;
+    });
+}
+int flh_decoder_compute_similarity_ids(void *ev, const uint32_t *a, size_t na, const uint32_t *b, size_t nb, float *out) {
+    return guard([&] {
+        if (!ev || !out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        *out = static_cast<DecoderEmbeddingModel *>(ev)->compute_similarity_ids(std::vector<uint32_t>(a, a + na), std::vector<uint32_t>(b, b + nb));
+        return 0;
+    });
+}
+
 }  // extern "C"

@@ -570,6 +570,50 @@ int fl_forward_score(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, si
 int fl_batch_score(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
                    const size_t *pos /* [n] */, const fl_score *sc /* ONE struct, arrays over offsets[n] rows */);
 
+/* ---- decoder-model embeddings: pooled final hidden states of a packed forward, optionally under a full (bidirectional) mask ---------
+ * The embedding checkpoints deployed today are decoder models of the three architectures this library runs: e5-mistral /
+ * SFR-Embedding-Mistral / Linq-Embed-Mistral (causal, last-token pooling), gte-Qwen2 (full mask, last-token pooling), LLM2Vec-style
+ * Llama (full mask, mean pooling); reward and *ForSequenceClassification heads need a row's final hidden state (FL_POOL_NONE, the
+ * caller applies the head).  fl_batch_embed is fl_batch_prefill's pack -- 1..64 members, at most 8192 tokens, every member non-empty,
+ * caches of this model, member i appended to caches[i] at RoPE offset pos[i] -- with a tail that pools instead of projecting: no
+ * lm_head, no token selection.  Installed logit rules and guides are ignored and left alone (as by fl_forward).
+ *   hidden state of row t: hid[t][j] = (x[t][j] * inv_rms[t]) * w[j], the model's final RMSNorm taken from the fp32 residual stream
+ *                          (bf16 models too), each multiply rounded to fp32 on its own.
+ *   pooling runs over the CALL's rows of a member only: a cached prefix (fl_cache_copy_prefix of a shared instruction) is attended
+ *   to, not pooled.  LAST / FIRST: that row.  MEAN: the fp32 sum over the member's rows in row order (one rounded add per row, from
+ *   +0), then one rounded division by (float)count.  NONE: every row, out is [offsets[n]][dims].
+ *   dims = dimensions ? dimensions : hidden_size: the first dims columns are kept, THEN (normalize) out[j] = p[j] / sqrt(sum p[j]^2)
+ *   in fp32; a zero vector stays zero.  The order of the sum of squares is fixed: the same call gives the same bits every time, and
+ *   a member's vector does not depend on the rest of the pack beyond what fl_batch_prefill's rows do.
+ *   out: host [n][dims] fp32 (LAST / MEAN / FIRST) or [offsets[n]][dims] (NONE; normalize applies per row).
+ * FL_MASK_CAUSAL leaves every cache exactly as fl_batch_prefill of the same pack leaves it (contents and length): decoding may go on
+ * from it.  FL_MASK_FULL: every row of a member sees all of the member's keys [0, len + count); the sliding window is not applied.
+ * It needs EMPTY caches (a prefix computed causally is not the bidirectional model's).  Afterwards the cache length has advanced by
+ * count as after a prefill, but its K/V are the full-mask model's: fl_cache_reset before decoding from or prefilling into it.
+ * FL_ERR_BAD_ARGUMENT, before the device or a cache is touched: null pointers, wrong struct_size, nonzero _reserved, unknown
+ * pooling / mask, normalize not 0 / 1, dimensions outside 0 .. hidden_size; then fl_batch_prefill's.  FL_ERR_UNSUPPORTED: tp_size > 1
+ * in any mode, FL_MASK_FULL on a cache that is not empty.  Any dtype and weight format otherwise (FL_WEIGHTS_E4M3_ROW models run
+ * prompts through the bf16 kernels).
+ * Memory: a model's first embed call allocates max(n, offsets[n]) x hidden_size x 4 bytes of HBM (growing with the largest call,
+ * half as much again each time, never more than a call can hold), counted in fl_model_hbm_bytes; models that never embed pay
+ * nothing.
+ * Not here: the tokenizer (and appending EOS for e5-style models), latent-attention pooling (NV-Embed), per-layer hidden states,
+ * embeddings under tensor parallelism, FL_MASK_FULL over a cached prefix, a StreamBatcher lane for embedding requests, the pool fused
+ * into the last down_proj epilogue. */
+typedef enum fl_pooling   { FL_POOL_LAST = 0, FL_POOL_MEAN = 1, FL_POOL_FIRST = 2, FL_POOL_NONE = 3 } fl_pooling;
+typedef enum fl_attn_mask { FL_MASK_CAUSAL = 0, FL_MASK_FULL = 1 } fl_attn_mask;
+typedef struct fl_embed {
+    uint32_t struct_size;   /* sizeof(fl_embed) */
+    int32_t  pooling;       /* fl_pooling */
+    int32_t  mask;          /* fl_attn_mask */
+    int32_t  normalize;     /* 0 / 1: divide each output vector by its L2 norm */
+    int64_t  dimensions;    /* 0: hidden_size; else 1..hidden_size: keep the first `dimensions` columns, THEN normalise
+                               (OpenAI `dimensions`, Matryoshka checkpoints) */
+    int64_t  _reserved[2];  /* 0 */
+} fl_embed;
+int fl_batch_embed(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
+                   const size_t *pos /* [n] */, const fl_embed *opts, float *out);
+
 /* ---- logit rules: logit_bias and repetition / frequency / presence penalties inside the device decode loop -------------------------
  * New capability (the reference has none).  What an OpenAI-compatible server is asked for as `logit_bias`, `frequency_penalty`,
  * `presence_penalty`, and the `repetition_penalty` of the open-source servers.  The rules belong to a cache: installing them gives
@@ -992,6 +1036,21 @@ int fl_op_attention_batch(const void *q, const void *const *k, const void *const
 int fl_op_attention_packed(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets,
                            const int64_t *s_past, const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer,
                            int64_t H, int64_t Hkv, int64_t d, int64_t window, float pad_value, float *out);
+/* ... with the mask chosen: mask 0 (FL_MASK_CAUSAL) launches exactly what fl_op_attention_packed launches; 1 (FL_MASK_FULL): every
+ * new token of a sequence sees all of its keys [0, s_past + new tokens), `window` is ignored. */
+int fl_op_attention_packed_ex(const void *q, const void *const *k, const void *const *v, int64_t n_seq, const int64_t *offsets,
+                              const int64_t *s_past, const int64_t *k_rows, const int64_t *seq_alloc, int64_t n_layers, int64_t layer,
+                              int64_t H, int64_t Hkv, int64_t d, int64_t window, float pad_value, int32_t mask, float *out);
+
+/* The pooling launch of fl_batch_embed alone, on host buffers (unit tests, micro-benchmarks): x [T][h] the fp32 residual rows,
+ * inv_rms [T], w [h] the final norm's weight, offsets [n_seq + 1] (from 0 to T, increasing); opts as fl_batch_embed's (mask is not
+ * looked at).  out: [n_seq][dims], or [T][dims] with FL_POOL_NONE; pre-filled with the 0xff pattern on the device.  h 1 .. 65536,
+ * T 1 .. 2^20.  The launch runs twice and the two results must agree bit for bit (FL_ERR_HIP otherwise).
+ * fl_op_pool_rows_time: the same launch(es) `iters` times between two events, *ms_out = ms per pool; nothing is downloaded. */
+int fl_op_pool_rows(const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h,
+                    const fl_embed *opts, float *out);
+int fl_op_pool_rows_time(const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h,
+                         const fl_embed *opts, int32_t iters, double *ms_out);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,28 @@ pub struct fl_score {
     pub _reserved: [i64; 2],
 }
 
+/// `fl_pooling`: which of a member's rows a decoder-model embedding call (`fl_batch_embed`) returns.
+pub const FL_POOL_LAST: i32 = 0;
+pub const FL_POOL_MEAN: i32 = 1;
+pub const FL_POOL_FIRST: i32 = 2;
+pub const FL_POOL_NONE: i32 = 3;
+/// `fl_attn_mask`: causal (with the model's sliding window) or full -- every token sees its whole sequence, no window.
+pub const FL_MASK_CAUSAL: i32 = 0;
+pub const FL_MASK_FULL: i32 = 1;
+
+/// `fl_embed`: the options of `fl_batch_embed` (and `fl_op_pool_rows`); `struct_size` is `size_of::<fl_embed>()`.  `dimensions` 0 is
+/// the hidden size; otherwise the first `dimensions` columns are kept and THEN normalised.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_embed {
+    pub struct_size: u32,
+    pub pooling: i32,
+    pub mask: i32,
+    pub normalize: i32,
+    pub dimensions: i64,
+    pub _reserved: [i64; 2],
+}
+
 /// `fl_logit_rules`: `logit_bias` entries and the repetition / frequency / presence penalties a cache applies on the device to every
 /// row it selects a token from (fl_cache_set_logit_rules); `struct_size` is `size_of::<fl_logit_rules>()`.  `repetition_penalty` 1 and
 /// the other two 0 are off; a bias of negative infinity bans an id.
@@ -651,6 +673,39 @@ extern "C" {
         pos: *const usize,
         sc: *const fl_score,
     ) -> c_int;
+    /// `fl_batch_prefill`'s pack with the pooled final hidden states coming back instead of logits (decoder-model embeddings):
+    /// `out` is `[n][dims]`, or `[offsets[n]][dims]` with `FL_POOL_NONE`.
+    pub fn fl_batch_embed(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        ids: *const u32,
+        offsets: *const usize,
+        pos: *const usize,
+        opts: *const fl_embed,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_pool_rows(
+        x: *const f32,
+        inv_rms: *const f32,
+        w: *const f32,
+        offsets: *const usize,
+        n_seq: usize,
+        h: i64,
+        opts: *const fl_embed,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_pool_rows_time(
+        x: *const f32,
+        inv_rms: *const f32,
+        w: *const f32,
+        offsets: *const usize,
+        n_seq: usize,
+        h: i64,
+        opts: *const fl_embed,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
     pub fn fl_op_score(
         logits: *const f32,
         t: i64,
@@ -870,6 +925,25 @@ extern "C" {
         d: i64,
         window: i64,
         pad_value: f32,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_attention_packed_ex(
+        q: *const c_void,
+        k: *const *const c_void,
+        v: *const *const c_void,
+        n_seq: i64,
+        offsets: *const i64,
+        s_past: *const i64,
+        k_rows: *const i64,
+        seq_alloc: *const i64,
+        n_layers: i64,
+        layer: i64,
+        h: i64,
+        hkv: i64,
+        d: i64,
+        window: i64,
+        pad_value: f32,
+        mask: i32,
         out: *mut f32,
     ) -> c_int;
 }

@@ -275,6 +275,34 @@ pub fn op_verify_select(logits: &[f32], v: usize, draft: &[u32]) -> Result<(Vec<
     Ok((am, n as usize))
 }
 
+/// `fl_pooling`: which rows of a member `Model::embed_packed` returns.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum Pooling {
+    Last = ffi::FL_POOL_LAST,
+    Mean = ffi::FL_POOL_MEAN,
+    First = ffi::FL_POOL_FIRST,
+    None = ffi::FL_POOL_NONE,
+}
+
+/// `fl_attn_mask`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum Mask {
+    Causal = ffi::FL_MASK_CAUSAL,
+    Full = ffi::FL_MASK_FULL,
+}
+
+/// The options of `Model::embed_packed` (`fl_embed`).  e5-mistral / SFR / Linq: `Last` + `Causal`; gte-Qwen2: `Last` + `Full`;
+/// LLM2Vec Llama: `Mean` + `Full`; reward / classification heads: `None`, unnormalised.
+#[derive(Clone, Copy, Debug)]
+pub struct EmbedOptions {
+    pub pooling: Pooling,
+    pub mask: Mask,
+    pub normalize: bool,
+    pub dimensions: usize,
+}
+
 /// `fl_weight_format`: what the single-stream decode step reads its projection weights as.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 #[repr(i32)]
@@ -441,6 +469,42 @@ impl Model {
             ffi::fl_batch_prefill(self.raw, raws.as_ptr(), n, ids.as_ptr(), offsets.as_ptr(), pos.as_ptr(), sp.as_ptr(), toks.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok(toks)
+    }
+
+    /// `fl_batch_embed`: `seqs[i]` appended to `caches[i]` at RoPE offset `pos[i]`, all in ONE forward, and the pooled final hidden
+    /// states instead of logits: one vector of `dims` values per member (`Pooling::None`: per token), `dims` = `opts.dimensions` or
+    /// the hidden size.  `Mask::Full` needs empty caches and leaves the full-mask model's K/V in them: reset them before decoding.
+    pub fn embed_packed(&self, caches: &mut [&mut Cache], seqs: &[&[u32]], pos: &[usize], opts: EmbedOptions) -> Result<Vec<Vec<f32>>> {
+        let n = caches.len();
+        if seqs.len() != n || pos.len() != n {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("packed embed of {} caches: every slice must have that length", n) });
+        }
+        let mut info: ffi::fl_model_info = unsafe { std::mem::zeroed() };
+        check(unsafe { ffi::fl_model_get_info(self.raw, &mut info) })?;
+        let hidden = info.cfg.hidden_size as usize;
+        let dims = if opts.dimensions == 0 { hidden } else { opts.dimensions };
+        if dims > hidden {
+            return Err(Error { code: ffi::FL_ERR_BAD_ARGUMENT, message: format!("dimensions {} exceeds the hidden size {}", dims, hidden) });
+        }
+        let raws: Vec<*mut ffi::fl_cache> = caches.iter().map(|c| c.raw).collect();
+        let mut ids: Vec<u32> = Vec::new();
+        let mut offsets = vec![0usize; n + 1];
+        for (i, p) in seqs.iter().enumerate() {
+            ids.extend_from_slice(p);
+            offsets[i + 1] = ids.len();
+        }
+        let rows = if opts.pooling == Pooling::None { ids.len() } else { n };
+        let e = ffi::fl_embed {
+            struct_size: std::mem::size_of::<ffi::fl_embed>() as u32,
+            pooling: opts.pooling as i32,
+            mask: opts.mask as i32,
+            normalize: opts.normalize as i32,
+            dimensions: opts.dimensions as i64,
+            _reserved: [0; 2],
+        };
+        let mut out = vec![0f32; (rows * dims).max(1)];
+        check(unsafe { ffi::fl_batch_embed(self.raw, raws.as_ptr(), n, ids.as_ptr(), offsets.as_ptr(), pos.as_ptr(), &e, out.as_mut_ptr()) })?;
+        Ok((0..rows).map(|r| out[r * dims..(r + 1) * dims].to_vec()).collect())
     }
 
     /// `fl_batch_verify`: the verify steps `[tokens[i], drafts[i]..]` of `caches[i]` at RoPE offset `pos[i]`, all in ONE forward -- per
