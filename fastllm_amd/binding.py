@@ -346,6 +346,12 @@ def lib():
         L.fl_forward_verify_ex.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, C.POINTER(FlSampler), vp, C.POINTER(sz), vp]
         L.fl_decode_lookup_ex.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), C.POINTER(FlSampler), vp,
                                           C.POINTER(sz), C.POINTER(FlSpecStats)]
+        L.fl_forward_verify_lp.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, C.POINTER(FlSampler), C.POINTER(FlLogprobs), vp, C.POINTER(sz), vp]
+        L.fl_decode_lookup_lp.argtypes = [vp, vp, vp, sz, C.c_uint32, sz, sz, C.c_int64, C.POINTER(FlLookup), C.POINTER(FlSampler),
+                                          C.POINTER(FlLogprobs), vp, C.POINTER(sz), C.POINTER(FlSpecStats)]
+        L.fl_op_verify_adjust.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(FlGuideDesc), vp, vp]
+        L.fl_op_verify_adjust_time.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(FlGuideDesc), vp, C.c_int32, C.POINTER(C.c_double)]
+        L.fl_op_rules_count.argtypes = [vp, C.c_int64, vp, C.c_int64]
         L.fl_op_verify_sample.argtypes = [vp, C.c_int64, C.c_int64, vp, C.POINTER(FlSampler), vp, C.POINTER(C.c_int64), vp]
         L.fl_op_verify_sample_time.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(FlSampler), vp, vp]
         L.fl_batch_verify.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
@@ -538,6 +544,54 @@ def op_guide_mask(logits, row_ptr, tokens, next, states, input_tokens, has_guide
                                   out.ctypes.data, nxt.ctypes.data))
     del keep
     return out, nxt
+
+
+def _verify_adjust_call(logits, ids, words, biases, scalars, guide, states):
+    """The arguments op_verify_adjust and its timed form share: (pointer list up to `states`, T, V, the words array or None, what must stay alive)."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    tk = np.ascontiguousarray(ids, dtype=np.uint32).reshape(T)
+    w = bs = sc = None
+    if words is not None:
+        w = np.array(words, dtype=np.uint32, order="C").reshape(V)
+        bs = np.ascontiguousarray(biases, dtype=np.float32).reshape(V)
+        sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(3)
+    st = keep = ss = None
+    if guide is not None:
+        st, keep = make_guide_desc(*guide)
+        ss = np.ascontiguousarray(states, dtype=np.uint32).reshape(T)
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    args = [a.ctypes.data, T, V, tk.ctypes.data, ptr(w), ptr(bs), ptr(sc), C.byref(st) if st is not None else None, ptr(ss)]
+    return args, T, V, w, (a, tk, bs, sc, st, keep, ss)
+
+
+def op_verify_adjust(logits, ids, words=None, biases=None, scalars=None, guide=None, states=None):
+    """verify_adjust_kernel alone: logits float32 [T, V] (the rows of one verify step, T <= 16) and ids [T] (row i's input id).  Rules:
+    words uint32 [V], biases float32 [V], scalars (repetition, frequency, presence penalty); guide: (row_ptr, tokens, next) with states
+    [T], the state each row is masked in.  At least one of the two.  Returns (adjusted rows float32 [T, V], words after the launches --
+    the table is only read, so they must be the words that went in -- or None without rules)."""
+    args, T, V, w, keep = _verify_adjust_call(logits, ids, words, biases, scalars, guide, states)
+    out = np.empty((T, V), dtype=np.float32)
+    _check(lib().fl_op_verify_adjust(*args, out.ctypes.data))
+    del keep
+    return out, w
+
+
+def op_verify_adjust_time(logits, ids, iters, words=None, biases=None, scalars=None, guide=None, states=None):
+    """op_verify_adjust timed: ms per launch, the mean of `iters` back-to-back launches between two events."""
+    args, _, _, _, keep = _verify_adjust_call(logits, ids, words, biases, scalars, guide, states)
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_verify_adjust_time(*args, int(iters), C.byref(ms)))
+    del keep
+    return ms.value
+
+
+def op_rules_count(words, ids):
+    """rules_count_kernel alone: ids (at most 16) counted into words uint32 [V], in order -> the words after the launch."""
+    w = np.array(words, dtype=np.uint32, order="C").reshape(-1)
+    tk = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    _check(lib().fl_op_rules_count(w.ctypes.data, w.size, tk.ctypes.data if tk.size else None, tk.size))
+    return w
 
 
 def abi_version():
@@ -777,6 +831,48 @@ class Model:
         if return_stats:
             return toks[: n.value], dict(steps=st.steps, drafted=st.drafted, accepted=st.accepted)
         return toks[: n.value]
+
+    def forward_verify_lp(self, cache, token, draft, pos, logprobs=None, temperature=None, top_p=None, top_k=None, seed=0, draws_done=0,
+                          want_logits=False):
+        """fl_forward_verify_lp: forward_verify on a cache that may have logit rules and / or a guide.  Returns (tokens, logits): the
+        accepted drafts followed by the model's own next token, and the RAW rows [len(draft) + 1, V] (None without want_logits; with a
+        guide only the rows of the draft the guide can reach are written).  logprobs = N: (tokens, logits, token_logprob [n], top_ids
+        [n, N], top_logprobs [n, N]) -- the model's own distribution for every returned token."""
+        d = np.ascontiguousarray(draft, dtype=np.uint32)
+        toks = np.zeros(d.size + 1, dtype=np.uint32)
+        lg = np.empty((d.size + 1, self.V), dtype=np.float32) if want_logits else None
+        n = C.c_size_t(0)
+        sp = make_sampler(temperature, seed, draws_done, top_p, top_k) if temperature is not None else None
+        lp = _LogprobArrays(d.size + 1, logprobs) if logprobs is not None else None
+        st = lp.struct() if lp is not None else None
+        _check(lib().fl_forward_verify_lp(self._h, cache._h, int(token), d.ctypes.data if d.size else None, d.size, pos,
+                                          C.byref(sp) if sp is not None else None, C.byref(st) if st is not None else None, toks.ctypes.data,
+                                          C.byref(n), lg.ctypes.data if want_logits else None))
+        res = (toks[: n.value], lg)
+        return res + lp.cut(n.value) if lp is not None else res
+
+    def decode_lookup_lp(self, cache, corpus, first_token, pos, n_steps, eos=-1, max_draft=7, ngram_max=3, ngram_min=1, return_stats=False,
+                         logprobs=None, temperature=None, top_p=None, top_k=None, seed=0, draws_done=0):
+        """fl_decode_lookup_lp: decode_lookup on a cache that may have logit rules and / or a guide -- the loop of decode_sample with the
+        same rules, guide and sampler.  Returns the tokens; with logprobs = N: (tokens, token_logprob [n], top_ids [n, N], top_logprobs
+        [n, N]); return_stats appends a dict(steps, drafted, accepted)."""
+        cp = np.ascontiguousarray(corpus, dtype=np.uint32)
+        toks = np.zeros(max(n_steps, 1), dtype=np.uint32)
+        n = C.c_size_t(0)
+        o = make_lookup(max_draft, ngram_max, ngram_min)
+        stats = FlSpecStats()
+        sp = make_sampler(temperature, seed, draws_done, top_p, top_k) if temperature is not None else None
+        lp = _LogprobArrays(n_steps, logprobs) if logprobs is not None else None
+        st = lp.struct() if lp is not None else None
+        _check(lib().fl_decode_lookup_lp(self._h, cache._h, cp.ctypes.data if cp.size else None, cp.size, int(first_token), pos, n_steps, eos,
+                                         C.byref(o), C.byref(sp) if sp is not None else None, C.byref(st) if st is not None else None,
+                                         toks.ctypes.data, C.byref(n), C.byref(stats)))
+        res = (toks[: n.value],)
+        if lp is not None:
+            res += lp.cut(n.value)
+        if return_stats:
+            res += (dict(steps=stats.steps, drafted=stats.drafted, accepted=stats.accepted),)
+        return res[0] if len(res) == 1 else res
 
     def verify_packed(self, caches, tokens, drafts, pos, temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None, want_logits=False):
         """fl_batch_verify: the verify steps [tokens[i], *drafts[i]] of caches[i] at RoPE offset pos[i], all in ONE forward.  Per member

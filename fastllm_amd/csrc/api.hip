@@ -216,6 +216,21 @@ int fl_decode_lookup_ex(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t
     });
 }
 
+int fl_forward_verify_lp(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, const fl_sampler *sampler,
+                         const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return forward_verify_lp(M(m), C(c), token, draft, n_draft, pos, sampler, lp, tokens_out, n_out, logits_out);
+    });
+}
+
+int fl_decode_lookup_lp(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos, size_t n_steps,
+                        int64_t eos, const fl_lookup *opts, const fl_sampler *sampler, const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out,
+                        fl_spec_stats *stats) {
+    return guarded([&]() -> int {
+        return decode_lookup_lp(M(m), C(c), corpus, n_corpus, first_token, pos, n_steps, eos, opts, sampler, lp, tokens_out, n_out, stats);
+    });
+}
+
 int fl_forward_argmax(fl_model *m, fl_cache *c, const uint32_t *ids, size_t T, size_t pos, uint32_t *token_out) {
     return guarded([&]() -> int {
         if (!token_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null token_out");

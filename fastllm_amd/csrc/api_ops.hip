@@ -571,6 +571,108 @@ int fl_op_guide_mask(const float *logits, int64_t B, int64_t V, const fl_guide_d
     });
 }
 
+// fl_op_verify_adjust (out) and fl_op_verify_adjust_time (ms_out: `iters` launches between two events, nothing comes back)
+static int op_verify_adjust(const float *logits, int64_t T, int64_t V, const uint32_t *ids, uint32_t *words, const float *biases, const float *scalars,
+                            const fl_guide_desc *desc, const uint32_t *states, float *out, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!logits || !ids || (!out && !ms_out)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: null argument");
+        if (ms_out && (iters < 1 || iters > (1 << 20))) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust_time: a bad iteration count");
+        if (T < 1 || T > kVerifyMaxRows) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: T %lld not in 1..%d", (long long)T, kVerifyMaxRows);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: V %lld not in 1..2^24", (long long)V);
+        if (!words && !desc) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: neither rules (words) nor a guide (desc)");
+        if (words && (!biases || !scalars)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: rules need words, biases and scalars");
+        if (desc) {
+            FL_TRY(check_guide(desc, V));
+            if (!states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: a guide needs states");
+            for (int64_t t = 0; t < T; t++)
+                if (states[t] >= desc->n_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: states[%lld] = %u is not below n_states %u", (long long)t, states[t], desc->n_states);
+        }
+        OpScope S;
+        FL_TRY(S.begin());
+        // the rows back to back as a verify step keeps them ([T][V]: with an odd V the rows i > 0 start off a 16-byte boundary)
+        float *lg, *od; LogitRuleEntry *tab = nullptr; uint32_t *ltok = nullptr; uint64_t *rp = nullptr;
+        FL_TRY(S.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(S.alloc(&od, (size_t)T * V * 4));
+        std::vector<LogitRuleEntry> img;
+        if (words) {
+            img.resize((size_t)V);
+            for (int64_t j = 0; j < V; j++) img[(size_t)j] = LogitRuleEntry{words[j], biases[j]};
+            FL_TRY(S.upload(&tab, img.data(), (size_t)V * sizeof(LogitRuleEntry)));
+        }
+        if (desc) {
+            const size_t ns = desc->n_states, nnz = (size_t)desc->row_ptr[ns];
+            FL_TRY(S.upload(&rp, desc->row_ptr, (ns + 1) * 8));
+            FL_TRY(S.upload(&ltok, desc->tokens, nnz * 4));
+        }
+        VerifyAdjustArgs a;
+        for (int64_t t = 0; t < T; t++) { a.ids[t] = ids[t]; a.states[t] = desc ? states[t] : 0u; }
+        a.table = tab;
+        if (words) { a.rp = scalars[0]; a.fp = scalars[1]; a.pp = scalars[2]; }
+        a.row_ptr = rp; a.tokens = ltok; a.out = od;
+        if (ms_out) {
+            FL_TRY(launch_verify_adjust(S.L, lg, V, (int)T, a));          // warm
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipEventCreate(&S.e0)); FL_HIP(hipEventCreate(&S.e1));
+            FL_HIP(hipEventRecord(S.e0, S.s));
+            for (int i = 0; i < iters; i++) FL_TRY(launch_verify_adjust(S.L, lg, V, (int)T, a));
+            FL_HIP(hipEventRecord(S.e1, S.s));
+            FL_HIP(hipEventSynchronize(S.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, S.e0, S.e1));
+            *ms_out = ms / iters;
+            return FL_OK;
+        }
+        std::vector<float> rows[2];
+        for (int rep = 0; rep < 2; rep++) {                               // twice: workgroups count, search and fill in any order, the result must not depend on it
+            rows[rep].resize((size_t)T * V);
+            FL_HIP(hipMemsetAsync(od, 0x55, (size_t)T * V * 4, S.s));
+            FL_TRY(launch_verify_adjust(S.L, lg, V, (int)T, a));
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipMemcpy(rows[rep].data(), od, (size_t)T * V * 4, hipMemcpyDeviceToHost));
+        }
+        if (memcmp(rows[0].data(), rows[1].data(), (size_t)T * V * 4)) FL_FAIL(FL_ERR_HIP, "verify_adjust: a repeated launch gave another row");
+        memcpy(out, rows[0].data(), (size_t)T * V * 4);
+        if (words) {                                                      // the table as the launches left it: unchanged, if the kernel keeps its word
+            FL_HIP(hipMemcpy(img.data(), tab, (size_t)V * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+            for (int64_t j = 0; j < V; j++) words[j] = img[(size_t)j].word;
+        }
+        return FL_OK;
+    });
+}
+
+int fl_op_verify_adjust(const float *logits, int64_t T, int64_t V, const uint32_t *ids, uint32_t *words, const float *biases, const float *scalars,
+                        const fl_guide_desc *desc, const uint32_t *states, float *out) {
+    if (!out) return guarded([&]() -> int { FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust: null out"); });
+    return op_verify_adjust(logits, T, V, ids, words, biases, scalars, desc, states, out, 0, nullptr);
+}
+
+int fl_op_verify_adjust_time(const float *logits, int64_t T, int64_t V, const uint32_t *ids, const uint32_t *words, const float *biases,
+                             const float *scalars, const fl_guide_desc *desc, const uint32_t *states, int32_t iters, double *ms_out) {
+    if (!ms_out) return guarded([&]() -> int { FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_verify_adjust_time: null ms_out"); });
+    return op_verify_adjust(logits, T, V, ids, const_cast<uint32_t *>(words), biases, scalars, desc, states, nullptr, iters, ms_out);
+}
+
+int fl_op_rules_count(uint32_t *words, int64_t V, const uint32_t *ids, int64_t n) {
+    return guarded([&]() -> int {
+        if (!words || (n > 0 && !ids)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rules_count: null argument");
+        if (n < 0 || n > kVerifyMaxRows) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rules_count: n %lld not in 0..%d", (long long)n, kVerifyMaxRows);
+        if (V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rules_count: V %lld not in 1..2^24", (long long)V);
+        OpScope S;
+        FL_TRY(S.begin());
+        std::vector<LogitRuleEntry> img((size_t)V);
+        for (int64_t j = 0; j < V; j++) img[(size_t)j] = LogitRuleEntry{words[j], 0.f};
+        LogitRuleEntry *tab;
+        FL_TRY(S.upload(&tab, img.data(), (size_t)V * sizeof(LogitRuleEntry)));
+        RulesCountArgs a;
+        a.n = (int)n;
+        for (int64_t r = 0; r < n; r++) a.ids[r] = ids[r];
+        FL_TRY(launch_rules_count(S.L, tab, V, a));
+        FL_HIP(hipStreamSynchronize(S.s));
+        FL_HIP(hipMemcpy(img.data(), tab, (size_t)V * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < V; j++) words[j] = img[(size_t)j].word;
+        return FL_OK;
+    });
+}
+
 int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
                             int32_t dtype, float *out) {
     return guarded([&]() -> int {

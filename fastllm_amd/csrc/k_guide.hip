@@ -20,27 +20,9 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "guide_dev.h"                                                // kGuideBlock .., guide_lower_bound
 
 namespace fl {
-
-constexpr int kGuideBlock = 256, kGuideIdsPerWg = 512, kGuideMaxGrid = 2048;
-
-// how many of list[0 .. n) (ascending) are < key: the same value in every thread of the workgroup, which calls it as a whole
-__device__ __forceinline__ uint32_t guide_lower_bound(const uint32_t *__restrict__ list, uint32_t n, uint32_t key) {
-    uint32_t lo = 0, hi = n;                                          // the answer is in [lo, hi]
-    while (hi > lo) {
-        const uint32_t chunk = (hi - lo + kGuideBlock - 1) / kGuideBlock;
-        const uint32_t begin = lo + threadIdx.x * chunk;              // (< 2^32: at most hi + 256 * chunk)
-        const uint32_t end = min(begin + chunk, hi);
-        const int below = begin < hi && list[end - 1] < key;          // this lane's whole chunk is below the key
-        const uint32_t k = (uint32_t)__syncthreads_count(below);      // (monotone: the first k chunks)
-        const uint32_t nlo = min(lo + k * chunk, hi);
-        if (nlo == hi) return hi;
-        lo = nlo;
-        hi = min(nlo + chunk, hi) - 1;                                // chunk k ends with an entry >= key
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(kGuideBlock) void guide_mask_kernel(const float *__restrict__ logits, int V, GuideSrc src) {
     const int b = blockIdx.y, tid = threadIdx.x;

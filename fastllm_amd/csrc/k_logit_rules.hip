@@ -17,22 +17,9 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "logit_rules_dev.h"                                          // logit_rule, logit_rule_count
 
 namespace fl {
-
-__device__ __forceinline__ float logit_rule(float x, uint32_t word, float bias, float rp, float fp, float pp) {
-    float y = x;
-    if (word != 0 && rp != 1.0f) y = y > 0.0f ? __fdiv_rn(y, rp) : __fmul_rn(y, rp);
-    const uint32_t c = word & ~kRulePromptBit;
-    if (c > 0) {
-        y = __fsub_rn(y, __fmul_rn(__uint2float_rn(c), fp));
-        y = __fsub_rn(y, pp);
-    }
-    return __fadd_rn(y, bias);
-}
-
-// one more output of id j (the count saturates at 2^31 - 1: the prompt bit is never carried into)
-__device__ __forceinline__ uint32_t logit_rule_count(uint32_t word) { return (word & ~kRulePromptBit) == ~kRulePromptBit ? word : word + 1; }
 
 constexpr int kRulesBlock = 256, kRulesPerThread = 4, kRulesMaxGrid = 2048;
 

@@ -501,6 +501,23 @@ struct GuideSrc {
 };
 int launch_guide_mask(Launcher &L, const float *logits, int64_t V, int rows, const GuideSrc &src);
 int launch_set_guide_ctl(Launcher &L, GuideCtl *ctl, const GuideCtl &value);
+// Rules and guide inside a verify step (k_verify_adjust.hip): out row i = logits row i ([T][V] fp32, T <= kVerifyMaxRows) adjusted with
+// the table AS IT STANDS AFTER THE INPUTS OF ROWS 0..i -- the table itself is only read: each table word is counted once per r <= i
+// with ids[r] == its id -- and masked in states[i].  Everything a row needs travels by value, so a packed form can pass other rows'.
+// table null: no rules (allowed ids keep their bits); row_ptr null: no guide; one of the two must be there.  out != logits.
+struct VerifyAdjustArgs {
+    uint32_t ids[kVerifyMaxRows] = {};       // row i's input id: the step's token, then its drafts (>= V: counts nothing)
+    uint32_t states[kVerifyMaxRows] = {};    // the guide state row i is masked in (< n_states: the caller's duty)
+    const LogitRuleEntry *table = nullptr;   // [V]
+    float rp = 1.f, fp = 0.f, pp = 0.f;
+    const uint64_t *row_ptr = nullptr;       // the guide's CSR arrays (GuideCtl's)
+    const uint32_t *tokens = nullptr;
+    float *out = nullptr;                    // [T][V]
+};
+int launch_verify_adjust(Launcher &L, const float *logits, int64_t V, int T, const VerifyAdjustArgs &a);
+// ... and behind the step's selection: ids[0 .. n) counted into the table, in order (an id twice: counted twice; >= V: nothing)
+struct RulesCountArgs { uint32_t ids[kVerifyMaxRows] = {}; int n = 0; };
+int launch_rules_count(Launcher &L, LogitRuleEntry *table, int64_t V, const RulesCountArgs &a);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

@@ -136,6 +136,8 @@ struct Shard {
     float *verify_logits = nullptr;  // [kVerifyMaxRows][V] all rows' logits of a verify step (fl_forward_verify); allocated at a model's first one
     uint32_t *verify_out = nullptr;  // [kVerifyWords] its ArgMax ids, accepted count and arrival ticket (launch_verify_select)
     float *verify_scratch = nullptr; // [kVerifyMaxRows][V] the rows' probabilities of a SAMPLED verify step (launch_verify_sample); allocated at a model's first one
+    float *verify_adjusted = nullptr; // [kVerifyMaxRows][V] the rule-adjusted, guide-masked rows the selection of a verify step reads (launch_verify_adjust); allocated at the first ruled or guided one
+    ScoreRec *verify_recs = nullptr; // [kVerifyMaxRows] the rows' log-prob records of a verify step with log-probs (launch_score_rows); allocated at the first one
     // the persistent decode engine (k_engine.hip): granule edges of one launch and the tag epoch
     unsigned long long *eng_edge[3] = {};   // o_proj deltas [h] | silu(g)*u pairs [Ip/2] | down_proj deltas [h]
     uint32_t *eng_epoch = nullptr;
@@ -159,6 +161,7 @@ struct Model {
     float *host_logits = nullptr;   // pinned staging [V]
     uint32_t *host_tokens = nullptr;
     uint32_t *host_verify = nullptr;   // pinned [kVerifyWords]: what a verify step brings back
+    ScoreRec *host_verify_recs = nullptr;   // pinned [kVerifyMaxRows]: ... and its log-prob records (fl_forward_verify_lp)
     bool use_graph = true;
     bool fused_decode = true;    // norm / RoPE / KV-append fused into the GEMV kernels
     int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;   // FL_WEIGHTS_E4M3_ROW: the decode step streams e4m3 weights (k_gemv_w8.hip)
@@ -340,7 +343,8 @@ int make_sampler(const fl_sampler *sampling, int64_t V, SampleState *out);
 int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float *logits_out, uint32_t *token_out,
             const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr);
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling = nullptr, const fl_logprobs *lp = nullptr,
+                  float *last_row_out = nullptr /* host [V]: the raw row of the last step that ran, copied under the call's lock */);
 // fl_forward_score / fl_batch_score (prompt log-probabilities).  check_score: the struct alone plus, where V > 0 is known, the
 // targets -- no device needed; the error names the field
 int check_score(const fl_score *sc, size_t T, int64_t V);
@@ -408,6 +412,12 @@ int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, si
                    size_t *n_out, float *logits_out, const fl_sampler *sampling = nullptr);
 int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
                   const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling = nullptr);
+// fl_forward_verify_lp / fl_decode_lookup_lp: the same two calls on a cache with logit rules and / or a guide, with log-probs (lp or null)
+int forward_verify_lp(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, const fl_sampler *sampling,
+                      const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out, float *logits_out);
+int decode_lookup_lp(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                     const fl_lookup *opts, const fl_sampler *sampling, const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out,
+                     fl_spec_stats *stats);
 int check_lookup(const fl_lookup *opts);     // FL_ERR_BAD_ARGUMENT: null, wrong struct_size, a range error
 // what a verify step may and may not be asked of one cache (sizes, room, tensor parallelism, the sliding window): no device needed
 int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos);

@@ -1110,7 +1110,7 @@ int forward(Model *m, Cache *c, const uint32_t *ids, size_t T, size_t pos, float
 }
 
 int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling, const fl_logprobs *lp) {
+                  uint32_t *tokens_out, size_t *n_out, const fl_sampler *sampling, const fl_logprobs *lp, float *last_row_out) {
     if (n_out) *n_out = 0;
     if (n_steps == 0) return FL_OK;
     FL_TRY(check_call(m, c, n_steps, pos));
@@ -1137,6 +1137,8 @@ int decode_greedy(Model *m, Cache *c, uint32_t first, size_t pos, size_t n_steps
         if (guide) FL_TRY(set_guide_ctl(m, c));                     // the host's state: the device advances it inside the chunk
         for (size_t i = 0; i < nb; i++) FL_TRY(decode_step(m, c, (int64_t)(c->len + i), kind));
         FL_TRY(finish_call(m, c, nb, lp ? nb : 0));
+        // (the raw row of the last step that ran, while the model is still locked: nobody else's step can have replaced it)
+        if (last_row_out) FL_HIP(hipMemcpy(last_row_out, m->shards[0].logits_full, (size_t)m->D.V * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < nb; i++) {
             const uint32_t t = m->host_tokens[i];
             if (guide) c->guide_state = guide->walk(c->guide_state, t);      // (the EOS's edge too; what ran behind it is discarded)
@@ -1385,11 +1387,18 @@ int check_verify(Model *m, Cache *c, size_t n_draft, size_t pos) {
 // one verify step with the model locked and the arguments checked; host_verify holds the ids and the accepted count afterwards.
 // sampler (null or on == 0: ArgMax, the launches there have always been): row i is drawn with word sampler->draw + i, and the host
 // stays authoritative for the draw count as it is for the cache length -- every call brings the state, nothing is left behind.
+// adjust (fl_forward_verify_lp / fl_decode_lookup_lp only; the other callers have refused such caches): the cache's logit rules and
+// guide are applied by ONE launch in front of the selection, which then reads the adjusted rows -- row i with the table as it stands
+// after the inputs of rows 0..i and in the guide state after drafts 0..i-1; the table and c->guide_state are left as they were, for
+// verify_commit once the caller knows which rows count.  lp: the RAW rows are scored against the ids the selection left on the device.
+// Without rules, guide and lp the launches are the ones above, unchanged.
 static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, float *logits_out,
-                       const SampleState *sampler = nullptr) {
+                       const SampleState *sampler = nullptr, bool adjust = false, const fl_logprobs *lp = nullptr) {
     const Dims &D = m->D;
     Shard &sh = m->shards[0];
     const int64_t T = (int64_t)n_draft + 1;
+    const bool rules = adjust && c->rules_on;
+    const Guide *guide = adjust ? c->guide : nullptr;
     FL_HIP(hipSetDevice(sh.device));
     if (!sh.verify_logits) {
         FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_out, kVerifyWords * 4, &m->hbm_bytes));
@@ -1399,6 +1408,11 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     }
     const bool sampled = sampler && sampler->on;
     if (sampled && !sh.verify_scratch) FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_scratch, (size_t)kVerifyMaxRows * D.V * 4, &m->hbm_bytes));
+    if ((rules || guide) && !sh.verify_adjusted) FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_adjusted, (size_t)kVerifyMaxRows * D.V * 4, &m->hbm_bytes));
+    if (lp && !sh.verify_recs) {
+        FL_TRY(dev_alloc(sh.allocs, (void **)&sh.verify_recs, kVerifyMaxRows * sizeof(ScoreRec), &m->hbm_bytes));
+        if (!m->host_verify_recs) FL_HIP(hipHostMalloc((void **)&m->host_verify_recs, kVerifyMaxRows * sizeof(ScoreRec), hipHostMallocDefault));
+    }
     if (sh.pre.cap_T < T) FL_TRY(grow_prefill_scratch(m, sh, T));
     uint32_t *ids = m->host_tokens;                                  // pinned, and idle until this call's sync
     ids[0] = token;
@@ -1409,8 +1423,26 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     const AllRows rows{sh.verify_logits, T, nullptr};
     FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, &rows));
     Launcher L = make_launcher(m, sh);
-    if (sampled) FL_TRY(launch_verify_sample(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, *sampler, sh.verify_scratch, sh.verify_out, nullptr));
-    else FL_TRY(launch_verify_select(L, sh.verify_logits, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));
+    const float *sel = sh.verify_logits;                             // what the selection reads
+    if (rules || guide) {
+        VerifyAdjustArgs a;
+        for (int64_t i = 0; i < T; i++) a.ids[i] = ids[i];
+        if (rules) { a.table = c->shards[0].rule_tab; a.rp = c->rule_rp; a.fp = c->rule_fp; a.pp = c->rule_pp; }
+        if (guide) {
+            a.row_ptr = guide->row_ptr_dev; a.tokens = guide->tokens_dev;
+            uint32_t s = c->guide_state;
+            for (int64_t i = 0; i < T; i++) { a.states[i] = s; if (i < (int64_t)n_draft) s = guide->walk(s, draft[i]); }
+        }
+        a.out = sh.verify_adjusted;
+        FL_TRY(launch_verify_adjust(L, sh.verify_logits, D.V, (int)T, a));
+        sel = sh.verify_adjusted;
+    }
+    if (sampled) FL_TRY(launch_verify_sample(L, sel, D.V, (int)T, sh.pre.ids + 1, *sampler, sh.verify_scratch, sh.verify_out, nullptr));
+    else FL_TRY(launch_verify_select(L, sel, D.V, (int)T, sh.pre.ids + 1, sh.verify_out));
+    if (lp) {                                                        // the model's own distribution: the raw rows, the selected ids as targets
+        FL_TRY(launch_score_rows(L, sh.verify_logits, D.V, (int)T, sh.verify_out, lp->top_n, sh.verify_recs));
+        FL_HIP(hipMemcpyAsync(m->host_verify_recs, sh.verify_recs, (size_t)T * sizeof(ScoreRec), hipMemcpyDeviceToHost, sh.stream));
+    }
     FL_HIP(hipMemcpyAsync(m->host_verify, sh.verify_out, (kVerifyNacc + 1) * 4, hipMemcpyDeviceToHost, sh.stream));
     FL_TRY(finish_call(m, c, 0));
     if (m->host_verify[kVerifyNacc] > n_draft) FL_FAIL(FL_ERR_HIP, "verify step: accepted count %u out of range", m->host_verify[kVerifyNacc]);
@@ -1419,53 +1451,133 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     return FL_OK;
 }
 
-int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
-                   size_t *n_out, float *logits_out, const fl_sampler *sampling) {
+// ------------------------------------------------------------------------------- verify steps with rules, a guide and log-probs
+// true, and *next: the state has an edge for t (Guide::walk cannot tell "no edge" from an edge back to the same state)
+static bool guide_edge(const Guide *g, uint32_t s, uint32_t t, uint32_t *next) {
+    const uint32_t *b = g->tokens.data() + g->row_ptr[s], *e = g->tokens.data() + g->row_ptr[s + 1];
+    const uint32_t *it = std::lower_bound(b, e, t);
+    if (it == e || *it != t) return false;
+    *next = g->next[(size_t)(it - g->tokens.data())];
+    return true;
+}
+
+// A draft id without an edge from the state reached is -inf in the row before it and can never be accepted: the draft ends there.
+static size_t guide_cut_draft(const Cache *c, const uint32_t *draft, size_t n_draft) {
+    if (!c->guide) return n_draft;
+    uint32_t s = c->guide_state;
+    for (size_t i = 0; i < n_draft; i++) if (!guide_edge(c->guide, s, draft[i], &s)) return i;
+    return n_draft;
+}
+
+// What a ruled / guided verify step leaves behind, once the caller knows which rows count (the model locked, behind verify_step): the
+// inputs of rows 0 .. n_rows-1 -- token, draft[0 .. n_rows-1) -- are counted into the rules table by one launch on the shard's stream,
+// behind the selection and ahead of everything submitted later; the ids the call returns (an EOS that ended it included) move the guide.
+static int verify_commit(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_rows, const uint32_t *ret, size_t n_ret) {
+    if (c->rules_on && n_rows > 0) {
+        Shard &sh = m->shards[0];
+        FL_HIP(hipSetDevice(sh.device));
+        RulesCountArgs a;
+        a.n = (int)n_rows;
+        a.ids[0] = token;
+        for (size_t i = 1; i < n_rows; i++) a.ids[i] = draft[i - 1];
+        Launcher L = make_launcher(m, sh);
+        FL_TRY(launch_rules_count(L, c->shards[0].rule_tab, m->D.V, a));
+    }
+    if (c->guide) for (size_t i = 0; i < n_ret; i++) c->guide_state = c->guide->walk(c->guide_state, ret[i]);
+    return FL_OK;
+}
+
+// lp's arrays from entry `at` on
+static fl_logprobs logprobs_from(const fl_logprobs *lp, size_t at) {
+    fl_logprobs r = *lp;
+    r.token_logprob += at;
+    if (r.top_ids) r.top_ids += at * (size_t)lp->top_n;
+    if (r.top_logprobs) r.top_logprobs += at * (size_t)lp->top_n;
+    return r;
+}
+
+// one counted, guided step of the plain loop (fl_decode_sample_lp with n_steps 1): what a verify call without drafts is, bit for bit.
+// logits_out: the step's raw row, copied while decode_greedy still holds the model's lock.
+static int plain_step(Model *m, Cache *c, uint32_t token, size_t pos, const fl_sampler *sampling, const fl_logprobs *lp, uint32_t *token_out,
+                      float *logits_out) {
+    size_t n = 0;
+    return decode_greedy(m, c, token, pos, 1, -1, token_out, &n, sampling, lp, logits_out);
+}
+
+// fl_forward_verify{,_ex} (full == false: a cache with rules or a guide is refused, lp is null) and fl_forward_verify_lp (full: the
+// superset).  One body, so the two cannot drift apart; `who` names the entry point in the messages.
+static int verify_call(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, const fl_sampler *sampling,
+                       const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out, float *logits_out, bool full, const char *who) {
     if (n_out) *n_out = 0;
     SampleState sampler;
     FL_TRY(make_sampler(sampling, 0, &sampler));                     // its argument errors, before the handles are looked at
-    if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null tokens_out or n_out");
-    if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_forward_verify: null draft");
-    FL_TRY(refuse_logit_rules(c, "fl_forward_verify"));
-    FL_TRY(refuse_guide(c, "fl_forward_verify"));
+    if (lp) FL_TRY(check_logprobs(lp, 0));
+    if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null tokens_out or n_out", who);
+    if (n_draft > 0 && !draft) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null draft", who);
+    if (!full) { FL_TRY(refuse_logit_rules(c, who)); FL_TRY(refuse_guide(c, who)); }
     FL_TRY(check_verify(m, c, n_draft, pos));
     FL_TRY(check_token(m, token, "token"));
     for (size_t i = 0; i < n_draft; i++) FL_TRY(check_token(m, draft[i], "draft"));
-    if (n_draft == 0) {                                              // the decode step itself: its mask, its kernels
-        FL_TRY(forward(m, c, &token, 1, pos, logits_out, tokens_out, sampler.on ? sampling : nullptr));
+    if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
+    if (full) n_draft = guide_cut_draft(c, draft, n_draft);
+    if (n_draft == 0) {
+        // the decode step itself: its mask, its kernels.  A ruled or guided cache, or one asked for log-probs, takes the COUNTED step of
+        // the plain loop; a bare one the step it has always taken (fl_forward_sample_ex of one token: rules would not be counted there)
+        if (full && (c->rules_on || c->guide || lp)) FL_TRY(plain_step(m, c, token, pos, sampler.on ? sampling : nullptr, lp, tokens_out, logits_out));
+        else FL_TRY(forward(m, c, &token, 1, pos, logits_out, tokens_out, sampler.on ? sampling : nullptr));
         *n_out = 1;
         return FL_OK;
     }
     FL_TRY(make_sampler(sampling, m->D.V, &sampler));                // (with the vocabulary: a top_k >= V is off)
     debug_inject("forward");
     std::lock_guard<std::mutex> lock(m->mu);
-    FL_TRY(verify_step(m, c, token, draft, n_draft, pos, logits_out, &sampler));
+    FL_TRY(verify_step(m, c, token, draft, n_draft, pos, logits_out, &sampler, full, lp));
     const size_t n = (size_t)m->host_verify[kVerifyNacc] + 1;
-    for (size_t i = 0; i < n; i++) tokens_out[i] = m->host_verify[i];
+    if (full) FL_TRY(verify_commit(m, c, token, draft, n, m->host_verify, n));
+    for (size_t i = 0; i < n; i++) {
+        tokens_out[i] = m->host_verify[i];
+        if (lp) scatter_logprobs(m->host_verify_recs[i].lp, lp, i);
+    }
     *n_out = n;
     return FL_OK;
 }
 
-int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
-                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling) {
+int forward_verify(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, uint32_t *tokens_out,
+                   size_t *n_out, float *logits_out, const fl_sampler *sampling) {
+    return verify_call(m, c, token, draft, n_draft, pos, sampling, nullptr, tokens_out, n_out, logits_out, false, "fl_forward_verify");
+}
+
+int forward_verify_lp(Model *m, Cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos, const fl_sampler *sampling,
+                      const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return verify_call(m, c, token, draft, n_draft, pos, sampling, lp, tokens_out, n_out, logits_out, true, "fl_forward_verify_lp");
+}
+
+// fl_decode_lookup{,_ex} (full == false) and fl_decode_lookup_lp (full): one loop.
+static int lookup_loop(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                       const fl_lookup *opts, const fl_sampler *sampling, const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out,
+                       fl_spec_stats *stats, bool full, const char *who) {
     if (n_out) *n_out = 0;
     if (stats) *stats = fl_spec_stats{};
     FL_TRY(check_lookup(opts));
     SampleState sampler;
     FL_TRY(make_sampler(sampling, 0, &sampler));                     // its argument errors, before the handles are looked at
     const bool sampled = sampler.on != 0;                            // false: the greedy loop, launch for launch
-    if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null n_out");
-    if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null corpus");
-    FL_TRY(refuse_logit_rules(c, "fl_decode_lookup"));
-    FL_TRY(refuse_guide(c, "fl_decode_lookup"));
+    if (lp) FL_TRY(check_logprobs(lp, 0));
+    if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null n_out", who);
+    if (n_corpus && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null corpus", who);
+    if (!full) { FL_TRY(refuse_logit_rules(c, who)); FL_TRY(refuse_guide(c, who)); }
     if (n_steps == 0) return FL_OK;
-    if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_decode_lookup: null tokens_out");
+    if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null tokens_out", who);
     FL_TRY(check_call(m, c, n_steps, pos));
     FL_TRY(check_token(m, first, "token"));
     if (m->tp > 1 && opts->max_draft > 0) FL_FAIL(FL_ERR_UNSUPPORTED, "the verify step does not run under tensor parallelism (tp_size %d)", m->tp);
+    if (lp) { FL_TRY(check_logprobs(lp, m->D.V)); FL_TRY(logprobs_supported(m)); }
     const size_t V = (size_t)m->D.V, L0 = c->len;
-    if (sampled && opts->max_draft == 0) {                           // nothing to verify: the plain sampled loop itself
-        FL_TRY(decode_greedy(m, c, first, pos, n_steps, eos, tokens_out, n_out, sampling));
+    // a cache with rules or a guide, or a call that wants log-probs, takes the plain loop's COUNTED step where nothing is drafted; a
+    // bare one the steps fl_decode_lookup{,_ex} have always taken
+    const bool counted = full && (c->rules_on || c->guide || lp);
+    if (opts->max_draft == 0 && (sampled || counted)) {              // nothing to verify: the plain loop itself
+        FL_TRY(decode_greedy(m, c, first, pos, n_steps, eos, tokens_out, n_out, sampled ? sampling : nullptr, lp));
         if (stats) stats->steps = c->len - L0;
         return FL_OK;
     }
@@ -1484,35 +1596,57 @@ int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, u
         if (m->D.window >= 0) limit = std::min(limit, (size_t)m->D.window);
         size_t nd = lookup_draft(hist.data(), hist.size(), opts->max_draft, opts->ngram_max, opts->ngram_min, limit, draft);
         for (size_t i = 0; i < nd; i++) if (draft[i] >= V) { nd = i; break; }      // (a corpus id the model does not have ends the draft)
-        size_t n = 0;
-        // token k of the request is drawn with word k: this step's row i with word draws_done + emitted + i, whatever was rejected before
+        if (full) nd = guide_cut_draft(c, draft, nd);                // ... and so does one the guide cannot reach
+        // token k of the request is drawn with word k, and reported in entry k of lp's arrays, whatever was rejected before
         fl_sampler sp{};
         if (sampled) { sp = *sampling; sp.draws_done += emitted; }
+        fl_logprobs lps{};
+        if (lp) lps = logprobs_from(lp, emitted);
+        size_t n = 0, keep = 0;                                      // ids the step returned; how many of them are emitted
         if (nd == 0) {
-            FL_TRY(forward(m, c, &tok, 1, pos + emitted, nullptr, got, sampled ? &sp : nullptr));
+            if (counted) FL_TRY(plain_step(m, c, tok, pos + emitted, sampled ? &sp : nullptr, lp ? &lps : nullptr, got, nullptr));
+            else FL_TRY(forward(m, c, &tok, 1, pos + emitted, nullptr, got, sampled ? &sp : nullptr));
             n = 1;
+            keep = eos >= 0 && (int64_t)got[0] == eos ? 0 : 1;
         } else {
             if (sampled) FL_TRY(make_sampler(&sp, m->D.V, &sampler));
             std::lock_guard<std::mutex> lock(m->mu);
-            FL_TRY(verify_step(m, c, tok, draft, nd, pos + emitted, nullptr, &sampler));
+            FL_TRY(verify_step(m, c, tok, draft, nd, pos + emitted, nullptr, &sampler, full, lp));
             n = (size_t)m->host_verify[kVerifyNacc] + 1;
             for (size_t i = 0; i < n; i++) got[i] = m->host_verify[i];
+            keep = n;
+            for (size_t i = 0; i < n; i++) if (eos >= 0 && (int64_t)got[i] == eos) { keep = i; break; }
+            // an EOS at got[i]: rows 0..i were the plain loop's steps -- their inputs are counted, the EOS's edge is walked -- the rest is dropped
+            const size_t rows = std::min(keep + 1, n);
+            if (full) FL_TRY(verify_commit(m, c, tok, draft, rows, got, rows));
+            if (lp) for (size_t i = 0; i < keep; i++) scatter_logprobs(m->host_verify_recs[i].lp, &lps, i);
         }
         if (stats) { stats->steps += 1; stats->drafted += nd; stats->accepted += n - 1; }
-        for (size_t i = 0; i < n; i++) {
-            if (eos >= 0 && (int64_t)got[i] == eos) {
-                // the forward that produced EOS was needed; what was accepted after it is dropped (fl_decode_greedy's length)
-                c->len = L0 + emitted + 1;
-                *n_out = emitted;
-                return FL_OK;
-            }
+        for (size_t i = 0; i < keep; i++) {
             tokens_out[emitted++] = got[i];
             hist.push_back(got[i]);
+        }
+        if (keep < n) {
+            // the forward that produced EOS was needed; what was accepted after it is dropped (fl_decode_greedy's length)
+            c->len = L0 + emitted + 1;
+            *n_out = emitted;
+            return FL_OK;
         }
         tok = got[n - 1];
     }
     *n_out = emitted;
     return FL_OK;
+}
+
+int decode_lookup(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                  const fl_lookup *opts, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, const fl_sampler *sampling) {
+    return lookup_loop(m, c, corpus, n_corpus, first, pos, n_steps, eos, opts, sampling, nullptr, tokens_out, n_out, stats, false, "fl_decode_lookup");
+}
+
+int decode_lookup_lp(Model *m, Cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first, size_t pos, size_t n_steps, int64_t eos,
+                     const fl_lookup *opts, const fl_sampler *sampling, const fl_logprobs *lp, uint32_t *tokens_out, size_t *n_out,
+                     fl_spec_stats *stats) {
+    return lookup_loop(m, c, corpus, n_corpus, first, pos, n_steps, eos, opts, sampling, lp, tokens_out, n_out, stats, true, "fl_decode_lookup_lp");
 }
 
 }  // namespace fl

@@ -139,6 +139,7 @@ Model::~Model() {
     if (host_logits) (void)hipHostFree(host_logits);
     if (host_tokens) (void)hipHostFree(host_tokens);
     if (host_verify) (void)hipHostFree(host_verify);
+    if (host_verify_recs) (void)hipHostFree(host_verify_recs);
     if (host_state) (void)hipHostFree(host_state);
     if (host_lp) (void)hipHostFree(host_lp);
     for (auto &r : prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }

@@ -1023,6 +1023,143 @@ struct Model {                                // mod.rs:342-361
         return n_forwards;
     }
 
+    // ... a FULL request decoded with prompt-lookup drafts (fl_decode_lookup_lp): penalties and logit_bias (rules), a response format
+    // (guide) and log-probs (top_logprobs >= 0 with `out`; < 0: none) no longer take a request out of the lookup loop.  The first token
+    // comes from the prompt's forward with the rules and the guide already installed (fl_forward_sample_ex / _lp, word 0), the other
+    // max_tokens - 1 from verify steps whose row i sees the rules table and the guide state the plain loop would hold at that step.
+    // The ids are those of the rules / guide overloads above with the same options (up to near-ties, include/fastllm_mi355x.h).
+    std::vector<uint32_t> generate_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature,
+                                       std::optional<uint32_t> eos, const SamplingOptions &opt, const LookupOptions &lookup,
+                                       const LogitRules *rules, const GuideOptions *guide, int top_logprobs = -1, TokenLogprobs *out = nullptr,
+                                       fl_spec_stats *stats = nullptr) {
+        const bool want_lp = top_logprobs >= 0;
+        if (want_lp && !out) throw Error(FL_ERR_BAD_ARGUMENT, "generate_ids: null TokenLogprobs");
+        if (top_logprobs > FL_LOGPROBS_MAX_TOP) throw Error(FL_ERR_BAD_ARGUMENT, "generate_ids: top_logprobs out of range");
+        cache = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        forwards = 0;
+        if (stats) *stats = fl_spec_stats{};
+        if (out) { *out = TokenLogprobs{}; out->top_n = want_lp ? top_logprobs : 0; }
+        std::vector<uint32_t> output_ids;
+        if (max_tokens == 0) { model.forward(Tensor::from_ids(prompt), 0, cache); forwards++; return output_ids; }
+        const size_t w = want_lp ? (size_t)top_logprobs : 0;
+        output_ids.assign(max_tokens, 0);
+        if (want_lp) { out->token.assign(max_tokens, 0.f); out->top_ids.assign(max_tokens * w, 0); out->top.assign(max_tokens * w, 0.f); }
+        auto lp_at = [&](size_t row) {
+            fl_logprobs lp{};
+            lp.struct_size = (uint32_t)sizeof(fl_logprobs);
+            lp.top_n = (int32_t)w;
+            lp.token_logprob = out->token.data() + row;
+            lp.top_ids = w ? out->top_ids.data() + row * w : nullptr;
+            lp.top_logprobs = w ? out->top.data() + row * w : nullptr;
+            return lp;
+        };
+        model.prepare(cache);
+        fl_cache *c = model.raw_cache(cache);
+        if (rules) rules->install(model.raw_model(), c, prompt);
+        if (guide) guide->install(model.raw_model(), c);
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        if (want_lp) {
+            const fl_logprobs lp0 = lp_at(0);
+            check(fl_forward_sample_lp(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0], &lp0),
+                  "Model forward pass failed");
+        } else {
+            check(fl_forward_sample_ex(model.raw_model(), c, prompt.data(), prompt.size(), model.rope_offset(0, cache), &s0, &output_ids[0]),
+                  "Model forward pass failed");
+        }
+        model.advance(cache, 1); forwards++;
+        size_t n = 0;
+        const bool ended = eos && output_ids[0] == *eos;
+        if (!ended && max_tokens > 1) {
+            const fl_sampler s1 = opt.to_ffi((double)temperature, 1);
+            const fl_lookup o = lookup.to_ffi();
+            fl_logprobs lp1{};
+            if (want_lp) lp1 = lp_at(1);
+            fl_spec_stats st{};
+            const size_t len0 = fl_cache_len(c);
+            check(fl_decode_lookup_lp(model.raw_model(), c, prompt.data(), prompt.size(), output_ids[0], model.rope_offset(prompt.size(), cache),
+                                      max_tokens - 1, eos ? (int64_t)*eos : -1, &o, &s1, want_lp ? &lp1 : nullptr, output_ids.data() + 1, &n, &st),
+                  "Model forward pass failed");
+            model.advance(cache, fl_cache_len(c) - len0);
+            forwards += (size_t)st.steps;
+            if (stats) *stats = st;
+        }
+        const size_t total = ended ? 0 : 1 + n;
+        output_ids.resize(total);
+        if (want_lp) { out->token.resize(total); out->top_ids.resize(total * w); out->top.resize(total * w); }
+        return output_ids;
+    }
+
+    // ... and as a stream: one fl_lookup_draft + fl_forward_verify_lp step at a time on the stream's own ruled / guided cache (the call
+    // counts its kept rows' inputs and walks the guide itself, so nothing is re-installed between steps), the draw position passed
+    // along; on_lp (or nullptr) receives each emitted token's log-probability record ahead of on_token.  Returns the forwards executed.
+    template <class OnToken>
+    size_t generate_stream_ids(const std::vector<uint32_t> &prompt, size_t max_tokens, float temperature, std::optional<uint32_t> eos,
+                               const SamplingOptions &opt, const LookupOptions &lookup, const LogitRules *rules, const GuideOptions *guide,
+                               OnToken &&on_token, int top_logprobs = -1,
+                               const std::function<void(float, const uint32_t *, const float *)> &on_lp = {}) const {
+        const bool want_lp = top_logprobs >= 0;
+        if (top_logprobs > FL_LOGPROBS_MAX_TOP) throw Error(FL_ERR_BAD_ARGUMENT, "generate_stream_ids: top_logprobs out of range");
+        M shared = model;
+        typename M::Cache own = M::initialize_cache(device, dtype);
+        if (prompt.empty()) throw Error(FL_ERR_BAD_ARGUMENT, "Tokenization error: empty prompt");
+        size_t n_forwards = 0;
+        if (max_tokens == 0) { shared.forward(Tensor::from_ids(prompt), 0, own); return 1; }
+        shared.prepare(own);
+        fl_cache *c = shared.raw_cache(own);
+        if (rules) rules->install(shared.raw_model(), c, prompt);
+        if (guide) guide->install(shared.raw_model(), c);
+        const size_t w = want_lp ? (size_t)top_logprobs : 0;
+        float tlp[FL_VERIFY_MAX_DRAFT + 1];
+        std::vector<uint32_t> top_ids((FL_VERIFY_MAX_DRAFT + 1) * std::max<size_t>(w, 1));
+        std::vector<float> top((FL_VERIFY_MAX_DRAFT + 1) * std::max<size_t>(w, 1));
+        fl_logprobs lp{};
+        lp.struct_size = (uint32_t)sizeof(fl_logprobs);
+        lp.top_n = (int32_t)w;
+        lp.token_logprob = tlp;
+        lp.top_ids = w ? top_ids.data() : nullptr;
+        lp.top_logprobs = w ? top.data() : nullptr;
+        auto report = [&](size_t i) { if (want_lp && on_lp) on_lp(tlp[i], top_ids.data() + i * w, top.data() + i * w); };
+        uint32_t tok = 0;
+        const fl_sampler s0 = opt.to_ffi((double)temperature, 0);
+        if (want_lp) check(fl_forward_sample_lp(shared.raw_model(), c, prompt.data(), prompt.size(), shared.rope_offset(0, own), &s0, &tok, &lp), "Model forward pass failed");
+        else check(fl_forward_sample_ex(shared.raw_model(), c, prompt.data(), prompt.size(), shared.rope_offset(0, own), &s0, &tok), "Model forward pass failed");
+        shared.advance(own, 1); n_forwards++;
+        if (eos && tok == *eos) return n_forwards;
+        report(0);
+        if (!on_token(tok)) return n_forwards;
+        const fl_lookup o = lookup.to_ffi();
+        fl_model_info info; check(fl_model_get_info(shared.raw_model(), &info), "fl_model_get_info");
+        std::vector<uint32_t> history(prompt);
+        history.push_back(tok);
+        size_t emitted = 1, pos = prompt.size();
+        uint32_t draft[FL_VERIFY_MAX_DRAFT + 1], got[FL_VERIFY_MAX_DRAFT + 1];
+        while (emitted < max_tokens) {
+            const size_t rope = shared.rope_offset(pos, own);
+            size_t limit = max_tokens - emitted - 1;
+            limit = std::min(limit, fl_cache_capacity(c) - fl_cache_len(c) - 1);
+            limit = std::min(limit, (size_t)info.cfg.max_position_embeddings - rope - 1);
+            if (info.cfg.family != FL_FAMILY_LLAMA && info.cfg.sliding_window > 0) limit = std::min(limit, (size_t)info.cfg.sliding_window);
+            size_t nd = 0, n = 0;
+            check(fl_lookup_draft(history.data(), history.size(), &o, limit, draft, &nd), "fl_lookup_draft");
+            const fl_sampler sp = opt.to_ffi((double)temperature, emitted);     // token k is drawn with word k
+            check(fl_forward_verify_lp(shared.raw_model(), c, tok, draft, nd, rope, &sp, want_lp ? &lp : nullptr, got, &n, nullptr),
+                  "Model forward pass failed");
+            n_forwards++;
+            shared.advance(own, n);
+            pos += n;
+            for (size_t i = 0; i < n; i++) {
+                if (eos && got[i] == *eos) return n_forwards;
+                report(i);
+                if (!on_token(got[i])) return n_forwards;
+                history.push_back(got[i]);
+                if (++emitted == max_tokens) return n_forwards;
+            }
+            tok = got[n - 1];
+        }
+        return n_forwards;
+    }
+
     // ModelWrapper::generate_stream + generate_tokens_inner (mod.rs:137-238, 268-340) on token ids: the model is CLONED (a
     // reference-count bump, mod.rs:155), the stream gets a FRESH cache of its own (mod.rs:156: this object's `cache` is not
     // touched, so several streams may run on one model at once, each from its own thread -- the reference spawns a task per

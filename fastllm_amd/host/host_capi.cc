@@ -441,6 +441,69 @@ int flh_generate_guide(void *hv, const uint32_t *prompt, size_t T, size_t max_to
         return 0;
     });
 }
+// ... a FULL request with prompt-lookup drafts (generate_ids / generate_stream_ids with LookupOptions + LogitRules + GuideOptions +
+// top_logprobs): has_rules != 0: the n_bias pairs and the three penalties; n_states > 0: the automaton; top_logprobs < 0: no log-probs,
+// else token_logprob [max_tokens] (and top_ids / top_lps [max_tokens][top_logprobs]) receive them; max_draft < 0: NO lookup -- the plain
+// ruled, guided generate_ids, for comparison.  stats (optional): steps, drafted, accepted of the non-stream form.
+int flh_generate_lookup_request(void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos, double top_p,
+                                int64_t top_k, int has_rules, size_t n_bias, const uint32_t *bias_ids, const float *bias_values,
+                                float repetition_penalty, float frequency_penalty, float presence_penalty, uint32_t n_states,
+                                const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state, int max_draft,
+                                int ngram_max, int ngram_min, int stream, int top_logprobs, uint32_t *out_tokens, size_t *n_out,
+                                float *token_logprob, uint32_t *top_ids, float *top_lps, size_t *forwards, uint64_t stats[3]) {
+    return guard([&] {
+        Handle *h = static_cast<Handle *>(hv);
+        if (!h || !prompt || !out_tokens || !n_out) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (n_states > 0 && (!row_ptr || !tokens || !next)) throw Error(FL_ERR_BAD_ARGUMENT, "null guide arrays");
+        if (top_logprobs >= 0 && !token_logprob) throw Error(FL_ERR_BAD_ARGUMENT, "null token_logprob");
+        std::vector<uint32_t> p(prompt, prompt + T), r;
+        std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
+        SamplingOptions opt;
+        if (top_p > 0) opt.top_p = top_p;
+        if (top_k > 0) opt.top_k = (size_t)top_k;
+        LogitRules rules;
+        if (has_rules) rules = make_rules(n_bias, bias_ids, bias_values, repetition_penalty, frequency_penalty, presence_penalty);
+        GuideOptions g;
+        if (n_states > 0) {
+            const size_t nnz = (size_t)row_ptr[n_states];
+            g.guide = Guide(model_of(h)->m, std::vector<uint64_t>(row_ptr, row_ptr + n_states + 1), std::vector<uint32_t>(tokens, tokens + nnz),
+                            std::vector<uint32_t>(next, next + nnz));
+            g.start_state = start_state;
+        }
+        const LogitRules *rp = has_rules ? &rules : nullptr;
+        const GuideOptions *gp = n_states > 0 ? &g : nullptr;
+        LookupOptions lk; lk.max_draft = max_draft; lk.ngram_max = ngram_max; lk.ngram_min = ngram_min;
+        fl_spec_stats st{};
+        TokenLogprobs lps;
+        size_t fw = 0;
+        auto run = [&](auto &m) {
+            if (max_draft < 0) { r = m.generate_ids(p, max_tokens, temperature, e, opt, rp, gp); fw = m.forwards; }
+            else if (stream) {
+                const size_t w = top_logprobs > 0 ? (size_t)top_logprobs : 0;
+                lps.top_n = (int)w;
+                fw = m.generate_stream_ids(p, max_tokens, temperature, e, opt, lk, rp, gp, [&](uint32_t t) { r.push_back(t); return true; }, top_logprobs,
+                                           [&](float v, const uint32_t *ids, const float *vals) {
+                                               lps.token.push_back(v);
+                                               lps.top_ids.insert(lps.top_ids.end(), ids, ids + w);
+                                               lps.top.insert(lps.top.end(), vals, vals + w);
+                                           });
+            } else { r = m.generate_ids(p, max_tokens, temperature, e, opt, lk, rp, gp, top_logprobs, top_logprobs >= 0 ? &lps : nullptr, &st); fw = m.forwards; }
+        };
+        if (h->llama) run(*h->llama);
+        else if (h->mistral) run(*h->mistral);
+        else run(*h->qwen);
+        for (size_t i = 0; i < r.size(); i++) out_tokens[i] = r[i];
+        *n_out = r.size();
+        if (top_logprobs >= 0 && max_draft >= 0) {
+            for (size_t i = 0; i < lps.token.size(); i++) token_logprob[i] = lps.token[i];
+            if (top_ids) for (size_t i = 0; i < lps.top_ids.size(); i++) top_ids[i] = lps.top_ids[i];
+            if (top_lps) for (size_t i = 0; i < lps.top.size(); i++) top_lps[i] = lps.top[i];
+        }
+        if (forwards) *forwards = fw;
+        if (stats) { stats[0] = st.steps; stats[1] = st.drafted; stats[2] = st.accepted; }
+        return 0;
+    });
+}
 // ... a request with a guide of its own (StreamBatcher::submit with GuideOptions); hv: the model the batcher was made for
 int flh_batcher_submit_guide(void *bv, void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
                              uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,

@@ -366,7 +366,8 @@ int fl_decode_lookup(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_
  * differently in the two loops: the sampled form of the greedy step's near-tie sentence.  Nothing else may separate them.
  * Refusals: those of the greedy calls (tensor parallelism, n_draft > sliding_window, a cache with logit rules or a guide, sizes and
  * null pointers) plus the sampler's (a wrong struct_size, a NaN top_p, a negative top_k: FL_ERR_BAD_ARGUMENT), all decided before
- * the device is touched.  Not built: logit rules, guides and log-probs inside verify steps, tensor parallelism, batches. */
+ * the device is touched.  Logit rules, guides and log-probs inside verify steps: fl_forward_verify_lp / fl_decode_lookup_lp below.
+ * Not built: tensor parallelism. */
 int fl_forward_verify_ex(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos,
                          const fl_sampler *sampler /* or NULL */, uint32_t *tokens_out /* [n_draft + 1] */, size_t *n_out,
                          float *logits_out /* [n_draft + 1][V] host, or NULL */);
@@ -712,6 +713,44 @@ int  fl_cache_set_guide(fl_model *m, fl_cache *c, fl_guide *g, uint32_t state);
 /* The state in which the next selected token is looked up.  FL_ERR_BAD_ARGUMENT: no guide installed. */
 int  fl_cache_guide_state(const fl_cache *c, uint32_t *state_out);
 
+/* ---- speculative decode for full requests: logit rules, guides and log-probs inside verify steps ------------------------------------
+ * fl_forward_verify{,_ex} and fl_decode_lookup{,_ex} understand only a sampler and KEEP REFUSING a cache with logit rules or a guide.
+ * These two calls are the superset: the same verify step and the same loop on a cache that may have rules, a guide or both, with
+ * optional log-probs (the _lp convention: sampler NULL or temperature < 1e-7 is ArgMax, lp NULL reports nothing).  One launch between
+ * lm_head and the step's selection (verify_adjust_kernel) writes the rows the selection reads; a cache with neither rules nor a guide
+ * and lp == NULL runs exactly the launches of fl_forward_verify_ex.
+ *   Counting.  Row i of a step sees the rules table that the plain ruled loop (fl_decode_sample_lp with the same rules) would hold at
+ *     its step i: that loop counts each step's INPUT token before it adjusts the row, so row i is adjusted with the table after the
+ *     inputs of rows 0..i -- token, draft[0..i).  The launch only reads the table; after the call the table has counted the inputs of
+ *     rows 0..n_acc, the rows the call kept (one small launch behind the selection, ahead of everything submitted later).  In the loop
+ *     an EOS at returned id i counts the inputs of rows 0..i only: what the plain loop holds when it draws that EOS.
+ *   Guide.  Row i is masked in the state after draft[0..i); fl_cache_guide_state afterwards is the state after the ids the call
+ *     returned, the EOS's edge included, as in the plain loop.  Rules first, mask last, as in the one-row step.
+ *   Draft trimming.  A draft id with no edge from the state reached is -inf in the row before it and can never be accepted, so both
+ *     calls cut the draft at the first such id before they forward: the returned ids do not change, logits_out holds one row per
+ *     remaining id (+ 1), and stats.drafted counts the cut draft.  Bias and penalties do not cut drafts.
+ *   Log-probs are the model's own distribution, computed from the RAW row of each returned id, whatever rules or guide chose it (as in
+ *     fl_decode_sample_lp); entry k of lp's arrays belongs to the k-th returned / emitted id.  logits_out are the raw rows.
+ *   n_draft == 0 (also after trimming), or a loop step without drafts: one step of fl_decode_sample_lp (counted, guided), bit for bit;
+ *     on a cache with neither rules nor a guide and lp == NULL, the step fl_forward_verify_ex / fl_decode_lookup_ex take there.
+ *   max_draft == 0: the loop IS fl_decode_sample_lp (on such a bare cache without lp: fl_decode_lookup_ex with max_draft == 0).
+ * GUARANTEE: that of fl_forward_verify_ex -- every emitted token is this library's sampler applied to the rule-adjusted, guide-masked
+ * logits of the preceding tokens, evaluated as a ROW OF A MULTI-ROW CALL, with the word the plain loop would use.  Logits of a
+ * multi-row call and of a one-row call differ in the last bits (more so in bf16), and a choice that lands that close to a tie or to a
+ * boundary of its cumulative interval can come out differently in the two loops.  Nothing else may separate them.
+ * Refusals: those of the _ex calls (tensor parallelism, n_draft > sliding_window, sizes, null pointers, the sampler's argument errors)
+ * plus those of fl_logprobs, all decided before the device is touched.  Not built: rules, guides and log-probs in a packed verify
+ * (fl_batch_verify), tensor parallelism, capturing the step in a graph.
+ * Memory: a model's first ruled or guided verify step allocates [16][V] fp32 of HBM (2 MB at V = 32 000, 9.7 MB at V = 152 064),
+ * its first with log-probs 16 records; both are counted in fl_model_hbm_bytes and freed with the model. */
+int fl_forward_verify_lp(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos,
+                         const fl_sampler *sampler /* or NULL */, const fl_logprobs *lp /* or NULL; arrays [n_draft + 1] */,
+                         uint32_t *tokens_out /* [n_draft + 1] */, size_t *n_out, float *logits_out /* [n_draft + 1][V] raw rows, or NULL */);
+int fl_decode_lookup_lp(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t n_corpus, uint32_t first_token, size_t pos,
+                        size_t n_steps, int64_t eos, const fl_lookup *opts, const fl_sampler *sampler /* or NULL */,
+                        const fl_logprobs *lp /* or NULL; arrays [n_steps] */, uint32_t *tokens_out, size_t *n_out,
+                        fl_spec_stats *stats /* or NULL */);
+
 int fl_synchronize(fl_model *m);
 
 /* ---- embeddings: the BERT / MiniLM encoder forward --------------------------------------------------------------------------------
@@ -976,6 +1015,23 @@ int fl_op_logit_rules(const float *logits /* [B][V] */, int64_t B, int64_t V, ui
 int fl_op_guide_mask(const float *logits /* [B][V] */, int64_t B, int64_t V, const fl_guide_desc *desc, const uint32_t *states /* [B] */,
                      const uint32_t *tokens /* [B] */, const uint8_t *has_guide /* [B] or NULL */, float *out /* [B][V] */,
                      uint32_t *next_states /* [B] */);
+
+/* verify_adjust_kernel alone, on host arrays (unit tests, tools/verify_adjust_cost.py): the rows of one verify step, logits [T][V],
+ * 1 <= T <= 16, row i's input id ids[i] (>= V: counts nothing).  Rules (words != NULL; then biases [V] and scalars = {repetition,
+ * frequency, presence penalty} too): row i is adjusted with each table word counted once per r <= i with ids[r] == its id; words is
+ * in/out and comes back AS THE LAUNCHES LEFT IT, i.e. unchanged.  Guide (desc != NULL, validated as fl_guide_create validates it
+ * against this V; states [T] < n_states): row i is masked in states[i].  At least one of the two; 1 <= V <= 1 << 24;
+ * FL_ERR_BAD_ARGUMENT otherwise (before the device is probed).  Launched twice: FL_ERR_HIP if the two results differ. */
+int fl_op_verify_adjust(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *ids /* [T] */, uint32_t *words /* [V] or NULL */,
+                        const float *biases /* [V] */, const float *scalars /* [3] */, const fl_guide_desc *desc /* or NULL */,
+                        const uint32_t *states /* [T] */, float *out /* [T][V] */);
+/* ... and timed (tools/verify_adjust_cost.py): *ms_out = ms per launch on the T rows, the mean of `iters` back-to-back launches between two
+ * events; nothing comes back and words is not written. */
+int fl_op_verify_adjust_time(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *ids /* [T] */, const uint32_t *words,
+                             const float *biases, const float *scalars, const fl_guide_desc *desc, const uint32_t *states, int32_t iters,
+                             double *ms_out);
+/* rules_count_kernel alone: ids[0 .. n), 0 <= n <= 16, counted into words [V] in order (saturating; an id >= V counts nothing). */
+int fl_op_rules_count(uint32_t *words /* [V] in/out */, int64_t V, const uint32_t *ids /* [n] */, int64_t n);
 
 /* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
  * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read

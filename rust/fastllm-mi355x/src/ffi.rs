@@ -526,6 +526,36 @@ extern "C" {
         n_out: *mut usize,
         stats: *mut fl_spec_stats,
     ) -> c_int;
+    /// The same two calls on a cache that may have logit rules and / or a guide, with optional log-probs (`lp` null: none).
+    pub fn fl_forward_verify_lp(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        token: u32,
+        draft: *const u32,
+        n_draft: usize,
+        pos: usize,
+        sampler: *const fl_sampler,
+        lp: *const fl_logprobs,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        logits_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_decode_lookup_lp(
+        m: *mut fl_model,
+        c: *mut fl_cache,
+        corpus: *const u32,
+        n_corpus: usize,
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: i64,
+        opts: *const fl_lookup,
+        sampler: *const fl_sampler,
+        lp: *const fl_logprobs,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        stats: *mut fl_spec_stats,
+    ) -> c_int;
     /// The verify steps of up to 64 streams as the rows of one packed forward, and the lookup loop built from such steps.
     pub fn fl_batch_verify(
         m: *mut fl_model,
@@ -755,6 +785,32 @@ extern "C" {
         out: *mut f32,
         next_states: *mut u32,
     ) -> c_int;
+    pub fn fl_op_verify_adjust(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        ids: *const u32,
+        words: *mut u32,
+        biases: *const f32,
+        scalars: *const f32,
+        desc: *const fl_guide_desc,
+        states: *const u32,
+        out: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_verify_adjust_time(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        ids: *const u32,
+        words: *const u32,
+        biases: *const f32,
+        scalars: *const f32,
+        desc: *const fl_guide_desc,
+        states: *const u32,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
+    pub fn fl_op_rules_count(words: *mut u32, v: i64, ids: *const u32, n: i64) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;
 

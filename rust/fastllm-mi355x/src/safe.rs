@@ -696,6 +696,65 @@ impl Model {
         Ok((toks, stats))
     }
 
+    /// `fl_decode_lookup_lp`: `decode_lookup_sampled` for a FULL request -- the cache may have logit rules (`frequency_penalty`,
+    /// `presence_penalty`, `logit_bias`) and / or a guide (`response_format`, strict tool calls) installed, and `top_n` (`None`: no
+    /// log-probs) asks for each emitted token's log-probability under the model's own distribution.  Row `i` of a verify step sees
+    /// the rules table and the guide state the plain loop (`decode_sample_logprobs` on the same cache) would hold at that step, so
+    /// the tokens, the table and the guide state afterwards are the plain loop's.  `s.temperature < 1e-7`: ArgMax.
+    pub fn decode_lookup_request(
+        &self,
+        cache: &mut Cache,
+        corpus: &[u32],
+        first_token: u32,
+        pos: usize,
+        n_steps: usize,
+        eos: Option<u32>,
+        opts: Lookup,
+        s: Sampler,
+        top_n: Option<usize>,
+    ) -> Result<(TokenLogprobs, ffi::fl_spec_stats)> {
+        let k = top_n.unwrap_or(0);
+        let mut toks = vec![0u32; n_steps.max(1)];
+        let mut token = vec![0f32; n_steps.max(1)];
+        let mut top_ids = vec![0u32; (n_steps * k).max(1)];
+        let mut top = vec![0f32; (n_steps * k).max(1)];
+        let mut n = 0usize;
+        let mut stats = ffi::fl_spec_stats::default();
+        let o = opts.to_ffi();
+        let sp = s.to_ffi();
+        let lp = ffi::fl_logprobs {
+            struct_size: std::mem::size_of::<ffi::fl_logprobs>() as u32,
+            top_n: k as i32,
+            token_logprob: token.as_mut_ptr(),
+            top_ids: if k > 0 { top_ids.as_mut_ptr() } else { ptr::null_mut() },
+            top_logprobs: if k > 0 { top.as_mut_ptr() } else { ptr::null_mut() },
+            _reserved: [0; 2],
+        };
+        check(unsafe {
+            ffi::fl_decode_lookup_lp(
+                self.raw,
+                cache.raw,
+                corpus.as_ptr(),
+                corpus.len(),
+                first_token,
+                pos,
+                n_steps,
+                eos.map(|e| e as i64).unwrap_or(-1),
+                &o,
+                &sp,
+                if top_n.is_some() { &lp } else { ptr::null() },
+                toks.as_mut_ptr(),
+                &mut n,
+                &mut stats,
+            )
+        })?;
+        toks.truncate(n);
+        token.truncate(if top_n.is_some() { n } else { 0 });
+        top_ids.truncate(n * k);
+        top.truncate(n * k);
+        Ok((TokenLogprobs { tokens: toks, token_logprob: token, top_ids, top_logprobs: top, top_n: k }, stats))
+    }
+
     pub fn synchronize(&self) -> Result<()> {
         check(unsafe { ffi::fl_synchronize(self.raw) })
     }
