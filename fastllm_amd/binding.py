@@ -169,6 +169,30 @@ class FlLinearResidArgs(C.Structure):
                 ("kernels_out", C.c_void_p)]
 
 
+class FlRopeSeqs(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("layers", C.c_int32), ("layer", C.c_int32), ("reserved", C.c_int32), ("count", C.c_void_p),
+                ("pos", C.c_void_p), ("len", C.c_void_p), ("seq_alloc", C.c_void_p), ("v_transposed", C.c_void_p), ("k_cache", C.c_void_p),
+                ("v_cache", C.c_void_p)]
+
+
+class FlRopeKvArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int32), ("dtype", C.c_int32), ("n_slab", C.c_int32), ("repeat", C.c_int32),
+                ("H", C.c_int64), ("Hkv", C.c_int64), ("d", C.c_int64), ("max_pos", C.c_int64), ("qkv", C.c_void_p), ("bias", C.c_void_p),
+                ("cos_tab", C.c_void_p), ("sin_tab", C.c_void_p), ("seqs", FlRopeSeqs), ("q_out", C.c_void_p), ("kernels_out", C.c_void_p)]
+
+
+class FlQkvRopeArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int32), ("dtype", C.c_int32), ("n_slab", C.c_int32), ("repeat", C.c_int32),
+                ("T", C.c_int64), ("K", C.c_int64), ("H", C.c_int64), ("Hkv", C.c_int64), ("d", C.c_int64), ("max_pos", C.c_int64),
+                ("vocab", C.c_int64), ("x_res", C.c_void_p), ("delta", C.c_void_p), ("norm_w", C.c_void_p), ("embed", C.c_void_p),
+                ("tokens", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p), ("bias", C.c_void_p), ("cos_tab", C.c_void_p),
+                ("sin_tab", C.c_void_p), ("eps", C.c_float), ("reserved", C.c_float), ("seqs", FlRopeSeqs), ("q_out", C.c_void_p),
+                ("x_out", C.c_void_p), ("kernels_out", C.c_void_p)]
+
+
+# kernels_out[0] of op_rope_kv
+ROPE_KV_NAMES = ("scalar", "vector", "batch", "packed")
+
 # kernel codes in the kernels_out arrays of op_norm_linear / op_linear_resid (FL_LK_* of the header)
 LK_NAMES = ("none", "gemv", "h4", "w14", "skf", "dma", "skinny", "8p", "8p_streamk", "256", "128", "4w_rope", "generic", "f32_rows", "f32_mfma")
 
@@ -336,6 +360,8 @@ def lib():
         L.fl_op_rmsnorm_add.argtypes = [vp, vp, C.c_int32, vp, C.c_float, C.c_int64, C.c_int64, C.c_int32, vp, vp]
         L.fl_op_norm_linear.argtypes = [C.POINTER(FlNormLinearArgs)]
         L.fl_op_linear_resid.argtypes = [C.POINTER(FlLinearResidArgs)]
+        L.fl_op_rope_kv.argtypes = [C.POINTER(FlRopeKvArgs)]
+        L.fl_op_qkv_rope.argtypes = [C.POINTER(FlQkvRopeArgs)]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
@@ -1551,3 +1577,87 @@ def op_linear_resid(x, w, h_in, w_next, eps, bias=None, w2=None, epi2=0, lazy=Fa
     k = dict(kernel=LK_NAMES[kernels[0]], ks=int(kernels[1]), tail=LK_NAMES[kernels[2]], tail_ks=int(kernels[3]), consumer=LK_NAMES[kernels[4]],
              consumer_reads_parts=bool(kernels[5]))
     return dict(h=h, xn=xn, inv_rms=inv, part=part, y2=y2, kernels=k)
+
+
+def _rope_seqs(st, seqs, layers, layer, bf16):
+    """fill an FlRopeSeqs from a list of dicts (count, pos, len, seq_alloc, vt, k, v); k / v: the whole caches, uint16 (bf16 bits) or
+    float32.  Returns (the copies of the caches that the call updates, arrays to keep alive)."""
+    n = len(seqs)
+    cols = [np.array([int(s[key]) for s in seqs], dtype=np.int32) for key in ("count", "pos", "len", "seq_alloc", "vt")]
+    et = np.uint16 if bf16 else np.float32
+    ks = [np.array(s["k"], dtype=et, order="C", copy=True) for s in seqs]
+    vs = [np.array(s["v"], dtype=et, order="C", copy=True) for s in seqs]
+    kp = (C.c_void_p * n)(*[a.ctypes.data for a in ks])
+    vp = (C.c_void_p * n)(*[a.ctypes.data for a in vs])
+    st.n_seq, st.layers, st.layer = n, layers, layer
+    st.count, st.pos, st.len, st.seq_alloc, st.v_transposed = (c.ctypes.data for c in cols)
+    st.k_cache, st.v_cache = C.addressof(kp), C.addressof(vp)
+    return list(zip(ks, vs)), (cols, kp, vp)
+
+
+def op_rope_kv(form, qkv, cos, sin, H, Hkv, d, seqs, dtype, bias=None, layers=1, layer=0, repeat=1):
+    """The stand-alone RoPE + KV-append kernels (fl_op_rope_kv; form 0: launch_rope_kv, 1: launch_rope_kv_batch, 2:
+    launch_rope_kv_packed).  qkv [n_slab, rows, (H + 2 Hkv) d] float32; cos / sin [max_pos, d / 2] float32; seqs: a list of dicts
+    (count, pos, len, seq_alloc, vt, k, v) with the whole caches k / v [layers, Hkv, seq_alloc, d] (v [layers, Hkv, d, seq_alloc] where
+    vt) as uint16 bf16 bits or float32 -- they are not modified.  Returns (q [rows, H d] as bits of dtype, [(k, v)] after the call,
+    kernels [4] with kernels[0] an index into ROPE_KV_NAMES)."""
+    bf16 = dtype == "bf16"
+    qkv, cos, sin = _f32(qkv), _f32(cos), _f32(sin)
+    n_slab, rows, N = qkv.shape
+    assert N == (H + 2 * Hkv) * d and cos.shape == sin.shape and cos.shape[1] == d // 2
+    bias = _f32(bias) if bias is not None else None
+    a = FlRopeKvArgs()
+    a.struct_size = C.sizeof(FlRopeKvArgs)
+    a.form, a.dtype, a.n_slab, a.repeat = form, BF16 if bf16 else F32, n_slab, repeat
+    a.H, a.Hkv, a.d, a.max_pos = H, Hkv, d, cos.shape[0]
+    a.qkv, a.bias, a.cos_tab, a.sin_tab = qkv.ctypes.data, _ptr(bias), cos.ctypes.data, sin.ctypes.data
+    caches, keep = _rope_seqs(a.seqs, seqs, layers, layer, bf16)
+    q = np.empty((rows, H * d), np.uint16 if bf16 else np.float32)
+    kernels = np.zeros(4, np.int32)
+    a.q_out, a.kernels_out = q.ctypes.data, kernels.ctypes.data
+    _check(lib().fl_op_rope_kv(C.byref(a)))
+    del keep
+    return q, caches, kernels
+
+
+def op_qkv_rope(form, w, norm_w, eps, cos, sin, H, Hkv, d, seqs, dtype, x_res=None, delta=None, embed=None, tokens=None, bias=None,
+                w_scale=None, layers=1, layer=0, repeat=1):
+    """Residual add -> RMSNorm -> QKV projection with RoPE and the KV append behind it (fl_op_qkv_rope; form 0: the prompt path by
+    plan_qkv_rope, 1: the single-sequence stream, 2: the same over FP8 weights (w uint8 + w_scale), 3: the batched stream).  w [N, K]
+    in dtype; the norm's inputs as op_norm_linear; cos / sin / seqs as op_rope_kv.  Returns (q [T, H d] as bits of dtype, [(k, v)]
+    after the call, x_out [T, K], kernels [4])."""
+    bf16 = dtype == "bf16"
+    w = np.ascontiguousarray(w)
+    N, K = w.shape
+    cos, sin, norm_w = _f32(cos), _f32(sin), _f32(norm_w)
+    assert N == (H + 2 * Hkv) * d and cos.shape == sin.shape and cos.shape[1] == d // 2 and norm_w.shape == (K,)
+    a = FlQkvRopeArgs()
+    a.struct_size = C.sizeof(FlQkvRopeArgs)
+    a.form, a.dtype, a.repeat, a.eps = form, BF16 if bf16 else F32, repeat, eps
+    a.K, a.H, a.Hkv, a.d, a.max_pos = K, H, Hkv, d, cos.shape[0]
+    if embed is not None:
+        embed = np.ascontiguousarray(embed)
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        T = tokens.shape[0]
+        assert embed.shape[1] == K
+        a.embed, a.tokens, a.vocab = embed.ctypes.data, tokens.ctypes.data, embed.shape[0]
+    else:
+        x_res = _f32(x_res)
+        T = x_res.shape[0]
+        assert x_res.shape == (T, K)
+        a.x_res = x_res.ctypes.data
+    if delta is not None:
+        delta = _f32(delta)
+        assert delta.shape[1:] == (T, K)
+        a.delta, a.n_slab = delta.ctypes.data, delta.shape[0]
+    bias = _f32(bias) if bias is not None else None
+    w_scale = _f32(w_scale) if w_scale is not None else None
+    a.T, a.w, a.norm_w, a.bias, a.w_scale, a.cos_tab, a.sin_tab = T, w.ctypes.data, norm_w.ctypes.data, _ptr(bias), _ptr(w_scale), cos.ctypes.data, sin.ctypes.data
+    caches, keep = _rope_seqs(a.seqs, seqs, layers, layer, bf16)
+    q = np.empty((T, H * d), np.uint16 if bf16 else np.float32)
+    x_out = np.empty((T, K), np.float32)
+    kernels = np.zeros(4, np.int32)
+    a.q_out, a.x_out, a.kernels_out = q.ctypes.data, x_out.ctypes.data, kernels.ctypes.data
+    _check(lib().fl_op_qkv_rope(C.byref(a)))
+    del keep
+    return q, caches, x_out, kernels

@@ -179,6 +179,167 @@ int norm_linear_check(const fl_norm_linear_args *a) {
     return FL_OK;
 }
 
+// ---- the RoPE + KV-append ops: what fl_op_rope_kv and fl_op_qkv_rope share ---------------------------------------------------------
+
+// the checks of an fl_rope_seqs that need no device; *rows_out: the rows of the call
+int rope_seqs_check(const char *who, const fl_rope_seqs &q, int32_t dtype, int64_t H, int64_t Hkv, int64_t d, int64_t max_pos, const float *cos_tab,
+                    const float *sin_tab, const void *q_out, int64_t *rows_out) {
+    if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "%s: dtype must be bf16 or f32", who);
+    if (H < 1 || Hkv < 1 || H > 1024 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: bad head counts (H %lld a multiple of Hkv %lld)", who, (long long)H, (long long)Hkv);
+    if (d < 2 || d > 1024 || d % 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: head_dim %lld must be even (2..1024)", who, (long long)d);
+    if (max_pos < 1 || max_pos > (1 << 24) || !cos_tab || !sin_tab) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: cos_tab / sin_tab [max_pos][d / 2], 1 <= max_pos <= 2^24", who);
+    if (!q_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null q_out", who);
+    if (q.n_seq < 1 || q.n_seq > 1024) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: n_seq %d not in 1..1024", who, q.n_seq);
+    if (q.layers < 1 || q.layers > 64 || q.layer < 0 || q.layer >= q.layers) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: layer %d not below layers %d (1..64)", who, q.layer, q.layers);
+    if (!q.count || !q.pos || !q.len || !q.seq_alloc || !q.v_transposed || !q.k_cache || !q.v_cache) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null per-sequence array", who);
+    int64_t rows = 0;
+    for (int s = 0; s < q.n_seq; s++) {
+        if (!q.k_cache[s] || !q.v_cache[s]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: sequence %d: null cache", who, s);
+        if (q.count[s] < 1 || q.pos[s] < 0 || q.len[s] < 0 || q.seq_alloc[s] < 1 || q.seq_alloc[s] > (1 << 24) || q.count[s] > (1 << 20))
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: sequence %d: count >= 1, pos >= 0, len >= 0, seq_alloc >= 1", who, s);
+        if ((int64_t)q.len[s] + q.count[s] > q.seq_alloc[s])
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: sequence %d: len %d + count %d exceeds seq_alloc %d", who, s, q.len[s], q.count[s], q.seq_alloc[s]);
+        if ((int64_t)q.pos[s] + q.count[s] > max_pos)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: sequence %d: pos %d + count %d exceeds max_pos %lld", who, s, q.pos[s], q.count[s], (long long)max_pos);
+        rows += q.count[s];
+    }
+    if (rows > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: too many rows", who);
+    *rows_out = rows;
+    return FL_OK;
+}
+
+// The sequences on the device: every cache an allocation of its own with a pristine copy beside it (a repeated launch starts from the
+// caller's bytes), a StepState per sequence and the SeqRef array the batched and the packed kernels read.
+struct RopeSeqsDev {
+    std::vector<void *> k, v, k0, v0;
+    std::vector<size_t> bytes;           // of one cache: layers * Hkv * seq_alloc * d elements
+    std::vector<SeqRef> refs;
+    StepState *st = nullptr;             // [n_seq]
+    SeqRef *refs_dev = nullptr;
+    size_t total = 0;                    // K and V bytes of all sequences
+
+    int upload(OpScope &B, const fl_rope_seqs &q, int64_t Hkv, int64_t d, size_t es, const uint32_t *tokens) {
+        const size_t n = (size_t)q.n_seq;
+        k.resize(n); v.resize(n); k0.resize(n); v0.resize(n); bytes.resize(n); refs.assign(n, SeqRef{});
+        std::vector<StepState> sts(n);
+        FL_TRY(B.alloc(&st, sizeof(StepState) * n));
+        for (size_t s = 0; s < n; s++) {
+            bytes[s] = (size_t)q.layers * Hkv * q.seq_alloc[s] * d * es;
+            total += 2 * bytes[s];
+            FL_TRY(B.upload(&k0[s], q.k_cache[s], bytes[s])); FL_TRY(B.upload(&v0[s], q.v_cache[s], bytes[s]));
+            FL_TRY(B.alloc(&k[s], bytes[s])); FL_TRY(B.alloc(&v[s], bytes[s]));
+            sts[s] = StepState{};
+            sts[s].token = tokens ? tokens[s] : 0u; sts[s].pos = (uint32_t)q.pos[s]; sts[s].len = (uint32_t)q.len[s]; sts[s].call0 = sts[s].len; sts[s].eos = -1;
+            refs[s].st = st + s; refs[s].k = k[s]; refs[s].v = v[s]; refs[s].seq_alloc = q.seq_alloc[s]; refs[s].nsplit = 1;
+        }
+        FL_HIP(hipMemcpy(st, sts.data(), sizeof(StepState) * n, hipMemcpyHostToDevice));
+        return B.upload(&refs_dev, refs.data(), sizeof(SeqRef) * n);
+    }
+    int restore(OpScope &B) {
+        for (size_t s = 0; s < k.size(); s++) {
+            FL_HIP(hipMemcpyAsync(k[s], k0[s], bytes[s], hipMemcpyDeviceToDevice, B.s));
+            FL_HIP(hipMemcpyAsync(v[s], v0[s], bytes[s], hipMemcpyDeviceToDevice, B.s));
+        }
+        return FL_OK;
+    }
+    int download(unsigned char *o) const {                        // K | V of sequence 0, of sequence 1, ...
+        for (size_t s = 0; s < k.size(); s++) {
+            FL_HIP(hipMemcpy(o, k[s], bytes[s], hipMemcpyDeviceToHost)); o += bytes[s];
+            FL_HIP(hipMemcpy(o, v[s], bytes[s], hipMemcpyDeviceToHost)); o += bytes[s];
+        }
+        return FL_OK;
+    }
+    void give_back(const fl_rope_seqs &q, const unsigned char *o) const {
+        for (size_t s = 0; s < k.size(); s++) {
+            memcpy(q.k_cache[s], o, bytes[s]); o += bytes[s];
+            memcpy(q.v_cache[s], o, bytes[s]); o += bytes[s];
+        }
+    }
+};
+
+// `repeat` runs of run() from the caller's caches and a NaN-filled q: the bytes q | caches of the first one into `first`, FL_ERR_HIP if a
+// later one differs
+template <typename Run>
+int rope_op_repeat(OpScope &B, const char *who, RopeSeqsDev &sq, void *qd, size_t qbytes, float *xo, size_t xbytes, int repeat, std::vector<unsigned char> &first, Run run) {
+    std::vector<unsigned char> again;
+    for (int rep = 0; rep < repeat; rep++) {
+        FL_TRY(sq.restore(B));
+        FL_HIP(hipMemsetAsync(qd, 0xff, qbytes, B.s));            // NaN pattern: an element no launch writes shows up
+        if (xo) FL_HIP(hipMemsetAsync(xo, 0xff, xbytes, B.s));
+        FL_TRY(run());
+        FL_HIP(hipStreamSynchronize(B.s));
+        std::vector<unsigned char> &o = rep ? again : first;
+        o.resize(qbytes + xbytes + sq.total);
+        FL_HIP(hipMemcpy(o.data(), qd, qbytes, hipMemcpyDeviceToHost));
+        if (xo) FL_HIP(hipMemcpy(o.data() + qbytes, xo, xbytes, hipMemcpyDeviceToHost));
+        FL_TRY(sq.download(o.data() + qbytes + xbytes));
+        if (rep && first != again) FL_FAIL(FL_ERR_HIP, "%s: launch %d gave other bytes than the first", who, rep);
+    }
+    return FL_OK;
+}
+
+// the fl_op_rope_kv checks that need no device
+int rope_kv_check(const fl_rope_kv_args *a, int64_t *rows_out) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: null args");
+    if (a->struct_size != sizeof(fl_rope_kv_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_rope_kv_args));
+    if (a->form < 0 || a->form > 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: form %d not in 0..2", a->form);
+    if (!a->qkv) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: null qkv");
+    if (a->n_slab < 1 || a->n_slab > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: n_slab %d not in 1..64", a->n_slab);
+    if (a->repeat < 1 || a->repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: repeat %d not in 1..8", a->repeat);
+    FL_TRY(rope_seqs_check("fl_op_rope_kv", a->seqs, a->dtype, a->H, a->Hkv, a->d, a->max_pos, a->cos_tab, a->sin_tab, a->q_out, rows_out));
+    const fl_rope_seqs &q = a->seqs;
+    if (a->form == 0 && q.n_seq != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: form 0 takes one sequence");
+    if (a->form == 1) {
+        for (int s = 0; s < q.n_seq; s++) {
+            if (q.count[s] != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_rope_kv: form 1 takes one row per sequence");
+            if ((q.v_transposed[s] != 0) != (q.v_transposed[0] != 0)) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_rope_kv: form 1: one value layout for the whole batch");
+        }
+        if (a->dtype == FL_DTYPE_F32 && q.v_transposed[0]) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_rope_kv: form 1: fp32 caches keep V row-major");
+    }
+    return FL_OK;
+}
+
+// the fl_op_qkv_rope checks that need no device
+int qkv_rope_check(const fl_qkv_rope_args *a) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: null args");
+    if (a->struct_size != sizeof(fl_qkv_rope_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_qkv_rope_args));
+    if (a->form < 0 || a->form > 3) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form %d not in 0..3", a->form);
+    if (!a->w || !a->norm_w) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: null argument (w, norm_w)");
+    if (a->T <= 0 || a->T > (1 << 20) || a->K <= 0 || a->K % 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: bad shape (K must be a multiple of 8)");
+    if (a->repeat < 1 || a->repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: repeat %d not in 1..8", a->repeat);
+    if (a->n_slab < 0 || a->n_slab > 64 || (a->n_slab > 0) != (a->delta != nullptr)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: n_slab 0..64, with delta exactly when it is not 0");
+    if (a->embed) {
+        if (a->x_res || a->delta || !a->tokens || a->vocab < 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: embed takes tokens and a vocab size, and neither x_res nor delta");
+        for (int64_t t = 0; t < a->T; t++)
+            if ((int64_t)a->tokens[t] >= a->vocab) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: tokens[%lld] = %u is not below vocab %lld", (long long)t, a->tokens[t], (long long)a->vocab);
+    } else if (!a->x_res) {
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: null x_res (and no embed)");
+    }
+    int64_t rows = 0;
+    FL_TRY(rope_seqs_check("fl_op_qkv_rope", a->seqs, a->dtype, a->H, a->Hkv, a->d, a->max_pos, a->cos_tab, a->sin_tab, a->q_out, &rows));
+    if (rows != a->T) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: the sequences' counts give %lld rows, T is %lld", (long long)rows, (long long)a->T);
+    const fl_rope_seqs &q = a->seqs;
+    const int64_t N = (a->H + 2 * a->Hkv) * a->d;
+    if (a->form != 3 && q.n_seq != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form %d takes one sequence", a->form);
+    if (a->form == 1) {
+        if (a->T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form 1: the single-sequence stream takes one row");
+        if (!gemv_norm_supported(a->dtype, N, a->K)) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 1: the norm prologue needs K <= 6144");
+    } else if (a->form == 2) {
+        if (a->T != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form 2: the single-sequence stream takes one row");
+        if (!a->w_scale) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form 2: null w_scale");
+        if (a->dtype != FL_DTYPE_BF16 || a->n_slab > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 2: bf16 activations, at most one delta vector");
+        if (!gemv_w8_norm_supported(N, a->K)) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 2: K a multiple of 16, at most 6144");
+    } else if (a->form == 3) {
+        if (a->T > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form 3: at most 8 rows");
+        if (q.n_seq != a->T) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_qkv_rope: form 3: one sequence per row");
+        if (a->dtype != FL_DTYPE_BF16) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 3: bf16");
+        for (int s = 0; s < q.n_seq; s++)
+            if (!q.v_transposed[s]) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 3: the batched stream appends to transposed value caches");
+        if (gemv_batch_ksplit((int)a->T, a->K, 0, EPI_QKV_ROPE) != 1) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 3: K %lld needs K slices, which the RoPE epilogue cannot take", (long long)a->K);
+    }
+    return FL_OK;
+}
+
 int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, int64_t d) {
     if ((dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) || layout < 0 || layout > 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype: bf16 or f32; layout: 0 plain, 1 MFMA");
     if (H < 1 || Hkv < 1 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head counts (H a multiple of Hkv)");
@@ -1422,6 +1583,146 @@ int fl_op_linear_resid(const fl_linear_resid_args *args) {
         } else if (y2) {
             memcpy(a.y2_out, first.data() + off_y2, y2bytes);
         }
+        return FL_OK;
+    });
+}
+
+int fl_op_rope_kv(const fl_rope_kv_args *args) {
+    return guarded([&]() -> int {
+        int64_t rows = 0;
+        FL_TRY(rope_kv_check(args, &rows));
+        const fl_rope_kv_args &a = *args;
+        const fl_rope_seqs &q = a.seqs;
+        OpScope B;
+        FL_TRY(B.begin());
+        const int dtype = a.dtype, form = a.form;
+        const int64_t H = a.H, Hkv = a.Hkv, d = a.d, N = (H + 2 * Hkv) * d;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, qbytes = (size_t)rows * H * d * es;
+        float *qkv, *bd = nullptr, *ct, *sn; void *qd;
+        FL_TRY(B.upload(&qkv, a.qkv, (size_t)a.n_slab * rows * N * 4));
+        if (a.bias) FL_TRY(B.upload(&bd, a.bias, (size_t)N * 4));
+        FL_TRY(B.upload(&ct, a.cos_tab, (size_t)a.max_pos * (d / 2) * 4));
+        FL_TRY(B.upload(&sn, a.sin_tab, (size_t)a.max_pos * (d / 2) * 4));
+        FL_TRY(B.alloc(&qd, qbytes));
+        RopeSeqsDev sq;
+        FL_TRY(sq.upload(B, q, Hkv, d, es, nullptr));
+        const size_t kv_layer_off = (size_t)q.layer * Hkv * d;       // times a sequence's seq_alloc: its layer, in elements
+        const bool vt0 = q.v_transposed[0] != 0;
+        const bool vec = form == 0 && rope_kv_takes_vec(dtype, vt0, rows, d, q.seq_alloc[0]);
+        PackedHost ph;
+        void *tabd = nullptr;
+        if (form == 2) {
+            std::vector<int> counts(q.count, q.count + q.n_seq), vt(q.n_seq);
+            for (int s = 0; s < q.n_seq; s++) vt[(size_t)s] = q.v_transposed[s] ? 1 : 0;
+            packed_table_build(sq.refs.data(), counts.data(), vt.data(), q.n_seq, H, Hkv, d, &ph);
+            FL_TRY(B.upload(&tabd, ph.bytes.data(), ph.bytes.size()));
+        }
+        if (a.kernels_out) {
+            a.kernels_out[0] = form == 0 ? (vec ? 1 : 0) : form + 1; a.kernels_out[1] = dtype; a.kernels_out[2] = form < 2 && vt0 ? 1 : 0;
+            a.kernels_out[3] = vec ? (int)((rows * (H + Hkv) * (d / 16) + 255) / 256) : 0;
+        }
+        std::vector<unsigned char> first;
+        FL_TRY(rope_op_repeat(B, "fl_op_rope_kv", sq, qd, qbytes, nullptr, 0, a.repeat, first, [&]() -> int {
+            if (form == 0) {
+                const size_t off = kv_layer_off * (size_t)q.seq_alloc[0] * es;
+                return launch_rope_kv(B.L, dtype, qkv, sq.st, ct, sn, a.max_pos, qd, (char *)sq.k[0] + off, (char *)sq.v[0] + off, rows, H, Hkv, d, q.seq_alloc[0],
+                                      vt0, a.n_slab, bd);
+            }
+            if (form == 1) return launch_rope_kv_batch(B.L, qkv, sq.refs_dev, ct, sn, a.max_pos, qd, kv_layer_off, q.n_seq, H, Hkv, d, a.n_slab, bd, dtype, vt0);
+            return launch_rope_kv_packed(B.L, dtype, qkv, ph.at(tabd), ct, sn, a.max_pos, qd, kv_layer_off, rows, H, Hkv, d, a.n_slab, bd);
+        }));
+        memcpy(a.q_out, first.data(), qbytes);
+        sq.give_back(q, first.data() + qbytes);
+        return FL_OK;
+    });
+}
+
+int fl_op_qkv_rope(const fl_qkv_rope_args *args) {
+    return guarded([&]() -> int {
+        FL_TRY(qkv_rope_check(args));
+        const fl_qkv_rope_args &a = *args;
+        const fl_rope_seqs &q = a.seqs;
+        OpScope B;
+        FL_TRY(B.begin());
+        const int dtype = a.dtype, form = a.form;
+        const int64_t T = a.T, K = a.K, H = a.H, Hkv = a.Hkv, d = a.d, N = (H + 2 * Hkv) * d;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, nx = (size_t)T * K, qbytes = (size_t)T * H * d * es;
+        // the plan of the prompt path, as enqueue_forward asks for it
+        const LinearPlan qp = form == 0 ? plan_qkv_rope(dtype, T, N, K, d, d * Hkv, B.L.tp, qkv_split(T)) : LinearPlan{};
+        if (form == 0 && qp.rope && d != 64 && d != 128) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_qkv_rope: form 0: the RoPE epilogue takes head_dim 64 / 128");
+        if (a.kernels_out) {
+            a.kernels_out[0] = form == 0 ? qp.kernel : (int)LK_GEMV; a.kernels_out[1] = form == 0 ? qp.ks : 1; a.kernels_out[2] = form == 0 && qp.n_main < N ? qp.tail : (int)LK_NONE;
+            a.kernels_out[3] = form != 0 || qp.rope ? 1 : 0;
+        }
+        void *wd; float *sd = nullptr, *bd = nullptr, *ct, *sn, *nw;
+        FL_TRY(B.upload(&wd, a.w, (size_t)N * K * (form == 2 ? 1 : es)));
+        if (form == 2) FL_TRY(B.upload(&sd, a.w_scale, (size_t)N * 4));
+        if (a.bias) FL_TRY(B.upload(&bd, a.bias, (size_t)N * 4));
+        FL_TRY(B.upload(&ct, a.cos_tab, (size_t)a.max_pos * (d / 2) * 4));
+        FL_TRY(B.upload(&sn, a.sin_tab, (size_t)a.max_pos * (d / 2) * 4));
+        FL_TRY(B.upload(&nw, a.norm_w, (size_t)K * 4));
+        // the norm's inputs, as fl_op_norm_linear holds them
+        float *xr0 = nullptr, *xr = nullptr, *xo = nullptr, *dd = nullptr, *inv = nullptr, *yd = nullptr;
+        void *xs = nullptr, *ed = nullptr, *qd; uint32_t *ids = nullptr;
+        FL_TRY(B.alloc(&qd, qbytes));
+        FL_TRY(B.alloc(&xo, nx * 4));
+        if (a.delta) FL_TRY(B.upload(&dd, a.delta, nx * 4 * a.n_slab));
+        if (a.embed) {
+            FL_TRY(B.upload(&ed, a.embed, (size_t)a.vocab * K * es));
+            FL_TRY(B.upload(&ids, a.tokens, (size_t)T * 4));
+        } else {
+            FL_TRY(B.upload(&xr0, a.x_res, nx * 4));
+        }
+        if (form == 0) {
+            FL_TRY(B.alloc(&xs, nx * es));
+            FL_TRY(B.alloc(&inv, (size_t)T * 4));
+            if (!qp.rope) FL_TRY(B.alloc(&yd, (size_t)T * N * 4 * std::max(qp.n_split, 1)));
+            xr = xo;                                                 // form 0 updates the residual rows in place: they are its x_out
+        }
+        RopeSeqsDev sq;
+        FL_TRY(sq.upload(B, q, Hkv, d, es, a.embed ? a.tokens : nullptr));
+        const int64_t sa = q.seq_alloc[0];
+        const size_t kv_layer_off = (size_t)q.layer * Hkv * d, off0 = kv_layer_off * (size_t)sa * es;
+        const bool vt0 = q.v_transposed[0] != 0;
+        std::vector<unsigned char> first;
+        FL_TRY(rope_op_repeat(B, "fl_op_qkv_rope", sq, qd, qbytes, xo, nx * 4, a.repeat, first, [&]() -> int {
+            void *kl = (char *)sq.k[0] + off0, *vl = (char *)sq.v[0] + off0;
+            if (form == 0) {
+                if (a.embed) FL_TRY(launch_embed(B.L, dtype, ed, ids, nullptr, xr, T, K));
+                else FL_HIP(hipMemcpyAsync(xr, xr0, nx * 4, hipMemcpyDeviceToDevice, B.s));
+                FL_TRY(launch_rmsnorm_add(B.L, dtype, xr, dd, nw, a.eps, xs, inv, T, K, std::max(a.n_slab, 1), (int64_t)nx));
+                if (qp.rope) {
+                    RopeEpi ro;
+                    ro.st = sq.st; ro.cos_tab = ct; ro.sin_tab = sn; ro.max_pos = (int)a.max_pos; ro.q_out = qd; ro.k_cache = kl; ro.v_cache = vl;
+                    ro.H = (int)H; ro.Hkv = (int)Hkv; ro.d = (int)d; ro.max_seq = (int)sa; ro.v_transposed = vt0 ? 1 : 0;
+                    return launch_plan(B.L, qp, dtype, wd, xs, bd, nullptr, T, N, K, EPI_QKV_ROPE, inv, nullptr, &ro);
+                }
+                FL_HIP(hipMemsetAsync(yd, 0xff, (size_t)T * N * 4 * std::max(qp.n_split, 1), B.s));
+                FL_TRY(launch_plan(B.L, qp, dtype, wd, xs, nullptr, yd, T, N, K, EPI_F32, inv));
+                return launch_rope_kv(B.L, dtype, yd, sq.st, ct, sn, a.max_pos, qd, kl, vl, T, H, Hkv, d, sa, vt0, qp.n_split, bd);
+            }
+            if (form == 3) {
+                GemvBatchArgs ga;
+                ga.B = (int)T; ga.seqs = sq.refs_dev; ga.W = wd; ga.bias = bd; ga.N = (int)N; ga.K = (int)K; ga.nks = 1;
+                ga.epi = EPI_QKV_ROPE; ga.pro = PRO_NORM; ga.norm_w = nw; ga.eps = a.eps; ga.x_out = xo;
+                if (a.embed) ga.embed = ed;
+                else { ga.x_in = xr0; ga.delta = dd; ga.n_slab = std::max(a.n_slab, 1); ga.slab_stride = (long long)nx; }
+                ga.cos_tab = ct; ga.sin_tab = sn; ga.q_out = qd; ga.kv_layer_off = kv_layer_off;
+                ga.H = (int)H; ga.Hkv = (int)Hkv; ga.d = (int)d; ga.max_pos = (int)a.max_pos;
+                return launch_gemv_batch(B.L, ga);
+            }
+            GemvArgs ga;                                             // as qkv_gemv_args (model.hip) lays it out
+            ga.W = wd; ga.bias = bd; ga.N = (int)N; ga.K = (int)K; ga.epi = EPI_QKV_ROPE; ga.pro = PRO_NORM; ga.norm_w = nw; ga.eps = a.eps; ga.st = sq.st;
+            ga.x_out = xo;
+            if (a.embed) ga.embed = ed;
+            else { ga.x_in = xr0; ga.delta = dd; ga.delta_nslab = std::max(a.n_slab, 1); }
+            ga.cos_tab = ct; ga.sin_tab = sn; ga.q_out = qd; ga.k_cache = kl; ga.v_cache = vl;
+            ga.H = (int)H; ga.Hkv = (int)Hkv; ga.d = (int)d; ga.max_seq = (int)sa; ga.max_pos = (int)a.max_pos; ga.v_ld = vt0 ? (int)sa : 0;
+            return form == 1 ? launch_gemv(B.L, dtype, ga) : launch_gemv_w8(B.L, ga, sd);
+        }));
+        memcpy(a.q_out, first.data(), qbytes);
+        if (a.x_out) memcpy(a.x_out, first.data() + qbytes, nx * 4);
+        sq.give_back(q, first.data() + qbytes + nx * 4);
         return FL_OK;
     });
 }

@@ -299,6 +299,18 @@ __device__ inline void rope_rotate(float x0, float x1, float c, float s, float &
     t0 = __fsub_rn(__fmul_rn(x0, c), __fmul_rn(x1, s));
     t1 = __fadd_rn(__fmul_rn(x0, s), __fmul_rn(x1, c));
 }
+// CAUTION: hipcc's __fmul_rn / __fsub_rn / __fadd_rn are inline functions around the plain * - +, and -ffp-contract=fast fuses them
+// after inlining (k_pool.hip met the same): rope_rotate above compiles to one product and one v_fma / v_fmac per output, within an
+// fp32 ulp of the separately rounded form.  The fused epilogues that call it (gemv_parts.h, k_gemv_batch.hip, gemm_w4.h,
+// k_gemm_skf.hip) are kept as they are -- a greedy token stream of a whole model follows their bits -- and are tested under a bound
+// that has room for either form.  The stand-alone kernels (rope_kv_store below, rope_kv_vec_kernel) use this one, whose operators
+// stand under the pragma: four products and two sums, each rounded once, which tests/test_gpu_rope_ops.py compares bit for bit.
+__device__ inline void rope_rotate_exact(float x0, float x1, float c, float s, float &t0, float &t1) {
+#pragma clang fp contract(off)
+    const float p0 = x0 * c, p1 = x1 * s, p2 = x0 * s, p3 = x1 * c;
+    t0 = p0 - p1;
+    t1 = p2 + p3;
+}
 
 // ---- the scalar RoPE + KV append, one thread per (row, head, j < d/2) pair.  rope_kv_kernel, rope_kv_batch_kernel (k_ops.hip) and
 // rope_kv_packed_kernel (k_prefill_packed.hip) differ in where a row's position, cache slot and destinations come from: each loads
@@ -337,7 +349,7 @@ __device__ __forceinline__ void rope_kv_store(const RopeKvPair &p, uint32_t pos,
     if (hd < H + Hkv) {
         const uint32_t pp = pos < (uint32_t)max_pos ? pos : (uint32_t)max_pos - 1;   // host validates range
         float ra, rb;
-        rope_rotate(p.a, p.b, cos_tab[(size_t)pp * half + j], sin_tab[(size_t)pp * half + j], ra, rb);
+        rope_rotate_exact(p.a, p.b, cos_tab[(size_t)pp * half + j], sin_tab[(size_t)pp * half + j], ra, rb);
         CT *o = hd < H ? static_cast<CT *>(dst.q_row) + (size_t)hd * d
                        : static_cast<CT *>(*dst.k_base) + dst.layer + ((size_t)(hd - H) * dst.sa + slot) * d;
         elem<CT>::st(o + j, ra); elem<CT>::st(o + j + half, rb);

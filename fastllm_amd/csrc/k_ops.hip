@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void rope_kv_vec_kernel(const float *__restric
         float c[8], sn[8], ra[8], rb[8];
         load8(cos_tab + (size_t)p * half + j0, c); load8(sin_tab + (size_t)p * half + j0, sn);
 #pragma unroll
-        for (int j = 0; j < 8; j++) rope_rotate(a[j], b[j], c[j], sn[j], ra[j], rb[j]);     // (separately rounded products, as every other RoPE site)
+        for (int j = 0; j < 8; j++) rope_rotate_exact(a[j], b[j], c[j], sn[j], ra[j], rb[j]);     // (separately rounded products, as the scalar kernels)
         bf16_t *o = hd < H ? q_out + ((size_t)t * H + hd) * d + j0 : kc + ((size_t)(hd - H) * max_seq + len + t) * d + j0;
         store8(o, ra); store8(o + half, rb);
         return;
@@ -216,6 +216,10 @@ __global__ __launch_bounds__(256) void rope_kv_vec_kernel(const float *__restric
     }
 }
 
+bool rope_kv_takes_vec(int dtype, bool v_transposed, int64_t T, int64_t d, int64_t max_seq) {
+    return tune(TK_ROPE_VEC) && dtype == FL_DTYPE_BF16 && v_transposed && T >= 16 && d % 64 == 0 && max_seq % 8 == 0;
+}
+
 int launch_rope_kv(Launcher &L, int dtype, const float *qkv, const StepState *st, const float *cos_tab,
                    const float *sin_tab, int64_t max_pos, void *q_out, void *k_cache, void *v_cache,
                    int64_t T, int64_t H, int64_t Hkv, int64_t d, int64_t max_seq, bool v_transposed, int nslab, const float *bias) {
@@ -224,8 +228,7 @@ int launch_rope_kv(Launcher &L, int dtype, const float *qkv, const StepState *st
     const unsigned blocks = (unsigned)((total + 255) / 256);
     const int es = dtype == FL_DTYPE_BF16 ? 2 : 4;
     double bytes = (double)T * (H + 2 * Hkv) * d * (4 + es);
-    const int use_vec = tune(TK_ROPE_VEC);
-    if (use_vec && dtype == FL_DTYPE_BF16 && v_transposed && T >= 16 && d % 64 == 0 && max_seq % 8 == 0) {
+    if (rope_kv_takes_vec(dtype, v_transposed, T, d, max_seq)) {
         const int64_t itemsA = T * (H + Hkv) * (d / 16);
         const int nA = (int)((itemsA + 255) / 256), nB = (int)(((T + 31) / 32) * Hkv * (d / 64));
         return L.launch(KC_ROPE_KV, bytes, 0, rope_kv_vec_kernel, dim3((unsigned)(nA + nB)), dim3(256), 0, qkv, st, cos_tab, sin_tab,

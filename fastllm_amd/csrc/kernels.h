@@ -414,6 +414,7 @@ int launch_rope_kv(Launcher &L, int dtype, const float *qkv, const StepState *st
                    int64_t T, int64_t H, int64_t Hkv, int64_t d, int64_t max_seq, bool v_transposed, int nslab = 1,
                    const float *bias = nullptr);   // bias: the QKV projection's, when it ran in K slices (added after the slabs are summed)
 // (nslab > 1: qkv is nslab split-K slabs of [T][(H+2Hkv)*d], summed here in slab order)
+bool rope_kv_takes_vec(int dtype, bool v_transposed, int64_t T, int64_t d, int64_t max_seq);   // launch_rope_kv's rule for rope_kv_vec_kernel
 // logits[V] -> st->token by ArgMax (ties: last max index) or, when ss->on, by temperature sampling with
 // the seeded ChaCha12 stream; out_tokens[st->step] = token; advances pos/len/step
 int launch_select_advance(Launcher &L, const float *logits, int64_t V, StepState *st, SampleState *ss, float *scratch /* [V] */,

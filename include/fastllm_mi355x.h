@@ -942,6 +942,68 @@ typedef struct fl_linear_resid_args {
 } fl_linear_resid_args;
 int fl_op_linear_resid(const fl_linear_resid_args *args);
 
+/* ---- QKV projection -> RoPE -> KV append in each of its forms, on host buffers (unit tests) -------------------------------------- */
+
+/* The sequences of one call, shared by the two calls below.  Sequence s brings count[s] new rows (the rows of all sequences back to
+ * back), rotated at positions pos[s] + t and appended at slots len[s] + t of its own cache: K [layers][Hkv][seq_alloc[s]][d] and V
+ * the same, or transposed [layers][Hkv][d][seq_alloc[s]] where v_transposed[s] != 0, both in `dtype` (bf16 bits or fp32).  The caches
+ * are passed in whole and come back whole, so a caller sees every element a kernel wrote outside the appended slots.  Only layer
+ * `layer` of `layers` is written.  Both calls return FL_ERR_BAD_ARGUMENT before the device is touched for len[s] + count[s] >
+ * seq_alloc[s], pos[s] + count[s] > max_pos, an odd d, H not a multiple of Hkv and layer >= layers, and FL_ERR_UNSUPPORTED for what
+ * the named form cannot take. */
+typedef struct fl_rope_seqs {
+    int32_t n_seq, layers, layer, reserved;
+    const int32_t *count, *pos, *len, *seq_alloc, *v_transposed;   /* [n_seq] each */
+    void *const *k_cache, *const *v_cache;                         /* [n_seq] host caches, updated in place */
+} fl_rope_seqs;
+
+/* The stand-alone RoPE + KV-append kernels.  qkv fp32 [n_slab][rows][(H + 2 Hkv) * d] (the K slabs of a projection, summed in slab
+ * order; then the optional bias [(H + 2 Hkv) * d]), cos_tab / sin_tab fp32 [max_pos][d / 2]; q_out [rows][H * d] in `dtype`.
+ *   form 0  launch_rope_kv: one sequence (the vector kernel where its own rule takes it, else the scalar one)
+ *   form 1  launch_rope_kv_batch: count[s] = 1 for every s, one layout for all sequences (fp32: row-major V only)
+ *   form 2  launch_rope_kv_packed: any counts, the layout per sequence
+ * repeat launches (1..8) start from the same caches: FL_ERR_HIP if one gives other bytes.  kernels_out [4] (or NULL) = {0 scalar /
+ * 1 vector / 2 batch / 3 packed, dtype, V transposed (forms 0 and 1), workgroups of the vector kernel's q / k part (else 0)}. */
+typedef struct fl_rope_kv_args {
+    size_t struct_size;             /* sizeof(fl_rope_kv_args) */
+    int32_t form, dtype, n_slab, repeat;
+    int64_t H, Hkv, d, max_pos;
+    const float *qkv, *bias, *cos_tab, *sin_tab;
+    fl_rope_seqs seqs;
+    void *q_out;
+    int32_t *kernels_out;
+} fl_rope_kv_args;
+int fl_op_rope_kv(const fl_rope_kv_args *args);
+
+/* Residual add -> RMSNorm -> QKV projection with RoPE and the KV append behind it; the inputs as fl_norm_linear_args (N = (H + 2 Hkv) * d).
+ *   form 0  a prompt of T rows as the forward pass runs it: launch_rmsnorm_add, plan_qkv_rope, then the planned kernel with the
+ *           epilogue -- or, where the plan keeps fp32 slabs, the plain projection and launch_rope_kv over the slabs (one sequence)
+ *   form 1  the single-sequence weight stream, norm prologue and RoPE epilogue (T = 1, K <= 6144)
+ *   form 2  the same over FP8 weights (T = 1, bf16, n_slab <= 1)
+ *   form 3  the batched stream: T = n_seq <= 8 rows, one sequence each, bf16, transposed V
+ * q_out [T][H * d] in `dtype`; x_out [T][K] (or NULL) = the normed vector's input v; repeat as above.  kernels_out [4] (or NULL):
+ * form 0: {kernel, K slices, tail kernel, 1 if the epilogue ran in the projection else 0} (FL_LK_*); the weight streams (forms 1 to 3): {FL_LK_GEMV, 1, 0, 1}. */
+typedef struct fl_qkv_rope_args {
+    size_t struct_size;             /* sizeof(fl_qkv_rope_args) */
+    int32_t form, dtype, n_slab, repeat;
+    int64_t T, K, H, Hkv, d, max_pos, vocab;
+    const float *x_res;             /* [T][K] fp32 */
+    const float *delta;             /* [n_slab][T][K] fp32, or NULL */
+    const float *norm_w;            /* [K] fp32 */
+    const void *embed;              /* [vocab][K] in dtype, or NULL */
+    const uint32_t *tokens;         /* [T], with embed */
+    const void *w;                  /* [N][K] in dtype (form 2: e4m3fn bytes) */
+    const float *w_scale;           /* form 2: [N] */
+    const float *bias;              /* [N] or NULL */
+    const float *cos_tab, *sin_tab;
+    float eps, reserved;
+    fl_rope_seqs seqs;
+    void *q_out;
+    float *x_out;
+    int32_t *kernels_out;
+} fl_qkv_rope_args;
+int fl_op_qkv_rope(const fl_qkv_rope_args *args);
+
 /* The token-selection kernel alone, for unit tests: `n_draws` successive selections from one host logits
  * vector (consuming successive words of the seeded stream; ArgMax when temperature < 1e-7). */
 int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out);

@@ -302,6 +302,82 @@ pub struct fl_linear_resid_args {
     pub kernels_out: *mut i32,
 }
 
+/// `fl_rope_seqs`: the sequences of an fl_op_rope_kv / fl_op_qkv_rope call -- per sequence its new rows, RoPE position, cache length,
+/// capacity and value layout, and its whole K / V caches (updated in place).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_rope_seqs {
+    pub n_seq: i32,
+    pub layers: i32,
+    pub layer: i32,
+    pub reserved: i32,
+    pub count: *const i32,
+    pub pos: *const i32,
+    pub len: *const i32,
+    pub seq_alloc: *const i32,
+    pub v_transposed: *const i32,
+    pub k_cache: *const *mut c_void,
+    pub v_cache: *const *mut c_void,
+}
+
+/// `fl_rope_kv_args`: the stand-alone RoPE + KV-append kernels on host buffers (fl_op_rope_kv, unit tests); `struct_size` is
+/// `size_of::<fl_rope_kv_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_rope_kv_args {
+    pub struct_size: usize,
+    pub form: i32,
+    pub dtype: i32,
+    pub n_slab: i32,
+    pub repeat: i32,
+    pub h: i64,
+    pub hkv: i64,
+    pub d: i64,
+    pub max_pos: i64,
+    pub qkv: *const f32,
+    pub bias: *const f32,
+    pub cos_tab: *const f32,
+    pub sin_tab: *const f32,
+    pub seqs: fl_rope_seqs,
+    pub q_out: *mut c_void,
+    pub kernels_out: *mut i32,
+}
+
+/// `fl_qkv_rope_args`: residual add -> RMSNorm -> QKV projection with the RoPE + KV-append epilogue in a named form (fl_op_qkv_rope,
+/// unit tests); `struct_size` is `size_of::<fl_qkv_rope_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_qkv_rope_args {
+    pub struct_size: usize,
+    pub form: i32,
+    pub dtype: i32,
+    pub n_slab: i32,
+    pub repeat: i32,
+    pub t: i64,
+    pub k: i64,
+    pub h: i64,
+    pub hkv: i64,
+    pub d: i64,
+    pub max_pos: i64,
+    pub vocab: i64,
+    pub x_res: *const f32,
+    pub delta: *const f32,
+    pub norm_w: *const f32,
+    pub embed: *const c_void,
+    pub tokens: *const u32,
+    pub w: *const c_void,
+    pub w_scale: *const f32,
+    pub bias: *const f32,
+    pub cos_tab: *const f32,
+    pub sin_tab: *const f32,
+    pub eps: f32,
+    pub reserved: f32,
+    pub seqs: fl_rope_seqs,
+    pub q_out: *mut c_void,
+    pub x_out: *mut f32,
+    pub kernels_out: *mut i32,
+}
+
 /// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -886,6 +962,8 @@ extern "C" {
     ) -> c_int;
     pub fn fl_op_norm_linear(args: *const fl_norm_linear_args) -> c_int;
     pub fn fl_op_linear_resid(args: *const fl_linear_resid_args) -> c_int;
+    pub fn fl_op_rope_kv(args: *const fl_rope_kv_args) -> c_int;
+    pub fn fl_op_qkv_rope(args: *const fl_qkv_rope_args) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;
