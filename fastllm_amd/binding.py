@@ -190,6 +190,13 @@ class FlQkvRopeArgs(C.Structure):
                 ("x_out", C.c_void_p), ("kernels_out", C.c_void_p)]
 
 
+class FlAttnOprojRepArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("H", C.c_int64), ("Hkv", C.c_int64), ("d", C.c_int64), ("N", C.c_int64), ("s_past", C.c_int64),
+                ("k_rows", C.c_int64), ("capacity", C.c_int64), ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("w_o", C.c_void_p),
+                ("pad_value", C.c_float), ("repeat", C.c_int32), ("query_only", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p),
+                ("info_out", C.c_void_p)]
+
+
 # kernels_out[0] of op_rope_kv
 ROPE_KV_NAMES = ("scalar", "vector", "batch", "packed")
 
@@ -362,6 +369,7 @@ def lib():
         L.fl_op_linear_resid.argtypes = [C.POINTER(FlLinearResidArgs)]
         L.fl_op_rope_kv.argtypes = [C.POINTER(FlRopeKvArgs)]
         L.fl_op_qkv_rope.argtypes = [C.POINTER(FlQkvRopeArgs)]
+        L.fl_op_attn_oproj_rep.argtypes = [C.POINTER(FlAttnOprojRepArgs)]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
@@ -1661,3 +1669,34 @@ def op_qkv_rope(form, w, norm_w, eps, cos, sin, H, Hkv, d, seqs, dtype, x_res=No
     _check(lib().fl_op_qkv_rope(C.byref(a)))
     del keep
     return q, caches, x_out, kernels
+
+
+def op_attn_oproj_rep(q, k, v, w_o, s_past, H, Hkv, d, capacity=None, pad_value=0.0, repeat=1):
+    """Decode attention replicated inside the o_proj launch, alone (fl_op_attn_oproj_rep): q [H d], k / v [rows, Hkv d] with rows >
+    s_past (the rows behind s_past + 1 are stale cache contents), w_o [N, H d], all uint16 bf16 bits; positions from rows to
+    `capacity` hold pad_value.  Returns (out [repeat, N] float32: the output of every launch, info [6] = (model rule, any-size
+    rule, rows per wave, GMAX, workgroups, slices per kv head))."""
+    q, k, v, w_o = (np.ascontiguousarray(a, dtype=np.uint16) for a in (q, k, v, w_o))
+    rows, N = k.shape[0], w_o.shape[0]
+    assert q.size == H * d and k.shape == (rows, Hkv * d) and v.shape == k.shape and w_o.shape == (N, H * d)
+    a = FlAttnOprojRepArgs()
+    a.struct_size = C.sizeof(FlAttnOprojRepArgs)
+    a.H, a.Hkv, a.d, a.N, a.s_past, a.k_rows, a.capacity = H, Hkv, d, N, s_past, rows, rows if capacity is None else capacity
+    a.q, a.k, a.v, a.w_o, a.pad_value, a.repeat = q.ctypes.data, k.ctypes.data, v.ctypes.data, w_o.ctypes.data, pad_value, repeat
+    out = np.empty((max(repeat, 1), N), dtype=np.float32)
+    info = np.zeros(6, np.int32)
+    a.out, a.info_out = out.ctypes.data, info.ctypes.data
+    _check(lib().fl_op_attn_oproj_rep(C.byref(a)))
+    return out, info
+
+
+def op_attn_oproj_rep_info(H, Hkv, d, N, capacity):
+    """info [6] of op_attn_oproj_rep for a shape and a cache capacity, without a device (query_only); FastLLMError for a head shape
+    the kernel does not take."""
+    a = FlAttnOprojRepArgs()
+    a.struct_size = C.sizeof(FlAttnOprojRepArgs)
+    a.H, a.Hkv, a.d, a.N, a.capacity, a.query_only = H, Hkv, d, N, capacity, 1
+    info = np.zeros(6, np.int32)
+    a.info_out = info.ctypes.data
+    _check(lib().fl_op_attn_oproj_rep(C.byref(a)))
+    return info

@@ -348,6 +348,30 @@ int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, i
     return FL_OK;
 }
 
+// the fl_op_attn_oproj_rep checks, none of which needs a device; *g: the launch's geometry and the two capacity rules
+int attn_oproj_rep_check(const fl_attn_oproj_rep_args *a, AttnRepGeometry *g) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: null args");
+    if (a->struct_size != sizeof(fl_attn_oproj_rep_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_attn_oproj_rep_args));
+    if (a->query_only != 0 && a->query_only != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: query_only %d not 0 or 1", a->query_only);
+    if (a->query_only ? !a->info_out : (!a->q || !a->k || !a->v || !a->w_o || !a->out)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: null argument");
+    if (a->H < 1 || a->Hkv < 1 || a->H > 1024 || a->H % a->Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: bad head counts (H %lld a multiple of Hkv %lld)", (long long)a->H, (long long)a->Hkv);
+    if (a->d < 1 || a->d > 1024) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: head_dim %lld not in 1..1024", (long long)a->d);
+    if (a->N < 1 || a->N > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: N %lld not in 1..2^20", (long long)a->N);
+    if (a->capacity < 1 || a->capacity > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: capacity %lld not in 1..2^20", (long long)a->capacity);
+    if (!a->query_only) {
+        if (a->s_past < 0 || a->k_rows < a->s_past + 1 || a->capacity < a->k_rows) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: s_past + 1 <= k_rows <= capacity");
+        if (!(a->pad_value == a->pad_value) || a->pad_value - a->pad_value != 0.f) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: pad_value must be finite");
+        if (a->repeat < 1 || a->repeat > 16) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_attn_oproj_rep: repeat %d not in 1..16", a->repeat);
+    }
+    const int64_t sa = (a->capacity + 31) / 32 * 32;
+    if (!attn_oproj_rep_geometry(a->H, a->Hkv, a->d, a->N, sa, g))
+        FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_attn_oproj_rep: head shape not taken (head_dim 64 / 128, at most 8 query heads per kv head, 8 a multiple of Hkv, H * d <= 2048)");
+    // The launch itself checks the head shape only -- in the model the capacity rule was applied when the cache was made -- and its
+    // burst loop takes any number of tiles; the any-size rule's 32 tiles per slice is as far as this entry point goes.
+    if (!a->query_only && !g->any_size) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_attn_oproj_rep: a capacity of %lld rows is more than 32 key tiles per slice", (long long)sa);
+    return FL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1723,6 +1747,42 @@ int fl_op_qkv_rope(const fl_qkv_rope_args *args) {
         memcpy(a.q_out, first.data(), qbytes);
         if (a.x_out) memcpy(a.x_out, first.data() + qbytes, nx * 4);
         sq.give_back(q, first.data() + qbytes + nx * 4);
+        return FL_OK;
+    });
+}
+
+int fl_op_attn_oproj_rep(const fl_attn_oproj_rep_args *args) {
+    return guarded([&]() -> int {
+        AttnRepGeometry g;
+        FL_TRY(attn_oproj_rep_check(args, &g));
+        const fl_attn_oproj_rep_args &a = *args;
+        const int info[6] = {g.model_rule ? 1 : 0, g.any_size ? 1 : 0, g.rpw, g.gmax, g.blocks, g.nslice};
+        if (a.query_only) {
+            memcpy(a.info_out, info, sizeof info);
+            return FL_OK;
+        }
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t H = a.H, Hkv = a.Hkv, d = a.d, N = a.N, K = H * d, sa = (a.capacity + 31) / 32 * 32;
+        void *qd, *kd, *vd, *wd; float *od; StepState *std_;
+        FL_TRY(B.upload(&qd, a.q, (size_t)K * 2));
+        FL_TRY(B.upload(&wd, a.w_o, (size_t)N * K * 2));
+        FL_TRY(B.alloc(&od, (size_t)a.repeat * N * 4));
+        // the cache layout of the model: K [Hkv][sa][d], V transposed [Hkv][d][sa]
+        FL_TRY(attn_op_upload_cache(B, &kd, &vd, FL_DTYPE_BF16, a.k, a.v, 1, a.k_rows, Hkv, sa, d, true, a.pad_value));
+        StepState st{}; st.pos = (uint32_t)a.s_past; st.len = (uint32_t)a.s_past; st.call0 = (uint32_t)a.s_past; st.eos = -1;
+        FL_TRY(B.upload(&std_, &st, sizeof st));
+        AttnRepArgs ra;                                              // as the decode step of model.hip fills it, without the tensor-parallel epilogue
+        ra.q = qd; ra.kc = kd; ra.vT = vd; ra.st = std_; ra.Wo = wd;
+        ra.H = (int)H; ra.Hkv = (int)Hkv; ra.seq_alloc = (int)sa; ra.N = (int)N; ra.K = (int)K; ra.scale = 1.0f / sqrtf((float)d);
+        for (int r = 0; r < a.repeat; r++) {
+            ra.out = od + (size_t)r * N;
+            FL_HIP(hipMemsetAsync(ra.out, 0xff, (size_t)N * 4, B.s));  // NaN pattern: a row the launch does not write shows up
+            FL_TRY(launch_attn_oproj_rep(B.L, ra));
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(a.out, od, (size_t)a.repeat * N * 4, hipMemcpyDeviceToHost));
+        if (a.info_out) memcpy(a.info_out, info, sizeof info);
         return FL_OK;
     });
 }

@@ -156,6 +156,22 @@ bool attn_oproj_rep_supported(int64_t H, int64_t Hkv, int64_t d, int64_t h, int6
     return (tiles + nslice - 1) / nslice <= 8 && 2 * Hkv * max_seq * d * 2 <= 96 * 1024;
 }
 
+// The geometry of a launch and what the two capacity rules say of a cache of seq_alloc rows: the expressions launch_attn_oproj_rep
+// itself runs on (fl_op_attn_oproj_rep reports them).  false: a head shape the kernel does not take.
+bool attn_oproj_rep_geometry(int64_t H, int64_t Hkv, int64_t d, int64_t N, int64_t seq_alloc, AttnRepGeometry *g) {
+    // the head shape alone: one tile of keys, any size (the model rule would also refuse Hkv * d = 1024, whose single tile is 128 KB)
+    if (H <= 0 || N < 1 || !attn_oproj_rep_supported(H, Hkv, d, N, 32, true)) return false;
+    g->model_rule = attn_oproj_rep_supported(H, Hkv, d, N, seq_alloc, false);
+    g->any_size = attn_oproj_rep_supported(H, Hkv, d, N, seq_alloc, true);
+    // rows per wave: one while that fills the chip's CUs, else two
+    g->rpw = N > 256 * R_NW ? 2 : 1;
+    g->blocks = (int)((N + R_NW * g->rpw - 1) / (R_NW * g->rpw));
+    g->gmax = H / Hkv <= 4 ? 4 : 8;
+    g->nslice = (int)(R_NW / Hkv);
+    g->lds = (size_t)R_NW * g->gmax * (d + 2) * 4 + (size_t)(H * d) * 2;
+    return true;
+}
+
 template <int D, int GMAX, int RPW>
 static int launch_rep_t(Launcher &L, const AttnRepArgs &a, int blocks, size_t lds) {
     auto kern = attn_oproj_rep_kernel<D, GMAX, RPW>;
@@ -166,16 +182,16 @@ static int launch_rep_t(Launcher &L, const AttnRepArgs &a, int blocks, size_t ld
     return LL.launch(KC_ATTN_OPROJ, (double)a.N * a.K * 2, 2.0 * a.N * a.K, kern, dim3((unsigned)blocks), dim3(R_NW * 64), lds, a);
 }
 
+// Checks the head shape only: that the cache is short enough for this form to pay (or, any size, has at most 32 tiles per slice) is
+// the caller's rule, attn_oproj_rep_supported on its capacity.
 int launch_attn_oproj_rep(Launcher &L, const AttnRepArgs &a) {
     if (!a.q || !a.kc || !a.vT || !a.st || !a.Wo || !a.out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "attn_oproj_rep: null argument");
     const int D = a.K / std::max(1, a.H);
-    if (a.H <= 0 || a.K != a.H * D || !attn_oproj_rep_supported(a.H, a.Hkv, D, a.N, 32, false)) FL_FAIL(FL_ERR_UNSUPPORTED, "attn_oproj_rep: unsupported shape");
+    AttnRepGeometry g;
+    if (a.H <= 0 || a.K != a.H * D || !attn_oproj_rep_geometry(a.H, a.Hkv, D, a.N, 32, &g)) FL_FAIL(FL_ERR_UNSUPPORTED, "attn_oproj_rep: unsupported shape");
     if (a.ll && a.ll_slot <= 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "attn_oproj_rep: fused all-reduce needs its slot");
-    // rows per wave: one while that fills the chip's CUs, else two
-    const int rpw = a.N > 256 * R_NW ? 2 : 1;
-    const int blocks = (a.N + R_NW * rpw - 1) / (R_NW * rpw);
-    const int G = a.H / a.Hkv, gmax = G <= 4 ? 4 : 8;
-    const size_t lds = (size_t)R_NW * gmax * (D + 2) * 4 + (size_t)a.K * 2;
+    const int rpw = g.rpw, gmax = g.gmax, blocks = g.blocks;
+    const size_t lds = g.lds;
     if (D == 64) {
         if (gmax == 4) return rpw == 1 ? launch_rep_t<64, 4, 1>(L, a, blocks, lds) : launch_rep_t<64, 4, 2>(L, a, blocks, lds);
         return rpw == 1 ? launch_rep_t<64, 8, 1>(L, a, blocks, lds) : launch_rep_t<64, 8, 2>(L, a, blocks, lds);

@@ -602,6 +602,10 @@ struct AttnRepArgs {
     const LLTable *ll = nullptr; int ll_slot = 0;
 };
 bool attn_oproj_rep_supported(int64_t H, int64_t Hkv, int64_t d, int64_t h, int64_t max_seq, bool any_size = false);
+// rows per wave, head slots per slab (GMAX), workgroups, slices per kv head and dynamic LDS of a launch with N rows; and whether a cache
+// of seq_alloc rows passes the model's rule / the any-size rule
+struct AttnRepGeometry { int rpw = 0, gmax = 0, blocks = 0, nslice = 0; size_t lds = 0; bool model_rule = false, any_size = false; };
+bool attn_oproj_rep_geometry(int64_t H, int64_t Hkv, int64_t d, int64_t N, int64_t seq_alloc, AttnRepGeometry *g);
 int launch_attn_oproj_rep(Launcher &L, const AttnRepArgs &a);
 
 // ---- the BERT / MiniLM encoder (k_encoder.hip): a packed, ragged batch of sequences -- row r of every [T_total][..] buffer belongs to

@@ -1004,6 +1004,32 @@ typedef struct fl_qkv_rope_args {
 } fl_qkv_rope_args;
 int fl_op_qkv_rope(const fl_qkv_rope_args *args);
 
+/* ---- decode attention replicated inside the o_proj launch (short caches), on host buffers (unit tests) ---------------------------- */
+
+/* launch_attn_oproj_rep alone, called as the decode step calls it (scale = 1 / sqrt(d), no tensor-parallel epilogue): out = w_o .
+ * attention(q, K, V), the attention output rounded to bf16 in between.  All operands are bf16 bits: q [H * d]; k / v [k_rows][Hkv * d]
+ * row-major, of which the kernel sees the first S = s_past + 1 rows (the rows behind are stale cache contents); w_o [N][H * d].  The
+ * call builds the cache in the model's layout, K [Hkv][sa][d] and V transposed [Hkv][d][sa] with sa = capacity rounded up to 32;
+ * rows k_rows .. sa hold pad_value (finite).  S <= k_rows <= capacity.  out fp32 [repeat][N]: each of the `repeat` launches (1..16)
+ * writes a row of its own, which is filled with the 0xff byte pattern (NaN) first.
+ * info_out [6] (or NULL) = {1 if the decode step would take this launch for a cache of sa rows, 1 if it would with FL_ATTN_REP=2
+ * (any size), rows per wave, head slots per wave slab (GMAX), workgroups, key slices per kv head}.  query_only = 1: fill info_out and
+ * return; no pointer but info_out is read, s_past and k_rows are ignored and the device is not touched.
+ * FL_ERR_BAD_ARGUMENT (null pointers, struct_size, sizes out of range, H not a multiple of Hkv, a pad_value that is not finite,
+ * repeat) and FL_ERR_UNSUPPORTED (head_dim other than 64 / 128, more than 8 query heads per kv head, 8 not a multiple of Hkv, H * d
+ * above 2048; without query_only also a capacity of more than 32 key tiles per slice) come back before the device is probed and write
+ * nothing. */
+typedef struct fl_attn_oproj_rep_args {
+    size_t struct_size;             /* sizeof(fl_attn_oproj_rep_args) */
+    int64_t H, Hkv, d, N, s_past, k_rows, capacity;
+    const void *q, *k, *v, *w_o;
+    float pad_value;
+    int32_t repeat, query_only, reserved;
+    float *out;
+    int32_t *info_out;
+} fl_attn_oproj_rep_args;
+int fl_op_attn_oproj_rep(const fl_attn_oproj_rep_args *args);
+
 /* The token-selection kernel alone, for unit tests: `n_draws` successive selections from one host logits
  * vector (consuming successive words of the seeded stream; ArgMax when temperature < 1e-7). */
 int fl_op_sample(const float *logits, int64_t V, const fl_sampling *sampling, int64_t n_draws, uint32_t *tokens_out);

@@ -378,6 +378,31 @@ pub struct fl_qkv_rope_args {
     pub kernels_out: *mut i32,
 }
 
+/// `fl_attn_oproj_rep_args`: decode attention replicated inside the o_proj launch on host buffers (fl_op_attn_oproj_rep, unit tests);
+/// `struct_size` is `size_of::<fl_attn_oproj_rep_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_attn_oproj_rep_args {
+    pub struct_size: usize,
+    pub h: i64,
+    pub hkv: i64,
+    pub d: i64,
+    pub n: i64,
+    pub s_past: i64,
+    pub k_rows: i64,
+    pub capacity: i64,
+    pub q: *const c_void,
+    pub k: *const c_void,
+    pub v: *const c_void,
+    pub w_o: *const c_void,
+    pub pad_value: f32,
+    pub repeat: i32,
+    pub query_only: i32,
+    pub reserved: i32,
+    pub out: *mut f32,
+    pub info_out: *mut i32,
+}
+
 /// `fl_lookup`: prompt-lookup drafting (fl_lookup_draft, fl_decode_lookup); `struct_size` is `size_of::<fl_lookup>()`.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -964,6 +989,7 @@ extern "C" {
     pub fn fl_op_linear_resid(args: *const fl_linear_resid_args) -> c_int;
     pub fn fl_op_rope_kv(args: *const fl_rope_kv_args) -> c_int;
     pub fn fl_op_qkv_rope(args: *const fl_qkv_rope_args) -> c_int;
+    pub fn fl_op_attn_oproj_rep(args: *const fl_attn_oproj_rep_args) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;

@@ -1,6 +1,7 @@
 """Decode attention replicated inside the o_proj launch (k_attn_rep.hip): used for caches of up to ~96 KB of K / V per layer.
 The small-cache tests of the whole suite run through it (against the oracle); here: that it really is the launch that runs, where
-it stops being used, and that it agrees with the two launches it replaces at TinyLlama's width."""
+it stops being used, and that it agrees with the two launches it replaces at TinyLlama's width.
+The kernel alone, exactly and at every instantiation: test_gpu_attn_rep_ops.py."""
 import numpy as np
 import pytest
 
