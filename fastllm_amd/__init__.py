@@ -9,7 +9,7 @@ from .binding import (Batch, Cache, FastLLMError, Model, abi_version, comm_uniqu
                       Encoder, FlEncoderConfig, make_encoder_config, op_encoder_attention, op_attention_plain, op_attention_batch, op_attention_packed, op_logprobs, FlLogprobs, LOGPROBS_MAX_TOP,
                       op_score, op_score_time, FlScore, SCORE_NO_TARGET, ScoreResult, op_pool_rows, FlEmbed, make_embed, POOLING, ATTN_MASK,
                       op_logit_rules, FlLogitRules, make_logit_rules, Guide, op_guide_mask, FlGuideDesc, make_guide_desc, op_verify_adjust, op_verify_adjust_time, op_rules_count,
-                      op_rmsnorm_add, op_norm_linear, op_linear_resid, FlNormLinearArgs, FlLinearResidArgs, LK_NAMES,
+                      op_rmsnorm_add, op_norm_linear, op_linear_resid, op_gemv_resid, FlNormLinearArgs, FlLinearResidArgs, FlGemvResidArgs, LK_NAMES,
                       op_rope_kv, op_qkv_rope, FlRopeSeqs, FlRopeKvArgs, FlQkvRopeArgs, ROPE_KV_NAMES,
                       op_attn_oproj_rep, op_attn_oproj_rep_info, FlAttnOprojRepArgs)
 from .configs import MODEL_CONFIGS  # noqa: F401

@@ -169,6 +169,16 @@ class FlLinearResidArgs(C.Structure):
                 ("kernels_out", C.c_void_p)]
 
 
+class FlGemvResidArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("mode", C.c_int32), ("epi2", C.c_int32), ("repeat", C.c_int32), ("reserved", C.c_int32),
+                ("N", C.c_int64), ("K", C.c_int64), ("N2", C.c_int64), ("H", C.c_int64), ("Hkv", C.c_int64), ("d", C.c_int64),
+                ("max_pos", C.c_int64), ("pos", C.c_int64), ("len", C.c_int64), ("seq_alloc", C.c_int64), ("x", C.c_void_p), ("w", C.c_void_p),
+                ("h_in", C.c_void_p), ("w_next", C.c_void_p), ("xs", C.c_void_p), ("cs", C.c_void_p), ("w2", C.c_void_p), ("cos_tab", C.c_void_p),
+                ("sin_tab", C.c_void_p), ("eps", C.c_float), ("reserved2", C.c_float), ("h_out", C.c_void_p), ("xs_out", C.c_void_p),
+                ("cs_out", C.c_void_p), ("delta_out", C.c_void_p), ("y_out", C.c_void_p), ("inv_out", C.c_void_p), ("h_ref", C.c_void_p),
+                ("y_ref", C.c_void_p), ("inv_ref", C.c_void_p), ("amax_out", C.c_void_p)]
+
+
 class FlRopeSeqs(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("layers", C.c_int32), ("layer", C.c_int32), ("reserved", C.c_int32), ("count", C.c_void_p),
                 ("pos", C.c_void_p), ("len", C.c_void_p), ("seq_alloc", C.c_void_p), ("v_transposed", C.c_void_p), ("k_cache", C.c_void_p),
@@ -367,6 +377,7 @@ def lib():
         L.fl_op_rmsnorm_add.argtypes = [vp, vp, C.c_int32, vp, C.c_float, C.c_int64, C.c_int64, C.c_int32, vp, vp]
         L.fl_op_norm_linear.argtypes = [C.POINTER(FlNormLinearArgs)]
         L.fl_op_linear_resid.argtypes = [C.POINTER(FlLinearResidArgs)]
+        L.fl_op_gemv_resid.argtypes = [C.POINTER(FlGemvResidArgs)]
         L.fl_op_rope_kv.argtypes = [C.POINTER(FlRopeKvArgs)]
         L.fl_op_qkv_rope.argtypes = [C.POINTER(FlQkvRopeArgs)]
         L.fl_op_attn_oproj_rep.argtypes = [C.POINTER(FlAttnOprojRepArgs)]
@@ -1585,6 +1596,56 @@ def op_linear_resid(x, w, h_in, w_next, eps, bias=None, w2=None, epi2=0, lazy=Fa
     k = dict(kernel=LK_NAMES[kernels[0]], ks=int(kernels[1]), tail=LK_NAMES[kernels[2]], tail_ks=int(kernels[3]), consumer=LK_NAMES[kernels[4]],
              consumer_reads_parts=bool(kernels[5]))
     return dict(h=h, xn=xn, inv_rms=inv, part=part, y2=y2, kernels=k)
+
+
+def op_gemv_resid(mode, eps, x=None, w=None, h_in=None, w_next=None, xs=None, cs=None, w2=None, epi2=0, rope=None, repeat=1):
+    """The decode stream's residual epilogue and the prologue that consumes it (fl_op_gemv_resid).  mode 0: the producer alone
+    (x [K], w [N, K] uint16 bf16 bits; h_in, w_next [N] float32); 1: the consumer alone on xs [N] (uint16) and cs [N/8] with w2
+    [N2, N]; 2: the pair next to today's two launches.  epi2: 0 fp32 (+ ArgMax candidates), 1 gate/up (w2 rows gate | up), 2 QKV
+    RoPE with rope = dict(H, Hkv, d, pos, len, seq_alloc, cos, sin) (cos / sin [max_pos, d/2] float32).  Returns a dict of what the mode
+    gives: h, xs (uint16), cs, delta (the producer's untouched `out`), y, inv, amax, and h_ref, y_ref, inv_ref, amax_ref (mode 2)."""
+    keep = []
+
+    def u16(v):
+        v = None if v is None else np.ascontiguousarray(v, dtype=np.uint16)
+        keep.append(v)
+        return v
+
+    def f32(v):
+        v = None if v is None else _f32(v)
+        keep.append(v)
+        return v
+    x, w, xs, w2 = u16(x), u16(w), u16(xs), u16(w2)
+    h_in, w_next, cs = f32(h_in), f32(w_next), f32(cs)
+    a = FlGemvResidArgs()
+    a.struct_size = C.sizeof(FlGemvResidArgs)
+    a.mode, a.epi2, a.repeat, a.eps = mode, epi2, repeat, eps
+    N = w.shape[0] if w is not None else xs.shape[0]
+    a.N, a.K, a.N2 = N, (w.shape[1] if w is not None else 0), (w2.shape[0] if w2 is not None else 0)
+    assert w is None or (x.shape == (w.shape[1],) and h_in.shape == (N,) and w_next.shape == (N,))
+    assert w2 is None or w2.shape[1] == N
+    assert xs is None or (xs.shape == (N,) and cs.shape == (N // 8,))
+    a.x, a.w, a.h_in, a.w_next, a.xs, a.cs, a.w2 = _ptr(x), _ptr(w), _ptr(h_in), _ptr(w_next), _ptr(xs), _ptr(cs), _ptr(w2)
+    if rope is not None:
+        cos, sin = f32(rope["cos"]), f32(rope["sin"])
+        a.H, a.Hkv, a.d, a.pos, a.len, a.seq_alloc, a.max_pos = rope["H"], rope["Hkv"], rope["d"], rope["pos"], rope["len"], rope["seq_alloc"], cos.shape[0]
+        a.cos_tab, a.sin_tab = cos.ctypes.data, sin.ctypes.data
+    out = {}
+    if mode != 1:
+        out.update(h=np.empty(N, np.float32), xs=np.empty(N, np.uint16), cs=np.empty(N // 8, np.float32), delta=np.empty(N, np.float32))
+        a.h_out, a.xs_out, a.cs_out, a.delta_out = (out[k].ctypes.data for k in ("h", "xs", "cs", "delta"))
+    amax = np.full(2, -2, np.int32)
+    if mode != 0:
+        ny = a.N2 // 2 if epi2 == 1 else a.N2
+        out.update(y=np.empty(ny, np.float32), inv=np.empty(1, np.float32))
+        a.y_out, a.inv_out, a.amax_out = out["y"].ctypes.data, out["inv"].ctypes.data, amax.ctypes.data
+        if mode == 2:
+            out.update(h_ref=np.empty(N, np.float32), y_ref=np.empty(ny, np.float32), inv_ref=np.empty(1, np.float32))
+            a.h_ref, a.y_ref, a.inv_ref = out["h_ref"].ctypes.data, out["y_ref"].ctypes.data, out["inv_ref"].ctypes.data
+    _check(lib().fl_op_gemv_resid(C.byref(a)))
+    if mode != 0:
+        out.update(amax=int(amax[0]), amax_ref=int(amax[1]))
+    return out
 
 
 def _rope_seqs(st, seqs, layers, layer, bf16):

@@ -1787,4 +1787,194 @@ int fl_op_attn_oproj_rep(const fl_attn_oproj_rep_args *args) {
     });
 }
 
+int fl_op_gemv_resid(const fl_gemv_resid_args *args) {
+    return guarded([&]() -> int {
+        if (!args) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: null args");
+        const fl_gemv_resid_args &a = *args;
+        if (a.struct_size != sizeof(fl_gemv_resid_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: struct_size %zu, expected %zu", a.struct_size, sizeof(fl_gemv_resid_args));
+        if (a.mode < 0 || a.mode > 2 || a.epi2 < 0 || a.epi2 > 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: mode 0..2, epi2 0..2");
+        if (a.repeat < 1 || a.repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: repeat %d not in 1..8", a.repeat);
+        const bool prod = a.mode != 1, cons = a.mode != 0, pair = a.mode == 2;
+        const int64_t N = a.N, K = a.K, N2 = a.N2, H = a.H, Hkv = a.Hkv, d = a.d, sa = a.seq_alloc;
+        if (N <= 0 || N % 8 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: N must be a multiple of 8");
+        if (prod && (K <= 0 || K % 8 || !a.x || !a.w || !a.h_in || !a.w_next || !a.h_out || !a.xs_out || !a.cs_out || !a.delta_out))
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: the producer takes x, w, h_in, w_next (K a multiple of 8) and gives h_out, xs_out, cs_out, delta_out");
+        if (!prod && (!a.xs || !a.cs)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: mode 1 takes xs and cs");
+        if (cons) {
+            if (!a.w2 || !a.y_out || !a.inv_out || N2 <= 0 || N2 > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: the consumer takes w2 [N2][N] and gives y_out, inv_out");
+            if (a.epi2 == 1 && N2 % 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: gate/up needs an even N2");
+            if (a.epi2 == 2 && (H < 1 || Hkv < 1 || d < 2 || d % 2 || N2 != (H + 2 * Hkv) * d || a.max_pos < 1 || a.pos < 0 || a.pos >= a.max_pos || sa < 1 ||
+                                sa > (1 << 20) || a.len < 0 || a.len >= sa || !a.cos_tab || !a.sin_tab))
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: QKV: N2 = (H + 2 Hkv) d, pos < max_pos, len < seq_alloc, cos_tab / sin_tab");
+            if (pair && (!a.h_ref || !a.y_ref || !a.inv_ref)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: mode 2 gives h_ref, y_ref, inv_ref");
+        }
+        OpScope B;
+        FL_TRY(B.begin());
+        const int dt = FL_DTYPE_BF16;
+        void *xd = nullptr, *wd = nullptr, *xsd, *w2d = nullptr; float *h0 = nullptr, *wn = nullptr, *h, *csd, *dl, *ct = nullptr, *sn = nullptr;
+        StepState *std_ = nullptr;
+        if (prod) {
+            FL_TRY(B.upload(&xd, a.x, (size_t)K * 2)); FL_TRY(B.upload(&wd, a.w, (size_t)N * K * 2));
+            FL_TRY(B.upload(&h0, a.h_in, (size_t)N * 4)); FL_TRY(B.upload(&wn, a.w_next, (size_t)N * 4));
+        }
+        FL_TRY(B.alloc(&h, (size_t)N * 4)); FL_TRY(B.alloc(&dl, (size_t)N * 4));
+        FL_TRY(B.alloc(&xsd, (size_t)N * 2)); FL_TRY(B.alloc(&csd, (size_t)N / 8 * 4));
+        // the consumer's matrix in its device layout, and one set of outputs per form: y (fp32 | packed silu(g)*u | q + one layer's
+        // caches, V transposed as the MFMA attention keeps it), the ArgMax candidates
+        int64_t N2w = N2, I2p = 0;
+        const int cepi = a.epi2 == 1 ? EPI_GATEUP : a.epi2 == 2 ? EPI_QKV_ROPE : EPI_F32;
+        struct ConsOut { void *y = nullptr, *k = nullptr, *v = nullptr; ArgmaxCand *amax = nullptr; float *h = nullptr, *dl = nullptr; };
+        ConsOut co[2];
+        const size_t ybytes = !cons ? 0 : a.epi2 == 1 ? (size_t)((N2 / 2 + 15) / 16 * 16) * 2 : a.epi2 == 2 ? (size_t)H * d * 2 : (size_t)N2 * 4;
+        const size_t cbytes = cons && a.epi2 == 2 ? (size_t)Hkv * sa * d * 2 : 0;
+        if (cons) {
+            FL_TRY(op_upload_matrix(B, dt, a.w2, N2, N, cepi, &w2d, &N2w, &I2p));
+            if (a.epi2 == 2) {
+                FL_TRY(B.upload(&ct, a.cos_tab, (size_t)a.max_pos * (d / 2) * 4)); FL_TRY(B.upload(&sn, a.sin_tab, (size_t)a.max_pos * (d / 2) * 4));
+            }
+            StepState st{}; st.pos = (uint32_t)a.pos; st.len = (uint32_t)a.len; st.call0 = (uint32_t)a.len; st.eos = -1;
+            FL_TRY(B.upload(&std_, &st, sizeof st));
+            for (int f = 0; f < (pair ? 2 : 1); f++) {
+                FL_TRY(B.alloc(&co[f].y, ybytes));
+                if (cbytes) { FL_TRY(B.alloc(&co[f].k, cbytes)); FL_TRY(B.alloc(&co[f].v, cbytes)); }
+                if (a.epi2 == 0) FL_TRY(B.alloc(&co[f].amax, sizeof(ArgmaxCand) * kMaxArgmaxCand));
+                if (f) { FL_TRY(B.alloc(&co[f].h, (size_t)N * 4)); FL_TRY(B.alloc(&co[f].dl, (size_t)N * 4)); }
+            }
+        }
+        auto consumer_args = [&](const ConsOut &o) {
+            GemvArgs g;
+            g.W = w2d; g.out = o.y; g.N = (int)N2w; g.K = (int)N; g.epi = cepi; g.eps = a.eps; g.st = std_;
+            if (a.epi2 == 0 && gemv_leaves_candidates(dt, g)) g.amax = o.amax;
+            if (a.epi2 == 2) {
+                g.cos_tab = ct; g.sin_tab = sn; g.q_out = o.y; g.k_cache = o.k; g.v_cache = o.v; g.out = nullptr;
+                g.H = (int)H; g.Hkv = (int)Hkv; g.d = (int)d; g.max_seq = (int)sa; g.max_pos = (int)a.max_pos; g.v_ld = (int)sa;
+            }
+            return g;
+        };
+        auto clear = [&](const ConsOut &o) -> int {              // NaN patterns: what no launch writes shows up
+            FL_HIP(hipMemsetAsync(o.y, 0xff, ybytes, B.s));
+            if (cbytes) { FL_HIP(hipMemsetAsync(o.k, 0xff, cbytes, B.s)); FL_HIP(hipMemsetAsync(o.v, 0xff, cbytes, B.s)); }
+            if (o.amax) FL_HIP(hipMemsetAsync(o.amax, 0xff, sizeof(ArgmaxCand) * kMaxArgmaxCand, B.s));
+            return FL_OK;
+        };
+        // the bytes one run left: h | delta | xs | cs, then per form y | k | v | candidates (and the old form's h | delta)
+        const size_t abytes = a.epi2 == 0 && cons ? sizeof(ArgmaxCand) * kMaxArgmaxCand : 0;
+        const size_t off_dl = (size_t)N * 4, off_xs = off_dl + (size_t)N * 4, off_cs = off_xs + (size_t)N * 2, off_c = off_cs + (size_t)N / 8 * 4;
+        const size_t per = ybytes + 2 * cbytes + abytes + (size_t)N * 8, total = off_c + 2 * per;
+        std::vector<unsigned char> first(total, 0), again(total, 0);
+        for (int rep = 0; rep < a.repeat; rep++) {
+            FL_HIP(hipMemsetAsync(h, 0xff, (size_t)N * 4, B.s)); FL_HIP(hipMemsetAsync(dl, 0xff, (size_t)N * 4, B.s));
+            if (prod) {
+                FL_HIP(hipMemsetAsync(xsd, 0xff, (size_t)N * 2, B.s)); FL_HIP(hipMemsetAsync(csd, 0xff, (size_t)N / 8 * 4, B.s));
+                GemvArgs p;                                          // as the step builder's producer (model.hip) lays it out
+                p.W = wd; p.x = xd; p.out = dl; p.N = (int)N; p.K = (int)K; p.epi = EPI_RESID; p.pro = PRO_X;
+                p.x_in = h0; p.norm_w = wn; p.x_out = h; p.xs_out = xsd; p.cs_out = csd;
+                FL_TRY(launch_gemv(B.L, dt, p));
+            } else {
+                FL_HIP(hipMemcpyAsync(xsd, a.xs, (size_t)N * 2, hipMemcpyHostToDevice, B.s)); FL_HIP(hipMemcpyAsync(csd, a.cs, (size_t)N / 8 * 4, hipMemcpyHostToDevice, B.s));
+            }
+            if (cons) {
+                FL_TRY(clear(co[0]));
+                GemvArgs g = consumer_args(co[0]);
+                g.pro = PRO_XS; g.x = xsd; g.cs = csd;
+                FL_TRY(launch_gemv(B.L, dt, g));
+            }
+            if (pair) {                                              // the same inputs through today's two launches
+                FL_TRY(clear(co[1]));
+                FL_HIP(hipMemsetAsync(co[1].h, 0xff, (size_t)N * 4, B.s)); FL_HIP(hipMemsetAsync(co[1].dl, 0xff, (size_t)N * 4, B.s));
+                GemvArgs p;
+                p.W = wd; p.x = xd; p.out = co[1].dl; p.N = (int)N; p.K = (int)K; p.epi = EPI_F32; p.pro = PRO_X;
+                FL_TRY(launch_gemv(B.L, dt, p));
+                GemvArgs g = consumer_args(co[1]);
+                g.pro = PRO_NORM; g.x_in = h0; g.delta = co[1].dl; g.norm_w = wn; g.x_out = co[1].h;
+                FL_TRY(launch_gemv(B.L, dt, g));
+            }
+            FL_HIP(hipStreamSynchronize(B.s));
+            unsigned char *o = (rep ? again : first).data();
+            FL_HIP(hipMemcpy(o, h, (size_t)N * 4, hipMemcpyDeviceToHost)); FL_HIP(hipMemcpy(o + off_dl, dl, (size_t)N * 4, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(o + off_xs, xsd, (size_t)N * 2, hipMemcpyDeviceToHost)); FL_HIP(hipMemcpy(o + off_cs, csd, (size_t)N / 8 * 4, hipMemcpyDeviceToHost));
+            for (int f = 0; cons && f < (pair ? 2 : 1); f++) {
+                unsigned char *c = o + off_c + (size_t)f * per;
+                FL_HIP(hipMemcpy(c, co[f].y, ybytes, hipMemcpyDeviceToHost)); c += ybytes;
+                if (cbytes) { FL_HIP(hipMemcpy(c, co[f].k, cbytes, hipMemcpyDeviceToHost)); FL_HIP(hipMemcpy(c + cbytes, co[f].v, cbytes, hipMemcpyDeviceToHost)); }
+                c += 2 * cbytes;
+                if (co[f].amax) FL_HIP(hipMemcpy(c, co[f].amax, abytes, hipMemcpyDeviceToHost));
+                c += abytes;
+                if (f) { FL_HIP(hipMemcpy(c, co[f].h, (size_t)N * 4, hipMemcpyDeviceToHost)); FL_HIP(hipMemcpy(c + (size_t)N * 4, co[f].dl, (size_t)N * 4, hipMemcpyDeviceToHost)); }
+            }
+            if (rep && first != again) FL_FAIL(FL_ERR_HIP, "fl_op_gemv_resid: launch %d gave other bytes than the first", rep);
+        }
+        // 1/m as each prologue computes it, read through a probe launch on the sums the run left: the staged vector is 1.0 at one
+        // element j and +-0 elsewhere, the matrix (the consumer's shape, fp32 epilogue) is 1.0 at [0][j], so row 0 comes out as 1.0 * 1/m.
+        // PRO_XS stages such a vector next to the producer's cs; PRO_NORM is given the norm weight 1 / v[j] at j (v[j] * w rounds to
+        // bf16 1.0 whatever its last fp32 bits are) and 0 elsewhere, next to the x_in and delta of the run.
+        if (cons) {
+            const float *hv = reinterpret_cast<const float *>(first.data() + off_c + per + ybytes + 2 * cbytes + abytes);
+            int64_t j = 0;
+            float wj = 1.0f;
+            if (pair) {
+                for (j = 0; j < N; j++)
+                    if (std::isfinite(hv[j]) && fabsf(hv[j]) >= 1e-3f && fabsf(hv[j]) <= 1e3f) break;
+                if (j == N) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_gemv_resid: no element of h between 1e-3 and 1e3 to probe 1/m with");
+                wj = 1.0f / hv[j];
+            }
+            std::vector<bf16_t> xp((size_t)N, 0);
+            std::vector<float> wp((size_t)N, 0.f);
+            xp[(size_t)j] = 0x3f80; wp[(size_t)j] = wj;
+            void *xpd, *Wp; float *wpd, *yp;
+            FL_TRY(B.upload(&xpd, xp.data(), (size_t)N * 2)); FL_TRY(B.upload(&wpd, wp.data(), (size_t)N * 4));
+            FL_TRY(B.alloc(&Wp, (size_t)N2w * N * 2)); FL_TRY(B.alloc(&yp, (size_t)N2w * 4));
+            FL_HIP(hipMemsetAsync(Wp, 0, (size_t)N2w * N * 2, B.s));
+            FL_HIP(hipMemcpyAsync((bf16_t *)Wp + j, &xp[(size_t)j], 2, hipMemcpyHostToDevice, B.s));
+            for (int f = 0; f < (pair ? 2 : 1); f++) {
+                FL_HIP(hipMemsetAsync(yp, 0xff, (size_t)N2w * 4, B.s));
+                GemvArgs g;
+                g.W = Wp; g.out = yp; g.N = (int)N2w; g.K = (int)N; g.epi = EPI_F32; g.eps = a.eps; g.st = std_;
+                if (f) { g.pro = PRO_NORM; g.x_in = h0; g.delta = co[1].dl; g.norm_w = wpd; }
+                else { g.pro = PRO_XS; g.x = xpd; g.cs = csd; }
+                FL_TRY(launch_gemv(B.L, dt, g));
+                FL_HIP(hipStreamSynchronize(B.s));
+                FL_HIP(hipMemcpy(f ? a.inv_ref : a.inv_out, yp, 4, hipMemcpyDeviceToHost));
+            }
+        }
+        if (prod) {
+            memcpy(a.h_out, first.data(), (size_t)N * 4); memcpy(a.delta_out, first.data() + off_dl, (size_t)N * 4);
+            memcpy(a.xs_out, first.data() + off_xs, (size_t)N * 2); memcpy(a.cs_out, first.data() + off_cs, (size_t)N / 8 * 4);
+        }
+        for (int f = 0; cons && f < (pair ? 2 : 1); f++) {
+            const unsigned char *c = first.data() + off_c + (size_t)f * per;
+            float *y = f ? a.y_ref : a.y_out;
+            const bf16_t *yb = reinterpret_cast<const bf16_t *>(c);
+            if (a.epi2 == 0) {
+                memcpy(y, c, ybytes);
+            } else if (a.epi2 == 1) {
+                for (int64_t j = 0; j < N2 / 2; j++) y[j] = bf16_bits_to_float(yb[j]);
+            } else {                                                 // q | the appended k row | the appended v row
+                const bf16_t *kb = reinterpret_cast<const bf16_t *>(c + ybytes), *vb = reinterpret_cast<const bf16_t *>(c + ybytes + cbytes);
+                for (int64_t j = 0; j < H * d; j++) y[j] = bf16_bits_to_float(yb[j]);
+                for (int64_t hd = 0; hd < Hkv; hd++)
+                    for (int64_t j = 0; j < d; j++) {
+                        y[H * d + hd * d + j] = bf16_bits_to_float(kb[(hd * sa + a.len) * d + j]);
+                        y[(H + Hkv) * d + hd * d + j] = bf16_bits_to_float(vb[(hd * d + j) * sa + a.len]);
+                    }
+            }
+            c += ybytes + 2 * cbytes;
+            if (a.amax_out) {                                        // the row the candidates give (ties: the larger index), -1 without candidates
+                int best = -1;
+                if (abytes) {
+                    const ArgmaxCand *cand = reinterpret_cast<const ArgmaxCand *>(c);
+                    float bv = 0.f;
+                    const int n = cand[0].i;
+                    for (int i = 1; n > 0 && n < kMaxArgmaxCand && i <= n; i++)
+                        if (cand[i].i >= 0 && (best < 0 || cand[i].v > bv || (cand[i].v == bv && cand[i].i > best))) { bv = cand[i].v; best = cand[i].i; }
+                }
+                a.amax_out[f] = best;
+            }
+            c += abytes;
+            if (f) memcpy(a.h_ref, c, (size_t)N * 4);
+        }
+        return FL_OK;
+    });
+}
+
 }  // extern "C"

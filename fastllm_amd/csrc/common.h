@@ -123,6 +123,7 @@ enum TuneKey {
     TK_F32_ROWS_MAX,   // fp32 mode: projections of 2 ... this many token rows (short prompts, decode batches; at most 64) as a weight stream with the x rows in LDS (gemv_f32_rows_kernel); 0: the MFMA tiles
     TK_GATEUP_ROWSPLIT,   // gate/up of a prompt 1-96 tokens past an EVEN number of 256-row tiles (513-608, 1025-1120 ...): whole rounds on the 224-column kernel + the last rows as a launch of their own; 0: one launch
     TK_SCORE_ROWS,   // fl_forward_score / fl_batch_score: rows per lm_head + score_rows block (1..1024); its [rows][V] fp32 scratch is allocated at a model's first scoring call
+    TK_GEMV_RESID,   // decode: o_proj / down_proj finish the residual add, the next norm's v * w and the chunk sums of squares in their epilogue, and the consumer stages the ready vector (k_gemv.hip EPI_RESID / PRO_XS), on every edge where gemv_resid_edge (gemv_geometry.h) says so; 0: the norm prologue everywhere; 2: as 1, and the launcher tags name the form (",resid" / ",xs"; by default a launch keeps the name it has always had)
     TK_COUNT
 };
 int tune(TuneKey k);

@@ -32,4 +32,35 @@ inline GemvGeometry gemv_geometry(int64_t ngroups, size_t lds_bytes, int cus, in
     return g;
 }
 
+// the grid launch_gemv runs an N x K bf16 matrix on, R rows per row group: gemv_geometry with its floor of four waves
+inline GemvGeometry gemv_stream_geometry(int64_t N, int64_t K, int R, int cus) {
+    GemvGeometry g = gemv_geometry((N + R - 1) / R, ((size_t)K * 2 + 15) & ~(size_t)15, cus, 0, 0);
+    if (g.waves < 4) g.waves = 4;
+    return g;
+}
+
+// One producer -> RMSNorm -> consumer edge of a decode step: may the producer (o_proj / down_proj, [N, K]) finish the residual add,
+// v * w_next and the chunk sums of squares in its epilogue (EPI_RESID), and the consumer ([Nc, N]: gate/up, the next QKV projection
+// or lm_head) stage the ready vector (PRO_XS)?  Everything else keeps the consumer's PRO_NORM prologue.
+struct GemvResidEdge {
+    int64_t N = 0, K = 0;                     // the producer's matrix
+    int64_t Nc = 0;                           // rows of the consumer's matrix (device layout: gate/up padded to whole 32s)
+    int R = 2;                                // rows per row group of both launches (fl_tune "gemv_r")
+    int cus = 256;
+    bool bf16 = true, one_shard = true, compute_weights = true;   // a bf16 model on one GPU that streams the compute-dtype weights
+    int force_blocks = 0, force_waves = 0;    // fl_tune "gemv_blocks" / "gemv_waves"
+};
+// *producer (if given): the grid the producer then runs on
+inline bool gemv_resid_edge(const GemvResidEdge &e, GemvGeometry *producer = nullptr) {
+    if (!e.bf16 || !e.one_shard || !e.compute_weights || e.force_blocks != 0 || e.force_waves != 0) return false;
+    if (e.N <= 0 || e.K <= 0 || e.Nc <= 0 || e.R <= 0 || e.N % 8 || e.K % 8 || e.N % e.R) return false;
+    const GemvGeometry p = gemv_stream_geometry(e.N, e.K, e.R, e.cus);
+    if (producer) *producer = p;
+    // the grid covers N exactly, one row group per wave; a workgroup's rows are whole 8-element chunks of the consumer's K
+    if ((int64_t)p.blocks * p.waves * e.R != e.N || (p.waves * e.R) % 8 != 0) return false;
+    // the consumer stages one chunk per thread
+    const GemvGeometry c = gemv_stream_geometry(e.Nc, e.N, e.R, e.cus);
+    return e.N / 8 <= (int64_t)c.waves * 64;
+}
+
 }  // namespace fl

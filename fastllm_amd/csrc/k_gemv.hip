@@ -27,6 +27,11 @@
 // staging; 1/m is applied to the accumulator in the epilogue.  Workgroup 0 also writes the updated
 // residual v to x_out (a different buffer than x_in: other workgroups still read x_in).
 //
+// Epilogue EPI_RESID + prologue PRO_XS (bf16): where gemv_resid_edge (gemv_geometry.h) says so, the o_proj / down_proj
+// launch finishes what PRO_NORM redoes in every workgroup -- per row, on the lane that holds the row's sum: v = h_in + sum to h_out,
+// bf16(v * w_next) to xs, and behind one barrier the fmaf chain over every 8 rows to cs -- and the launch behind the norm stages xs
+// (one 16-byte chunk and one float per thread) and sums cs where PRO_NORM sums its own squares: the same chains, the same bits.
+//
 // Epilogues: EPI_F32 (+bias) -> fp32, or -- GemvArgs::ll, the row-parallel o_proj / down_proj of a tensor-parallel
 // group -- summed over the ranks right here (comm_ll.h);  EPI_GATEUP: silu(gate)*up on the 16-interleaved layout;
 // EPI_QKV_ROPE (fused K4/K5): rows are paired (j, j+d/2) per head, RoPE is applied with the
@@ -86,6 +91,7 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
     __shared__ float red[kGemvMaxThreads / 64];
     __shared__ float cv[kGemvMaxThreads / 64];       // ArgMax candidates of the waves (GemvArgs::amax)
     __shared__ int ci[kGemvMaxThreads / 64];
+    __shared__ float rv[EPI == EPI_RESID ? kGemvMaxThreads / 64 * R : 1];   // EPI_RESID: the rows the workgroup finished (v), [wave * R + r]
     XT *xs = reinterpret_cast<XT *>(lds_raw);
     const WT *__restrict__ W = reinterpret_cast<const WT *>(a.W);
     const int N = a.N, K = a.K;
@@ -127,22 +133,72 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
         }
         if (++lb == nb) { lb = 0; lg += nw; }
     };
+    constexpr bool kStraightPre = SMALL && (PRO == PRO_XS || EPI == EPI_RESID);
+    const WT *wrow[R];                               // kStraightPre: this lane's first chunk of the wave's rows, worked out ahead of the prologue's requests
+    if constexpr (kStraightPre) {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int row = row_of(gw, r);
+            wrow[r] = W + (size_t)(row < N ? row : N - 1) * K + lane * 8;
+        }
+    }
     auto prefetch = [&]() {
         if constexpr (PIPE) { load_next(pre[0]); return; }
 #pragma unroll
         for (int i = 0; i < NPRE; i++) {
-            if (!have_pre[i]) continue;
+            // PRO_XS / EPI_RESID: the first block goes out with no control flow around it (K >= one block: host-checked; a wave
+            // without a row group re-reads the last row), so that the wait for the activations requested in front of it stays a
+            // COUNTED one.  Behind a branch hipcc waits for the weights as well before x is staged: the stream's round trip and
+            // the prologue then run one after the other.
+            if (!(kStraightPre && i == 0) && !have_pre[i]) continue;
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const int row = row_of(gw, r);
-                const WT *wp = W + (size_t)(row < N ? row : N - 1) * K;
+                if constexpr (kStraightPre) {
 #pragma unroll
-                for (int u = 0; u < U; u++) load_raw_nt(wp + (size_t)(lane + 64 * (U * i + u)) * 8, pre[i][r][u]);
+                    for (int u = 0; u < U; u++) load_raw_nt(wrow[r] + (size_t)(64 * (U * i + u)) * 8, pre[i][r][u]);
+                } else {
+                    const int row = row_of(gw, r);
+                    const WT *wp = W + (size_t)(row < N ? row : N - 1) * K;
+#pragma unroll
+                    for (int u = 0; u < U; u++) load_raw_nt(wp + (size_t)(lane + 64 * (U * i + u)) * 8, pre[i][r][u]);
+                }
             }
         }
     };
+    // EPI_RESID: the wave's rows of the residual stream and of the next norm's weight, requested before anything else (one row
+    // group per wave, the grid covers N exactly: host-checked), so that their round trip does not trail the stream
+    float hin[R], wnx[R];
+    if constexpr (EPI == EPI_RESID) {
+#pragma unroll
+        for (int r = 0; r < R; r++) { hin[r] = a.x_in[gw_u * R + r]; wnx[r] = a.norm_w[gw_u * R + r]; }
+    }
     float inv_m = 1.0f;
-    if constexpr (PRO == PRO_NORM) {
+    if constexpr (PRO == PRO_XS) {
+        // The vector an EPI_RESID launch finished: thread c stages chunk c of bf16(v * w) and takes that chunk's sum of squares --
+        // the fmaf chain thread c of PRO_NORM runs over the same eight v -- so everything from wave_sum on is PRO_NORM's text and
+        // 1/m has PRO_NORM's bits.  One chunk per thread (nthr >= K / 8, host-checked); no residual write, no norm weight.
+        static_assert(PRO != PRO_XS || sizeof(XT) == 2, "PRO_XS stages a bf16 vector");
+        const XT *__restrict__ x = reinterpret_cast<const XT *>(a.x);
+        // requests only, and no branch around them (a thread past the vector re-reads its last chunk): behind a branch the
+        // loaded values meet a constant at the join, which is a use -- hipcc then waits for them before the weights go out
+        const int cc = min(tid, nchunk - 1);
+        __builtin_amdgcn_sched_barrier(0);               // (the row addresses above stay above)
+        const uint4v xr = *reinterpret_cast<const uint4v *>(x + cc * 8);
+        const float csv = a.cs[cc];
+        // ... and the order pinned: activations, then the stream, then the first use.  Left to itself the scheduler puts the
+        // stream's loads in front (loads return in order: x then waits for the weights) or the select below in front of the stream
+        __builtin_amdgcn_sched_barrier(0);
+        prefetch();
+        __builtin_amdgcn_sched_barrier(0);
+        if (tid < nchunk) *reinterpret_cast<uint4v *>(xs + tid * 8) = xr;
+        float ss = tid < nchunk ? csv : 0.f;
+        ss = wave_sum(ss);
+        if (lane == 0) red[wave] = ss;
+        __syncthreads();
+        ss = 0.f;
+        for (int w = 0; w < nwv; w++) ss += red[w];
+        inv_m = 1.0f / sqrtf(ss / (float)K + a.eps);           // candle rms_norm (App. A.2)
+    } else if constexpr (PRO == PRO_NORM) {
         // This is gemv_norm_prologue (gemv_parts.h) written out, plus the sliced delta: called through the header, the bf16 SMALL
         // forms (the default QKV / o_proj / down_proj launches) took 98-100 VGPRs instead of 94-96 -- 4 waves per SIMD instead of
         // 5 -- and three fp32 forms spilled 12-16 bytes more (profiles/gemv_parts/README.md)
@@ -260,12 +316,41 @@ __global__ __launch_bounds__(MAXT) void gemv_kernel(const GemvArgs a) {
             return;
         }
         if (lane != 0) return;
+        if constexpr (EPI == EPI_RESID) {
+            // each row is finished once, here: the residual add (sum + 0.f: the bits the plain epilogue stores as delta, a -0 sum
+            // included), the next norm's v * w in the conversion of store8, and v for the workgroup's chunk sums below
+            uint32_t pk[R / 2];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const float v = hin[r] + (sum[r] + 0.f);
+                rv[wave * R + r] = v;
+                a.x_out[g * R + r] = v;
+                const uint32_t b = float_to_bf16_bits(v * wnx[r]);
+                if (r & 1) pk[r >> 1] |= b << 16; else pk[r >> 1] = b;
+            }
+#pragma unroll
+            for (int r = 0; r < R / 2; r++) reinterpret_cast<uint32_t *>(a.xs_out)[g * (R / 2) + r] = pk[r];
+            return;
+        }
         if constexpr (EPI == EPI_GATEUP) gemv_store_gateup<XT, R>(reinterpret_cast<XT *>(a.out), N, g, sum);
         else if constexpr (EPI == EPI_QKV_ROPE) rope.store(g, sum);
         else gemv_store_f32<R>(reinterpret_cast<float *>(a.out), a.bias, N, g, sum, a.amax != nullptr, best);
     };
-    // the workgroup's ArgMax candidate (EPI_F32 with GemvArgs::amax)
+    // what a workgroup does once its waves are through: the ArgMax candidate (EPI_F32 with GemvArgs::amax), or (EPI_RESID) the sums of
+    // squares of its nwv * R rows (a multiple of 8, host-checked) in chunks of 8 -- ss = fmaf(v, v, ss) from 0 in element order,
+    // the chain thread c of the PRO_NORM prologue runs over chunk c
     auto leave_candidate = [&]() {
+        if constexpr (EPI == EPI_RESID) {
+            __syncthreads();
+            const int nch = (nwv * R) >> 3;
+            if (tid < nch) {
+                float ss = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; j++) ss = fmaf(rv[8 * tid + j], rv[8 * tid + j], ss);
+                a.cs_out[blockIdx.x * nch + tid] = ss;
+            }
+            return;
+        }
         if constexpr (EPI != EPI_F32 || FUSE_AR) return;
         if (a.amax) gemv_leave_candidate(a.amax, cv, ci, 0, nwv, best);              // (kernel argument: uniform)
     };
@@ -462,16 +547,27 @@ static int launch_gemv_ke(Launcher &L, const GemvArgs &a, int blocks, int waves,
     FL_TRY(raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds));
     double bytes = (double)a.N * a.K * sizeof(WT);
     char tag[32];
-    snprintf(tag, sizeof tag, "%dx%d%s%s", a.N, a.K, PRO == PRO_NORM ? ",norm" : "", a.epi == EPI_GATEUP ? ",glu" : (a.epi == EPI_QKV_ROPE ? ",rope" : ""));
+    // ",norm": the launch applies an RMSNorm to its input, through either prologue.  The recorded kernel lists
+    // (tests/golden/kernel_selection.json) know a decode step's launches by these names, so the form an edge took shows only on
+    // request -- fl_tune "gemv_resid" = 2: ",xs" for the staged-vector prologue, ",resid" for the producer
+    const bool forms = tune(TK_GEMV_RESID) >= 2;
+    snprintf(tag, sizeof tag, "%dx%d%s%s", a.N, a.K, PRO == PRO_XS && forms ? ",xs" : (PRO != PRO_X ? ",norm" : ""),
+             a.epi == EPI_GATEUP ? ",glu" : (a.epi == EPI_QKV_ROPE ? ",rope" : (a.epi == EPI_RESID && forms ? ",resid" : "")));
     Launcher LL = L; LL.tag = tag;
     return LL.launch(KC_GEMV, bytes, 2.0 * a.N * a.K, kern, dim3((unsigned)blocks), dim3((unsigned)waves * 64), lds, a);
 }
 
 template <typename WT, typename XT, int R, int U, int PRO, int MAXT, bool SMALL>
 static int launch_gemv_k(Launcher &L, const GemvArgs &a, int blocks, int waves, size_t lds) {
+    if (a.epi == EPI_RESID) {                               // (bf16, plain prologue: launch_gemv has checked)
+        if constexpr (sizeof(WT) == 2 && PRO == PRO_X) return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_RESID>(L, a, blocks, waves, lds);
+        else FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the residual epilogue is a bf16 launch with the plain prologue");
+    }
     if (a.epi == EPI_GATEUP) return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_GATEUP>(L, a, blocks, waves, lds);
     if (a.epi == EPI_QKV_ROPE) return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_QKV_ROPE>(L, a, blocks, waves, lds);
-    if (a.ll) return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_F32, true>(L, a, blocks, waves, lds);
+    if constexpr (PRO != PRO_XS) {                          // (no tensor-parallel form of the staged-vector prologue)
+        if (a.ll) return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_F32, true>(L, a, blocks, waves, lds);
+    }
     return launch_gemv_ke<WT, XT, R, U, PRO, MAXT, SMALL, EPI_F32>(L, a, blocks, waves, lds);
 }
 
@@ -487,6 +583,13 @@ static int launch_gemv_t(Launcher &L, const GemvArgs &a) {
     }
     if (PRO == PRO_NORM && (int64_t)waves * 64 * 3 * 8 < K) waves = (int)((K + 64 * 3 * 8 - 1) / (64 * 3 * 8));   // staging capacity
     if (waves < 4) waves = 4;
+    if (PRO == PRO_XS && (int64_t)waves * 64 < (K >> 3)) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: %d threads stage fewer than K / 8 = %d chunks", waves * 64, (int)(K >> 3));
+    if (a.epi == EPI_RESID) {
+        // each row finished once by the wave that holds its sum, a workgroup's rows whole chunks of 8 (gemv_resid_edge, gemv_geometry.h)
+        if (g_force_blocks.load() != 0 || g_force_waves.load() != 0) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the residual epilogue does not run on a forced grid");
+        if ((int64_t)blocks * waves * R != N || (waves * R) % 8 != 0)
+            FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the residual epilogue needs a grid that covers N = %d exactly (%d x %d waves x %d rows)", (int)N, blocks, waves, R);
+    }
     const int allow_small = tune(TK_GEMV_SMALL);
     const bool small = allow_small && sizeof(WT) == 2 && ngroups <= (int64_t)blocks * waves && (K >> 3) % (64 * U) == 0 &&
                        (K >> 3) <= 2 * 64 * U && (PRO != PRO_NORM || (int64_t)waves * 64 * 8 >= K);
@@ -512,7 +615,7 @@ static int launch_gemv_ru(Launcher &L, const GemvArgs &a) {
         // the QKV projection is short enough for every wave to own ONE row group: with U = K / 512 its whole share is one block,
         // requested before the norm prologue runs (the SMALL form): Mistral-7B 11.8 -> 10.5 us
         // (bf16 only: with fp32 weights eight chunks per row are 128 VGPRs of stream buffers -- the fp32 mode's QKV ran at 1.4 TB/s from scratch spills)
-        if (sizeof(WT) == 2 && R == 2 && a.epi == EPI_QKV_ROPE && a.pro == PRO_NORM && (a.K == 4096 || a.K == 3584)) U = a.K / 512;
+        if (sizeof(WT) == 2 && R == 2 && a.epi == EPI_QKV_ROPE && a.pro != PRO_X && (a.K == 4096 || a.K == 3584)) U = a.K / 512;
     }
     if (R == 4 && U == 2) return launch_gemv_t<WT, XT, 4, 2, PRO>(L, a);
     if (R == 2 && U == 7) return launch_gemv_t<WT, XT, 2, 7, PRO>(L, a);
@@ -537,6 +640,15 @@ int64_t gemv_owner_chunk(int dtype, int64_t N, int64_t K) {
     return (int64_t)waves * R * K * (int64_t)es;
 }
 
+bool gemv_resid_edge_fits(int dtype, bool one_shard, bool compute_weights, int64_t N, int64_t K, int64_t Nc) {
+    GemvResidEdge e;
+    e.N = N; e.K = K; e.Nc = Nc; e.cus = device_cu_count();
+    e.bf16 = dtype == FL_DTYPE_BF16; e.one_shard = one_shard; e.compute_weights = compute_weights;
+    e.force_blocks = g_force_blocks.load(); e.force_waves = g_force_waves.load();
+    // (R = 2 whatever "gemv_u" says: launch_gemv_ru; a forced "gemv_r" keeps the norm prologue)
+    return tune(TK_GEMV_R) == 2 && gemv_supported(dtype, N, K) && gemv_supported(dtype, Nc, N) && gemv_resid_edge(e);
+}
+
 int launch_gemv(Launcher &L, int dtype, const GemvArgs &a) {
     if (a.N <= 0 || a.K <= 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: bad shape");
     if (!gemv_supported(dtype, a.N, a.K)) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: K=%d unsupported", a.K);
@@ -544,6 +656,18 @@ int launch_gemv(Launcher &L, int dtype, const GemvArgs &a) {
     if (a.epi == EPI_GATEUP && a.N % 32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up matrix rows must be a multiple of 32");
     if (a.ll && (a.epi != EPI_F32 || a.bias || a.ll_slot <= 0)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fused all-reduce: plain fp32 epilogue without bias only");
     if (a.epi == EPI_QKV_ROPE && (a.d <= 0 || a.d % 2 || a.N != (a.H + 2 * a.Hkv) * a.d)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad qkv shape");
+    if (a.pro != PRO_X && a.pro != PRO_NORM && a.pro != PRO_XS) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: prologue %d", a.pro);
+    if (a.epi == EPI_RESID) {
+        if (dtype != FL_DTYPE_BF16 || a.pro != PRO_X) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the residual epilogue is a bf16 launch with the plain prologue");
+        if (a.ll || a.bias || a.x_scale || a.amax) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: the residual epilogue takes no bias, row scale, all-reduce or ArgMax");
+        if (!a.x_in || !a.norm_w || !a.x_out || !a.xs_out || !a.cs_out || a.x_in == a.x_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: the residual epilogue needs x_in, norm_w, x_out (not x_in), xs_out and cs_out");
+        if (a.N % 8) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the residual epilogue needs N a multiple of 8");
+    }
+    if (a.pro == PRO_XS) {
+        if (dtype != FL_DTYPE_BF16 || a.ll || a.epi == EPI_RESID) FL_FAIL(FL_ERR_UNSUPPORTED, "launch_gemv: the staged-vector prologue is a bf16 launch with the fp32, gate/up or RoPE epilogue");
+        if (!a.x || !a.cs) FL_FAIL(FL_ERR_BAD_ARGUMENT, "launch_gemv: the staged-vector prologue needs x and cs");
+        return launch_gemv_ru<bf16_t, bf16_t, PRO_XS>(L, a);
+    }
     if (dtype == FL_DTYPE_BF16)
         return a.pro == PRO_NORM ? launch_gemv_ru<bf16_t, bf16_t, PRO_NORM>(L, a) : launch_gemv_ru<bf16_t, bf16_t, PRO_X>(L, a);
     return a.pro == PRO_NORM ? launch_gemv_ru<float, float, PRO_NORM>(L, a) : launch_gemv_ru<float, float, PRO_X>(L, a);

@@ -51,7 +51,7 @@ struct Launcher {
 int device_cu_count();   // CUs of the current device, cached per device (runtime.hip); 256 where the runtime does not tell
 
 enum { EPI_F32 = 0, EPI_GATEUP = 1, EPI_QKV_ROPE = 2, EPI_RESID = 3 };
-// EPI_RESID (256x256 prefill GEMM only): the o_proj / down_proj epilogue takes over the residual add and the next
+// EPI_RESID (prefill GEMMs; the decode stream's form: GemvArgs below): the o_proj / down_proj epilogue takes over the residual add and the next
 // RMSNorm's first pass -- h += y (fp32, in place), xn = (h + y) * w in the compute dtype, and partial sums of squares of
 // h + y per (row, column tile, wave column) that rms_finalize turns into 1/rms -- instead of a y round trip through
 // HBM and an rmsnorm_add launch.
@@ -62,7 +62,7 @@ struct ResidEpi {
     float *part = nullptr;         // [T][np]
     int np = 0;
 };
-enum { PRO_X = 0, PRO_NORM = 1 };
+enum { PRO_X = 0, PRO_NORM = 1, PRO_XS = 2 };   // PRO_XS (decode stream): the normalised vector and its chunk sums of squares, left by an EPI_RESID launch
 
 struct LLTable;
 // Arguments of the decode weight-streaming kernel (k_gemv.hip), passed by value as kernarg.
@@ -95,6 +95,14 @@ struct GemvArgs {
     // ((value, index) pairs; ties -> the larger index, as argmax_last), so that token selection reads gridDim.x candidates
     // instead of the whole vocabulary; amax[0] is the candidate count.  null = not wanted.
     ArgmaxCand *amax = nullptr;
+    // EPI_RESID (bf16, PRO_X, no bias / ll; the o_proj / down_proj of a decode step where gemv_resid_edge_fits): v = x_in + W . x goes
+    // to x_out, bf16(v * norm_w) to xs_out [N] and the sum of squares of every 8 consecutive v to cs_out [N / 8]; `out` is not written.
+    // Its grid must cover N exactly with one row group per wave: FL_ERR_UNSUPPORTED otherwise.
+    void *xs_out = nullptr;
+    float *cs_out = nullptr;
+    // PRO_XS (bf16): x = such an xs [K], cs = such a cs [K / 8]: the RMSNorm of PRO_NORM with the residual add, v * w and the squares
+    // already done; one chunk per staging thread (FL_ERR_UNSUPPORTED where the grid's workgroups have fewer than K / 8 threads)
+    const float *cs = nullptr;
 };
 int launch_gemv(Launcher &L, int dtype, const GemvArgs &a);
 // bytes of W that workgroup b of the plain-epilogue launch (no norm prologue) of an N x K matrix reads as one contiguous piece
@@ -102,6 +110,8 @@ int launch_gemv(Launcher &L, int dtype, const GemvArgs &a);
 int64_t gemv_owner_chunk(int dtype, int64_t N, int64_t K);
 bool gemv_leaves_candidates(int dtype, const GemvArgs &a);   // the grid launch_gemv would pick fits the candidate buffer
 bool gemv_norm_supported(int dtype, int64_t N, int64_t K);
+// gemv_resid_edge (gemv_geometry.h) for an [N, K] producer and an [Nc, N] consumer on the current device, under the fl_tune grid and "gemv_r"
+bool gemv_resid_edge_fits(int dtype, bool one_shard, bool compute_weights, int64_t N, int64_t K, int64_t Nc);
 void gemv_set_tuning(int blocks, int waves);   // fl_tune "gemv_blocks" / "gemv_waves": force the grid / waves per workgroup (0 automatic, -1 keep)
 
 // ---- FP8 weights (k_gemv_w8.hip): W' = s[row] * q, q e4m3fn, s a power of two per row (FL_WEIGHTS_E4M3_ROW) ------------

@@ -51,6 +51,9 @@ struct Scratch {                 // activations of one forward chunk on one shar
     void *ao = nullptr;          // [T,Hs*d] attention output
     void *act = nullptr;         // [T,Ip] silu(gate)*up
     uint32_t *ids = nullptr;     // [T]
+    // decode only: what an o_proj / down_proj with the residual epilogue leaves for the projection behind the next norm
+    void *xs_res = nullptr;      // [h] bf16: (x_res + delta) * norm_weight
+    float *cs_res = nullptr;     // [h/8] sums of squares of x_res + delta per 8 elements
 };
 
 // One-shot collectives over peer-mapped HBM (k_comm.hip): this rank's inbox and its view of the peers'.

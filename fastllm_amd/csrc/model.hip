@@ -305,6 +305,12 @@ static GemvArgs qkv_gemv_args(Model *m, Cache *c, Shard &sh, CacheShard &cs, con
     return a;
 }
 
+// A consumer behind a norm takes the vector its producer's residual epilogue finished (GemvArgs: PRO_XS) instead of x_in + delta
+static void take_finished_norm(GemvArgs &a, const Scratch &sc) {
+    a.pro = PRO_XS; a.x = sc.xs_res; a.cs = sc.cs_res;
+    a.x_in = nullptr; a.delta = nullptr; a.delta_nslab = 1; a.norm_w = nullptr; a.x_out = nullptr;
+}
+
 static int enqueue_decode_engine(Model *m, Cache *c, int64_t len_hint) {
     const Dims &D = m->D;
     const int dt = m->dtype;
@@ -370,11 +376,28 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
         a.ll = sh.pc.ll_dev; a.ll_slot = slot;
         return launch_gemv(L, dt, a);
     };
+    // The two norm edges of a layer (fl_tune "gemv_resid"), decided edge by edge (gemv_resid_edge, gemv_geometry.h): the producer --
+    // o_proj / down_proj as a plain launch_gemv -- finishes h = res_in + W . x, h * w_next and the chunk sums of squares in its
+    // epilogue, and the consumer stages that vector.  res_in / res_out: the buffers the norm prologue of the edge's consumer reads as
+    // x_in and writes as x_out, so that an edge in either form leaves the residual where the next one looks for it.
+    const bool resid = tune(TK_GEMV_RESID) != 0 && !far;
+    auto edge_fits = [&](int64_t K, int64_t Nc) -> bool {
+        return resid && gemv_resid_edge_fits(dt, m->shards.size() == 1 && m->tp == 1, !w8, D.h, K, Nc);
+    };
+    auto producer = [&](Launcher &L, Scratch &sc, const void *W, const void *x, int64_t K, const float *res_in, float *res_out, const float *w_next) -> int {
+        GemvArgs a;
+        a.W = W; a.x = x; a.N = (int)D.h; a.K = (int)K; a.epi = EPI_RESID; a.pro = PRO_X;
+        a.x_in = res_in; a.norm_w = w_next; a.x_out = res_out; a.xs_out = sc.xs_res; a.cs_out = sc.cs_res;
+        return launch_gemv(L, dt, a);
+    };
+    bool down_done = false;                                  // the previous layer's down_proj has finished this layer's first norm
     for (int64_t l = 0; l < D.L; l++) {
+        bool o_done = false;
         FL_TRY(each_shard(m, c, [&](Shard &sh, CacheShard &cs, Launcher &L) -> int {
             Scratch &sc = sh.dec; LayerW &ly = sh.layers[l];
             const KvLayer kv(m, c, sh, cs, l);
             GemvArgs a = qkv_gemv_args(m, c, sh, cs, kv, l);
+            if (down_done) take_finished_norm(a, sc);
             FL_TRY(gemv(L, a, ly.wqkv8, ly.sqkv));
             AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, len_hint + 1};
             if (!w8) {
@@ -392,7 +415,9 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
                 FL_TRY(launch_attn_oproj_rep(L, ra));
             } else {
                 FL_TRY(attend_decode(L, m, c, sh, cs, kv, sc.q, sc.ao, as));
-                if (w8) FL_TRY(plain_w8(L, ly.wo8, ly.so, sc.ao, sh.Hs * D.d, sc.delta));
+                o_done = edge_fits(sh.Hs * D.d, 2 * sh.Ip);
+                if (o_done) FL_TRY(producer(L, sc, ly.wo, sc.ao, sh.Hs * D.d, sc.x_res2, sc.x_res, ly.ln2));
+                else if (w8) FL_TRY(plain_w8(L, ly.wo8, ly.so, sc.ao, sh.Hs * D.d, sc.delta));
                 else if (far) FL_TRY(row_parallel(L, sh, ly.wo, sc.ao, sh.Hs * D.d, sc.delta, (int)(2 * l + 1)));
                 else FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, 1, D.h, sh.Hs * D.d, EPI_F32));
             }
@@ -405,8 +430,12 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             a.W = ly.wgu; a.out = sc.act; a.N = (int)(2 * sh.Ip); a.K = (int)D.h; a.epi = EPI_GATEUP; a.pro = PRO_NORM;
             a.x_in = sc.x_res2; a.delta = sc.delta; a.norm_w = ly.ln2; a.eps = D.eps; a.x_out = sc.x_res; a.st = cs.st;
             if (c->fuse_oproj) a.delta_nslab = (int)sh.Hkvs;           // one partial vector per kv head
+            if (o_done) take_finished_norm(a, sc);
             FL_TRY(gemv(L, a, ly.wgu8, ly.sgu));
-            if (w8) FL_TRY(plain_w8(L, ly.wd8, ly.sd, sc.act, sh.Ip, sc.delta));
+            const bool last = l + 1 == D.L;
+            down_done = edge_fits(sh.Ip, last ? sh.Vs : (sh.Hs + 2 * sh.Hkvs) * D.d);
+            if (down_done) FL_TRY(producer(L, sc, ly.wd, sc.act, sh.Ip, sc.x_res, sc.x_res2, last ? sh.norm : sh.layers[l + 1].ln1));
+            else if (w8) FL_TRY(plain_w8(L, ly.wd8, ly.sd, sc.act, sh.Ip, sc.delta));
             else if (far) FL_TRY(row_parallel(L, sh, ly.wd, sc.act, sh.Ip, sc.delta, (int)(2 * l + 2)));
             else FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, 1, D.h, sh.Ip, EPI_F32));
             return FL_OK;
@@ -419,6 +448,7 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
         a.W = sh.lm_head; a.out = lm_head_out(m, sh); a.N = (int)sh.Vs; a.K = (int)D.h; a.epi = EPI_F32; a.pro = PRO_NORM;
         if (!m->vocab_parallel && tune(TK_ARGMAX_FUSED) && (w8 ? gemv_w8_leaves_candidates(a.N, a.K) : gemv_leaves_candidates(dt, a))) { a.amax = sh.amax; sh.amax_valid = true; }   // token selection reads one candidate per workgroup
         a.x_in = sc.x_res; a.delta = sc.delta; a.norm_w = sh.norm; a.eps = D.eps; a.st = cs.st;
+        if (down_done) take_finished_norm(a, sc);
         return gemv(L, a, sh.lm_head8, sh.lm_head_s);
     }));
     return gather_logits(m);

@@ -146,6 +146,7 @@ static const TuneEntry g_tune_table[TK_COUNT] = {
     {"f32_rows_max", 64},
     {"gateup_rowsplit", 1},
     {"score_rows", 256},
+    {"gemv_resid", 1},
 };
 static_assert(sizeof(g_tune_table) / sizeof(g_tune_table[0]) == TK_COUNT, "one row per TuneKey, in the enum's order");
 static std::atomic<int> g_tune[TK_COUNT];

@@ -382,6 +382,10 @@ int alloc_scratch(Model *m, Shard &sh, Scratch &sc, int64_t T, std::vector<void 
     sc.cap_T = T;
     FL_TRY(dev_alloc(own, (void **)&sc.x_res, (size_t)T * D.h * 4, acct));
     if (T == 1) FL_TRY(dev_alloc(own, (void **)&sc.x_res2, (size_t)D.h * 4, acct));
+    if (T == 1 && m->dtype == FL_DTYPE_BF16) {
+        FL_TRY(dev_alloc(own, &sc.xs_res, (size_t)D.h * 2, acct));
+        FL_TRY(dev_alloc(own, (void **)&sc.cs_res, (size_t)(D.h + 7) / 8 * 4, acct));
+    }
     // split-K slabs of any prompt <= T; decode: one partial vector per kv head (fused attention + o_proj launch)
     FL_TRY(dev_alloc(own, (void **)&sc.delta, (size_t)std::max<int64_t>(slab_rows(T, ksplit_cap_max), T == 1 ? sh.Hkvs : 0) * D.h * 4, acct));
     FL_TRY(dev_alloc(own, &sc.xn, (size_t)T * D.h * es, acct));

@@ -942,6 +942,38 @@ typedef struct fl_linear_resid_args {
 } fl_linear_resid_args;
 int fl_op_linear_resid(const fl_linear_resid_args *args);
 
+/* The decode stream's residual epilogue and the prologue that consumes it (bf16, one row; k_gemv.hip EPI_RESID / PRO_XS).
+ * mode 0, the producer alone: h_out = h_in + w . x, xs_out = bf16(h_out * w_next) (bits), cs_out [N/8] = the sum of squares of every 8
+ *   consecutive h_out; delta_out [N]: the launch's `out` buffer, which it must leave as the NaN pattern it was filled with.
+ * mode 1, the consumer alone on the caller's xs (bf16 bits) and cs: y = (w2 . xs) / sqrt(sum(cs) / N + eps) through epilogue epi2 --
+ *   0: y_out [N2] fp32, and amax_out[0] = the row the launch's ArgMax candidates give (-1 where its grid leaves none); 1 (w2 rows
+ *   gate | up in HF order): [N2/2] silu(gate) * up; 2 (N2 = (H + 2 Hkv) d): RoPE at `pos`, the row appended at slot `len` of a cache
+ *   of seq_alloc positions (V transposed); y_out [N2] = q | the appended k row | the appended v row.
+ * mode 2, the pair, next to today's two launches (plain epilogue, then the norm prologue) on the same inputs: the above, and h_ref,
+ *   y_ref, amax_out[1] from those.
+ * inv_out / inv_ref: the 1/m the prologue applied, read through a probe launch of the consumer's shape on the same sums (see
+ * api_ops.hip).  FL_ERR_UNSUPPORTED where a launch does not take the form (a grid that does not cover N exactly, a forced grid,
+ * fewer staging threads than N / 8).  repeat launches (1..8) run on the same buffers: FL_ERR_HIP if one gives other bytes. */
+typedef struct fl_gemv_resid_args {
+    size_t struct_size;             /* sizeof(fl_gemv_resid_args) */
+    int32_t mode, epi2, repeat, reserved;
+    int64_t N, K, N2;
+    int64_t H, Hkv, d, max_pos, pos, len, seq_alloc;   /* epi2 2 */
+    const void *x;                  /* [K] bf16 */
+    const void *w;                  /* [N][K] bf16 */
+    const float *h_in, *w_next;     /* [N] fp32 */
+    const void *xs;                 /* mode 1: [N] bf16 */
+    const float *cs;                /* mode 1: [N/8] */
+    const void *w2;                 /* [N2][N] bf16 */
+    const float *cos_tab, *sin_tab; /* epi2 2: [max_pos][d/2] */
+    float eps, reserved2;
+    float *h_out; void *xs_out; float *cs_out, *delta_out;
+    float *y_out, *inv_out;
+    float *h_ref, *y_ref, *inv_ref;
+    int32_t *amax_out;              /* [2] or NULL */
+} fl_gemv_resid_args;
+int fl_op_gemv_resid(const fl_gemv_resid_args *args);
+
 /* ---- QKV projection -> RoPE -> KV append in each of its forms, on host buffers (unit tests) -------------------------------------- */
 
 /* The sequences of one call, shared by the two calls below.  Sequence s brings count[s] new rows (the rows of all sequences back to

@@ -302,6 +302,49 @@ pub struct fl_linear_resid_args {
     pub kernels_out: *mut i32,
 }
 
+/// `fl_gemv_resid_args`: the decode stream's residual epilogue and the prologue that consumes it (fl_op_gemv_resid, unit tests);
+/// `struct_size` is `size_of::<fl_gemv_resid_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_gemv_resid_args {
+    pub struct_size: usize,
+    pub mode: i32,
+    pub epi2: i32,
+    pub repeat: i32,
+    pub reserved: i32,
+    pub n: i64,
+    pub k: i64,
+    pub n2: i64,
+    pub h: i64,
+    pub hkv: i64,
+    pub d: i64,
+    pub max_pos: i64,
+    pub pos: i64,
+    pub len: i64,
+    pub seq_alloc: i64,
+    pub x: *const c_void,
+    pub w: *const c_void,
+    pub h_in: *const f32,
+    pub w_next: *const f32,
+    pub xs: *const c_void,
+    pub cs: *const f32,
+    pub w2: *const c_void,
+    pub cos_tab: *const f32,
+    pub sin_tab: *const f32,
+    pub eps: f32,
+    pub reserved2: f32,
+    pub h_out: *mut f32,
+    pub xs_out: *mut c_void,
+    pub cs_out: *mut f32,
+    pub delta_out: *mut f32,
+    pub y_out: *mut f32,
+    pub inv_out: *mut f32,
+    pub h_ref: *mut f32,
+    pub y_ref: *mut f32,
+    pub inv_ref: *mut f32,
+    pub amax_out: *mut i32,
+}
+
 /// `fl_rope_seqs`: the sequences of an fl_op_rope_kv / fl_op_qkv_rope call -- per sequence its new rows, RoPE position, cache length,
 /// capacity and value layout, and its whole K / V caches (updated in place).
 #[repr(C)]
@@ -987,6 +1030,7 @@ extern "C" {
     ) -> c_int;
     pub fn fl_op_norm_linear(args: *const fl_norm_linear_args) -> c_int;
     pub fn fl_op_linear_resid(args: *const fl_linear_resid_args) -> c_int;
+    pub fn fl_op_gemv_resid(args: *const fl_gemv_resid_args) -> c_int;
     pub fn fl_op_rope_kv(args: *const fl_rope_kv_args) -> c_int;
     pub fn fl_op_qkv_rope(args: *const fl_qkv_rope_args) -> c_int;
     pub fn fl_op_attn_oproj_rep(args: *const fl_attn_oproj_rep_args) -> c_int;
