@@ -207,6 +207,17 @@ class FlAttnOprojRepArgs(C.Structure):
                 ("info_out", C.c_void_p)]
 
 
+class FlEncoderRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int32), ("dtype", C.c_int32), ("n_slab", C.c_int32), ("repeat", C.c_int32),
+                ("act", C.c_int32), ("reserved", C.c_int32), ("T", C.c_int64), ("h", C.c_int64), ("vocab", C.c_int64), ("P", C.c_int64),
+                ("n_seq", C.c_size_t), ("word", C.c_void_p), ("pos", C.c_void_p), ("tt0", C.c_void_p), ("ids", C.c_void_p),
+                ("offsets", C.c_void_p), ("x", C.c_void_p), ("slabs", C.c_void_p), ("bias", C.c_void_p), ("ln_w", C.c_void_p),
+                ("ln_b", C.c_void_p), ("eps", C.c_float), ("reserved2", C.c_float), ("x_res_out", C.c_void_p), ("out", C.c_void_p)]
+
+
+# act of op_encoder_bias_act
+ENC_ACT = {None: -1, "none": -1, "gelu_tanh": 0, "gelu_erf": 1}
+
 # kernels_out[0] of op_rope_kv
 ROPE_KV_NAMES = ("scalar", "vector", "batch", "packed")
 
@@ -410,6 +421,7 @@ def lib():
         L.fl_encoder_hidden.argtypes = [vp, vp, sz, vp]
         L.fl_encoder_embed.argtypes = [vp, vp, vp, sz, vp]
         L.fl_op_encoder_attention.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.c_int64, C.c_int32, vp]
+        L.fl_op_encoder_rows.argtypes = [C.POINTER(FlEncoderRowsArgs)]
         _LIB = L
     return _LIB
 
@@ -764,6 +776,74 @@ def op_encoder_attention(q, k, v, lengths, H, d):
     _check(lib().fl_op_encoder_attention(q.ctypes.data, k.ctypes.data, v.ctypes.data, offs.ctypes.data, len(lengths), H, d,
                                          _np_dtype_code(q), out.ctypes.data))
     return out
+
+
+def _encoder_rows(form, dtype, T, h, out_rows, keep, repeat=1, **fields):
+    """one fl_op_encoder_rows call; fields: name -> array (its pointer), int or float.  Returns (x_res_out [T, h] float32 for forms 0
+    and 1, out [out_rows, h] as stored: uint16 bf16 bits or float32)."""
+    bf16 = dtype == "bf16"
+    a = FlEncoderRowsArgs()
+    a.struct_size = C.sizeof(FlEncoderRowsArgs)
+    a.form, a.dtype, a.repeat, a.n_slab, a.T, a.h = form, BF16 if bf16 else F32, repeat, 1, T, h
+    for name, v in fields.items():
+        setattr(a, name, v.ctypes.data if isinstance(v, np.ndarray) else v)
+    x_res = np.empty((T, h), np.float32) if form <= 1 else None
+    out = np.empty((out_rows, h), np.uint16 if bf16 and form != 3 else np.float32)
+    a.x_res_out, a.out = _ptr(x_res), out.ctypes.data
+    _check(lib().fl_op_encoder_rows(C.byref(a)))
+    del keep
+    return x_res, out
+
+
+def _offsets(lengths):
+    offs = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lengths)
+    return offs
+
+
+def op_encoder_embed_ln(word, pos, ids, lengths, ln_w, ln_b, eps, dtype, tt0=None, repeat=1):
+    """launch_encoder_embed_ln alone (fl_op_encoder_rows form 0): word [vocab, h], pos [P, h] and tt0 [h] (optional) as uint16 bf16 bits
+    (dtype "bf16") or float32; ids [sum(lengths)]; sequence s owns lengths[s] rows.  Returns (x_res [T, h] float32, xn [T, h] as
+    stored)."""
+    et = np.uint16 if dtype == "bf16" else np.float32
+    word, pos = np.ascontiguousarray(word, dtype=et), np.ascontiguousarray(pos, dtype=et)
+    tt0 = np.ascontiguousarray(tt0, dtype=et) if tt0 is not None else None
+    ids, offs, ln_w, ln_b = np.ascontiguousarray(ids, dtype=np.uint32), _offsets(lengths), _f32(ln_w), _f32(ln_b)
+    T, h = int(offs[-1]), word.shape[1]
+    assert ids.shape == (T,) and pos.shape[1] == h and ln_w.shape == ln_b.shape == (h,) and (tt0 is None or tt0.shape == (h,))
+    return _encoder_rows(0, dtype, T, h, T, (word, pos, tt0, ids, offs, ln_w, ln_b), repeat, word=word, pos=pos, tt0=_ptr(tt0), ids=ids,
+                         offsets=offs, n_seq=len(lengths), vocab=word.shape[0], P=pos.shape[0], ln_w=ln_w, ln_b=ln_b, eps=eps)
+
+
+def op_encoder_add_ln(x, slabs, ln_w, ln_b, eps, dtype, bias=None, repeat=1):
+    """launch_encoder_add_ln alone (fl_op_encoder_rows form 1): x [T, h] and slabs [n_slab, T, h] float32, bias [h] (optional).
+    Returns (x_res [T, h] float32 after the call, xn [T, h] as stored: uint16 bf16 bits or float32)."""
+    x, slabs, ln_w, ln_b = _f32(x), _f32(slabs), _f32(ln_w), _f32(ln_b)
+    bias = _f32(bias) if bias is not None else None
+    T, h = x.shape
+    assert slabs.shape[1:] == (T, h) and ln_w.shape == ln_b.shape == (h,) and (bias is None or bias.shape == (h,))
+    return _encoder_rows(1, dtype, T, h, T, (x, slabs, ln_w, ln_b, bias), repeat, x=x, slabs=slabs, n_slab=slabs.shape[0], bias=_ptr(bias),
+                         ln_w=ln_w, ln_b=ln_b, eps=eps)
+
+
+def op_encoder_bias_act(slabs, dtype, bias=None, act=None, repeat=1):
+    """launch_encoder_bias_act alone (fl_op_encoder_rows form 2): slabs [n_slab, T, N] float32, bias [N] (optional), act None /
+    "gelu_tanh" / "gelu_erf" (ENC_ACT).  Returns out [T, N] as stored: uint16 bf16 bits or float32."""
+    slabs = _f32(slabs)
+    bias = _f32(bias) if bias is not None else None
+    n_slab, T, N = slabs.shape
+    assert bias is None or bias.shape == (N,)
+    return _encoder_rows(2, dtype, T, N, T, (slabs, bias), repeat, slabs=slabs, n_slab=n_slab, bias=_ptr(bias),
+                         act=act if isinstance(act, int) else ENC_ACT[act])[1]
+
+
+def op_encoder_pool_l2(x, lengths, repeat=1):
+    """launch_encoder_pool_l2 alone (fl_op_encoder_rows form 3): x [sum(lengths), h] float32; returns the L2-normalised mean of each
+    member's rows, [len(lengths), h] float32."""
+    x, offs = _f32(x), _offsets(lengths)
+    T, h = x.shape
+    assert T == int(offs[-1])
+    return _encoder_rows(3, "f32", T, h, len(lengths), (x, offs), repeat, x=x, offsets=offs, n_seq=len(lengths))[1]
 
 
 class Model:

@@ -340,6 +340,40 @@ int qkv_rope_check(const fl_qkv_rope_args *a) {
     return FL_OK;
 }
 
+// the fl_op_encoder_rows checks, none of which needs a device; *T_out: the rows of the call
+int encoder_rows_check(const fl_encoder_rows_args *a, int64_t *T_out) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: null args");
+    if (a->struct_size != sizeof(fl_encoder_rows_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_encoder_rows_args));
+    if (a->form < 0 || a->form > 3) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: form %d not in 0..3", a->form);
+    if (a->dtype != FL_DTYPE_BF16 && a->dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: dtype must be bf16 or f32");
+    if (a->repeat < 1 || a->repeat > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: repeat %d not in 1..8", a->repeat);
+    if (!a->out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: null out");
+    if (a->h < 1 || a->h > 65536) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: h %lld not in 1..65536", (long long)a->h);
+    if (a->form != 3 && a->h % 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: form %d: the row width %lld must be a multiple of 8", a->form, (long long)a->h);
+    if (a->form == 1 || a->form == 2) {
+        if (a->n_slab < 1 || a->n_slab > 8) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: n_slab %d not in 1..8", a->n_slab);
+        if (a->T < 1 || a->T > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: T %lld not in 1..2^20", (long long)a->T);
+        if (!a->slabs) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: null slabs");
+        *T_out = a->T;
+    } else {
+        int64_t longest = 0;
+        if (a->form == 0 && (a->P < 1 || a->P > (1 << 20) || a->vocab < 1 || a->vocab > (1 << 24))) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: P in 1..2^20, vocab in 1..2^24");
+        if (a->n_seq > ((size_t)1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: n_seq above 2^20");
+        FL_TRY(encoder_check_offsets(a->offsets, a->n_seq, a->form == 0 ? a->P : 0, 1 << 20, T_out, &longest));
+    }
+    if ((double)*T_out * (double)a->h * (a->form == 0 || a->form == 3 ? 1 : a->n_slab) > (double)(1 << 28)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: more than 2^28 elements");
+    if (a->form == 0) {
+        if (!a->word || !a->pos || !a->ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: form 0: null argument (word, pos, ids)");
+        for (int64_t t = 0; t < *T_out; t++)
+            if ((int64_t)a->ids[t] >= a->vocab) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: ids[%lld] = %u is not below vocab %lld", (long long)t, a->ids[t], (long long)a->vocab);
+    }
+    if (a->form <= 1 && (!a->ln_w || !a->ln_b || !a->x_res_out)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: form %d: null argument (ln_w, ln_b, x_res_out)", a->form);
+    if ((a->form == 1 || a->form == 3) && !a->x) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: form %d: null x", a->form);
+    if (a->form == 2 && a->act != ENC_ACT_NONE && a->act != ENC_ACT_GELU_TANH && a->act != ENC_ACT_GELU_ERF)
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_encoder_rows: act %d (-1 none, 0 gelu_tanh, 1 gelu_erf)", a->act);
+    return FL_OK;
+}
+
 int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, int64_t d) {
     if ((dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) || layout < 0 || layout > 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype: bf16 or f32; layout: 0 plain, 1 MFMA");
     if (H < 1 || Hkv < 1 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head counts (H a multiple of Hkv)");
@@ -880,6 +914,66 @@ int fl_op_encoder_attention(const void *q, const void *k, const void *v, const s
         FL_TRY(launch_encoder_attention(B.L, dtype, qd, kd, vd, H * d, offd, (int64_t)n_seq, longest, T, H, d, 1.0f / sqrtf((float)d), od));
         FL_HIP(hipStreamSynchronize(B.s));
         return op_download(out, od, n, dtype);
+    });
+}
+
+int fl_op_encoder_rows(const fl_encoder_rows_args *args) {
+    return guarded([&]() -> int {
+        int64_t T = 0;
+        FL_TRY(encoder_rows_check(args, &T));
+        const fl_encoder_rows_args &a = *args;
+        OpScope B;
+        FL_TRY(B.begin());
+        const int form = a.form, dtype = a.dtype;
+        const int64_t h = a.h;
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4, n = (size_t)T * h;
+        const size_t xbytes = form <= 1 ? n * 4 : 0;                          // x_res_out
+        const size_t obytes = form == 3 ? a.n_seq * (size_t)h * 4 : n * es;   // out
+        void *word = nullptr, *pos = nullptr, *tt0 = nullptr, *od; uint32_t *ids = nullptr; int32_t *row_seq = nullptr, *offd = nullptr;
+        float *x0 = nullptr, *xr = nullptr, *slabs = nullptr, *bias = nullptr, *lnw = nullptr, *lnb = nullptr;
+        if (form == 0 || form == 3) {
+            std::vector<int32_t> rs((size_t)T), off(a.n_seq + 1);
+            for (size_t s = 0; s <= a.n_seq; s++) off[s] = (int32_t)a.offsets[s];
+            for (size_t s = 0; s < a.n_seq; s++)
+                for (size_t r = a.offsets[s]; r < a.offsets[s + 1]; r++) rs[r] = (int32_t)s;
+            FL_TRY(B.upload(&offd, off.data(), (a.n_seq + 1) * 4));
+            if (form == 0) FL_TRY(B.upload(&row_seq, rs.data(), (size_t)T * 4));
+        }
+        if (form == 0) {
+            FL_TRY(B.upload(&word, a.word, (size_t)a.vocab * h * es)); FL_TRY(B.upload(&pos, a.pos, (size_t)a.P * h * es));
+            if (a.tt0) FL_TRY(B.upload(&tt0, a.tt0, (size_t)h * es));
+            FL_TRY(B.upload(&ids, a.ids, (size_t)T * 4));
+        }
+        if (form == 1 || form == 3) FL_TRY(B.upload(&x0, a.x, n * 4));
+        if (form == 1 || form == 2) {
+            FL_TRY(B.upload(&slabs, a.slabs, (size_t)a.n_slab * n * 4));
+            if (a.bias) FL_TRY(B.upload(&bias, a.bias, (size_t)h * 4));
+        }
+        if (form <= 1) {
+            FL_TRY(B.upload(&lnw, a.ln_w, (size_t)h * 4)); FL_TRY(B.upload(&lnb, a.ln_b, (size_t)h * 4));
+            FL_TRY(B.alloc(&xr, xbytes));
+        }
+        FL_TRY(B.alloc(&od, obytes));
+        std::vector<unsigned char> first, again;
+        for (int rep = 0; rep < a.repeat; rep++) {
+            // NaN pattern: an element no launch writes shows up.  Form 1 updates the residual stream in place: from the caller's rows each time.
+            if (form == 0) FL_HIP(hipMemsetAsync(xr, 0xff, xbytes, B.s));
+            if (form == 1) FL_HIP(hipMemcpyAsync(xr, x0, xbytes, hipMemcpyDeviceToDevice, B.s));
+            FL_HIP(hipMemsetAsync(od, 0xff, obytes, B.s));
+            if (form == 0) FL_TRY(launch_encoder_embed_ln(B.L, dtype, word, pos, tt0, ids, row_seq, offd, lnw, lnb, a.eps, xr, od, T, h));
+            else if (form == 1) FL_TRY(launch_encoder_add_ln(B.L, dtype, xr, slabs, a.n_slab, (int64_t)n, bias, lnw, lnb, a.eps, od, T, h));
+            else if (form == 2) FL_TRY(launch_encoder_bias_act(B.L, dtype, slabs, a.n_slab, (int64_t)n, bias, a.act, od, T, h));
+            else FL_TRY(launch_encoder_pool_l2(B.L, x0, offd, (int64_t)a.n_seq, h, (float *)od));
+            FL_HIP(hipStreamSynchronize(B.s));
+            std::vector<unsigned char> &o = rep ? again : first;
+            o.resize(xbytes + obytes);
+            if (xbytes) FL_HIP(hipMemcpy(o.data(), xr, xbytes, hipMemcpyDeviceToHost));
+            FL_HIP(hipMemcpy(o.data() + xbytes, od, obytes, hipMemcpyDeviceToHost));
+            if (rep && first != again) FL_FAIL(FL_ERR_HIP, "fl_op_encoder_rows: launch %d gave other bytes than the first", rep);
+        }
+        if (xbytes) memcpy(a.x_res_out, first.data(), xbytes);
+        memcpy(a.out, first.data() + xbytes, obytes);
+        return FL_OK;
     });
 }
 

@@ -806,6 +806,37 @@ int  fl_encoder_embed(fl_encoder *e, const uint32_t *ids, const size_t *offsets 
 int  fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq,
                              int64_t H, int64_t d, int32_t dtype, float *out);
 
+/* The encoder's four row kernels alone on host buffers (unit tests).  fp32 matrices are row-major; `dtype` (FL_DTYPE_BF16 bits or
+ * FL_DTYPE_F32) is the type of the tables of form 0 and of `out` in forms 0 to 2.
+ *   form 0  launch_encoder_embed_ln: word [vocab][h], pos [P][h] and tt0 [h] (or NULL) in `dtype`, ids [T], offsets [n_seq + 1] with
+ *           T = offsets[n_seq], ln_w / ln_b [h], eps; the row -> sequence table is built as the encoder's forward builds it
+ *   form 1  launch_encoder_add_ln: x [T][h] (the residual stream), slabs [n_slab][T][h] (a projection's split-K slabs), bias [h] (or
+ *           NULL), ln_w / ln_b [h], eps
+ *   form 2  launch_encoder_bias_act: slabs [n_slab][T][h] (h: the row width N), bias [h] (or NULL), act (-1 none, or an fl_activation)
+ *   form 3  launch_encoder_pool_l2: x [T][h], offsets [n_seq + 1] with T = offsets[n_seq]
+ * x_res_out [T][h] fp32: the residual stream after forms 0 and 1.  out: forms 0 and 1 the normalised rows [T][h] and form 2 the
+ * activation [T][h], as stored (`dtype`); form 3 the pooled rows [n_seq][h] fp32.  Every output is filled with the 0xff byte pattern
+ * (NaN) before each launch -- but form 1's residual stream, which the kernel updates in place and which starts as x --; the `repeat`
+ * launches (1..8) start from the same inputs: FL_ERR_HIP if one gives other bytes.
+ * Decided before the device is probed, writing nothing: FL_ERR_BAD_ARGUMENT (null pointers, struct_size, form, dtype, act, repeat,
+ * n_slab outside 1..8, sizes that are not positive, h not a multiple of 8 in forms 0 to 2, offsets that do not start at 0, decrease
+ * or hold an empty sequence, an id >= vocab) and FL_ERR_SEQ_OVERFLOW (form 0: a sequence longer than P). */
+typedef struct fl_encoder_rows_args {
+    size_t struct_size;             /* sizeof(fl_encoder_rows_args) */
+    int32_t form, dtype, n_slab, repeat;
+    int32_t act, reserved;
+    int64_t T, h, vocab, P;         /* T: forms 1 and 2 (forms 0 and 3 take it from offsets) */
+    size_t n_seq;
+    const void *word, *pos, *tt0;
+    const uint32_t *ids;
+    const size_t *offsets;
+    const float *x, *slabs, *bias, *ln_w, *ln_b;
+    float eps, reserved2;
+    float *x_res_out;
+    void *out;
+} fl_encoder_rows_args;
+int  fl_op_encoder_rows(const fl_encoder_rows_args *args);
+
 /* Which slice of a full HF tensor does tp_rank own?  Pure host function (no GPU):
  * out = {row_begin, row_end, col_begin, col_end}.  Column-parallel q/k/v/gate/up/lm_head
  * (rows of the [out,in] matrix), row-parallel o_proj/down_proj (columns), everything else whole. */

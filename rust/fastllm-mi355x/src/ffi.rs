@@ -421,6 +421,39 @@ pub struct fl_qkv_rope_args {
     pub kernels_out: *mut i32,
 }
 
+/// `fl_encoder_rows_args`: the encoder's LayerNorm, bias + GELU and pooling kernels alone on host buffers (fl_op_encoder_rows, unit
+/// tests); `struct_size` is `size_of::<fl_encoder_rows_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_encoder_rows_args {
+    pub struct_size: usize,
+    pub form: i32,
+    pub dtype: i32,
+    pub n_slab: i32,
+    pub repeat: i32,
+    pub act: i32,
+    pub reserved: i32,
+    pub t: i64,
+    pub h: i64,
+    pub vocab: i64,
+    pub p: i64,
+    pub n_seq: usize,
+    pub word: *const c_void,
+    pub pos: *const c_void,
+    pub tt0: *const c_void,
+    pub ids: *const u32,
+    pub offsets: *const usize,
+    pub x: *const f32,
+    pub slabs: *const f32,
+    pub bias: *const f32,
+    pub ln_w: *const f32,
+    pub ln_b: *const f32,
+    pub eps: f32,
+    pub reserved2: f32,
+    pub x_res_out: *mut f32,
+    pub out: *mut c_void,
+}
+
 /// `fl_attn_oproj_rep_args`: decode attention replicated inside the o_proj launch on host buffers (fl_op_attn_oproj_rep, unit tests);
 /// `struct_size` is `size_of::<fl_attn_oproj_rep_args>()`.
 #[repr(C)]
@@ -1034,6 +1067,7 @@ extern "C" {
     pub fn fl_op_rope_kv(args: *const fl_rope_kv_args) -> c_int;
     pub fn fl_op_qkv_rope(args: *const fl_qkv_rope_args) -> c_int;
     pub fn fl_op_attn_oproj_rep(args: *const fl_attn_oproj_rep_args) -> c_int;
+    pub fn fl_op_encoder_rows(args: *const fl_encoder_rows_args) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;

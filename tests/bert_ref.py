@@ -25,6 +25,10 @@ CONFIGS = {
     # head_dim 64 (BERT-base's); I is not a multiple of 256 and h is not a power of two
     "bert_b": dict(hidden_size=192, num_attention_heads=3, intermediate_size=320, num_hidden_layers=2, vocab_size=300,
                    max_position_embeddings=160, layer_norm_eps=1e-5),
+    # above the widths at which the row kernels take a second trip: a LayerNorm lane owns a second chunk from h = 520 on, a pooling
+    # thread a second column from h = 257 on (all-MiniLM-L6 is 384 / 1536, BERT-base 768 / 3072).  head_dim 64, packed qkv rows of 1728.
+    "bert_c": dict(hidden_size=576, num_attention_heads=9, intermediate_size=1088, num_hidden_layers=1, vocab_size=160,
+                   max_position_embeddings=96, layer_norm_eps=1e-12),
 }
 
 # std of the intermediate.dense and token-type weights: large enough that the two GELU forms and the token-type option move the

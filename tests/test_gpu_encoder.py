@@ -13,8 +13,8 @@ import bert_ref as R
 pytestmark = pytest.mark.gpu
 
 RAGGED = [1, 17, 64, 3, 33, 16]
-LENGTHS = {"bert_a": [1, 2, 15, 16, 17, 33, 64], "bert_b": [1, 2, 15, 16, 17, 33, 64, 65, 160]}
-CASES = [(n, T) for n in ("bert_a", "bert_b") for T in LENGTHS[n]]
+LENGTHS = {"bert_a": [1, 2, 15, 16, 17, 33, 64], "bert_b": [1, 2, 15, 16, 17, 33, 64, 65, 160], "bert_c": [1, 17, 65]}
+CASES = [(n, T) for n in ("bert_a", "bert_b", "bert_c") for T in LENGTHS[n]]
 
 
 @pytest.fixture(scope="module")
@@ -103,7 +103,7 @@ def test_activation_and_token_type_options_bite(encoder):
 
 
 # ---- ragged batches ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["bert_a", "bert_b"])
+@pytest.mark.parametrize("name", ["bert_a", "bert_b", "bert_c"])
 def test_fp32_ragged_batch(encoder, name):
     seqs = ragged_ids(name)
     enc = encoder(name)
@@ -175,7 +175,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
-@pytest.mark.parametrize("name,T", [(n, T) for n in ("bert_a", "bert_b") for T in (1, 17, 64)])
+@pytest.mark.parametrize("name,T", [(n, T) for n in ("bert_a", "bert_b") for T in (1, 17, 64)] + [("bert_c", 17)])
 def test_bf16_against_an_independent_bf16_execution(encoder, name, T):
     ids = R.prompt_ids(R.CONFIGS[name], T)
     h64, ht = ref(name, ids), torch_bf16_hidden(name, ids)
