@@ -12,5 +12,6 @@ from .binding import (Batch, Cache, FastLLMError, Model, abi_version, comm_uniqu
                       op_rmsnorm_add, op_norm_linear, op_linear_resid, op_gemv_resid, FlNormLinearArgs, FlLinearResidArgs, FlGemvResidArgs, LK_NAMES,
                       op_rope_kv, op_qkv_rope, FlRopeSeqs, FlRopeKvArgs, FlQkvRopeArgs, ROPE_KV_NAMES,
                       op_attn_oproj_rep, op_attn_oproj_rep_info, FlAttnOprojRepArgs,
-                      op_encoder_embed_ln, op_encoder_add_ln, op_encoder_bias_act, op_encoder_pool_l2, FlEncoderRowsArgs, ENC_ACT)
+                      op_encoder_embed_ln, op_encoder_add_ln, op_encoder_bias_act, op_encoder_pool_l2, FlEncoderRowsArgs, ENC_ACT,
+                      op_convert_slice, FlConvertSliceArgs, MODEL_TENSORS, ELEM_E4M3)
 from .configs import MODEL_CONFIGS  # noqa: F401

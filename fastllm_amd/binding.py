@@ -215,6 +215,19 @@ class FlEncoderRowsArgs(C.Structure):
                 ("ln_b", C.c_void_p), ("eps", C.c_float), ("reserved2", C.c_float), ("x_res_out", C.c_void_p), ("out", C.c_void_p)]
 
 
+class FlConvertSliceArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32), ("row_mode", C.c_int32),
+                ("head_pad", C.c_int32), ("via_bf16", C.c_int32), ("reserved", C.c_int32), ("R", C.c_int64), ("C", C.c_int64),
+                ("r0", C.c_int64), ("c0", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("dst_rows", C.c_int64), ("dst_ld", C.c_int64), ("dst_row0", C.c_int64), ("dm", C.c_int64),
+                ("d", C.c_int64), ("src", C.c_void_p), ("dst", C.c_void_p)]
+
+
+# selectors of Model.tensor (FL_MT_* of the header); ELEM_E4M3: the element code of the *_q tensors
+MODEL_TENSORS = {"embed": 0, "norm": 1, "lm_head": 2, "cos_tab": 3, "sin_tab": 4, "wqkv": 5, "bqkv": 6, "wo": 7, "wgu": 8, "wd": 9, "ln1": 10,
+                 "ln2": 11, "wqkv_q": 12, "wqkv_s": 13, "wo_q": 14, "wo_s": 15, "wgu_q": 16, "wgu_s": 17, "wd_q": 18, "wd_s": 19,
+                 "lm_head_q": 20, "lm_head_s": 21}
+ELEM_E4M3 = 3
+
 # act of op_encoder_bias_act
 ENC_ACT = {None: -1, "none": -1, "gelu_tanh": 0, "gelu_erf": 1}
 
@@ -422,6 +435,8 @@ def lib():
         L.fl_encoder_embed.argtypes = [vp, vp, vp, sz, vp]
         L.fl_op_encoder_attention.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.c_int64, C.c_int32, vp]
         L.fl_op_encoder_rows.argtypes = [C.POINTER(FlEncoderRowsArgs)]
+        L.fl_op_convert_slice.argtypes = [C.POINTER(FlConvertSliceArgs)]
+        L.fl_op_model_tensor.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         _LIB = L
     return _LIB
 
@@ -846,6 +861,23 @@ def op_encoder_pool_l2(x, lengths, repeat=1):
     return _encoder_rows(3, "f32", T, h, len(lengths), (x, offs), repeat, x=x, offsets=offs, n_seq=len(lengths))[1]
 
 
+def op_convert_slice(src, r0, c0, rows, cols, dst_dtype, dst_rows, dst_ld, dst_row0=0, row_mode=0, head_pad=0, dm=0, d=0, via_bf16=False):
+    """launch_convert_slice alone (fl_op_convert_slice): src [R, C] float32 / float16 / uint16 bf16 bits; dst_dtype "bf16" or "f32"
+    (via_bf16: the fp32 of the value rounded to bf16).
+    Returns the whole destination [dst_rows, dst_ld] as bit patterns (uint16 / uint32); what the launch left alone is all ones."""
+    src = np.ascontiguousarray(src)
+    assert src.ndim == 2
+    out = np.zeros((max(int(dst_rows), 1), max(int(dst_ld), 1)), np.uint16 if dst_dtype == "bf16" else np.uint32)
+    a = FlConvertSliceArgs()
+    a.struct_size = C.sizeof(FlConvertSliceArgs)
+    a.src_dtype, a.dst_dtype, a.row_mode, a.head_pad = _np_dtype_code(src), BF16 if dst_dtype == "bf16" else F32, row_mode, head_pad
+    a.R, a.C, a.r0, a.c0, a.rows, a.cols = src.shape[0], src.shape[1], r0, c0, rows, cols
+    a.dst_rows, a.dst_ld, a.dst_row0, a.dm, a.d, a.via_bf16 = dst_rows, dst_ld, dst_row0, dm, d, int(via_bf16)
+    a.src, a.dst = src.ctypes.data, out.ctypes.data
+    _check(lib().fl_op_convert_slice(C.byref(a)))
+    return out
+
+
 class Model:
     """fl_model handle.  tensors: dict name -> numpy array (float32 / float16 / uint16 bf16 bits), or
     name -> (device_ptr, dtype_code, shape, device_ordinal) for tensors already in HBM.
@@ -900,6 +932,21 @@ class Model:
 
     def new_cache(self, max_seq):
         return Cache(self, max_seq)
+
+    def tensor(self, name, layer=0, shard=0, shape_only=False):
+        """fl_op_model_tensor: the device tensor `name` (MODEL_TENSORS) of a local shard as it lies in HBM -- bit patterns: uint16 for
+        bf16, uint32 for fp32 weights; float32 for norms, biases, scales and the RoPE tables; uint8 for e4m3 bytes.  shape_only: (rows,
+        cols, element code) without a copy."""
+        r, c, e = C.c_int64(0), C.c_int64(0), C.c_int32(-1)
+        sel = name if isinstance(name, int) else MODEL_TENSORS[name]
+        _check(lib().fl_op_model_tensor(self._h, shard, sel, layer, None, C.byref(r), C.byref(c), C.byref(e)))
+        if shape_only:
+            return r.value, c.value, e.value
+        plain_f32 = sel in (1, 3, 4, 6, 10, 11) or (sel >= 12 and sel % 2 == 1)
+        dt = np.uint8 if e.value == ELEM_E4M3 else np.uint16 if e.value == BF16 else np.float32 if plain_f32 else np.uint32
+        out = np.empty((r.value, c.value), dt)
+        _check(lib().fl_op_model_tensor(self._h, shard, sel, layer, out.ctypes.data, C.byref(r), C.byref(c), C.byref(e)))
+        return out
 
     def forward(self, cache, ids, pos):
         ids = np.ascontiguousarray(ids, dtype=np.uint32)

@@ -374,6 +374,39 @@ int encoder_rows_check(const fl_encoder_rows_args *a, int64_t *T_out) {
     return FL_OK;
 }
 
+// the fl_op_convert_slice checks, none of which needs a device: the slice inside the source, and every element's destination --
+// found by walking the rows' and the columns' maps as convert_slice_kernel applies them -- inside dst
+int convert_slice_check(const fl_convert_slice_args *a) {
+    const int64_t kMax = (int64_t)1 << 26;
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: null args");
+    if (a->struct_size != sizeof(fl_convert_slice_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_convert_slice_args));
+    if (!a->src || !a->dst) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: null argument (src, dst)");
+    if (a->src_dtype < FL_DTYPE_F32 || a->src_dtype > FL_DTYPE_F16) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: src_dtype %d (f32, bf16 or f16)", a->src_dtype);
+    if (a->dst_dtype != FL_DTYPE_F32 && a->dst_dtype != FL_DTYPE_BF16) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: dst_dtype %d (f32 or bf16)", a->dst_dtype);
+    if (a->row_mode < 0 || a->row_mode > 2 || a->head_pad < 0 || a->head_pad > 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: row_mode and head_pad are 0, 1 or 2");
+    if ((a->via_bf16 != 0 && a->via_bf16 != 1) || (a->via_bf16 && a->dst_dtype != FL_DTYPE_F32)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: via_bf16 is 0 or 1, and 1 only with an fp32 destination");
+    if (a->R < 1 || a->C < 1 || a->R > kMax || a->C > kMax || a->R * a->C > kMax) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: source shape (1 .. 2^26 elements)");
+    if (a->dst_rows < 1 || a->dst_ld < 1 || a->dst_rows > kMax || a->dst_ld > kMax || a->dst_rows * a->dst_ld > kMax)
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: destination shape (1 .. 2^26 elements)");
+    if (a->r0 < 0 || a->c0 < 0 || a->rows < 1 || a->cols < 1 || a->rows > a->R - a->r0 || a->cols > a->C - a->c0)
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: the slice [%lld + %lld) x [%lld + %lld) leaves the source %lld x %lld", (long long)a->r0, (long long)a->rows,
+                (long long)a->c0, (long long)a->cols, (long long)a->R, (long long)a->C);
+    if (a->dst_row0 < 0 || a->dst_row0 >= a->dst_rows) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: dst_row0 %lld not in the destination's %lld rows", (long long)a->dst_row0, (long long)a->dst_rows);
+    if (a->row_mode != 0 && (a->dst_row0 != 0 || a->head_pad == 1)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: the gate/up interleave takes neither a row offset nor padded head rows");
+    if (a->head_pad != 0 && (a->dm < 2 || a->d < a->dm || a->dm % 2 || a->d % 2 || a->d > (1 << 20)))
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: head_pad needs 2 <= dm <= d <= 2^20, both even (dm %lld, d %lld)", (long long)a->dm, (long long)a->d);
+    auto padded = [&](int64_t x) { const int64_t hd = x / a->dm, j = x % a->dm; return hd * a->d + (j < a->dm / 2 ? j : a->d / 2 + j - a->dm / 2); };
+    for (int64_t r = 0; r < a->rows; r++) {
+        const int64_t dr = a->head_pad == 1 ? a->dst_row0 + padded(r) : (a->row_mode == 0 ? a->dst_row0 + r : gateup_row(r, a->row_mode == 2));
+        if (dr < 0 || dr >= a->dst_rows) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: source row %lld would land in row %lld of %lld", (long long)r, (long long)dr, (long long)a->dst_rows);
+    }
+    for (int64_t c = 0; c < a->cols; c++) {
+        const int64_t dc = a->head_pad == 2 ? padded(c) : c;
+        if (dc < 0 || dc >= a->dst_ld) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_convert_slice: source column %lld would land in column %lld of %lld", (long long)c, (long long)dc, (long long)a->dst_ld);
+    }
+    return FL_OK;
+}
+
 int attn_op_check_heads(int32_t dtype, int32_t layout, int64_t H, int64_t Hkv, int64_t d) {
     if ((dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) || layout < 0 || layout > 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "dtype: bf16 or f32; layout: 0 plain, 1 MFMA");
     if (H < 1 || Hkv < 1 || H % Hkv != 0) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad head counts (H a multiple of Hkv)");
@@ -2067,6 +2100,78 @@ int fl_op_gemv_resid(const fl_gemv_resid_args *args) {
             c += abytes;
             if (f) memcpy(a.h_ref, c, (size_t)N * 4);
         }
+        return FL_OK;
+    });
+}
+
+int fl_op_convert_slice(const fl_convert_slice_args *args) {
+    return guarded([&]() -> int {
+        FL_TRY(convert_slice_check(args));
+        const fl_convert_slice_args &a = *args;
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t ses = a.src_dtype == FL_DTYPE_F32 ? 4 : 2, des = a.dst_dtype == FL_DTYPE_F32 ? 4 : 2;
+        const size_t dbytes = (size_t)a.dst_rows * a.dst_ld * des;
+        void *sd, *dd;
+        FL_TRY(B.upload(&sd, a.src, (size_t)a.R * a.C * ses));
+        FL_TRY(B.alloc(&dd, dbytes));
+        FL_HIP(hipMemsetAsync(dd, 0xff, dbytes, B.s));             // NaN pattern: an element the launch leaves alone shows up
+        FL_TRY(launch_convert_slice(B.L, a.src_dtype, sd, a.C, a.r0, a.c0, a.rows, a.cols, a.dst_dtype, dd, a.dst_ld, a.dst_row0, a.row_mode,
+                                    a.head_pad, a.head_pad ? a.dm : 0, a.head_pad ? a.d : 0, a.via_bf16));
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(a.dst, dd, dbytes, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_model_tensor(fl_model *m, int32_t shard, int32_t selector, int64_t layer, void *out, int64_t *rows_out, int64_t *cols_out,
+                       int32_t *elem_out) {
+    return guarded([&]() -> int {
+        if (!m || !rows_out || !cols_out || !elem_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: null argument (model, rows_out, cols_out, elem_out)");
+        Model *mm = M(m);
+        std::lock_guard<std::mutex> lock(mm->mu);
+        if (shard < 0 || (size_t)shard >= mm->shards.size()) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: shard %d not below %zu local shards", shard, mm->shards.size());
+        if (selector < FL_MT_EMBED || selector > FL_MT_LM_HEAD_S) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: unknown selector %d", selector);
+        const bool per_layer = (selector >= FL_MT_WQKV && selector <= FL_MT_LN2) || (selector >= FL_MT_WQKV_Q && selector <= FL_MT_WD_S);
+        if (per_layer && (layer < 0 || layer >= mm->D.L)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: layer %lld not below %lld", (long long)layer, (long long)mm->D.L);
+        const Dims &D = mm->D;
+        Shard &sh = mm->shards[(size_t)shard];
+        const LayerW none, &ly = per_layer ? sh.layers[(size_t)layer] : none;
+        const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d, half = D.d / 2;
+        const int wdt = mm->dtype;
+        const void *p = nullptr; int64_t R = 0, C = 0; int elem = FL_DTYPE_F32;
+        auto is = [&](const void *ptr, int64_t r, int64_t c, int e) { p = ptr; R = r; C = c; elem = e; };
+        switch (selector) {
+            case FL_MT_EMBED:     is(sh.embed, D.V, D.h, wdt); break;
+            case FL_MT_NORM:      is(sh.norm, D.h, 1, FL_DTYPE_F32); break;
+            case FL_MT_LM_HEAD:   is(sh.lm_head, sh.Vs, D.h, wdt); break;
+            case FL_MT_COS_TAB:   is(sh.cos_tab, D.max_pos, half, FL_DTYPE_F32); break;
+            case FL_MT_SIN_TAB:   is(sh.sin_tab, D.max_pos, half, FL_DTYPE_F32); break;
+            case FL_MT_WQKV:      is(ly.wqkv, nq, D.h, wdt); break;
+            case FL_MT_BQKV:      is(ly.bqkv, nq, 1, FL_DTYPE_F32); break;
+            case FL_MT_WO:        is(ly.wo, D.h, sh.Hs * D.d, wdt); break;
+            case FL_MT_WGU:       is(ly.wgu, 2 * sh.Ip, D.h, wdt); break;
+            case FL_MT_WD:        is(ly.wd, D.h, sh.Ip, wdt); break;
+            case FL_MT_LN1:       is(ly.ln1, D.h, 1, FL_DTYPE_F32); break;
+            case FL_MT_LN2:       is(ly.ln2, D.h, 1, FL_DTYPE_F32); break;
+            case FL_MT_WQKV_Q:    is(ly.wqkv8, nq, D.h, FL_ELEM_E4M3); break;
+            case FL_MT_WQKV_S:    is(ly.sqkv, nq, 1, FL_DTYPE_F32); break;
+            case FL_MT_WO_Q:      is(ly.wo8, D.h, sh.Hs * D.d, FL_ELEM_E4M3); break;
+            case FL_MT_WO_S:      is(ly.so, D.h, 1, FL_DTYPE_F32); break;
+            case FL_MT_WGU_Q:     is(ly.wgu8, 2 * sh.Ip, D.h, FL_ELEM_E4M3); break;
+            case FL_MT_WGU_S:     is(ly.sgu, 2 * sh.Ip, 1, FL_DTYPE_F32); break;
+            case FL_MT_WD_Q:      is(ly.wd8, D.h, sh.Ip, FL_ELEM_E4M3); break;
+            case FL_MT_WD_S:      is(ly.sd, D.h, 1, FL_DTYPE_F32); break;
+            case FL_MT_LM_HEAD_Q: is(sh.lm_head8, sh.Vs, D.h, FL_ELEM_E4M3); break;
+            default:              is(sh.lm_head_s, sh.Vs, 1, FL_DTYPE_F32); break;      // FL_MT_LM_HEAD_S
+        }
+        if (!p) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: this model has no tensor for selector %d (q/k/v bias, FL_WEIGHTS_E4M3_ROW)", selector);
+        *rows_out = R; *cols_out = C; *elem_out = elem;
+        if (!out) return FL_OK;
+        const size_t es = elem == FL_DTYPE_F32 ? 4 : (elem == FL_ELEM_E4M3 ? 1 : 2);
+        FL_HIP(hipSetDevice(sh.device));
+        FL_HIP(hipStreamSynchronize(sh.stream));
+        FL_HIP(hipMemcpy(out, p, (size_t)R * C * es, hipMemcpyDeviceToHost));
         return FL_OK;
     });
 }

@@ -477,11 +477,12 @@ template <typename DT>
 __global__ __launch_bounds__(256) void convert_slice_kernel(const void *__restrict__ src, int src_dt, long long src_ld,
                                                             long long r0, long long c0, long long rows, long long cols,
                                                             DT *__restrict__ dst, long long dst_ld, long long dst_row0,
-                                                            int row_mode, int head_pad, int dm, int d) {
+                                                            int row_mode, int head_pad, int dm, int d, int via_bf16) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= rows * cols) return;
     const long long r = i / cols, c = i % cols;
-    const float v = load_as_f32(src, (size_t)((r0 + r) * src_ld + c0 + c), src_dt);
+    float v = load_as_f32(src, (size_t)((r0 + r) * src_ld + c0 + c), src_dt);
+    if (via_bf16) v = bf16_bits_to_float(float_to_bf16_bits(v));
     long long dr = row_mode == 0 ? dst_row0 + r : gateup_row(r, row_mode == 2), dc = c;
     // head_pad: element j of a head of the model's head_dim dm goes to j (first half) or d/2 + j - dm/2 (second half) of a padded
     // head of d: rotate-half partners stay d/2 apart; 1 = the slice's rows are heads, 2 = its columns are
@@ -493,16 +494,16 @@ __global__ __launch_bounds__(256) void convert_slice_kernel(const void *__restri
 
 int launch_convert_slice(Launcher &L, int src_dtype, const void *src, int64_t src_ld, int64_t r0, int64_t c0,
                          int64_t rows, int64_t cols, int dst_dtype, void *dst, int64_t dst_ld, int64_t dst_row0,
-                         int row_mode, int head_pad, int64_t dm, int64_t d) {
+                         int row_mode, int head_pad, int64_t dm, int64_t d, int via_bf16) {
     const int64_t total = rows * cols;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     if (dst_dtype == FL_DTYPE_BF16)
         return L.launch(KC_CONVERT, 0, 0, convert_slice_kernel<bf16_t>, dim3(blocks), dim3(256), 0, src, src_dtype,
                         (long long)src_ld, (long long)r0, (long long)c0, (long long)rows, (long long)cols,
-                        (bf16_t *)dst, (long long)dst_ld, (long long)dst_row0, row_mode, head_pad, (int)dm, (int)d);
+                        (bf16_t *)dst, (long long)dst_ld, (long long)dst_row0, row_mode, head_pad, (int)dm, (int)d, 0);
     return L.launch(KC_CONVERT, 0, 0, convert_slice_kernel<float>, dim3(blocks), dim3(256), 0, src, src_dtype,
                     (long long)src_ld, (long long)r0, (long long)c0, (long long)rows, (long long)cols, (float *)dst,
-                    (long long)dst_ld, (long long)dst_row0, row_mode, head_pad, (int)dm, (int)d);
+                    (long long)dst_ld, (long long)dst_row0, row_mode, head_pad, (int)dm, (int)d, via_bf16);
 }
 
 int launch_convert_vec_f32(Launcher &L, int src_dtype, const void *src, int64_t off, int64_t n, float *dst) {

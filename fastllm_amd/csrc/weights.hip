@@ -184,6 +184,9 @@ struct Builder {
 // Copy slice [r0,r1) x [c0,c1) of tensor `name` (full shape R x C) into dst (ld = dst_ld) on every
 // shard that lives on st.device; dst_of(shard) gives the destination base, row_mode the row map.
 // head_pad: 0 none; 1 the ROWS are heads of the model's head_dim dm, placed as padded heads of d rows; 2 the COLUMNS are
+// An fp32 destination of a bf16 model (norm weights, q/k/v biases) takes the value ROUNDED TO BF16: the reference casts every tensor
+// of the checkpoint to the model's dtype (VarBuilder::from_tensors(tensors, dtype, device), llama.rs:112, mistral.rs:190, qwen.rs:108),
+// so an f32 or f16 checkpoint served in bf16 has bf16 norm weights and biases; the fp32 copy only spares the kernels a conversion.
 template <typename DstFn>
 static int put_matrix(Builder &B, Stager &st, const std::string &name, int64_t R, int64_t C, int dst_dtype,
                       int64_t dst_ld, int64_t dst_row0, int row_mode, DstFn dst_of, int head_pad = 0) {
@@ -198,7 +201,8 @@ static int put_matrix(Builder &B, Stager &st, const std::string &name, int64_t R
         FL_TRY(tp_slice(m->D, name.c_str(), sh.rank, m->tp, sl));
         Launcher L; L.stream = sh.stream;
         FL_TRY(launch_convert_slice(L, t->dtype, src, C, sl[0], sl[2], sl[1] - sl[0], sl[3] - sl[2], dst_dtype,
-                                    dst_of(sh), dst_ld, dst_row0, row_mode, m->D.dm != m->D.d ? head_pad : 0, m->D.dm, m->D.d));
+                                    dst_of(sh), dst_ld, dst_row0, row_mode, m->D.dm != m->D.d ? head_pad : 0, m->D.dm, m->D.d,
+                                    dst_dtype == FL_DTYPE_F32 && m->dtype == FL_DTYPE_BF16));
     }
     FL_HIP(hipDeviceSynchronize());       // the staging buffer is reused by the next tensor
     return FL_OK;

@@ -1259,6 +1259,46 @@ int fl_op_pool_rows(const float *x, const float *inv_rms, const float *w, const 
 int fl_op_pool_rows_time(const float *x, const float *inv_rms, const float *w, const size_t *offsets, size_t n_seq, int64_t h,
                          const fl_embed *opts, int32_t iters, double *ms_out);
 
+/* The weight conversion launch of the model build alone, on host buffers (unit tests): the slice [r0, r0 + rows) x [c0, c0 + cols) of
+ * src [R][C] (src_dtype: f32 / bf16 / f16) goes, converted to dst_dtype (bf16 / f32), into dst [dst_rows][dst_ld].
+ *   row_mode 0  source row r lands in row dst_row0 + r
+ *            1  ... in the gate row of the 16 x 16 gate/up interleave, (r / 16) * 32 + r % 16;  2: in the up row, 16 further
+ *               (dst_row0 must be 0: the interleave has no offset)
+ *   head_pad 0  none;  1: the ROWS are heads of dm, laid out as heads of d: element j of a head goes to j (j < dm / 2) or to
+ *               d / 2 + j - dm / 2 (row_mode must be 0);  2: the COLUMNS are
+ *   via_bf16    fp32 destinations only: the value is rounded to bf16 first (how a bf16 model holds its norm weights and biases)
+ * dst is output only: the device buffer is filled with 0xff bytes before the launch and returned whole, so the elements the launch
+ * left alone show.  FL_ERR_BAD_ARGUMENT, before the device is touched, for a slice that leaves the source, for ANY element whose
+ * destination is outside dst, for head_pad without 2 <= dm <= d (both even), and for more than 2^26 elements on either side. */
+typedef struct fl_convert_slice_args {
+    size_t struct_size;          /* sizeof(fl_convert_slice_args) */
+    int32_t src_dtype, dst_dtype, row_mode, head_pad, via_bf16, reserved;
+    int64_t R, C;                /* the source matrix */
+    int64_t r0, c0, rows, cols;  /* the slice */
+    int64_t dst_rows, dst_ld, dst_row0;
+    int64_t dm, d;               /* head_pad 1 / 2 only */
+    const void *src;
+    void *dst;
+} fl_convert_slice_args;
+int fl_op_convert_slice(const fl_convert_slice_args *args);
+
+/* One device tensor of a built model, copied to the host as it lies in HBM (unit tests of the model build: weights.hip's layout).
+ * shard: index among the model's LOCAL shards (0 without tensor parallelism; the rank under FL_TP_SINGLE_PROCESS / FL_TP_EMULATED).
+ * layer is looked at for the per-layer selectors only.  *rows_out, *cols_out, *elem_out (an fl_dtype, or FL_ELEM_E4M3: one byte per
+ * element) are always written; out == NULL returns only those, otherwise out takes rows x cols elements.  The FL_MT_*_Q (e4m3 bytes)
+ * and FL_MT_*_S (fp32 row scales, [rows][1]) selectors exist for FL_WEIGHTS_E4M3_ROW models, FL_MT_BQKV for models with q/k/v bias;
+ * a selector the model does not have, a bad shard or a bad layer: FL_ERR_BAD_ARGUMENT.  The call takes the model's lock, waits for
+ * the shard's stream and copies; it launches nothing. */
+enum { FL_ELEM_E4M3 = 3 };
+typedef enum fl_model_tensor_sel {
+    FL_MT_EMBED = 0, FL_MT_NORM = 1, FL_MT_LM_HEAD = 2, FL_MT_COS_TAB = 3, FL_MT_SIN_TAB = 4,
+    FL_MT_WQKV = 5, FL_MT_BQKV = 6, FL_MT_WO = 7, FL_MT_WGU = 8, FL_MT_WD = 9, FL_MT_LN1 = 10, FL_MT_LN2 = 11,
+    FL_MT_WQKV_Q = 12, FL_MT_WQKV_S = 13, FL_MT_WO_Q = 14, FL_MT_WO_S = 15, FL_MT_WGU_Q = 16, FL_MT_WGU_S = 17,
+    FL_MT_WD_Q = 18, FL_MT_WD_S = 19, FL_MT_LM_HEAD_Q = 20, FL_MT_LM_HEAD_S = 21
+} fl_model_tensor_sel;
+int fl_op_model_tensor(fl_model *m, int32_t shard, int32_t selector, int64_t layer, void *out, int64_t *rows_out, int64_t *cols_out,
+                       int32_t *elem_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -454,6 +454,58 @@ pub struct fl_encoder_rows_args {
     pub out: *mut c_void,
 }
 
+/// `fl_convert_slice_args`: the weight conversion launch of the model build alone on host buffers (fl_op_convert_slice, unit tests);
+/// `struct_size` is `size_of::<fl_convert_slice_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_convert_slice_args {
+    pub struct_size: usize,
+    pub src_dtype: i32,
+    pub dst_dtype: i32,
+    pub row_mode: i32,
+    pub head_pad: i32,
+    pub via_bf16: i32,
+    pub reserved: i32,
+    pub r: i64,
+    pub c: i64,
+    pub r0: i64,
+    pub c0: i64,
+    pub rows: i64,
+    pub cols: i64,
+    pub dst_rows: i64,
+    pub dst_ld: i64,
+    pub dst_row0: i64,
+    pub dm: i64,
+    pub d: i64,
+    pub src: *const c_void,
+    pub dst: *mut c_void,
+}
+
+// fl_model_tensor_sel: the device tensors fl_op_model_tensor copies out; FL_ELEM_E4M3: the element code of the *_Q tensors
+pub const FL_ELEM_E4M3: i32 = 3;
+pub const FL_MT_EMBED: i32 = 0;
+pub const FL_MT_NORM: i32 = 1;
+pub const FL_MT_LM_HEAD: i32 = 2;
+pub const FL_MT_COS_TAB: i32 = 3;
+pub const FL_MT_SIN_TAB: i32 = 4;
+pub const FL_MT_WQKV: i32 = 5;
+pub const FL_MT_BQKV: i32 = 6;
+pub const FL_MT_WO: i32 = 7;
+pub const FL_MT_WGU: i32 = 8;
+pub const FL_MT_WD: i32 = 9;
+pub const FL_MT_LN1: i32 = 10;
+pub const FL_MT_LN2: i32 = 11;
+pub const FL_MT_WQKV_Q: i32 = 12;
+pub const FL_MT_WQKV_S: i32 = 13;
+pub const FL_MT_WO_Q: i32 = 14;
+pub const FL_MT_WO_S: i32 = 15;
+pub const FL_MT_WGU_Q: i32 = 16;
+pub const FL_MT_WGU_S: i32 = 17;
+pub const FL_MT_WD_Q: i32 = 18;
+pub const FL_MT_WD_S: i32 = 19;
+pub const FL_MT_LM_HEAD_Q: i32 = 20;
+pub const FL_MT_LM_HEAD_S: i32 = 21;
+
 /// `fl_attn_oproj_rep_args`: decode attention replicated inside the o_proj launch on host buffers (fl_op_attn_oproj_rep, unit tests);
 /// `struct_size` is `size_of::<fl_attn_oproj_rep_args>()`.
 #[repr(C)]
@@ -1068,6 +1120,17 @@ extern "C" {
     pub fn fl_op_qkv_rope(args: *const fl_qkv_rope_args) -> c_int;
     pub fn fl_op_attn_oproj_rep(args: *const fl_attn_oproj_rep_args) -> c_int;
     pub fn fl_op_encoder_rows(args: *const fl_encoder_rows_args) -> c_int;
+    pub fn fl_op_convert_slice(args: *const fl_convert_slice_args) -> c_int;
+    pub fn fl_op_model_tensor(
+        m: *mut fl_model,
+        shard: i32,
+        selector: i32,
+        layer: i64,
+        out: *mut c_void,
+        rows_out: *mut i64,
+        cols_out: *mut i64,
+        elem_out: *mut i32,
+    ) -> c_int;
     pub fn fl_op_sample(logits: *const f32, v: i64, sampling: *const fl_sampling, n_draws: i64, tokens_out: *mut u32) -> c_int;
     pub fn fl_op_sample_ex(logits: *const f32, v: i64, sampler: *const fl_sampler, n_draws: i64, tokens_out: *mut u32, kept_out: *mut i64) -> c_int;
     pub fn fl_op_verify_select(logits: *const f32, t: i64, v: i64, draft: *const u32, argmax_out: *mut u32, n_accepted_out: *mut i64) -> c_int;

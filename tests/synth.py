@@ -17,7 +17,8 @@ def f32_to_bf16_bits(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     u = a.view(np.uint32)
     r = ((u >> 16) & 1) + 0x7FFF
-    return ((u + r) >> 16).astype(np.uint16)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000               # a NaN stays a NaN (the increment would carry some into +-0 or inf)
+    return np.where(nan, (u >> 16) | 0x40, (u + r) >> 16).astype(np.uint16)
 
 
 def bf16_bits_to_f32(b):

@@ -371,6 +371,20 @@ def test_f16_and_f32_source_tensors(fa):
     d = fa.Model(cfg, wf, dtype="f32")
     cc, cd = c.new_cache(16), d.new_cache(16)
     np.testing.assert_array_equal(c.forward(cc, ids, 0), d.forward(cd, ids, 0))
+    # ... and sources the bf16 build has to ROUND (fp32 values that are no bf16 values; f16 values with more significand bits than
+    # bf16 keeps) give the model of the rounded values handed in as bf16: the build's conversion is model_image_ref.convert
+    import model_image_ref as ref
+    for src_dtype in ("f32", "f16"):
+        src = ref.rounding_sources(wb, src_dtype, "model.layers.0.self_attn.q_proj.weight", special_row=False)
+        rounded = {k: ref.convert(v, src_dtype, "bf16") for k, v in src.items()}
+        assert any(not np.array_equal(rounded[k], wb[k]) for k in wb)
+        e, f = fa.Model(cfg, src, dtype="bf16"), fa.Model(cfg, rounded, dtype="bf16")
+        ce, cf = e.new_cache(16), f.new_cache(16)
+        le, lf = e.forward(ce, ids, 0), f.forward(cf, ids, 0)
+        assert np.isfinite(le).all()
+        np.testing.assert_array_equal(le, lf)                                     # prefill
+        tok = int(np.argmax(le))
+        np.testing.assert_array_equal(e.forward(ce, [tok], len(ids)), f.forward(cf, [tok], len(ids)))       # a decode step
 
 
 def test_concurrent_streams_on_one_model(fa):
