@@ -421,9 +421,13 @@ def lib():
         L.fl_op_verify_adjust.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(FlGuideDesc), vp, vp]
         L.fl_op_verify_adjust_time.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.POINTER(FlGuideDesc), vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_op_rules_count.argtypes = [vp, C.c_int64, vp, C.c_int64]
+        L.fl_op_verify_adjust_packed.argtypes = [vp, C.c_int64, C.c_int64, sz, vp, vp, vp, vp, vp, vp, C.POINTER(FlGuideDesc), vp, vp, C.c_int64, vp, vp, vp,
+                                                 vp, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_op_verify_sample.argtypes = [vp, C.c_int64, C.c_int64, vp, C.POINTER(FlSampler), vp, C.POINTER(C.c_int64), vp]
         L.fl_op_verify_sample_time.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(FlSampler), vp, vp]
         L.fl_batch_verify.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.fl_batch_verify_lp.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.fl_batch_decode_lookup_lp.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(FlLookup), vp, vp, vp, vp, vp]
         L.fl_batch_decode_lookup.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(FlLookup), vp, vp, vp, vp]
         L.fl_op_verify_packed.argtypes = [vp, C.c_int64, C.c_int64, sz, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_cache_copy_prefix.argtypes = [vp, vp, sz]
@@ -664,6 +668,40 @@ def op_rules_count(words, ids):
     tk = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
     _check(lib().fl_op_rules_count(w.ctypes.data, w.size, tk.ctypes.data if tk.size else None, tk.size))
     return w
+
+
+def op_verify_adjust_packed(logits, offsets, ids, words=None, biases=None, scalars=None, has_rules=None, guide=None, states=None, has_guide=None,
+                            block_rows=0, n_acc=None, returned=None, eos=None, iters=0):
+    """verify_adjust_packed_kernel and rules_count_packed_kernel alone: logits float32 [T, V], the rows of a pack whose member s is rows
+    offsets[s] .. offsets[s + 1]; ids [T].  Rules: words uint32 [n, V], biases float32 [n, V], scalars [n, 3], has_rules [n] (None: all);
+    guide: one (row_ptr, tokens, next) with states [T] and has_guide [n] (None: all).  block_rows: rows per adjust launch (0: all).
+    n_acc [n] (with returned [T] and eos [n], both optional): the count launch runs too.  Returns (adjusted rows [T, V], the tables
+    after the adjust launches, the tables after the count launch) -- the last two None without rules / without n_acc.  iters > 0:
+    returns ms per adjust pass instead."""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    T, V = a.shape
+    of = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = of.size - 1
+    tk = np.ascontiguousarray(ids, dtype=np.uint32).reshape(T)
+    arr = lambda x, dt, shape: None if x is None else np.ascontiguousarray(x, dtype=dt).reshape(shape)
+    w = None if words is None else np.array(words, dtype=np.uint32, order="C").reshape(n, V)
+    bs, sc, hr = arr(biases, np.float32, (n, V)), arr(scalars, np.float32, (n, 3)), arr(has_rules, np.uint8, n)
+    st = keep = None
+    if guide is not None:
+        st, keep = make_guide_desc(*guide)
+    ss, hg = arr(states, np.uint32, T), arr(has_guide, np.uint8, n)
+    na, rt, es = arr(n_acc, np.int64, n), arr(returned, np.uint32, T), arr(eos, np.int64, n)
+    out = np.empty((T, V), dtype=np.float32) if iters == 0 else None
+    mid = np.zeros_like(w) if w is not None and iters == 0 else None
+    ms = C.c_double(0.0)
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    _check(lib().fl_op_verify_adjust_packed(a.ctypes.data, T, V, n, of.ctypes.data, tk.ctypes.data, ptr(w), ptr(bs), ptr(sc), ptr(hr),
+                                            C.byref(st) if st is not None else None, ptr(ss), ptr(hg), int(block_rows), ptr(na), ptr(rt), ptr(es),
+                                            ptr(out), ptr(mid), int(iters), C.byref(ms)))
+    del keep
+    if iters:
+        return ms.value
+    return out, mid, (w if na is not None else None)
 
 
 def abi_version():
@@ -1098,6 +1136,75 @@ class Model:
         if return_stats:
             return got, [dict(steps=st[i].steps, drafted=st[i].drafted, accepted=st[i].accepted) for i in range(n)]
         return got
+
+    @staticmethod
+    def _member_logprobs(n, sizes, logprobs):
+        """logprobs: None, or a list with one top_n (None: no log-probs for that member) per member -> (struct array or None, the arrays)."""
+        if logprobs is None:
+            return None, [None] * n
+        assert len(logprobs) == n
+        arrs = [_LogprobArrays(sizes[i], logprobs[i]) if logprobs[i] is not None else None for i in range(n)]
+        st = (FlLogprobs * max(n, 1))()
+        for i in range(n):
+            if arrs[i] is not None:
+                st[i] = arrs[i].struct()
+            else:
+                st[i].top_n = -1
+        return st, arrs
+
+    def verify_packed_lp(self, caches, tokens, drafts, pos, logprobs=None, temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None,
+                         want_logits=False):
+        """fl_batch_verify_lp: verify_packed for members whose caches may have logit rules and / or a guide.  logprobs: None, or a list
+        with one top_n per member (None: none for that member).  Returns (list of per-member id arrays, logits [total rows, V] at the
+        caller's offsets or None, list of per-member (token_logprob, top_ids, top_logprobs) or None)."""
+        n = len(caches)
+        assert len(tokens) == n and len(drafts) == n
+        ms = [np.concatenate([[int(tokens[i])], np.asarray(drafts[i], dtype=np.uint32).reshape(-1)]).astype(np.uint32) for i in range(n)]
+        ids = np.ascontiguousarray(np.concatenate(ms) if ms else np.zeros(0, np.uint32), dtype=np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.size for x in ms])]), dtype=np.uint64)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        assert pos.shape == (n,)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        spx = _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done)
+        lst, lar = self._member_logprobs(n, [x.size for x in ms], logprobs)
+        toks = np.zeros(max(ids.size, 1), dtype=np.uint32)
+        cnt = np.zeros(max(n, 1), dtype=np.uint64)
+        lg = np.full((ids.size, self.V), np.nan, dtype=np.float32) if want_logits else None
+        _check(lib().fl_batch_verify_lp(self._h, C.cast(arr, C.c_void_p), n, ids.ctypes.data, offsets.ctypes.data, pos.ctypes.data,
+                                        C.cast(spx, C.c_void_p) if spx is not None else None, C.cast(lst, C.c_void_p) if lst is not None else None,
+                                        toks.ctypes.data, cnt.ctypes.data, lg.ctypes.data if want_logits else None))
+        got = [toks[int(offsets[i]): int(offsets[i]) + int(cnt[i])].copy() for i in range(n)]
+        return got, lg, [a.cut(int(cnt[i])) if a is not None else None for i, a in enumerate(lar)]
+
+    def decode_lookup_packed_lp(self, caches, corpora, first_tokens, pos, n_steps, eos=None, max_draft=7, ngram_max=3, ngram_min=1, logprobs=None,
+                                temperatures=None, seeds=None, top_p=None, top_k=None, draws_done=None):
+        """fl_batch_decode_lookup_lp: decode_lookup_packed for members whose caches may have logit rules and / or a guide.  Returns (list
+        of per-member id arrays, list of per-member (token_logprob, top_ids, top_logprobs) or None, [dict(steps, drafted, accepted)])."""
+        n = len(caches)
+        cps = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in corpora]
+        assert len(cps) == n and len(first_tokens) == n and len(pos) == n and len(n_steps) == n
+        corpus = np.ascontiguousarray(np.concatenate(cps) if cps else np.zeros(0, np.uint32), dtype=np.uint32)
+        coff = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.size for x in cps])]), dtype=np.uint64)
+        first = np.ascontiguousarray(first_tokens, dtype=np.uint32)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        steps = np.ascontiguousarray(n_steps, dtype=np.uint64)
+        eos_a = None if eos is None else np.ascontiguousarray([-1 if e is None else e for e in eos], dtype=np.int64)
+        stride = int(steps.max()) if n else 0
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in caches])
+        spx = _member_samplers(n, temperatures, seeds, top_p, top_k, draws_done)
+        lst, lar = self._member_logprobs(n, [int(x) for x in steps], logprobs)
+        o = make_lookup(max_draft, ngram_max, ngram_min)
+        toks = np.zeros((max(n, 1), max(stride, 1)), dtype=np.uint32)
+        cnt = np.zeros(max(n, 1), dtype=np.uint64)
+        st = (FlSpecStats * max(n, 1))()
+        _check(lib().fl_batch_decode_lookup_lp(self._h, C.cast(arr, C.c_void_p), n, corpus.ctypes.data if corpus.size else None, coff.ctypes.data,
+                                               first.ctypes.data, pos.ctypes.data, steps.ctypes.data, eos_a.ctypes.data if eos_a is not None else None,
+                                               C.byref(o), C.cast(spx, C.c_void_p) if spx is not None else None,
+                                               C.cast(lst, C.c_void_p) if lst is not None else None, toks.ctypes.data, cnt.ctypes.data,
+                                               C.cast(st, C.c_void_p)))
+        got = [toks[i, : int(cnt[i])].copy() for i in range(n)]
+        return (got, [a.cut(int(cnt[i])) if a is not None else None for i, a in enumerate(lar)],
+                [dict(steps=st[i].steps, drafted=st[i].drafted, accepted=st[i].accepted) for i in range(n)])
 
     def forward_sample(self, cache, ids, pos, temperature, seed=0, draws_done=0, top_p=None, top_k=None, logprobs=None):
         """logprobs = N (0: the chosen token's only): returns (token, token_logprob [1], top_ids [1, N], top_logprobs [1, N]) --

@@ -412,6 +412,20 @@ int fl_batch_decode_lookup(fl_model *m, fl_cache *const *caches, size_t n, const
                                    samplers, tokens_out, n_out, stats);
     });
 }
+int fl_batch_verify_lp(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                       const fl_sampler *samplers, const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return guarded([&]() -> int {
+        return batch_verify_lp(M(m), reinterpret_cast<Cache *const *>(caches), n, ids, offsets, pos, samplers, lps, tokens_out, n_out, logits_out);
+    });
+}
+int fl_batch_decode_lookup_lp(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets,
+                              const uint32_t *first_tokens, const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts,
+                              const fl_sampler *samplers, const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return guarded([&]() -> int {
+        return batch_decode_lookup_lp(M(m), reinterpret_cast<Cache *const *>(caches), n, corpus, corpus_offsets, first_tokens, pos, n_steps, eos,
+                                      opts, samplers, lps, tokens_out, n_out, stats);
+    });
+}
 int fl_batch_decode(fl_batch *b, const uint32_t *first_tokens, const size_t *pos, size_t n_steps, int64_t eos,
                     const fl_sampling *sampling, uint32_t *tokens_out, size_t *n_out) {
     return guarded([&]() -> int {

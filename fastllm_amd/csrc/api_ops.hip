@@ -925,6 +925,121 @@ int fl_op_rules_count(uint32_t *words, int64_t V, const uint32_t *ids, int64_t n
     });
 }
 
+int fl_op_verify_adjust_packed(const float *logits, int64_t T, int64_t V, size_t n_seq, const size_t *offsets, const uint32_t *ids, uint32_t *words,
+                               const float *biases, const float *scalars, const uint8_t *has_rules, const fl_guide_desc *desc, const uint32_t *states,
+                               const uint8_t *has_guide, int64_t block_rows, const int64_t *n_acc, const uint32_t *returned, const int64_t *eos,
+                               float *out, uint32_t *words_adjusted, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        const char *who = "fl_op_verify_adjust_packed";
+        if (!logits || !offsets || !ids || (!out && !ms_out)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null argument", who);
+        if (T < 1 || T > kVerifyPackedMaxRows || V < 1 || V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: bad size (1 <= T <= %d, 1 <= V <= 2^24)", who, kVerifyPackedMaxRows);
+        if (n_seq < 1 || n_seq > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: n_seq %zu not in 1..%d", who, n_seq, kMaxBatch);
+        if (block_rows < 0 || iters < 0 || iters > (1 << 20)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: negative block_rows or a bad iteration count", who);
+        if (offsets[0] != 0 || offsets[n_seq] != (size_t)T) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: offsets must run from 0 to T", who);
+        if (words && (!biases || !scalars)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: rules need words, biases and scalars", who);
+        if (desc) {
+            FL_TRY(check_guide(desc, V));
+            if (!states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: a guide needs states", who);
+            for (int64_t t = 0; t < T; t++)
+                if (states[t] >= desc->n_states) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: states[%lld] = %u is not below n_states %u", who, (long long)t, states[t], desc->n_states);
+        }
+        std::vector<PackedRow> rows;
+        std::vector<int> off(n_seq), cnt(n_seq);
+        for (size_t s = 0; s < n_seq; s++) {
+            if (offsets[s + 1] <= offsets[s] || offsets[s + 1] - offsets[s] > (size_t)kVerifyMaxRows || offsets[s + 1] > (size_t)T)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: member %zu must have 1..%d rows", who, s, kVerifyMaxRows);
+            off[s] = (int)offsets[s]; cnt[s] = (int)(offsets[s + 1] - offsets[s]);
+            for (int t = 0; t < cnt[s]; t++) rows.push_back(PackedRow{(int)s, t});
+            if (n_acc && (n_acc[s] < 0 || n_acc[s] >= cnt[s])) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: n_acc[%zu] = %lld is not below the member's %d rows", who, s, (long long)n_acc[s], cnt[s]);
+        }
+        const int64_t R = block_rows == 0 ? T : std::min<int64_t>(block_rows, T);
+        OpScope S;
+        FL_TRY(S.begin());
+        float *lg, *od; LogitRuleEntry *tab = nullptr; uint32_t *ltok = nullptr, *idd, *sel; uint64_t *rp = nullptr;
+        PackedRow *rd; int *ofd, *cnd; VerifyAdjustMember *md;
+        FL_TRY(S.upload(&lg, logits, (size_t)T * V * 4));
+        FL_TRY(S.alloc(&od, (size_t)T * V * 4));
+        // every member's table back to back ([n_seq][V] entries: with an odd V the tables s > 0 start off a 16-byte boundary)
+        std::vector<LogitRuleEntry> img;
+        if (words) {
+            img.resize(n_seq * (size_t)V);
+            for (size_t j = 0; j < img.size(); j++) img[j] = LogitRuleEntry{words[j], biases[j]};
+            FL_TRY(S.upload(&tab, img.data(), img.size() * sizeof(LogitRuleEntry)));
+        }
+        if (desc) {
+            const size_t ns = desc->n_states, nnz = (size_t)desc->row_ptr[ns];
+            FL_TRY(S.upload(&rp, desc->row_ptr, (ns + 1) * 8));
+            FL_TRY(S.upload(&ltok, desc->tokens, nnz * 4));
+        }
+        std::vector<VerifyAdjustMember> mem(n_seq);
+        for (size_t s = 0; s < n_seq; s++) {
+            VerifyAdjustMember &M = mem[s];
+            if (words && (!has_rules || has_rules[s])) { M.table = tab + s * (size_t)V; M.rp = scalars[3 * s]; M.fp = scalars[3 * s + 1]; M.pp = scalars[3 * s + 2]; }
+            if (desc && (!has_guide || has_guide[s])) {
+                M.row_ptr = rp; M.tokens = ltok;
+                for (int t = 0; t < cnt[s]; t++) M.states[t] = states[off[s] + t];
+            }
+            M.eos = eos ? eos[s] : -1;
+        }
+        // the selection's out block as the count launch reads it: the returned ids and the accepted counts
+        std::vector<uint32_t> selh((size_t)kVerifyPackedWords, 0u);
+        for (int64_t t = 0; t < T; t++) selh[(size_t)t] = returned ? returned[t] : 0xffffffffu;
+        if (n_acc) for (size_t s = 0; s < n_seq; s++) selh[kVerifyPackedNacc + s] = (uint32_t)n_acc[s];
+        FL_TRY(S.upload(&rd, rows.data(), rows.size() * sizeof(PackedRow)));
+        FL_TRY(S.upload(&ofd, off.data(), n_seq * 4));
+        FL_TRY(S.upload(&cnd, cnt.data(), n_seq * 4));
+        FL_TRY(S.upload(&idd, ids, (size_t)T * 4));
+        FL_TRY(S.upload(&md, mem.data(), n_seq * sizeof(VerifyAdjustMember)));
+        FL_TRY(S.upload(&sel, selh.data(), selh.size() * 4));
+        VerifyAdjustPackedArgs a;
+        a.rows = rd; a.seq_off = ofd; a.seq_cnt = cnd; a.ids = idd; a.members = md;
+        auto pass = [&]() -> int {
+            for (int64_t r0 = 0; r0 < T; r0 += R) {
+                const int64_t nb = std::min<int64_t>(R, T - r0);
+                VerifyAdjustPackedArgs b = a;
+                b.out = od + (size_t)r0 * V;
+                const int nm = rows[(size_t)(r0 + nb - 1)].seq - rows[(size_t)r0].seq + 1;
+                FL_TRY(launch_verify_adjust_packed(S.L, lg + (size_t)r0 * V, V, (int)r0, (int)nb, (int)T, (int)n_seq, nm, b));
+            }
+            return FL_OK;
+        };
+        if (ms_out && iters > 0) {
+            FL_TRY(pass());                                               // warm
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipEventCreate(&S.e0)); FL_HIP(hipEventCreate(&S.e1));
+            FL_HIP(hipEventRecord(S.e0, S.s));
+            for (int i = 0; i < iters; i++) FL_TRY(pass());
+            FL_HIP(hipEventRecord(S.e1, S.s));
+            FL_HIP(hipEventSynchronize(S.e1));
+            float ms = 0.f; FL_HIP(hipEventElapsedTime(&ms, S.e0, S.e1));
+            *ms_out = ms / iters;
+        }
+        if (!out) return FL_OK;
+        std::vector<float> got[2];
+        for (int rep = 0; rep < 2; rep++) {                               // twice: workgroups count, search and fill in any order, the result must not depend on it
+            got[rep].resize((size_t)T * V);
+            FL_HIP(hipMemsetAsync(od, 0x55, (size_t)T * V * 4, S.s));
+            FL_TRY(pass());
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipMemcpy(got[rep].data(), od, (size_t)T * V * 4, hipMemcpyDeviceToHost));
+        }
+        if (memcmp(got[0].data(), got[1].data(), (size_t)T * V * 4)) FL_FAIL(FL_ERR_HIP, "verify_adjust_packed: a repeated pass gave another row");
+        memcpy(out, got[0].data(), (size_t)T * V * 4);
+        if (!words) return FL_OK;
+        if (words_adjusted) {                                             // the tables as the adjust launches left them: unchanged, if the kernel keeps its word
+            FL_HIP(hipMemcpy(img.data(), tab, img.size() * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < img.size(); j++) words_adjusted[j] = img[j].word;
+        }
+        if (n_acc) {
+            FL_TRY(launch_rules_count_packed(S.L, V, (int)n_seq, a, sel));
+            FL_HIP(hipStreamSynchronize(S.s));
+            FL_HIP(hipMemcpy(img.data(), tab, img.size() * sizeof(LogitRuleEntry), hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < img.size(); j++) words[j] = img[j].word;
+        }
+        return FL_OK;
+    });
+}
+
 int fl_op_encoder_attention(const void *q, const void *k, const void *v, const size_t *offsets, size_t n_seq, int64_t H, int64_t d,
                             int32_t dtype, float *out) {
     return guarded([&]() -> int {

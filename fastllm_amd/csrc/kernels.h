@@ -529,6 +529,34 @@ int launch_verify_adjust(Launcher &L, const float *logits, int64_t V, int T, con
 // ... and behind the step's selection: ids[0 .. n) counted into the table, in order (an id twice: counted twice; >= V: nothing)
 struct RulesCountArgs { uint32_t ids[kVerifyMaxRows] = {}; int n = 0; };
 int launch_rules_count(Launcher &L, LogitRuleEntry *table, int64_t V, const RulesCountArgs &a);
+// The packed form (k_verify_adjust_packed.hip; fl_batch_verify_lp): the same adjustment for the rows r0 .. r0 + R of a pack of
+// T_total <= kVerifyPackedMaxRows rows (launch_verify_packed's pack and tables), one launch per lm_head block in front of the block's
+// selection.  What differs per member lies in a DEVICE array, one VerifyAdjustMember each (uploaded with the pack's table image);
+// a member with neither table nor row_ptr has its rows copied through.  logits / out: [R][V], row r of the pack at row r - r0.
+struct VerifyAdjustMember {
+    LogitRuleEntry *table = nullptr;         // [V] or null: no rules (only read by the adjust launch; counted by launch_rules_count_packed)
+    const uint64_t *row_ptr = nullptr;       // the guide's CSR arrays, or null: no guide
+    const uint32_t *tokens = nullptr;
+    float rp = 1.f, fp = 0.f, pp = 0.f;
+    uint32_t _pad = 0;
+    int64_t eos = -1;                        // < 0: none (read by the count launch only)
+    uint32_t states[kVerifyMaxRows] = {};    // the guide state row t of the member is masked in (< n_states: the caller's duty)
+};
+struct VerifyAdjustPackedArgs {              // every pointer is device memory
+    const PackedRow *rows = nullptr;         // [T_total]
+    const int *seq_off = nullptr;            // [n_seq] a member's first row
+    const int *seq_cnt = nullptr;            // [n_seq] its rows, 1..16
+    const uint32_t *ids = nullptr;           // [T_total] the pack's ids: a member's token, then its draft
+    const VerifyAdjustMember *members = nullptr;   // [n_seq]
+    float *out = nullptr;                    // [R][V]
+};
+// n_members: how many members have a row in r0 .. r0 + R (consecutive ones, the first being rows[r0].seq)
+int launch_verify_adjust_packed(Launcher &L, const float *logits, int64_t V, int r0, int R, int T_total, int n_seq, int n_members,
+                                const VerifyAdjustPackedArgs &a);
+// ... and behind the LAST block's selection, on the same stream: per ruled member the inputs of the rows it keeps -- rows 0 .. n_acc,
+// n_acc read from sel_out[kVerifyPackedNacc + s] (launch_verify_packed's out block); rows 0 .. k only where returned id sel_out[seq_off[s]
+// + k] is the member's eos -- counted into its table, one lane per member, serially
+int launch_rules_count_packed(Launcher &L, int64_t V, int n_seq, const VerifyAdjustPackedArgs &a, const uint32_t *sel_out);
 // dst[i] = sum_s src[s][i] for n floats, written to every src (emulated all-reduce)
 int launch_reduce_shards(Launcher &L, float *const *bufs_dev, int nshards, int64_t n);
 

@@ -95,6 +95,14 @@ struct PackedScratch {
     uint32_t *verify_out = nullptr;
     uint32_t *host_verify = nullptr;
     float *verify_prob = nullptr; int64_t verify_prob_R = 0;
+    // fl_batch_verify_lp: the rule-adjusted, guide-masked rows of one lm_head block [verify_adj_R][V] fp32 that the selection reads in
+    // place of the raw block (launch_verify_adjust_packed) -- as large as the block scratch itself, FL_SCORE_ROWS x V x 4 bytes;
+    // allocated at a model's first packed verify with a ruled or guided member, regrown with the score_rows switch, counted in
+    // hbm_bytes -- and, allocated at the first one that asks for log-probs, a selection block of its own with the rows' records
+    // behind it ([kVerifyPackedWords] words | [kVerifyPackedMaxRows] ScoreRec; the words zeroed once), so that ids and records come
+    // back in one copy, and its pinned image
+    float *verify_adj = nullptr; int64_t verify_adj_R = 0;
+    uint32_t *verify_lp = nullptr, *host_verify_lp = nullptr;
     // fl_batch_embed: the pooled vectors [embed_rows][h] fp32 and the column chunks' partial sums of squares [embed_rows][chunks];
     // allocated at a model's first embed call, regrown with the largest call, counted in hbm_bytes
     float *embed_out = nullptr, *embed_part = nullptr; size_t embed_rows = 0;
@@ -430,6 +438,17 @@ int batch_verify(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, 
 int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
                         const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
                         uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
+// fl_batch_verify_lp / fl_batch_decode_lookup_lp: the same two calls for members with logit rules and / or a guide, with log-probs
+// (lps [n] or null; an entry with top_n < 0: none for that member)
+int batch_verify_lp(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                    const fl_sampler *samplers, const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, float *logits_out);
+int batch_decode_lookup_lp(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
+                           const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
+                           const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats);
+// how much of a draft the cache's guide can reach (all of it without one): a draft id without an edge can never be accepted
+size_t guide_cut_draft(const Cache *c, const uint32_t *draft, size_t n_draft);
+// lp's arrays from entry `at` on
+fl_logprobs logprobs_from(const fl_logprobs *lp, size_t at);
 
 // most K slices (fp32 slabs summed by the next launch) a row-parallel projection may use at T tokens (weights.hip)
 constexpr int kMaxKSplit = 4;

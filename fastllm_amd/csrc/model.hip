@@ -1492,7 +1492,7 @@ static bool guide_edge(const Guide *g, uint32_t s, uint32_t t, uint32_t *next) {
 }
 
 // A draft id without an edge from the state reached is -inf in the row before it and can never be accepted: the draft ends there.
-static size_t guide_cut_draft(const Cache *c, const uint32_t *draft, size_t n_draft) {
+size_t guide_cut_draft(const Cache *c, const uint32_t *draft, size_t n_draft) {
     if (!c->guide) return n_draft;
     uint32_t s = c->guide_state;
     for (size_t i = 0; i < n_draft; i++) if (!guide_edge(c->guide, s, draft[i], &s)) return i;
@@ -1518,7 +1518,7 @@ static int verify_commit(Model *m, Cache *c, uint32_t token, const uint32_t *dra
 }
 
 // lp's arrays from entry `at` on
-static fl_logprobs logprobs_from(const fl_logprobs *lp, size_t at) {
+fl_logprobs logprobs_from(const fl_logprobs *lp, size_t at) {
     fl_logprobs r = *lp;
     r.token_logprob += at;
     if (r.top_ids) r.top_ids += at * (size_t)lp->top_n;

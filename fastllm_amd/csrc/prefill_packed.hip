@@ -71,6 +71,28 @@ int grow_verify(Model *m, Shard &sh, bool any_sampled, float **rows, int64_t *R)
     return FL_OK;
 }
 
+// fl_batch_verify_lp's own buffers on top of grow_verify's: the adjusted block (as large as the block scratch: R x V x 4 bytes) for a
+// pack with a ruled or guided member, and for one that wants log-probs the selection block with the records behind it
+constexpr size_t kVerifyLpBytes = (size_t)kVerifyPackedWords * 4 + (size_t)kVerifyPackedMaxRows * sizeof(ScoreRec);
+int grow_verify_full(Model *m, Shard &sh, bool any_adjust, bool any_lp, int64_t R) {
+    PackedScratch &ps = sh.packed;
+    if (any_adjust && ps.verify_adj_R < R) {
+        const int64_t V = m->D.V;
+        FL_HIP(hipStreamSynchronize(sh.stream));                 // (idle anyway: every call ends with a synchronise)
+        if (ps.verify_adj) { (void)hipFree(ps.verify_adj); ps.verify_adj = nullptr; }
+        m->hbm_bytes -= ps.verify_adj_R * V * 4; ps.verify_adj_R = 0;
+        std::vector<void *> own;
+        FL_TRY(dev_alloc(own, (void **)&ps.verify_adj, (size_t)(R * V) * 4, nullptr));
+        m->hbm_bytes += R * V * 4; ps.verify_adj_R = R;
+    }
+    if (any_lp && !ps.verify_lp) {
+        FL_TRY(dev_alloc(sh.allocs, (void **)&ps.verify_lp, kVerifyLpBytes, &m->hbm_bytes));
+        FL_HIP(hipMemsetAsync(ps.verify_lp, 0, (size_t)kVerifyPackedWords * 4, sh.stream));
+    }
+    if (any_lp && !ps.host_verify_lp) FL_HIP(hipHostMalloc((void **)&ps.host_verify_lp, kVerifyLpBytes, hipHostMallocDefault));
+    return FL_OK;
+}
+
 // fl_batch_embed's buffers: the pooled vectors of `rows` outputs and the column chunks' partial sums of squares.  Allocated at a
 // model's first embed call and regrown with the largest one; models that never embed pay nothing.
 int grow_embed(Model *m, Shard &sh, size_t rows) {
@@ -123,7 +145,9 @@ int check_pack_shape(const PackWords &w, Cache *const *caches, size_t n, const s
 }
 
 // what a packed verify step hands back: member i's ids at tokens_out[offsets[i] ..], n_out[i] of them
-struct VerifyMode { uint32_t *tokens_out; size_t *n_out; };
+// full (fl_batch_verify_lp): members may have logit rules and / or a guide; lps [n] or null (top_n < 0: none for that member); eos [n]
+// or null: a member's returned ids end at its EOS as far as its rules table, its guide state and its log-prob arrays are concerned
+struct VerifyMode { uint32_t *tokens_out; size_t *n_out; bool full = false; const fl_logprobs *lps = nullptr; const int64_t *eos = nullptr; };
 
 // batch_prefill, or -- score != null -- batch_score, or -- vf != null -- batch_verify: the same checks and the same layers; behind them
 // either the n last rows go through the final norm, lm_head and token selection, or ALL rows go through the final norm and lm_head in
@@ -142,8 +166,21 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         if (caches[i]->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%scache %zu is null or belongs to another model", w.prefix, i);
         if (tokens_out) FL_TRY(refuse_logit_rules(caches[i], "fl_batch_prefill with tokens_out"));   // (its selection reads the raw rows)
         if (tokens_out) FL_TRY(refuse_guide(caches[i], "fl_batch_prefill with tokens_out"));
-        if (vf) FL_TRY(refuse_logit_rules(caches[i], "fl_batch_verify"));
-        if (vf) FL_TRY(refuse_guide(caches[i], "fl_batch_verify"));
+        if (vf && !vf->full) FL_TRY(refuse_logit_rules(caches[i], "fl_batch_verify"));
+        if (vf && !vf->full) FL_TRY(refuse_guide(caches[i], "fl_batch_verify"));
+    }
+    bool any_adjust = false, any_ruled = false, any_lp = false;
+    int lp_top = 0;
+    if (vf && vf->full) {
+        for (size_t i = 0; i < n; i++) {
+            any_ruled |= caches[i]->rules_on;
+            any_adjust |= caches[i]->rules_on || caches[i]->guide != nullptr;
+            if (!vf->lps || vf->lps[i].top_n < 0) continue;
+            FL_TRY(check_logprobs(vf->lps + i, m->D.V));
+            FL_TRY(logprobs_supported(m));
+            any_lp = true;
+            lp_top = std::max(lp_top, vf->lps[i].top_n);
+        }
     }
     if (emb) FL_TRY(check_embed(emb, m->D.h));
     const int mask = emb ? emb->mask : FL_MASK_CAUSAL;
@@ -212,18 +249,36 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
     PackedHost ph;
     packed_table_build(refs.data(), counts.data(), vt.data(), (int)n, sh.Hs, sh.Hkvs, D.d, &ph, (int)pad);
     // ... and behind it every member's step state for the call, set by ONE launch (not one per cache)
-    const size_t init_off = (ph.bytes.size() + 7) / 8 * 8, tab_bytes = init_off + n * sizeof(PackedSeqInit);
+    // ... and, for a pack with a ruled or guided member, every member's VerifyAdjustMember behind those: one copy for all of it
+    const size_t init_off = (ph.bytes.size() + 7) / 8 * 8, adj_off = (init_off + n * sizeof(PackedSeqInit) + 7) / 8 * 8;
+    const size_t tab_bytes = any_adjust ? adj_off + n * sizeof(VerifyAdjustMember) : init_off + n * sizeof(PackedSeqInit);
     FL_TRY(grow_packed(m, sh, (int)n, tab_bytes));
     PackedScratch &ps = sh.packed;
     float *vrows = nullptr;
     int64_t vR = 0;
     if (vf) FL_TRY(grow_verify(m, sh, any_sampled, &vrows, &vR));
+    if (vf) FL_TRY(grow_verify_full(m, sh, any_adjust, any_lp, vR));
     if (emb) FL_TRY(grow_embed(m, sh, T_total));
     StreamDrain drain{sh.stream};
     memcpy(ps.host_tab, ph.bytes.data(), ph.bytes.size());
     PackedSeqInit *init = reinterpret_cast<PackedSeqInit *>(ps.host_tab + init_off);
     for (size_t i = 0; i < n; i++)
         init[i] = PackedSeqInit{caches[i]->shards[0].heads_done, ids[offsets[i]], (uint32_t)pos[i], (uint32_t)caches[i]->len, 0u, sampler[i]};
+    if (any_adjust) {
+        VerifyAdjustMember *am = reinterpret_cast<VerifyAdjustMember *>(ps.host_tab + adj_off);
+        for (size_t i = 0; i < n; i++) {
+            const Cache *c = caches[i];
+            VerifyAdjustMember a;
+            if (c->rules_on) { a.table = c->shards[0].rule_tab; a.rp = c->rule_rp; a.fp = c->rule_fp; a.pp = c->rule_pp; }
+            if (c->guide) {                                      // the states the host walks: row t is masked in the state after drafts 0 .. t-1
+                a.row_ptr = c->guide->row_ptr_dev; a.tokens = c->guide->tokens_dev;
+                uint32_t st = c->guide_state;
+                for (size_t t = 0; t < (size_t)counts[i]; t++) { a.states[t] = st; if (t + 1 < (size_t)counts[i]) st = c->guide->walk(st, ids[offsets[i] + t + 1]); }
+            }
+            a.eos = vf->eos ? vf->eos[i] : -1;
+            am[i] = a;
+        }
+    }
     FL_HIP(hipMemcpyAsync(ps.tab, ps.host_tab, tab_bytes, hipMemcpyHostToDevice, sh.stream));
     FL_HIP(hipMemcpyAsync(sc.ids, pad ? twice : ids, (size_t)T * 4, hipMemcpyHostToDevice, sh.stream));
     const PackedTable tb = ph.at(ps.tab);
@@ -306,7 +361,16 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         VerifyPackedArgs va;
         va.rows = tb.rows; va.seq_off = tb.seq_off; va.seq_cnt = tb.seq_cnt;
         va.ss = &init_dev->ss; va.ss_stride = sizeof(PackedSeqInit);
-        va.ids = sc.ids; va.out = ps.verify_out;
+        uint32_t *const vout = any_lp ? ps.verify_lp : ps.verify_out;       // (a call with log-probs: the block that has the records behind it)
+        uint32_t *const hvout = any_lp ? ps.host_verify_lp : ps.host_verify;
+        ScoreRec *const recs = any_lp ? reinterpret_cast<ScoreRec *>(ps.verify_lp + kVerifyPackedWords) : nullptr;
+        va.ids = sc.ids; va.out = vout;
+        VerifyAdjustPackedArgs aa;
+        aa.rows = tb.rows; aa.seq_off = tb.seq_off; aa.seq_cnt = tb.seq_cnt; aa.ids = sc.ids;
+        aa.members = reinterpret_cast<const VerifyAdjustMember *>((const char *)ps.tab + adj_off);
+        aa.out = ps.verify_adj;
+        std::vector<int> member_of;                                          // row -> member, for the adjust launch's grid
+        if (any_adjust) for (size_t i = 0; i < n; i++) member_of.insert(member_of.end(), (size_t)counts[i], (int)i);
         const size_t V = (size_t)D.V;
         // fp32: a block never exceeds the 64 rows of the fp32 row-stream GEMM, and no block but a whole pack's is one row (below), so
         // that blocks of 3 .. 64 rows and more all run lm_head through that one kernel and what a row selects does not depend on the
@@ -314,11 +378,19 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         // bf16: the planner picks lm_head's kernel by the block's rows, so two switch values agree bit for bit only where it picks
         // the same one.
         const int64_t block = dt == FL_DTYPE_F32 ? std::min<int64_t>(vR, 64) : vR;
-        TicketReset tickets{ps.verify_out, sh.stream};
+        TicketReset tickets{vout, sh.stream};
         AllRows rows{vrows, block, [&](Launcher &L2, int64_t r0, int64_t nb) -> int {
             nb = std::min<int64_t>(nb, (int64_t)T_total - r0);           // (the copy of a one-row pack is neither selected nor returned)
             if (nb <= 0) return FL_OK;
-            FL_TRY(launch_verify_packed(L2, vrows, D.V, (int)r0, (int)nb, (int)T_total, va, ps.verify_prob, any_sampled));
+            const float *sel = vrows;                                    // what the selection reads
+            if (any_adjust) {
+                const int nm = member_of[(size_t)(r0 + nb - 1)] - member_of[(size_t)r0] + 1;
+                FL_TRY(launch_verify_adjust_packed(L2, vrows, D.V, (int)r0, (int)nb, (int)T_total, nn, nm, aa));
+                sel = ps.verify_adj;
+            }
+            FL_TRY(launch_verify_packed(L2, sel, D.V, (int)r0, (int)nb, (int)T_total, va, ps.verify_prob, any_sampled));
+            // the model's own distribution: the RAW block, the ids the selection just left on the device as targets
+            if (any_lp) FL_TRY(launch_score_rows(L2, vrows, D.V, (int)nb, vout + r0, lp_top, recs + r0));
             // (the diagnostic copy: stream-ordered, so the next block's lm_head overwrites the rows only behind it)
             if (logits_out) FL_HIP(hipMemcpyAsync(logits_out + (size_t)r0 * V, vrows, (size_t)nb * V * 4, hipMemcpyDeviceToHost, sh.stream));
             return FL_OK;
@@ -326,10 +398,12 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         rows.no_one_row_tail = true;
         FL_TRY(lm_head_rows(m, sh, L, sc, T, rows));
         // ... the members' error words into the same block: ids, accepted counts and error words come back in one copy
-        FL_TRY(launch_packed_collect(L, tb, ps.verify_out + kVerifyPackedAux, nn));
-        FL_HIP(hipMemcpyAsync(ps.host_verify, ps.verify_out, (size_t)kVerifyPackedWords * 4, hipMemcpyDeviceToHost, sh.stream));
+        FL_TRY(launch_packed_collect(L, tb, vout + kVerifyPackedAux, nn));
+        // the kept rows' inputs into every ruled member's table: behind the last selection, no host round trip in between
+        if (any_ruled) FL_TRY(launch_rules_count_packed(L, D.V, nn, aa, vout));
+        FL_HIP(hipMemcpyAsync(hvout, vout, (size_t)kVerifyPackedWords * 4 + (any_lp ? T_total * sizeof(ScoreRec) : 0), hipMemcpyDeviceToHost, sh.stream));
         FL_HIP(hipStreamSynchronize(sh.stream));
-        const uint32_t *hv = ps.host_verify;
+        const uint32_t *hv = hvout;
         for (size_t i = 0; i < n; i++) {
             if (hv[kVerifyPackedTicket + i]) FL_FAIL(FL_ERR_HIP, "packed verify step: the ticket of sequence %zu came back as %u, not 0", i, hv[kVerifyPackedTicket + i]);
             if (hv[kVerifyPackedAux + 2 * i + 1]) FL_FAIL(FL_ERR_HIP, "device-side wait gave up (code 0x%x) in sequence %zu", hv[kVerifyPackedAux + 2 * i + 1], i);
@@ -340,6 +414,17 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
             for (size_t k = 0; k < got; k++) vf->tokens_out[offsets[i] + k] = hv[offsets[i] + k];
             vf->n_out[i] = got;
             caches[i]->len += got;                               // rejected rows' K/V stay behind the length; the next append overwrites them
+            if (!vf->full) continue;
+            // the ids that count for the member's guide and log-prob arrays: all of them, or up to its EOS -- whose edge is walked,
+            // whose log-prob is not reported (fl_decode_lookup_lp's rule)
+            size_t upto = got, n_lp = got;
+            if (vf->eos && vf->eos[i] >= 0)
+                for (size_t k = 0; k < got; k++) if ((int64_t)hv[offsets[i] + k] == vf->eos[i]) { upto = k + 1; n_lp = k; break; }
+            if (caches[i]->guide) for (size_t k = 0; k < upto; k++) caches[i]->guide_state = caches[i]->guide->walk(caches[i]->guide_state, hv[offsets[i] + k]);
+            if (vf->lps && vf->lps[i].top_n >= 0) {
+                const ScoreRec *hr = reinterpret_cast<const ScoreRec *>(hvout + kVerifyPackedWords);
+                for (size_t k = 0; k < n_lp; k++) scatter_logprobs(hr[offsets[i] + k].lp, vf->lps + i, k);
+            }
         }
         tickets.armed = false;
         return FL_OK;
@@ -414,31 +499,79 @@ int batch_verify(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, 
     return packed_forward(m, caches, n, ids, offsets, pos, samplers, nullptr, logits_out, nullptr, &vf);
 }
 
-int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
+// fl_batch_verify_lp: batch_verify's checks in batch_verify's order (minus rules and guide), fl_logprobs' own behind the samplers';
+// then every guided member's draft is cut at the first id its guide cannot reach, and the cut pack goes through packed_forward
+static int verify_lp_call(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                          const fl_sampler *samplers, const fl_logprobs *lps, const int64_t *eos, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    const PackWords w{"fl_batch_verify_lp: ", "packed verify"};
+    if (n < 1 || n > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_verify_lp: %zu sequences: a packed verify takes 1..%d", n, kMaxBatch);
+    if (n_out) for (size_t i = 0; i < n; i++) n_out[i] = 0;
+    if (!caches || !ids || !offsets || !pos) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_verify_lp: null caches, ids, offsets or pos");
+    if (!tokens_out || !n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_verify_lp: null tokens_out or n_out");
+    SampleState probe;
+    if (samplers) for (size_t i = 0; i < n; i++) FL_TRY(make_sampler(samplers + i, 0, &probe));
+    if (lps) for (size_t i = 0; i < n; i++) if (lps[i].top_n >= 0) FL_TRY(check_logprobs(lps + i, 0));
+    FL_TRY(check_pack_shape(w, caches, n, offsets, (size_t)FL_VERIFY_MAX_DRAFT + 1));
+    if (!m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_verify_lp: null model");
+    VerifyMode vf{tokens_out, n_out, true, lps, eos};
+    bool cut = false;
+    std::vector<size_t> coff(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        const size_t nd = offsets[i + 1] - offsets[i] - 1;
+        const size_t keep = caches[i]->m == m ? guide_cut_draft(caches[i], ids + offsets[i] + 1, nd) : nd;   // (another model's cache: refused below)
+        cut |= keep != nd;
+        coff[i + 1] = coff[i] + 1 + keep;
+    }
+    if (!cut) return packed_forward(m, caches, n, ids, offsets, pos, samplers, nullptr, logits_out, nullptr, &vf);
+    // the cut pack: ids, tokens and raw rows in its own row order, moved to the caller's offsets afterwards
+    std::vector<uint32_t> cids(coff[n]), ctok(coff[n]);
+    for (size_t i = 0; i < n; i++) std::copy(ids + offsets[i], ids + offsets[i] + (coff[i + 1] - coff[i]), cids.begin() + (ptrdiff_t)coff[i]);
+    std::vector<float> crow;
+    const size_t V = (size_t)m->D.V;
+    if (logits_out) crow.resize(coff[n] * V);
+    vf.tokens_out = ctok.data();
+    FL_TRY(packed_forward(m, caches, n, cids.data(), coff.data(), pos, samplers, nullptr, logits_out ? crow.data() : nullptr, nullptr, &vf));
+    for (size_t i = 0; i < n; i++) {
+        std::copy(ctok.begin() + (ptrdiff_t)coff[i], ctok.begin() + (ptrdiff_t)(coff[i] + n_out[i]), tokens_out + offsets[i]);
+        if (logits_out) std::copy(crow.begin() + (ptrdiff_t)(coff[i] * V), crow.begin() + (ptrdiff_t)(coff[i + 1] * V), logits_out + offsets[i] * V);
+    }
+    return FL_OK;
+}
+
+int batch_verify_lp(Model *m, Cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets, const size_t *pos,
+                    const fl_sampler *samplers, const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, float *logits_out) {
+    return verify_lp_call(m, caches, n, ids, offsets, pos, samplers, lps, nullptr, tokens_out, n_out, logits_out);
+}
+
+// fl_batch_decode_lookup (full == false: ruled and guided members are refused, lps is null) and fl_batch_decode_lookup_lp: one loop
+static int batch_lookup_loop(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
                         const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
-                        uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
-    if (n < 1 || n > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: n = %zu sequences, a packed verify takes 1..%d", n, kMaxBatch);
+                        const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats, bool full) {
+    const char *fn = full ? "fl_batch_decode_lookup_lp" : "fl_batch_decode_lookup";
+    if (n < 1 || n > (size_t)kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: n = %zu sequences, a packed verify takes 1..%d", fn, n, kMaxBatch);
     if (n_out) for (size_t i = 0; i < n; i++) n_out[i] = 0;
     if (stats) for (size_t i = 0; i < n; i++) stats[i] = fl_spec_stats{};
     FL_TRY(check_lookup(opts));
     SampleState probe;
     if (samplers) for (size_t i = 0; i < n; i++) FL_TRY(make_sampler(samplers + i, 0, &probe));   // their argument errors, before the handles are looked at
-    if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: null n_out");
+    if (lps) for (size_t i = 0; i < n; i++) if (lps[i].top_n >= 0) FL_TRY(check_logprobs(lps + i, 0));
+    if (!n_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null n_out", fn);
     if (!caches || !corpus_offsets || !first || !pos || !n_steps)
-        FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: null caches, corpus_offsets, first_tokens, pos or n_steps");
+        FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null caches, corpus_offsets, first_tokens, pos or n_steps", fn);
     for (size_t i = 0; i < n; i++)
-        if (corpus_offsets[i + 1] < corpus_offsets[i]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: corpus_offsets decrease at sequence %zu", i);
-    if (corpus_offsets[n] > corpus_offsets[0] && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: null corpus");
+        if (corpus_offsets[i + 1] < corpus_offsets[i]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: corpus_offsets decrease at sequence %zu", fn, i);
+    if (corpus_offsets[n] > corpus_offsets[0] && !corpus) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null corpus", fn);
     size_t stride = 0;
     for (size_t i = 0; i < n; i++) stride = std::max(stride, n_steps[i]);
     if (stride == 0) return FL_OK;
-    if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: null tokens_out");
-    if (!m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: null model or cache");
+    if (!tokens_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null tokens_out", fn);
+    if (!m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: null model or cache", fn);
     for (size_t i = 0; i < n; i++) {
-        if (!caches[i] || caches[i]->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: cache %zu is null or belongs to another model", i);
-        for (size_t j = 0; j < i; j++) if (caches[j] == caches[i]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_batch_decode_lookup: cache %zu appears twice in the call", i);
-        FL_TRY(refuse_logit_rules(caches[i], "fl_batch_decode_lookup"));
-        FL_TRY(refuse_guide(caches[i], "fl_batch_decode_lookup"));
+        if (!caches[i] || caches[i]->m != m) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: cache %zu is null or belongs to another model", fn, i);
+        for (size_t j = 0; j < i; j++) if (caches[j] == caches[i]) FL_FAIL(FL_ERR_BAD_ARGUMENT, "%s: cache %zu appears twice in the call", fn, i);
+        if (!full) FL_TRY(refuse_logit_rules(caches[i], fn));
+        if (!full) FL_TRY(refuse_guide(caches[i], fn));
+        if (lps && lps[i].top_n >= 0) { FL_TRY(check_logprobs(lps + i, m->D.V)); FL_TRY(logprobs_supported(m)); }
         if (n_steps[i] == 0) continue;
         FL_TRY(check_call(m, caches[i], n_steps[i], pos[i]));
         FL_TRY(check_token(m, first[i], "token"));
@@ -458,8 +591,10 @@ int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t
     std::vector<size_t> who, poff, ppos, pn(n);
     std::vector<uint32_t> pids, got;
     std::vector<fl_sampler> psp;
+    std::vector<fl_logprobs> plp;
+    std::vector<int64_t> peos;
     for (;;) {
-        pc.clear(); who.clear(); pids.clear(); ppos.clear(); psp.clear();
+        pc.clear(); who.clear(); pids.clear(); ppos.clear(); psp.clear(); plp.clear(); peos.clear();
         poff.assign(1, 0);
         for (size_t i = 0; i < n; i++) {
             Member &b = mem[i];
@@ -473,6 +608,7 @@ int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t
             uint32_t draft[FL_VERIFY_MAX_DRAFT + 1];
             size_t nd = lookup_draft(b.hist.data(), b.hist.size(), opts->max_draft, opts->ngram_max, opts->ngram_min, limit, draft);
             for (size_t k = 0; k < nd; k++) if (draft[k] >= V) { nd = k; break; }      // (a corpus id the model does not have ends the draft)
+            if (full) nd = guide_cut_draft(c, draft, nd);            // ... and so does one the guide cannot reach
             who.push_back(i); pc.push_back(c);
             pids.push_back(b.tok);
             for (size_t k = 0; k < nd; k++) pids.push_back(draft[k]);
@@ -480,10 +616,15 @@ int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t
             ppos.push_back(pos[i] + b.emitted);
             // token k of the request is drawn with word k: this step's row r with word draws_done + emitted + r, whatever was rejected before
             if (samplers) { fl_sampler sp = samplers[i]; sp.draws_done += b.emitted; psp.push_back(sp); }
+            // ... and reported in entry k of the member's log-prob arrays
+            if (lps) { fl_logprobs lp = lps[i]; if (lp.top_n >= 0) lp = logprobs_from(lps + i, b.emitted); plp.push_back(lp); }
+            peos.push_back(eos ? eos[i] : -1);
         }
         if (who.empty()) break;
         got.resize(pids.size());
-        FL_TRY(batch_verify(m, pc.data(), who.size(), pids.data(), poff.data(), ppos.data(), samplers ? psp.data() : nullptr, got.data(), pn.data(), nullptr));
+        if (full) FL_TRY(verify_lp_call(m, pc.data(), who.size(), pids.data(), poff.data(), ppos.data(), samplers ? psp.data() : nullptr,
+                                        lps ? plp.data() : nullptr, peos.data(), got.data(), pn.data(), nullptr));
+        else FL_TRY(batch_verify(m, pc.data(), who.size(), pids.data(), poff.data(), ppos.data(), samplers ? psp.data() : nullptr, got.data(), pn.data(), nullptr));
         for (size_t a = 0; a < who.size(); a++) {
             const size_t i = who[a];
             Member &b = mem[i];
@@ -506,6 +647,18 @@ int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t
         }
     }
     return FL_OK;
+}
+
+int batch_decode_lookup(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
+                        const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
+                        uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return batch_lookup_loop(m, caches, n, corpus, corpus_offsets, first, pos, n_steps, eos, opts, samplers, nullptr, tokens_out, n_out, stats, false);
+}
+
+int batch_decode_lookup_lp(Model *m, Cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets, const uint32_t *first,
+                           const size_t *pos, const size_t *n_steps, const int64_t *eos, const fl_lookup *opts, const fl_sampler *samplers,
+                           const fl_logprobs *lps, uint32_t *tokens_out, size_t *n_out, fl_spec_stats *stats) {
+    return batch_lookup_loop(m, caches, n, corpus, corpus_offsets, first, pos, n_steps, eos, opts, samplers, lps, tokens_out, n_out, stats, true);
 }
 
 }  // namespace fl

@@ -1348,9 +1348,9 @@ struct PackedAdmit {
 
 // StreamBatcher option: on == false (default) is the batcher exactly as before.  With `on`, every step() drafts for each active
 // stream from prompt ++ emitted (fl_lookup_draft; the limit covers the stream's remaining max_tokens, its slot's capacity and the
-// model's sliding window), and when no active stream has logit rules or a guide and at least min_drafted ids were drafted in all, the
-// step is ONE fl_batch_verify over the active slots -- every stream advances by its accepted drafts + 1 for one read of the weights --
-// instead of a chunk of one-token steps.  Per stream the tokens are those of the plain batcher: ArgMax, or the seeded stream with the
+// model's sliding window), and when at least min_drafted ids were drafted in all, the step is ONE packed verify over the active slots
+// -- fl_batch_verify, or fl_batch_verify_lp while a stream with logit rules or a guide is active -- so that every stream advances by
+// its accepted drafts + 1 for one read of the weights, instead of a chunk of one-token steps.  Per stream the tokens are those of the plain batcher: ArgMax, or the seeded stream with the
 // word of each token's index (fl_forward_verify_ex's GUARANTEE).  Where nothing was drafted the step is the existing chunk.
 struct BatchLookup {
     bool on = false; LookupOptions lookup; size_t min_drafted = 1;
@@ -1377,8 +1377,9 @@ struct BatchLookup {
 // With PackedAdmit.on the admissions of one step() share forwards (fl_batch_prefill); per stream the tokens are those of the single
 // admission (the same logits up to fp32 summation order), and every counter but packed_calls / prefill_calls keeps its value.
 //
-// With BatchLookup.on a step with drafts is one packed verify step (fl_batch_verify) over the active slots; verify_steps / drafted /
-// accepted count them.  Refused together with counter_positions, like the prefix store: a verify step's rows sit at token positions.
+// With BatchLookup.on a step with drafts is one packed verify step (fl_batch_verify; fl_batch_verify_lp while a ruled or guided slot is
+// active, which counts that slot's rules and moves its guide as its plain steps do) over the active slots; verify_steps / drafted /
+// accepted count them (drafted: the ids looked up, before a guide cuts what it cannot reach).  Refused together with counter_positions, like the prefix store: a verify step's rows sit at token positions.
 class StreamBatcher {
   public:
     using OnToken = std::function<bool(uint32_t)>;
@@ -1535,9 +1536,10 @@ class StreamBatcher {
         std::vector<uint32_t> hist;          // with BatchLookup: the same ids, the text the drafts are looked up in
     };
 
-    // BatchLookup: draft for every active slot; false (and nothing done) when the step has to be the plain chunk -- a ruled or guided
-    // stream is active, or fewer than min_drafted ids were drafted in all.  Otherwise ONE fl_batch_verify over the active slots and the
-    // plain step's bookkeeping per returned id: an EOS, max_tokens or a refused callback finishes the slot and drops the ids behind it.
+    // BatchLookup: draft for every active slot; false (and nothing done) when the step has to be the plain chunk -- fewer than
+    // min_drafted ids were drafted in all.  Otherwise ONE packed verify over the active slots (fl_batch_verify_lp while one of them has
+    // logit rules or a guide: the launches of fl_batch_verify plus the adjust and count launches) and the plain step's bookkeeping per
+    // returned id: an EOS, max_tokens or a refused callback finishes the slot and drops the ids behind it.
     bool verify_step() {
         const fl_lookup o = lookup_.lookup.to_ffi();
         std::vector<Slot *> who;
@@ -1546,9 +1548,10 @@ class StreamBatcher {
         std::vector<size_t> offsets{0}, pos;
         std::vector<fl_sampler> sp;
         size_t total = 0;
+        bool full = false;                                         // a ruled or guided slot is active
         for (auto &sl : slots_) {
             if (!sl.active) continue;
-            if (sl.ruled || sl.guided) return false;
+            full |= sl.ruled || sl.guided;
             // room: this step caches the slot's token and its drafts, and hands back at most one id more than it drafted
             size_t limit = std::min(sl.req.max_tokens - sl.emitted, cap_ - sl.pos) - 1;
             limit = std::min(limit, draft_limit_);
@@ -1568,8 +1571,12 @@ class StreamBatcher {
         if (total < std::max<size_t>(lookup_.min_drafted, 1)) return false;
         std::vector<uint32_t> out(ids.size(), 0);
         std::vector<size_t> n_out(who.size(), 0);
-        check(fl_batch_verify(model_->m, caches.data(), caches.size(), ids.data(), offsets.data(), pos.data(), sp.data(), out.data(), n_out.data(), nullptr),
-              "Model forward pass failed");
+        if (full)
+            check(fl_batch_verify_lp(model_->m, caches.data(), caches.size(), ids.data(), offsets.data(), pos.data(), sp.data(), nullptr, out.data(),
+                                     n_out.data(), nullptr), "Model forward pass failed");
+        else
+            check(fl_batch_verify(model_->m, caches.data(), caches.size(), ids.data(), offsets.data(), pos.data(), sp.data(), out.data(), n_out.data(), nullptr),
+                  "Model forward pass failed");
         verify_steps++; drafted += total;
         for (size_t i = 0; i < who.size(); i++) accepted += n_out[i] - 1;
         std::exception_ptr failed;                                 // a callback that throws does not keep the other streams from their ids

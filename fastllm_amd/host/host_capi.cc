@@ -504,19 +504,19 @@ int flh_generate_lookup_request(void *hv, const uint32_t *prompt, size_t T, size
         return 0;
     });
 }
-// ... a request with a guide of its own (StreamBatcher::submit with GuideOptions); hv: the model the batcher was made for
-int flh_batcher_submit_guide(void *bv, void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
-                             uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,
-                             int (*on_token)(uint64_t id, uint32_t token, void *user), void (*on_done)(uint64_t id, size_t n_tokens, void *user),
-                             void *user, uint64_t *id_out) {
+// ... a request with a guide of its own (StreamBatcher::submit with GuideOptions); m: the model the batcher was made for
+static int batcher_submit_guide(void *bv, fl_model *m, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
+                                uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,
+                                int (*on_token)(uint64_t id, uint32_t token, void *user), void (*on_done)(uint64_t id, size_t n_tokens, void *user),
+                                void *user, uint64_t *id_out) {
     return guard([&] {
-        if (!bv || !hv || !on_token || (!prompt && T) || !row_ptr || !tokens || !next) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (!bv || !m || !on_token || (!prompt && T) || !row_ptr || !tokens || !next) throw Error(FL_ERR_BAD_ARGUMENT, "null argument");
         auto *bh = static_cast<BatcherHandle *>(bv);
         auto id = std::make_shared<uint64_t>(0);
         std::optional<uint32_t> e = eos >= 0 ? std::optional<uint32_t>((uint32_t)eos) : std::nullopt;
         const size_t nnz = (size_t)row_ptr[n_states];
         GuideOptions g;
-        g.guide = Guide(model_of(static_cast<Handle *>(hv))->m, std::vector<uint64_t>(row_ptr, row_ptr + n_states + 1),
+        g.guide = Guide(m, std::vector<uint64_t>(row_ptr, row_ptr + n_states + 1),
                         std::vector<uint32_t>(tokens, tokens + nnz), std::vector<uint32_t>(next, next + nnz));
         g.start_state = start_state;
         StreamBatcher::OnDone done;
@@ -526,6 +526,22 @@ int flh_batcher_submit_guide(void *bv, void *hv, const uint32_t *prompt, size_t 
         if (id_out) *id_out = *id;
         return 0;
     });
+}
+int flh_batcher_submit_guide(void *bv, void *hv, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
+                             uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,
+                             int (*on_token)(uint64_t id, uint32_t token, void *user), void (*on_done)(uint64_t id, size_t n_tokens, void *user),
+                             void *user, uint64_t *id_out) {
+    if (!hv) return guard([&]() -> int { throw Error(FL_ERR_BAD_ARGUMENT, "null argument"); });
+    return batcher_submit_guide(bv, model_of(static_cast<Handle *>(hv))->m, prompt, T, max_tokens, temperature, eos, n_states, row_ptr, tokens, next,
+                                start_state, on_token, on_done, user, id_out);
+}
+// ... on a batcher made with flh_batcher_create_on{,_packed,_lookup}: the fl_model the caller holds
+int flh_batcher_submit_guide_on(void *bv, void *fl_model_ptr, const uint32_t *prompt, size_t T, size_t max_tokens, float temperature, int64_t eos,
+                                uint32_t n_states, const uint64_t *row_ptr, const uint32_t *tokens, const uint32_t *next, uint32_t start_state,
+                                int (*on_token)(uint64_t id, uint32_t token, void *user), void (*on_done)(uint64_t id, size_t n_tokens, void *user),
+                                void *user, uint64_t *id_out) {
+    return batcher_submit_guide(bv, static_cast<fl_model *>(fl_model_ptr), prompt, T, max_tokens, temperature, eos, n_states, row_ptr, tokens, next,
+                                start_state, on_token, on_done, user, id_out);
 }
 int flh_batcher_run(void *bv, size_t *batch_steps, size_t *prefills) {
     return guard([&] {
@@ -593,7 +609,7 @@ int flh_batcher_create_on_packed(void *fl_model_ptr, size_t slots, size_t max_se
         return 0;
     });
 }
-// ... with BatchLookup (a step with drafts is one fl_batch_verify over the active slots): flh_batcher_create_on plus the option's values;
+// ... with BatchLookup (a step with drafts is one packed verify over the active slots): flh_batcher_create_on plus the option's values;
 // lookup_on == 0 is flh_batcher_create_on
 int flh_batcher_create_on_lookup(void *fl_model_ptr, size_t slots, size_t max_seq, size_t chunk, int counter_positions, int lookup_on, int max_draft,
                                  int ngram_max, int ngram_min, size_t min_drafted, void **out) {

@@ -408,7 +408,8 @@ int fl_decode_lookup_ex(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t
  *                        rows; a sampler error (struct_size, a NaN top_p, a negative top_k); null tokens_out / n_out
  *   FL_ERR_SEQ_OVERFLOW  per member, as fl_forward
  *   FL_ERR_UNSUPPORTED   tp_size > 1; n_draft_i above the sliding window of a Mistral / Qwen2 model; a member with logit rules or a guide
- * Not built: rules, guides and log-probs inside a packed verify, tensor parallelism, capturing the packed step in a graph. */
+ * Rules, guides and log-probs inside a packed verify: fl_batch_verify_lp below; this call keeps refusing such members.
+ * Not built: tensor parallelism, capturing the packed step in a graph. */
 int fl_batch_verify(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
                     const size_t *pos /* [n] */, const fl_sampler *samplers /* [n] or NULL: ArgMax for all */,
                     uint32_t *tokens_out /* [offsets[n]]: member i's ids at offsets[i] .. */, size_t *n_out /* [n] */,
@@ -739,8 +740,8 @@ int  fl_cache_guide_state(const fl_cache *c, uint32_t *state_out);
  * multi-row call and of a one-row call differ in the last bits (more so in bf16), and a choice that lands that close to a tie or to a
  * boundary of its cumulative interval can come out differently in the two loops.  Nothing else may separate them.
  * Refusals: those of the _ex calls (tensor parallelism, n_draft > sliding_window, sizes, null pointers, the sampler's argument errors)
- * plus those of fl_logprobs, all decided before the device is touched.  Not built: rules, guides and log-probs in a packed verify
- * (fl_batch_verify), tensor parallelism, capturing the step in a graph.
+ * plus those of fl_logprobs, all decided before the device is touched.  The packed form: fl_batch_verify_lp /
+ * fl_batch_decode_lookup_lp below.  Not built: tensor parallelism, capturing the step in a graph.
  * Memory: a model's first ruled or guided verify step allocates [16][V] fp32 of HBM (2 MB at V = 32 000, 9.7 MB at V = 152 064),
  * its first with log-probs 16 records; both are counted in fl_model_hbm_bytes and freed with the model. */
 int fl_forward_verify_lp(fl_model *m, fl_cache *c, uint32_t token, const uint32_t *draft, size_t n_draft, size_t pos,
@@ -750,6 +751,40 @@ int fl_decode_lookup_lp(fl_model *m, fl_cache *c, const uint32_t *corpus, size_t
                         size_t n_steps, int64_t eos, const fl_lookup *opts, const fl_sampler *sampler /* or NULL */,
                         const fl_logprobs *lp /* or NULL; arrays [n_steps] */, uint32_t *tokens_out, size_t *n_out,
                         fl_spec_stats *stats /* or NULL */);
+
+/* ---- packed verify for full requests: fl_batch_verify / fl_batch_decode_lookup for members with rules, a guide, log-probs --------------
+ * The same pack, the same forward and the same selection launches as fl_batch_verify; a member's cache may have logit rules, a guide or
+ * both, and any member may ask for log-probs.  Per member the contract is that of fl_forward_verify_lp / fl_decode_lookup_lp above, in
+ * the sense of its GUARANTEE (counting, guide states, draft trimming, raw-row log-probs, the EOS rule of the loop), and what
+ * fl_batch_verify says about WHAT A MEMBER'S RESULT DEPENDS ON holds unchanged.  As there, a member without drafts (also after
+ * trimming) is a row of the pack, not the one-row decode step.
+ *   Launches.  For a pack with at least one ruled or guided member, ONE launch per lm_head block (verify_adjust_packed_kernel) writes
+ *     the block the selection reads -- bare members' rows copied through bit for bit -- and one small launch behind the last block's
+ *     selection counts every ruled member's kept inputs into its table, reading the accepted counts on the device (no host round
+ *     trip).  Where any member asks for log-probs, one score launch per block on the RAW rows with the selected ids as targets, at the
+ *     largest requested top_n; each member receives its own first top_n, and the records come back with the ids in one copy.  A pack
+ *     in which no member has rules or a guide and no log-probs are asked runs exactly the launches of fl_batch_verify.
+ *   lps: NULL, or [n] fl_logprobs.  NO LOG-PROBS FOR MEMBER i: lps[i].top_n < 0 -- the entry's other fields are then not read (not
+ *     even struct_size).  Otherwise lps[i] is checked as fl_logprobs always is, its arrays hold one entry per row of the member
+ *     (fl_batch_verify_lp) or n_steps[i] entries (the loop), and entry k belongs to the member's k-th returned / emitted id.
+ *   logits_out: the raw rows at the caller's offsets; of a trimmed member only the rows of its remaining ids are written.
+ *   Memory: a model's first such call with a ruled or guided member allocates a second block scratch, [FL_SCORE_ROWS][V] fp32 (33 MB
+ *     at V = 32 000, 156 MB at V = 152 064 with the default 256 rows); its first with log-probs 1280 words + 1024 records (173 KB).
+ *     Both are counted in fl_model_hbm_bytes and freed with the model.
+ * Refusals: fl_batch_verify's (minus rules and guide) plus fl_logprobs' (behind the samplers' errors), all decided before the device or
+ * any cache is touched; a refused call modifies nothing and zeroes n_out.  A DEVICE failure reported after the forward (FL_ERR_HIP: a
+ * ticket or a device-side wait) is not a refusal: the count launch has run by then, so ruled members' tables have counted the kept
+ * inputs while cache lengths and guide states were not advanced -- reinstall the rules before such a cache is used again.
+ * Not built: tensor parallelism, graph capture. */
+int fl_batch_verify_lp(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *ids, const size_t *offsets /* [n+1] */,
+                       const size_t *pos /* [n] */, const fl_sampler *samplers /* [n] or NULL */,
+                       const fl_logprobs *lps /* [n] or NULL; top_n < 0 in an entry: none for that member */,
+                       uint32_t *tokens_out /* [offsets[n]] */, size_t *n_out /* [n] */, float *logits_out /* [offsets[n]][V] raw rows, or NULL */);
+int fl_batch_decode_lookup_lp(fl_model *m, fl_cache *const *caches, size_t n, const uint32_t *corpus, const size_t *corpus_offsets /* [n+1] */,
+                              const uint32_t *first_tokens, const size_t *pos, const size_t *n_steps /* [n] */, const int64_t *eos /* [n] or NULL */,
+                              const fl_lookup *opts, const fl_sampler *samplers /* [n] or NULL */,
+                              const fl_logprobs *lps /* [n] or NULL; top_n < 0 in an entry: none for that member */,
+                              uint32_t *tokens_out /* [n][max n_steps] */, size_t *n_out /* [n] */, fl_spec_stats *stats /* [n] or NULL */);
 
 int fl_synchronize(fl_model *m);
 
@@ -1183,6 +1218,25 @@ int fl_op_verify_adjust_time(const float *logits /* [T][V] */, int64_t T, int64_
                              double *ms_out);
 /* rules_count_kernel alone: ids[0 .. n), 0 <= n <= 16, counted into words [V] in order (saturating; an id >= V counts nothing). */
 int fl_op_rules_count(uint32_t *words /* [V] in/out */, int64_t V, const uint32_t *ids /* [n] */, int64_t n);
+
+/* verify_adjust_packed_kernel and rules_count_packed_kernel alone, on host arrays (unit tests, tools/verify_adjust_packed_cost.py): a pack
+ * of n_seq members (1..64), member s = rows offsets[s] .. offsets[s+1] (1..16 of them) of logits [T][V], T <= 1024, input ids `ids`.
+ * Rules (words != NULL; then biases [n_seq][V] and scalars [n_seq][3] too): member s has its own table; has_rules[s] == 0 gives it none.
+ * Guide (desc != NULL: ONE automaton, validated as fl_guide_create validates it; states [T] < n_states): row r of a guided member is
+ * masked in states[r]; has_guide[s] == 0 gives member s none.  A member with neither has its rows copied through.  The adjust kernel
+ * is launched once per block of block_rows rows (0: one block), the whole pass twice (FL_ERR_HIP if the two results differ); out [T][V]
+ * gets the adjusted rows and words_adjusted (or NULL) the tables AS THE ADJUST LAUNCHES LEFT THEM, i.e. unchanged.  With n_acc != NULL
+ * ([n_seq], below the member's row count) the count kernel then runs ONCE on an out block holding `returned` ([T] in pack order, or
+ * NULL) and n_acc, with member s's eos[s] (eos NULL or < 0: none), and words comes back counted.  iters > 0 with ms_out: the mean
+ * ms of `iters` adjust passes between two events (out may then be NULL: nothing else runs).  Argument errors: FL_ERR_BAD_ARGUMENT
+ * before the device is probed. */
+int fl_op_verify_adjust_packed(const float *logits /* [T][V] */, int64_t T, int64_t V, size_t n_seq, const size_t *offsets /* [n_seq+1] */,
+                               const uint32_t *ids /* [T] */, uint32_t *words /* [n_seq][V] in/out, or NULL */, const float *biases,
+                               const float *scalars, const uint8_t *has_rules /* [n_seq] or NULL */, const fl_guide_desc *desc /* or NULL */,
+                               const uint32_t *states /* [T] */, const uint8_t *has_guide /* [n_seq] or NULL */, int64_t block_rows,
+                               const int64_t *n_acc /* [n_seq] or NULL */, const uint32_t *returned /* [T] or NULL */,
+                               const int64_t *eos /* [n_seq] or NULL */, float *out /* [T][V] */, uint32_t *words_adjusted /* [n_seq][V] or NULL */,
+                               int32_t iters, double *ms_out);
 
 /* The copy kernel of fl_cache_copy_prefix alone on host buffers (unit tests, micro-benchmarks): `rows` rows of `width_bytes` bytes go
  * from src (rows * src_pitch bytes) to dst (rows * dst_pitch bytes).  dst is in/out: it is uploaded, the kernel runs, and it is read

@@ -814,6 +814,38 @@ extern "C" {
         n_out: *mut usize,
         stats: *mut fl_spec_stats,
     ) -> c_int;
+    /// The same two calls for members whose caches may have logit rules and / or a guide, with optional log-probs (`lps` null: none;
+    /// an entry with `top_n < 0`: none for that member).
+    pub fn fl_batch_verify_lp(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        ids: *const u32,
+        offsets: *const usize,
+        pos: *const usize,
+        samplers: *const fl_sampler,
+        lps: *const fl_logprobs,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        logits_out: *mut f32,
+    ) -> c_int;
+    pub fn fl_batch_decode_lookup_lp(
+        m: *mut fl_model,
+        caches: *const *mut fl_cache,
+        n: usize,
+        corpus: *const u32,
+        corpus_offsets: *const usize,
+        first_tokens: *const u32,
+        pos: *const usize,
+        n_steps: *const usize,
+        eos: *const i64,
+        opts: *const fl_lookup,
+        samplers: *const fl_sampler,
+        lps: *const fl_logprobs,
+        tokens_out: *mut u32,
+        n_out: *mut usize,
+        stats: *mut fl_spec_stats,
+    ) -> c_int;
     pub fn fl_op_verify_packed(
         logits: *const f32,
         t: i64,
@@ -1040,6 +1072,29 @@ extern "C" {
         ms_out: *mut f64,
     ) -> c_int;
     pub fn fl_op_rules_count(words: *mut u32, v: i64, ids: *const u32, n: i64) -> c_int;
+    pub fn fl_op_verify_adjust_packed(
+        logits: *const f32,
+        t: i64,
+        v: i64,
+        n_seq: usize,
+        offsets: *const usize,
+        ids: *const u32,
+        words: *mut u32,
+        biases: *const f32,
+        scalars: *const f32,
+        has_rules: *const u8,
+        desc: *const fl_guide_desc,
+        states: *const u32,
+        has_guide: *const u8,
+        block_rows: i64,
+        n_acc: *const i64,
+        returned: *const u32,
+        eos: *const i64,
+        out: *mut f32,
+        words_adjusted: *mut u32,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
 
     pub fn fl_synchronize(m: *mut fl_model) -> c_int;
 
