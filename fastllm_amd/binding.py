@@ -406,6 +406,8 @@ def lib():
         L.fl_op_qkv_rope.argtypes = [C.POINTER(FlQkvRopeArgs)]
         L.fl_op_attn_oproj_rep.argtypes = [C.POINTER(FlAttnOprojRepArgs)]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
+        L.fl_op_linear_w8.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
+        L.fl_op_linear_w8_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
         L.fl_lookup_draft.argtypes = [vp, sz, C.POINTER(FlLookup), sz, vp, C.POINTER(sz)]
@@ -1733,6 +1735,30 @@ def op_gemv_w8(x, q, s, bias=None, epilogue=0, iters=0):
     _check(lib().fl_op_gemv_w8(x.ctypes.data, q.ctypes.data, s.ctypes.data, b.ctypes.data if b is not None else None, N, K,
                                epilogue, y.ctypes.data, iters, C.byref(ms)))
     return (y, ms.value) if iters else y
+
+
+def op_linear_w8(x, q, s, bias=None, row_scale=None, epilogue=0, iters=0):
+    """y[T,N] = row_scale[t] * s[n] * (x . q^T) (+bias) through the 2-16-row FP8 weight stream (the kernel under a verify step of an
+    FP8 model).  x [T,K] uint16 (bf16 bits), q [N,K] uint8 (e4m3fn), s [N] float32, row_scale [T] float32 or None; epilogue 1: rows
+    are gate | up in HF order, y is [T, N/2]."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    N, K = q.shape
+    T = x.shape[0]
+    assert x.shape == (T, K) and s.shape == (N,)
+    y = np.empty((T, N // 2 if epilogue == 1 else N), dtype=np.float32)
+    b = _f32(bias) if bias is not None else None
+    r = _f32(row_scale) if row_scale is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_linear_w8(x.ctypes.data, q.ctypes.data, s.ctypes.data, _ptr(b), _ptr(r), T, N, K, epilogue, iters, C.byref(ms),
+                                 y.ctypes.data))
+    return (y, ms.value) if iters else y
+
+
+def op_linear_w8_plan(T, N, K, epilogue=0, bias=False):
+    """K slices op_linear_w8 runs such a product in, or 0: not served (no device needed)."""
+    return int(lib().fl_op_linear_w8_plan(T, N, K, epilogue, 1 if bias else 0))
 
 
 def _f32(a):

@@ -121,6 +121,14 @@ int launch_gemv_w8(Launcher &L, const GemvArgs &a, const float *wscale /* [N] */
 bool gemv_w8_supported(int64_t N, int64_t K);          // K a multiple of 16 (a lane's 16-byte load)
 bool gemv_w8_norm_supported(int64_t N, int64_t K);
 bool gemv_w8_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgMax candidate buffer
+// the 2-16-row sibling (k_gemm_rows_w8.hip): y[T,N] = rs[t] * s[n] * (x[T,K] . q[N,K]^T) (+ bias[n]), x bf16, rs (1/rms) optional;
+// EPI_F32 (y fp32) or EPI_GATEUP (q / s in the 16-interleaved layout, y bf16 [T, N/2]).  gemm_rows_w8_plan: the K slices the launch
+// will leave as fp32 slabs [nks][T][N] for the caller's next launch to sum (> 1 only for EPI_F32 without bias and max_split > 1),
+// or 0: not served (T outside 2..16, K no multiple of 16, x rows beyond LDS where slabs are not allowed) -- the caller then runs
+// what it ran before.  launch_gemm_rows_w8 fails with FL_ERR_UNSUPPORTED exactly where the plan is 0.
+int gemm_rows_w8_plan(int64_t T, int64_t N, int64_t K, int epi, bool bias, int max_split);
+int launch_gemm_rows_w8(Launcher &L, const uint8_t *q, const float *s, const void *x, const float *bias, void *y, int64_t T, int64_t N,
+                        int64_t K, int epi, const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
 // src [N,K] bf16 / fp32 -> q [N,K], s [N] and (img non-null; may be src when that is bf16) the bf16 image s * q
 int launch_quantize_rows(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, float *s, void *img_bf16);
 // rows in HF order (gate [0, I) | up [I, 2 I)) -> the 16-interleaved decode layout (test hook)

@@ -370,6 +370,9 @@ struct AllRows {
     // never leave a one-row last block where R >= 3 allows it (the block before it gives up a row): a one-row lm_head launch is the
     // planner's T = 1 kernel, another summation order than the rows of every other block see
     bool no_one_row_tail = false;
+    // a single-stream verify step: on an FL_WEIGHTS_E4M3_ROW model its 2-16 rows stream the e4m3 bytes (k_gemm_rows_w8.hip, fl_tune
+    // "verify_w8") wherever gemm_rows_w8_plan serves the projection; every other forward keeps the bf16 image
+    bool verify = false;
 };
 int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows);
 // the model's [R][V] fp32 block scratch of such a forward (ScoreScratch::rows; R: the score_rows switch now), allocated -- or regrown,

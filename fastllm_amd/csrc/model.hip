@@ -559,6 +559,13 @@ ResidEpi resid_epi(const Scratch &sc, const Dims &D, const float *next_norm_w) {
     return re;
 }
 
+// A single-stream verify step of an FL_WEIGHTS_E4M3_ROW model (one shard, bf16: model_create) reads the e4m3 bytes: its projections of
+// 2-16 rows go to k_gemm_rows_w8.hip wherever gemm_rows_w8_plan serves them, in their plain forms (the rope_kv and rmsnorm_add launches
+// behind them).  fl_tune "verify_w8" = 0, every other forward and every other model: the bf16 image, the launches there have always been.
+static bool verify_w8(const Model *m, const AllRows *rows, int64_t T) {
+    return rows && rows->verify && m->decode_weights == FL_WEIGHTS_E4M3_ROW && T >= 2 && T <= 16 && tune(TK_VERIFY_W8) != 0;
+}
+
 // lm_head on the T rows whose xn and 1/rms the final norm has left in sc, in blocks of at most rows.R rows into rows.out; rows.each
 // (if any) is enqueued behind every block, before the next one overwrites it
 int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows) {
@@ -566,7 +573,11 @@ int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const
     for (int64_t r0 = 0, n = 0; r0 < T; r0 += n) {
         n = std::min<int64_t>(rows.R, T - r0);
         if (rows.no_one_row_tail && T - r0 - n == 1 && n > 2) n -= 1;
-        FL_TRY(launch_linear(L, m->dtype, sh.lm_head, (char *)sc.xn + (size_t)r0 * D.h * m->esize(), nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
+        const void *xb = (char *)sc.xn + (size_t)r0 * D.h * m->esize();
+        if (verify_w8(m, &rows, n) && gemm_rows_w8_plan(n, sh.Vs, D.h, EPI_F32, false, 1))
+            FL_TRY(launch_gemm_rows_w8(L, sh.lm_head8, sh.lm_head_s, xb, nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
+        else
+            FL_TRY(launch_linear(L, m->dtype, sh.lm_head, xb, nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
         if (rows.each) FL_TRY(rows.each(L, r0, n));
     }
     return FL_OK;
@@ -611,6 +622,7 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
         if (rs_lazy) return FL_OK;
         return launch_rms_finalize(L, sc.rs_part, re.np, D.eps, sc.inv_rms, T, D.h);
     };
+    const bool w8 = verify_w8(m, all_rows, T);
     auto with_parts = [&](Launcher &L, Scratch &sc) {             // the launcher of the projection behind a lazy residual epilogue
         if (rs_lazy) { L.rsp = RsParts{sc.rs_part, gemm_resid_partials(D.h), D.eps, 1.0f / (float)D.h}; rs_lazy = false; }
     };
@@ -626,7 +638,11 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             const int64_t sa = (int64_t)c->seq_alloc;
             with_parts(L, sc);                                       // (the previous layer's down_proj may have left 1/rms as partial sums)
             const LinearPlan qp = plan_qkv_rope(dt, T, nq, D.h, D.d, D.d * sh.Hkvs, m->tp, qkv_split(T));
-            if (qp.rope) {
+            if (w8 && gemm_rows_w8_plan(T, nq, D.h, EPI_F32, false, qkv_split(T))) {
+                int qs = 1;
+                FL_TRY(launch_gemm_rows_w8(L, ly.wqkv8, ly.sqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qs));
+                FL_TRY(launch_rope_kv(L, dt, sc.qkv, cs.st, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kv.k, kv.v, T, sh.Hs, sh.Hkvs, D.d, sa, c->v_transposed, qs, ly.bqkv));
+            } else if (qp.rope) {
                 // RoPE, bias and the KV append ride in the projection's epilogue: no fp32 QKV matrix
                 RopeEpi ro;
                 ro.st = cs.st; ro.cos_tab = sh.cos_tab; ro.sin_tab = sh.sin_tab; ro.max_pos = (int)D.max_pos; ro.q_out = sc.q; ro.k_cache = kv.k; ro.v_cache = kv.v;
@@ -643,8 +659,11 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             } else {
                 FL_TRY(attend_prefill(L, m, c, sh, cs, kv, sc, T));
             }
-            const LinearPlan op = resid_ok ? plan_resid(dt, T, D.h, sh.Hs * D.d, max_split, false) : LinearPlan{};
-            if (op.kernel != LK_NONE) {
+            const bool o8 = w8 && gemm_rows_w8_plan(T, D.h, sh.Hs * D.d, EPI_F32, false, max_split);
+            const LinearPlan op = resid_ok && !o8 ? plan_resid(dt, T, D.h, sh.Hs * D.d, max_split, false) : LinearPlan{};
+            if (o8) {
+                FL_TRY(launch_gemm_rows_w8(L, ly.wo8, ly.so, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
+            } else if (op.kernel != LK_NONE) {
                 const bool gu_parts = plan_linear(dt, T, 2 * sh.Ip, D.h, EPI_GATEUP, m->tp, 1, false, false, false).reads_rs_parts;
                 FL_TRY(linear_resid(L, sc, op, ly.wo, sc.ao, sh.Hs * D.d, ly.ln2, gu_parts));
                 norm_done = true;
@@ -659,10 +678,16 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             if (!norm_done) FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
             norm_done = false;
             with_parts(L, sc);
-            FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
+            if (w8 && gemm_rows_w8_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP, false, 1))
+                FL_TRY(launch_gemm_rows_w8(L, ly.wgu8, ly.sgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
+            else
+                FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
             L.rsp = RsParts{};
-            const LinearPlan dp = resid_ok ? plan_resid(dt, T, D.h, sh.Ip, max_split, false) : LinearPlan{};
-            if (dp.kernel != LK_NONE) {
+            const bool d8 = w8 && gemm_rows_w8_plan(T, D.h, sh.Ip, EPI_F32, false, max_split);
+            const LinearPlan dp = resid_ok && !d8 ? plan_resid(dt, T, D.h, sh.Ip, max_split, false) : LinearPlan{};
+            if (d8) {
+                FL_TRY(launch_gemm_rows_w8(L, ly.wd8, ly.sd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
+            } else if (dp.kernel != LK_NONE) {
                 // (the next layer's QKV projection takes the partial sums if its kernel can; the last layer's final norm wants the vector)
                 const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
                 const bool qkv_parts = l + 1 < D.L && plan_qkv_rope(dt, T, nq, D.h, D.d, D.d * sh.Hkvs, m->tp, qkv_split(T)).reads_rs_parts;
@@ -1450,7 +1475,8 @@ static int verify_step(Model *m, Cache *c, uint32_t token, const uint32_t *draft
     FL_HIP(hipMemcpyAsync(sh.pre.ids, ids, (size_t)T * 4, hipMemcpyHostToDevice, sh.stream));
     const SampleState argmax{};
     FL_TRY(set_state(m, c, token, pos, c->len, 0, -1, c->len, &argmax));
-    const AllRows rows{sh.verify_logits, T, nullptr};
+    AllRows rows{sh.verify_logits, T, nullptr};
+    rows.verify = true;
     FL_TRY(enqueue_forward(m, c, true, T, true, (int64_t)c->len, &rows));
     Launcher L = make_launcher(m, sh);
     const float *sel = sh.verify_logits;                             // what the selection reads

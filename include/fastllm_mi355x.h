@@ -937,6 +937,18 @@ int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint
 int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
                   float *y, int32_t iters, double *ms_out);
 
+/* Its 2-16-row sibling, the kernel under a verify step of an FL_WEIGHTS_E4M3_ROW model (unit tests, micro-benchmarks):
+ * y[T,N] = row_scale[t] * s[n] * (x[T,K] . q[N,K]^T) (+bias).  x host bf16 [T,K], q host e4m3fn [N,K], s host fp32 [N], bias (or
+ * NULL) fp32 [N], row_scale (or NULL) fp32 [T]; y fp32.  epilogue as fl_op_gemv_w8 (1: q / s rows are gate/up in HF order, y is
+ * [T, N/2], the kernel's bf16 output widened; no bias).  K slices the launch leaves as slabs are summed in slab order, as fl_op_linear
+ * does.  FL_ERR_UNSUPPORTED where fl_op_linear_w8_plan is 0.  iters > 0 with ms_out != NULL times `iters` launches over rotating
+ * copies of q. */
+int fl_op_linear_w8(const void *x, const uint8_t *q, const float *s, const float *bias, const float *row_scale, int64_t T, int64_t N,
+                    int64_t K, int32_t epilogue, int32_t iters, double *ms_out, float *y);
+/* The K slices fl_op_linear_w8 runs such a product in (>= 1), or 0: not served -- T outside 2..16, K no multiple of 16, an
+ * epilogue other than 0 / 1, an odd gate/up row count, or x rows that do not fit LDS where slices are not allowed (gate/up, bias). */
+int fl_op_linear_w8_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue, int32_t has_bias);
+
 /* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
 
 /* launch_rmsnorm_add alone: x_res [T][h] fp32 (updated in place: += the n_slab slabs of delta, summed in slab order), delta
