@@ -408,6 +408,8 @@ def lib():
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_op_linear_w8.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
         L.fl_op_linear_w8_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+        L.fl_op_linear_w8_wide.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
+        L.fl_op_linear_w8_wide_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
         L.fl_lookup_draft.argtypes = [vp, sz, C.POINTER(FlLookup), sz, vp, C.POINTER(sz)]
@@ -1759,6 +1761,26 @@ def op_linear_w8(x, q, s, bias=None, row_scale=None, epilogue=0, iters=0):
 def op_linear_w8_plan(T, N, K, epilogue=0, bias=False):
     """K slices op_linear_w8 runs such a product in, or 0: not served (no device needed)."""
     return int(lib().fl_op_linear_w8_plan(T, N, K, epilogue, 1 if bias else 0))
+
+
+def op_linear_w8_wide(x, q, s, row_scale=None, epilogue=0, iters=0):
+    """op_linear_w8 (no bias) through the 17-64-row FP8 weight stream, the kernel under a decode batch of an FP8 model."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    N, K = q.shape
+    T = x.shape[0]
+    assert x.shape == (T, K) and s.shape == (N,)
+    y = np.empty((T, N // 2 if epilogue == 1 else N), dtype=np.float32)
+    r = _f32(row_scale) if row_scale is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_linear_w8_wide(x.ctypes.data, q.ctypes.data, s.ctypes.data, _ptr(r), T, N, K, epilogue, iters, C.byref(ms), y.ctypes.data))
+    return (y, ms.value) if iters else y
+
+
+def op_linear_w8_wide_plan(T, N, K, epilogue=0):
+    """K slices op_linear_w8_wide runs such a product in, or 0: not served (no device needed)."""
+    return int(lib().fl_op_linear_w8_wide_plan(T, N, K, epilogue))
 
 
 def _f32(a):

@@ -87,6 +87,11 @@ int batch_create(Model *m, Cache *const *caches, size_t B, Batch **out) {
                  gemm_skinny_supported((int64_t)B, D.h, sh.Ip);
     // more than eight streams, or a tensor-parallel rank: always the prefill-shaped step (launch_linear finds a kernel for every shape)
     if (!gemv_rows) b->unfused = true;
+    // an FL_WEIGHTS_E4M3_ROW model (one GPU, bf16: model_create): three members and more take the prefill-shaped step with its
+    // projections on the e4m3 bytes; one or two keep the fused step on the image.  The switch is read here, once: the step is a
+    // captured graph
+    b->w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW && B >= 3 && !per_seq && !tp_rank && tune(TK_BATCH_W8) != 0;
+    if (b->w8) b->unfused = true;
     if (b->unfused) {
         FL_TRY(alloc_scratch(m, sh, b->sc, (int64_t)B, &b->allocs));
     }
@@ -219,6 +224,18 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
         ga.W = W; ga.x = sc.xn; ga.x_scale = sc.inv_rms; ga.out = out; ga.N = (int)N; ga.K = (int)D.h; ga.epi = epi; ga.pro = PRO_X; ga.B = B; ga.nks = 1;
         return launch_gemv_dma(L, ga);
     };
+    // an FP8 batch: the projection from the e4m3 bytes where the kernel of its row count serves it (k_gemm_rows_w8.hip up to 16 rows,
+    // k_gemm_rows64_w8.hip from 17); *served = false: the caller's launch on the image.  From 17 rows a product that the plan would
+    // cut into K slices stays on the image: measured on Mistral-7B (profiles/r21/batch_w8.txt) the sliced QKV, o_proj and down_proj
+    // ran at 0.70-0.92x of the sliced short-prompt GEMM, the unsliced gate/up and lm_head at 1.09-1.51x
+    auto fp8 = [&](const uint8_t *q8, const float *s8, const void *x, void *out, int64_t N, int64_t K, int epi, const float *rs, int max_split, int *nsl,
+                   bool *served) -> int {
+        *served = b->w8 && (T <= 16 ? gemm_rows_w8_plan(T, N, K, epi, false, max_split) > 0 : gemm_rows64_w8_plan(T, N, K, epi, max_split) == 1);
+        if (!*served) return FL_OK;
+        if (T <= 16) return launch_gemm_rows_w8(L, q8, s8, x, nullptr, out, T, N, K, epi, rs, max_split, nsl);
+        return launch_gemm_rows64_w8(L, q8, s8, x, out, T, N, K, epi, rs, max_split, nsl);
+    };
+    bool on8 = false;
     const bool ps = b->per_seq;
     const size_t es = m->esize();
     if (ps && !b->plain) { for (int i = 0; i < B; i++) FL_TRY(launch_embed(L, dt, sh.embed, nullptr, b->caches[i]->shards[0].st, sc.x_res + (size_t)i * D.h, 1, D.h)); }
@@ -241,7 +258,7 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
     // down_proj with the residual + next norm in theirs (K slices met inside the launch: no slabs, no rmsnorm_add), gate/up with its
     // row scales from the partial sums -- where every projection of the model has a plan there; otherwise the eight-launch layer below
     const bool tpr = m->tp > 1;                                        // a rank of a multi-process group: all-reduce behind o_proj / down_proj, gathered logits
-    const int ks_q = dt == FL_DTYPE_BF16 && sc.rs_part && !tpr && !ps && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
+    const int ks_q = dt == FL_DTYPE_BF16 && sc.rs_part && !tpr && !ps && !b->w8 && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
     const LinearPlan po = plan_resid(dt, T, D.h, sh.Hs * D.d, 1, true), pd = plan_resid(dt, T, D.h, sh.Ip, 1, true);
     if (ks_q && po.kernel == LK_SKF && pd.kernel == LK_SKF && gemm_skf_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP) > 0) {
         const int np = gemm_resid_partials(D.h);
@@ -293,18 +310,22 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
             FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, 1, nullptr, true));
             FL_TRY(rope_attn_per_seq(l, ly.bqkv));
         } else {
-            FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, true));
+            FL_TRY(fp8(ly.wqkv8, ly.sqkv, sc.xn, sc.qkv, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, &on8));
+            if (!on8) FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, true));
             FL_TRY(launch_rope_kv_batch(L, sc.qkv, b->seqs_dev, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, (size_t)l * sh.Hkvs * D.d, B, sh.Hs,
                                         sh.Hkvs, D.d, qkv_slabs, ly.bqkv));
             FL_TRY(launch_attn_decode_mfma_batch(L, sc.q, b->seqs_dev, B, b->max_nsplit, (size_t)l * sh.Hkvs * D.d, sc.ao, sh.Hs, sh.Hkvs,
                                                  D.d, D.scale, 0.0));
         }
         // (a rank's row-parallel outputs: complete, no slabs -- the all-reduce wants the sum; sums in rank order on every rank)
-        FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
+        FL_TRY(fp8(ly.wo8, ly.so, sc.ao, sc.delta, D.h, sh.Hs * D.d, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
+        if (!on8) FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
-        FL_TRY(wide(ly.wgu, sc.act, 2 * sh.Ip, EPI_GATEUP));
-        FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
+        FL_TRY(fp8(ly.wgu8, ly.sgu, sc.xn, sc.act, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms, 1, nullptr, &on8));
+        if (!on8) FL_TRY(wide(ly.wgu, sc.act, 2 * sh.Ip, EPI_GATEUP));
+        FL_TRY(fp8(ly.wd8, ly.sd, sc.act, sc.delta, D.h, sh.Ip, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
+        if (!on8) FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
     }
     FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
@@ -314,7 +335,8 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
         FL_TRY(oneshot(m, sh, true, b->logits_local, b->logits_ranks, (int64_t)B * sh.Vs, (int64_t)B * sh.Vs));
         FL_TRY(launch_unshard_logits(L, b->logits_ranks, b->logits, m->tp, B, sh.Vs));
     } else {
-        FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
+        FL_TRY(fp8(sh.lm_head8, sh.lm_head_s, sc.xn, b->logits, D.V, D.h, EPI_F32, sc.inv_rms, 1, nullptr, &on8));
+        if (!on8) FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
     }
     return batch_select(b, L, kind);
 }

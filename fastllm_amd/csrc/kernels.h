@@ -129,6 +129,12 @@ bool gemv_w8_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgM
 int gemm_rows_w8_plan(int64_t T, int64_t N, int64_t K, int epi, bool bias, int max_split);
 int launch_gemm_rows_w8(Launcher &L, const uint8_t *q, const float *s, const void *x, const float *bias, void *y, int64_t T, int64_t N,
                         int64_t K, int epi, const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
+// the 17-64-row sibling (k_gemm_rows64_w8.hip; x through LDS in double-buffered K blocks, 32 weight rows per wave): the same product
+// without bias, the same epilogues and slabs.  gemm_rows64_w8_plan: the K slices, or 0: not served (T outside 17..64, K no multiple
+// of 16, gate/up rows no multiple of 32); launch_gemm_rows64_w8 fails with FL_ERR_UNSUPPORTED exactly there.
+int gemm_rows64_w8_plan(int64_t T, int64_t N, int64_t K, int epi, int max_split);
+int launch_gemm_rows64_w8(Launcher &L, const uint8_t *q, const float *s, const void *x, void *y, int64_t T, int64_t N, int64_t K, int epi,
+                          const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
 // src [N,K] bf16 / fp32 -> q [N,K], s [N] and (img non-null; may be src when that is bf16) the bf16 image s * q
 int launch_quantize_rows(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, float *s, void *img_bf16);
 // rows in HF order (gate [0, I) | up [I, 2 I)) -> the 16-interleaved decode layout (test hook)

@@ -144,8 +144,10 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
 /* Weight format of the decode step (fl_model_create_opts).  FL_WEIGHTS_E4M3_ROW: the single-stream decode step (T = 1) reads its
  * projection weights (q/k/v, o, gate/up, down, lm_head) as FP8: W'[n,k] = s[n] * q[n,k], q OCP e4m3fn, s[n] = 2^e one fp32 scale
  * per output row, e the smallest integer with absmax(W[n,:]) / 2^e <= 448 (all-zero row: s = 1), q = RNE_e4m3(W / s).  s * q is
- * exact in bf16, so the model IS the bf16 model whose weights are W': prompts (T > 1) and fl_batch_* steps run the bf16 kernels on
- * a bf16 image of W', and every path sees the same weights.  Both images are kept: weight memory is 1.5x a bf16 model's -- this
+ * exact in bf16, so the model IS the bf16 model whose weights are W': prompts (T > 1) and fl_batch_* steps of 1-2 members run the
+ * bf16 kernels on a bf16 image of W', and every path sees the same weights.  A batch of 3-64 members streams the e4m3 bytes too
+ * (rows equal the image's up to fp32 summation order); its switch, fl_tune "batch_w8" (FL_BATCH_W8; 0: the image), is read by
+ * fl_batch_create -- the batch's step is a captured graph, so a later change reaches new batches only.  Both images are kept: weight memory is 1.5x a bf16 model's -- this
  * mode buys decode speed (half the bytes of the weight stream), not capacity.  Embedding and norm weights stay as they are.
  * REFUSED: compute_dtype other than BF16, tp_size > 1 (any mode), a model whose fused decode step is off (FL_FUSED=0, hidden_size
  * above 6144), hidden_size not a multiple of 16 -> FL_ERR_UNSUPPORTED; an unknown decode_weights or a struct_size that is not
@@ -948,6 +950,15 @@ int fl_op_linear_w8(const void *x, const uint8_t *q, const float *s, const float
 /* The K slices fl_op_linear_w8 runs such a product in (>= 1), or 0: not served -- T outside 2..16, K no multiple of 16, an
  * epilogue other than 0 / 1, an odd gate/up row count, or x rows that do not fit LDS where slices are not allowed (gate/up, bias). */
 int fl_op_linear_w8_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue, int32_t has_bias);
+
+/* The 17-64-row kernel under a decode batch of an FL_WEIGHTS_E4M3_ROW model (k_gemm_rows64_w8.hip), alone: the product, operands,
+ * epilogues, slab summation and timing form of fl_op_linear_w8, without bias.  FL_ERR_UNSUPPORTED where fl_op_linear_w8_wide_plan
+ * is 0. */
+int fl_op_linear_w8_wide(const void *x, const uint8_t *q, const float *s, const float *row_scale, int64_t T, int64_t N, int64_t K,
+                         int32_t epilogue, int32_t iters, double *ms_out, float *y);
+/* The K slices fl_op_linear_w8_wide runs such a product in (>= 1), or 0: not served -- T outside 17..64, K no multiple of 16, an
+ * epilogue other than 0 / 1, an odd gate/up row count. */
+int fl_op_linear_w8_wide_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue);
 
 /* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
 
