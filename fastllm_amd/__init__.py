@@ -13,5 +13,7 @@ from .binding import (Batch, Cache, FastLLMError, Model, abi_version, comm_uniqu
                       op_rope_kv, op_qkv_rope, FlRopeSeqs, FlRopeKvArgs, FlQkvRopeArgs, ROPE_KV_NAMES,
                       op_attn_oproj_rep, op_attn_oproj_rep_info, FlAttnOprojRepArgs,
                       op_encoder_embed_ln, op_encoder_add_ln, op_encoder_bias_act, op_encoder_pool_l2, FlEncoderRowsArgs, ENC_ACT,
-                      op_convert_slice, FlConvertSliceArgs, MODEL_TENSORS, ELEM_E4M3)
+                      op_convert_slice, FlConvertSliceArgs, MODEL_TENSORS, ELEM_E4M3,
+                      op_select_rows, op_embed_rows, op_unshard_logits, op_gather_last_rows, op_reduce_shards, op_packed_states, make_sampler,
+                      FlSelectRowsArgs, FlMoveRowsArgs, FlSampler, STEP_STATE, LOGPROB_REC, MOVE_ROWS_GUARD, MOVE_KINDS)
 from .configs import MODEL_CONFIGS  # noqa: F401

@@ -215,6 +215,33 @@ class FlEncoderRowsArgs(C.Structure):
                 ("ln_b", C.c_void_p), ("eps", C.c_float), ("reserved2", C.c_float), ("x_res_out", C.c_void_p), ("out", C.c_void_p)]
 
 
+class FlSelectRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("form", C.c_int32), ("advance", C.c_int32), ("n_steps", C.c_int32), ("top_n", C.c_int32),
+                ("B", C.c_int64), ("V", C.c_int64), ("out_cap", C.c_int64), ("lp_cap", C.c_int64), ("logits", C.c_void_p),
+                ("states", C.c_void_p), ("samplers", C.c_void_p), ("cand_values", C.c_void_p), ("cand_indices", C.c_void_p),
+                ("cand_count", C.c_int64), ("states_out", C.c_void_p), ("out_tokens", C.c_void_p), ("kept_out", C.c_void_p),
+                ("lp_records_out", C.c_void_p), ("launches_out", C.c_void_p)]
+
+
+class FlMoveRowsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("kind", C.c_int32), ("dtype", C.c_int32), ("use_state", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("h", C.c_int64), ("vocab", C.c_int64), ("tp", C.c_int64), ("Vs", C.c_int64), ("n_seq", C.c_int64),
+                ("n_slab", C.c_int64), ("src_slab", C.c_int64), ("dst_slab", C.c_int64), ("nshards", C.c_int64), ("n", C.c_int64),
+                ("n_tickets", C.c_int64), ("table", C.c_void_p), ("ids", C.c_void_p), ("src", C.c_void_p), ("counts", C.c_void_p),
+                ("tokens", C.c_void_p), ("pos", C.c_void_p), ("len", C.c_void_p), ("samplers", C.c_void_p), ("plant_tokens", C.c_void_p),
+                ("plant_errors", C.c_void_p), ("out_words", C.c_int64), ("out", C.c_void_p), ("states_out", C.c_void_p),
+                ("ss_init_out", C.c_void_p), ("ss_out", C.c_void_p), ("tickets_out", C.c_void_p), ("collect_out", C.c_void_p),
+                ("launches_out", C.c_void_p)]
+
+
+# fl_step_state and one log-prob record of op_select_rows as numpy record types; the guard band of op_move_rows' destinations
+STEP_STATE = np.dtype([("token", "<u4"), ("pos", "<u4"), ("len", "<u4"), ("step", "<u4"), ("eos", "<i4"), ("done", "<u4"), ("error", "<u4"),
+                       ("call0", "<u4")])
+LOGPROB_REC = np.dtype([("chosen", "<f4"), ("ids", "<u4", (20,)), ("lps", "<f4", (20,))])
+MOVE_ROWS_GUARD = 64
+MOVE_KINDS = {"embed": 0, "embed_batch": 1, "unshard_logits": 2, "gather_last_rows": 3, "reduce_shards": 4, "packed_states": 5}
+
+
 class FlConvertSliceArgs(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32), ("row_mode", C.c_int32),
                 ("head_pad", C.c_int32), ("via_bf16", C.c_int32), ("reserved", C.c_int32), ("R", C.c_int64), ("C", C.c_int64),
@@ -444,6 +471,8 @@ def lib():
         L.fl_op_encoder_attention.argtypes = [vp, vp, vp, vp, sz, C.c_int64, C.c_int64, C.c_int32, vp]
         L.fl_op_encoder_rows.argtypes = [C.POINTER(FlEncoderRowsArgs)]
         L.fl_op_convert_slice.argtypes = [C.POINTER(FlConvertSliceArgs)]
+        L.fl_op_select_rows.argtypes = [C.POINTER(FlSelectRowsArgs)]
+        L.fl_op_move_rows.argtypes = [C.POINTER(FlMoveRowsArgs)]
         L.fl_op_model_tensor.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         _LIB = L
     return _LIB
@@ -918,6 +947,130 @@ def op_convert_slice(src, r0, c0, rows, cols, dst_dtype, dst_rows, dst_ld, dst_r
     a.src, a.dst = src.ctypes.data, out.ctypes.data
     _check(lib().fl_op_convert_slice(C.byref(a)))
     return out
+
+
+def _sampler_array(samplers, n):
+    """an fl_sampler array out of a list of FlSampler / None (ArgMax) entries, or None for a None list"""
+    if samplers is None:
+        return None
+    assert len(samplers) == n
+    spx = (FlSampler * max(n, 1))()
+    for i, s in enumerate(samplers):
+        spx[i] = s if s is not None else make_sampler(0.0)
+    return spx
+
+
+SelectRows = collections.namedtuple("SelectRows", "states out_tokens kept records launches")
+
+
+def op_select_rows(logits, states, form=0, advance=1, n_steps=1, out_cap=None, samplers=None, cand=None, lp_cap=0, top_n=0):
+    """The token selection launches alone (fl_op_select_rows): logits [B, V] float32; states: a STEP_STATE array [B]; samplers: a list of
+    FlSampler / None (ArgMax) or None; form 0: launch_select_advance per member, 1: launch_select_advance_batch, 2: launch_select_advance
+    over cand = (values, indices), the candidate list of an lm_head launch.  The launch is repeated n_steps times; lp_cap > 0: each is
+    followed by launch_token_logprobs in the matching state form.  Returns SelectRows: states STEP_STATE [B] after the last launch,
+    out_tokens uint32 [B, out_cap] whole (0xffffffff: not written), kept uint32 [B, n_steps], records LOGPROB_REC [B, lp_cap + 1] (or
+    None; all-ones bits: not written) and launches = (select_advance, select_advance_batch, token_logprobs) counts."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    Bn, V = lg.shape
+    st = np.ascontiguousarray(states, dtype=STEP_STATE).reshape(-1)
+    assert st.shape == (Bn,)
+    cap = int(out_cap) if out_cap is not None else int(st["step"].max()) + int(n_steps)
+    spx = _sampler_array(samplers, Bn)
+    a = FlSelectRowsArgs()
+    a.struct_size = C.sizeof(FlSelectRowsArgs)
+    a.form, a.advance, a.n_steps, a.top_n, a.B, a.V, a.out_cap, a.lp_cap = form, advance, n_steps, top_n, Bn, V, cap, lp_cap
+    a.logits, a.states = lg.ctypes.data, st.ctypes.data
+    a.samplers = C.cast(spx, C.c_void_p) if spx is not None else None
+    if cand is not None:
+        cv, ci = np.ascontiguousarray(cand[0], dtype=np.float32).reshape(-1), np.ascontiguousarray(cand[1], dtype=np.int32).reshape(-1)
+        assert cv.shape == ci.shape
+        a.cand_values, a.cand_indices, a.cand_count = _ptr(cv) if cv.size else None, _ptr(ci) if ci.size else None, cv.size
+    out_st = np.zeros(Bn, STEP_STATE)
+    toks = np.zeros((Bn, max(cap, 1)), np.uint32)
+    kept = np.zeros((Bn, max(int(n_steps), 1)), np.uint32)
+    recs = np.zeros((Bn, int(lp_cap) + 1), LOGPROB_REC) if lp_cap > 0 else None
+    launches = np.zeros(3, np.int32)
+    a.states_out, a.out_tokens, a.kept_out, a.lp_records_out, a.launches_out = out_st.ctypes.data, toks.ctypes.data, kept.ctypes.data, _ptr(recs), launches.ctypes.data
+    _check(lib().fl_op_select_rows(C.byref(a)))
+    return SelectRows(out_st, toks, kept, recs, tuple(int(x) for x in launches))
+
+
+def _move_rows(kind, payload_words, keep, shards=1, **fields):
+    """one fl_op_move_rows call of kinds 0 to 4: the destination whole, uint32 words [shards, guard + payload + guard] ([..] for one
+    shard), and the launch counts"""
+    a = FlMoveRowsArgs()
+    a.struct_size = C.sizeof(FlMoveRowsArgs)
+    a.kind = MOVE_KINDS[kind]
+    for name, v in fields.items():
+        setattr(a, name, v.ctypes.data if isinstance(v, np.ndarray) else v)
+    out = np.zeros((shards, int(payload_words) + 2 * MOVE_ROWS_GUARD), np.uint32)
+    launches = np.zeros(2, np.int32)
+    a.out_words, a.out, a.launches_out = out.size, out.ctypes.data, launches.ctypes.data
+    _check(lib().fl_op_move_rows(C.byref(a)))
+    del keep
+    return (out if shards > 1 or kind == "reduce_shards" else out[0]), tuple(int(x) for x in launches)
+
+
+def op_embed_rows(table, ids, batch=False, use_state=False):
+    """launch_embed (or, batch: launch_embed_batch, the ids in the members' step states; use_state: launch_embed reading its one id from
+    a step state) alone: table [vocab, h] uint16 bf16 bits or float32, ids [rows].  Returns (uint32 words [guard + rows * h + guard]:
+    fp32 rows between guard bands of all-ones words, launch counts)."""
+    table = np.ascontiguousarray(table)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    return _move_rows("embed_batch" if batch else "embed", ids.size * table.shape[1], (table, ids), dtype=_np_dtype_code(table), use_state=int(use_state),
+                      rows=ids.size, h=table.shape[1], vocab=table.shape[0], table=table, ids=ids)
+
+
+def op_unshard_logits(src):
+    """launch_unshard_logits alone: src [tp, B, Vs] float32 -> (uint32 words [guard + B * tp * Vs + guard], launch counts)."""
+    src = _f32(src)
+    tp, Bn, Vs = src.shape
+    return _move_rows("unshard_logits", src.size, (src,), tp=tp, rows=Bn, Vs=Vs, src=src)
+
+
+def op_gather_last_rows(src, counts, h, dst_slab):
+    """launch_gather_last_rows alone: src [n_slab, src_slab] float32, each slab beginning with the pack's [sum(counts), h] rows; member
+    s owns counts[s] rows -> (uint32 words [guard + n_slab * dst_slab + guard], launch counts)."""
+    src = _f32(src)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    n_slab, src_slab = src.shape
+    return _move_rows("gather_last_rows", n_slab * int(dst_slab), (src, counts), n_seq=counts.size, h=h, n_slab=n_slab, src_slab=src_slab,
+                      dst_slab=dst_slab, src=src, counts=counts)
+
+
+def op_reduce_shards(src):
+    """launch_reduce_shards alone: src [nshards, n] float32, a device buffer per shard -> (uint32 words [nshards, guard + n + guard],
+    launch counts)."""
+    src = _f32(src)
+    nshards, n = src.shape
+    return _move_rows("reduce_shards", n, (src,), shards=nshards, nshards=nshards, n=n, src=src)
+
+
+PackedStates = collections.namedtuple("PackedStates", "states ss_init ss tickets collect launches")
+
+
+def op_packed_states(tokens, pos, lens, n_tickets, plant_tokens, plant_errors, samplers=None, tickets=True):
+    """launch_packed_set_states, then launch_packed_collect alone over n members whose device states start as all-ones bits.  Returns
+    PackedStates: states STEP_STATE [n] after the first launch, ss_init / ss uint32 [n, 16] (the token selection state as built on the
+    host / as the device holds it), tickets uint32 [n, n_tickets + guard] (None with tickets=False), collect uint32 [guard + 2 n + guard]
+    (what the second launch gathered after plant_tokens / plant_errors went into the states) and the launch counts."""
+    cols = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (tokens, pos, lens, plant_tokens, plant_errors)]
+    n = cols[0].size
+    assert all(c.size == n for c in cols)
+    spx = _sampler_array(samplers, n)
+    a = FlMoveRowsArgs()
+    a.struct_size = C.sizeof(FlMoveRowsArgs)
+    a.kind, a.n_seq, a.n_tickets = MOVE_KINDS["packed_states"], n, n_tickets
+    a.tokens, a.pos, a.len, a.plant_tokens, a.plant_errors = (c.ctypes.data for c in cols)
+    a.samplers = C.cast(spx, C.c_void_p) if spx is not None else None
+    st = np.zeros(max(n, 1), STEP_STATE)
+    ss0, ss1 = np.zeros((max(n, 1), 16), np.uint32), np.zeros((max(n, 1), 16), np.uint32)
+    tk = np.zeros((max(n, 1), max(int(n_tickets), 0) + MOVE_ROWS_GUARD), np.uint32) if tickets else None
+    col = np.zeros(2 * max(n, 1) + 2 * MOVE_ROWS_GUARD, np.uint32)
+    launches = np.zeros(2, np.int32)
+    a.states_out, a.ss_init_out, a.ss_out, a.tickets_out, a.collect_out, a.launches_out = st.ctypes.data, ss0.ctypes.data, ss1.ctypes.data, _ptr(tk), col.ctypes.data, launches.ctypes.data
+    _check(lib().fl_op_move_rows(C.byref(a)))
+    return PackedStates(st, ss0, ss1, tk, col, tuple(int(x) for x in launches))
 
 
 class Model:

@@ -2432,4 +2432,315 @@ int fl_op_model_tensor(fl_model *m, int32_t shard, int32_t selector, int64_t lay
     });
 }
 
+// ---- token selection's step state and the row-moving launches -------------------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(fl_step_state) == sizeof(StepState) && offsetof(fl_step_state, eos) == offsetof(StepState, eos) &&
+              offsetof(fl_step_state, call0) == offsetof(StepState, call0), "fl_step_state is StepState");
+static_assert(sizeof(SampleState) == 64, "fl_move_rows_args::ss_out is 16 words per member");
+static_assert(sizeof(LogprobRec) == 4 * (1 + 2 * FL_LOGPROBS_MAX_TOP), "fl_select_rows_args::lp_records_out");
+constexpr size_t kGuard = FL_MOVE_ROWS_GUARD;
+
+// the fl_op_select_rows checks that need no device; ss: the members' token selection states
+int select_rows_check(const fl_select_rows_args *a, std::vector<SampleState> &ss) {
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: null args");
+    if (a->struct_size != sizeof(fl_select_rows_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_select_rows_args));
+    if (a->form < 0 || a->form > 2) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: form %d not in 0..2", a->form);
+    if (a->advance != 0 && a->advance != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: advance %d is neither 0 nor 1", a->advance);
+    if (!a->logits || !a->states || !a->states_out || !a->out_tokens) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: null argument (logits, states, states_out, out_tokens)");
+    if (a->B < 1 || a->B > kMaxBatch) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: B %lld not in 1..%d", (long long)a->B, kMaxBatch);
+    if (a->V < 1 || a->V > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: V %lld not in 1..2^24", (long long)a->V);
+    if (a->n_steps < 1 || a->n_steps > 64) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: n_steps %d not in 1..64", a->n_steps);
+    if (a->out_cap < 1 || a->out_cap > (1 << 16)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: out_cap %lld not in 1..2^16", (long long)a->out_cap);
+    if (a->lp_cap < 0 || a->lp_cap > 1024) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: lp_cap %lld not in 0..1024", (long long)a->lp_cap);
+    if (a->lp_cap > 0) {
+        if (!a->lp_records_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: null lp_records_out with lp_cap %lld", (long long)a->lp_cap);
+        if (a->top_n < 0 || a->top_n > FL_LOGPROBS_MAX_TOP || a->top_n > a->V)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: top_n %d not in 0..min(%d, V = %lld)", a->top_n, FL_LOGPROBS_MAX_TOP, (long long)a->V);
+    }
+    ss.resize((size_t)a->B);
+    for (int64_t b = 0; b < a->B; b++) {
+        // the kernel writes out_tokens[step] unbounded: every slot the launches can reach lies inside the member's buffer
+        if ((int64_t)a->states[b].step + a->n_steps > a->out_cap)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: member %lld: step %u + n_steps %d exceeds out_cap %lld", (long long)b, a->states[b].step, a->n_steps, (long long)a->out_cap);
+        FL_TRY(make_sampler(a->samplers ? a->samplers + b : nullptr, a->V, &ss[(size_t)b]));
+    }
+    if (a->form == 2) {
+        if (a->B != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: form 2 takes one member");
+        if (ss[0].on) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: form 2 is ArgMax: the candidates replace the vocabulary for no sampler");
+        if (!a->cand_values || !a->cand_indices) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: form 2: null argument (cand_values, cand_indices)");
+        if (a->cand_count < 1 || a->cand_count > kMaxArgmaxCand - 1)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: cand_count %lld not in 1..%d", (long long)a->cand_count, kMaxArgmaxCand - 1);
+        for (int64_t i = 0; i < a->cand_count; i++)
+            if (a->cand_indices[i] < 0 || a->cand_indices[i] >= a->V)
+                FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_select_rows: cand_indices[%lld] = %d is not in 0..V-1", (long long)i, a->cand_indices[i]);
+    }
+    return FL_OK;
+}
+
+// the fl_op_move_rows checks that need no device; *payload: the destination's words between its guard bands (kind 4: per shard)
+int move_rows_check(const fl_move_rows_args *a, int64_t *payload, int64_t *T_total) {
+    const int64_t kMax = (int64_t)1 << 26;
+    if (!a) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: null args");
+    if (a->struct_size != sizeof(fl_move_rows_args)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: struct_size %zu, expected %zu", a->struct_size, sizeof(fl_move_rows_args));
+    if (a->kind < 0 || a->kind > 5) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind %d not in 0..5", a->kind);
+    auto in = [&](int64_t v, int64_t hi) { return v >= 1 && v <= hi; };
+    *T_total = 0;
+    switch (a->kind) {
+    case 0: case 1:
+        if (a->dtype != FL_DTYPE_BF16 && a->dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: dtype must be bf16 or f32");
+        if (!a->table || !a->ids) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind %d: null argument (table, ids)", a->kind);
+        if (!in(a->rows, 1024) || !in(a->h, 65536) || !in(a->vocab, 1 << 24) || a->vocab * a->h > kMax)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind %d: rows %lld in 1..1024, h in 1..65536, vocab * h up to 2^26", a->kind, (long long)a->rows);
+        if (a->h % 8) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_move_rows: kind %d: the embedding kernels take a hidden size that is a multiple of 8, not %lld", a->kind, (long long)a->h);
+        if (a->kind == 0 && a->use_state && a->rows != 1) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: use_state takes one row");
+        for (int64_t t = 0; t < a->rows; t++)
+            if ((int64_t)a->ids[t] >= a->vocab) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: ids[%lld] = %u is not below vocab %lld", (long long)t, a->ids[t], (long long)a->vocab);
+        *payload = a->rows * a->h;
+        break;
+    case 2:
+        if (!a->src) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 2: null src");
+        if (!in(a->tp, 64) || !in(a->rows, 1024) || !in(a->Vs, 1 << 24) || a->tp * a->rows * a->Vs > kMax)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 2: tp %lld in 1..64, rows %lld in 1..1024, tp * rows * Vs up to 2^26", (long long)a->tp, (long long)a->rows);
+        if (a->Vs % 4) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_move_rows: kind 2: a vocabulary shard of %lld is not a multiple of 4", (long long)a->Vs);
+        *payload = a->tp * a->rows * a->Vs;
+        break;
+    case 3:
+        if (!a->src || !a->counts) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 3: null argument (src, counts)");
+        if (!in(a->n_seq, 1024) || !in(a->h, 65536) || !in(a->n_slab, 64))
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 3: n_seq %lld in 1..1024, h in 1..65536, n_slab %lld in 1..64", (long long)a->n_seq, (long long)a->n_slab);
+        for (int64_t s = 0; s < a->n_seq; s++) {
+            if (a->counts[s] < 1 || a->counts[s] > (1 << 16)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 3: counts[%lld] = %d not in 1..2^16", (long long)s, a->counts[s]);
+            *T_total += a->counts[s];
+        }
+        if (a->src_slab < *T_total * a->h || a->dst_slab < a->n_seq * a->h || a->n_slab * a->src_slab > kMax || a->n_slab * a->dst_slab > kMax)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 3: a slab stride smaller than its rows (src %lld < %lld or dst %lld < %lld), or more than 2^26 words",
+                    (long long)a->src_slab, (long long)(*T_total * a->h), (long long)a->dst_slab, (long long)(a->n_seq * a->h));
+        if (a->h % 4) FL_FAIL(FL_ERR_UNSUPPORTED, "fl_op_move_rows: kind 3: hidden size %lld is not a multiple of 4", (long long)a->h);
+        *payload = a->n_slab * a->dst_slab;
+        break;
+    case 4:
+        if (!a->src) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 4: null src");
+        if (!in(a->nshards, 64)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 4: nshards %lld not in 1..64", (long long)a->nshards);
+        if (!in(a->n, kMax) || a->nshards * a->n > kMax) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 4: n %lld must be positive, nshards * n up to 2^26", (long long)a->n);
+        *payload = a->n;
+        break;
+    default:
+        if (!a->tokens || !a->pos || !a->len || !a->plant_tokens || !a->plant_errors || !a->states_out || !a->ss_init_out || !a->ss_out || !a->collect_out)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 5: null argument (tokens, pos, len, plant_tokens, plant_errors, states_out, ss_init_out, ss_out, collect_out)");
+        if (!in(a->n_seq, 1024)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 5: n_seq %lld not in 1..1024", (long long)a->n_seq);
+        if (a->n_tickets < 0 || a->n_tickets > 4096) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 5: n_tickets %lld not in 0..4096", (long long)a->n_tickets);
+        if (a->n_tickets > 0 && !a->tickets_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind 5: %lld tickets per member and no tickets_out: the kernel would zero through a null pointer", (long long)a->n_tickets);
+        *payload = 0;
+        return FL_OK;
+    }
+    if (!a->out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: null out");
+    const int64_t want = (a->kind == 4 ? a->nshards : 1) * (*payload + 2 * (int64_t)kGuard);
+    if (a->out_words != want) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_move_rows: kind %d: out_words %lld, the destination with its guard bands has %lld", a->kind, (long long)a->out_words, (long long)want);
+    return FL_OK;
+}
+
+// device words filled with the 0xff byte pattern: what no launch writes shows up
+int move_alloc_ff(OpScope &B, uint32_t **out, size_t words) {
+    FL_TRY(B.alloc(out, words * 4));
+    FL_HIP(hipMemset(*out, 0xff, words * 4));
+    return FL_OK;
+}
+
+// n step states and token selection states on the device under the 0xff pattern, and the pack's table over them (members of
+// counts[s] rows, plain caches: no attention item), built by the packed prefill's builder
+struct MovePack {
+    StepState *st = nullptr; SampleState *ss = nullptr;
+    PackedHost ph; void *tabd = nullptr;
+    int build(OpScope &B, const int32_t *counts, int64_t n) {
+        FL_TRY(move_alloc_ff(B, reinterpret_cast<uint32_t **>(&st), (size_t)n * sizeof(StepState) / 4));
+        FL_TRY(move_alloc_ff(B, reinterpret_cast<uint32_t **>(&ss), (size_t)n * sizeof(SampleState) / 4));
+        std::vector<SeqRef> refs((size_t)n, SeqRef{});
+        std::vector<int> cnt((size_t)n, 1), vt((size_t)n, 0);
+        for (int64_t s = 0; s < n; s++) { refs[(size_t)s].st = st + s; refs[(size_t)s].ss = ss + s; if (counts) cnt[(size_t)s] = counts[s]; }
+        packed_table_build(refs.data(), cnt.data(), vt.data(), (int)n, 1, 1, 64, &ph);
+        return B.upload(&tabd, ph.bytes.data(), ph.bytes.size());
+    }
+    PackedTable table() const { return ph.at(tabd); }
+};
+
+}  // namespace
+
+int fl_op_select_rows(const fl_select_rows_args *args) {
+    return guarded([&]() -> int {
+        std::vector<SampleState> ss;
+        FL_TRY(select_rows_check(args, ss));
+        const fl_select_rows_args &a = *args;
+        const size_t Bn = (size_t)a.B, V = (size_t)a.V, cap = (size_t)a.out_cap, lpc = (size_t)a.lp_cap, nrec = lpc ? lpc + 1 : 0;
+        OpScope B;
+        FL_TRY(B.begin());
+        float *lg, *sc; StepState *std_; SampleState *ssd; uint32_t *od, *kd = nullptr, *recs = nullptr;
+        ArgmaxCand *cd = nullptr; LogprobCtl *ctl = nullptr; const LogprobCtl **ctls = nullptr; SeqRef *refs_dev = nullptr;
+        FL_TRY(B.upload(&lg, a.logits, Bn * V * 4));
+        FL_TRY(B.alloc(&sc, Bn * V * 4));
+        FL_TRY(B.upload(&std_, a.states, Bn * sizeof(StepState)));
+        FL_TRY(B.upload(&ssd, ss.data(), Bn * sizeof(SampleState)));
+        FL_TRY(move_alloc_ff(B, &od, Bn * cap));
+        if (a.kept_out) FL_TRY(move_alloc_ff(B, &kd, Bn * (size_t)a.n_steps));
+        if (a.form == 1) {
+            std::vector<SeqRef> refs(Bn, SeqRef{});
+            for (size_t b = 0; b < Bn; b++) { refs[b].st = std_ + b; refs[b].ss = ssd + b; refs[b].out_tokens = od + b * cap; refs[b].sel_scratch = sc + b * V; }
+            FL_TRY(B.upload(&refs_dev, refs.data(), Bn * sizeof(SeqRef)));
+        }
+        if (a.form == 2) {
+            std::vector<ArgmaxCand> cand((size_t)a.cand_count + 1);
+            cand[0] = ArgmaxCand{0.f, (int)a.cand_count};
+            for (int64_t i = 0; i < a.cand_count; i++) cand[(size_t)i + 1] = ArgmaxCand{a.cand_values[i], a.cand_indices[i]};
+            FL_TRY(B.upload(&cd, cand.data(), cand.size() * sizeof(ArgmaxCand)));
+        }
+        if (lpc) {
+            FL_TRY(move_alloc_ff(B, &recs, Bn * nrec * sizeof(LogprobRec) / 4));
+            std::vector<LogprobCtl> ch(Bn);
+            std::vector<const LogprobCtl *> cp(Bn);
+            for (size_t b = 0; b < Bn; b++) ch[b] = LogprobCtl{reinterpret_cast<LogprobRec *>(recs) + b * nrec, (uint32_t)lpc, a.top_n};
+            FL_TRY(B.upload(&ctl, ch.data(), Bn * sizeof(LogprobCtl)));
+            for (size_t b = 0; b < Bn; b++) cp[b] = ctl + b;
+            FL_TRY(B.upload(&ctls, cp.data(), Bn * sizeof(LogprobCtl *)));
+        }
+        int launches[3] = {0, 0, 0};
+        // what the member's filter kept at this step: the word its launch left in its SampleState (no filter: every token is kept)
+        auto keep = [&](size_t b, int i) -> int {
+            if (kd && ss[b].filter) FL_HIP(hipMemcpyAsync(kd + b * (size_t)a.n_steps + (size_t)i, &ssd[b].kept, 4, hipMemcpyDeviceToDevice, B.s));
+            return FL_OK;
+        };
+        for (int i = 0; i < a.n_steps; i++) {
+            if (a.form == 1) {
+                FL_TRY(launch_select_advance_batch(B.L, lg, a.V, refs_dev, (int)a.B, a.advance)); launches[1]++;
+                for (size_t b = 0; b < Bn; b++) FL_TRY(keep(b, i));
+                if (lpc) {
+                    LogprobSrc src;
+                    src.seqs = refs_dev; src.ctls = ctls;
+                    FL_TRY(launch_token_logprobs(B.L, lg, a.V, (int)a.B, src, a.advance)); launches[2]++;
+                }
+                continue;
+            }
+            for (size_t b = 0; b < Bn; b++) {
+                FL_TRY(launch_select_advance(B.L, lg + b * V, a.V, std_ + b, ssd + b, sc + b * V, od + b * cap, a.advance, cd)); launches[0]++;
+                FL_TRY(keep(b, i));
+                if (lpc) {
+                    LogprobSrc src;
+                    src.st = std_ + b; src.ctl = ctl + b;
+                    FL_TRY(launch_token_logprobs(B.L, lg + b * V, a.V, 1, src, a.advance)); launches[2]++;
+                }
+            }
+        }
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(a.states_out, std_, Bn * sizeof(StepState), hipMemcpyDeviceToHost));
+        FL_HIP(hipMemcpy(a.out_tokens, od, Bn * cap * 4, hipMemcpyDeviceToHost));
+        if (kd) {
+            FL_HIP(hipMemcpy(a.kept_out, kd, Bn * (size_t)a.n_steps * 4, hipMemcpyDeviceToHost));
+            for (size_t b = 0; b < Bn; b++)
+                if (!ss[b].filter) std::fill(a.kept_out + b * (size_t)a.n_steps, a.kept_out + (b + 1) * (size_t)a.n_steps, (uint32_t)a.V);
+        }
+        if (lpc) FL_HIP(hipMemcpy(a.lp_records_out, recs, Bn * nrec * sizeof(LogprobRec), hipMemcpyDeviceToHost));
+        if (a.launches_out) memcpy(a.launches_out, launches, sizeof launches);
+        return FL_OK;
+    });
+}
+
+int fl_op_move_rows(const fl_move_rows_args *args) {
+    return guarded([&]() -> int {
+        int64_t payload = 0, T_total = 0;
+        FL_TRY(move_rows_check(args, &payload, &T_total));
+        const fl_move_rows_args &a = *args;
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t words = (size_t)payload + 2 * kGuard;
+        int launches[2] = {0, 0};
+        uint32_t *od = nullptr;
+        if (a.kind < 4) FL_TRY(move_alloc_ff(B, &od, words));
+        float *dst = reinterpret_cast<float *>(od + kGuard);
+        if (a.kind <= 1) {
+            const size_t es = a.dtype == FL_DTYPE_BF16 ? 2 : 4;
+            void *tab; uint32_t *ids = nullptr;
+            FL_TRY(B.upload(&tab, a.table, (size_t)a.vocab * a.h * es));
+            if (a.kind == 0 && !a.use_state) {
+                FL_TRY(B.upload(&ids, a.ids, (size_t)a.rows * 4));
+                FL_TRY(launch_embed(B.L, a.dtype, tab, ids, nullptr, dst, a.rows, a.h));
+            } else {
+                // the members' step states under the 0xff pattern but for the token; the SeqRef holds nothing else these kernels read
+                std::vector<StepState> sts((size_t)a.rows);
+                memset(sts.data(), 0xff, sts.size() * sizeof(StepState));
+                for (int64_t b = 0; b < a.rows; b++) sts[(size_t)b].token = a.ids[b];
+                StepState *std_; SeqRef *refs_dev;
+                FL_TRY(B.upload(&std_, sts.data(), sts.size() * sizeof(StepState)));
+                if (a.kind == 0) {
+                    FL_TRY(launch_embed(B.L, a.dtype, tab, nullptr, std_, dst, 1, a.h));
+                } else {
+                    std::vector<SeqRef> refs((size_t)a.rows, SeqRef{});
+                    for (int64_t b = 0; b < a.rows; b++) refs[(size_t)b].st = std_ + b;
+                    FL_TRY(B.upload(&refs_dev, refs.data(), refs.size() * sizeof(SeqRef)));
+                    FL_TRY(launch_embed_batch(B.L, tab, refs_dev, dst, (int)a.rows, a.h, a.dtype));
+                }
+            }
+            launches[0]++;
+        } else if (a.kind == 2) {
+            float *sd;
+            FL_TRY(B.upload(&sd, a.src, (size_t)payload * 4));
+            FL_TRY(launch_unshard_logits(B.L, sd, dst, (int)a.tp, (int)a.rows, a.Vs)); launches[0]++;
+        } else if (a.kind == 3) {
+            float *sd;
+            MovePack pk;
+            FL_TRY(B.upload(&sd, a.src, (size_t)(a.n_slab * a.src_slab) * 4));
+            FL_TRY(pk.build(B, a.counts, a.n_seq));
+            FL_TRY(launch_gather_last_rows(B.L, sd, pk.table(), dst, (int)a.n_seq, a.h, (int)a.n_slab, a.src_slab, a.dst_slab)); launches[0]++;
+        } else if (a.kind == 4) {
+            std::vector<float *> bufs((size_t)a.nshards);
+            float **tab;
+            for (int64_t k = 0; k < a.nshards; k++) {
+                uint32_t *w;
+                FL_TRY(move_alloc_ff(B, &w, words));
+                bufs[(size_t)k] = reinterpret_cast<float *>(w + kGuard);
+                FL_HIP(hipMemcpy(bufs[(size_t)k], a.src + (size_t)k * a.n, (size_t)a.n * 4, hipMemcpyHostToDevice));
+            }
+            FL_TRY(B.upload(&tab, bufs.data(), bufs.size() * sizeof(float *)));
+            FL_TRY(launch_reduce_shards(B.L, tab, (int)a.nshards, a.n)); launches[0]++;
+            FL_HIP(hipStreamSynchronize(B.s));
+            for (int64_t k = 0; k < a.nshards; k++)
+                FL_HIP(hipMemcpy(a.out + (size_t)k * words, reinterpret_cast<uint32_t *>(bufs[(size_t)k]) - kGuard, words * 4, hipMemcpyDeviceToHost));
+        } else {
+            const size_t n = (size_t)a.n_seq, nt = (size_t)a.n_tickets, tstride = nt + kGuard;
+            MovePack pk;
+            FL_TRY(pk.build(B, nullptr, a.n_seq));
+            uint32_t *tk = nullptr, *cd;
+            if (a.tickets_out) FL_TRY(move_alloc_ff(B, &tk, n * tstride));
+            std::vector<PackedSeqInit> init(n);
+            memset(init.data(), 0, n * sizeof(PackedSeqInit));
+            for (size_t s = 0; s < n; s++) {
+                init[s].heads_done = tk ? tk + s * tstride : nullptr;
+                init[s].token = a.tokens[s]; init[s].pos = a.pos[s]; init[s].len = a.len[s];
+                FL_TRY(make_sampler(a.samplers ? a.samplers + s : nullptr, 0, &init[s].ss));
+                memcpy(a.ss_init_out + s * 16, &init[s].ss, sizeof(SampleState));
+            }
+            PackedSeqInit *initd;
+            FL_TRY(B.upload(&initd, init.data(), n * sizeof(PackedSeqInit)));
+            FL_TRY(launch_packed_set_states(B.L, pk.table(), initd, (int)a.n_seq, (int)a.n_tickets)); launches[0]++;
+            FL_HIP(hipStreamSynchronize(B.s));
+            std::vector<StepState> sts(n);
+            FL_HIP(hipMemcpy(sts.data(), pk.st, n * sizeof(StepState), hipMemcpyDeviceToHost));
+            memcpy(a.states_out, sts.data(), n * sizeof(StepState));
+            FL_HIP(hipMemcpy(a.ss_out, pk.ss, n * sizeof(SampleState), hipMemcpyDeviceToHost));
+            if (tk) FL_HIP(hipMemcpy(a.tickets_out, tk, n * tstride * 4, hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < n; s++) { sts[s].token = a.plant_tokens[s]; sts[s].error = a.plant_errors[s]; }
+            FL_HIP(hipMemcpy(pk.st, sts.data(), n * sizeof(StepState), hipMemcpyHostToDevice));
+            FL_TRY(move_alloc_ff(B, &cd, 2 * n + 2 * kGuard));
+            FL_TRY(launch_packed_collect(B.L, pk.table(), cd + kGuard, (int)a.n_seq)); launches[1]++;
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(a.collect_out, cd, (2 * n + 2 * kGuard) * 4, hipMemcpyDeviceToHost));
+        }
+        if (a.kind < 4) {
+            FL_HIP(hipStreamSynchronize(B.s));
+            FL_HIP(hipMemcpy(a.out, od, words * 4, hipMemcpyDeviceToHost));
+        }
+        if (a.launches_out) memcpy(a.launches_out, launches, sizeof launches);
+        return FL_OK;
+    });
+}
+
 }  // extern "C"

@@ -304,6 +304,10 @@ int launch_rope_kv_batch(Launcher &L, const float *qkv, const SeqRef *seqs_dev, 
 // replayed back to back with no host round trip.
 //
 // argmax_reduce / argmax_last: argmax_dev.h (shared with k_verify_packed.hip)
+//
+// `done` is set and never cleared, and it stops nothing here: a launch on a state that is done selects, writes out_tokens[step] and
+// token and advances like any other (a captured graph replays whole; the host reads `done` and cuts the tokens).  out_tokens[step] is
+// not bounded by the kernel: the caller sizes the buffer for the steps it enqueues.
 
 // ArgMax over the candidates the lm_head launch left (GemvArgs::amax: one per workgroup, ties -> the larger index):
 // the same result as argmax_last over the logits they were taken from, without reading the vocabulary again

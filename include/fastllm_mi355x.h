@@ -1195,6 +1195,98 @@ int fl_op_verify_packed(const float *logits /* [T][V] */, int64_t T, int64_t V, 
 int fl_op_logprobs(const float *logits /* [T][V] */, int64_t T, int64_t V, const uint32_t *chosen /* [T] */, int32_t top_n,
                    float *token_logprob /* [T] */, uint32_t *top_ids /* [T][top_n] or NULL */, float *top_logprobs /* [T][top_n] or NULL */);
 
+/* ---- token selection's step state and the batch row kernels alone, on host arrays (unit tests) ------------------------------------ */
+
+/* The loop-carried state of one sequence as the device keeps it (eight words): what token selection reads and advances. */
+typedef struct fl_step_state {
+    uint32_t token, pos, len, step;
+    int32_t  eos;                   /* -1: none */
+    uint32_t done, error, call0;
+} fl_step_state;
+
+/* The token selection launches alone: B members, member b with row b of logits [B][V], its own state (states[b], taken as given:
+ * error and call0 too), its own sampler (samplers[b]; samplers NULL or a temperature < 1e-7: ArgMax), its own scratch and its own
+ * out_tokens buffer of out_cap slots.  The launch is repeated n_steps times on the same logits.
+ *   form 0  one launch_select_advance per member and step
+ *   form 1  one launch_select_advance_batch over the members per step
+ *   form 2  launch_select_advance with the candidate list the lm_head launch would leave: B = 1, ArgMax only, cand_count entries
+ *           (cand_values[i], cand_indices[i]); the logits row is passed but not read
+ * lp_cap > 0: each selection is followed by launch_token_logprobs in the matching state form (one sequence: its state and control
+ * block; a batch: the members' states and control blocks) with records of capacity lp_cap and top_n entries.
+ * Outputs, every device buffer filled with the 0xff byte pattern first and returned whole: states_out [B]; out_tokens [B][out_cap];
+ * kept_out (or NULL) [B][n_steps]: what the member's filter kept at each step (V without one); lp_records_out (with lp_cap > 0)
+ * [B][lp_cap + 1] records of 1 + 2 * FL_LOGPROBS_MAX_TOP words (the log-prob, the ids, their log-probs): the last one lies behind
+ * the capacity.  launches_out [3] (or NULL): launches of launch_select_advance, launch_select_advance_batch, launch_token_logprobs.
+ * A state keeps being selected into after `done`: the host stops a decode loop, the kernel does not.
+ * Decided before the device is probed, writing nothing: FL_ERR_BAD_ARGUMENT for null pointers, struct_size, form, advance other than
+ * 0 / 1, B outside 1..64, V outside 1..2^24, n_steps outside 1..64, out_cap outside 1..2^16, states[b].step + n_steps > out_cap (the
+ * kernel does not bound out_tokens[step]), lp_cap outside 0..1024, top_n outside 0..min(FL_LOGPROBS_MAX_TOP, V), a bad sampler, and in
+ * form 2 B != 1, a sampler that is on, cand_count outside 1..1023 or an index outside 0..V-1. */
+typedef struct fl_select_rows_args {
+    size_t struct_size;             /* sizeof(fl_select_rows_args) */
+    int32_t form, advance, n_steps, top_n;
+    int64_t B, V, out_cap, lp_cap;
+    const float *logits;            /* [B][V] */
+    const fl_step_state *states;    /* [B] */
+    const fl_sampler *samplers;     /* [B] or NULL */
+    const float *cand_values;       /* form 2: [cand_count] */
+    const int32_t *cand_indices;    /* form 2: [cand_count] */
+    int64_t cand_count;
+    fl_step_state *states_out;      /* [B] */
+    uint32_t *out_tokens;           /* [B][out_cap] */
+    uint32_t *kept_out;             /* [B][n_steps] or NULL */
+    uint32_t *lp_records_out;       /* [B][lp_cap + 1][1 + 2 * FL_LOGPROBS_MAX_TOP], with lp_cap > 0 */
+    int32_t *launches_out;          /* [3] or NULL */
+} fl_select_rows_args;
+int fl_op_select_rows(const fl_select_rows_args *args);
+
+/* The launches that move rows and step states between the arithmetic kernels, each alone.  Every destination is device memory of
+ * 32-bit words with FL_MOVE_ROWS_GUARD words in front of and behind it, all filled with the 0xff byte pattern before the launch and
+ * returned whole: out holds out_words = guard + payload + guard words (kind 4: per shard).
+ *   kind 0  launch_embed: table [vocab][h] in `dtype`, ids [rows] -> payload [rows][h] fp32.  use_state = 1: rows = 1 and the id is
+ *           read from a step state's token instead of the ids array on the device.
+ *   kind 1  launch_embed_batch: the same with member b's id in its own step state -> [rows][h]
+ *   kind 2  launch_unshard_logits: src [tp][rows][Vs] -> payload [rows][tp * Vs]
+ *   kind 3  launch_gather_last_rows: member s owns counts[s] rows of a pack of sum(counts) rows; src holds n_slab slabs of
+ *           [sum(counts)][h], src_slab floats apart -> payload n_slab slabs of [n_seq][h], dst_slab floats apart (n_slab * dst_slab words)
+ *   kind 4  launch_reduce_shards: src [nshards][n], one device buffer per shard -> [nshards] x (guard + n + guard)
+ *   kind 5  launch_packed_set_states, then launch_packed_collect: member s starts from (tokens[s], pos[s], len[s], samplers[s]) over a
+ *           state and a sampler filled with 0xff.  states_out [n_seq]: the states the first launch left; ss_init_out / ss_out
+ *           [n_seq][16]: the words of the member's token selection state as built on the host and as the device holds it;
+ *           tickets_out [n_seq][n_tickets + guard] (NULL only with n_tickets == 0: the kernel then gets a null pointer); then
+ *           plant_tokens[s] / plant_errors[s] are written into the states, and collect_out [guard + 2 * n_seq + guard] is what
+ *           launch_packed_collect gathers.  out is not used.
+ * The table of a pack (kinds 3 and 5) is built by the packed prefill's own builder.  launches_out [2] (or NULL): launches of the
+ * kind's launcher, and of launch_packed_collect.
+ * Decided before the device is probed, writing nothing: FL_ERR_BAD_ARGUMENT (null pointers, struct_size, kind, dtype, sizes that are
+ * not positive or above 2^26 words, rows / n_seq above 1024, an id >= vocab, use_state with rows != 1, counts below 1, a slab
+ * stride smaller than its rows, tp outside 1..64, nshards outside 1..64, n_tickets outside 0..4096 or > 0 with null tickets_out, an
+ * out_words that is not the size above) and FL_ERR_UNSUPPORTED (kinds 0, 1: h not a multiple of 8; kind 2: Vs not a multiple of 4;
+ * kind 3: h not a multiple of 4). */
+#define FL_MOVE_ROWS_GUARD 64
+typedef struct fl_move_rows_args {
+    size_t struct_size;             /* sizeof(fl_move_rows_args) */
+    int32_t kind, dtype, use_state, reserved;
+    int64_t rows, h, vocab;         /* kinds 0, 1; rows: kind 2 too; h: kind 3 too */
+    int64_t tp, Vs;                 /* kind 2 */
+    int64_t n_seq, n_slab, src_slab, dst_slab;   /* kind 3; n_seq: kind 5 too */
+    int64_t nshards, n;             /* kind 4 */
+    int64_t n_tickets;              /* kind 5 */
+    const void *table;              /* kinds 0, 1 */
+    const uint32_t *ids;            /* kinds 0, 1: [rows] */
+    const float *src;               /* kinds 2, 3, 4 */
+    const int32_t *counts;          /* kind 3: [n_seq] */
+    const uint32_t *tokens, *pos, *len;             /* kind 5: [n_seq] each */
+    const fl_sampler *samplers;     /* kind 5: [n_seq] or NULL */
+    const uint32_t *plant_tokens, *plant_errors;    /* kind 5: [n_seq] each */
+    int64_t out_words;
+    uint32_t *out;                  /* kinds 0 to 4 */
+    fl_step_state *states_out;      /* kind 5 */
+    uint32_t *ss_init_out, *ss_out, *tickets_out, *collect_out;   /* kind 5 */
+    int32_t *launches_out;          /* [2] or NULL */
+} fl_move_rows_args;
+int fl_op_move_rows(const fl_move_rows_args *args);
+
 /* The scoring kernel of fl_forward_score / fl_batch_score alone, on host logits (unit tests, micro-benchmarks): row t's target is
  * targets[t] (FL_SCORE_NO_TARGET: none).  1 <= T <= 1024, 0 <= top_n <= min(FL_LOGPROBS_MAX_TOP, V), V <= 1 << 24, targets[t] < V or
  * the sentinel (FL_ERR_BAD_ARGUMENT otherwise, before the device is probed); target_rank may be NULL, top_ids / top_logprobs when

@@ -481,6 +481,92 @@ pub struct fl_convert_slice_args {
     pub dst: *mut c_void,
 }
 
+/// `fl_step_state`: the loop-carried state of one sequence as the device keeps it (fl_op_select_rows / fl_op_move_rows, unit tests).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct fl_step_state {
+    pub token: u32,
+    pub pos: u32,
+    pub len: u32,
+    pub step: u32,
+    pub eos: i32,
+    pub done: u32,
+    pub error: u32,
+    pub call0: u32,
+}
+
+/// `fl_select_rows_args`: the token selection launches alone on host arrays (fl_op_select_rows, unit tests); `struct_size` is
+/// `size_of::<fl_select_rows_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_select_rows_args {
+    pub struct_size: usize,
+    pub form: i32,
+    pub advance: i32,
+    pub n_steps: i32,
+    pub top_n: i32,
+    pub b: i64,
+    pub v: i64,
+    pub out_cap: i64,
+    pub lp_cap: i64,
+    pub logits: *const f32,
+    pub states: *const fl_step_state,
+    pub samplers: *const fl_sampler,
+    pub cand_values: *const f32,
+    pub cand_indices: *const i32,
+    pub cand_count: i64,
+    pub states_out: *mut fl_step_state,
+    pub out_tokens: *mut u32,
+    pub kept_out: *mut u32,
+    pub lp_records_out: *mut u32,
+    pub launches_out: *mut i32,
+}
+
+/// The guard band, in 32-bit words, on either side of every destination `fl_op_move_rows` returns.
+pub const FL_MOVE_ROWS_GUARD: i32 = 64;
+
+/// `fl_move_rows_args`: the launches that move rows and step states between the arithmetic kernels, each alone on host arrays
+/// (fl_op_move_rows, unit tests); `struct_size` is `size_of::<fl_move_rows_args>()`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct fl_move_rows_args {
+    pub struct_size: usize,
+    pub kind: i32,
+    pub dtype: i32,
+    pub use_state: i32,
+    pub reserved: i32,
+    pub rows: i64,
+    pub h: i64,
+    pub vocab: i64,
+    pub tp: i64,
+    pub vs: i64,
+    pub n_seq: i64,
+    pub n_slab: i64,
+    pub src_slab: i64,
+    pub dst_slab: i64,
+    pub nshards: i64,
+    pub n: i64,
+    pub n_tickets: i64,
+    pub table: *const c_void,
+    pub ids: *const u32,
+    pub src: *const f32,
+    pub counts: *const i32,
+    pub tokens: *const u32,
+    pub pos: *const u32,
+    pub len: *const u32,
+    pub samplers: *const fl_sampler,
+    pub plant_tokens: *const u32,
+    pub plant_errors: *const u32,
+    pub out_words: i64,
+    pub out: *mut u32,
+    pub states_out: *mut fl_step_state,
+    pub ss_init_out: *mut u32,
+    pub ss_out: *mut u32,
+    pub tickets_out: *mut u32,
+    pub collect_out: *mut u32,
+    pub launches_out: *mut i32,
+}
+
 // fl_model_tensor_sel: the device tensors fl_op_model_tensor copies out; FL_ELEM_E4M3: the element code of the *_Q tensors
 pub const FL_ELEM_E4M3: i32 = 3;
 pub const FL_MT_EMBED: i32 = 0;
@@ -1205,6 +1291,8 @@ extern "C" {
     pub fn fl_op_attn_oproj_rep(args: *const fl_attn_oproj_rep_args) -> c_int;
     pub fn fl_op_encoder_rows(args: *const fl_encoder_rows_args) -> c_int;
     pub fn fl_op_convert_slice(args: *const fl_convert_slice_args) -> c_int;
+    pub fn fl_op_select_rows(args: *const fl_select_rows_args) -> c_int;
+    pub fn fl_op_move_rows(args: *const fl_move_rows_args) -> c_int;
     pub fn fl_op_model_tensor(
         m: *mut fl_model,
         shard: i32,
