@@ -16,8 +16,8 @@ F32, BF16, F16 = 0, 1, 2
 TP_NONE, TP_SINGLE_PROCESS, TP_MULTI_PROCESS, TP_EMULATED = 0, 1, 2, 3
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
-WEIGHTS_COMPUTE_DTYPE, WEIGHTS_E4M3_ROW = 0, 1
-DECODE_WEIGHTS = {None: WEIGHTS_COMPUTE_DTYPE, "compute": WEIGHTS_COMPUTE_DTYPE, "e4m3": WEIGHTS_E4M3_ROW}
+WEIGHTS_COMPUTE_DTYPE, WEIGHTS_E4M3_ROW, WEIGHTS_MXFP4 = 0, 1, 2
+DECODE_WEIGHTS = {None: WEIGHTS_COMPUTE_DTYPE, "compute": WEIGHTS_COMPUTE_DTYPE, "e4m3": WEIGHTS_E4M3_ROW, "mxfp4": WEIGHTS_MXFP4}
 
 
 class FastLLMError(RuntimeError):
@@ -433,6 +433,8 @@ def lib():
         L.fl_op_qkv_rope.argtypes = [C.POINTER(FlQkvRopeArgs)]
         L.fl_op_attn_oproj_rep.argtypes = [C.POINTER(FlAttnOprojRepArgs)]
         L.fl_op_gemv_w8.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
+        L.fl_op_quantize_mx4.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, vp, vp]
+        L.fl_op_gemv_w4.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_op_linear_w8.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
         L.fl_op_linear_w8_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
         L.fl_op_linear_w8_wide.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
@@ -1076,7 +1078,8 @@ def op_packed_states(tokens, pos, lens, n_tickets, plant_tokens, plant_errors, s
 class Model:
     """fl_model handle.  tensors: dict name -> numpy array (float32 / float16 / uint16 bf16 bits), or
     name -> (device_ptr, dtype_code, shape, device_ordinal) for tensors already in HBM.
-    decode_weights: None / "compute" (fl_model_create) or "e4m3" (FL_WEIGHTS_E4M3_ROW: the decode step streams FP8 weights; an int
+    decode_weights: None / "compute" (fl_model_create), "e4m3" (FL_WEIGHTS_E4M3_ROW: the decode step streams FP8 weights) or
+    "mxfp4" (FL_WEIGHTS_MXFP4: the decode step streams e2m1 weights with one e8m0 scale per 32; an int
     is passed through as the fl_weight_format value)."""
 
     def __init__(self, cfg, tensors, dtype="bf16", tp_mode=TP_NONE, tp_size=1, tp_rank=0, device_ids=None,
@@ -1888,6 +1891,34 @@ def op_gemv_w8(x, q, s, bias=None, epilogue=0, iters=0):
     b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
     ms = C.c_double(0.0)
     _check(lib().fl_op_gemv_w8(x.ctypes.data, q.ctypes.data, s.ctypes.data, b.ctypes.data if b is not None else None, N, K,
+                               epilogue, y.ctypes.data, iters, C.byref(ms)))
+    return (y, ms.value) if iters else y
+
+
+def op_quantize_mx4(w):
+    """The MXFP4 quantiser (device kernel) on a host matrix w [N,K], float32 or uint16 (bf16 bits), K a multiple of 32: returns
+    (q uint8 [N,K/2]: element 2j in the low nibble of byte j, e uint8 [N,K/32] of e8m0 block scales)."""
+    w = np.ascontiguousarray(w)
+    N, K = w.shape
+    q = np.empty((N, K // 2), dtype=np.uint8)
+    e = np.empty((N, K // 32), dtype=np.uint8)
+    _check(lib().fl_op_quantize_mx4(w.ctypes.data, _np_dtype_code(w), N, K, q.ctypes.data, e.ctypes.data))
+    return q, e
+
+
+def op_gemv_w4(x, q, e, bias=None, epilogue=0, iters=0):
+    """y[N] = sum over blocks of 2^(e - 127) * (q . x) (+bias) through the MXFP4 decode weight stream.  x [K] uint16 (bf16 bits),
+    q [N,K/2] uint8 (two e2m1 to a byte), e [N,K/32] uint8 (e8m0), both in the logical layouts; epilogue 1: rows are gate | up in HF
+    order, y is [N/2]."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    e = np.ascontiguousarray(e, dtype=np.uint8)
+    N, K = q.shape[0], x.shape[0]
+    assert q.shape == (N, K // 2) and e.shape == (N, K // 32)
+    y = np.empty(N // 2 if epilogue == 1 else N, dtype=np.float32)
+    b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_gemv_w4(x.ctypes.data, q.ctypes.data, e.ctypes.data, b.ctypes.data if b is not None else None, N, K,
                                epilogue, y.ctypes.data, iters, C.byref(ms)))
     return (y, ms.value) if iters else y
 

@@ -110,7 +110,12 @@ int fl_model_get_info(const fl_model *m, fl_model_info *out) {
             const int64_t rows = D.h + 2 * D.Hkv * D.dm + D.h + 2 * D.inter + D.h;      // q | k, v | o | gate, up | down
             out->weight_bytes_per_token = D.L * (per_layer + 4 * rows + es * small) + es * D.h + D.V * D.h + 4 * D.V;
         }
-        out->kv_bytes_per_position = es * D.L * D.Hkv * D.dm * 2;
+        if (mm->decode_weights == FL_WEIGHTS_MXFP4) {
+            // what the MXFP4 step streams: K/2 + K/32 bytes per projection row (two weights to a byte, one scale byte per 32); the
+            // embedding row, norms and biases as before
+            out->weight_bytes_per_token = D.L * (per_layer * 17 / 32 + es * small) + es * D.h + D.V * D.h * 17 / 32;
+        }
+        out->kv_bytes_per_position =es * D.L * D.Hkv * D.dm * 2;
         out->hbm_bytes_allocated = mm->hbm_bytes;
         // + the GEMM workspaces of each shard's streams (first long prompt).  The workspace tables are keyed by (current device,
         // stream): the calling thread's device is put back afterwards, and forward() is kept out meanwhile (it sets devices too).

@@ -1300,6 +1300,73 @@ int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *
     });
 }
 
+int fl_op_quantize_mx4(const void *w, int32_t dtype, int64_t N, int64_t K, uint8_t *q_out, uint8_t *e_out) {
+    return guarded([&]() -> int {
+        if (!w || !q_out || !e_out) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (dtype != FL_DTYPE_BF16 && dtype != FL_DTYPE_F32) FL_FAIL(FL_ERR_UNSUPPORTED, "dtype must be bf16 or f32");
+        if (N <= 0 || K <= 0 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape");
+        if (K % 32) FL_FAIL(FL_ERR_UNSUPPORTED, "K must be a multiple of 32 (one MX block)");
+        OpScope B;
+        FL_TRY(B.begin());
+        const size_t es = dtype == FL_DTYPE_BF16 ? 2 : 4;
+        void *wd; uint8_t *qd, *ed;
+        FL_TRY(B.upload(&wd, w, (size_t)N * K * es));
+        FL_TRY(B.alloc(&qd, (size_t)N * (K / 2)));
+        FL_TRY(B.alloc(&ed, (size_t)N * (K / 32)));
+        FL_TRY(launch_quantize_mx4(B.L, dtype, wd, N, K, qd, ed, false, nullptr));
+        FL_HIP(hipStreamSynchronize(B.s));
+        FL_HIP(hipMemcpy(q_out, qd, (size_t)N * (K / 2), hipMemcpyDeviceToHost));
+        FL_HIP(hipMemcpy(e_out, ed, (size_t)N * (K / 32), hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
+int fl_op_gemv_w4(const void *x, const uint8_t *q, const uint8_t *e, const float *bias, int64_t N, int64_t K, int32_t epilogue,
+                  float *y, int32_t iters, double *ms_out) {
+    return guarded([&]() -> int {
+        if (!x || !q || !e || !y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (N <= 0 || K <= 0 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape");
+        if (epilogue != EPI_F32 && epilogue != EPI_GATEUP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "epilogue must be 0 or 1");
+        if (epilogue == EPI_GATEUP && ((N % 2) || bias)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count and takes no bias");
+        if (!gemv_w4_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "K must be a multiple of 32 (a lane of the MXFP4 stream loads one block of 32 weights), at most 81792");
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t I = N / 2, Ip = (I + 15) / 16 * 16;
+        const int64_t Nw = epilogue == EPI_GATEUP ? 2 * Ip : N;          // rows of the device matrix
+        const int64_t Ny = epilogue == EPI_GATEUP ? Ip : N;
+        // one working set: the nibbles, then (256-byte aligned) the scale stream in the kernel's order
+        const size_t qbytes = ((size_t)Nw * (K / 2) + 255) & ~(size_t)255, ebytes = (size_t)Nw * mx4_scale_stride(K);
+        const size_t wbytes = qbytes + ebytes, ybytes = (size_t)Ny * (epilogue == EPI_GATEUP ? 2 : 4);
+        void *xd, *yd; uint8_t *wd, *qs, *es; float *bd = nullptr;
+        FL_TRY(B.upload(&xd, x, (size_t)K * 2));
+        FL_TRY(B.upload(&qs, q, (size_t)N * (K / 2)));
+        FL_TRY(B.upload(&es, e, (size_t)N * (K / 32)));
+        FL_TRY(B.alloc(&wd, wbytes));
+        FL_TRY(B.alloc(&yd, ybytes));
+        if (bias) FL_TRY(B.upload(&bd, bias, (size_t)N * 4));
+        FL_HIP(hipMemsetAsync(wd, 0, qbytes, B.s));                      // padding rows: zeros under the scale 2^0
+        FL_HIP(hipMemsetAsync(wd + qbytes, 127, ebytes, B.s));
+        FL_TRY(launch_mx4_layout(B.L, qs, es, N, epilogue == EPI_GATEUP ? I : 0, K, wd, wd + qbytes));
+        std::vector<const uint8_t *> Q{wd};                              // the copies of the working set a timed run rotates over
+        auto make = [&](int) -> int {
+            uint8_t *p;
+            FL_TRY(B.alloc(&p, wbytes));
+            FL_HIP(hipMemcpyAsync(p, wd, wbytes, hipMemcpyDeviceToDevice, B.s));
+            Q.push_back(p);
+            return FL_OK;
+        };
+        auto run = [&](int c) -> int {
+            GemvArgs a;
+            a.W = Q[(size_t)c]; a.x = xd; a.bias = bd; a.out = yd; a.N = (int)Nw; a.K = (int)K; a.epi = epilogue; a.pro = PRO_X;
+            return launch_gemv_w4(B.L, a, Q[(size_t)c] + qbytes);
+        };
+        FL_TRY(op_run(B, wbytes, iters, ms_out, make, run));
+        if (epilogue == EPI_GATEUP) return op_download(y, yd, (size_t)I, FL_DTYPE_BF16);                    // without the padding columns
+        FL_HIP(hipMemcpy(y, yd, ybytes, hipMemcpyDeviceToHost));
+        return FL_OK;
+    });
+}
+
 // the slabs an op-level launch may leave: where the model would allow them, as fl_op_linear
 static int op_linear_w8_split(int64_t T, int32_t epilogue, bool bias) {
     const int op_split = tune(TK_OP_MAXSPLIT);
@@ -2390,6 +2457,9 @@ int fl_op_model_tensor(fl_model *m, int32_t shard, int32_t selector, int64_t lay
         if (selector < FL_MT_EMBED || selector > FL_MT_LM_HEAD_S) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: unknown selector %d", selector);
         const bool per_layer = (selector >= FL_MT_WQKV && selector <= FL_MT_LN2) || (selector >= FL_MT_WQKV_Q && selector <= FL_MT_WD_S);
         if (per_layer && (layer < 0 || layer >= mm->D.L)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: layer %lld not below %lld", (long long)layer, (long long)mm->D.L);
+        // an MXFP4 model's byte pointers hold nibbles [rows][K/2] and its scale stream is in the kernel's own order: neither is a logical tensor
+        if (mm->decode_weights == FL_WEIGHTS_MXFP4 && selector >= FL_MT_WQKV_Q)
+            FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_op_model_tensor: an FL_WEIGHTS_MXFP4 model has no tensor for selector %d (its nibbles and scale stream are not logical tensors)", selector);
         const Dims &D = mm->D;
         Shard &sh = mm->shards[(size_t)shard];
         const LayerW none, &ly = per_layer ? sh.layers[(size_t)layer] : none;

@@ -140,6 +140,21 @@ int launch_quantize_rows(Launcher &L, int src_dtype, const void *src, int64_t N,
 // rows in HF order (gate [0, I) | up [I, 2 I)) -> the 16-interleaved decode layout (test hook)
 int launch_w8_gateup_layout(Launcher &L, const uint8_t *q, const float *s, int64_t I, int64_t K, uint8_t *qo, float *so);
 
+// ---- MXFP4 weights (k_gemv_w4.hip): W' = 2^e[row, k / 32] * q, q e2m1 two to a byte, e an e8m0 byte per 32 k (FL_WEIGHTS_MXFP4) ----
+// the decode stream over them: GemvArgs as for launch_gemv_w8 with W = the nibbles [N, K/2] and escale = the scale STREAM
+// (N x mx4_scale_stride(K) bytes in the kernel's own order: see the file's header); PRO_X / PRO_NORM, no fused all-reduce, no sliced delta
+int launch_gemv_w4(Launcher &L, const GemvArgs &a, const uint8_t *escale);
+bool gemv_w4_supported(int64_t N, int64_t K);          // K a multiple of 32 (a lane's 16-byte load: one block)
+bool gemv_w4_norm_supported(int64_t N, int64_t K);
+bool gemv_w4_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgMax candidate buffer
+int64_t mx4_scale_stride(int64_t K);                   // bytes of one row in the scale stream (>= K / 32)
+// src [N,K] bf16 / fp32 -> q [N, K/2], e (e_stream: the scale stream; else the logical [N, K/32]) and (img non-null; may be src
+// when that is bf16) the bf16 image 2^e * q
+int launch_quantize_mx4(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, uint8_t *e, bool e_stream, void *img_bf16);
+// logical q [N, K/2], e [N, K/32] -> device rows and scale stream (test hook); I > 0: N = 2 I rows gate | up in HF order -> the
+// 16-interleaved decode layout.  The caller zeroes qo's padding rows and fills eo with 127 first.
+int launch_mx4_layout(Launcher &L, const uint8_t *q, const uint8_t *e, int64_t N, int64_t I, int64_t K, uint8_t *qo, uint8_t *eo);
+
 // k_kvcopy.hip: a 2-D byte copy on the device, `rows` rows of `width` bytes (a multiple of 2) with a source and a destination pitch
 // (multiples of 16, >= width; 16-byte aligned bases).  launch_kv_copy moves two such jobs -- the K and the V prefix of a cache -- in
 // ONE launch and writes exactly the bytes [0, width) of every destination row.  kv_copy_check (the shape alone, no pointers): FL_ERR_BAD_ARGUMENT for anything else.

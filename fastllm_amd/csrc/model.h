@@ -36,6 +36,9 @@ struct LayerW {
     // above then hold the bf16 image s * q
     uint8_t *wqkv8 = nullptr, *wo8 = nullptr, *wgu8 = nullptr, *wd8 = nullptr;
     float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
+    // FL_WEIGHTS_MXFP4: the *8 pointers hold the e2m1 nibbles [rows, K/2], these the e8m0 scale streams (k_gemv_w4.hip's own order,
+    // mx4_scale_stride(K) bytes per row); the fp32 row scales stay null
+    uint8_t *eqkv = nullptr, *eo = nullptr, *egu = nullptr, *ed = nullptr;
 };
 
 struct Scratch {                 // activations of one forward chunk on one shard
@@ -136,6 +139,7 @@ struct Shard {
     void *lm_head = nullptr;     // [Vs,h]
     uint8_t *lm_head8 = nullptr; // FL_WEIGHTS_E4M3_ROW: its e4m3 bytes and row scales (lm_head is then the bf16 image)
     float *lm_head_s = nullptr;
+    uint8_t *lm_head_e = nullptr; // FL_WEIGHTS_MXFP4: lm_head8 holds the e2m1 nibbles, this the e8m0 scale stream
     float *cos_tab = nullptr, *sin_tab = nullptr;   // [max_pos][d/2]
     Scratch dec, pre;
     PackedScratch packed;
@@ -175,7 +179,7 @@ struct Model {
     ScoreRec *host_verify_recs = nullptr;   // pinned [kVerifyMaxRows]: ... and its log-prob records (fl_forward_verify_lp)
     bool use_graph = true;
     bool fused_decode = true;    // norm / RoPE / KV-append fused into the GEMV kernels
-    int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;   // FL_WEIGHTS_E4M3_ROW: the decode step streams e4m3 weights (k_gemv_w8.hip)
+    int decode_weights = FL_WEIGHTS_COMPUTE_DTYPE;   // FL_WEIGHTS_E4M3_ROW: the decode step streams e4m3 weights (k_gemv_w8.hip); FL_WEIGHTS_MXFP4: e2m1 nibbles and e8m0 block scales (k_gemv_w4.hip)
     int engine = -1;             // persistent decode engine (k_engine.hip): 0 off, 1 on, -1 automatic
     int fuse_oproj = 0;          // decode attention + o_proj in one launch (k_attn_oproj.hip): 0 never (default), 1 wherever it fits, -1 where it pays most
     StepState *host_state = nullptr;   // pinned: device step state read back for the error word

@@ -358,16 +358,19 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
     const int dt = m->dtype;
     const bool far = fused_all_reduce(m, c);
     // FL_WEIGHTS_E4M3_ROW (one shard, bf16: model_create): all six projections stream the e4m3 bytes (k_gemv_w8.hip)
-    const bool w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW;
-    auto gemv = [&](Launcher &L, GemvArgs &a, const uint8_t *q8, const float *s8) -> int {
+    // FL_WEIGHTS_MXFP4 (the same models): the same six launches on the e2m1 nibbles and their scale stream (k_gemv_w4.hip); below,
+    // `w8` stands for either -- the byte pointers hold whichever the model was built with
+    const bool w4 = m->decode_weights == FL_WEIGHTS_MXFP4;
+    const bool w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW || w4;
+    auto gemv = [&](Launcher &L, GemvArgs &a, const uint8_t *q8, const float *s8, const uint8_t *e4) -> int {
         if (!w8) return launch_gemv(L, dt, a);
         a.W = q8;
-        return launch_gemv_w8(L, a, s8);
+        return w4 ? launch_gemv_w4(L, a, e4) : launch_gemv_w8(L, a, s8);
     };
-    auto plain_w8 = [&](Launcher &L, const uint8_t *q8, const float *s8, const void *x, int64_t K, float *out) -> int {
+    auto plain_w8 = [&](Launcher &L, const uint8_t *q8, const float *s8, const uint8_t *e4, const void *x, int64_t K, float *out) -> int {
         GemvArgs a;
         a.W = q8; a.x = x; a.out = out; a.N = (int)D.h; a.K = (int)K; a.epi = EPI_F32; a.pro = PRO_X;
-        return launch_gemv_w8(L, a, s8);
+        return w4 ? launch_gemv_w4(L, a, e4) : launch_gemv_w8(L, a, s8);
     };
     // out = sum over ranks of W[h, K] . x  -- the row-parallel projection with the exchange in its epilogue
     auto row_parallel = [&](Launcher &L, Shard &sh, const void *W, const void *x, int64_t K, float *out, int slot) -> int {
@@ -398,7 +401,7 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             const KvLayer kv(m, c, sh, cs, l);
             GemvArgs a = qkv_gemv_args(m, c, sh, cs, kv, l);
             if (down_done) take_finished_norm(a, sc);
-            FL_TRY(gemv(L, a, ly.wqkv8, ly.sqkv));
+            FL_TRY(gemv(L, a, ly.wqkv8, ly.sqkv, ly.eqkv));
             AttnScratch as{cs.part_m, cs.part_l, cs.part_o, cs.counters, c->nsplit, len_hint + 1};
             if (!w8) {
                 as.prefetch = ly.wo; as.prefetch_bytes = D.h * sh.Hs * D.d * (int64_t)m->esize();   // o_proj's weights, while HBM idles under the attention
@@ -417,7 +420,7 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
                 FL_TRY(attend_decode(L, m, c, sh, cs, kv, sc.q, sc.ao, as));
                 o_done = edge_fits(sh.Hs * D.d, 2 * sh.Ip);
                 if (o_done) FL_TRY(producer(L, sc, ly.wo, sc.ao, sh.Hs * D.d, sc.x_res2, sc.x_res, ly.ln2));
-                else if (w8) FL_TRY(plain_w8(L, ly.wo8, ly.so, sc.ao, sh.Hs * D.d, sc.delta));
+                else if (w8) FL_TRY(plain_w8(L, ly.wo8, ly.so, ly.eo, sc.ao, sh.Hs * D.d, sc.delta));
                 else if (far) FL_TRY(row_parallel(L, sh, ly.wo, sc.ao, sh.Hs * D.d, sc.delta, (int)(2 * l + 1)));
                 else FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, 1, D.h, sh.Hs * D.d, EPI_F32));
             }
@@ -431,11 +434,11 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
             a.x_in = sc.x_res2; a.delta = sc.delta; a.norm_w = ly.ln2; a.eps = D.eps; a.x_out = sc.x_res; a.st = cs.st;
             if (c->fuse_oproj) a.delta_nslab = (int)sh.Hkvs;           // one partial vector per kv head
             if (o_done) take_finished_norm(a, sc);
-            FL_TRY(gemv(L, a, ly.wgu8, ly.sgu));
+            FL_TRY(gemv(L, a, ly.wgu8, ly.sgu, ly.egu));
             const bool last = l + 1 == D.L;
             down_done = edge_fits(sh.Ip, last ? sh.Vs : (sh.Hs + 2 * sh.Hkvs) * D.d);
             if (down_done) FL_TRY(producer(L, sc, ly.wd, sc.act, sh.Ip, sc.x_res, sc.x_res2, last ? sh.norm : sh.layers[l + 1].ln1));
-            else if (w8) FL_TRY(plain_w8(L, ly.wd8, ly.sd, sc.act, sh.Ip, sc.delta));
+            else if (w8) FL_TRY(plain_w8(L, ly.wd8, ly.sd, ly.ed, sc.act, sh.Ip, sc.delta));
             else if (far) FL_TRY(row_parallel(L, sh, ly.wd, sc.act, sh.Ip, sc.delta, (int)(2 * l + 2)));
             else FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, 1, D.h, sh.Ip, EPI_F32));
             return FL_OK;
@@ -446,10 +449,10 @@ static int enqueue_decode_fused(Model *m, Cache *c, int64_t len_hint) {
         Scratch &sc = sh.dec;
         GemvArgs a;
         a.W = sh.lm_head; a.out = lm_head_out(m, sh); a.N = (int)sh.Vs; a.K = (int)D.h; a.epi = EPI_F32; a.pro = PRO_NORM;
-        if (!m->vocab_parallel && tune(TK_ARGMAX_FUSED) && (w8 ? gemv_w8_leaves_candidates(a.N, a.K) : gemv_leaves_candidates(dt, a))) { a.amax = sh.amax; sh.amax_valid = true; }   // token selection reads one candidate per workgroup
+        if (!m->vocab_parallel && tune(TK_ARGMAX_FUSED) && (w4 ? gemv_w4_leaves_candidates(a.N, a.K) : w8 ? gemv_w8_leaves_candidates(a.N, a.K) : gemv_leaves_candidates(dt, a))) { a.amax = sh.amax; sh.amax_valid = true; }   // token selection reads one candidate per workgroup
         a.x_in = sc.x_res; a.delta = sc.delta; a.norm_w = sh.norm; a.eps = D.eps; a.st = cs.st;
         if (down_done) take_finished_norm(a, sc);
-        return gemv(L, a, sh.lm_head8, sh.lm_head_s);
+        return gemv(L, a, sh.lm_head8, sh.lm_head_s, sh.lm_head_e);
     }));
     return gather_logits(m);
 }

@@ -315,12 +315,21 @@ static int build_weights(Builder &B) {
 // FL_WEIGHTS_E4M3_ROW: every projection matrix (in its final decode layout: a row scale follows its row through every row
 // permutation) gets its e4m3 bytes and row scales, and the bf16 matrix itself becomes the image s * q -- what prefill, batches
 // and every other bf16 kernel then read.  Both images stay: 1.5x a bf16 model's weight memory.
+// FL_WEIGHTS_MXFP4: the same with the e2m1 nibbles in the byte pointers and an e8m0 scale stream (k_gemv_w4.hip's order) beside
+// them; blocks run along K, so the row permutations do not matter here either.  Nibbles, scales and image: 1.27x.
 static int quantize_weights(Model *m) {
     const Dims &D = m->D;
+    const bool mx4 = m->decode_weights == FL_WEIGHTS_MXFP4;
     for (auto &sh : m->shards) {
         FL_HIP(hipSetDevice(sh.device));
         Launcher L; L.stream = sh.stream;
-        auto one = [&](void *w, int64_t N, int64_t K, uint8_t **q, float **s) -> int {
+        auto one = [&](void *w, int64_t N, int64_t K, uint8_t **q, float **s, uint8_t **e) -> int {
+            if (mx4) {
+                if (!gemv_w4_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4: a %lld x %lld projection (K must be a multiple of 32)", (long long)N, (long long)K);
+                FL_TRY(dev_alloc(sh.allocs, (void **)q, (size_t)N * (K / 2), &m->hbm_bytes));
+                FL_TRY(dev_alloc(sh.allocs, (void **)e, (size_t)N * mx4_scale_stride(K), &m->hbm_bytes));
+                return launch_quantize_mx4(L, FL_DTYPE_BF16, w, N, K, *q, *e, true, w);
+            }
             if (!gemv_w8_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW: a %lld x %lld projection (K must be a multiple of 16)", (long long)N, (long long)K);
             FL_TRY(dev_alloc(sh.allocs, (void **)q, (size_t)N * K, &m->hbm_bytes));
             FL_TRY(dev_alloc(sh.allocs, (void **)s, (size_t)N * 4, &m->hbm_bytes));
@@ -328,12 +337,12 @@ static int quantize_weights(Model *m) {
         };
         const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
         for (auto &ly : sh.layers) {
-            FL_TRY(one(ly.wqkv, nq, D.h, &ly.wqkv8, &ly.sqkv));
-            FL_TRY(one(ly.wo, D.h, sh.Hs * D.d, &ly.wo8, &ly.so));
-            FL_TRY(one(ly.wgu, 2 * sh.Ip, D.h, &ly.wgu8, &ly.sgu));
-            FL_TRY(one(ly.wd, D.h, sh.Ip, &ly.wd8, &ly.sd));
+            FL_TRY(one(ly.wqkv, nq, D.h, &ly.wqkv8, &ly.sqkv, &ly.eqkv));
+            FL_TRY(one(ly.wo, D.h, sh.Hs * D.d, &ly.wo8, &ly.so, &ly.eo));
+            FL_TRY(one(ly.wgu, 2 * sh.Ip, D.h, &ly.wgu8, &ly.sgu, &ly.egu));
+            FL_TRY(one(ly.wd, D.h, sh.Ip, &ly.wd8, &ly.sd, &ly.ed));
         }
-        FL_TRY(one(sh.lm_head, sh.Vs, D.h, &sh.lm_head8, &sh.lm_head_s));
+        FL_TRY(one(sh.lm_head, sh.Vs, D.h, &sh.lm_head8, &sh.lm_head_s, &sh.lm_head_e));
         FL_HIP(hipStreamSynchronize(sh.stream));
     }
     return FL_OK;
@@ -446,7 +455,7 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
         if (opts->struct_size != sizeof(fl_model_options))
             FL_FAIL(FL_ERR_BAD_ARGUMENT, "fl_model_options.struct_size is %u, this library's is %zu", opts->struct_size, sizeof(fl_model_options));
         decode_weights = opts->decode_weights;
-        if (decode_weights != FL_WEIGHTS_COMPUTE_DTYPE && decode_weights != FL_WEIGHTS_E4M3_ROW)
+        if (decode_weights != FL_WEIGHTS_COMPUTE_DTYPE && decode_weights != FL_WEIGHTS_E4M3_ROW && decode_weights != FL_WEIGHTS_MXFP4)
             FL_FAIL(FL_ERR_BAD_ARGUMENT, "unknown decode_weights %d (fl_weight_format)", decode_weights);
     }
     if (decode_weights == FL_WEIGHTS_E4M3_ROW) {
@@ -455,6 +464,15 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
         // a lane of the FP8 stream loads 16 weights: every projection's K (hidden_size, heads x padded head_dim, intermediate_size
         // padded to 16) is a multiple of 16 once hidden_size is
         if (D.h % 16) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW needs hidden_size to be a multiple of 16 (it is %lld)", (long long)D.h);
+    }
+    if (decode_weights == FL_WEIGHTS_MXFP4) {
+        if (compute_dtype != FL_DTYPE_BF16) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4 needs compute dtype BF16 (2^e * q is exact in bf16, the fp32 mode has no use for it)");
+        if (par && par->mode != FL_TP_NONE && par->tp_size > 1) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4 does not support tensor parallelism (tp_size %d)", par->tp_size);
+        // a block is 32 consecutive k: of the projections' K, hidden_size and heads x padded head_dim (64 or 128) are multiples of
+        // 32 once hidden_size is; intermediate_size is padded to 16 only, so down_proj is checked on its own
+        if (D.h % 32) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4 needs hidden_size to be a multiple of 32 (it is %lld)", (long long)D.h);
+        const int64_t Ip = (D.inter + 15) / 16 * 16;
+        if (Ip % 32) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4 needs intermediate_size (down_proj's K, padded to 16: %lld) to be a multiple of 32", (long long)Ip);
     }
     debug_inject("model_create");
 
@@ -481,6 +499,8 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
     m->decode_weights = decode_weights;
     if (decode_weights == FL_WEIGHTS_E4M3_ROW && (!m->fused_decode || !gemv_w8_norm_supported(1, D.h)))
         FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW needs the fused decode step (FL_FUSED=0, or hidden_size %lld above 6144)", (long long)D.h);
+    if (decode_weights == FL_WEIGHTS_MXFP4 && (!m->fused_decode || !gemv_w4_norm_supported(1, D.h)))
+        FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4 needs the fused decode step (FL_FUSED=0, or hidden_size %lld above 6144)", (long long)D.h);
 
     auto dev_of = [&](int i) -> int { return (P.device_ids && i < P.n_device_ids) ? P.device_ids[i] : i; };
     int nlocal = 1;
@@ -523,7 +543,7 @@ int model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n, int c
         for (auto &sh : m->shards) { FL_HIP(hipSetDevice(sh.device)); FL_HIP(hipDeviceSynchronize()); }
     }
     FL_TRY(build_weights(B));
-    if (decode_weights == FL_WEIGHTS_E4M3_ROW) FL_TRY(quantize_weights(m.get()));
+    if (decode_weights != FL_WEIGHTS_COMPUTE_DTYPE) FL_TRY(quantize_weights(m.get()));
     FL_TRY(build_rope(m.get()));
     for (auto &sh : m->shards) {
         FL_HIP(hipSetDevice(sh.device));

@@ -151,8 +151,20 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
  * mode buys decode speed (half the bytes of the weight stream), not capacity.  Embedding and norm weights stay as they are.
  * REFUSED: compute_dtype other than BF16, tp_size > 1 (any mode), a model whose fused decode step is off (FL_FUSED=0, hidden_size
  * above 6144), hidden_size not a multiple of 16 -> FL_ERR_UNSUPPORTED; an unknown decode_weights or a struct_size that is not
- * sizeof(fl_model_options) -> FL_ERR_BAD_ARGUMENT.  All but the fused-step one are decided before the device probe. */
-typedef enum fl_weight_format { FL_WEIGHTS_COMPUTE_DTYPE = 0, FL_WEIGHTS_E4M3_ROW = 1 } fl_weight_format;
+ * sizeof(fl_model_options) -> FL_ERR_BAD_ARGUMENT.  All but the fused-step one are decided before the device probe.
+ *
+ * FL_WEIGHTS_MXFP4: the same design at 4.25 bits per weight (OCP microscaling: e2m1 elements, one e8m0 scale per 32).  A block is 32
+ * consecutive k of one row of a projection matrix.  Its scale is 2^e, e the smallest integer with absmax(block) / 2^e <= 6
+ * (absmax = m * 2^x, m in [0.5, 1): e = x - 3 if m <= 0.75, else x - 2), kept at -120 or above, 0 for an all-zero block, stored as the
+ * byte e + 127.  An element is q = RNE_e2m1(W / 2^e) on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the code whose mantissa bit is
+ * 0, the code's sign bit the source's; byte j of a row holds element 2j in its low nibble and element 2j + 1 in its high nibble.
+ * 2^e * q is exact in bf16, so the model IS the bf16 model whose weights are W' = 2^e * q.  WHAT RUNS WHERE: only the single-stream
+ * decode step (T = 1) reads the nibbles and scales (k_gemv_w4.hip); prompts, verify steps, fl_batch_* steps of every size,
+ * embeddings and scoring run the bf16 kernels on the bf16 image of W' (fl_tune "verify_w8" / "batch_w8" do not apply), and every path
+ * sees the same weights.  MEMORY: nibbles, scales and the image are kept, about 1.27x a bf16 model's weights.  REFUSED as above
+ * (compute_dtype other than BF16, tp_size > 1, fused decode step off -> FL_ERR_UNSUPPORTED), and where hidden_size, or any
+ * projection's K (heads x padded head_dim, intermediate_size padded to 16), is not a multiple of 32 -> FL_ERR_UNSUPPORTED naming it. */
+typedef enum fl_weight_format { FL_WEIGHTS_COMPUTE_DTYPE = 0, FL_WEIGHTS_E4M3_ROW = 1, FL_WEIGHTS_MXFP4 = 2 } fl_weight_format;
 typedef struct fl_model_options {
     uint32_t struct_size;           /* sizeof(fl_model_options) */
     int32_t  decode_weights;        /* fl_weight_format */
@@ -182,9 +194,10 @@ typedef struct fl_model_info {
     int32_t compute_dtype;
     int32_t tp_size;
     int64_t weight_bytes_per_token; /* algorithmic HBM bytes a decode step reads from weights (whole model); FL_WEIGHTS_E4M3_ROW: what
-                                       that step really streams -- 1 byte per projection weight + 4 per projection row */
+                                       that step really streams -- 1 byte per projection weight + 4 per projection row;
+                                       FL_WEIGHTS_MXFP4: K/2 + K/32 bytes per projection row */
     int64_t kv_bytes_per_position;  /* K+V bytes one cached position adds to a decode step */
-    int64_t hbm_bytes_allocated;    /* this process, all shards (FL_WEIGHTS_E4M3_ROW: the e4m3 bytes, the scales AND the bf16 image) */
+    int64_t hbm_bytes_allocated;    /* this process, all shards (FL_WEIGHTS_E4M3_ROW: the e4m3 bytes, the scales AND the bf16 image; FL_WEIGHTS_MXFP4 likewise: nibbles, scale streams and image) */
     int32_t small_collectives;      /* decode collectives: 0 none (tp 1), 1 RCCL, 2 one-shot peer inboxes, 3 local (emulated) */
     int32_t fused_all_reduce;       /* 1: decode all-reduces ride in the o_proj / down_proj GEMV epilogues (no kernel of their own) */
     int32_t rccl_ranks;             /* ncclCommCount of this rank's RCCL communicator; 0: no communicator (tp 1, emulated, IPC-only groups) */
@@ -939,6 +952,19 @@ int fl_op_quantize_rows(const void *w, int32_t dtype, int64_t N, int64_t K, uint
 int fl_op_gemv_w8(const void *x, const uint8_t *q, const float *s, const float *bias, int64_t N, int64_t K, int32_t epilogue,
                   float *y, int32_t iters, double *ms_out);
 
+/* The MXFP4 quantiser alone (unit tests): w host [N,K] of `dtype` (FL_DTYPE_F32 or FL_DTYPE_BF16), K a multiple of 32 (else
+ * FL_ERR_UNSUPPORTED), through the device kernel -> q_out [N,K/2] (two e2m1 to a byte, element 2j in the low nibble) and e_out
+ * [N,K/32] e8m0 bytes, both in the LOGICAL layouts of FL_WEIGHTS_MXFP4 above. */
+int fl_op_quantize_mx4(const void *w, int32_t dtype, int64_t N, int64_t K, uint8_t *q_out, uint8_t *e_out);
+
+/* The MXFP4 decode weight stream alone (unit tests, micro-benchmarks): y[n] = sum_k 2^(e[n,k/32] - 127) * q[n,k] * x[k] (+bias).
+ * x host bf16 [K], q host [N,K/2], e host [N,K/32] in the logical layouts (the hook lays the scales out in the kernel's stream
+ * order), K a multiple of 32 (else FL_ERR_UNSUPPORTED); y fp32.  epilogue as fl_op_gemv_w8: 0 none, 1 silu-gate (q / e rows are
+ * gate/up in HF order and are interleaved as the model does; y is [N/2], the kernel's bf16 output widened; no bias).  iters > 0 with
+ * ms_out != NULL times `iters` launches over rotating copies of nibbles and scales. */
+int fl_op_gemv_w4(const void *x, const uint8_t *q, const uint8_t *e, const float *bias, int64_t N, int64_t K, int32_t epilogue,
+                  float *y, int32_t iters, double *ms_out);
+
 /* Its 2-16-row sibling, the kernel under a verify step of an FL_WEIGHTS_E4M3_ROW model (unit tests, micro-benchmarks):
  * y[T,N] = row_scale[t] * s[n] * (x[T,K] . q[N,K]^T) (+bias).  x host bf16 [T,K], q host e4m3fn [N,K], s host fp32 [N], bias (or
  * NULL) fp32 [N], row_scale (or NULL) fp32 [T]; y fp32.  epilogue as fl_op_gemv_w8 (1: q / s rows are gate/up in HF order, y is
@@ -1456,6 +1482,8 @@ int fl_op_convert_slice(const fl_convert_slice_args *args);
  * layer is looked at for the per-layer selectors only.  *rows_out, *cols_out, *elem_out (an fl_dtype, or FL_ELEM_E4M3: one byte per
  * element) are always written; out == NULL returns only those, otherwise out takes rows x cols elements.  The FL_MT_*_Q (e4m3 bytes)
  * and FL_MT_*_S (fp32 row scales, [rows][1]) selectors exist for FL_WEIGHTS_E4M3_ROW models, FL_MT_BQKV for models with q/k/v bias;
+ * an FL_WEIGHTS_MXFP4 model refuses the *_Q / *_S selectors (its nibbles are not one byte per element and its scale stream lies in
+ * the kernel's own order, not a logical tensor: read the bf16 image, which holds the same weights);
  * a selector the model does not have, a bad shard or a bad layer: FL_ERR_BAD_ARGUMENT.  The call takes the model's lock, waits for
  * the shard's stream and copies; it launches nothing. */
 enum { FL_ELEM_E4M3 = 3 };

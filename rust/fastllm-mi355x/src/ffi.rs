@@ -44,6 +44,8 @@ pub const FL_TP_EMULATED: i32 = 3;
 // fl_weight_format: what the decode step streams (E4M3_ROW: e4m3fn weights with one power-of-two fp32 scale per output row)
 pub const FL_WEIGHTS_COMPUTE_DTYPE: i32 = 0;
 pub const FL_WEIGHTS_E4M3_ROW: i32 = 1;
+// MXFP4: e2m1 weights, two to a byte, with one e8m0 scale per 32 consecutive k of a row
+pub const FL_WEIGHTS_MXFP4: i32 = 2;
 
 // fl_activation: the encoder's GELU form (TANH: candle's Tensor::gelu, what the reference runs; ERF: the exact form HF BERT checkpoints were trained with)
 pub const FL_ACT_GELU_TANH: i32 = 0;
@@ -1234,6 +1236,19 @@ extern "C" {
         x: *const c_void,
         q: *const u8,
         s: *const f32,
+        bias: *const f32,
+        n: i64,
+        k: i64,
+        epilogue: i32,
+        y: *mut f32,
+        iters: i32,
+        ms_out: *mut f64,
+    ) -> c_int;
+    pub fn fl_op_quantize_mx4(w: *const c_void, dtype: i32, n: i64, k: i64, q_out: *mut u8, e_out: *mut u8) -> c_int;
+    pub fn fl_op_gemv_w4(
+        x: *const c_void,
+        q: *const u8,
+        e: *const u8,
         bias: *const f32,
         n: i64,
         k: i64,

@@ -309,6 +309,7 @@ pub struct EmbedOptions {
 pub enum WeightFormat {
     ComputeDtype = ffi::FL_WEIGHTS_COMPUTE_DTYPE,
     E4m3Row = ffi::FL_WEIGHTS_E4M3_ROW,
+    Mxfp4 = ffi::FL_WEIGHTS_MXFP4,
 }
 
 /// `fl_model*`.  Immutable after creation; `Clone` is a reference-count bump (the streaming path clones the model per
