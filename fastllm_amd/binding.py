@@ -437,6 +437,8 @@ def lib():
         L.fl_op_gemv_w4.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int32, C.POINTER(C.c_double)]
         L.fl_op_linear_w8.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
         L.fl_op_linear_w8_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+        L.fl_op_linear_w4.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
+        L.fl_op_linear_w4_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]
         L.fl_op_linear_w8_wide.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
         L.fl_op_linear_w8_wide_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
         L.fl_cache_truncate.argtypes = [vp, sz]
@@ -1945,6 +1947,30 @@ def op_linear_w8(x, q, s, bias=None, row_scale=None, epilogue=0, iters=0):
 def op_linear_w8_plan(T, N, K, epilogue=0, bias=False):
     """K slices op_linear_w8 runs such a product in, or 0: not served (no device needed)."""
     return int(lib().fl_op_linear_w8_plan(T, N, K, epilogue, 1 if bias else 0))
+
+
+def op_linear_w4(x, q, e, bias=None, row_scale=None, epilogue=0, iters=0):
+    """y[T,N] = row_scale[t] * (x . W'^T) (+bias), W' = 2^(e - 127) * q, through the 2-16-row MXFP4 weight stream (the kernel under a
+    verify step or a small batch of an MXFP4 model with tune("rows_w4", 1)).  x [T,K] uint16 (bf16 bits), q [N,K/2] uint8 (two e2m1
+    to a byte), e [N,K/32] uint8 (e8m0), both in the logical layouts; epilogue 1: rows are gate | up in HF order, y is [T, N/2]."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    e = np.ascontiguousarray(e, dtype=np.uint8)
+    T, K = x.shape
+    N = q.shape[0]
+    assert q.shape == (N, K // 2) and e.shape == (N, K // 32)
+    y = np.empty((T, N // 2 if epilogue == 1 else N), dtype=np.float32)
+    b = _f32(bias) if bias is not None else None
+    r = _f32(row_scale) if row_scale is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_linear_w4(x.ctypes.data, q.ctypes.data, e.ctypes.data, _ptr(b), _ptr(r), T, N, K, epilogue, iters, C.byref(ms),
+                                 y.ctypes.data))
+    return (y, ms.value) if iters else y
+
+
+def op_linear_w4_plan(T, N, K, epilogue=0, bias=False):
+    """K slices op_linear_w4 runs such a product in, or 0: not served (no device needed)."""
+    return int(lib().fl_op_linear_w4_plan(T, N, K, epilogue, 1 if bias else 0))
 
 
 def op_linear_w8_wide(x, q, s, row_scale=None, epilogue=0, iters=0):

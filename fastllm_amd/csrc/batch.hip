@@ -91,7 +91,9 @@ int batch_create(Model *m, Cache *const *caches, size_t B, Batch **out) {
     // projections on the e4m3 bytes; one or two keep the fused step on the image.  The switch is read here, once: the step is a
     // captured graph
     b->w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW && B >= 3 && !per_seq && !tp_rank && tune(TK_BATCH_W8) != 0;
-    if (b->w8) b->unfused = true;
+    // an FL_WEIGHTS_MXFP4 model likewise from 3 to 16 members, on the nibbles (k_gemm_rows_w4.hip; fl_tune "rows_w4", off by default)
+    b->w4 = m->decode_weights == FL_WEIGHTS_MXFP4 && B >= 3 && B <= 16 && !per_seq && !tp_rank && tune(TK_ROWS_W4) != 0;
+    if (b->w8 || b->w4) b->unfused = true;
     if (b->unfused) {
         FL_TRY(alloc_scratch(m, sh, b->sc, (int64_t)B, &b->allocs));
     }
@@ -225,14 +227,16 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
         return launch_gemv_dma(L, ga);
     };
     // an FP8 batch: the projection from the e4m3 bytes where the kernel of its row count serves it (k_gemm_rows_w8.hip up to 16 rows,
-    // k_gemm_rows64_w8.hip from 17); *served = false: the caller's launch on the image.  From 17 rows a product that the plan would
+    // k_gemm_rows64_w8.hip from 17), an MXFP4 batch (up to 16 rows) from the nibbles and their group-order scales g
+    // (k_gemm_rows_w4.hip); *served = false: the caller's launch on the image.  From 17 rows a product that the plan would
     // cut into K slices stays on the image: measured on Mistral-7B (profiles/r21/batch_w8.txt) the sliced QKV, o_proj and down_proj
     // ran at 0.70-0.92x of the sliced short-prompt GEMM, the unsliced gate/up and lm_head at 1.09-1.51x
-    auto fp8 = [&](const uint8_t *q8, const float *s8, const void *x, void *out, int64_t N, int64_t K, int epi, const float *rs, int max_split, int *nsl,
-                   bool *served) -> int {
-        *served = b->w8 && (T <= 16 ? gemm_rows_w8_plan(T, N, K, epi, false, max_split) > 0 : gemm_rows64_w8_plan(T, N, K, epi, max_split) == 1);
+    const int wq = b->w8 ? FL_WEIGHTS_E4M3_ROW : b->w4 ? FL_WEIGHTS_MXFP4 : 0;
+    auto bytes = [&](const uint8_t *q8, const float *s8, const uint8_t *g, const void *x, void *out, int64_t N, int64_t K, int epi, const float *rs, int max_split,
+                     int *nsl, bool *served) -> int {
+        *served = T <= 16 ? rows_wq_plan(wq, T, N, K, epi, max_split) > 0 : (b->w8 && gemm_rows64_w8_plan(T, N, K, epi, max_split) == 1);
         if (!*served) return FL_OK;
-        if (T <= 16) return launch_gemm_rows_w8(L, q8, s8, x, nullptr, out, T, N, K, epi, rs, max_split, nsl);
+        if (T <= 16) return launch_rows_wq(L, wq, q8, s8, g, x, out, T, N, K, epi, rs, max_split, nsl);
         return launch_gemm_rows64_w8(L, q8, s8, x, out, T, N, K, epi, rs, max_split, nsl);
     };
     bool on8 = false;
@@ -258,7 +262,7 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
     // down_proj with the residual + next norm in theirs (K slices met inside the launch: no slabs, no rmsnorm_add), gate/up with its
     // row scales from the partial sums -- where every projection of the model has a plan there; otherwise the eight-launch layer below
     const bool tpr = m->tp > 1;                                        // a rank of a multi-process group: all-reduce behind o_proj / down_proj, gathered logits
-    const int ks_q = dt == FL_DTYPE_BF16 && sc.rs_part && !tpr && !ps && !b->w8 && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
+    const int ks_q = dt == FL_DTYPE_BF16 && sc.rs_part && !tpr && !ps && !wq && tune(TK_GEMM_SKF) >= 2 ? gemm_skf_plan(T, nq, D.h, EPI_QKV_ROPE, (int)D.d) : 0;
     const LinearPlan po = plan_resid(dt, T, D.h, sh.Hs * D.d, 1, true), pd = plan_resid(dt, T, D.h, sh.Ip, 1, true);
     if (ks_q && po.kernel == LK_SKF && pd.kernel == LK_SKF && gemm_skf_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP) > 0) {
         const int np = gemm_resid_partials(D.h);
@@ -310,7 +314,7 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
             FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, 1, nullptr, true));
             FL_TRY(rope_attn_per_seq(l, ly.bqkv));
         } else {
-            FL_TRY(fp8(ly.wqkv8, ly.sqkv, sc.xn, sc.qkv, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, &on8));
+            FL_TRY(bytes(ly.wqkv8, ly.sqkv, ly.gqkv, sc.xn, sc.qkv, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, &on8));
             if (!on8) FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, kMaxQkvSplitShort, &qkv_slabs, true));
             FL_TRY(launch_rope_kv_batch(L, sc.qkv, b->seqs_dev, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, (size_t)l * sh.Hkvs * D.d, B, sh.Hs,
                                         sh.Hkvs, D.d, qkv_slabs, ly.bqkv));
@@ -318,13 +322,13 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
                                                  D.d, D.scale, 0.0));
         }
         // (a rank's row-parallel outputs: complete, no slabs -- the all-reduce wants the sum; sums in rank order on every rank)
-        FL_TRY(fp8(ly.wo8, ly.so, sc.ao, sc.delta, D.h, sh.Hs * D.d, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
+        FL_TRY(bytes(ly.wo8, ly.so, ly.go, sc.ao, sc.delta, D.h, sh.Hs * D.d, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
         if (!on8) FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
-        FL_TRY(fp8(ly.wgu8, ly.sgu, sc.xn, sc.act, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms, 1, nullptr, &on8));
+        FL_TRY(bytes(ly.wgu8, ly.sgu, ly.ggu, sc.xn, sc.act, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms, 1, nullptr, &on8));
         if (!on8) FL_TRY(wide(ly.wgu, sc.act, 2 * sh.Ip, EPI_GATEUP));
-        FL_TRY(fp8(ly.wd8, ly.sd, sc.act, sc.delta, D.h, sh.Ip, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
+        FL_TRY(bytes(ly.wd8, ly.sd, ly.gd, sc.act, sc.delta, D.h, sh.Ip, EPI_F32, nullptr, kMaxKSplit, &nslab, &on8));
         if (!on8) FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, tpr ? 1 : kMaxKSplit, &nslab, true));
         if (tpr) FL_TRY(oneshot(m, sh, false, sc.delta, sc.delta, T * D.h, 0));
     }
@@ -335,7 +339,7 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
         FL_TRY(oneshot(m, sh, true, b->logits_local, b->logits_ranks, (int64_t)B * sh.Vs, (int64_t)B * sh.Vs));
         FL_TRY(launch_unshard_logits(L, b->logits_ranks, b->logits, m->tp, B, sh.Vs));
     } else {
-        FL_TRY(fp8(sh.lm_head8, sh.lm_head_s, sc.xn, b->logits, D.V, D.h, EPI_F32, sc.inv_rms, 1, nullptr, &on8));
+        FL_TRY(bytes(sh.lm_head8, sh.lm_head_s, sh.lm_head_g, sc.xn, b->logits, D.V, D.h, EPI_F32, sc.inv_rms, 1, nullptr, &on8));
         if (!on8) FL_TRY(wide(sh.lm_head, b->logits, D.V, EPI_F32));
     }
     return batch_select(b, L, kind);

@@ -39,18 +39,10 @@ namespace fl {
 constexpr int kW4MaxThreads = 768;       // 12 waves: 170 VGPRs per lane
 constexpr int kW4R = 4;
 
-// chunks (wave instructions) per item: the one of {2, 1} that pads the row's instruction count least, ties to the larger
-// (K = 4096: 2 instructions -> U 2, one block; 14336: 7 -> U 1; 11008: 6 -> U 2).  U = 4 with four rows is 128 VGPRs of stream
-// buffers: it does not fit under the 168-register cap of a 12-wave workgroup.
-static int mx4_u(int64_t K) { return (((K >> 5) + 63) / 64) % 2 == 0 ? 2 : 1; }
+// (mx4_u, the chunks per item, and mx4_scale_slot, the place of a block's scale in the stream: kernels.h)
 int64_t mx4_scale_stride(int64_t K) {
     const int64_t per = 64 * mx4_u(K);
     return ((K >> 5) + per - 1) / per * per;
-}
-// where the scale of block c of a row sits in the row's part of the stream
-__host__ __device__ inline int64_t mx4_scale_slot(int64_t c, int U) {
-    const int64_t per = 64 * U, rem = c % per;
-    return c / per * per + (rem & 63) * U + (rem >> 6);
 }
 
 // byte B of `w` (two e2m1: low nibble first) times the scale as a packed bf16 pair

@@ -148,12 +148,33 @@ bool gemv_w4_supported(int64_t N, int64_t K);          // K a multiple of 32 (a 
 bool gemv_w4_norm_supported(int64_t N, int64_t K);
 bool gemv_w4_leaves_candidates(int64_t N, int64_t K);  // its grid fits the ArgMax candidate buffer
 int64_t mx4_scale_stride(int64_t K);                   // bytes of one row in the scale stream (>= K / 32)
+// chunks (wave instructions) per item of that stream: the one of {2, 1} that pads the row's instruction count least, ties to the larger
+// (K = 4096: 2 instructions -> U 2, one block; 14336: 7 -> U 1; 11008: 6 -> U 2).  U = 4 with four rows is 128 VGPRs of stream
+// buffers: it does not fit under the 168-register cap of a 12-wave workgroup.
+inline int mx4_u(int64_t K) { return (((K >> 5) + 63) / 64) % 2 == 0 ? 2 : 1; }
+// where the scale of block c of a row sits in the row's part of the stream
+__host__ __device__ inline int64_t mx4_scale_slot(int64_t c, int U) {
+    const int64_t per = 64 * U, rem = c % per;
+    return c / per * per + (rem & 63) * U + (rem >> 6);
+}
 // src [N,K] bf16 / fp32 -> q [N, K/2], e (e_stream: the scale stream; else the logical [N, K/32]) and (img non-null; may be src
 // when that is bf16) the bf16 image 2^e * q
 int launch_quantize_mx4(Launcher &L, int src_dtype, const void *src, int64_t N, int64_t K, uint8_t *q, uint8_t *e, bool e_stream, void *img_bf16);
 // logical q [N, K/2], e [N, K/32] -> device rows and scale stream (test hook); I > 0: N = 2 I rows gate | up in HF order -> the
 // 16-interleaved decode layout.  The caller zeroes qo's padding rows and fills eo with 127 first.
 int launch_mx4_layout(Launcher &L, const uint8_t *q, const uint8_t *e, int64_t N, int64_t I, int64_t K, uint8_t *qo, uint8_t *eo);
+// the 2-16-row sibling (k_gemm_rows_w4.hip): y[T,N] = rs[t] * (x[T,K] . W'[N,K]^T) (+ bias[n]), x bf16, rs (1/rms) optional; q the
+// nibbles [N, K/2], e the scales in GROUP order (N x rows_w4_scale_stride(K) bytes: byte 16 J + 4 g + u of a row = the scale of block
+// 16 J + 4 u + g, slots past K / 32 = 127; launch_mx4_group_scales writes it from the GEMV's scale stream of the same rows).
+// EPI_F32 (y fp32) or EPI_GATEUP (rows in the 16-interleaved layout, y bf16 [T, N/2]).  gemm_rows_w4_plan: the K slices (multiples
+// of 512 columns) the launch will leave as fp32 slabs [nks][T][N] for the caller's next launch to sum (> 1 only for EPI_F32 without
+// bias and max_split > 1), or 0: not served (T outside 2..16, K no multiple of 32, x rows beyond LDS where slabs are not allowed).
+// launch_gemm_rows_w4 fails with FL_ERR_UNSUPPORTED exactly where the plan is 0.
+int gemm_rows_w4_plan(int64_t T, int64_t N, int64_t K, int epi, bool bias, int max_split);
+int launch_gemm_rows_w4(Launcher &L, const uint8_t *q, const uint8_t *e, const void *x, const float *bias, void *y, int64_t T, int64_t N,
+                        int64_t K, int epi, const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
+int64_t rows_w4_scale_stride(int64_t K);               // bytes of one row in the group-order scale stream: ceil(K / 512) * 16
+int launch_mx4_group_scales(Launcher &L, const uint8_t *e_stream, int64_t N, int64_t K, uint8_t *eo);
 
 // k_kvcopy.hip: a 2-D byte copy on the device, `rows` rows of `width` bytes (a multiple of 2) with a source and a destination pitch
 // (multiples of 16, >= width; 16-byte aligned bases).  launch_kv_copy moves two such jobs -- the K and the V prefix of a cache -- in

@@ -39,6 +39,8 @@ struct LayerW {
     // FL_WEIGHTS_MXFP4: the *8 pointers hold the e2m1 nibbles [rows, K/2], these the e8m0 scale streams (k_gemv_w4.hip's own order,
     // mx4_scale_stride(K) bytes per row); the fp32 row scales stay null
     uint8_t *eqkv = nullptr, *eo = nullptr, *egu = nullptr, *ed = nullptr;
+    // ... and the same scales in the group order of the 2-16-row stream (k_gemm_rows_w4.hip, rows_w4_scale_stride(K) bytes per row)
+    uint8_t *gqkv = nullptr, *go = nullptr, *ggu = nullptr, *gd = nullptr;
 };
 
 struct Scratch {                 // activations of one forward chunk on one shard
@@ -140,6 +142,7 @@ struct Shard {
     uint8_t *lm_head8 = nullptr; // FL_WEIGHTS_E4M3_ROW: its e4m3 bytes and row scales (lm_head is then the bf16 image)
     float *lm_head_s = nullptr;
     uint8_t *lm_head_e = nullptr; // FL_WEIGHTS_MXFP4: lm_head8 holds the e2m1 nibbles, this the e8m0 scale stream
+    uint8_t *lm_head_g = nullptr; // ... and this the scales in the group order of k_gemm_rows_w4.hip
     float *cos_tab = nullptr, *sin_tab = nullptr;   // [max_pos][d/2]
     Scratch dec, pre;
     PackedScratch packed;
@@ -268,6 +271,7 @@ struct Batch {
     bool dma = false;                            // B >= 3: projections on the LDS-DMA ring kernel (k_gemv_dma.hip)
     bool unfused = false;                        // large B: norm / GEMM / RoPE as separate launches around the short-prompt GEMM
     bool w8 = false;                             // B >= 3 on an FL_WEIGHTS_E4M3_ROW model: the prefill-shaped step reads the e4m3 bytes (fl_tune "batch_w8" when the batch was created)
+    bool w4 = false;                             // 3 <= B <= 16 on an FL_WEIGHTS_MXFP4 model: the prefill-shaped step reads the e2m1 nibbles (fl_tune "rows_w4" when the batch was created)
     bool plain = false;                          // ... all caches in the plain layout and head_dim 64 / 128: the batch kernels' plain-layout forms (one RoPE and one attention launch per layer)
     bool per_seq = false;                        // fp32 models, caches without the MFMA attention layout: embedding / RoPE / attention as launches per sequence (the single-sequence kernels on row i), the projections still once for all B rows
     Scratch sc;                                  // ... with the prefill scratch layout at T = B
@@ -376,9 +380,15 @@ struct AllRows {
     // planner's T = 1 kernel, another summation order than the rows of every other block see
     bool no_one_row_tail = false;
     // a single-stream verify step: on an FL_WEIGHTS_E4M3_ROW model its 2-16 rows stream the e4m3 bytes (k_gemm_rows_w8.hip, fl_tune
-    // "verify_w8") wherever gemm_rows_w8_plan serves the projection; every other forward keeps the bf16 image
+    // "verify_w8") wherever gemm_rows_w8_plan serves the projection, on an FL_WEIGHTS_MXFP4 model the e2m1 nibbles (k_gemm_rows_w4.hip,
+    // fl_tune "rows_w4", off by default) likewise; every other forward keeps the bf16 image
     bool verify = false;
 };
+// one projection of 2-16 rows from a model's byte weights, fmt = FL_WEIGHTS_E4M3_ROW (q e4m3, s the row scales: k_gemm_rows_w8.hip) or
+// FL_WEIGHTS_MXFP4 (q nibbles, g the group-order scales: k_gemm_rows_w4.hip).  rows_wq_plan: the K slices, 0: not served
+int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split);
+int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
+                   int epi, const float *rs, int max_split = 1, int *n_split_out = nullptr);
 int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const AllRows &rows);
 // the model's [R][V] fp32 block scratch of such a forward (ScoreScratch::rows; R: the score_rows switch now), allocated -- or regrown,
 // after waiting for the stream -- by whichever call needs it first: the scoring calls and fl_batch_verify share it

@@ -565,8 +565,22 @@ ResidEpi resid_epi(const Scratch &sc, const Dims &D, const float *next_norm_w) {
 // A single-stream verify step of an FL_WEIGHTS_E4M3_ROW model (one shard, bf16: model_create) reads the e4m3 bytes: its projections of
 // 2-16 rows go to k_gemm_rows_w8.hip wherever gemm_rows_w8_plan serves them, in their plain forms (the rope_kv and rmsnorm_add launches
 // behind them).  fl_tune "verify_w8" = 0, every other forward and every other model: the bf16 image, the launches there have always been.
-static bool verify_w8(const Model *m, const AllRows *rows, int64_t T) {
-    return rows && rows->verify && m->decode_weights == FL_WEIGHTS_E4M3_ROW && T >= 2 && T <= 16 && tune(TK_VERIFY_W8) != 0;
+// An FL_WEIGHTS_MXFP4 model does the same on its nibbles (k_gemm_rows_w4.hip) under fl_tune "rows_w4", which is off by default.
+// verify_wq: the format whose row stream the step takes, or 0: the image
+static int verify_wq(const Model *m, const AllRows *rows, int64_t T) {
+    if (!rows || !rows->verify || T < 2 || T > 16) return 0;
+    if (m->decode_weights == FL_WEIGHTS_E4M3_ROW) return tune(TK_VERIFY_W8) != 0 ? FL_WEIGHTS_E4M3_ROW : 0;
+    if (m->decode_weights == FL_WEIGHTS_MXFP4) return tune(TK_ROWS_W4) != 0 ? FL_WEIGHTS_MXFP4 : 0;
+    return 0;
+}
+int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split) {
+    if (fmt == FL_WEIGHTS_MXFP4) return gemm_rows_w4_plan(T, N, K, epi, false, max_split);
+    return fmt == FL_WEIGHTS_E4M3_ROW ? gemm_rows_w8_plan(T, N, K, epi, false, max_split) : 0;
+}
+int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
+                   int epi, const float *rs, int max_split, int *n_split_out) {
+    if (fmt == FL_WEIGHTS_MXFP4) return launch_gemm_rows_w4(L, q, g, x, nullptr, out, T, N, K, epi, rs, max_split, n_split_out);
+    return launch_gemm_rows_w8(L, q, s, x, nullptr, out, T, N, K, epi, rs, max_split, n_split_out);
 }
 
 // lm_head on the T rows whose xn and 1/rms the final norm has left in sc, in blocks of at most rows.R rows into rows.out; rows.each
@@ -577,8 +591,9 @@ int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const
         n = std::min<int64_t>(rows.R, T - r0);
         if (rows.no_one_row_tail && T - r0 - n == 1 && n > 2) n -= 1;
         const void *xb = (char *)sc.xn + (size_t)r0 * D.h * m->esize();
-        if (verify_w8(m, &rows, n) && gemm_rows_w8_plan(n, sh.Vs, D.h, EPI_F32, false, 1))
-            FL_TRY(launch_gemm_rows_w8(L, sh.lm_head8, sh.lm_head_s, xb, nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
+        const int wq = verify_wq(m, &rows, n);
+        if (rows_wq_plan(wq, n, sh.Vs, D.h, EPI_F32, 1))
+            FL_TRY(launch_rows_wq(L, wq, sh.lm_head8, sh.lm_head_s, sh.lm_head_g, xb, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
         else
             FL_TRY(launch_linear(L, m->dtype, sh.lm_head, xb, nullptr, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
         if (rows.each) FL_TRY(rows.each(L, r0, n));
@@ -625,7 +640,7 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
         if (rs_lazy) return FL_OK;
         return launch_rms_finalize(L, sc.rs_part, re.np, D.eps, sc.inv_rms, T, D.h);
     };
-    const bool w8 = verify_w8(m, all_rows, T);
+    const int wq = verify_wq(m, all_rows, T);
     auto with_parts = [&](Launcher &L, Scratch &sc) {             // the launcher of the projection behind a lazy residual epilogue
         if (rs_lazy) { L.rsp = RsParts{sc.rs_part, gemm_resid_partials(D.h), D.eps, 1.0f / (float)D.h}; rs_lazy = false; }
     };
@@ -641,9 +656,9 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             const int64_t sa = (int64_t)c->seq_alloc;
             with_parts(L, sc);                                       // (the previous layer's down_proj may have left 1/rms as partial sums)
             const LinearPlan qp = plan_qkv_rope(dt, T, nq, D.h, D.d, D.d * sh.Hkvs, m->tp, qkv_split(T));
-            if (w8 && gemm_rows_w8_plan(T, nq, D.h, EPI_F32, false, qkv_split(T))) {
+            if (rows_wq_plan(wq, T, nq, D.h, EPI_F32, qkv_split(T))) {
                 int qs = 1;
-                FL_TRY(launch_gemm_rows_w8(L, ly.wqkv8, ly.sqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qs));
+                FL_TRY(launch_rows_wq(L, wq, ly.wqkv8, ly.sqkv, ly.gqkv, sc.xn, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qs));
                 FL_TRY(launch_rope_kv(L, dt, sc.qkv, cs.st, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kv.k, kv.v, T, sh.Hs, sh.Hkvs, D.d, sa, c->v_transposed, qs, ly.bqkv));
             } else if (qp.rope) {
                 // RoPE, bias and the KV append ride in the projection's epilogue: no fp32 QKV matrix
@@ -662,10 +677,10 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             } else {
                 FL_TRY(attend_prefill(L, m, c, sh, cs, kv, sc, T));
             }
-            const bool o8 = w8 && gemm_rows_w8_plan(T, D.h, sh.Hs * D.d, EPI_F32, false, max_split);
+            const bool o8 = rows_wq_plan(wq, T, D.h, sh.Hs * D.d, EPI_F32, max_split) != 0;
             const LinearPlan op = resid_ok && !o8 ? plan_resid(dt, T, D.h, sh.Hs * D.d, max_split, false) : LinearPlan{};
             if (o8) {
-                FL_TRY(launch_gemm_rows_w8(L, ly.wo8, ly.so, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
+                FL_TRY(launch_rows_wq(L, wq, ly.wo8, ly.so, ly.go, sc.ao, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
             } else if (op.kernel != LK_NONE) {
                 const bool gu_parts = plan_linear(dt, T, 2 * sh.Ip, D.h, EPI_GATEUP, m->tp, 1, false, false, false).reads_rs_parts;
                 FL_TRY(linear_resid(L, sc, op, ly.wo, sc.ao, sh.Hs * D.d, ly.ln2, gu_parts));
@@ -681,15 +696,15 @@ static int enqueue_forward(Model *m, Cache *c, bool pre, int64_t T, bool ids_in_
             if (!norm_done) FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
             norm_done = false;
             with_parts(L, sc);
-            if (w8 && gemm_rows_w8_plan(T, 2 * sh.Ip, D.h, EPI_GATEUP, false, 1))
-                FL_TRY(launch_gemm_rows_w8(L, ly.wgu8, ly.sgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
+            if (rows_wq_plan(wq, T, 2 * sh.Ip, D.h, EPI_GATEUP, 1))
+                FL_TRY(launch_rows_wq(L, wq, ly.wgu8, ly.sgu, ly.ggu, sc.xn, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
             else
                 FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
             L.rsp = RsParts{};
-            const bool d8 = w8 && gemm_rows_w8_plan(T, D.h, sh.Ip, EPI_F32, false, max_split);
+            const bool d8 = rows_wq_plan(wq, T, D.h, sh.Ip, EPI_F32, max_split) != 0;
             const LinearPlan dp = resid_ok && !d8 ? plan_resid(dt, T, D.h, sh.Ip, max_split, false) : LinearPlan{};
             if (d8) {
-                FL_TRY(launch_gemm_rows_w8(L, ly.wd8, ly.sd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
+                FL_TRY(launch_rows_wq(L, wq, ly.wd8, ly.sd, ly.gd, sc.act, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
             } else if (dp.kernel != LK_NONE) {
                 // (the next layer's QKV projection takes the partial sums if its kernel can; the last layer's final norm wants the vector)
                 const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;

@@ -149,6 +149,7 @@ static const TuneEntry g_tune_table[TK_COUNT] = {
     {"gemv_resid", 1},
     {"verify_w8", 1},
     {"batch_w8", 1},
+    {"rows_w4", 0},
 };
 static_assert(sizeof(g_tune_table) / sizeof(g_tune_table[0]) == TK_COUNT, "one row per TuneKey, in the enum's order");
 static std::atomic<int> g_tune[TK_COUNT];

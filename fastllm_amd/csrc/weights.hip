@@ -316,19 +316,23 @@ static int build_weights(Builder &B) {
 // permutation) gets its e4m3 bytes and row scales, and the bf16 matrix itself becomes the image s * q -- what prefill, batches
 // and every other bf16 kernel then read.  Both images stay: 1.5x a bf16 model's weight memory.
 // FL_WEIGHTS_MXFP4: the same with the e2m1 nibbles in the byte pointers and an e8m0 scale stream (k_gemv_w4.hip's order) beside
-// them; blocks run along K, so the row permutations do not matter here either.  Nibbles, scales and image: 1.27x.
+// them -- and once more in the group order of the 2-16-row stream (k_gemm_rows_w4.hip: + K / 32 bytes per row) -- blocks run along K,
+// so the row permutations do not matter here either.  Nibbles, scales and image: 1.27x.
 static int quantize_weights(Model *m) {
     const Dims &D = m->D;
     const bool mx4 = m->decode_weights == FL_WEIGHTS_MXFP4;
     for (auto &sh : m->shards) {
         FL_HIP(hipSetDevice(sh.device));
         Launcher L; L.stream = sh.stream;
-        auto one = [&](void *w, int64_t N, int64_t K, uint8_t **q, float **s, uint8_t **e) -> int {
+        auto one = [&](void *w, int64_t N, int64_t K, uint8_t **q, float **s, uint8_t **e, uint8_t **g) -> int {
             if (mx4) {
                 if (!gemv_w4_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_MXFP4: a %lld x %lld projection (K must be a multiple of 32)", (long long)N, (long long)K);
                 FL_TRY(dev_alloc(sh.allocs, (void **)q, (size_t)N * (K / 2), &m->hbm_bytes));
                 FL_TRY(dev_alloc(sh.allocs, (void **)e, (size_t)N * mx4_scale_stride(K), &m->hbm_bytes));
-                return launch_quantize_mx4(L, FL_DTYPE_BF16, w, N, K, *q, *e, true, w);
+                // the scales once more in the group order of the 2-16-row stream: always, fl_tune "rows_w4" can be set after creation
+                FL_TRY(dev_alloc(sh.allocs, (void **)g, (size_t)N * rows_w4_scale_stride(K), &m->hbm_bytes));
+                FL_TRY(launch_quantize_mx4(L, FL_DTYPE_BF16, w, N, K, *q, *e, true, w));
+                return launch_mx4_group_scales(L, *e, N, K, *g);
             }
             if (!gemv_w8_supported(N, K)) FL_FAIL(FL_ERR_UNSUPPORTED, "FL_WEIGHTS_E4M3_ROW: a %lld x %lld projection (K must be a multiple of 16)", (long long)N, (long long)K);
             FL_TRY(dev_alloc(sh.allocs, (void **)q, (size_t)N * K, &m->hbm_bytes));
@@ -337,12 +341,12 @@ static int quantize_weights(Model *m) {
         };
         const int64_t nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
         for (auto &ly : sh.layers) {
-            FL_TRY(one(ly.wqkv, nq, D.h, &ly.wqkv8, &ly.sqkv, &ly.eqkv));
-            FL_TRY(one(ly.wo, D.h, sh.Hs * D.d, &ly.wo8, &ly.so, &ly.eo));
-            FL_TRY(one(ly.wgu, 2 * sh.Ip, D.h, &ly.wgu8, &ly.sgu, &ly.egu));
-            FL_TRY(one(ly.wd, D.h, sh.Ip, &ly.wd8, &ly.sd, &ly.ed));
+            FL_TRY(one(ly.wqkv, nq, D.h, &ly.wqkv8, &ly.sqkv, &ly.eqkv, &ly.gqkv));
+            FL_TRY(one(ly.wo, D.h, sh.Hs * D.d, &ly.wo8, &ly.so, &ly.eo, &ly.go));
+            FL_TRY(one(ly.wgu, 2 * sh.Ip, D.h, &ly.wgu8, &ly.sgu, &ly.egu, &ly.ggu));
+            FL_TRY(one(ly.wd, D.h, sh.Ip, &ly.wd8, &ly.sd, &ly.ed, &ly.gd));
         }
-        FL_TRY(one(sh.lm_head, sh.Vs, D.h, &sh.lm_head8, &sh.lm_head_s, &sh.lm_head_e));
+        FL_TRY(one(sh.lm_head, sh.Vs, D.h, &sh.lm_head8, &sh.lm_head_s, &sh.lm_head_e, &sh.lm_head_g));
         FL_HIP(hipStreamSynchronize(sh.stream));
     }
     return FL_OK;

@@ -158,10 +158,13 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
  * (absmax = m * 2^x, m in [0.5, 1): e = x - 3 if m <= 0.75, else x - 2), kept at -120 or above, 0 for an all-zero block, stored as the
  * byte e + 127.  An element is q = RNE_e2m1(W / 2^e) on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the code whose mantissa bit is
  * 0, the code's sign bit the source's; byte j of a row holds element 2j in its low nibble and element 2j + 1 in its high nibble.
- * 2^e * q is exact in bf16, so the model IS the bf16 model whose weights are W' = 2^e * q.  WHAT RUNS WHERE: only the single-stream
- * decode step (T = 1) reads the nibbles and scales (k_gemv_w4.hip); prompts, verify steps, fl_batch_* steps of every size,
- * embeddings and scoring run the bf16 kernels on the bf16 image of W' (fl_tune "verify_w8" / "batch_w8" do not apply), and every path
- * sees the same weights.  MEMORY: nibbles, scales and the image are kept, about 1.27x a bf16 model's weights.  REFUSED as above
+ * 2^e * q is exact in bf16, so the model IS the bf16 model whose weights are W' = 2^e * q.  WHAT RUNS WHERE: by default only the
+ * single-stream decode step (T = 1) reads the nibbles and scales (k_gemv_w4.hip); prompts, verify steps, fl_batch_* steps of every
+ * size, embeddings and scoring run the bf16 kernels on the bf16 image of W' (fl_tune "verify_w8" / "batch_w8" do not apply), and
+ * every path sees the same weights.  fl_tune "rows_w4" (FL_ROWS_W4; default 0) = 1: a single-stream verify step of 2-16 rows and a
+ * batch of 3-16 members stream the nibbles too (k_gemm_rows_w4.hip; rows equal the image's up to fp32 summation order); it is read
+ * per verify step and, for a batch, by fl_batch_create -- the batch's step is a captured graph.  MEMORY: nibbles, the scales in the
+ * order of either kernel and the image are kept, about 1.27x a bf16 model's weights.  REFUSED as above
  * (compute_dtype other than BF16, tp_size > 1, fused decode step off -> FL_ERR_UNSUPPORTED), and where hidden_size, or any
  * projection's K (heads x padded head_dim, intermediate_size padded to 16), is not a multiple of 32 -> FL_ERR_UNSUPPORTED naming it. */
 typedef enum fl_weight_format { FL_WEIGHTS_COMPUTE_DTYPE = 0, FL_WEIGHTS_E4M3_ROW = 1, FL_WEIGHTS_MXFP4 = 2 } fl_weight_format;
@@ -985,6 +988,18 @@ int fl_op_linear_w8_wide(const void *x, const uint8_t *q, const float *s, const 
 /* The K slices fl_op_linear_w8_wide runs such a product in (>= 1), or 0: not served -- T outside 17..64, K no multiple of 16, an
  * epilogue other than 0 / 1, an odd gate/up row count. */
 int fl_op_linear_w8_wide_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue);
+
+/* The 2-16-row kernel over MXFP4 weights (k_gemm_rows_w4.hip), the one under a verify step or a batch of 3-16 members of an
+ * FL_WEIGHTS_MXFP4 model with fl_tune "rows_w4" on, alone: y[T,N] = row_scale[t] * sum_k 2^(e[n,k/32] - 127) * q[n,k] * x[t,k] (+bias).
+ * x host bf16 [T,K], q host [N,K/2], e host [N,K/32] in the logical layouts of fl_op_gemv_w4 (the hook interleaves gate/up rows and
+ * lays the scales out in the kernel's group order), bias (or NULL) fp32 [N], row_scale (or NULL) fp32 [T]; y fp32.  epilogue, slab
+ * summation and timing form as fl_op_linear_w8.  FL_ERR_UNSUPPORTED where fl_op_linear_w4_plan is 0. */
+int fl_op_linear_w4(const void *x, const uint8_t *q, const uint8_t *e, const float *bias, const float *row_scale, int64_t T, int64_t N,
+                    int64_t K, int32_t epilogue, int32_t iters, double *ms_out, float *y);
+/* The K slices (multiples of 512 columns) fl_op_linear_w4 runs such a product in (>= 1), or 0: not served -- T outside 2..16, K no
+ * multiple of 32, an epilogue other than 0 / 1, an odd gate/up row count, or x rows that do not fit LDS where slices are not allowed
+ * (gate/up, bias). */
+int fl_op_linear_w4_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue, int32_t has_bias);
 
 /* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
 
