@@ -91,8 +91,9 @@ int batch_create(Model *m, Cache *const *caches, size_t B, Batch **out) {
     // projections on the e4m3 bytes; one or two keep the fused step on the image.  The switch is read here, once: the step is a
     // captured graph
     b->w8 = m->decode_weights == FL_WEIGHTS_E4M3_ROW && B >= 3 && !per_seq && !tp_rank && tune(TK_BATCH_W8) != 0;
-    // an FL_WEIGHTS_MXFP4 model likewise from 3 to 16 members, on the nibbles (k_gemm_rows_w4.hip; fl_tune "rows_w4", off by default)
-    b->w4 = m->decode_weights == FL_WEIGHTS_MXFP4 && B >= 3 && B <= 16 && !per_seq && !tp_rank && tune(TK_ROWS_W4) != 0;
+    // an FL_WEIGHTS_MXFP4 model likewise from 3 to 64 members, on the nibbles (k_gemm_rows_w4.hip up to 16 members, k_gemm_rows64_w4.hip
+    // from 17; fl_tune "rows_w4", off by default)
+    b->w4 = m->decode_weights == FL_WEIGHTS_MXFP4 && B >= 3 && B <= 64 && !per_seq && !tp_rank && tune(TK_ROWS_W4) != 0;
     if (b->w8 || b->w4) b->unfused = true;
     if (b->unfused) {
         FL_TRY(alloc_scratch(m, sh, b->sc, (int64_t)B, &b->allocs));
@@ -227,17 +228,15 @@ static int enqueue_batch_step_unfused(Batch *b, int kind) {
         return launch_gemv_dma(L, ga);
     };
     // an FP8 batch: the projection from the e4m3 bytes where the kernel of its row count serves it (k_gemm_rows_w8.hip up to 16 rows,
-    // k_gemm_rows64_w8.hip from 17), an MXFP4 batch (up to 16 rows) from the nibbles and their group-order scales g
-    // (k_gemm_rows_w4.hip); *served = false: the caller's launch on the image.  From 17 rows a product that the plan would
-    // cut into K slices stays on the image: measured on Mistral-7B (profiles/r21/batch_w8.txt) the sliced QKV, o_proj and down_proj
-    // ran at 0.70-0.92x of the sliced short-prompt GEMM, the unsliced gate/up and lm_head at 1.09-1.51x
+    // k_gemm_rows64_w8.hip from 17), an MXFP4 batch from the nibbles and their group-order scales g (k_gemm_rows_w4.hip,
+    // k_gemm_rows64_w4.hip from 17); *served = false: the caller's launch on the image.  From 17 rows (MXFP4: from 33) a product that
+    // the plan would cut into K slices stays on the image (rows_wq_plan, model.hip, with the measurements behind the rule)
     const int wq = b->w8 ? FL_WEIGHTS_E4M3_ROW : b->w4 ? FL_WEIGHTS_MXFP4 : 0;
     auto bytes = [&](const uint8_t *q8, const float *s8, const uint8_t *g, const void *x, void *out, int64_t N, int64_t K, int epi, const float *rs, int max_split,
                      int *nsl, bool *served) -> int {
-        *served = T <= 16 ? rows_wq_plan(wq, T, N, K, epi, max_split) > 0 : (b->w8 && gemm_rows64_w8_plan(T, N, K, epi, max_split) == 1);
+        *served = rows_wq_plan(wq, T, N, K, epi, max_split) > 0;
         if (!*served) return FL_OK;
-        if (T <= 16) return launch_rows_wq(L, wq, q8, s8, g, x, out, T, N, K, epi, rs, max_split, nsl);
-        return launch_gemm_rows64_w8(L, q8, s8, x, out, T, N, K, epi, rs, max_split, nsl);
+        return launch_rows_wq(L, wq, q8, s8, g, x, out, T, N, K, epi, rs, max_split, nsl);
     };
     bool on8 = false;
     const bool ps = b->per_seq;

@@ -42,8 +42,7 @@ namespace fl {
 constexpr int kRowsW4MaxThreads = 768;              // 12 waves: 170 VGPRs per lane
 constexpr size_t kRowsW4Lds = 160 * 1024;           // x rows of a workgroup: all of a CU's LDS (no static arrays)
 constexpr int kRowsW4Pad = 8;                       // bf16 elements: (Ks + 8) / 8 is odd (Ks % 32 == 0)
-constexpr int kRowsW4Group = 512;                   // columns of a scale group: 16 blocks, four instructions
-typedef __bf16 bf16x8q __attribute__((ext_vector_type(8)));
+// (kRowsW4Group, the 512 columns of a scale group, and e2m1x8_to_bf16x8: kernels.h, shared with k_gemm_rows64_w4.hip)
 
 struct RowsW4Args {
     const uint8_t *q, *e;                           // [N, K/2] nibbles; the group-order scale stream, `es` bytes per row
@@ -52,16 +51,6 @@ struct RowsW4Args {
     void *out;                                      // EPI_F32: float [nks][T][N]; EPI_GATEUP: bf16 [T][N/2]
     int T, N, K, Ks, es;                            // Ks: columns per slice (K, or a multiple of 512)
 };
-
-// eight e2m1 (one dword, low nibble first) times `scale` as one bf16 MFMA operand, element i = nibble i
-__device__ inline bf16x8q e2m1x8_to_bf16x8(unsigned w, float scale) {
-    uint4v r;
-    r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-    r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-    r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-    r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-    return __builtin_bit_cast(bf16x8q, r);
-}
 
 template <int G, int EPI>
 __global__ __launch_bounds__(kRowsW4MaxThreads) void gemm_rows_w4_kernel(const RowsW4Args a) {

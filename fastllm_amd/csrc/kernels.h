@@ -175,6 +175,25 @@ int launch_gemm_rows_w4(Launcher &L, const uint8_t *q, const uint8_t *e, const v
                         int64_t K, int epi, const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
 int64_t rows_w4_scale_stride(int64_t K);               // bytes of one row in the group-order scale stream: ceil(K / 512) * 16
 int launch_mx4_group_scales(Launcher &L, const uint8_t *e_stream, int64_t N, int64_t K, uint8_t *eo);
+// the 17-64-row sibling (k_gemm_rows64_w4.hip; x through LDS in double-buffered 512-column blocks, 32 or 16 weight rows per wave): the
+// same product from the same operands, without bias, the same epilogues and slabs.  gemm_rows64_w4_plan: the K slices (multiples of
+// 512 columns), or 0: not served (T outside 17..64, K no multiple of 32, gate/up rows no multiple of 32); launch_gemm_rows64_w4
+// fails with FL_ERR_UNSUPPORTED exactly there.
+int gemm_rows64_w4_plan(int64_t T, int64_t N, int64_t K, int epi, int max_split);
+int launch_gemm_rows64_w4(Launcher &L, const uint8_t *q, const uint8_t *e, const void *x, void *y, int64_t T, int64_t N, int64_t K, int epi,
+                          const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
+// what both row kernels share: the columns of a scale group (16 blocks, four wave instructions) and the conversion -- eight e2m1 (one
+// dword, low nibble first) times `scale` as one bf16 MFMA operand, element i = nibble i
+constexpr int kRowsW4Group = 512;
+typedef __bf16 bf16x8q __attribute__((ext_vector_type(8)));
+__device__ inline bf16x8q e2m1x8_to_bf16x8(unsigned w, float scale) {
+    uint4v r;
+    r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
+    r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
+    r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
+    r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
+    return __builtin_bit_cast(bf16x8q, r);
+}
 
 // k_kvcopy.hip: a 2-D byte copy on the device, `rows` rows of `width` bytes (a multiple of 2) with a source and a destination pitch
 // (multiples of 16, >= width; 16-byte aligned bases).  launch_kv_copy moves two such jobs -- the K and the V prefix of a cache -- in

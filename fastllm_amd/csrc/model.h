@@ -271,7 +271,7 @@ struct Batch {
     bool dma = false;                            // B >= 3: projections on the LDS-DMA ring kernel (k_gemv_dma.hip)
     bool unfused = false;                        // large B: norm / GEMM / RoPE as separate launches around the short-prompt GEMM
     bool w8 = false;                             // B >= 3 on an FL_WEIGHTS_E4M3_ROW model: the prefill-shaped step reads the e4m3 bytes (fl_tune "batch_w8" when the batch was created)
-    bool w4 = false;                             // 3 <= B <= 16 on an FL_WEIGHTS_MXFP4 model: the prefill-shaped step reads the e2m1 nibbles (fl_tune "rows_w4" when the batch was created)
+    bool w4 = false;                             // 3 <= B <= 64 on an FL_WEIGHTS_MXFP4 model: the prefill-shaped step reads the e2m1 nibbles (fl_tune "rows_w4" when the batch was created)
     bool plain = false;                          // ... all caches in the plain layout and head_dim 64 / 128: the batch kernels' plain-layout forms (one RoPE and one attention launch per layer)
     bool per_seq = false;                        // fp32 models, caches without the MFMA attention layout: embedding / RoPE / attention as launches per sequence (the single-sequence kernels on row i), the projections still once for all B rows
     Scratch sc;                                  // ... with the prefill scratch layout at T = B
@@ -384,8 +384,9 @@ struct AllRows {
     // fl_tune "rows_w4", off by default) likewise; every other forward keeps the bf16 image
     bool verify = false;
 };
-// one projection of 2-16 rows from a model's byte weights, fmt = FL_WEIGHTS_E4M3_ROW (q e4m3, s the row scales: k_gemm_rows_w8.hip) or
-// FL_WEIGHTS_MXFP4 (q nibbles, g the group-order scales: k_gemm_rows_w4.hip).  rows_wq_plan: the K slices, 0: not served
+// one projection of 2-64 rows from a model's byte weights, fmt = FL_WEIGHTS_E4M3_ROW (q e4m3, s the row scales: k_gemm_rows_w8.hip, from
+// 17 rows k_gemm_rows64_w8.hip) or FL_WEIGHTS_MXFP4 (q nibbles, g the group-order scales: k_gemm_rows_w4.hip, from 17 rows
+// k_gemm_rows64_w4.hip).  rows_wq_plan: the K slices, 0: not served -- from 17 rows also where the wide kernel would slice K (MXFP4: from 33 rows)
 int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split);
 int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
                    int epi, const float *rs, int max_split = 1, int *n_split_out = nullptr);

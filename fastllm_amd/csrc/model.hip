@@ -574,11 +574,27 @@ static int verify_wq(const Model *m, const AllRows *rows, int64_t T) {
     return 0;
 }
 int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split) {
+    if (T > 16) {
+        // 17-64 rows (a decode batch), measured against the short-prompt GEMM on the image, Mistral-7B.  FP8 (profiles/r21/batch_w8.txt):
+        // the sliced QKV, o_proj and down_proj ran at 0.70-0.92x, the unsliced gate/up and lm_head at 1.09-1.51x: served only where the
+        // wide kernel's plan does not slice K.  MXFP4 (profiles/r24/batch_w4.txt): unsliced 1.93-1.98x at 17 and 32 rows, 1.02-1.27x at
+        // 64; sliced 1.03-1.17x at 17, 1.01-1.14x at 32, but 0.65-0.88x at 64 rows: a product that the plan slices is served up to two
+        // token tiles (32 rows) only
+        if (fmt == FL_WEIGHTS_MXFP4) {
+            const int nks = gemm_rows64_w4_plan(T, N, K, epi, max_split);
+            return nks == 1 || T <= 32 ? nks : 0;
+        }
+        return fmt == FL_WEIGHTS_E4M3_ROW && gemm_rows64_w8_plan(T, N, K, epi, max_split) == 1 ? 1 : 0;
+    }
     if (fmt == FL_WEIGHTS_MXFP4) return gemm_rows_w4_plan(T, N, K, epi, false, max_split);
     return fmt == FL_WEIGHTS_E4M3_ROW ? gemm_rows_w8_plan(T, N, K, epi, false, max_split) : 0;
 }
 int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
                    int epi, const float *rs, int max_split, int *n_split_out) {
+    if (T > 16) {
+        if (fmt == FL_WEIGHTS_MXFP4) return launch_gemm_rows64_w4(L, q, g, x, out, T, N, K, epi, rs, max_split, n_split_out);
+        return launch_gemm_rows64_w8(L, q, s, x, out, T, N, K, epi, rs, max_split, n_split_out);
+    }
     if (fmt == FL_WEIGHTS_MXFP4) return launch_gemm_rows_w4(L, q, g, x, nullptr, out, T, N, K, epi, rs, max_split, n_split_out);
     return launch_gemm_rows_w8(L, q, s, x, nullptr, out, T, N, K, epi, rs, max_split, n_split_out);
 }

@@ -162,7 +162,8 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
  * single-stream decode step (T = 1) reads the nibbles and scales (k_gemv_w4.hip); prompts, verify steps, fl_batch_* steps of every
  * size, embeddings and scoring run the bf16 kernels on the bf16 image of W' (fl_tune "verify_w8" / "batch_w8" do not apply), and
  * every path sees the same weights.  fl_tune "rows_w4" (FL_ROWS_W4; default 0) = 1: a single-stream verify step of 2-16 rows and a
- * batch of 3-16 members stream the nibbles too (k_gemm_rows_w4.hip; rows equal the image's up to fp32 summation order); it is read
+ * batch of 3-64 members stream the nibbles too (k_gemm_rows_w4.hip, from 17 members k_gemm_rows64_w4.hip: up to 32 members every projection, beyond that those it does not slice;
+ * rows equal the image's up to fp32 summation order); it is read
  * per verify step and, for a batch, by fl_batch_create -- the batch's step is a captured graph.  MEMORY: nibbles, the scales in the
  * order of either kernel and the image are kept, about 1.27x a bf16 model's weights.  REFUSED as above
  * (compute_dtype other than BF16, tp_size > 1, fused decode step off -> FL_ERR_UNSUPPORTED), and where hidden_size, or any
@@ -1000,6 +1001,15 @@ int fl_op_linear_w4(const void *x, const uint8_t *q, const uint8_t *e, const flo
  * multiple of 32, an epilogue other than 0 / 1, an odd gate/up row count, or x rows that do not fit LDS where slices are not allowed
  * (gate/up, bias). */
 int fl_op_linear_w4_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue, int32_t has_bias);
+
+/* The 17-64-row kernel under a decode batch of 17-64 members of an FL_WEIGHTS_MXFP4 model with fl_tune "rows_w4" on
+ * (k_gemm_rows64_w4.hip), alone: the product, operands (logical layouts), epilogues, slab summation and timing form of
+ * fl_op_linear_w4, without bias.  FL_ERR_UNSUPPORTED where fl_op_linear_w4_wide_plan is 0. */
+int fl_op_linear_w4_wide(const void *x, const uint8_t *q, const uint8_t *e, const float *row_scale, int64_t T, int64_t N, int64_t K,
+                         int32_t epilogue, int32_t iters, double *ms_out, float *y);
+/* The K slices (multiples of 512 columns) fl_op_linear_w4_wide runs such a product in (>= 1), or 0: not served -- T outside 17..64, K
+ * no multiple of 32, an epilogue other than 0 / 1, an odd gate/up row count. */
+int fl_op_linear_w4_wide_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue);
 
 /* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
 
