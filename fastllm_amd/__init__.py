@@ -5,7 +5,7 @@ include/fastllm_mi355x.h).  This Python package is the thin ctypes harness the t
 bench.py drive it with; it contains no arithmetic and no CPU fallback.
 """
 from .binding import (Batch, Cache, FastLLMError, Model, abi_version, comm_unique_id, device_count, lib, op_attention, op_linear, op_sample,  # noqa: F401
-                      tp_slice, tune, reload_env, library_loaded, op_quantize_rows, op_gemv_w8, op_quantize_mx4, op_gemv_w4, op_linear_w8, op_linear_w8_plan, op_linear_w4, op_linear_w4_plan, op_linear_w8_wide, op_linear_w8_wide_plan, op_linear_w4_wide, op_linear_w4_wide_plan, lookup_draft, op_verify_select, op_verify_sample, op_verify_sample_time, op_verify_packed, op_kv_copy,
+                      tp_slice, tune, reload_env, library_loaded, op_quantize_rows, op_gemv_w8, op_quantize_mx4, op_gemv_w4, op_linear_w8, op_linear_w8_plan, op_linear_w4, op_linear_w4_plan, op_linear_w8_wide, op_linear_w8_wide_plan, op_linear_w4_wide, op_linear_w4_wide_plan, op_linear_w4_tall, op_linear_w4_tall_plan, lookup_draft, op_verify_select, op_verify_sample, op_verify_sample_time, op_verify_packed, op_kv_copy,
                       Encoder, FlEncoderConfig, make_encoder_config, op_encoder_attention, op_attention_plain, op_attention_batch, op_attention_packed, op_logprobs, FlLogprobs, LOGPROBS_MAX_TOP,
                       op_score, op_score_time, FlScore, SCORE_NO_TARGET, ScoreResult, op_pool_rows, FlEmbed, make_embed, POOLING, ATTN_MASK,
                       op_logit_rules, FlLogitRules, make_logit_rules, Guide, op_guide_mask, FlGuideDesc, make_guide_desc, op_verify_adjust, op_verify_adjust_time, op_rules_count, op_verify_adjust_packed,

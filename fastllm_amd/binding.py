@@ -443,6 +443,8 @@ def lib():
         L.fl_op_linear_w8_wide_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
         L.fl_op_linear_w4_wide.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
         L.fl_op_linear_w4_wide_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+        L.fl_op_linear_w4_tall.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), vp]
+        L.fl_op_linear_w4_tall_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
         L.fl_cache_truncate.argtypes = [vp, sz]
         L.fl_forward_verify.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, C.POINTER(sz), vp]
         L.fl_lookup_draft.argtypes = [vp, sz, C.POINTER(FlLookup), sz, vp, C.POINTER(sz)]
@@ -2014,6 +2016,27 @@ def op_linear_w4_wide(x, q, e, row_scale=None, epilogue=0, iters=0):
 def op_linear_w4_wide_plan(T, N, K, epilogue=0):
     """K slices op_linear_w4_wide runs such a product in, or 0: not served (no device needed)."""
     return int(lib().fl_op_linear_w4_wide_plan(T, N, K, epilogue))
+
+
+def op_linear_w4_tall(x, q, e, row_scale=None, epilogue=0, iters=0):
+    """op_linear_w4 (no bias) through the 65-128-row MXFP4 weight stream, the kernel under a packed forward of 65-128 rows of an MXFP4
+    model with tune("rows_w4", 1)."""
+    x = np.ascontiguousarray(x, dtype=np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    e = np.ascontiguousarray(e, dtype=np.uint8)
+    T, K = x.shape
+    N = q.shape[0]
+    assert q.shape == (N, K // 2) and e.shape == (N, K // 32)
+    y = np.empty((T, N // 2 if epilogue == 1 else N), dtype=np.float32)
+    r = _f32(row_scale) if row_scale is not None else None
+    ms = C.c_double(0.0)
+    _check(lib().fl_op_linear_w4_tall(x.ctypes.data, q.ctypes.data, e.ctypes.data, _ptr(r), T, N, K, epilogue, iters, C.byref(ms), y.ctypes.data))
+    return (y, ms.value) if iters else y
+
+
+def op_linear_w4_tall_plan(T, N, K, epilogue=0):
+    """K slices op_linear_w4_tall runs such a product in, or 0: not served (no device needed)."""
+    return int(lib().fl_op_linear_w4_tall_plan(T, N, K, epilogue))
 
 
 def _f32(a):

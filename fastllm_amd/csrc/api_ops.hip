@@ -1643,6 +1643,73 @@ int fl_op_linear_w4_wide(const void *x, const uint8_t *q, const uint8_t *e, cons
     });
 }
 
+// ... and the 65-128-row kernel under a packed forward (k_gemm_rows128_w4.hip): the same hook
+int fl_op_linear_w4_tall_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue) {
+    int nks = 0;
+    const int rc = guarded([&]() -> int {
+        if (epilogue == EPI_GATEUP && N % 2 == 0) N = (N / 2 + 15) / 16 * 16 * 2;        // rows of the device matrix
+        nks = gemm_rows128_w4_plan(T, N, K, epilogue, op_linear_w8_split(T, epilogue, false));
+        return FL_OK;
+    });
+    return rc == FL_OK ? nks : 0;
+}
+
+int fl_op_linear_w4_tall(const void *x, const uint8_t *q, const uint8_t *e, const float *row_scale, int64_t T, int64_t N, int64_t K,
+                         int32_t epilogue, int32_t iters, double *ms_out, float *y) {
+    return guarded([&]() -> int {
+        if (!x || !q || !e || !y) FL_FAIL(FL_ERR_BAD_ARGUMENT, "null argument");
+        if (T <= 0 || N <= 0 || K <= 0 || N > (1 << 24)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "bad shape");
+        if (epilogue != EPI_F32 && epilogue != EPI_GATEUP) FL_FAIL(FL_ERR_BAD_ARGUMENT, "epilogue must be 0 or 1");
+        if (epilogue == EPI_GATEUP && (N % 2)) FL_FAIL(FL_ERR_BAD_ARGUMENT, "gate/up needs an even row count");
+        if (!fl_op_linear_w4_tall_plan(T, N, K, epilogue))
+            FL_FAIL(FL_ERR_UNSUPPORTED, "the tall MXFP4 row stream takes 65..128 rows and K a multiple of 32 (a lane loads one block of 32 weights)");
+        OpScope B;
+        FL_TRY(B.begin());
+        const int64_t I = N / 2, Ip = (I + 15) / 16 * 16;
+        const int64_t Nw = epilogue == EPI_GATEUP ? 2 * Ip : N;          // rows of the device matrix
+        const int64_t Ny = epilogue == EPI_GATEUP ? Ip : N;
+        const int max_split = op_linear_w8_split(T, epilogue, false);
+        // one working set: the nibbles, then (256-byte aligned) the scales in the kernel's group order
+        const size_t qbytes = ((size_t)Nw * (K / 2) + 255) & ~(size_t)255, gbytes = (size_t)Nw * rows_w4_scale_stride(K);
+        const size_t wbytes = qbytes + gbytes, sbytes = (size_t)Nw * mx4_scale_stride(K), ybytes = (size_t)T * Ny * (epilogue == EPI_GATEUP ? 2 : 4);
+        int nsplit = 1;
+        void *xd, *yd; uint8_t *wd, *sd, *qs, *es; float *rd = nullptr;
+        FL_TRY(B.upload(&xd, x, (size_t)T * K * 2));
+        FL_TRY(B.upload(&qs, q, (size_t)N * (K / 2)));
+        FL_TRY(B.upload(&es, e, (size_t)N * (K / 32)));
+        FL_TRY(B.alloc(&wd, wbytes));
+        FL_TRY(B.alloc(&sd, sbytes));                                    // the GEMV's scale stream of the device rows: what a model holds
+        FL_TRY(B.alloc(&yd, ybytes * max_split));
+        if (row_scale) FL_TRY(B.upload(&rd, row_scale, (size_t)T * 4));
+        FL_HIP(hipMemsetAsync(wd, 0, qbytes, B.s));                      // padding rows: zeros under the scale 2^0
+        FL_HIP(hipMemsetAsync(sd, 127, sbytes, B.s));
+        FL_TRY(launch_mx4_layout(B.L, qs, es, N, epilogue == EPI_GATEUP ? I : 0, K, wd, sd));
+        FL_TRY(launch_mx4_group_scales(B.L, sd, Nw, K, wd + qbytes));
+        std::vector<const uint8_t *> Q{wd};                              // the copies of the working set a timed run rotates over
+        auto make = [&](int) -> int {
+            uint8_t *p;
+            FL_TRY(B.alloc(&p, wbytes));
+            FL_HIP(hipMemcpyAsync(p, wd, wbytes, hipMemcpyDeviceToDevice, B.s));
+            Q.push_back(p);
+            return FL_OK;
+        };
+        auto run = [&](int c) -> int {
+            return launch_gemm_rows128_w4(B.L, Q[(size_t)c], Q[(size_t)c] + qbytes, xd, yd, T, Nw, K, epilogue, rd, max_split, &nsplit);
+        };
+        FL_TRY(op_run(B, wbytes, iters, ms_out, make, run));
+        if (epilogue == EPI_GATEUP) return op_download(y, yd, (size_t)T, (size_t)I, (size_t)Ip, FL_DTYPE_BF16);   // without the padding columns
+        FL_HIP(hipMemcpy(y, yd, ybytes, hipMemcpyDeviceToHost));
+        if (nsplit > 1) {                                   // sum the K slabs in slab order, like rmsnorm_add does
+            std::unique_ptr<float[]> tmp(new float[(size_t)T * Ny]);
+            for (int sl = 1; sl < nsplit; sl++) {
+                FL_HIP(hipMemcpy(tmp.get(), (char *)yd + (size_t)sl * ybytes, ybytes, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < (size_t)T * Ny; i++) y[i] += tmp[i];
+            }
+        }
+        return FL_OK;
+    });
+}
+
 int fl_op_kv_copy(const void *src, void *dst, int64_t rows, int64_t width_bytes, int64_t src_pitch, int64_t dst_pitch, int32_t iters,
                   double *ms_out) {
     return guarded([&]() -> int {

@@ -126,7 +126,7 @@ enum TuneKey {
     TK_GEMV_RESID,   // decode: o_proj / down_proj finish the residual add, the next norm's v * w and the chunk sums of squares in their epilogue, and the consumer stages the ready vector (k_gemv.hip EPI_RESID / PRO_XS), on every edge where gemv_resid_edge (gemv_geometry.h) says so; 0: the norm prologue everywhere; 2: as 1, and the launcher tags name the form (",resid" / ",xs"; by default a launch keeps the name it has always had)
     TK_VERIFY_W8,   // a single-stream verify step (2-16 rows) of an FL_WEIGHTS_E4M3_ROW model streams the e4m3 bytes through k_gemm_rows_w8.hip where gemm_rows_w8_plan serves the projection; 0: the bf16 image everywhere, exactly the launches there were before
     TK_BATCH_W8,   // a decode batch of 3-64 members on an FL_WEIGHTS_E4M3_ROW model takes the prefill-shaped step with its projections on the e4m3 bytes: k_gemm_rows_w8.hip up to 16 members, k_gemm_rows64_w8.hip from 17, each where its plan serves the projection; 0: the bf16 image, exactly the launches there were before.  Read when the batch is created (fl_batch_create): its step is a captured graph, a later fl_tune reaches new batches only
-    TK_ROWS_W4,   // an FL_WEIGHTS_MXFP4 model: a single-stream verify step of 2-16 rows and a decode batch of 3-64 members stream the e2m1 nibbles through k_gemm_rows_w4.hip (from 17 members k_gemm_rows64_w4.hip) where the kernel's plan serves the projection; 0 (default: the rows differ from the image's in fp32 summation order): the bf16 image, exactly the launches there were before.  Read per verify step, and for a batch when it is created (its step is a captured graph)
+    TK_ROWS_W4,   // an FL_WEIGHTS_MXFP4 model: a single-stream verify step of 2-16 rows and a decode batch of 3-64 members stream the e2m1 nibbles through k_gemm_rows_w4.hip (from 17 members k_gemm_rows64_w4.hip) where the kernel's plan serves the projection; 0 (default: the rows differ from the image's in fp32 summation order): the bf16 image, exactly the launches there were before.  Read per verify step, and for a batch when it is created (its step is a captured graph); read per call by the packed forwards (prefill_packed.hip), whose packs of 2-64 rows take the same kernels under the same plan (65-80 rows: k_gemm_rows128_w4.hip for the products it does not slice; beyond, rows_wq_plan keeps the image, where the kernel measured slower)
     TK_COUNT
 };
 int tune(TuneKey k);

@@ -182,7 +182,14 @@ int launch_mx4_group_scales(Launcher &L, const uint8_t *e_stream, int64_t N, int
 int gemm_rows64_w4_plan(int64_t T, int64_t N, int64_t K, int epi, int max_split);
 int launch_gemm_rows64_w4(Launcher &L, const uint8_t *q, const uint8_t *e, const void *x, void *y, int64_t T, int64_t N, int64_t K, int epi,
                           const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
-// what both row kernels share: the columns of a scale group (16 blocks, four wave instructions) and the conversion -- eight e2m1 (one
+// the 65-128-row sibling (k_gemm_rows128_w4.hip; x through LDS in double-buffered 128-column stages, a lane's two adjacent blocks per
+// weight step, 32 or 16 weight rows per wave): the same product from the same operands, without bias, the same epilogues and slabs.
+// gemm_rows128_w4_plan: the K slices (multiples of 512 columns), or 0: not served (T outside 65..128, K no multiple of 32, gate/up
+// rows no multiple of 32); launch_gemm_rows128_w4 fails with FL_ERR_UNSUPPORTED exactly there.
+int gemm_rows128_w4_plan(int64_t T, int64_t N, int64_t K, int epi, int max_split);
+int launch_gemm_rows128_w4(Launcher &L, const uint8_t *q, const uint8_t *e, const void *x, void *y, int64_t T, int64_t N, int64_t K, int epi,
+                           const float *row_scale, int max_split = 1, int *n_split_out = nullptr);
+// what the row kernels share: the columns of a scale group (16 blocks, four wave instructions) and the conversion -- eight e2m1 (one
 // dword, low nibble first) times `scale` as one bf16 MFMA operand, element i = nibble i
 constexpr int kRowsW4Group = 512;
 typedef __bf16 bf16x8q __attribute__((ext_vector_type(8)));

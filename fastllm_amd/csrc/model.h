@@ -383,10 +383,15 @@ struct AllRows {
     // "verify_w8") wherever gemm_rows_w8_plan serves the projection, on an FL_WEIGHTS_MXFP4 model the e2m1 nibbles (k_gemm_rows_w4.hip,
     // fl_tune "rows_w4", off by default) likewise; every other forward keeps the bf16 image
     bool verify = false;
+    // a packed forward: on an FL_WEIGHTS_MXFP4 model under fl_tune "rows_w4" a block streams the nibbles where rows_wq_plan serves
+    // it -- 2-64 rows under the row kernels' rules, 65-80 rows where K is not sliced (packed_wq)
+    bool packed = false;
 };
-// one projection of 2-64 rows from a model's byte weights, fmt = FL_WEIGHTS_E4M3_ROW (q e4m3, s the row scales: k_gemm_rows_w8.hip, from
+// one projection of 2-64 rows (MXFP4: 2-80) from a model's byte weights, fmt = FL_WEIGHTS_E4M3_ROW (q e4m3, s the row scales: k_gemm_rows_w8.hip, from
 // 17 rows k_gemm_rows64_w8.hip) or FL_WEIGHTS_MXFP4 (q nibbles, g the group-order scales: k_gemm_rows_w4.hip, from 17 rows
-// k_gemm_rows64_w4.hip).  rows_wq_plan: the K slices, 0: not served -- from 17 rows also where the wide kernel would slice K (MXFP4: from 33 rows)
+// k_gemm_rows64_w4.hip, from 65 rows k_gemm_rows128_w4.hip).  rows_wq_plan: the K slices, 0: not served -- from 17 rows also where the
+// wide kernel would slice K (MXFP4: from 33 rows), from 65 rows served only unsliced and up to 80 rows.  packed_wq: the format a packed forward of m streams now, or 0: the image
+int packed_wq(const Model *m);
 int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split);
 int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
                    int epi, const float *rs, int max_split = 1, int *n_split_out = nullptr);

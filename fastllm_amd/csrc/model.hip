@@ -573,7 +573,20 @@ static int verify_wq(const Model *m, const AllRows *rows, int64_t T) {
     if (m->decode_weights == FL_WEIGHTS_MXFP4) return tune(TK_ROWS_W4) != 0 ? FL_WEIGHTS_MXFP4 : 0;
     return 0;
 }
+// A packed forward (prefill_packed.hip) of an FL_WEIGHTS_MXFP4 model under fl_tune "rows_w4" streams the nibbles too, wherever
+// rows_wq_plan serves the row count (2-64 rows, and 65-80 unsliced); read per call: these forwards are eager
+int packed_wq(const Model *m) { return m->decode_weights == FL_WEIGHTS_MXFP4 && tune(TK_ROWS_W4) != 0 ? FL_WEIGHTS_MXFP4 : 0; }
 int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_split) {
+    if (T > 64) {
+        // 65-128 rows (a packed forward; k_gemm_rows128_w4.hip, MXFP4 only), measured against the short-prompt GEMM on the image,
+        // Mistral-7B at 65 / 80 / 96 / 128 rows (profiles/r25/packed_w4.txt, medians of 5 with min .. max).  Unsliced: gate/up 1.22x at
+        // 65 (40.0 us against 46.7 .. 53.0), 1.16x at 80 (42.7 .. 42.8 against 49.2 .. 51.2), 1.01x at 96 with overlapping ranges
+        // (49.8 .. 50.0 against 49.4 .. 52.7), 0.87x at 128; lm_head 1.34 / 1.28 / 1.16 / 0.98x.  Sliced: QKV 0.82 / 0.71 / 0.59x, o_proj 0.85 / 0.75 / 0.63x, down_proj 1.01 / 0.89 / 0.75x.  The kernel's
+        // time goes by token tiles (5 at 65-80 rows, 6 from 81), the image's hardly moves: an unsliced product is served up to five
+        // tiles, 80 rows; six tiles do not win beyond the spreads for gate/up, eight lose; a sliced product stays on the image
+        if (fmt != FL_WEIGHTS_MXFP4 || T > 80) return 0;
+        return gemm_rows128_w4_plan(T, N, K, epi, max_split) == 1 ? 1 : 0;
+    }
     if (T > 16) {
         // 17-64 rows (a decode batch), measured against the short-prompt GEMM on the image, Mistral-7B.  FP8 (profiles/r21/batch_w8.txt):
         // the sliced QKV, o_proj and down_proj ran at 0.70-0.92x, the unsliced gate/up and lm_head at 1.09-1.51x: served only where the
@@ -591,6 +604,7 @@ int rows_wq_plan(int fmt, int64_t T, int64_t N, int64_t K, int epi, int max_spli
 }
 int launch_rows_wq(Launcher &L, int fmt, const uint8_t *q, const float *s, const uint8_t *g, const void *x, void *out, int64_t T, int64_t N, int64_t K,
                    int epi, const float *rs, int max_split, int *n_split_out) {
+    if (T > 64 && fmt == FL_WEIGHTS_MXFP4) return launch_gemm_rows128_w4(L, q, g, x, out, T, N, K, epi, rs, max_split, n_split_out);
     if (T > 16) {
         if (fmt == FL_WEIGHTS_MXFP4) return launch_gemm_rows64_w4(L, q, g, x, out, T, N, K, epi, rs, max_split, n_split_out);
         return launch_gemm_rows64_w8(L, q, s, x, out, T, N, K, epi, rs, max_split, n_split_out);
@@ -607,7 +621,7 @@ int lm_head_rows(Model *m, Shard &sh, Launcher &L, Scratch &sc, int64_t T, const
         n = std::min<int64_t>(rows.R, T - r0);
         if (rows.no_one_row_tail && T - r0 - n == 1 && n > 2) n -= 1;
         const void *xb = (char *)sc.xn + (size_t)r0 * D.h * m->esize();
-        const int wq = verify_wq(m, &rows, n);
+        const int wq = rows.packed ? packed_wq(m) : verify_wq(m, &rows, n);
         if (rows_wq_plan(wq, n, sh.Vs, D.h, EPI_F32, 1))
             FL_TRY(launch_rows_wq(L, wq, sh.lm_head8, sh.lm_head_s, sh.lm_head_g, xb, rows.out, n, sh.Vs, D.h, EPI_F32, sc.inv_rms + r0));
         else

@@ -4,6 +4,8 @@
 // the same launches (and the same planner) as a single prompt; RoPE / KV append and attention go through k_prefill_packed.hip, which
 // finds every row's own cache in a device table; the final norm, lm_head and token selection run on the n last rows only.
 // Eager launches: no graph, no residual or RoPE epilogues in the projections.
+// An FL_WEIGHTS_MXFP4 model under fl_tune "rows_w4" reads its projections from the e2m1 nibbles where rows_wq_plan serves them: 2-64
+// rows (k_gemm_rows_w4.hip, k_gemm_rows64_w4.hip) under those kernels' rules, 65-80 rows unsliced (k_gemm_rows128_w4.hip).
 #include "model.h"
 #include "lookup.h"
 
@@ -291,13 +293,22 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
     const int max_split = T > 1 ? ksplit_cap(T) : 1;
     const int64_t slab = T * D.h, nq = (sh.Hs + 2 * sh.Hkvs) * D.d;
     int nslab = 1;
+    // one projection: on an FL_WEIGHTS_MXFP4 model under fl_tune "rows_w4" (read here, per call) from the nibbles wherever rows_wq_plan
+    // serves the row count and the shape (2-64 rows; 65-80 unsliced: model.hip, with the measurements behind its rules), otherwise -- and with the switch at 0
+    // always -- the launch on the bf16 image there has always been.  The plain forms are what a packed forward launches anyway
+    const int wq = packed_wq(m);
+    auto linear = [&](const void *W, const uint8_t *q8, const float *s8, const uint8_t *g8, const void *x, void *out, int64_t rows, int64_t N, int64_t K,
+                      int epi, const float *rs, int split, int *nsl) -> int {
+        if (rows_wq_plan(wq, rows, N, K, epi, split)) return launch_rows_wq(L, wq, q8, s8, g8, x, out, rows, N, K, epi, rs, split, nsl);
+        return launch_linear(L, dt, W, x, nullptr, out, rows, N, K, epi, rs, split, nsl);
+    };
     for (int64_t l = 0; l < D.L; l++) {
         LayerW &ly = sh.layers[l];
         const size_t kv_layer_off = (size_t)l * sh.Hkvs * D.d;
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, l == 0 ? nullptr : sc.delta, ly.ln1, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
         // QKV in K slabs (the bias, if any, moves into the RoPE launch, which sums the slabs anyway); no RoPE epilogue: it writes ONE cache
         int qkv_slabs = 1;
-        FL_TRY(launch_linear(L, dt, ly.wqkv, sc.xn, nullptr, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qkv_slabs));
+        FL_TRY(linear(ly.wqkv, ly.wqkv8, ly.sqkv, ly.gqkv, sc.xn, sc.qkv, T, nq, D.h, EPI_F32, sc.inv_rms, qkv_split(T), &qkv_slabs));
         FL_TRY(launch_rope_kv_packed(L, dt, sc.qkv, tb, sh.cos_tab, sh.sin_tab, D.max_pos, sc.q, kv_layer_off, T, sh.Hs, sh.Hkvs, D.d, qkv_slabs, ly.bqkv));
         if (any_mfma)
             FL_TRY(launch_attn_prefill_packed_mfma(L, sc.q, tb, ph.n_items, ph.TT, ph.ks, kv_layer_off, sc.ao, sh.Hs, sh.Hkvs, D.d, D.scale, D.window, attn_flops, mask));
@@ -324,10 +335,10 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         // (the copy of a one-row verify pack is not attended: it takes the row's attention output, and stays the row's exact copy in
         // every layer -- what it writes to the row's cache slot is what the row writes there)
         if (pad) FL_HIP(hipMemcpyAsync((char *)sc.ao + (size_t)(sh.Hs * D.d) * es, sc.ao, (size_t)(sh.Hs * D.d) * es, hipMemcpyDeviceToDevice, sh.stream));
-        FL_TRY(launch_linear(L, dt, ly.wo, sc.ao, nullptr, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
+        FL_TRY(linear(ly.wo, ly.wo8, ly.so, ly.go, sc.ao, sc.delta, T, D.h, sh.Hs * D.d, EPI_F32, nullptr, max_split, &nslab));
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, ly.ln2, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
-        FL_TRY(launch_linear(L, dt, ly.wgu, sc.xn, nullptr, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms));
-        FL_TRY(launch_linear(L, dt, ly.wd, sc.act, nullptr, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
+        FL_TRY(linear(ly.wgu, ly.wgu8, ly.sgu, ly.ggu, sc.xn, sc.act, T, 2 * sh.Ip, D.h, EPI_GATEUP, sc.inv_rms, 1, nullptr));
+        FL_TRY(linear(ly.wd, ly.wd8, ly.sd, ly.gd, sc.act, sc.delta, T, D.h, sh.Ip, EPI_F32, nullptr, max_split, &nslab));
     }
 
     const int nn = (int)n;
@@ -336,7 +347,9 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         // ---- every row: final norm (residual + delta slabs) at T = T_total, lm_head in blocks, one score_rows launch behind each
         FL_TRY(call.begin(tg.data()));
         FL_TRY(launch_rmsnorm_add(L, dt, sc.x_res, sc.delta, sh.norm, D.eps, sc.xn, sc.inv_rms, T, D.h, nslab, slab));
-        FL_TRY(lm_head_rows(m, sh, L, sc, T, call.sink(0)));
+        AllRows srows = call.sink(0);
+        srows.packed = true;
+        FL_TRY(lm_head_rows(m, sh, L, sc, T, srows));
         FL_TRY(call.fetch());
     } else if (emb) {
         // ---- every row: final norm at T = T_total, which leaves the fp32 residual stream and 1/rms of every row; the pool launch
@@ -396,6 +409,7 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
             return FL_OK;
         }};
         rows.no_one_row_tail = true;
+        rows.packed = true;
         FL_TRY(lm_head_rows(m, sh, L, sc, T, rows));
         // ... the members' error words into the same block: ids, accepted counts and error words come back in one copy
         FL_TRY(launch_packed_collect(L, tb, vout + kVerifyPackedAux, nn));
@@ -434,7 +448,7 @@ int packed_forward(Model *m, Cache *const *caches, size_t n, const uint32_t *ids
         FL_TRY(launch_gather_last_rows(L, sc.x_res, tb, ps.xl, nn, D.h, 1, 0, 0));
         FL_TRY(launch_gather_last_rows(L, sc.delta, tb, ps.dl, nn, D.h, nslab, slab, lslab));
         FL_TRY(launch_rmsnorm_add(L, dt, ps.xl, ps.dl, sh.norm, D.eps, ps.xnl, ps.inv_rms, nn, D.h, nslab, lslab));
-        FL_TRY(launch_linear(L, dt, sh.lm_head, ps.xnl, nullptr, ps.logits, nn, D.V, D.h, EPI_F32, ps.inv_rms));
+        FL_TRY(linear(sh.lm_head, sh.lm_head8, sh.lm_head_s, sh.lm_head_g, ps.xnl, ps.logits, nn, D.V, D.h, EPI_F32, ps.inv_rms, 1, nullptr));
         FL_TRY(launch_select_advance_batch(L, ps.logits, D.V, tb.seqs, nn, 0));
     }
 

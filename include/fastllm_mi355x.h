@@ -164,7 +164,12 @@ int fl_model_create(const fl_config *cfg, const fl_tensor *tensors, size_t n_ten
  * every path sees the same weights.  fl_tune "rows_w4" (FL_ROWS_W4; default 0) = 1: a single-stream verify step of 2-16 rows and a
  * batch of 3-64 members stream the nibbles too (k_gemm_rows_w4.hip, from 17 members k_gemm_rows64_w4.hip: up to 32 members every projection, beyond that those it does not slice;
  * rows equal the image's up to fp32 summation order); it is read
- * per verify step and, for a batch, by fl_batch_create -- the batch's step is a captured graph.  MEMORY: nibbles, the scales in the
+ * per verify step and, for a batch, by fl_batch_create -- the batch's step is a captured graph.  The packed forwards (fl_batch_prefill,
+ * fl_batch_verify / _lp, fl_batch_decode_lookup / _lp, fl_batch_embed, fl_batch_score) read it per call: packs of 2-64 rows take the
+ * same kernels under the same rules; packs of 65-80 rows take k_gemm_rows128_w4.hip (fl_op_linear_w4_tall) for
+ * the projections it does not slice (1.23-1.34x there; sliced products and 81-128 rows measured 0.59-1.15x, not clear of the spreads,
+ * and stay on the image); everything from 81 rows, lm_head blocks included, stays on the image too.  A member's rows depend on the pack's
+ * row count where the kernel or the K split changes (17, 33, 65 and 81 rows): equal up to fp32 summation order across, bit for bit within.  MEMORY: nibbles, the scales in the
  * order of either kernel and the image are kept, about 1.27x a bf16 model's weights.  REFUSED as above
  * (compute_dtype other than BF16, tp_size > 1, fused decode step off -> FL_ERR_UNSUPPORTED), and where hidden_size, or any
  * projection's K (heads x padded head_dim, intermediate_size padded to 16), is not a multiple of 32 -> FL_ERR_UNSUPPORTED naming it. */
@@ -1010,6 +1015,14 @@ int fl_op_linear_w4_wide(const void *x, const uint8_t *q, const uint8_t *e, cons
 /* The K slices (multiples of 512 columns) fl_op_linear_w4_wide runs such a product in (>= 1), or 0: not served -- T outside 17..64, K
  * no multiple of 32, an epilogue other than 0 / 1, an odd gate/up row count. */
 int fl_op_linear_w4_wide_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue);
+/* The 65-128-row kernel under a packed forward of 65-128 rows of an FL_WEIGHTS_MXFP4 model with fl_tune "rows_w4" on
+ * (k_gemm_rows128_w4.hip), alone: the product, operands (logical layouts), epilogues, slab summation and timing form of
+ * fl_op_linear_w4_wide.  FL_ERR_UNSUPPORTED where fl_op_linear_w4_tall_plan is 0. */
+int fl_op_linear_w4_tall(const void *x, const uint8_t *q, const uint8_t *e, const float *row_scale, int64_t T, int64_t N, int64_t K,
+                         int32_t epilogue, int32_t iters, double *ms_out, float *y);
+/* The K slices (multiples of 512 columns) fl_op_linear_w4_tall runs such a product in (>= 1), or 0: not served -- T outside 65..128, K
+ * no multiple of 32, an epilogue other than 0 / 1, an odd gate/up row count. */
+int fl_op_linear_w4_tall_plan(int64_t T, int64_t N, int64_t K, int32_t epilogue);
 
 /* ---- residual add -> RMSNorm -> projection in each of its fused forms, on host buffers (unit tests) ----------------------------- */
 

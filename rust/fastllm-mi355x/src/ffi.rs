@@ -1315,6 +1315,20 @@ extern "C" {
         y: *mut f32,
     ) -> c_int;
     pub fn fl_op_linear_w4_wide_plan(t: i64, n: i64, k: i64, epilogue: i32) -> c_int;
+    pub fn fl_op_linear_w4_tall(
+        x: *const c_void,
+        q: *const u8,
+        e: *const u8,
+        row_scale: *const f32,
+        t: i64,
+        n: i64,
+        k: i64,
+        epilogue: i32,
+        iters: i32,
+        ms_out: *mut f64,
+        y: *mut f32,
+    ) -> c_int;
+    pub fn fl_op_linear_w4_tall_plan(t: i64, n: i64, k: i64, epilogue: i32) -> c_int;
     pub fn fl_op_rmsnorm_add(
         x_res: *mut f32,
         delta: *const f32,
